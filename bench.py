@@ -16,9 +16,13 @@ ranks split into B/N whole sequences each, dealt round-robin; `--s
 32x512 shard instead.  Gradients, loss sums and the valid-frame count are all-reduced over RCCL by the engine's
 communicator (gt_comm_*), overlapped with the backward pass.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel = the f32
-MFMA GEMM family, per-launch HIP-event timing on the launch stream) and `cpu_baseline` (the CPU
-oracle -- a torch-CPU restatement of the reference step -- timed on this host's cores).
+Prints ONE JSON line (rank 0) with the driver's contract (metric / value / unit / higher_is_better / dtype /
+ms_per_step ...).  A plain run does only what that headline needs: set-up, clock spin-up, W warm-up steps, the K timed
+steps, the line.  `--full` adds everything else behind (or, for the sampled kernel timing, inside) the timed region:
+`roofline` (dominant kernel = the f32 MFMA GEMM family, per-launch HIP-event timing on the launch stream), the companion
+measurements (other x layout, single-GPU scaling proxy), `other_configs` (BASELINE.json configs[2..4]) and `cpu_baseline`
+(the CPU oracle -- a torch-CPU restatement of the reference step -- timed on this host's cores); the `--no-*` switches
+below leave out single parts of it.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -228,11 +232,35 @@ def comm_schedule(rec, steps, traced_ms, args):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> float32 / float64 numpy array) as <path>/<name>.npy.  When they exceed the budget together,
+    every array above an equal share of it is replaced by a fixed sample of its flattened elements (seeded: the same positions in
+    every run with the same arguments), so that two builds stay comparable element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if over and a.nbytes > share:
+            flat = a.reshape(-1)
+            a = flat[np.sort(np.random.default_rng(0).choice(flat.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and per-kernel table (sampled HIP events in the timed region), the companion "
+                         "measurements, other_configs and cpu_baseline (each can be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the step's scalars, the generator's outputs, "
+                         "the updated parameters and optimizer state of G and D) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -268,6 +296,8 @@ def main():
     ap.add_argument("--dp-python", action="store_true", help="data parallelism orchestrated from Python (torch.distributed "
                     "all-reduce between the split-phase calls) instead of the engine's own RCCL communicator")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.force_dp:      # a one-rank communicator would otherwise take the plain path (a sum over one rank is the identity)
         os.environ["GT_COMM_FORCE_COLLECTIVES"] = "1"
@@ -361,6 +391,7 @@ def main():
     cpu_lengths = [Tn] * B
     y_static = get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
     mask = sequence_mask(lengths).unsqueeze(-1)
+    gen_out = {}          # the generator's outputs of the latest step (--dump-outputs)
 
     if (world > 1 or args.force_dp) and args.dp_python:
         backend = HipStepBackend(hp, mg, md, og, od)
@@ -407,6 +438,7 @@ def main():
             og.zero_grad()
             od.zero_grad()
             y_hat, y_hat_static = T.apply_generator(mg, x, R, cpu_lengths)
+            gen_out["y_hat"], gen_out["y_hat_static"] = y_hat, y_hat_static     # (the engine holds them until the next step anyway)
             d = T.update_discriminator(md, od, x, y_static, y_hat_static, cpu_lengths, mask, "train")
             g = T.update_generator(mg, md, og, x, y, y_hat, y_static, y_hat_static, 1.0, cpu_lengths, mask,
                                    "train", mse_w=0.0, mge_w=1.0)
@@ -439,7 +471,7 @@ def main():
     spin_after_first = args.spinup_order == "after-first" and args.warmup >= 1
     if args.spinup_ms > 0 and not spin_after_first:
         spin_up()
-    profile = not args.no_roofline
+    profile = args.full and not args.no_roofline
     pre_stats = None
     for w in range(args.warmup):
         # the last warm-up step runs with EVERY product launch instrumented: the per-kernel table of the line (`variants`, the
@@ -496,6 +528,19 @@ def main():
         t = torch.tensor([elapsed], device=boot_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # taken before any --full measurement runs more steps on the same models
+        import numpy as np
+        arrays = {"d_scalars": np.array([float(v) for v in last[0]], dtype=np.float64),
+                  "g_scalars": np.array([float(v) for v in last[1]], dtype=np.float64)}
+        for k, v in gen_out.items():
+            arrays[k] = v.detach().float().cpu().numpy()
+        for tag, m, o in (("g", mg, og), ("d", md, od)):
+            arrays[tag + "_params"] = m.flat_params().detach().cpu().numpy()
+            st = o.state_dict()["state"]
+            for key in o.STATE_KEYS:
+                arrays["%s_opt_%s" % (tag, key)] = torch.cat([st[i][key].reshape(-1) for i in sorted(st)]).cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
 
     roofline = None
     if profile:
@@ -548,7 +593,7 @@ def main():
         return 1e3 * (time.perf_counter() - t1) / n
 
     companion = {}
-    if world == 1 and not args.force_dp and not args.no_roofline and not args.no_companion:
+    if args.full and world == 1 and not args.force_dp and not args.no_roofline and not args.no_companion:
         # (a) the other x layout: dense 425-float rows when the headline ran on the pitched rows train_loop stages (or vice versa)
         x_other = x.contiguous() if not args.dense_x else None
         if x_other is None:
@@ -637,7 +682,7 @@ def main():
             except Exception as e:      # noqa: BLE001
                 out["config"]["rccl_ranks"] = "unavailable: %s" % e
         out.update(companion)
-        if world == 1 and not args.no_other_configs and not args.force_dp:
+        if args.full and world == 1 and not args.no_other_configs and not args.force_dp:
             # the other BASELINE.json configurations, a few steps each, BEHIND the headline's timed region
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_configs
@@ -649,7 +694,7 @@ def main():
                     out["other_configs"][name] = bench_configs.run_config(name)
                 except Exception as e:      # noqa: BLE001 -- a failing side measurement must not lose the headline line
                     out["other_configs"][name] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(Bglobal, Tn)
         print(json.dumps(out), flush=True)
     if world > 1 or args.force_dp:

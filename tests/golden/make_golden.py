@@ -274,8 +274,58 @@ def run_inference():
     print("inference -> %s: %s" % (os.path.relpath(path, ROOT), {k: v.shape for k, v in out.items()}))
 
 
+def _plain(v):
+    """JSON form of an hparams value that keeps what `==` tells apart: tuples are tagged, arrays become lists."""
+    if isinstance(v, tuple):
+        return {"tuple": [_plain(u) for u in v]}
+    if isinstance(v, list):
+        return [_plain(u) for u in v]
+    if isinstance(v, dict):
+        return {k: _plain(u) for k, u in v.items()}
+    if isinstance(v, np.ndarray):
+        return {"array": v.tolist()}
+    return v
+
+
+def run_reference_hparams():
+    """The reference's three hparams sets (hparams.py:16-258) as recorded values: reference_hparams.json."""
+    import json
+    _, hparams, _ = ref_loader.load_reference()
+    out = {}
+    for name in ("vc", "tts_duration", "tts_acoustic"):
+        vals = dict(getattr(hparams, name).values())
+        # an absolute path into the reference's checkout: only its file name is compared
+        if "question_path" in vals:
+            vals["question_path"] = os.path.basename(vals["question_path"])
+        out[name] = _plain(vals)
+    path = os.path.join(HERE, "reference_hparams.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("hparams -> %s" % os.path.relpath(path, ROOT))
+
+
+def run_reference_mlp():
+    """An eval-mode forward of the reference's gantts.models.MLP on seeded weights and input, and its state_dict key order:
+    reference_mlp_eval.npz (the spec and weight seed are the ones tests/test_oracle.py builds the oracle network with)."""
+    _, _, gantts = ref_loader.load_reference()
+    spec = dict(kind="MLP", in_dim=20, out_dim=7, num_hidden=2, hidden_dim=16, dropout=0.5, last_sigmoid=True)
+    ref = gantts.models.MLP(**{k: v for k, v in spec.items() if k != "kind"}).eval()
+    ref.load_state_dict({k: torch.from_numpy(v) for k, v in C.make_weights(spec, 3).items()})
+    x = torch.rand(2, 9, 20, generator=torch.Generator().manual_seed(0))
+    with torch.no_grad():
+        y = ref(x)
+    path = os.path.join(HERE, "reference_mlp_eval.npz")
+    np.savez_compressed(path, x=x.numpy(), y=y.numpy(), names=np.array(list(ref.state_dict().keys())))
+    print("reference MLP -> %s" % os.path.relpath(path, ROOT))
+
+
 def main():
     only = sys.argv[1:]
+    if not only or "hparams" in only:
+        run_reference_hparams()
+    if not only or "reference_mlp" in only:
+        run_reference_mlp()
     if not only or "inference" in only:
         run_inference()
     for name, case in C.TRAIN_LOOP_CASES.items():

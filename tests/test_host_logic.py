@@ -28,15 +28,28 @@ def test_hparams_sets_and_parse():
     assert H.tts_acoustic == H.tts_acoustic and H.tts_acoustic != H.vc     # identity comparisons (train.py:447)
 
 
+def _recorded(v):
+    """tests/golden/reference_hparams.json back to hparams values (tuples and arrays are tagged there: make_golden.py _plain)."""
+    if isinstance(v, list):
+        return [_recorded(u) for u in v]
+    if isinstance(v, dict):
+        if set(v) == {"tuple"}:
+            return tuple(_recorded(u) for u in v["tuple"])
+        if set(v) == {"array"}:
+            return np.array(v["array"])
+        return {k: _recorded(u) for k, u in v.items()}
+    return v
+
+
 def test_reference_hparams_values_match_when_reference_present():
+    """The three hparams sets against the reference's own values, as tests/golden/make_golden.py recorded them from its hparams.py."""
+    import json
     import os
-    if not os.path.isfile("/root/reference/hparams.py"):
-        pytest.skip("reference tree absent")
-    import ref_loader
-    _, ref, _ = ref_loader.load_reference()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_hparams.json")) as f:
+        ref = json.load(f)
     from gantts_amd import hparams as H
     for name in ("vc", "tts_duration", "tts_acoustic"):
-        a, b = getattr(H, name).values(), getattr(ref, name).values()
+        a, b = getattr(H, name).values(), _recorded(ref[name])
         assert set(a) == set(b), name
         for k in a:
             if k == "windows":
@@ -178,6 +191,31 @@ def _load_bench():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def test_bench_dump_outputs_stays_within_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: arrays under the budget are written whole; above it, every array larger than an equal share becomes a
+    sample of its elements taken at the same positions in every run, and the files together stay within the budget."""
+    import os
+    bench = _load_bench()
+    small = {"s": np.arange(5, dtype=np.float64), "p": np.linspace(0, 1, 1000, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    for k, v in small.items():
+        got = np.load(str(tmp_path / "a" / (k + ".npy")))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    budget = bench.DUMP_BUDGET_BYTES
+    big = {"s": np.arange(9, dtype=np.float64), "y": np.arange(budget // 4 + 7, dtype=np.float32),
+           "w": np.arange(budget // 16, dtype=np.float32)}
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    total = sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b")))
+    assert total <= budget + 3 * 4096 and budget + 4096 < 64 * 2 ** 20
+    assert np.array_equal(np.load(str(tmp_path / "b" / "s.npy")), big["s"])
+    y = np.load(str(tmp_path / "b" / "y.npy"))
+    assert y.dtype == np.float32 and y.size == budget // 3 // 4
+    assert np.all(np.diff(y) > 0) and np.all(np.isin(y, big["y"]))       # distinct elements, in their original order
+    assert np.array_equal(y, np.load(str(tmp_path / "c" / "y.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "b" / "w.npy")), big["w"])     # within its share: whole
 
 
 def test_bench_condenses_a_schedule_trace_into_exposed_and_hidden_time():

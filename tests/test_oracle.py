@@ -117,20 +117,18 @@ def test_masked_mse_divides_by_valid_frames():
     assert float(O.masked_mse(a, b, m)) == pytest.approx(5.0)  # 4 valid frames * 5 dims / 4
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/train.py"), reason="reference tree absent")
 def test_oracle_live_against_reference_models():
-    import ref_loader
-    train, hparams, gantts = ref_loader.load_reference()
+    """Eval-mode forward and state_dict key order of the oracle MLP against the reference's gantts.models.MLP on the same weights,
+    as tests/golden/make_golden.py recorded them (reference_mlp_eval.npz)."""
+    gold = np.load(os.path.join(GOLDEN, "reference_mlp_eval.npz"))
     spec = dict(kind="MLP", in_dim=20, out_dim=7, num_hidden=2, hidden_dim=16, dropout=0.5, last_sigmoid=True)
-    ref = gantts.models.MLP(**{k: v for k, v in spec.items() if k != "kind"}).eval()
     sd = C.make_weights(spec, 3)
-    ref.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     mine = O.OracleMLP(**{k: v for k, v in spec.items() if k != "kind"})
     mine.load_state_dict(sd)
     mine.training = False
-    x = torch.rand(2, 9, 20)
-    assert torch.allclose(ref(x), mine(x), atol=1e-7)
-    assert list(ref.state_dict().keys()) == mine.names
+    x = torch.from_numpy(gold["x"])
+    assert torch.allclose(torch.from_numpy(gold["y"]), mine(x), atol=1e-7)
+    assert [str(n) for n in gold["names"]] == mine.names
 
 
 def test_sru_restatement_gradients_by_finite_differences():

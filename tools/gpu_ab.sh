@@ -3,7 +3,7 @@
 O=gpurun_out/ab; mkdir -p $O
 VAR=$1; shift
 for v in "$@" "$@"; do
-  env $VAR=$v timeout 200 python bench.py --steps 50 --warmup 10 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
+  env $VAR=$v timeout 200 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
   python - <<PY
 import json
 d=[json.loads(l) for l in open("$O/bench_$v.json") if l.startswith("{")][-1]
