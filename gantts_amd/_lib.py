@@ -24,6 +24,7 @@ OPT_LAUNCH_RIDERS, OPT_COMM_CLOSE_INLINE, OPT_POLL_RESULTS = 14, 15, 16
 OPT_COMM_TV_IN_SUMS, OPT_COMM_IPC, OPT_FUSED_DSTACK = 17, 18, 19
 IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
+LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts
 ARCH_MLP, ARCH_IN2OUT, ARCH_LSTM, ARCH_SRU, ARCH_IN2OUT_RNN = 0, 1, 2, 3, 4
 OPT_ADAGRAD, OPT_ADAM = 0, 1
 MAX_STREAMS = 8
@@ -100,6 +101,7 @@ SIGNATURES = {
     "gt_set_x_pitch": (_I, [_P, _I, _I]),
     "gt_set_tuning": (_I, [C.c_char_p, _I]),
     "gt_check_faults": (_I, [_P, _P]),
+    "gt_lstm_path_counts": (_I, [_P, C.POINTER(_L), _I]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -397,6 +397,8 @@ GtTuning& gt_tuning() {
     v.mlpg_fpl = geti("GT_MLPG_FPL", v.mlpg_fpl); v.mlpg_tt = geti("GT_MLPG_TT", v.mlpg_tt); v.sru_lw = geti("GT_SRU_LW", v.sru_lw); v.sru_cs_waves = geti("GT_SRU_CS_WAVES", v.sru_cs_waves); v.leak_rider = geti("GT_LEAK_RIDER", v.leak_rider);
     v.head_vec = geti("GT_HEAD_VEC", v.head_vec);
     v.mlpg_small16 = geti("GT_MLPG_SMALL16", v.mlpg_small16);
+    v.lstm_bt = geti("GT_LSTM_BT", v.lstm_bt);
+    if (v.lstm_bt != 8 && v.lstm_bt != 16) v.lstm_bt = 0;
     return v;
   }();
   return t;
@@ -408,6 +410,11 @@ extern "C" int gt_set_tuning(const char* name, int value) {
       {"gemm_pair", &t.gemm_pair}, {"pair_order", &t.pair_order}, {"gemm_tiles_big", &t.gemm_tiles_big}, {"gemm_unaligned", &t.gemm_unaligned},
       {"tn_wgs", &t.tn_wgs}, {"tn_split_wgs", &t.tn_split_wgs}, {"split_fused", &t.split_fused}, {"b16_tiles", &t.b16_tiles},
       {"b16_wg_tile", &t.b16_wg_tile}, {"b16_dma", &t.b16_dma}, {"mlpg_fpl", &t.mlpg_fpl}, {"mlpg_tt", &t.mlpg_tt}, {"sru_lw", &t.sru_lw}, {"sru_cs_waves", &t.sru_cs_waves}, {"leak_rider", &t.leak_rider}, {"head_vec", &t.head_vec}, {"mlpg_small16", &t.mlpg_small16}};
+  if (!strcmp(name, "lstm_bt")) {
+    if (value != 0 && value != 8 && value != 16) return fail(GT_ERR_INVALID, "lstm_bt must be 0 (by shape), 8 or 16, not %d", value);
+    t.lstm_bt = value;
+    return GT_OK;
+  }
   for (auto& e : tab) if (!strcmp(e.n, name)) { *e.p = value; return GT_OK; }
   return fail(GT_ERR_INVALID, "unknown tuning knob '%s'", name);
 }
@@ -569,6 +576,12 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   e->g_pass_valid = false; e->leak_pending = false; e->fake_cat_valid = false; e->adv2_fake_ok = false; e->cxd_src = nullptr;
   e->d_begin_done = e->g_begin_done = false; e->early_done = false;
+  return GT_OK;
+}
+extern "C" int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset) {
+  if (!e) return fail(GT_ERR_INVALID, "null engine");
+  if (counts) memcpy(counts, e->lstm_paths, sizeof(e->lstm_paths));
+  if (reset) memset(e->lstm_paths, 0, sizeof(e->lstm_paths));
   return GT_OK;
 }
 extern "C" int gt_check_faults(gt_engine* e, void* stream) {

@@ -25,9 +25,12 @@ int lstm_check_lengths(gt_engine* e, int B, int T) {
   return GT_OK;
 }
 
+enum { GT_LSTM_PATH_STEPS = 32, GT_LSTM_PATH_DECLINED = 33 };    // gt_lstm_path_counts: per-step kernels / no persistent grid fitted
+
 static int lstm_launch_steps(gt_engine* e, const Net& G, const LstmBufs& W, int layer, int B, int T, bool backward, const float* dout, hipStream_t s) {
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1;
   const int Bpad = cdiv(B, 32) * 32;
+  e->lstm_paths[GT_LSTM_PATH_STEPS]++;
   const size_t st = (size_t)dirs * Bpad * H;              // floats per state array
   CHK(e->l_state.ensure(5 * st * sizeof(float)));          // h0,h1,c0,c1 (ping-pong) + dc
   float* base = e->l_state.as<float>();
@@ -122,8 +125,11 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, const LstmBufs& W, bool b
   int nxcd = 1, cpx = 1;
   CHK(seq_xcds(&nxcd, &cpx));
   // batch tile: 16 sequences per group (full MFMA rows) once that already gives every XCD a group; else 8, which
-  // halves the exchange volume of a group and spreads the recurrences over more XCDs (their L2s bound the exchange)
-  const int bt = dirs * cdiv(B, 16) >= nxcd ? 16 : 8;
+  // halves the exchange volume of a group and spreads the recurrences over more XCDs (their L2s bound the exchange).
+  // gt_set_tuning("lstm_bt") forces one.
+  const int bt = gt_tuning().lstm_bt ? gt_tuning().lstm_bt : dirs * cdiv(B, 16) >= nxcd ? 16 : 8;
+  // gt_lstm_path_counts: slot of the instantiation that runs (the forward's UPC bit is added below)
+  const int slot = 16 * (backward ? 1 : 0) + 8 * (HP == 512 ? 1 : 0) + 2 * (bt == 16 ? 1 : 0) + (bf16 ? 1 : 0);
   LstmSeqArgs a;
   memset(&a, 0, sizeof(a));
   a.B = B; a.T = T; a.H = H; a.dirs = dirs; a.nbt = cdiv(B, bt);
@@ -146,6 +152,7 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, const LstmBufs& W, bool b
   if (backward) {
     a.ncu = cdiv(H, 16);
     CHK(HP == 256 ? launch_bwd_seq<256>(a, bt, bf16, s, launched) : launch_bwd_seq<512>(a, bt, bf16, s, launched));
+    e->lstm_paths[*launched ? slot : GT_LSTM_PATH_DECLINED]++;
     if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     return GT_OK;
   }
@@ -156,7 +163,9 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, const LstmBufs& W, bool b
     a.ncu = cdiv(H, upc);
     if (upc == 8) CHK(HP == 256 ? (launch_fwd_seq<256, 8>(a, bt, bf16, s, launched)) : (launch_fwd_seq<512, 8>(a, bt, bf16, s, launched)));
     else          CHK(HP == 256 ? (launch_fwd_seq<256, 16>(a, bt, bf16, s, launched)) : (launch_fwd_seq<512, 16>(a, bt, bf16, s, launched)));
+    if (*launched) e->lstm_paths[slot + (upc == 16 ? 4 : 0)]++;
   }
+  if (!*launched) e->lstm_paths[GT_LSTM_PATH_DECLINED]++;
   if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   return GT_OK;
 }

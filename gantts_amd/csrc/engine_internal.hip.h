@@ -88,6 +88,7 @@ struct GtTuning {
   int leak_rider = 1;         // GT_LEAK_RIDER     D step: the kept dloss_d / dy_hat_static product rides in the split first layer's weight-gradient launch
   int sru_cs_waves = 0;       // GT_SRU_CS_WAVES   waves per 64 columns of the cooperative SRU scans: 0 = by shape (8 where B x ncols / 64 <= CUs, else 4), 4, 8
   int sru_lw = 2;             // GT_SRU_LW         2: cooperative block scans (sru_cs_kernels.hip.h); 1: loader-wave scans; 0: one-wave kernels (1 == 0 bit for bit)
+  int lstm_bt = 0;            // GT_LSTM_BT        sequences per batch tile of the persistent LSTM kernels: 0 = by shape, 8, 16 (still subject to co-residency)
 };
 GtTuning& gt_tuning();
 
@@ -313,6 +314,7 @@ struct gt_engine {
   bool lstm_persistent = getenv("GT_LSTM_STEPS") == nullptr;   // GT_OPT_LSTM_PERSISTENT (the environment only provides the default at creation)
   int lstm_fwd_upc = 0;                            // 0 = automatic
   bool lstm_xcd_local = getenv("GT_LSTM_NO_XCD_LOCAL") == nullptr;   // GT_OPT_LSTM_XCD_LOCAL
+  int64_t lstm_paths[GT_LSTM_PATH_SLOTS] = {};      // recurrence layer-passes by kernel instantiation (gt_lstm_path_counts), counted on the host
   bool matmul_bf16 = false;                                          // GT_OPT_MATMUL_BF16
   // sequence lengths travel on the step stream through a small ring (pinned host slot -> device slot): the kernels of
   // the previous step, still queued when the next batch's lengths arrive, keep reading THEIR slot

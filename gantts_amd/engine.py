@@ -220,6 +220,15 @@ class StepEngine(object):
         """Synchronises the current stream and raises if a persistent kernel gave up waiting for a peer."""
         check(lib.gt_check_faults(self._h, L.current_stream()))
 
+    def lstm_path_counts(self, reset=False):
+        """Recurrence layer-passes run so far, by kernel instantiation (gt_lstm_path_counts): a list of L.LSTM_PATH_SLOTS
+        counts, slot 16 * backward + 8 * (HP == 512) + 4 * (UPC == 16) + 2 * (BT == 16) + bf16 for the persistent kernels,
+        L.LSTM_PATH_STEPS for the per-step kernels, L.LSTM_PATH_DECLINED for passes whose persistent grid did not fit.
+        Host-side counts of issued launches: no synchronisation.  ``reset`` zeroes them after the read."""
+        out = (C.c_int64 * L.LSTM_PATH_SLOTS)()
+        check(lib.gt_lstm_path_counts(self._h, out, 1 if reset else 0))
+        return list(out)
+
     def clear_faults(self):
         """Re-arms the engine after a reported fault (gt_clear_faults): the faulted step's optimizer updates were skipped
         on the device, the step counters are put back, the next call must be apply_generator."""

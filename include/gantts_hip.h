@@ -246,8 +246,9 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
 int gt_set_option(gt_engine* e, int option, int value);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,
- * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_lw, head_vec, mlpg_small16; the environment variables GT_<NAME>
- * provide the initial values. */
+ * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_lw, head_vec, mlpg_small16, lstm_bt; the environment variables GT_<NAME>
+ * provide the initial values.  lstm_bt: sequences per batch tile of the persistent LSTM kernels, 0 (by shape), 8 or 16; any other
+ * value is refused.  A forced tile still has to pass the co-residency check of the launch (else the per-step kernels run). */
 int gt_set_tuning(const char* name, int value);
 /* Row pitch (in floats) of the input tensors `x` of the step functions, like the `lda` of a BLAS call: ld_generator_input for the
  * x of gt_apply_generator (train.py:542: cat(x, z) or x), ld_condition for the conditioning x of gt_update_discriminator /
@@ -261,6 +262,16 @@ int gt_set_x_pitch(gt_engine* e, int ld_generator_input, int ld_condition);
  * word instead of hanging.  The step functions report a fault they have seen (GT_ERR_HIP) at their next entry;
  * this call synchronises `stream` and reports the current state. */
 int gt_check_faults(gt_engine* e, void* stream);
+/* Recurrence layer-passes of this engine (both roles) by the kernels that ran them, counted on the host when the launches are
+ * issued (no device work, no synchronisation).  One layer's forward, or its backward, is one pass (all directions and batch
+ * tiles in one launch).  Slot 16 * backward + 8 * (HP == 512) + 4 * (UPC == 16) + 2 * (BT == 16) + bf16 counts the persistent
+ * kernel of that instantiation (HP: hidden units padded to 256 or 512; UPC: hidden units per workgroup of the forward, 8 or 16 --
+ * always 0 in the bit for a backward; BT: sequences per batch tile; bf16: recurrent products in bf16).  Slot 32 counts passes run
+ * on the per-step kernels; slot 33 those of them where the persistent path applied (GT_OPT_LSTM_PERSISTENT, H <= 512, T >= 2)
+ * but no persistent grid was co-resident.  Copies the GT_LSTM_PATH_SLOTS counts to `counts` (may be null); reset != 0 then
+ * zeroes them. */
+#define GT_LSTM_PATH_SLOTS 34
+int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset);
 /* A raised fault word makes every optimizer launch behind it a no-op (parameters, gradients and optimizer state of the
  * faulted step stay as they were; optimizer.step() of train.py:276,318 is simply not taken).  This call synchronises,
  * takes the skipped steps back out of the step counters, clears the word and resets the per-step call state, so the

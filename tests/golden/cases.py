@@ -232,7 +232,7 @@ ORACLE_ONLY_CASES = {
         windows=3, steps=2, adv_w=1.0, mse_w=0.5, mge_w=1.0, dropout_on=True,
         update_d=True, update_g=True),
     # cfg3 (BASELINE.json configs[2]) at its real widths -- BiLSTM 3 x 256 generator, 425 -> 187, conditioned MLP D
-    # 483 -> 256 x 3 -> 1, B = 32 (two 16-sequence batch tiles), variable lengths -- with T cut to what the CPU oracle's
+    # 483 -> 256 x 3 -> 1, B = 32 (four 8-sequence batch tiles per direction), variable lengths -- with T cut to what the CPU oracle's
     # python time loop finishes in seconds: every code path of the persistent recurrence kernels that depends on the
     # widths (64 workgroups per group, K split over the waves, the 4H-wide backward exchange) is the full-size one
     "acoustic_lstm_at_size": dict(

@@ -976,7 +976,8 @@ def test_philox_dropout_step_matches_oracle_with_dumped_masks(tag, B, Tn, gh, dh
                                             (3, 17, 10, 300, 1, True)])
 def test_lstmrnn_forward_matches_oracle_unsorted_lengths(B, T, din, H, L, bi):
     """LSTMRNN.forward(sequence, lengths) vs the oracle's masked time loop (== nn.LSTM over packed
-    sequences, pinned by the golden case); lengths deliberately NOT sorted, B > 32 covers 2 batch tiles."""
+    sequences, pinned by the golden case); lengths deliberately NOT sorted, B = 37 runs five
+    8-sequence batch tiles, the last one ragged.  (16-sequence tiles, every unit count and precision: test_gpu_lstm_recurrence.py.)"""
     from gantts_amd import models
     spec = dict(kind="LSTMRNN", in_dim=din, out_dim=11, num_hidden=L, hidden_dim=H, bidirectional=bi, dropout=0.0,
                 last_sigmoid=False)
