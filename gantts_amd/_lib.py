@@ -25,6 +25,8 @@ OPT_COMM_TV_IN_SUMS, OPT_COMM_IPC, OPT_FUSED_DSTACK = 17, 18, 19
 IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts
+GEMM_PATH_SLOTS = 588                                                   # gt_gemm_path_counts
+GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
 ARCH_MLP, ARCH_IN2OUT, ARCH_LSTM, ARCH_SRU, ARCH_IN2OUT_RNN = 0, 1, 2, 3, 4
 OPT_ADAGRAD, OPT_ADAM = 0, 1
 MAX_STREAMS = 8
@@ -68,6 +70,14 @@ class GResult(C.Structure):
                 ("loss_g", C.c_float), ("grad_norm", C.c_float)]
 
 
+class GemmCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("route", "prec", "rows", "in_dim", "out_dim", "act", "drop")] + [("p", C.c_float)]
+                + [("key0", C.c_uint32), ("key1", C.c_uint32)]
+                + [(n, C.c_int32) for n in ("accumulate", "col0", "ncols", "wrap", "cd", "rider", "defer", "ldx", "ldw", "ldy", "ld_dy",
+                                            "ldh", "ld_mask", "ld_addm", "ld_adv", "ld_dx")]
+                + [(n, C.c_void_p) for n in ("x", "w", "bias", "y", "dy", "h", "mask", "addm", "adv", "dx", "dw", "db")])
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> (restype, argtypes); every symbol declared in include/gantts_hip.h
@@ -102,6 +112,8 @@ SIGNATURES = {
     "gt_set_tuning": (_I, [C.c_char_p, _I]),
     "gt_check_faults": (_I, [_P, _P]),
     "gt_lstm_path_counts": (_I, [_P, C.POINTER(_L), _I]),
+    "gt_gemm_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_op_gemm_f32": (_I, [C.POINTER(GemmCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

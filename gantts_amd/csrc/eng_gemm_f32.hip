@@ -1,5 +1,6 @@
 // libgantts_hip.so -- dispatch of the float32 MFMA GEMM family (gemm_f32.hip.h): tile choice, pair launches, weight-gradient slabs
 #include "engine_internal.hip.h"
+#include <atomic>
 
 using namespace gt;
 // the kernels are instantiated per operand orientation in their own translation units (eng_gemm_f32_{nt,nn,tn,pair}.hip)
@@ -25,6 +26,17 @@ int gemm_cu_count() {
 // products of the GEMM family: f32 MFMA (default) or bf16 MFMA with f32 accumulation (GT_OPT_MATMUL_BF16; set per engine
 // entry point for the launches it issues on this thread)
 thread_local int tl_gemm_prec = PREC_F32;
+
+// gt_gemm_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
+static std::atomic<int64_t> g_gemm_paths[GT_GEMM_PATH_SLOTS];
+void gemm_path_count(int slot) { g_gemm_paths[slot].fetch_add(1, std::memory_order_relaxed); }
+extern "C" int gt_gemm_path_counts(int64_t* counts, int reset) {
+  for (int i = 0; i < GT_GEMM_PATH_SLOTS; ++i) {
+    const int64_t v = reset ? g_gemm_paths[i].exchange(0, std::memory_order_relaxed) : g_gemm_paths[i].load(std::memory_order_relaxed);
+    if (counts) counts[i] = v;
+  }
+  return GT_OK;
+}
 
 static int pick_bn(int N) { return (cdiv(N, 64) * 64 < cdiv(N, 128) * 128) ? 64 : 128; }
 
@@ -124,6 +136,7 @@ static bool gemm_pair_ok(const GemmArgs& nn) {
 // nothing reads a weight gradient between a network's backward pass and its optimizer step.
 int slab_defer_flush(SlabDefer& d, hipStream_t s) {
   if (d.jobs.n > 0) {
+    gemm_path_count(GEMM_PATH_REDUCE_MULTI);
     hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(d.blocks), dim3(256), 0, s, d.jobs);
     LAUNCH_CHECK();
   }
@@ -190,15 +203,18 @@ int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, l
         defer->blocks += main_blocks + bias_blocks;
         return GT_OK;
       }
-      hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab,
+      gemm_path_count(GEMM_PATH_REDUCE4);
+    hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab,
                          slab_stride / 4, dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
       LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slabs.as<float>(),
+      gemm_path_count(GEMM_PATH_REDUCE);
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slabs.as<float>(),
                          slab_stride, nslab, slab_stride, dW, accumulate ? 1 : 0);
       LAUNCH_CHECK();
       if (db) {
-        hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db,
+        gemm_path_count(GEMM_PATH_REDUCE_SMALL);
+      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db,
                            accumulate ? 1 : 0);
         LAUNCH_CHECK();
       }
@@ -207,9 +223,11 @@ int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, l
     const int rows_per_blk = 128;
     const int nblk = cdiv(rows, rows_per_blk);
     CHK(colp.ensure((size_t)nblk * out * sizeof(float)));
+    gemm_path_count(GEMM_PATH_COLSUM_PARTIAL);
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk, cdiv(out, 64)), dim3(256), 0, s, dZ, lddz, rows, out, rows_per_blk,
                        colp.as<float>());
     LAUNCH_CHECK();
+    gemm_path_count(GEMM_PATH_COLSUM_FINALIZE);
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(out, 256)), dim3(256), 0, s, colp.as<float>(), nblk, out, db,
                        accumulate ? 1 : 0);
     LAUNCH_CHECK();
@@ -286,14 +304,17 @@ int linear_backward_weight_split(const float* dZ, int lddz, long rows, long wrap
       defer->blocks += main_blocks + bias_blocks;
       return GT_OK;
     }
+    gemm_path_count(GEMM_PATH_REDUCE4);
     hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab,
                        slab_stride / 4, dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
     LAUNCH_CHECK();
   } else {
+    gemm_path_count(GEMM_PATH_REDUCE);
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride, dW,
                        accumulate ? 1 : 0);
     LAUNCH_CHECK();
     if (db) {
+      gemm_path_count(GEMM_PATH_REDUCE_SMALL);
       hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db, accumulate ? 1 : 0);
       LAUNCH_CHECK();
     }

@@ -25,6 +25,7 @@ int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, hi
   // GT_PAIR_ORDER (default 1): weight-gradient workgroups first (longest work first); 0 = backward-data tiles first
   const int tn_first = gt_tuning().pair_order;   // measured: 108.2 -> 104.4 us per pair launch, cfg2 step 1.523 -> 1.499 ms
   const int grid = n1 + n2;
+  gemm_path_count(GEMM_PATH_PAIR + (bf16 ? 3 : am == GEMM_A_NONE ? 0 : am == GEMM_A_LEAKY_PHILOX ? 1 : 2));
   if (bf16) hipLaunchKernelGGL(gemm_pair_kernel<PREC_BF16>, dim3(grid), dim3(GEMM_THREADS), lds, s, nn, tn, n1, tn_first);
   else if (am == GEMM_A_NONE) hipLaunchKernelGGL((gemm_pair_kernel<PREC_F32, GEMM_A_NONE>), dim3(grid), dim3(GEMM_THREADS), lds, s, nn, tn, n1, tn_first);
   else if (am == GEMM_A_LEAKY_PHILOX) hipLaunchKernelGGL((gemm_pair_kernel<PREC_F32, GEMM_A_LEAKY_PHILOX>), dim3(grid), dim3(GEMM_THREADS), lds, s, nn, tn, n1, tn_first);
@@ -63,6 +64,7 @@ int launch_gemm_tn_pair(const GemmArgs& g1_in, const GemmArgs& g2_in, int nslab1
     rec.e0 = g_prof.get(); rec.e1 = g_prof.get();
     HIPCHK(hipEventRecord(rec.e0, s));
   }
+  gemm_path_count(GEMM_PATH_TN_PAIR + (n3 > 0 ? 1 : 0));
   hipLaunchKernelGGL(gemm_tn_pair_kernel<PREC_F32>, dim3(n1 + n2 + n3), dim3(GEMM_THREADS), lds, s, g1, g2, n1, g3, n3);
   LAUNCH_CHECK();
   if (g_prof.wants(6)) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }

@@ -220,3 +220,97 @@ extern "C" int gt_op_linear_bf16(const float* X, const float* W, const float* bi
   return GT_OK;
 }
 
+// One product of the float32 MFMA family through the engine's own dispatch (linear_forward / launch_gemm / linear_backward_data /
+// linear_backward_weight / linear_backward_weight_split): parity hook of tests/test_gpu_gemm_f32.py.  Forms the engine builds in
+// place (the added-matrix and two-segment forward of the split first layer, eng_step.hip: stack_forward; accumulate) are built
+// here the same way and go to launch_gemm.
+extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (c->route < GT_GEMM_ROUTE_FORWARD || c->route > GT_GEMM_ROUTE_WEIGHT_GRAD_SPLIT) return fail(GT_ERR_INVALID, "unknown route %d", c->route);
+  if (c->prec != 0 && c->prec != 1) return fail(GT_ERR_INVALID, "prec must be 0 (float32) or 1 (bf16)");
+  if (c->rows < 1 || c->in_dim < 1 || c->out_dim < 1) return fail(GT_ERR_INVALID, "bad sizes");
+  if (c->act < ACT_NONE || c->act > ACT_SIGMOID || c->drop < DROP_NONE || c->drop > DROP_BUFFER) return fail(GT_ERR_INVALID, "unknown activation / dropout");
+  if (c->drop != DROP_NONE && (c->act != ACT_LEAKY_DROPOUT || !(c->p > 0.f && c->p < 1.f) || (c->drop == DROP_BUFFER && !c->mask)))
+    return fail(GT_ERR_INVALID, "dropout needs act 1, 0 < p < 1 and (buffer) a mask");
+  const int route = c->route;
+  const bool seg = route == GT_GEMM_ROUTE_FORWARD_SEG, split = route == GT_GEMM_ROUTE_WEIGHT_GRAD_SPLIT;
+  const bool wgrad = route == GT_GEMM_ROUTE_WEIGHT_GRAD || split;
+  const bool data = route == GT_GEMM_ROUTE_BACKWARD_DATA || (wgrad && c->rider);
+  if ((seg || split) && (c->rows != c->wrap && c->rows != 2L * c->wrap)) return fail(GT_ERR_INVALID, "rows must be wrap or 2 wrap");
+  if ((seg || split) && (c->cd < 1 || c->cd >= c->in_dim || !c->x || !c->adv)) return fail(GT_ERR_INVALID, "split layer needs x, adv and 0 < cd < in_dim");
+  if ((route == GT_GEMM_ROUTE_FORWARD || seg) && (!c->x || !c->w || !c->y)) return fail(GT_ERR_INVALID, "forward needs x, w and y");
+  if (route == GT_GEMM_ROUTE_FORWARD && c->addm && (c->wrap < 1 || c->rows > 2L * c->wrap)) return fail(GT_ERR_INVALID, "added matrix needs rows <= 2 wrap");
+  if (data && (!c->dy || !c->w || !c->dx || c->col0 < 0 || c->ncols < 1 || (long)c->col0 + c->ncols > c->in_dim))
+    return fail(GT_ERR_INVALID, "backward-data needs dy, w, dx and col0 + ncols <= in_dim");
+  if (data && c->act != ACT_NONE && !c->h) return fail(GT_ERR_INVALID, "activation derivative without h");
+  if (wgrad && (!c->dy || (!c->dw && !c->db) || (c->dw && !c->x) || (split && !c->dw))) return fail(GT_ERR_INVALID, "weight gradient needs dy, x and dw / db");
+  hipStream_t s = (hipStream_t)stream;
+  DropoutSpec drop = no_drop();
+  if (c->drop == DROP_BUFFER) {
+    drop = buffer_spec(c->mask, c->p, c->ld_mask);
+  } else if (c->drop == DROP_PHILOX) {     // as philox_site_spec, with the caller's keys
+    drop.mode = DROP_PHILOX; drop.p = c->p; drop.scale = 1.f / (1.f - c->p);
+    const double th = (double)c->p * 65536.0 + 0.5;
+    drop.thresh = th >= 65535.0 ? 65535u : (uint32_t)th;
+    drop.key0 = c->key0; drop.key1 = c->key1;
+  }
+  Scratch slabs, colp;
+  SlabDefer sd;
+  sd.active = c->defer != 0;
+  tl_gemm_prec = c->prec ? PREC_BF16 : PREC_F32;
+  auto body = [&]() -> int {
+    if (route == GT_GEMM_ROUTE_FORWARD) {
+      if (!c->addm && !c->accumulate)
+        return linear_forward(c->x, c->ldx, c->w, c->ldw, c->bias, c->y, c->ldy, c->rows, c->in_dim, c->out_dim, c->act, drop, s);
+      GemmArgs g;
+      memset(&g, 0, sizeof(g));
+      g.A = c->x; g.lda = c->ldx; g.B = c->w; g.ldb = c->ldw; g.C = c->y; g.ldc = c->ldy;
+      g.M = c->rows; g.N = c->out_dim; g.K = c->in_dim; g.bias = c->bias; g.act = c->act; g.drop = drop; g.accumulate = c->accumulate ? 1 : 0;
+      if (c->addm) { g.addm = c->addm; g.ld_addm = c->ld_addm; g.addm_wrap = c->wrap; }
+      return launch_gemm(GEMM_NT, g, 1, s);
+    }
+    if (seg) {
+      GemmArgs g;
+      memset(&g, 0, sizeof(g));
+      g.A = c->x; g.lda = c->ldx; g.B = c->w; g.ldb = c->ldw; g.C = c->y; g.ldc = c->ldy;
+      g.M = c->wrap; g.N = c->out_dim; g.K = c->cd; g.bias = c->bias; g.act = c->act; g.drop = drop;
+      g.A_seg = c->adv; g.lda_seg = c->ld_adv; g.B_seg = c->w + c->cd; g.K_seg = c->in_dim - c->cd;
+      g.dual_rows = c->rows == 2 * c->wrap ? c->wrap : 0;
+      return launch_gemm(GEMM_NT, g, 1, s);
+    }
+    if (route == GT_GEMM_ROUTE_BACKWARD_DATA) {
+      if (!c->accumulate)
+        return linear_backward_data(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h, c->ldh,
+                                    drop, s);
+      GemmArgs g = backward_data_args(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h,
+                                      c->ldh, drop);
+      g.accumulate = 1;
+      return launch_gemm(GEMM_NN, g, 1, s);
+    }
+    bool rode = false;
+    GemmArgs nn;
+    memset(&nn, 0, sizeof(nn));
+    if (route == GT_GEMM_ROUTE_WEIGHT_GRAD) {
+      if (c->rider)
+        nn = backward_data_args(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h, c->ldh, drop);
+      CHK(linear_backward_weight(c->dy, c->ld_dy, c->x, c->ldx, c->rows, c->out_dim, c->in_dim, c->dw, c->db, c->accumulate != 0, slabs, colp, s,
+                                 &sd, c->rider ? &nn : nullptr, &rode));
+    } else {
+      const long row0 = c->rows - c->wrap;      // the rider reads the last half's rows (the generated rows of the D step)
+      if (c->rider)
+        nn = backward_data_args(c->dy + row0 * c->ld_dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->wrap, c->out_dim, c->ncols, c->act,
+                                c->h, c->ldh, drop);
+      CHK(linear_backward_weight_split(c->dy, c->ld_dy, c->rows, c->wrap, c->x, c->ldx, c->cd, c->adv, c->ld_adv, c->in_dim - c->cd, c->out_dim,
+                                       c->dw, c->db, c->accumulate != 0, slabs, s, &sd, c->rider ? &nn : nullptr, &rode));
+    }
+    if (c->rider && !rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+    return slab_defer_flush(sd, s);
+  };
+  const int r = body();
+  tl_gemm_prec = PREC_F32;
+  const hipError_t err = hipStreamSynchronize(s);
+  slabs.release(); colp.release(); sd.pool.release();
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_f32: %s", hipGetErrorString(err));
+  return GT_OK;
+}

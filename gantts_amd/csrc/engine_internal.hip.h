@@ -346,6 +346,14 @@ gt::DropoutSpec drop_spec(gt_engine* e, int role, int pass, int layer, const flo
 // engine entry point for the launches it issues on this thread
 // ------------------------------------------------------------------------------------------
 extern thread_local int tl_gemm_prec;
+// gt_gemm_path_counts: launches of the family by kernel, counted on the host where they are issued (slot encoding in gantts_hip.h)
+enum { GEMM_PATH_PAIR = 576, GEMM_PATH_TN_PAIR = 580, GEMM_PATH_REDUCE4 = 582, GEMM_PATH_REDUCE = 583, GEMM_PATH_REDUCE_SMALL = 584,
+       GEMM_PATH_COLSUM_PARTIAL = 585, GEMM_PATH_COLSUM_FINALIZE = 586, GEMM_PATH_REDUCE_MULTI = 587 };
+static_assert(GEMM_PATH_REDUCE_MULTI + 1 == GT_GEMM_PATH_SLOTS, "gt_gemm_path_counts slots");
+constexpr int gemm_path_slot(int kind, int bm, int bn, bool va, bool vb, int prec, int amode) {
+  return (((((kind * 2 + (bm == 128)) * 2 + (bn == 128)) * 2 + va) * 2 + vb) * 2 + (prec == gt::PREC_BF16)) * 6 + (amode + 1);
+}
+void gemm_path_count(int slot);
 // may this operand be loaded 16 bytes per lane?  k-contiguous operands (rows of X / W in the forward product, rows of dZ in
 // backward-data): any float pointer and pitch (unaligned 16-byte loads, gemm_f32.hip.h: ld4u); operands whose contiguous
 // direction is m / n: 16-byte aligned base and a pitch that is a multiple of 4 floats (GT_GEMM_UNALIGNED=0: that rule for all)

@@ -263,6 +263,17 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int sla
   float* C = g.C + (KIND == GEMM_TN ? (long)slab * g.slab_stride : 0L);
   const bool full_tile = m0 + BM <= m_lim && n0 + BN <= g.N;   // workgroup-uniform: no per-element guards (m_lim: row limit of this result block)
   const bool philox = (KIND != GEMM_TN) && g_act == ACT_LEAKY_DROPOUT && g_dmode == DROP_PHILOX;
+  // The C layout names a row's Philox counter and piece (q, half, s below) only in a tile that starts on a 16-row group.  The second
+  // half of a two-segment product starts its tiles at dual_rows + 64 t: for dual_rows % 16 != 0 each of the lane's 16 elements of a
+  // 32 x 32 block draws its own bit (philox_keep_spec), collected by a rolled loop into a mask (bit 4 q + s).
+  const bool px_own = AMODE == GEMM_A_LEAKY_PHILOX_SEG && philox && (m0 & 15) != 0;
+  auto own_keep_bits = [&](int i, int n) -> uint32_t {
+    uint32_t bits = 0u;
+#pragma unroll 1
+    for (int e = 0; e < 16; ++e)
+      bits |= (uint32_t)philox_keep_spec(g.drop, m0 + wm * WM + i * 32 + 8 * (e >> 2) + 4 * half + (e & 3), n) << e;
+    return bits;
+  };
 
   if (KIND != GEMM_TN && full_tile && g.wide_store) {
     // Wide path: everything that is keyed by the MFMA layout (bias column, the 4 Philox words of rows
@@ -284,14 +295,15 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int sla
         float bias = 0.f;
         if (KIND == GEMM_NT && g.bias) bias = g.bias[n];
         uint32_t rnd[4] = {0u, 0u, 0u, 0u};
+        const uint32_t own = px_own ? own_keep_bits(i, n) : 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int mrow = m0 + wm * WM + i * 32 + 8 * q + 4 * half;
-          if (philox && (q & 1) == 0)
+          if (philox && !px_own && (q & 1) == 0)
             philox4x32_10(2u * philox_group(g.drop, (uint32_t)mrow >> 4) + (uint32_t)half, (uint32_t)n, g.drop.key0, g.drop.key1, rnd);
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
-            const bool keep_px = philox_piece(rnd, 4 * (q & 1) + s4) >= g.drop.thresh;
+            const bool keep_px = px_own ? ((own >> (4 * q + s4)) & 1u) != 0u : philox_piece(rnd, 4 * (q & 1) + s4) >= g.drop.thresh;
             float v = acc[i][j][q * 4 + s4];
             if (KIND == GEMM_NT) {
               v += bias;
@@ -352,15 +364,16 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int sla
       float bias = 0.f;
       if (KIND == GEMM_NT && g.bias && n_ok) bias = g.bias[n];
       uint32_t rnd[4] = {0u, 0u, 0u, 0u};
+      const uint32_t own = px_own ? own_keep_bits(i, n) : 0u;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int mrow = m0 + wm * WM + i * 32 + 8 * q + 4 * half;  // rows mrow..mrow+3
-        if (philox && (q & 1) == 0)
+        if (philox && !px_own && (q & 1) == 0)
           philox4x32_10(2u * philox_group(g.drop, (uint32_t)mrow >> 4) + (uint32_t)half, (uint32_t)n, g.drop.key0, g.drop.key1, rnd);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const int m = mrow + s;
-          const bool keep_px = philox_piece(rnd, 4 * (q & 1) + s) >= g.drop.thresh;
+          const bool keep_px = px_own ? ((own >> (4 * q + s)) & 1u) != 0u : philox_piece(rnd, 4 * (q & 1) + s) >= g.drop.thresh;
           if (!full_tile && (!n_ok || m >= m_lim)) continue;
           float v = acc[i][j][q * 4 + s];
           if (KIND == GEMM_NT) {

@@ -418,6 +418,66 @@ int gt_op_linear_bf16(const float* X, const float* W, const float* bias, int64_t
                       const float* keep_mask_prev, float p_prev, float* dX, float* dW, float* db,
                       float* Y_image, float* YT_image, void* stream);
 
+/* Parity hook of the float32 MFMA product family (gemm_f32.hip.h): one product through the engine's own dispatch (tile,
+ * loader, slab split, pair and combine choice are the production ones).  Precision: prec 0 float32 products, 1 bf16 products
+ * (operands rounded to bf16 in the loader, float32 accumulation).  Dropout: drop 0 none, 1 Philox keep bits of (key0, key1)
+ * (philox_keep of gemm_f32.hip.h; thresh = round(p * 2^16)), 2 the 0/1 float mask `mask` [rows][ld_mask].  All pointers are
+ * device pointers, all pitches in floats.  Routes:
+ *   FORWARD          y[rows][ldy] (+= if accumulate) act(x[rows][ldx] . w[out][ldw]^T + bias [+ addm[m mod wrap][ld_addm]]), act on y's
+ *                    columns with the dropout of `drop`;  the addm form is the split first layer's adversarial product (rows <= 2 wrap)
+ *   FORWARD_SEG      the split first layer in one launch: y = LeakyReLU + Philox of x[m mod wrap][ldx] . w[:, :cd]^T +
+ *                    adv[rows][ld_adv] . w[:, cd:in]^T + bias, rows = wrap or 2 wrap (float32, 64 x 64 tiles, 16-byte loadable)
+ *   BACKWARD_DATA    dx[rows][ld_dx] (+=) (dy[rows][ld_dy] . w[:, col0:col0+ncols]) (.) f'(h[rows][ldh]) for act (the
+ *                    producer's activation) with the producer's dropout
+ *   WEIGHT_GRAD      dw[out][in] (+=) dy^T . x over rows frames, db[out] (+=) column sums of dy (either may be null);
+ *                    rider != 0: the BACKWARD_DATA product of the same case may share the launch; defer != 0: deferred combine
+ *   WEIGHT_GRAD_SPLIT  the split first layer's weight gradient: dw[:, :cd] = (dy[:wrap] (+ dy[wrap:])) ^T . x over wrap frames,
+ *                    dw[:, cd:] = dy^T . adv over rows frames, db = column sums of dy; rows = wrap or 2 wrap; rider != 0: the
+ *                    backward-data product dx = dy[rows - wrap:] . w[:, col0:col0+ncols] (no f') may share the launch
+ * Scratch is allocated, synchronised and released inside the call.  A malformed case returns GT_ERR_INVALID. */
+#define GT_GEMM_ROUTE_FORWARD 0
+#define GT_GEMM_ROUTE_FORWARD_SEG 1
+#define GT_GEMM_ROUTE_BACKWARD_DATA 2
+#define GT_GEMM_ROUTE_WEIGHT_GRAD 3
+#define GT_GEMM_ROUTE_WEIGHT_GRAD_SPLIT 4
+typedef struct gt_gemm_case {
+  int32_t route, prec;
+  int32_t rows, in_dim, out_dim;
+  int32_t act, drop;
+  float p;
+  uint32_t key0, key1;
+  int32_t accumulate;
+  int32_t col0, ncols;       /* BACKWARD_DATA and riders: column slice of w */
+  int32_t wrap, cd;          /* FORWARD addm wrap; FORWARD_SEG / WEIGHT_GRAD_SPLIT: rows of one half, width of x */
+  int32_t rider, defer;
+  int32_t ldx, ldw, ldy, ld_dy, ldh, ld_mask, ld_addm, ld_adv, ld_dx;
+  const float* x;
+  const float* w;
+  const float* bias;
+  float* y;
+  const float* dy;
+  const float* h;
+  const float* mask;
+  const float* addm;
+  const float* adv;
+  float* dx;
+  float* dw;
+  float* db;
+} gt_gemm_case;
+int gt_op_gemm_f32(const gt_gemm_case* c, void* stream);
+/* Product and combine launches of the float32 family by kernel, process-wide (the stand-alone operators have no engine), counted on
+ * the host where each launch is issued (no device work, no synchronisation).  Slots:
+ *   single product  (((((kind * 2 + (BM == 128)) * 2 + (BN == 128)) * 2 + VA) * 2 + VB) * 2 + bf16) * 6 + (AMODE + 1)   (0..575)
+ *                   kind 0 forward (GEMM_NT), 1 backward-data (GEMM_NN), 2 weight gradient (GEMM_TN); VA / VB: 16-byte loader of
+ *                   A / B; AMODE: GemmAmode, -1 epilogue decided at run time, 0 none, 1 LeakyReLU + Philox, 2 ... + added matrix,
+ *                   3 summed A operand, 4 two-segment forward
+ *   576..579        gemm_pair_kernel: float32 none / float32 LeakyReLU + Philox / float32 run time / bf16
+ *   580, 581        gemm_tn_pair_kernel without / with the riding backward-data product
+ *   582..587        combines: slab_reduce4, slab_reduce, slab_reduce_small, colsum_partial, colsum_finalize, slab_reduce_multi
+ * Copies the GT_GEMM_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
+#define GT_GEMM_PATH_SLOTS 588
+int gt_gemm_path_counts(int64_t* counts, int reset);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

@@ -39,6 +39,7 @@ def test_ctypes_structs_match_header_layout():
     assert C.sizeof(_lib.DResult) == 24 and C.sizeof(_lib.GResult) == 20
     assert _lib.ModelDesc.params.offset == 48 and C.sizeof(_lib.ModelDesc) == 72
     assert _lib.OptimDesc.step.offset == 32 and C.sizeof(_lib.OptimDesc) == 56
+    assert _lib.GemmCase.x.offset == 104 and _lib.GemmCase.db.offset == 192 and C.sizeof(_lib.GemmCase) == 200
 
 
 def test_invalid_arguments_are_reported_not_crashing():
