@@ -20,8 +20,6 @@ struct RcclApi {
   int (*CommInitRank)(void**, int, GtNcclId, int) = nullptr;
   int (*CommDestroy)(void*) = nullptr;
   int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
   const char* (*GetErrorString)(int) = nullptr;
 };
 static RcclApi* rccl_api() {
@@ -44,10 +42,9 @@ static RcclApi* rccl_api() {
   if (!h) return nullptr;
 #define GT_SYM(field, name) *(void**)(&api.field) = dlsym(h, name)
   GT_SYM(GetUniqueId, "ncclGetUniqueId"); GT_SYM(CommInitRank, "ncclCommInitRank"); GT_SYM(CommDestroy, "ncclCommDestroy");
-  GT_SYM(AllReduce, "ncclAllReduce"); GT_SYM(GroupStart, "ncclGroupStart"); GT_SYM(GroupEnd, "ncclGroupEnd");
-  GT_SYM(GetErrorString, "ncclGetErrorString");
+  GT_SYM(AllReduce, "ncclAllReduce"); GT_SYM(GetErrorString, "ncclGetErrorString");
 #undef GT_SYM
-  if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllReduce || !api.GroupStart || !api.GroupEnd) return nullptr;
+  if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllReduce) return nullptr;
   api.lib = h;
   return &api;
 }
@@ -251,13 +248,11 @@ int comm_flush(gt_engine* e, int role, hipStream_t compute, bool closing) {
 int comm_finish_step(gt_engine* e, int role, bool grads, double* sums, int n_sums, hipStream_t compute) {
   if (!comm_on(e)) return GT_OK;
   Net& n = e->net[role];
-  const bool grp = e->opt_comm_group && rccl_api();
   const bool inl = e->opt_comm_close_inline;
   // closing messages on the step's own stream: whatever the communicator's stream still carries (earlier buckets of this step)
   // must be ordered in front of them for the final join below to cover everything; RCCL serialises the calls of a communicator
   // in issue order, and the step stream also waits for the communicator's stream explicitly before the first inline call
   if (inl) CHK(comm_join(e, compute));
-  if (grp) NCCLCHK(rccl_api()->GroupStart());       // the closing messages of a step (rest of the gradient + loss sums): one launch
   if (grads) {
     CHK(comm_flush(e, role, compute, inl));
     auto& done = e->comm_done[role];
@@ -272,7 +267,6 @@ int comm_finish_step(gt_engine* e, int role, bool grads, double* sums, int n_sum
   e->comm_done[role].clear();
   e->comm_pending[role].clear();
   if (sums && n_sums > 0) CHK(comm_allreduce_after(e, sums, (size_t)n_sums, GT_NCCL_DOUBLE, compute, inl));
-  if (grp) NCCLCHK(rccl_api()->GroupEnd());
   return inl ? GT_OK : comm_join(e, compute);
 }
 

@@ -165,7 +165,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
                     &e->headp, &e->headw, &e->gx_dense, &e->cx_dense, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp};
   for (auto* s : all) s->release();
   e->w0pad[0].release(); e->w0pad[1].release();
-  e->opt_bar.release(); e->d_pre.release(); e->adv2.release(); e->pitched[0].buf.release(); e->pitched[1].buf.release();
+  e->d_pre.release(); e->adv2.release(); e->pitched[0].buf.release(); e->pitched[1].buf.release();
   for (auto* v : {&e->g_actb, &e->d_actb}) for (auto& b : *v) b.release();
   e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
   for (int r = 0; r < 2; ++r) for (auto& w : e->wsh[r]) { w.w.release(); w.wt.release(); }
@@ -175,9 +175,6 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   for (auto& w : e->ssh) { w.w.release(); w.wt.release(); }
   for (auto& b : e->l_dg_b) b.release();
   e->l_hs_b.release();
-  if (e->side) (void)hipStreamDestroy(e->side);
-  if (e->ev_side_go) (void)hipEventDestroy(e->ev_side_go);
-  if (e->ev_side_done) (void)hipEventDestroy(e->ev_side_done);
   for (auto& w : e->lsh) { w.w.release(); w.wt.release(); }
   e->sdefer[0].pool.release(); e->sdefer[1].pool.release();
   e->mlpg.clear();
@@ -360,12 +357,8 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       if (e->opt_split_first != (value != 0)) { e->fake_cat_valid = false; e->adv2_fake_ok = false; }
       e->opt_split_first = value != 0;
       return GT_OK;
-    case GT_OPT_FUSED_OPTIMIZER: e->opt_fused_optimizer = value != 0; return GT_OK;
-    case GT_OPT_SIDE_OVERLAP: e->opt_side_overlap = value != 0; return GT_OK;
-    case GT_OPT_LSTM_SIDE: return value ? fail(GT_ERR_INVALID, "GT_OPT_LSTM_SIDE: removed in round 6 (measured: no gain); the value must be 0") : GT_OK;
     case GT_OPT_COMM_D_ONE_MSG: e->opt_comm_d_one_msg = value != 0; return GT_OK;
     case GT_OPT_COMM_EARLY_G: e->opt_comm_early_g = value != 0; return GT_OK;
-    case GT_OPT_COMM_GROUP: e->opt_comm_group = value != 0; return GT_OK;
     case GT_OPT_COMM_FORCE: e->opt_comm_force = value != 0; return GT_OK;
     case GT_OPT_COMM_CLOSE_INLINE: e->opt_comm_close_inline = value != 0; return GT_OK;
     case GT_OPT_COMM_IPC: e->opt_comm_ipc = value != 0; return GT_OK;
@@ -394,9 +387,8 @@ GtTuning& gt_tuning() {
     { const char* s = getenv("GT_GEMM_TILES"); v.gemm_tiles_big = s && !strcmp(s, "big") ? 1 : 0; }
     v.gemm_unaligned = geti("GT_GEMM_UNALIGNED", v.gemm_unaligned); v.tn_wgs = geti("GT_TN_WGS", v.tn_wgs); v.tn_split_wgs = geti("GT_TN_SPLIT_WGS", v.tn_split_wgs); v.split_fused = geti("GT_SPLIT_FUSED", v.split_fused);
     v.b16_tiles = geti("GT_B16_TILES", v.b16_tiles); v.b16_wg_tile = geti("GT_B16_WG_TILE", v.b16_wg_tile); v.b16_dma = geti("GT_B16_DMA", v.b16_dma);
-    v.mlpg_fpl = geti("GT_MLPG_FPL", v.mlpg_fpl); v.mlpg_tt = geti("GT_MLPG_TT", v.mlpg_tt); v.sru_lw = geti("GT_SRU_LW", v.sru_lw); v.sru_cs_waves = geti("GT_SRU_CS_WAVES", v.sru_cs_waves); v.leak_rider = geti("GT_LEAK_RIDER", v.leak_rider);
+    v.mlpg_fpl = geti("GT_MLPG_FPL", v.mlpg_fpl); v.mlpg_tt = geti("GT_MLPG_TT", v.mlpg_tt); v.sru_coop = geti("GT_SRU_COOP", v.sru_coop); v.sru_cs_waves = geti("GT_SRU_CS_WAVES", v.sru_cs_waves); v.leak_rider = geti("GT_LEAK_RIDER", v.leak_rider);
     v.head_vec = geti("GT_HEAD_VEC", v.head_vec);
-    v.mlpg_small16 = geti("GT_MLPG_SMALL16", v.mlpg_small16);
     v.lstm_bt = geti("GT_LSTM_BT", v.lstm_bt);
     if (v.lstm_bt != 8 && v.lstm_bt != 16) v.lstm_bt = 0;
     return v;
@@ -409,12 +401,13 @@ extern "C" int gt_set_tuning(const char* name, int value) {
   struct { const char* n; int* p; } tab[] = {
       {"gemm_pair", &t.gemm_pair}, {"pair_order", &t.pair_order}, {"gemm_tiles_big", &t.gemm_tiles_big}, {"gemm_unaligned", &t.gemm_unaligned},
       {"tn_wgs", &t.tn_wgs}, {"tn_split_wgs", &t.tn_split_wgs}, {"split_fused", &t.split_fused}, {"b16_tiles", &t.b16_tiles},
-      {"b16_wg_tile", &t.b16_wg_tile}, {"b16_dma", &t.b16_dma}, {"mlpg_fpl", &t.mlpg_fpl}, {"mlpg_tt", &t.mlpg_tt}, {"sru_lw", &t.sru_lw}, {"sru_cs_waves", &t.sru_cs_waves}, {"leak_rider", &t.leak_rider}, {"head_vec", &t.head_vec}, {"mlpg_small16", &t.mlpg_small16}};
+      {"b16_wg_tile", &t.b16_wg_tile}, {"b16_dma", &t.b16_dma}, {"mlpg_fpl", &t.mlpg_fpl}, {"mlpg_tt", &t.mlpg_tt}, {"sru_coop", &t.sru_coop}, {"sru_cs_waves", &t.sru_cs_waves}, {"leak_rider", &t.leak_rider}, {"head_vec", &t.head_vec}};
   if (!strcmp(name, "lstm_bt")) {
     if (value != 0 && value != 8 && value != 16) return fail(GT_ERR_INVALID, "lstm_bt must be 0 (by shape), 8 or 16, not %d", value);
     t.lstm_bt = value;
     return GT_OK;
   }
+  if (!strcmp(name, "sru_lw")) { t.sru_coop = value >= 2; return GT_OK; }      // former name of sru_coop (2: cooperative; 0 / 1: the sequential forms), still accepted
   for (auto& e : tab) if (!strcmp(e.n, name)) { *e.p = value; return GT_OK; }
   return fail(GT_ERR_INVALID, "unknown tuning knob '%s'", name);
 }
@@ -571,7 +564,6 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemset(e->d_fault, 0, 64));
-  if (e->opt_bar.p) { HIPCHK(hipMemset(e->opt_bar.p, 0, 64)); e->opt_bar_count = 0; }      // the barrier counter restarts with the re-armed engine
   for (int r = 0; r < 2; ++r) { e->net[r].step -= (long)e->h_fault[2 + r]; if (e->net[r].step < 0) e->net[r].step = 0; }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   e->g_pass_valid = false; e->leak_pending = false; e->fake_cat_valid = false; e->adv2_fake_ok = false; e->cxd_src = nullptr;

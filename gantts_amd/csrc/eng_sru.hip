@@ -37,13 +37,11 @@ static SruArgs sru_args(gt_engine* e, const Net& G, int l, int B, int T, const f
   return a;
 }
 
-// the scans with loader waves (sru_kernels.hip.h); GT_SRU_LW=0 selects the one-wave kernels (A/B reference, bit-identical results)
-// (read at every launch: the A/B test flips it between two steps of one process)
-static bool sru_loader_waves() { return gt_tuning().sru_lw != 0; }
-// GT_SRU_LW=2 (default): the cooperative block scans (sru_cs_kernels.hip.h): every wave of a workgroup loads AND walks eight frames
+// GT_SRU_COOP=1 (default): the cooperative block scans (sru_cs_kernels.hip.h): every wave of a workgroup loads AND walks eight frames
 // of a block, the waves' composites are combined through LDS.  Eight waves per 64 columns up to two workgroups per CU (cfg4's B = 16, the
-// hparams-default generator's B = 32), four beyond.
-static bool sru_coop() { return gt_tuning().sru_lw >= 2; }
+// hparams-default generator's B = 32), four beyond.  0 selects the one-wave kernels (sru_kernels.hip.h), the sequential reference of the
+// tests (read at every launch: a test flips it between two steps of one process).
+static bool sru_coop() { return gt_tuning().sru_coop != 0; }
 static int sru_coop_waves(long B, int ncols) {
   const int forced = gt_tuning().sru_cs_waves;      // (tests: both instantiations on every shape)
   if (forced == 4 || forced == 8) return forced;
@@ -167,9 +165,6 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
         else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, true>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(true), s, a);
       } else if (w8) hipLaunchKernelGGL((sru_fwd_cs_kernel<8, false>), dim3(grid), dim3(512), sru_fwd_cs_lds<8>(), s, a);
       else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, false>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(), s, a);
-    } else if (sru_loader_waves()) {
-      CHK(ensure_dyn_lds((const void*)sru_fwd_lw_kernel, sru_fwd_lw_lds()));
-      hipLaunchKernelGGL(sru_fwd_lw_kernel, dim3(cdiv((long)B * ncols, 64)), dim3(SRU_LW_THREADS), sru_fwd_lw_lds(), s, a);
     } else {
       hipLaunchKernelGGL(sru_fwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
     }
@@ -241,9 +236,9 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
       a.ld_up_add = ncols;
     }
     a.dbias_part = e->s_dbias.as<float>();
-    // bf16 storage with loader waves, whole blocks of 8 frames, whole workgroups inside one sequence and one direction: dU leaves
-    // the scan as the bf16 images the two products read (no float32 dU, no cast pass)
-    const bool du_b16 = b16 && sru_loader_waves() && T % 8 == 0 && H % 64 == 0;
+    // bf16 storage with the cooperative scans, whole blocks of 8 frames, whole workgroups inside one sequence and one direction: dU
+    // leaves the scan as the bf16 images the two products read (no float32 dU, no cast pass)
+    const bool du_b16 = b16 && sru_coop() && T % 8 == 0 && H % 64 == 0;
     if (du_b16) {
       B16Img& DU = e->s_du_b;
       CHK(DU.ensure(N, ncols * L.k, true));
@@ -260,12 +255,6 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
       if (du_b16) { if (w8) GT_SRU_CS_LAUNCH(8, true); else GT_SRU_CS_LAUNCH(4, true); }
       else { if (w8) GT_SRU_CS_LAUNCH(8, false); else GT_SRU_CS_LAUNCH(4, false); }
 #undef GT_SRU_CS_LAUNCH
-    } else if (du_b16) {
-      CHK(ensure_dyn_lds((const void*)sru_bwd_lw_kernel<true>, sru_bwd_lw_lds()));
-      hipLaunchKernelGGL(sru_bwd_lw_kernel<true>, dim3(cdiv((long)B * ncols, 64)), dim3(SRU_LW_THREADS), sru_bwd_lw_lds(), s, a);
-    } else if (sru_loader_waves()) {
-      CHK(ensure_dyn_lds((const void*)sru_bwd_lw_kernel<false>, sru_bwd_lw_lds()));
-      hipLaunchKernelGGL(sru_bwd_lw_kernel<false>, dim3(cdiv((long)B * ncols, 64)), dim3(SRU_LW_THREADS), sru_bwd_lw_lds(), s, a);
     } else {
       hipLaunchKernelGGL(sru_bwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
     }

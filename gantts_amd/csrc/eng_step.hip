@@ -54,7 +54,7 @@ extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
   return GT_OK;
 }
 
-// output frames per workgroup of the MLPG kernels: 32; 16-frame tiles (gt_set_tuning("mlpg_tt", 16) / "mlpg_small16"): twice the workgroups for
+// output frames per workgroup of the MLPG kernels: 32; 16-frame tiles (gt_set_tuning("mlpg_tt", 16)): twice the workgroups for
 // batches whose 32-frame tiles leave CUs empty (a rank's share of a strong-scaling run: B * ceil(T / 32) = 64 workgroups at 4 sequences of
 // 512 frames), at (16 + 2 kb) / 16 staged rows per output frame.  (64-frame tiles -- half the halo re-reads, one workgroup per CU instead of two --
 // measured no gain in round 4, 1.404 / 1.398 vs 1.393 / 1.398 ms, and left the library in round 6.)
@@ -62,7 +62,6 @@ static int mlpg_tile_frames(gt_engine* e, int B, int T) {
   (void)e;
   const int tt = gt_tuning().mlpg_tt;
   if (tt == 16) return 16;
-  if (tt == 0 && gt_tuning().mlpg_small16 && (long)B * cdiv(T, 32) * 2 <= gemm_cu_count()) return 16;
   return 32;
 }
 int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const int* sstride, int Ds,
@@ -219,7 +218,7 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
 
 // Measured with one rank and forced collectives (bench.py --force-dp, plain step 1.465 ms): round-2 schedule 1.577 ms; the
 // discriminator's gradient as ONE message 1.561 (kept); additionally ncclGroupStart/End around a step's closing messages
-// 1.571 (off); generator loss sums sent with the closing messages instead of early 1.604 (off: the host then waits for the
+// 1.571 (removed); generator loss sums sent with the closing messages instead of early 1.604 (off: the host then waits for the
 // whole step before it can enqueue the next one).
 
 // hidden stack backward.  dz_top: gradient w.r.t. the pre-activation of the TOP hidden layer
@@ -646,8 +645,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   if (sd.active && sd.jobs.n > 0) {
     // The fused step recorded this network's weight-gradient combines.  They write disjoint ranges of the flat gradient; whatever
     // they do not cover (the discriminator's last layer, written by the head's reduction) still counts for the norm and is
-    // stepped: `rest`.  Default: combines + squared norm in ONE launch (slab_reduce_norm_kernel), then clip + step;
-    // GT_OPT_FUSED_OPTIMIZER: all of it in one launch behind a device-wide barrier (measured slower).
+    // stepped: `rest`.  Combines + squared norm in ONE launch (slab_reduce_norm_kernel), then clip + step.
     std::vector<std::pair<long, long>> cov;
     bool ok = true;
     for (int q = 0; q < sd.jobs.n && ok; ++q) {
@@ -674,18 +672,6 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
         rest_total += next - pos;
       }
       if (i < cov.size()) pos = cov[i].first + cov[i].second;
-    }
-    if (ok && e->opt_fused_optimizer && !gscale) {
-      if (!e->opt_bar.p) { CHK(e->opt_bar.ensure(64)); HIPCHK(hipMemsetAsync(e->opt_bar.p, 0, 64, s)); e->opt_bar_count = 0; }
-      const int grid = std::min(4 * gemm_cu_count(), std::max(sd.blocks, 64));
-      e->opt_bar_count += (unsigned long long)grid;
-      n.step += 1;
-      hipLaunchKernelGGL(optim_fused_kernel, dim3(grid), dim3(256), 0, s, sd.jobs, sd.blocks, rest, n.d.params, n.d.grads, n.od.state0, n.od.state1,
-                         part, e->opt_bar.as<unsigned long long>(), e->opt_bar_count, 200000000ULL /* 2 s of 100 MHz ticks */, norm2_out, o,
-                         e->d_fault, e->h_fault_dev, skipped);
-      LAUNCH_CHECK();
-      sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; sd.active = false;
-      return GT_OK;
     }
     const int rest_blocks = rest_total > 0 ? (int)std::min<long>(64, cdiv(rest_total, 256)) : 0;
     if (ok && sd.blocks + rest_blocks <= 2048) {
@@ -769,28 +755,6 @@ int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket) {
 // ------------------------------------------------------------------------------------------
 // update_discriminator
 // ------------------------------------------------------------------------------------------
-// Small HBM-bound kernels that nothing in front of them depends on run on the engine's side stream, UNDER the matrix
-// products of the step stream (which leave the memory system mostly idle): the valid-frame count of the D step (needed
-// only by the head, a whole forward pass later) and the reported MSE loss of the G step (train.py:294; needed only by the
-// step's finalisation).  side_fork: the side stream starts behind everything queued on `s` so far; side_join: `s` continues
-// behind the side stream.  Fused single-GPU calls only.  MEASURED SLOWER (cfg2 1.426 vs 1.413 ms: two event hand-offs per use cost
-// more than the 17 us of kernels they hide), so GT_OPT_SIDE_OVERLAP is off by default.
-static int side_fork(gt_engine* e, hipStream_t s) {
-  if (!e->side) {
-    HIPCHK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&e->ev_side_go, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->ev_side_done, hipEventDisableTiming));
-  }
-  HIPCHK(hipEventRecord(e->ev_side_go, s));
-  HIPCHK(hipStreamWaitEvent(e->side, e->ev_side_go, 0));
-  return GT_OK;
-}
-static int side_join(gt_engine* e, hipStream_t s) {
-  HIPCHK(hipEventRecord(e->ev_side_done, e->side));
-  HIPCHK(hipStreamWaitEvent(s, e->ev_side_done, 0));
-  return GT_OK;
-}
-
 // the split first layer (FirstSplit) applies to the conditioned discriminator on the float32 path
 static bool d_split_ok(gt_engine* e, const float* x, bool b16) {
   return e->opt_split_first && !b16 && e->net[GT_ROLE_D].d.arch == GT_ARCH_MLP && tl_gemm_prec == PREC_F32 && e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0 &&
@@ -826,8 +790,6 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     hipLaunchKernelGGL(mask_total_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, &e->sc()->tv_sum);
     LAUNCH_CHECK();
   }
-  const bool tv_side = e->early && !comm_on(e) && e->opt_side_overlap && !(e->tv_mask == mask && e->tv_n == N && e->tv_ovr == e->tv_override);
-  if (tv_side) { CHK(side_fork(e, s)); CHK(ensure_tv(e, mask, N, e->side)); }      // single GPU: the count is summed under the D forward pass
   const int passes[2] = {0, 1};
   // the [x | adv] image of both halves: real rows, then generated rows
   const bool b16 = use_b16(e, GT_ROLE_D);
@@ -853,7 +815,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     e->ld_adv2 = (e->Da + 3) & ~3;
     CHK(e->adv2.ensure((size_t)2 * N * e->ld_adv2 * sizeof(float)));
     // (the valid-frame count rides in this launch when it is not known yet: fused single-GPU call)
-    const bool tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_side && !tv_known;
+    const bool tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_known;
     const bool any_ride = tv_ride || tv_ride_dp || unnorm;
     hipLaunchKernelGGL(build_adv_kernel, dim3(cdiv(2 * N * (e->ld_adv2 / 4), 256) + (any_ride ? 1 : 0)), dim3(256), 0, s, y_static, y_hat_static,
                        e->Ds, e->d_adv_cols, e->Da, e->adv2.as<float>(), e->ld_adv2, N, 2 * N, any_ride ? mask : (const float*)nullptr,
@@ -905,7 +867,6 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   // fused call: losses and counts are final after the head (the gradient norm is not: reported as 0), so the head's
   // reduction kernel also writes the result struct and the scalars start their way to the host right behind it
   const bool plain_early = e->early && !comm_on(e), comm_early = e->early && comm_on(e);
-  if (tv_side) CHK(side_join(e, s));
   // data parallel + riders: the head reads the all-reduced count where the collective left it (and files it in the step's scalars):
   // no conversion launch between the join and the head
   const unsigned d_ticket = plain_early ? take_ticket(e) : 0;
@@ -1165,10 +1126,9 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   // (the fused single-GPU call reduces the MSE partials inside its finalisation launch: see early_now below)
   const bool early_fold = e->early && !comm_on(e) && !(tr && direct && mse_w != 0.f);
   int mse_blocks = 0, mge_pre_blocks = 0;
-  const bool mse_side = early_fold && e->opt_side_overlap && adv_w > 0.f;      // (under the D pass of the adversarial term)
   // launch riders (fused single-GPU call): both reported sums of squares in one launch here; the head's scalar reduction and the
   // step's finalisation as one extra workgroup of the gradient-assembly launch -- four launches become two
-  const bool riders = early_fold && e->opt_launch_riders && !mse_side;
+  const bool riders = early_fold && e->opt_launch_riders;
   // data parallel: the same launches, the rider then only files the three sums for the collective (nothing is reported from it)
   const bool riders_dp = e->early && comm_on(e) && e->opt_launch_riders && !(tr && direct && mse_w != 0.f);
   if (riders || riders_dp) {
@@ -1179,8 +1139,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
                        e->partial.as<double>() + 1024, y_hat_static, Ds, y_static, Ds, Ds, e->partial.as<double>(), mask, N);
     LAUNCH_CHECK();
   } else if (!(tr && direct && mse_w != 0.f)) {
-    if (mse_side) CHK(side_fork(e, s));
-    CHK(sum_sqerr(e, y_hat, Do, y, Do, mask, N, Do, &e->sc()->s_mse, nullptr, 0, 0.f, mse_side ? e->side : s, early_fold ? &mse_blocks : nullptr));
+    CHK(sum_sqerr(e, y_hat, Do, y, Do, mask, N, Do, &e->sc()->s_mse, nullptr, 0, 0.f, s, early_fold ? &mse_blocks : nullptr));
   }
   // adversarial term with the CURRENT (already updated) D weights and a fresh dropout mask (train.py:297-308)
   e->g_has_adv = adv_w > 0.f;
@@ -1313,7 +1272,6 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
       LAUNCH_CHECK();
     }
   }
-  if (mse_side && mse_blocks) CHK(side_join(e, s));
   if (early_now && !riders) {   // all four losses are final here; the MGE partials are reduced inside the finalisation launch
     hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(256), 0, s, e->sc(), early_res_target(e), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1,
                        (const double*)e->partial.as<double>(), mge_blocks,

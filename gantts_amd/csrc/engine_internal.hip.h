@@ -83,11 +83,10 @@ struct GtTuning {
   int head_vec = 0;           // GT_HEAD_VEC       discriminator head: 16-byte accesses (lane <-> four consecutive hidden units); measured -3 us
                               //                   per step, NOT the default: it sums the row's dot product in another order, and one oracle-only
                               //                   at-size case (a cold-Adagrad update, lr * g / |g|) then lands 1.2x outside its 1e-4
-  int mlpg_small16 = 0;       // GT_MLPG_SMALL16   16-frame MLPG tiles when 32-frame tiles would fill at most half the CUs (mlpg_tt == 0)
   int mlpg_tt = 0;            // GT_MLPG_TT        output frames per MLPG workgroup (0 = by shape, 16, 32)
   int leak_rider = 1;         // GT_LEAK_RIDER     D step: the kept dloss_d / dy_hat_static product rides in the split first layer's weight-gradient launch
   int sru_cs_waves = 0;       // GT_SRU_CS_WAVES   waves per 64 columns of the cooperative SRU scans: 0 = by shape (8 where B x ncols / 64 <= CUs, else 4), 4, 8
-  int sru_lw = 2;             // GT_SRU_LW         2: cooperative block scans (sru_cs_kernels.hip.h); 1: loader-wave scans; 0: one-wave kernels (1 == 0 bit for bit)
+  int sru_coop = 1;           // GT_SRU_COOP       1: cooperative block scans (sru_cs_kernels.hip.h); 0: one-wave kernels (sru_kernels.hip.h: the sequential reference)
   int lstm_bt = 0;            // GT_LSTM_BT        sequences per batch tile of the persistent LSTM kernels: 0 = by shape, 8, 16 (still subject to co-residency)
 };
 GtTuning& gt_tuning();
@@ -264,10 +263,8 @@ struct gt_engine {
   std::vector<B16Img> s_in_b;                      // SRU generator: image of every layer's (dropped) input (+ the top output, last entry)
   B16Img s_du_b;                                   // SRU: dU of the current layer, both orientations
   std::vector<LinShadow> ssh;                      // SRU: per layer W (n_in, ncols*k) as w [n_in][..] and wt [ncols*k][n_in]; last entry: hidden2out
-  std::vector<B16Img> l_dg_b;                      // per layer: dG image (both orientations; per layer because the side stream reads it late)
+  std::vector<B16Img> l_dg_b;                      // per layer: dG image (both orientations; every product that reads it runs on the step stream)
   B16Img l_hs_b;                                   // h that entered each frame (transposed)
-  hipStream_t side = nullptr;                      // recurrent generator: weight-gradient products run beside the next layer's recurrence
-  hipEvent_t ev_side_go = nullptr, ev_side_done = nullptr;
   std::vector<LinShadow> lsh;                      // per LSTM layer: W_ih of all directions stacked [dirs*4H][in]; last entry: hidden2out
   bool dcat_b_ok = false;                          // dcat_b's generated half holds [x | adv(y_hat_static)] of the tensors below
   const float* dcat_b_x = nullptr; const float* dcat_b_yhs = nullptr;
@@ -278,17 +275,15 @@ struct gt_engine {
   bool adv2_fake_ok = false; const float* adv2_yhs = nullptr;   // its generated half holds adv(y_hat_static) of this tensor
   struct Pitched { Scratch buf; const float* src = nullptr; int ld = 0, cols = 0; long rows = 0; uint64_t step = ~0ULL; };
   Pitched pitched[2];                              // 16-byte-pitch copies of caller tensors (slot 0: D's x, 1: G's input), once per step
-  // GT_OPT_SPLIT_FIRST_LAYER / GT_OPT_FUSED_OPTIMIZER (per engine; the environment only provides the default at creation)
+  // GT_OPT_SPLIT_FIRST_LAYER (per engine; the environment only provides the default at creation)
   // GT_OPT_FUSED_DSTACK: the float32 MLP discriminator's layers above the first one + the head (+, in the generator step, the
   // backward-data chain down to the adversarial columns) as ONE launch per pass (dstack_f32.hip.h)
   int opt_fused_dstack = getenv("GT_FUSED_DSTACK") ? atoi(getenv("GT_FUSED_DSTACK")) : 1;      // 0 off, 1 when the pass has >= one panel per CU, 2 always
   bool opt_split_first = env_flag("GT_D_SPLIT", true);
-  bool opt_fused_optimizer = env_flag("GT_OPT_FUSED", false);      // measured slower: off
-  bool opt_side_overlap = env_flag("GT_SIDE_OVERLAP", false);      // GT_OPT_SIDE_OVERLAP: tv / MSE kernels on the side stream (measured slower: off)
-  // data-parallel schedule (GT_OPT_COMM_*): D's gradient as one message, G's loss sums early, grouped closing messages,
+  // data-parallel schedule (GT_OPT_COMM_*): D's gradient as one message, G's loss sums early,
   // collectives issued even with one rank (bench.py --force-dp, tests)
   bool opt_comm_d_one_msg = env_flag("GT_COMM_D_ONE_MSG", true), opt_comm_early_g = env_flag("GT_COMM_EARLY_G", true),
-       opt_comm_group = env_flag("GT_COMM_GROUP", false), opt_comm_force = getenv("GT_COMM_FORCE_COLLECTIVES") != nullptr;
+       opt_comm_force = getenv("GT_COMM_FORCE_COLLECTIVES") != nullptr;
   bool opt_comm_close_inline = env_flag("GT_COMM_CLOSE_INLINE", true);   // GT_OPT_COMM_CLOSE_INLINE: a step's closing messages on the step stream itself
   // GT_OPT_COMM_TV_IN_SUMS: the data-parallel D step does not all-reduce the valid-frame count ahead of the head; the head seeds the
   // backward pass of the UNNORMALISED loss, the local count leaves with the four loss / count sums (one message instead of two), and
@@ -306,7 +301,6 @@ struct gt_engine {
   Scratch gx_dense, cx_dense;
   bool gx_dense_on = false;                        // this step's generator input is the dense copy: gx_pitch() == in_dim
   const float* cxd_src = nullptr; uint64_t cxd_step = ~0ull; long cxd_rows = 0; int cxd_ld = 0, cxd_cols = 0;     // what cx_dense holds
-  Scratch opt_bar; unsigned long long opt_bar_count = 0;   // arrival counter of optim_fused_kernel's device-wide barrier (monotonic across launches)
   Scratch w0pad[2];                                // per role: first hidden layer's weight with a 16-byte row pitch (stack_forward)
   unsigned int* h_fault_dev = nullptr;             // device view of h_fault[1]: the optimizer kernel mirrors a raised fault word
   unsigned int* d_fault = nullptr;                 // device fault word of the persistent kernels (0 = ok)

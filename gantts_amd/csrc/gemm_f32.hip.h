@@ -183,10 +183,10 @@ template <int KIND, int BM> constexpr int gemm_ldm() { return KIND == GEMM_TN ? 
 template <int KIND, int BN> constexpr int gemm_ldn() { return KIND == GEMM_NT ? BN + 1 : BN + 4; }
 // (r6: a k-contiguous operand kept as ROWS in LDS, its fragments of four MFMA groups fetched with one ds_read_b128 -- a quarter of the LDS read
 //  instructions, bit-identical, measured slower: forward launch 75.6 -> 78.5 us; tools/experiments/gemm_f32_lds_rows.patch)
-template <int KIND, int BM, int BN, int PREC = PREC_F32, int BKT = GEMM_BK>
+template <int KIND, int BM, int BN, int PREC = PREC_F32>
 constexpr size_t gemm_lds_bytes() {
   if (PREC == PREC_F32) {     // the operand image, but never less than the epilogue staging (4 waves x 32 x (BN/2 + 4) floats)
-    size_t img = (size_t)2 * BKT * (gemm_ldm<KIND, BM>() + gemm_ldn<KIND, BN>()) * sizeof(float), stg = (size_t)4 * 32 * (BN / 2 + 4) * 4;
+    size_t img = (size_t)2 * GEMM_BK * (gemm_ldm<KIND, BM>() + gemm_ldn<KIND, BN>()) * sizeof(float), stg = (size_t)4 * 32 * (BN / 2 + 4) * 4;
     return img > stg ? img : stg;
   }
   // bf16 image [2][BM + BN rows][GEMM_KP], but never less than what the epilogue staging (4 waves x 32 x (BN/2 + 4) floats)
@@ -246,7 +246,7 @@ enum GemmAmode { GEMM_A_RUNTIME = -1, GEMM_A_NONE = 0, GEMM_A_LEAKY_PHILOX = 1,
                  GEMM_A_LEAKY_PHILOX_ADDM = 2,   // NT: LeakyReLU + Philox dropout on (product + bias + addm)
                  GEMM_A_TN_SUM2 = 3,             // TN: loader sums A + A2
                  GEMM_A_LEAKY_PHILOX_SEG = 4 };  // NT: LeakyReLU + Philox dropout behind a two-segment K loop (A_seg / B_seg)
-template <int KIND, int BM, int BN, int PREC, int BKT, int AMODE = GEMM_A_RUNTIME>
+template <int KIND, int BM, int BN, int PREC, int AMODE = GEMM_A_RUNTIME>
 __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int slab, const int m0, const int n0,
                                                 f32x16 (&acc)[BM / 64][BN / 64], float* smem, const int m_lim) {
   constexpr bool RT = AMODE == GEMM_A_RUNTIME || AMODE == GEMM_A_TN_SUM2;
@@ -281,7 +281,7 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int sla
     // LDS region, and the strip leaves row-wise: 16 B per lane, WN*4-byte contiguous row segments
     // (4x fewer store instructions, full-line writes).  H (NN: f' of the producer) is read the same way.
     constexpr int EP = WN + 4;                    // pitch (floats), keeps 16 B alignment
-    static_assert((size_t)4 * 32 * EP * sizeof(float) <= gemm_lds_bytes<KIND, BM, BN, PREC, BKT>(), "epilogue staging exceeds the LDS image");
+    static_assert((size_t)4 * 32 * EP * sizeof(float) <= gemm_lds_bytes<KIND, BM, BN, PREC>(), "epilogue staging exceeds the LDS image");
     constexpr int LPR = WN / 4;                   // lanes per row
     constexpr int RPI = 64 / LPR;                 // rows per store instruction
     __syncthreads();                              // the K loop's LDS image is dead from here on
@@ -414,11 +414,8 @@ __device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const int sla
 // workgroup; `smem` = gemm_lds_bytes<KIND, BM, BN, PREC>() bytes of LDS, free on entry (callers that run several tiles in
 // one workgroup put a barrier between them).
 // VA / VB: operand is loaded 16 B per lane (requires 16-byte aligned base and pitch % 4 == 0)
-// BKT: K depth of one LDS stage (f32 only: 32, or 16 = half the LDS image, twice the workgroups per CU)
-template <int KIND, int BM, int BN, bool VA, bool VB, int PREC = PREC_F32, int BKT = 32, int AMODE = GEMM_A_RUNTIME>
+template <int KIND, int BM, int BN, bool VA, bool VB, int PREC = PREC_F32, int AMODE = GEMM_A_RUNTIME>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int slab, const int tile_m, const int tile_n, float* smem) {
-  static_assert(BKT == 32 || (BKT == 16 && PREC == PREC_F32), "K depth of an LDS stage");
-  constexpr int GEMM_BK = BKT;                  // shadows the namespace constant inside this function
   constexpr int LDM = gemm_ldm<KIND, BM>(), LDN = gemm_ldn<KIND, BN>();
   constexpr int WM = BM / 2, WN = BN / 2;       // wave tile
   constexpr int TM = WM / 32, TN_ = WN / 32;    // MFMA tiles per wave
@@ -870,11 +867,11 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int slab, con
       prologue();
       k_loop();
       gemm_kloop_prio(false);
-      gemm_store_tile<KIND, BM, BN, PREC, BKT, AMODE>(g, slab, m0 + h * g.dual_rows, n0, acc, smem, nh > 1 ? (h + 1) * g.dual_rows : g.M);
+      gemm_store_tile<KIND, BM, BN, PREC, AMODE>(g, slab, m0 + h * g.dual_rows, n0, acc, smem, nh > 1 ? (h + 1) * g.dual_rows : g.M);
     }
     return;
   }
-  gemm_store_tile<KIND, BM, BN, PREC, BKT, AMODE>(g, slab, m0, n0, acc, smem, g.M);
+  gemm_store_tile<KIND, BM, BN, PREC, AMODE>(g, slab, m0, n0, acc, smem, g.M);
 }
 
 // XCD-aware tile order: consecutive workgroup ids round-robin over the 8 XCDs, so give each XCD a contiguous run of
@@ -899,7 +896,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_pair_kernel(const GemmAr
   if (is_nn) {
     bid = gemm_xcd_order(tn_first ? bid - n2 : bid, n1);
     const int tile_m = bid / g1.n_tiles_n, tile_n = bid - tile_m * g1.n_tiles_n;
-    gemm_tile<GEMM_NN, 64, 64, true, true, PREC, 32, AMODE>(g1, 0, tile_m, tile_n, smem);
+    gemm_tile<GEMM_NN, 64, 64, true, true, PREC, AMODE>(g1, 0, tile_m, tile_n, smem);
   } else {
     bid = gemm_xcd_order(tn_first ? bid : bid - n1, n2);
     const int tiles_mn = g2.n_tiles_m * g2.n_tiles_n;
@@ -921,7 +918,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_tn_pair_kernel(const Gem
   int bid = blockIdx.x;
   if (bid >= (int)gridDim.x - n3) {
     bid -= (int)gridDim.x - n3;
-    gemm_tile<GEMM_NN, 64, 64, true, false, PREC, 32, GEMM_A_NONE>(g3, 0, bid / g3.n_tiles_n, bid % g3.n_tiles_n, smem);
+    gemm_tile<GEMM_NN, 64, 64, true, false, PREC, GEMM_A_NONE>(g3, 0, bid / g3.n_tiles_n, bid % g3.n_tiles_n, smem);
     return;
   }
   const int n2 = (int)gridDim.x - n3 - n1;
@@ -929,7 +926,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_tn_pair_kernel(const Gem
     bid = gemm_xcd_order(bid - n2, n1);
     const int tiles_mn = g1.n_tiles_m * g1.n_tiles_n;
     const int slab = bid / tiles_mn, t = bid - slab * tiles_mn;
-    gemm_tile<GEMM_TN, 64, 64, true, true, PREC, 32, GEMM_A_TN_SUM2>(g1, slab, t / g1.n_tiles_n, t % g1.n_tiles_n, smem);
+    gemm_tile<GEMM_TN, 64, 64, true, true, PREC, GEMM_A_TN_SUM2>(g1, slab, t / g1.n_tiles_n, t % g1.n_tiles_n, smem);
   } else {
     bid = gemm_xcd_order(bid, n2);
     const int tiles_mn = g2.n_tiles_m * g2.n_tiles_n;
@@ -944,7 +941,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_tn_pair_kernel(const Gem
 #define GT_SEG_WGS 4
 #endif
 template <int BM, int BN, int AMODE> constexpr int gemm_min_wgs() { return (BM == 64 && BN == 64 && AMODE == GEMM_A_LEAKY_PHILOX_SEG) ? GT_SEG_WGS : 2; }
-template <int KIND, int BM, int BN, bool VA, bool VB, int PREC = PREC_F32, int BKT = 32, int AMODE = GEMM_A_RUNTIME>
+template <int KIND, int BM, int BN, bool VA, bool VB, int PREC = PREC_F32, int AMODE = GEMM_A_RUNTIME>
 __global__ __launch_bounds__(GEMM_THREADS, (gemm_min_wgs<BM, BN, AMODE>())) void gemm_f32_kernel(const GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int bid = gemm_xcd_order(blockIdx.x, gridDim.x);
@@ -953,7 +950,7 @@ __global__ __launch_bounds__(GEMM_THREADS, (gemm_min_wgs<BM, BN, AMODE>())) void
   const int t = bid - slab * tiles_mn;
   // n fastest: workgroups sharing an M panel (the big frame matrix) run back to back
   const int tile_m = t / g.n_tiles_n, tile_n = t - tile_m * g.n_tiles_n;
-  gemm_tile<KIND, BM, BN, VA, VB, PREC, BKT, AMODE>(g, slab, tile_m, tile_n, smem);
+  gemm_tile<KIND, BM, BN, VA, VB, PREC, AMODE>(g, slab, tile_m, tile_n, smem);
 }
 
 }  // namespace gt

@@ -8,12 +8,12 @@ static double gemm_algorithmic_bytes(int kind, const GemmArgs& g) {
   if (kind == GEMM_NN && g.act != ACT_NONE && g.H) b += 4.0 * (double)g.M * g.N;     // the producer's stored activation
   return b;
 }
-// (r6: the hot 64 x 64 forward launches with HALF the LDS stage (BKT = 16: 58 VGPRs, 18 KB of LDS, eight workgroups per CU instead of four) measured
-//  77.6 vs 77.1 us: the K stage is not waiting for latency.  BKT stays 32.)
+// (r6: the hot 64 x 64 forward launches with HALF the LDS stage (a 16-deep K stage: 58 VGPRs, 18 KB of LDS, eight workgroups per CU instead of four) measured
+//  77.6 vs 77.1 us: the K stage is not waiting for latency.  The depth is fixed at GEMM_BK = 32.)
 template <int KIND, int BM, int BN, bool VA, bool VB, int PREC, int AM>
 static int launch_gemm_impl(GemmArgs g, int nslab, hipStream_t s) {
   const size_t lds = gemm_lds_bytes<KIND, BM, BN, PREC>();
-  CHK(ensure_dyn_lds((const void*)gemm_f32_kernel<KIND, BM, BN, VA, VB, PREC, 32, AM>, lds));
+  CHK(ensure_dyn_lds((const void*)gemm_f32_kernel<KIND, BM, BN, VA, VB, PREC, AM>, lds));
   g.n_tiles_m = cdiv(g.M, BM);
   g.n_tiles_n = cdiv(g.N, BN);
   const int grid = g.n_tiles_m * g.n_tiles_n * nslab;
@@ -30,7 +30,7 @@ static int launch_gemm_impl(GemmArgs g, int nslab, hipStream_t s) {
     HIPCHK(hipEventRecord(rec.e0, s));
   }
   gemm_path_count(gemm_path_slot(KIND, BM, BN, VA, VB, PREC, AM));
-  hipLaunchKernelGGL((gemm_f32_kernel<KIND, BM, BN, VA, VB, PREC, 32, AM>), dim3(grid), dim3(GEMM_THREADS), lds, s, g);
+  hipLaunchKernelGGL((gemm_f32_kernel<KIND, BM, BN, VA, VB, PREC, AM>), dim3(grid), dim3(GEMM_THREADS), lds, s, g);
   LAUNCH_CHECK();
   if (g_prof.wants(KIND)) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }
   return GT_OK;

@@ -1,7 +1,7 @@
 // Cooperative block scans of the SRU recurrence (reference gantts/models.py:144-167 -> `cuda_functional.SRU`, un-vendored: restated
 // recurrence, parity unpinned -- see sru_kernels.hip.h / oracle/gantts_oracle.py).
 //
-// The loader-wave scans of sru_kernels.hip.h give a workgroup's 64 columns ONE wave that walks the recurrence (three more only load):
+// A sequential scan gives 64 columns ONE wave that walks the recurrence (sru_kernels.hip.h; an earlier form added three waves that only loaded):
 // at B = 16 (BASELINE.json configs[3]: B x ncols = 16 384 lanes = one workgroup per CU) that is one wave per CU doing all the
 // arithmetic, ~440 cycles per frame, and the scans ran at 2.1 / 2.9 TB/s (0.27 / 0.36 of the HBM peak).  The cell is LINEAR in the
 // carried state,
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(64 * NW) void sru_fwd_cs_kernel(const SruArgs a) {
 // is one more load per block.  B16OUT: dU leaves as the two bf16 images the products read -- the transposed image straight from the
 // registers (a lane's eight frames of one gate column are 16 contiguous bytes), the row-major image through a wave-private LDS
 // stage (the lanes' values of one frame are interleaved k by k).  Needs T % 8 == 0, H % 64 == 0, B * ncols % 64 == 0 (checked by
-// the launcher) exactly like sru_bwd_lw_kernel<true>.
+// the launcher).
 template <int NW, bool B16OUT>
 __global__ __launch_bounds__(64 * NW) void sru_bwd_cs_kernel(const SruArgs a) {
   constexpr int S = SRU_CS_S, FBT = NW * S;

@@ -41,7 +41,7 @@ struct SruArgs {
   // backward only: this layer's output is the NEXT layer's input, and that layer's variational input dropout (+ its k == 3
   // highway gradient) is applied here, where the gradient is read: dh = g * up_mul[b][col] + up_add.  The multiplier is
   // constant per lane (one (sequence, column) pair per lane).
-  // backward, GT_OPT_MATMUL_BF16 with loader waves (T % 8 == 0, H % 64 == 0, B * ncols % 64 == 0): dU leaves the scan as the two
+  // backward, GT_OPT_MATMUL_BF16 with the cooperative scans (T % 8 == 0, H % 64 == 0, B * ncols % 64 == 0): dU leaves the scan as the two
   // bf16 images the products read (row-major [N][ld_dub], transposed [ncols*k][ld_dubt]) instead of float32 + a cast pass
   __bf16* dU_b; int ld_dub;
   __bf16* dU_bt; long ld_dubt;
@@ -67,8 +67,8 @@ __device__ __forceinline__ float sru_mask(const SruArgs& a, int b, int col) {
   return r[0] >= a.thresh ? a.keep_scale : 0.f;
 }
 
-// One frame of the recurrence / of its adjoint: ONE definition used by the one-wave and the loader-wave kernels (written with
-// explicit fmaf / __fmul_rn so that the two kernels cannot end up with different contractions).
+// One frame of the recurrence / of its adjoint, written with explicit fmaf / __fmul_rn: the contractions are fixed here, not
+// chosen by the compiler per call site.
 struct SruFwdOut { float c, h; };
 // The two sigmoids are fast_sigmoid (fast_math.hip.h: v_exp_f32 + v_rcp_f32, a few ulp): with one or two waves per SIMD the
 // scan is bound by the instruction count of a frame, and the library expf was most of it.
@@ -204,226 +204,12 @@ __global__ __launch_bounds__(SRU_THREADS) void sru_bwd_kernel(const SruArgs a) {
   a.dbias_part[(long)b * 2 * ncols + ncols + col] = dbr;
 }
 
-// ------------------------------------------------------------------------------------------
-// Loader-wave form of the two scans.  The scan has B * ncols independent lanes and nothing more (two waves per CU at
-// B = 32, 6 x 512 bidirectional): its HBM rate is the bytes those lanes keep in flight over the load latency, ~3 TB/s with
-// 48 / 56 loads per lane.  Here a workgroup is 64 lanes' worth of columns handled by FOUR waves: wave 0 does the recurrence,
-// waves 1-3 only load -- loader l fetches frame blocks l, l+3, l+6, ... (FB frames each) into registers and hands them to
-// wave 0 through a 3-slot LDS ring, so three blocks per column are in flight instead of one.  Same arithmetic in the same
-// order as sru_fwd_kernel / sru_bwd_kernel: results are bit-identical.  One s_barrier per block; the barrier is a bare
-// s_barrier behind lgkmcnt(0) (the ring is LDS; __syncthreads() would also drain the loaders' global loads, i.e. undo the
-// run-ahead).
-// ------------------------------------------------------------------------------------------
+// Helpers of the cooperative block scans (sru_cs_kernels.hip.h).  sru_ring_barrier: the workgroup barrier between the phases of a block,
+// a bare s_barrier behind lgkmcnt(0) -- what is exchanged is in LDS; __syncthreads() would also drain the global loads of the next
+// block that are in flight, i.e. undo the run-ahead.  sru_pack_bf16x2: two floats rounded to bf16, as one 32-bit word of an image store.
 __device__ __forceinline__ void sru_ring_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-constexpr int SRU_LW_THREADS = 256;
-constexpr int SRU_LW_FBF = 12, SRU_LW_FBB = 8;      // frames per block, forward / backward
-constexpr size_t sru_fwd_lw_lds() { return (size_t)3 * SRU_LW_FBF * 4 * 64 * sizeof(float); }
-constexpr size_t sru_bwd_lw_lds() { return (size_t)(3 * SRU_LW_FBB * 7 * 64 + 2 * SRU_LW_FBB * 4 * 64) * sizeof(float); }   // in ring + (B16OUT) out ring
-
-// grid = ceil(B*ncols / 64) workgroups of 256
-__global__ __launch_bounds__(SRU_LW_THREADS) void sru_fwd_lw_kernel(const SruArgs a) {
-  constexpr int FB = SRU_LW_FBF;
-  extern __shared__ __attribute__((aligned(16))) float ring[];      // [3][FB][4][64]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ncols = a.H * a.dirs;
-  const long gid0 = (long)blockIdx.x * 64 + lane;
-  const bool valid = gid0 < (long)a.B * ncols;
-  const long gid = valid ? gid0 : 0;
-  const int col = (int)(gid % ncols), b = (int)(gid / ncols);
-  const bool flip = col >= a.H;
-  const int T = a.T, k = a.k;
-  const int nblk = (T + FB - 1) / FB;
-  const float* Ub = a.U + (long)b * T * a.ldu + (long)col * k;
-  const float* xb = a.x + (long)b * T * a.ldx + col;
-  if (wave > 0) {
-    const int l = wave - 1;
-    float v[FB][4];
-    auto request = [&](int blk) {
-#pragma unroll
-      for (int q = 0; q < FB; ++q) {
-        const int tt = min(blk * FB + q, T - 1);
-        const int t = flip ? T - 1 - tt : tt;
-        const float* u = Ub + (long)t * a.ldu;
-        v[q][0] = u[0]; v[q][1] = u[1]; v[q][2] = u[2];
-        v[q][3] = k == 3 ? xb[(long)t * a.ldx] : u[3];
-      }
-    };
-    auto deposit = [&](int slot) {
-      float* r = ring + (size_t)slot * FB * 4 * 64 + lane;
-#pragma unroll
-      for (int q = 0; q < FB; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r[(q * 4 + j) * 64] = v[q][j];
-    };
-    if (l < nblk) request(l);
-    if (l == 0) { deposit(0); if (3 < nblk) request(3); }
-    for (int i = 0; i < nblk; ++i) {
-      sru_ring_barrier();
-      const int kb = i + 1;                 // the block the recurrence reads next
-      if (kb < nblk && kb % 3 == l) { deposit(l); if (kb + 3 < nblk) request(kb + 3); }
-    }
-    return;
-  }
-  const float bf = a.bias[col], br = a.bias[ncols + col];
-  const float mk = sru_mask(a, b, col);
-  float* hb = a.h + (long)b * T * ncols + col;
-  float* cb = a.c + (long)b * T * ncols + col;
-  float c = 0.f;
-  for (int i = 0; i < nblk; ++i) {
-    sru_ring_barrier();
-    const float* r = ring + (size_t)(i % 3) * FB * 4 * 64 + lane;
-    float fg[FB], rg[FB];
-#pragma unroll
-    for (int q = 0; q < FB; ++q) { fg[q] = fast_sigmoid(r[(q * 4 + 1) * 64] + bf); rg[q] = fast_sigmoid(r[(q * 4 + 2) * 64] + br); }
-#pragma unroll
-    for (int q = 0; q < FB; ++q) {
-      const int tt = i * FB + q;
-      if (tt < T) {
-        const int t = flip ? T - 1 - tt : tt;
-        const float u0 = r[(q * 4 + 0) * 64], xp = r[(q * 4 + 3) * 64];
-        const SruFwdOut o = sru_fwd_frame(u0, fg[q], rg[q], xp, c, mk, a.act);
-        c = o.c;
-        if (valid) {
-          hb[(long)t * ncols] = o.h;
-          cb[(long)t * ncols] = c;
-        }
-      }
-    }
-  }
-}
-
 __device__ __forceinline__ unsigned sru_pack_bf16x2(float lo, float hi) {
   return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)lo) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
-}
-// B16OUT: dU as bf16 images.  The recurrence wave leaves a block's dU (8 frames x k values x 64 columns, float32) in a 2-slot LDS
-// ring; during the next block the three loader waves -- which have issue slots to spare -- round it to bf16 and write both images
-// with 16-byte stores: one chunk of the row-major image (8 consecutive gate columns of one frame) and one of the transposed image
-// (8 consecutive frames of one gate column) per lane.  The recurrence wave issues no dU store at all.
-template <bool B16OUT>
-__global__ __launch_bounds__(SRU_LW_THREADS) void sru_bwd_lw_kernel(const SruArgs a) {
-  constexpr int FB = SRU_LW_FBB;
-  static_assert(FB == 8, "a transposed-image chunk is 8 frames");
-  extern __shared__ __attribute__((aligned(16))) float ring[];      // [3][FB][7][64]: u0, u1, u2, x', c of the predecessor frame, dh, highway gradient
-  float* oring = ring + 3 * FB * 7 * 64;                             // B16OUT: [2][FB][4][64] dU of the block just walked
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ncols = a.H * a.dirs;
-  const long gid0 = (long)blockIdx.x * 64 + lane;
-  const bool valid = gid0 < (long)a.B * ncols;
-  const long gid = valid ? gid0 : 0;
-  const int col = (int)(gid % ncols), b = (int)(gid / ncols);
-  const bool flip = col >= a.H;
-  const int T = a.T, k = a.k;
-  const int nblk = (T + FB - 1) / FB;
-  const float* Ub = a.U + (long)b * T * a.ldu + (long)col * k;
-  const float* xb = a.x + (long)b * T * a.ldx + col;
-  const float* cb = a.c + (long)b * T * ncols + col;
-  const float* dhb = a.dh + (long)b * T * ncols + col;
-  const float* upb = a.up_add ? a.up_add + (long)b * T * a.ld_up_add + col : nullptr;
-  if (wave > 0) {
-    const int l = wave - 1;
-    float v[FB][7];
-    auto request = [&](int blk) {
-#pragma unroll
-      for (int q = 0; q < FB; ++q) {
-        const int tt = max(T - 1 - (blk * FB + q), 0);     // forward-order index, descending
-        const int t = flip ? T - 1 - tt : tt;
-        const int tp = flip ? t + 1 : t - 1;               // frame of c_{tt-1}
-        const float* u = Ub + (long)t * a.ldu;
-        v[q][0] = u[0]; v[q][1] = u[1]; v[q][2] = u[2];
-        v[q][3] = k == 3 ? xb[(long)t * a.ldx] : u[3];
-        v[q][4] = tt > 0 ? cb[(long)min(max(tp, 0), T - 1) * ncols] : 0.f;
-        v[q][5] = dhb[(long)t * ncols];
-        v[q][6] = upb ? upb[(long)t * a.ld_up_add] : 0.f;
-      }
-    };
-    auto deposit = [&](int slot) {
-      float* r = ring + (size_t)slot * FB * 7 * 64 + lane;
-#pragma unroll
-      for (int q = 0; q < FB; ++q)
-#pragma unroll
-        for (int j = 0; j < 7; ++j) r[(q * 7 + j) * 64] = v[q][j];
-    };
-    // B16OUT: block j's dU -> bf16 images.  The workgroup's 64 columns are one sequence's (B * ncols % 64 == 0 and ncols % 64 == 0)
-    // and one direction's (H % 64 == 0): col0 = first column, frames t_lo .. t_lo + 7 ascending = walk order (flip) or reversed
-    const int col0 = (int)(((long)blockIdx.x * 64) % ncols);
-    auto store_block = [&](int j) {
-      const float* o = oring + (size_t)(j & 1) * FB * 4 * 64;
-      const int t_lo = flip ? FB * j : T - FB * (j + 1);
-      const long row0 = (long)b * T + t_lo;
-      const int nchunk = FB * 8 * k;                       // 16-byte chunks of either image: 8 frames x (64 k / 8), resp. 64 k gate columns
-      for (int c = l * 64 + lane; c < nchunk; c += 192) {
-        {   // row-major: frame f (ascending), chunk cc of its 64 k values
-          const int f = c / (8 * k), cc = c % (8 * k), q = flip ? f : FB - 1 - f;
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { const int idx = 8 * cc + e; v[e] = o[(q * 4 + idx % k) * 64 + idx / k]; }
-          uint4 w;
-          w.x = sru_pack_bf16x2(v[0], v[1]); w.y = sru_pack_bf16x2(v[2], v[3]); w.z = sru_pack_bf16x2(v[4], v[5]); w.w = sru_pack_bf16x2(v[6], v[7]);
-          *reinterpret_cast<uint4*>(a.dU_b + (row0 + f) * a.ld_dub + (long)col0 * k + 8 * cc) = w;
-        }
-        {   // transposed: gate column gc = c (local column c / k, value c % k), its 8 frames ascending
-          const int lc = c / k, jv = c % k;
-          float v[8];
-#pragma unroll
-          for (int f = 0; f < 8; ++f) v[f] = o[((flip ? f : FB - 1 - f) * 4 + jv) * 64 + lc];
-          uint4 w;
-          w.x = sru_pack_bf16x2(v[0], v[1]); w.y = sru_pack_bf16x2(v[2], v[3]); w.z = sru_pack_bf16x2(v[4], v[5]); w.w = sru_pack_bf16x2(v[6], v[7]);
-          *reinterpret_cast<uint4*>(a.dU_bt + ((long)(col0 + lc) * k + jv) * a.ld_dubt + row0) = w;
-        }
-      }
-    };
-    if (l < nblk) request(l);
-    if (l == 0) { deposit(0); if (3 < nblk) request(3); }
-    for (int i = 0; i < nblk; ++i) {
-      sru_ring_barrier();
-      if (B16OUT && i > 0) store_block(i - 1);
-      const int kb = i + 1;
-      if (kb < nblk && kb % 3 == l) { deposit(l); if (kb + 3 < nblk) request(kb + 3); }
-    }
-    if (B16OUT) { sru_ring_barrier(); store_block(nblk - 1); }
-    return;
-  }
-  const float bf = a.bias[col], br = a.bias[ncols + col];
-  const float mk = sru_mask(a, b, col);
-  const float up_mul = a.up_mul ? a.up_mul[(long)b * ncols + col] : 1.f;
-  float* dUb = B16OUT ? nullptr : a.dU + (long)b * T * a.ldu + (long)col * k;
-  float* dxb = a.dx ? a.dx + (long)b * T * a.lddx + col : nullptr;
-  float dc = 0.f, dbf = 0.f, dbr = 0.f;
-  float c_here = cb[(long)(flip ? 0 : T - 1) * ncols];      // cell state of the first frame of the walk
-  for (int i = 0; i < nblk; ++i) {
-    sru_ring_barrier();
-    const float* r = ring + (size_t)(i % 3) * FB * 7 * 64 + lane;
-    float fg[FB], rg[FB];
-#pragma unroll
-    for (int q = 0; q < FB; ++q) { fg[q] = fast_sigmoid(r[(q * 7 + 1) * 64] + bf); rg[q] = fast_sigmoid(r[(q * 7 + 2) * 64] + br); }
-#pragma unroll
-    for (int q = 0; q < FB; ++q) {
-      const int tt = T - 1 - (i * FB + q);
-      if (tt < 0) continue;
-      const int t = flip ? T - 1 - tt : tt;
-      const float u0 = r[(q * 7 + 0) * 64], xp = r[(q * 7 + 3) * 64];
-      const float c_prev = r[(q * 7 + 4) * 64];
-      const float dh = fmaf(r[(q * 7 + 5) * 64], up_mul, r[(q * 7 + 6) * 64]);
-      const SruBwdOut o = sru_bwd_frame(u0, fg[q], rg[q], xp, c_here, c_prev, dh, dc, mk, a.act);
-      dc = o.dc;
-      if (B16OUT) {
-        float* od = oring + ((size_t)(i & 1) * FB + q) * 4 * 64 + lane;
-        od[0 * 64] = o.du0; od[1 * 64] = o.du1; od[2 * 64] = o.du2; od[3 * 64] = o.dxp;
-        if (k == 3) dxb[(long)t * a.lddx] = o.dxp;
-      } else if (valid) {
-        float* du = dUb + (long)t * a.ldu;
-        du[0] = o.du0; du[1] = o.du1; du[2] = o.du2;
-        if (k == 3) dxb[(long)t * a.lddx] = o.dxp; else du[3] = o.dxp;
-      }
-      dbf += o.du1; dbr += o.du2;
-      c_here = c_prev;
-    }
-  }
-  if (B16OUT) sru_ring_barrier();        // the last block's dU is in LDS: the loader waves write it out
-  if (valid) {
-    a.dbias_part[(long)b * 2 * ncols + col] = dbf;
-    a.dbias_part[(long)b * 2 * ncols + ncols + col] = dbr;
-  }
 }
 
 // The variational input-dropout mask of a layer as multipliers {0, 1/(1-p)}, [B][n]: drawn once per step (Philox, or the

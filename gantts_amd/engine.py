@@ -258,14 +258,13 @@ class StepEngine(object):
 
     def set_option(self, name, value):
         """Engine switches (results unchanged up to fp32 summation order): ``"lstm_persistent"``,
-        ``"lstm_fwd_units"``, ``"lstm_xcd_local"``, ``"split_first_layer"`` (conditioned D: x product once per D step),
-        ``"fused_optimizer"`` (combines + norm + clip + step in one launch); ``"matmul_bf16"`` switches the GEMMs to bf16 products
+        ``"lstm_fwd_units"``, ``"lstm_xcd_local"``, ``"split_first_layer"`` (conditioned D: x product once per D step);
+        ``"matmul_bf16"`` switches the GEMMs to bf16 products
         with float32 accumulation."""
         opts = {"lstm_persistent": L.OPT_LSTM_PERSISTENT,
                 "lstm_fwd_units": L.OPT_LSTM_FWD_UNITS, "lstm_xcd_local": L.OPT_LSTM_XCD_LOCAL,
                 "matmul_bf16": L.OPT_MATMUL_BF16, "split_first_layer": L.OPT_SPLIT_FIRST_LAYER,
-                "fused_optimizer": L.OPT_FUSED_OPTIMIZER, "side_overlap": L.OPT_SIDE_OVERLAP, "lstm_side": L.OPT_LSTM_SIDE,
-                "comm_d_one_msg": L.OPT_COMM_D_ONE_MSG, "comm_early_g": L.OPT_COMM_EARLY_G, "comm_group": L.OPT_COMM_GROUP,
+                "comm_d_one_msg": L.OPT_COMM_D_ONE_MSG, "comm_early_g": L.OPT_COMM_EARLY_G,
                 "comm_force": L.OPT_COMM_FORCE, "launch_riders": L.OPT_LAUNCH_RIDERS,
                 "comm_close_inline": L.OPT_COMM_CLOSE_INLINE, "poll_results": L.OPT_POLL_RESULTS,
                 "comm_tv_in_sums": L.OPT_COMM_TV_IN_SUMS, "comm_ipc": L.OPT_COMM_IPC, "fused_dstack": L.OPT_FUSED_DSTACK}

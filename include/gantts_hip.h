@@ -208,13 +208,8 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  * D step, shared by the real and the generated rows) + adv . W_adv^T instead of one product over a concatenated [x | adv] image
  * (train.py:254-256); 0 = the concatenated image.  Same sums up to float32 association. */
 #define GT_OPT_SPLIT_FIRST_LAYER 6
-/* GT_OPT_FUSED_OPTIMIZER (default 0): the fused single-GPU step closes a network's update with ONE launch (weight-gradient
- * combines + squared norm + clip + optimizer step behind a device-wide barrier) instead of three.  Same arithmetic; measured
- * SLOWER on MI355X (the barrier's wait costs more than two launch edges: cfg2 1.453 vs 1.411 ms), so it is off by default. */
-#define GT_OPT_FUSED_OPTIMIZER 7
 /* Schedule switches (defaults are the measured best; the GT_* environment variables of the same names only provide the default at
- * engine creation): GT_OPT_SIDE_OVERLAP (0; measured slower) small memory-bound kernels on a side stream under the products; GT_OPT_LSTM_SIDE
- * (removed in round 6: LSTM weight gradients beside the next layer's recurrence measured no gain; only the value 0 is accepted); GT_OPT_COMM_D_ONE_MSG (1) / _EARLY_G (1) / _GROUP (0) data-parallel
+ * engine creation; the ids 7, 8, 9 and 12 are retired and not reused): GT_OPT_COMM_D_ONE_MSG (1) / _EARLY_G (1) data-parallel
  * message schedule; GT_OPT_COMM_FORCE (0) issue the collectives with one rank as well (bench.py --force-dp, tests);
  * GT_OPT_LAUNCH_RIDERS (1) the fused single-GPU step's small reductions (valid-frame count, the head's scalars in the generator
  * step, the generator step's finalisation) ride as an extra workgroup of a neighbouring launch instead of launches of their own;
@@ -225,11 +220,8 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  * per G+D step instead of six): the backward pass runs on the unnormalised loss, 1 / Tv is applied by the optimizer kernel (the
  * gradient it writes back is the normalised, clipped one) and by the generator step where it adds the kept gradient;
  * GT_OPT_COMM_IPC (1) see gt_comm_ipc_* below. */
-#define GT_OPT_SIDE_OVERLAP 8
-#define GT_OPT_LSTM_SIDE 9
 #define GT_OPT_COMM_D_ONE_MSG 10
 #define GT_OPT_COMM_EARLY_G 11
-#define GT_OPT_COMM_GROUP 12
 #define GT_OPT_COMM_FORCE 13
 #define GT_OPT_LAUNCH_RIDERS 14
 #define GT_OPT_COMM_CLOSE_INLINE 15
@@ -246,7 +238,7 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
 int gt_set_option(gt_engine* e, int option, int value);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,
- * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_lw, head_vec, mlpg_small16, lstm_bt; the environment variables GT_<NAME>
+ * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_coop (its former name sru_lw, 0 / 1 / 2, is still accepted: 2 = 1), head_vec, lstm_bt; the environment variables GT_<NAME>
  * provide the initial values.  lstm_bt: sequences per batch tile of the persistent LSTM kernels, 0 (by shape), 8 or 16; any other
  * value is refused.  A forced tile still has to pass the co-residency check of the launch (else the per-step kernels run). */
 int gt_set_tuning(const char* name, int value);

@@ -2,8 +2,8 @@
 // communicator (gt_comm_init with world > 1, engine.hip) for real: RCCL itself refuses two ranks on one device, and
 // the build / GPU boxes have a single MI355X.  Selected with GT_RCCL_LIB=<path to this .so> (engine.hip: rccl_api()).
 //
-// Exports the seven symbols the engine binds: ncclGetUniqueId / CommInitRank / CommDestroy / AllReduce / GroupStart /
-// GroupEnd / GetErrorString.  The ranks meet in a POSIX shared-memory segment named after the unique id.  An all-reduce
+// Exports seven symbols, ncclGetUniqueId / CommInitRank / CommDestroy / AllReduce / GroupStart / GroupEnd / GetErrorString
+// (the engine binds all but the two Group calls).  The ranks meet in a POSIX shared-memory segment named after the unique id.  An all-reduce
 // honours the stream it is given:   D2H copy (async, pinned)  ->  host function on the stream: publish the rank's slot,
 // barrier, sum the slots IN RANK ORDER (every rank computes the same sum: replicas stay bit-identical), barrier
 // ->  H2D copy (async).  Nothing here is a product path; it only has to be correct and stream-ordered.

@@ -420,18 +420,15 @@ def test_pitched_x_is_accepted_by_every_network(name, options):
 
 
 @pytest.mark.parametrize("name", ["acoustic_mlp", "acoustic_mlp_dropout", "acoustic_chain_d", "acoustic_lstm"])
-def test_split_first_layer_and_fused_optimizer_match_the_plain_launches(name):
+def test_split_first_layer_matches_the_concatenated_image(name):
     """GT_OPT_SPLIT_FIRST_LAYER (x . W_x^T once per D step + adv . W_adv^T, weight gradient with the two halves summed in the
-    loader) and GT_OPT_FUSED_OPTIMIZER (combines + norm + clip + step behind a device-wide barrier) against the concatenated
-    [x | adv] image and the three-launch optimizer: the reference golden holds for BOTH settings (test_step_matches_reference_golden
-    runs the defaults); here the two settings are compared with each other at the same 1e-4, counts exactly, and the fused
-    optimizer alone must agree with the three launches to rounding (same arithmetic per element; the squared norm is the
-    same double-precision sum over a different partition, so the clip coefficient may differ in its last bit)."""
+    loader) against the concatenated [x | adv] image: the reference golden holds for BOTH settings
+    (test_step_matches_reference_golden runs the defaults); here the two settings are compared with each other at the same 1e-4,
+    counts exactly."""
     from hip_runner import run_hip_case
     case = C.CASES[name]
-    on = run_hip_case(case, engine_options={"split_first_layer": 1, "fused_optimizer": 1})
-    off = run_hip_case(case, engine_options={"split_first_layer": 0, "fused_optimizer": 0})
-    fused_only = run_hip_case(case, engine_options={"split_first_layer": 0, "fused_optimizer": 1})
+    on = run_hip_case(case, engine_options={"split_first_layer": 1})
+    off = run_hip_case(case, engine_options={"split_first_layer": 0})
     for k in off:
         if "scalars" in k:
             _close(on[k], off[k], msg=k)
@@ -441,7 +438,6 @@ def test_split_first_layer_and_fused_optimizer_match_the_plain_launches(name):
             _close_state(on[k], off[k], k)
         else:
             _close(on[k], off[k], msg=k)
-        _close(fused_only[k], off[k], rtol=2e-6, atol=1e-9, msg="fused optimizer " + k)
 
 
 @pytest.mark.parametrize("name,philox", [("acoustic_chain_d", False), ("acoustic_chain_d", True), ("acoustic_chain_d_uncond", False),
@@ -1133,38 +1129,13 @@ def test_bf16_storage_sru_step_tracks_the_float32_oracle():
             assert err < 8e-2, (tag + name, err)
 
 
-@pytest.mark.parametrize("name,bf16", [("acoustic_sru_at_size", 0), ("acoustic_sru_uni_k3_dropout", 0), ("vc_sru_multistream", 0),
-                                       ("acoustic_sru_at_size", 1), ("acoustic_sru_dropout", 1)])
-def test_sru_loader_wave_scans_equal_the_one_wave_scans_bit_for_bit(name, bf16):
-    """The SRU scans with loader waves (three frame blocks per column in flight through an LDS ring, sru_kernels.hip.h)
-    against the one-wave scans (gt_set_tuning("sru_lw", 0)): same arithmetic in the same order, so a whole G+D step -- outputs, scalars,
-    parameters after the update, optimizer state -- must agree bit for bit (widths 6 x 512 bidirectional with both
-    dropouts, a unidirectional tanh k = 3 net, a 3-stream net with ragged T = 19: partial blocks, partial workgroups).
-    Also with bf16 storage (the scans are float32 there too; the products around them read bf16 images of their results)."""
-    from hip_runner import run_hip_case
-    case = C.ORACLE_ONLY_CASES[name]
-    from gantts_amd import _lib as L
-    opts = {"matmul_bf16": 1} if bf16 else None
-    try:
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 0))
-        ref = run_hip_case(case, engine_options=opts)
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 1))
-        got = run_hip_case(case, engine_options=opts)
-    finally:
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 2))      # the default: cooperative block scans
-    assert set(got) == set(ref)
-    for k in ref:
-        a, b = np.asarray(got[k]), np.asarray(ref[k])
-        assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True), k
-
-
 @pytest.mark.parametrize("waves", [8, 4])
 @pytest.mark.parametrize("name,bf16", [("acoustic_sru_at_size", 0), ("acoustic_sru_uni_k3_dropout", 0), ("vc_sru_multistream", 0), ("acoustic_sru_uni_k3", 0),
                                        ("acoustic_sru_bi_saturated", 0), ("acoustic_sru_at_size", 1), ("acoustic_sru_dropout", 1)])
 def test_sru_cooperative_block_scans_match_the_sequential_scans(name, bf16, waves):
     """The cooperative block scans (sru_cs_kernels.hip.h, the default: every wave of a workgroup walks eight frames of a block from a
     zero state, the waves' composites (prod f, end state) are combined through LDS, each wave corrects its frames by prefix
-    product x incoming state) against the sequential loader-wave scans: the same linear recurrence under another association of the
+    product x incoming state) against the sequential one-wave scans (sru_kernels.hip.h, gt_set_tuning("sru_coop", 0)): the same linear recurrence under another association of the
     products, so a whole G+D step agrees to rounding -- 1e-4 like every float32 comparison of the suite (bf16 storage: the products
     around the scans round their operands to bf16, where a last-bit difference of a scan output can flip a rounding: 2e-2) --
     forward and backward, both directions, k = 3 and 4, tanh / relu, saturated gates, ragged T (partial blocks: frames past T are
@@ -1174,13 +1145,13 @@ def test_sru_cooperative_block_scans_match_the_sequential_scans(name, bf16, wave
     from gantts_amd import _lib as L
     opts = {"matmul_bf16": 1} if bf16 else None
     try:
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 1))
+        L.check(L.lib.gt_set_tuning(b"sru_coop", 0))
         ref = run_hip_case(case, engine_options=opts)
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 2))
+        L.check(L.lib.gt_set_tuning(b"sru_coop", 1))
         L.check(L.lib.gt_set_tuning(b"sru_cs_waves", waves))      # both instantiations (8 / 4 waves per 64 columns) on every shape
         got = run_hip_case(case, engine_options=opts)
     finally:
-        L.check(L.lib.gt_set_tuning(b"sru_lw", 2))
+        L.check(L.lib.gt_set_tuning(b"sru_coop", 1))
         L.check(L.lib.gt_set_tuning(b"sru_cs_waves", 0))
     assert set(got) == set(ref)
     rtol = 2e-2 if bf16 else RTOL

@@ -78,8 +78,8 @@ template <int KIND, int AMODE>
 static void launch_old(GemmArgs g, int nslab) {
   const size_t lds = gemm_lds_bytes<KIND, 64, 64>();
   static bool once = false;
-  if (!once) { CK(hipFuncSetAttribute((const void*)gemm_f32_kernel<KIND, 64, 64, true, true, PREC_F32, 32, AMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
-  hipLaunchKernelGGL((gemm_f32_kernel<KIND, 64, 64, true, true, PREC_F32, 32, AMODE>), dim3(g.n_tiles_m * g.n_tiles_n * nslab), dim3(256), lds, 0, g);
+  if (!once) { CK(hipFuncSetAttribute((const void*)gemm_f32_kernel<KIND, 64, 64, true, true, PREC_F32, AMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
+  hipLaunchKernelGGL((gemm_f32_kernel<KIND, 64, 64, true, true, PREC_F32, AMODE>), dim3(g.n_tiles_m * g.n_tiles_n * nslab), dim3(256), lds, 0, g);
 }
 template <int KIND, int AMODE>
 static void launch_new(GemmArgs g, int nslab) {
