@@ -29,6 +29,8 @@ GEMM_PATH_SLOTS = 588                                                   # gt_gem
 GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
 ARCH_MLP, ARCH_IN2OUT, ARCH_LSTM, ARCH_SRU, ARCH_IN2OUT_RNN = 0, 1, 2, 3, 4
 OPT_ADAGRAD, OPT_ADAM = 0, 1
+OPT_SGD, OPT_RMSPROP, OPT_ADADELTA, OPT_ADAMW, OPT_ADAMAX = 2, 3, 4, 5, 6
+OPTF_NESTEROV, OPTF_CENTERED, OPTF_AMSGRAD, OPTF_BUFFER_LIVE = 1, 2, 4, 8      # OptimDescEx.flags
 MAX_STREAMS = 8
 COMM_ID_BYTES = 128
 
@@ -58,6 +60,13 @@ class OptimDesc(C.Structure):
                 ("lr_decay", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
                 ("max_grad_norm", C.c_float), ("step", C.c_int64),
                 ("state0", C.c_void_p), ("state1", C.c_void_p)]
+
+
+class OptimDescEx(C.Structure):
+    _fields_ = ([("kind", C.c_int32), ("flags", C.c_uint32)]
+                + [(n, C.c_double) for n in ("lr", "weight_decay", "eps", "lr_decay", "beta1", "beta2", "momentum", "dampening", "alpha")]
+                + [("max_grad_norm", C.c_float), ("reserved_", C.c_int32), ("step", C.c_int64),
+                   ("state0", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p)])
 
 
 class DResult(C.Structure):
@@ -93,6 +102,8 @@ SIGNATURES = {
     "gt_engine_destroy": (None, [_P]),
     "gt_bind_model": (_I, [_P, _I, C.POINTER(ModelDesc)]),
     "gt_bind_optimizer": (_I, [_P, _I, C.POINTER(OptimDesc)]),
+    "gt_bind_optimizer_ex": (_I, [_P, _I, C.POINTER(OptimDescEx)]),
+    "gt_op_optim_step": (_I, [C.POINTER(OptimDescEx), _P, _P, _L, _P, C.POINTER(_F), _P]),
     "gt_set_training": (_I, [_P, _I, _I]),
     "gt_set_lr": (_I, [_P, _I, _F]),
     "gt_get_optimizer_step": (_I, [_P, _I, C.POINTER(_L)]),

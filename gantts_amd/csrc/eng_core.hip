@@ -316,8 +316,27 @@ extern "C" int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* od
   if (!n.d.grads) return fail(GT_ERR_INVALID, "model was bound without a grads buffer");
   if (od->kind != GT_OPT_ADAGRAD && od->kind != GT_OPT_ADAM) return fail(GT_ERR_INVALID, "unknown optimizer kind");
   if (!od->state0 || (od->kind == GT_OPT_ADAM && !od->state1)) return fail(GT_ERR_INVALID, "optimizer state buffer is null");
+  gt_optim_desc_ex x;
+  memset(&x, 0, sizeof(x));
+  x.kind = od->kind; x.lr = od->lr; x.weight_decay = od->weight_decay; x.eps = od->eps; x.lr_decay = od->lr_decay;
+  x.beta1 = od->beta1; x.beta2 = od->beta2; x.max_grad_norm = od->max_grad_norm; x.step = od->step;
+  x.state0 = od->state0; x.state1 = od->state1;
+  n.od = x;
+  n.step = n.bound_step = od->step;
+  n.buf_live = false;
+  n.has_opt = true;
+  return GT_OK;
+}
+extern "C" int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_ex* od) {
+  if (!e || !od || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
+  Net& n = e->net[role];
+  if (!n.bound) return fail(GT_ERR_STATE, "bind the model before its optimizer");
+  if (!n.d.grads) return fail(GT_ERR_INVALID, "model was bound without a grads buffer");
+  CHK(optim_check_desc(od));
   n.od = *od;
-  n.step = od->step;
+  n.od.lr = (double)(float)od->lr;      // what gt_set_lr would store
+  n.step = n.bound_step = od->step;
+  n.buf_live = (od->flags & GT_OPTF_BUFFER_LIVE) != 0;
   n.has_opt = true;
   return GT_OK;
 }
@@ -564,7 +583,13 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemset(e->d_fault, 0, 64));
-  for (int r = 0; r < 2; ++r) { e->net[r].step -= (long)e->h_fault[2 + r]; if (e->net[r].step < 0) e->net[r].step = 0; }
+  for (int r = 0; r < 2; ++r) {
+    Net& n = e->net[r];
+    n.step -= (long)e->h_fault[2 + r];
+    if (n.step < 0) n.step = 0;
+    // every update since the bind was skipped: SGD's momentum_buffer is as live as the bind said, not more
+    if (e->h_fault[2 + r] && n.step <= n.bound_step) n.buf_live = (n.od.flags & GT_OPTF_BUFFER_LIVE) != 0;
+  }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   e->g_pass_valid = false; e->leak_pending = false; e->fake_cat_valid = false; e->adv2_fake_ok = false; e->cxd_src = nullptr;
   e->d_begin_done = e->g_begin_done = false; e->early_done = false;

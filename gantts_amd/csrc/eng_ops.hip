@@ -314,3 +314,141 @@ extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
   if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_f32: %s", hipGetErrorString(err));
   return GT_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// the optimizer family: validation, the step's scalars, the launch (engine and stand-alone operator alike)
+// ------------------------------------------------------------------------------------------
+int optim_check_desc(const gt_optim_desc_ex* od) {
+  const int k = od->kind;
+  if (k < GT_OPT_ADAGRAD || k > GT_OPT_ADAMAX) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", k);
+  const unsigned allowed = GT_OPTF_BUFFER_LIVE | (k == GT_OPT_SGD ? GT_OPTF_NESTEROV : 0u) | (k == GT_OPT_RMSPROP ? GT_OPTF_CENTERED : 0u) |
+                           ((k == GT_OPT_ADAM || k == GT_OPT_ADAMW) ? GT_OPTF_AMSGRAD : 0u);
+  if (od->flags & ~allowed) return fail(GT_ERR_INVALID, "optimizer flags 0x%x do not belong to kind %d", od->flags, k);
+  // the checks of torch.optim's constructors (written so that a NaN fails them)
+  if (!(od->lr >= 0.0)) return fail(GT_ERR_INVALID, "Invalid learning rate: %g", od->lr);
+  if (!(od->weight_decay >= 0.0)) return fail(GT_ERR_INVALID, "Invalid weight_decay value: %g", od->weight_decay);
+  if (k != GT_OPT_SGD && !(od->eps >= 0.0)) return fail(GT_ERR_INVALID, "Invalid epsilon value: %g", od->eps);
+  if (k == GT_OPT_ADAGRAD && !(od->lr_decay >= 0.0)) return fail(GT_ERR_INVALID, "Invalid lr_decay value: %g", od->lr_decay);
+  if (k == GT_OPT_ADAM || k == GT_OPT_ADAMW || k == GT_OPT_ADAMAX) {
+    if (!(od->beta1 >= 0.0 && od->beta1 < 1.0)) return fail(GT_ERR_INVALID, "Invalid beta parameter at index 0: %g", od->beta1);
+    if (!(od->beta2 >= 0.0 && od->beta2 < 1.0)) return fail(GT_ERR_INVALID, "Invalid beta parameter at index 1: %g", od->beta2);
+  }
+  if ((k == GT_OPT_SGD || k == GT_OPT_RMSPROP) && !(od->momentum >= 0.0)) return fail(GT_ERR_INVALID, "Invalid momentum value: %g", od->momentum);
+  if (k == GT_OPT_SGD && (od->flags & GT_OPTF_NESTEROV) && (od->momentum <= 0.0 || od->dampening != 0.0))
+    return fail(GT_ERR_INVALID, "Nesterov momentum requires a momentum and zero dampening");
+  if (k == GT_OPT_RMSPROP && !(od->alpha >= 0.0)) return fail(GT_ERR_INVALID, "Invalid alpha value: %g", od->alpha);
+  if (k == GT_OPT_ADADELTA && !(od->alpha >= 0.0 && od->alpha <= 1.0)) return fail(GT_ERR_INVALID, "Invalid rho value: %g", od->alpha);
+  if (od->step < 0) return fail(GT_ERR_INVALID, "negative step count");
+  const bool mom = (k == GT_OPT_SGD || k == GT_OPT_RMSPROP) && od->momentum != 0.0;
+  const bool need0 = k != GT_OPT_SGD || mom;
+  const bool need1 = k == GT_OPT_RMSPROP ? mom : k != GT_OPT_ADAGRAD && k != GT_OPT_SGD;
+  const bool need2 = (od->flags & (GT_OPTF_CENTERED | GT_OPTF_AMSGRAD)) != 0;
+  if ((need0 && !od->state0) || (need1 && !od->state1) || (need2 && !od->state2))
+    return fail(GT_ERR_INVALID, "optimizer state buffer is null (kind %d, flags 0x%x needs state%s%s%s)", k, od->flags, need0 ? " 0" : "",
+                need1 ? " 1" : "", need2 ? " 2" : "");
+  return GT_OK;
+}
+
+// The scalars of update number `step` (1-based), formed in double from the double hyper-parameters and rounded to float
+// once -- python arithmetic followed by a Scalar -> float conversion in torch's single-tensor code paths.
+static OptimSpecEx optim_spec_ex(const gt_optim_desc_ex& od, long step, bool buf_live) {
+  OptimSpecEx o;
+  memset(&o, 0, sizeof(o));
+  const double lr = od.lr;
+  o.max_norm = od.max_grad_norm; o.wd = (float)od.weight_decay; o.eps = (float)od.eps;
+  o.neg_step = (float)-lr;
+  o.live = buf_live ? 1 : 0;
+  switch (od.kind) {
+    case GT_OPT_SGD:
+      o.mu = (float)od.momentum; o.omd = (float)(1.0 - od.dampening);
+      break;
+    case GT_OPT_RMSPROP:
+      o.mu = (float)od.momentum; o.a = (float)od.alpha; o.oma = (float)(1.0 - od.alpha);
+      break;
+    case GT_OPT_ADADELTA:
+      o.a = (float)od.alpha; o.oma = (float)(1.0 - od.alpha);
+      break;
+    case GT_OPT_ADAM: case GT_OPT_ADAMW:
+      o.w1 = (float)(1.0 - od.beta1); o.a = (float)od.beta2; o.oma = (float)(1.0 - od.beta2);
+      o.neg_step = (float)-(lr / (1.0 - pow(od.beta1, (double)step)));
+      o.bc2_sqrt = (float)sqrt(1.0 - pow(od.beta2, (double)step));
+      o.decay = (float)(1.0 - lr * od.weight_decay);
+      break;
+    case GT_OPT_ADAMAX:
+      o.w1 = (float)(1.0 - od.beta1); o.a = (float)od.beta2;
+      o.neg_step = (float)-(lr / (1.0 - pow(od.beta1, (double)step)));
+      break;
+  }
+  return o;
+}
+
+int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, float* params, float* grads, long n, const double* part,
+                      int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s) {
+  const dim3 grid((unsigned)std::min<long>(1024, cdiv(n, RED_THREADS))), block(RED_THREADS);
+  const bool ams = (od.flags & GT_OPTF_AMSGRAD) != 0;
+  if (od.kind == GT_OPT_ADAGRAD || (od.kind == GT_OPT_ADAM && !ams)) {      // the two kinds of gt_bind_optimizer: their own kernel
+    OptimSpec o;
+    o.kind = od.kind; o.lr = (float)od.lr; o.weight_decay = (float)od.weight_decay; o.eps = (float)od.eps; o.lr_decay = (float)od.lr_decay;
+    o.beta1 = (float)od.beta1; o.beta2 = (float)od.beta2; o.step = step; o.max_norm = od.max_grad_norm;
+    hipLaunchKernelGGL(optim_step_kernel, grid, block, 0, s, params, grads, od.state0, od.state1, n, part, n_partial, norm2_out, o,
+                       fault_dev, fault_host, skipped_host, gscale);
+    LAUNCH_CHECK();
+    return GT_OK;
+  }
+  const OptimSpecEx o = optim_spec_ex(od, step, buf_live);
+#define GT_OPTIM_LAUNCH(KIND, F)                                                                                                      \
+  hipLaunchKernelGGL((optim_step_ex_kernel<KIND, F>), grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, \
+                     n_partial, norm2_out, o, fault_dev, fault_host, skipped_host, gscale)
+  const bool mom = od.momentum != 0.0, nest = (od.flags & GT_OPTF_NESTEROV) != 0, cen = (od.flags & GT_OPTF_CENTERED) != 0;
+  switch (od.kind) {
+    case GT_OPT_SGD:
+      if (!mom) GT_OPTIM_LAUNCH(OPTK_SGD, 0u);
+      else if (!nest) GT_OPTIM_LAUNCH(OPTK_SGD, OPTI_MOMENTUM);
+      else GT_OPTIM_LAUNCH(OPTK_SGD, OPTI_MOMENTUM | OPTI_NESTEROV);
+      break;
+    case GT_OPT_RMSPROP:
+      if (!mom && !cen) GT_OPTIM_LAUNCH(OPTK_RMSPROP, 0u);
+      else if (!mom) GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_CENTERED);
+      else if (!cen) GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_MOMENTUM);
+      else GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_MOMENTUM | OPTI_CENTERED);
+      break;
+    case GT_OPT_ADADELTA: GT_OPTIM_LAUNCH(OPTK_ADADELTA, 0u); break;
+    case GT_OPT_ADAM: GT_OPTIM_LAUNCH(OPTK_ADAM, OPTI_AMSGRAD); break;
+    case GT_OPT_ADAMW:
+      if (ams) GT_OPTIM_LAUNCH(OPTK_ADAMW, OPTI_AMSGRAD);
+      else GT_OPTIM_LAUNCH(OPTK_ADAMW, 0u);
+      break;
+    case GT_OPT_ADAMAX: GT_OPTIM_LAUNCH(OPTK_ADAMAX, 0u); break;
+    default: return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
+  }
+#undef GT_OPTIM_LAUNCH
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+
+extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
+                                float* grad_norm_out, void* stream) {
+  if (!desc || !params || !grads || n < 1) return fail(GT_ERR_INVALID, "bad argument");
+  CHK(optim_check_desc(desc));
+  hipStream_t s = (hipStream_t)stream;
+  static thread_local Scratch tls_ws;     // [0, 512) squared-norm partials, [512] the squared norm
+  CHK(tls_ws.ensure(513 * sizeof(double)));
+  double* part = (double*)tls_ws.p;
+  gt_optim_desc_ex od = *desc;
+  od.lr = (double)(float)desc->lr;        // as gt_bind_optimizer_ex keeps it
+  // the engine's fallback branch (optimizer_step, eng_step.hip): partials, then clip + update
+  const int nblk = (int)std::min<long>(512, cdiv(n, RED_THREADS * 4));
+  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, (const float*)grads, (long)n, part);
+  LAUNCH_CHECK();
+  CHK(launch_optim_step(od, (long)desc->step + 1, (desc->flags & GT_OPTF_BUFFER_LIVE) != 0, params, grads, (long)n, part, nblk,
+                        grad_norm_out ? part + 512 : (double*)nullptr, (const unsigned int*)nullptr, (unsigned int*)nullptr,
+                        (unsigned int*)nullptr, gscale, s));
+  if (grad_norm_out) {
+    double norm2 = 0.0;
+    HIPCHK(hipMemcpyAsync(&norm2, part + 512, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *grad_norm_out = (float)sqrt(norm2);
+  }
+  return GT_OK;
+}

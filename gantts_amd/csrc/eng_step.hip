@@ -634,9 +634,6 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   const long np = n.d.n_params;
   CHK(e->partial.ensure(4096 * sizeof(double)));
   double* part = e->partial.as<double>() + 2048;
-  OptimSpec o;
-  o.kind = n.od.kind; o.lr = n.od.lr; o.weight_decay = n.od.weight_decay; o.eps = n.od.eps; o.lr_decay = n.od.lr_decay;
-  o.beta1 = n.od.beta1; o.beta2 = n.od.beta2; o.step = n.step + 1; o.max_norm = n.od.max_grad_norm;
   unsigned int* skipped = e->h_fault_dev ? e->h_fault_dev + 1 + role : (unsigned int*)nullptr;
   // the discriminator's gradient of a GT_OPT_COMM_TV_IN_SUMS step is that of the unnormalised loss: x 1 / Tv in the update kernel
   const float* gscale = (role == GT_ROLE_D && e->d_unnorm) ? &e->sc()->inv_tv : (const float*)nullptr;
@@ -680,10 +677,9 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
       const int n_partial = sd.blocks + rest_blocks;
       sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; sd.active = false;
       n.step += 1;
-      const int grid = (int)std::min<long>(1024, cdiv(np, RED_THREADS));
-      hipLaunchKernelGGL(optim_step_kernel, dim3(grid), dim3(RED_THREADS), 0, s, n.d.params, n.d.grads, n.od.state0, n.od.state1, np,
-                         part, n_partial, norm2_out, o, (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale);
-      LAUNCH_CHECK();
+      CHK(launch_optim_step(n.od, n.step, n.buf_live, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
+                            (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
+      n.buf_live = true;
       return GT_OK;
     }
   }
@@ -693,10 +689,9 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, n.d.grads, np, part);
   LAUNCH_CHECK();
   n.step += 1;
-  const int grid = (int)std::min<long>(1024, cdiv(np, RED_THREADS));
-  hipLaunchKernelGGL(optim_step_kernel, dim3(grid), dim3(RED_THREADS), 0, s, n.d.params, n.d.grads, n.od.state0, n.od.state1, np,
-                     part, nblk, norm2_out, o, (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale);
-  LAUNCH_CHECK();
+  CHK(launch_optim_step(n.od, n.step, n.buf_live, n.d.params, n.d.grads, np, part, nblk, norm2_out,
+                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
+  n.buf_live = true;
   return GT_OK;
 }
 

@@ -169,8 +169,10 @@ struct Net {
   bool training = true;
   bool grads_dirty = false;      // false after zero_grad: next backward overwrites instead of accumulating
   bool has_opt = false;
-  gt_optim_desc od;
+  gt_optim_desc_ex od;            // gt_bind_optimizer widens its descriptor to this one
   long step = 0;
+  long bound_step = 0;            // `step` at the bind
+  bool buf_live = false;          // SGD: momentum_buffer holds a value (GT_OPTF_BUFFER_LIVE at the bind, or an update since)
   // injected dropout masks [pass][layer]
   const float* inj[3][16];
   Net() { memset(inj, 0, sizeof(inj)); }
@@ -332,6 +334,12 @@ struct gt_engine {
 // ------------------------------------------------------------------------------------------
 int check_common(gt_engine* e, int B, int T);
 int fault_seen(gt_engine* e);
+// the optimizer family (eng_ops.hip): validation shared by gt_bind_optimizer_ex / gt_op_optim_step, and the one place that
+// launches the fused clip + update kernel.  `step`: 1-based count of THIS update; `part`: n_partial squared-norm partials.
+int optim_check_desc(const gt_optim_desc_ex* od);
+int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, float* params, float* grads, long n, const double* part,
+                      int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s);
 gt::DropoutSpec philox_site_spec(gt_engine* e, int role, int pass, int layer, uint64_t step, float p, long half_rows = 0);
 gt::DropoutSpec drop_spec(gt_engine* e, int role, int pass, int layer, const float* stacked_mask, int ld, long half_rows = 0);
 

@@ -1342,6 +1342,164 @@ static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The rest of torch.optim's family behind the same clip: SGD, RMSprop, Adadelta, Adam / AdamW with amsgrad, AdamW, Adamax.
+// One instantiation per (kind, flags): nothing is decided per element, and optim_step_kernel above (Adagrad, Adam: the
+// headline step) is not touched.  Each rule restates torch's single-tensor code path (torch/optim/<name>.py,
+// _single_tensor_<name>, foreach=False), operation by operation in float32; the step's scalars are formed on the host in
+// double and rounded once, as python does there (optim_spec_ex, engine_internal.hip.h).
+// HBM traffic: 16 B per parameter (p and g, read and written) + 8 B per live state buffer, up to three of them (40 B).
+// ---------------------------------------------------------------------------------------
+enum OptimKind { OPTK_ADAGRAD = 0, OPTK_ADAM = 1, OPTK_SGD = 2, OPTK_RMSPROP = 3, OPTK_ADADELTA = 4, OPTK_ADAMW = 5, OPTK_ADAMAX = 6 };
+constexpr unsigned OPTI_NESTEROV = 1u, OPTI_CENTERED = 2u, OPTI_AMSGRAD = 4u;   // GT_OPTF_* of the C ABI
+constexpr unsigned OPTI_MOMENTUM = 16u;                                         // momentum != 0 (SGD, RMSprop): decided by the host
+struct OptimSpecEx {
+  float max_norm;      // clip threshold; <= 0 disables clipping
+  float wd;            // weight_decay
+  float eps;
+  float neg_step;      // -lr (SGD, RMSprop, Adadelta), -lr / (1 - beta1^t) (Adam, AdamW, Adamax)
+  float decay;         // AdamW: 1 - lr * weight_decay
+  float mu;            // momentum
+  float omd;           // SGD: 1 - dampening
+  float a, oma;        // RMSprop alpha, Adadelta rho, Adam / Adamax beta2, and one minus it
+  float w1;            // Adam / Adamax: 1 - beta1 (the lerp weight)
+  float bc2_sqrt;      // Adam: sqrt(1 - beta2^t)
+  int live;            // SGD: momentum_buffer holds a value (not the first update)
+};
+// which of the three state streams a (kind, flags) pair reads and writes
+template <int KIND, unsigned F> struct OptimStreams {
+  static constexpr bool s0 = KIND != OPTK_SGD || (F & OPTI_MOMENTUM) != 0;
+  static constexpr bool s1 = KIND == OPTK_SGD ? false : KIND == OPTK_RMSPROP ? (F & OPTI_MOMENTUM) != 0 : true;
+  static constexpr bool s2 = KIND == OPTK_RMSPROP ? (F & OPTI_CENTERED) != 0 : (KIND == OPTK_ADAM || KIND == OPTK_ADAMW) && (F & OPTI_AMSGRAD) != 0;
+};
+// Tensor.lerp_(end, weight) as ATen evaluates it (aten/src/ATen/native/Lerp.h): the form that is exact at the nearer end
+__device__ __forceinline__ float torch_lerp(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w); }
+
+template <int KIND, unsigned F>
+__device__ __forceinline__ void optim_update_ex(float& p, float& g, float& s0, float& s1, float& s2, float coef, const OptimSpecEx& o) {
+  float gi = g * coef;
+  g = gi;                                     // clip_grad_norm_ scales .grad in place
+  float pi = p;
+  if (KIND == OPTK_ADAMW) {                   // _single_tensor_adam, decoupled_weight_decay: param.mul_(1 - lr * weight_decay)
+    if (o.wd != 0.f) pi *= o.decay;
+  } else if (o.wd != 0.f) {
+    gi = gi + o.wd * pi;                      // grad.add(param, alpha=weight_decay)
+  }
+  if (KIND == OPTK_SGD) {                     // _single_tensor_sgd
+    if (F & OPTI_MOMENTUM) {
+      const float buf = o.live ? s0 * o.mu + o.omd * gi : gi;     // buf = clone(grad) on the first update, else buf.mul_(mu).add_(grad, alpha=1 - dampening)
+      s0 = buf;
+      gi = (F & OPTI_NESTEROV) ? gi + o.mu * buf : buf;
+    }
+    p = pi + o.neg_step * gi;
+  } else if (KIND == OPTK_RMSPROP) {          // _single_tensor_rmsprop
+    const float sq = s0 * o.a + (o.oma * gi) * gi;                // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    s0 = sq;
+    float avg;
+    if (F & OPTI_CENTERED) {
+      const float ga = torch_lerp(s2, gi, o.oma);                 // grad_avg.lerp_(grad, 1 - alpha)
+      s2 = ga;
+      avg = sqrtf(sq + (-ga) * ga);                               // square_avg.addcmul(grad_avg, grad_avg, value=-1).sqrt_()
+    } else {
+      avg = sqrtf(sq);
+    }
+    avg += o.eps;
+    if (F & OPTI_MOMENTUM) {
+      const float buf = s1 * o.mu + gi / avg;                     // buf.mul_(momentum).addcdiv_(grad, avg)
+      s1 = buf;
+      p = pi + o.neg_step * buf;
+    } else {
+      p = pi + (o.neg_step * gi) / avg;                           // param.addcdiv_(grad, avg, value=-lr)
+    }
+  } else if (KIND == OPTK_ADADELTA) {         // _single_tensor_adadelta
+    const float sq = s0 * o.a + (o.oma * gi) * gi;
+    s0 = sq;
+    const float delta = sqrtf(s1 + o.eps) / sqrtf(sq + o.eps) * gi;
+    s1 = s1 * o.a + (o.oma * delta) * delta;
+    p = pi + o.neg_step * delta;
+  } else if (KIND == OPTK_ADAM || KIND == OPTK_ADAMW) {           // _single_tensor_adam
+    const float m = torch_lerp(s0, gi, o.w1);                     // exp_avg.lerp_(grad, 1 - beta1)
+    const float v = s1 * o.a + (o.oma * gi) * gi;                 // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    s0 = m; s1 = v;
+    float vd = v;
+    if (F & OPTI_AMSGRAD) { vd = fmaxf(s2, v); s2 = vd; }         // torch.maximum(max_exp_avg_sq, exp_avg_sq, out=max_exp_avg_sq)
+    const float denom = sqrtf(vd) / o.bc2_sqrt + o.eps;
+    p = pi + (o.neg_step * m) / denom;                            // param.addcdiv_(exp_avg, denom, value=-step_size)
+  } else {                                    // _single_tensor_adamax
+    const float m = torch_lerp(s0, gi, o.w1);
+    const float u = fmaxf(s1 * o.a, fabsf(gi) + o.eps);           // torch.maximum(exp_inf.mul_(beta2), grad.abs().add_(eps), out=exp_inf)
+    s0 = m; s1 = u;
+    p = pi + (o.neg_step * m) / u;                                // param.addcdiv_(exp_avg, exp_inf, value=-clr)
+  }
+}
+
+// Same frame as optim_step_kernel: fault-word early return, fixed-order sum of the norm partials in every workgroup, 1 / Tv
+// folded into the clip coefficient, four grid strides in flight with a predicated last trip.
+template <int KIND, unsigned F>
+static __global__ __launch_bounds__(RED_THREADS) void optim_step_ex_kernel(
+    float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1, float* __restrict__ s2, long n,
+    const double* __restrict__ norm_partial, int n_partial, double* __restrict__ norm2_out, OptimSpecEx o,
+    const unsigned int* __restrict__ fault_dev, unsigned int* fault_host /* pinned, or null */,
+    unsigned int* skipped_host /* pinned, or null */, const float* __restrict__ gscale /* or null */) {
+  typedef OptimStreams<KIND, F> S;
+  __shared__ float coef_sh;
+  __shared__ double shn[16];
+  if (fault_dev && *fault_dev) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (fault_host) *fault_host = *fault_dev;
+      if (skipped_host) *skipped_host += 1u;
+      if (norm2_out) *norm2_out = __longlong_as_double(0x7ff8000000000000LL);
+    }
+    return;
+  }
+  double part = 0.0;
+  {
+    const int bd = blockDim.x;
+    int i = threadIdx.x;
+    for (; i + 3 * bd < n_partial; i += 4 * bd) {
+      const double a0 = norm_partial[i], a1 = norm_partial[i + bd], a2 = norm_partial[i + 2 * bd], a3 = norm_partial[i + 3 * bd];
+      part += a0; part += a1; part += a2; part += a3;
+    }
+    for (; i < n_partial; i += bd) part += norm_partial[i];
+  }
+  double tot = block_sum_d(part, shn);
+  if (threadIdx.x == 0) {
+    const float gsc = gscale ? *gscale : 1.f;
+    tot *= (double)gsc * (double)gsc;
+    if (blockIdx.x == 0 && norm2_out) *norm2_out = tot;
+    float coef = 1.f;
+    if (o.max_norm > 0.f) {
+      const float total_norm = (float)sqrt(tot);
+      coef = fminf(o.max_norm / (total_norm + 1e-6f), 1.f);
+    }
+    coef_sh = coef * gsc;
+  }
+  __syncthreads();
+  const float coef = coef_sh;
+  const long gstride = (long)gridDim.x * blockDim.x;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < n; i += 4 * gstride) {
+    float pv[4], gv[4], av[4], bv[4], cv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long k = i + u * gstride;
+      const bool ok = k < n;
+      pv[u] = ok ? p[k] : 0.f; gv[u] = ok ? g[k] : 0.f;
+      av[u] = (S::s0 && ok) ? s0[k] : 0.f; bv[u] = (S::s1 && ok) ? s1[k] : 0.f; cv[u] = (S::s2 && ok) ? s2[k] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long k = i + u * gstride;
+      if (k >= n) continue;
+      optim_update_ex<KIND, F>(pv[u], gv[u], av[u], bv[u], cv[u], coef, o);
+      p[k] = pv[u]; g[k] = gv[u];
+      if (S::s0) s0[k] = av[u];
+      if (S::s1) s1[k] = bv[u];
+      if (S::s2) s2[k] = cv[u];
+    }
+  }
+}
+
 constexpr int OPTIM_REST_MAX = 12;
 struct OptimRest { long off[OPTIM_REST_MAX]; long n[OPTIM_REST_MAX]; int n_rest, pad_; };   // ranges of the flat gradient that no slab job writes
 // block `blk` of slab job J: sums its elements' slabs, writes the gradient, returns this thread's share of the squared sum

@@ -136,7 +136,7 @@ class StepEngine(object):
 
     def bind_optimizer(self, role, optimizer):
         """torch.optim reads ``param_groups`` on every step: any hyper-parameter edited since the last bind (weight_decay,
-        eps, betas, lr_decay, ``max_grad_norm``) re-binds; a change of ``lr`` alone (exp_lr_scheduler, train.py:323-333)
+        eps, betas, lr_decay, momentum, dampening, nesterov, alpha, centered, rho, amsgrad, ``max_grad_norm``) re-binds; a change of ``lr`` alone (exp_lr_scheduler, train.py:323-333)
         takes the cheap ``gt_set_lr`` path."""
         ref, ver, hyper = self._bound_opt[role]
         now = optimizer._hyper()
@@ -146,7 +146,8 @@ class StepEngine(object):
                 self._bound_opt[role] = (ref, ver, now)
             return
         desc = optimizer._desc()
-        check(lib.gt_bind_optimizer(self._h, role, C.byref(desc)))
+        bind = lib.gt_bind_optimizer_ex if isinstance(desc, L.OptimDescEx) else lib.gt_bind_optimizer
+        check(bind(self._h, role, C.byref(desc)))
         self._bound_opt[role] = (weakref.ref(optimizer), optimizer._version, now)
         optimizer._engines[id(self)] = (weakref.ref(self), role)
 

@@ -1,5 +1,6 @@
-"""``Adagrad`` / ``Adam`` with torch.optim's constructor signature, ``param_groups`` and
-``state_dict`` layout (reference train.py:796-799 builds them with
+"""torch.optim's first-order family -- ``Adagrad``, ``Adam`` (``amsgrad``, ``decoupled_weight_decay``), ``AdamW``, ``SGD``,
+``RMSprop``, ``Adadelta``, ``Adamax`` -- with torch.optim's constructor signatures, ``param_groups`` and ``state_dict``
+layout (reference train.py:796-799 builds them with
 ``getattr(optim, hp.optimizer_g)(model.parameters(), **hp.optimizer_g_params)``; checkpoints
 store ``optimizer.state_dict()``, train.py:162-171).
 
@@ -33,6 +34,7 @@ def _owner_of(params):
 class _FlatOptimizer(object):
     KIND = None
     STATE_KEYS = ()
+    HAS_STEP = True       # torch keeps a "step" entry in the per-parameter state (every class but SGD)
 
     def __init__(self, params, defaults):
         self.model, self._params = _owner_of(params)
@@ -40,16 +42,22 @@ class _FlatOptimizer(object):
         group = dict(defaults)
         group["params"] = list(range(len(self._params)))
         self.param_groups = [group]
-        self._state = [None, None]
+        self._state = [None, None, None]
         self._step = 0
+        self._step0 = 0               # step count at construction / load_state_dict
+        self._live0 = False           # SGD: a loaded checkpoint carried momentum_buffer
         self._version = 0
         self._engines = {}
         self.max_grad_norm = 1.0      # clip_grad_norm_(params, 1.0), train.py:275,317
 
     # -- flat state -------------------------------------------------------------------------
+    def _slots(self):
+        """State buffer index (state0..2 of the descriptor) of every key of ``STATE_KEYS``."""
+        return list(range(len(self.STATE_KEYS)))
+
     def _ensure_state(self):
         flat = self.model.flat_params()
-        for i in range(len(self.STATE_KEYS)):
+        for i in self._slots():
             st = self._state[i]
             if st is None:
                 self._state[i] = torch.zeros_like(flat)
@@ -79,8 +87,11 @@ class _FlatOptimizer(object):
         """(lr, everything else the fused update kernel reads) -- compared by StepEngine.bind_optimizer on every step."""
         g = self.param_groups[0]
         b1, b2 = g.get("betas", (0.0, 0.0))
-        return (float(g["lr"]), float(g.get("weight_decay", 0.0)), float(g["eps"]), float(g.get("lr_decay", 0.0)),
-                float(b1), float(b2), float(self.max_grad_norm))
+        return (float(g["lr"]), float(g.get("weight_decay", 0.0)), float(g.get("eps", 0.0)), float(g.get("lr_decay", 0.0)),
+                float(b1), float(b2), float(self.max_grad_norm),
+                float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0)), bool(g.get("nesterov", False)),
+                float(g.get("alpha", g.get("rho", 0.0))), bool(g.get("centered", False)), bool(g.get("amsgrad", False)),
+                bool(g.get("decoupled_weight_decay", False)))
 
     def _note_step(self, engine, role):
         self._step = engine.optimizer_step_count(role)
@@ -108,15 +119,42 @@ class _FlatOptimizer(object):
             off += n
         return out
 
+    def _has_state(self):
+        """torch creates the per-parameter state on the first step() (Adagrad: at construction)."""
+        return self._step > 0
+
+    def _live(self):
+        """SGD's "momentum_buffer holds a value": a step was taken since construction / load, or the loaded checkpoint had it."""
+        return self._live0 or self._step > self._step0
+
+    def _desc_ex(self, kind, flags=0, momentum=0.0, dampening=0.0, alpha=0.0):
+        self._ensure_state()
+        g = self.param_groups[0]
+        d = L.OptimDescEx()
+        d.kind, d.flags = kind, flags
+        d.lr = float(g["lr"])
+        d.weight_decay = float(g.get("weight_decay", 0.0))
+        d.eps = float(g.get("eps", 0.0))
+        b1, b2 = g.get("betas", (0.0, 0.0))
+        d.beta1, d.beta2 = float(b1), float(b2)
+        d.momentum, d.dampening, d.alpha = float(momentum), float(dampening), float(alpha)
+        d.max_grad_norm = float(self.max_grad_norm)
+        d.step = int(self._step)
+        slots = self._slots()
+        for k in range(3):
+            setattr(d, "state%d" % k, self._state[k].data_ptr() if k in slots else None)
+        return d
+
     def state_dict(self):
         state = {}
         if self.KIND == L.OPT_ADAGRAD:
             self._ensure_state()      # torch.optim.Adagrad creates "sum" at construction
-        if self._state[0] is not None and (self._step > 0 or self.KIND == L.OPT_ADAGRAD):
-            views = [self._views(s) for s in self._state[:len(self.STATE_KEYS)]]
+        keys, slots = self.STATE_KEYS, self._slots()
+        if self._has_state() and all(self._state[k] is not None for k in slots):
+            views = [self._views(self._state[k]) for k in slots]
             for i in range(len(self._params)):
-                st = {"step": torch.tensor(float(self._step))}
-                for k, key in enumerate(self.STATE_KEYS):
+                st = {"step": torch.tensor(float(self._step))} if self.HAS_STEP else {}
+                for k, key in enumerate(keys):
                     st[key] = views[k][i].clone()
                 state[i] = st
         return {"state": state, "param_groups": [dict(g) for g in self.param_groups]}
@@ -129,18 +167,24 @@ class _FlatOptimizer(object):
         g["params"] = list(range(len(self._params)))
         self.param_groups = [g]
         state = sd.get("state", {})
+        self._live0 = False
         if state:
             self._ensure_state()
-            views = [self._views(s) for s in self._state[:len(self.STATE_KEYS)]]
+            keys, slots = self.STATE_KEYS, self._slots()
+            views = [self._views(self._state[k]) for k in slots]
             steps = set()
             for i in range(len(self._params)):
                 st = state[i]
-                steps.add(int(float(st["step"])))
-                for k, key in enumerate(self.STATE_KEYS):
+                if self.HAS_STEP:
+                    steps.add(int(float(st["step"])))
+                for k, key in enumerate(keys):
                     views[k][i].copy_(st[key])
-            if len(steps) != 1:
-                raise ValueError("per-parameter step counts differ; not a checkpoint of this optimizer")
-            self._step = steps.pop()
+            if self.HAS_STEP:
+                if len(steps) != 1:
+                    raise ValueError("per-parameter step counts differ; not a checkpoint of this optimizer")
+                self._step = steps.pop()
+            self._live0 = len(keys) > 0
+        self._step0 = self._step
         self._version += 1
 
 
@@ -149,12 +193,16 @@ class Adagrad(_FlatOptimizer):
     KIND = L.OPT_ADAGRAD
     STATE_KEYS = ("sum",)
 
-    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10):
+    def __init__(self, params, lr=1e-2, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10, *, maximize=False):
+        _reject(maximize)
         if lr < 0 or lr_decay < 0 or weight_decay < 0 or eps < 0:
             raise ValueError("invalid Adagrad hyper-parameter")
         super(Adagrad, self).__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
                                                    initial_accumulator_value=initial_accumulator_value))
         self._init_acc = float(initial_accumulator_value)
+
+    def _has_state(self):
+        return True
 
     def _ensure_state(self):
         fresh = self._state[0] is None
@@ -163,15 +211,150 @@ class Adagrad(_FlatOptimizer):
             self._state[0].fill_(self._init_acc)
 
 
-class Adam(_FlatOptimizer):
-    """torch.optim.Adam semantics (bias-corrected, no amsgrad)."""
-    KIND = L.OPT_ADAM
-    STATE_KEYS = ("exp_avg", "exp_avg_sq")
+def _reject(maximize):
+    if maximize:
+        raise ValueError("maximize is not supported")
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
-        if amsgrad:
-            raise ValueError("amsgrad is not supported")
+
+def _check_betas(betas):
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError("Invalid beta parameter at index 0: %s" % (betas[0],))
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError("Invalid beta parameter at index 1: %s" % (betas[1],))
+
+
+class Adam(_FlatOptimizer):
+    """torch.optim.Adam semantics (bias-corrected; ``amsgrad`` keeps ``max_exp_avg_sq``; ``decoupled_weight_decay`` is AdamW)."""
+    KIND = L.OPT_ADAM
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
+                 decoupled_weight_decay=False):
+        _reject(maximize)
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameter")
         super(Adam, self).__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
-                                                amsgrad=False))
+                                                amsgrad=bool(amsgrad), decoupled_weight_decay=bool(decoupled_weight_decay)))
+
+    @property
+    def STATE_KEYS(self):
+        return ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if self.param_groups[0].get("amsgrad") else ())
+
+    def _desc(self):
+        g = self.param_groups[0]
+        ams, dec = bool(g.get("amsgrad")), bool(g.get("decoupled_weight_decay"))
+        if not ams and not dec:
+            return super(Adam, self)._desc()      # the kernel of the two original kinds
+        return self._desc_ex(L.OPT_ADAMW if dec else L.OPT_ADAM, L.OPTF_AMSGRAD if ams else 0)
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: ``param *= 1 - lr * weight_decay``, then Adam without weight decay."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False):
+        super(AdamW, self).__init__(params, lr, betas, eps, weight_decay, amsgrad, maximize=maximize, decoupled_weight_decay=True)
+
+
+class SGD(_FlatOptimizer):
+    """torch.optim.SGD semantics (momentum, dampening, nesterov, weight_decay)."""
+    KIND = L.OPT_SGD
+    HAS_STEP = False
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
+        _reject(maximize)
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: %s" % (lr,))
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: %s" % (momentum,))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: %s" % (weight_decay,))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super(SGD, self).__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                               nesterov=bool(nesterov)))
+
+    @property
+    def STATE_KEYS(self):
+        return ("momentum_buffer",) if self.param_groups[0]["momentum"] != 0 else ()
+
+    def _has_state(self):
+        return self._live()
+
+    def _desc(self):
+        g = self.param_groups[0]
+        flags = (L.OPTF_NESTEROV if g["nesterov"] else 0) | (L.OPTF_BUFFER_LIVE if self._live() else 0)
+        return self._desc_ex(L.OPT_SGD, flags, momentum=g["momentum"], dampening=g["dampening"])
+
+
+class RMSprop(_FlatOptimizer):
+    """torch.optim.RMSprop semantics (alpha, momentum, centered)."""
+    KIND = L.OPT_RMSPROP
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, *, maximize=False):
+        _reject(maximize)
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: %s" % (lr,))
+        if eps < 0.0:
+            raise ValueError("Invalid epsilon value: %s" % (eps,))
+        if momentum < 0.0:
+            raise ValueError("Invalid momentum value: %s" % (momentum,))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: %s" % (weight_decay,))
+        if alpha < 0.0:
+            raise ValueError("Invalid alpha value: %s" % (alpha,))
+        super(RMSprop, self).__init__(params, dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=bool(centered),
+                                                   weight_decay=weight_decay))
+
+    @property
+    def STATE_KEYS(self):
+        g = self.param_groups[0]
+        return ("square_avg",) + (("momentum_buffer",) if g["momentum"] > 0 else ()) + (("grad_avg",) if g["centered"] else ())
+
+    def _slots(self):
+        g = self.param_groups[0]
+        return [0] + ([1] if g["momentum"] > 0 else []) + ([2] if g["centered"] else [])
+
+    def _desc(self):
+        g = self.param_groups[0]
+        return self._desc_ex(L.OPT_RMSPROP, L.OPTF_CENTERED if g["centered"] else 0, momentum=max(float(g["momentum"]), 0.0),
+                             alpha=g["alpha"])
+
+
+class Adadelta(_FlatOptimizer):
+    """torch.optim.Adadelta semantics (rho, eps, lr)."""
+    KIND = L.OPT_ADADELTA
+    STATE_KEYS = ("square_avg", "acc_delta")
+
+    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0, *, maximize=False):
+        _reject(maximize)
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: %s" % (lr,))
+        if not 0.0 <= rho <= 1.0:
+            raise ValueError("Invalid rho value: %s" % (rho,))
+        if eps < 0.0:
+            raise ValueError("Invalid epsilon value: %s" % (eps,))
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: %s" % (weight_decay,))
+        super(Adadelta, self).__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay))
+
+    def _desc(self):
+        return self._desc_ex(L.OPT_ADADELTA, alpha=self.param_groups[0]["rho"])
+
+
+class Adamax(_FlatOptimizer):
+    """torch.optim.Adamax semantics (exponentially weighted infinity norm)."""
+    KIND = L.OPT_ADAMAX
+    STATE_KEYS = ("exp_avg", "exp_inf")
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, *, maximize=False):
+        _reject(maximize)
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: %s" % (lr,))
+        if eps < 0.0:
+            raise ValueError("Invalid epsilon value: %s" % (eps,))
+        _check_betas(betas)
+        if weight_decay < 0.0:
+            raise ValueError("Invalid weight_decay value: %s" % (weight_decay,))
+        super(Adamax, self).__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+
+    def _desc(self):
+        return self._desc_ex(L.OPT_ADAMAX)

@@ -46,6 +46,17 @@ extern "C" {
 
 #define GT_OPT_ADAGRAD 0      /* torch.optim.Adagrad, train.py:796-799 with hparams.py:48-52,223-227 */
 #define GT_OPT_ADAM 1         /* torch.optim.Adam,    hparams.py:125-130 */
+/* the rest of the torch.optim names a reference script may put into hp.optimizer_g / hp.optimizer_d (gt_optim_desc_ex only) */
+#define GT_OPT_SGD 2          /* torch.optim.SGD      (momentum, dampening, nesterov) */
+#define GT_OPT_RMSPROP 3      /* torch.optim.RMSprop  (alpha, momentum, centered) */
+#define GT_OPT_ADADELTA 4     /* torch.optim.Adadelta (rho) */
+#define GT_OPT_ADAMW 5        /* torch.optim.AdamW == Adam(decoupled_weight_decay=True) */
+#define GT_OPT_ADAMAX 6       /* torch.optim.Adamax */
+/* gt_optim_desc_ex.flags */
+#define GT_OPTF_NESTEROV 1u     /* SGD */
+#define GT_OPTF_CENTERED 2u     /* RMSprop */
+#define GT_OPTF_AMSGRAD 4u      /* Adam, AdamW */
+#define GT_OPTF_BUFFER_LIVE 8u  /* SGD: momentum_buffer holds a value (a step was taken, or a checkpoint that has it was loaded) */
 
 #define GT_MAX_STREAMS 8
 
@@ -99,6 +110,34 @@ typedef struct {
   float* state1;             /* Adam "exp_avg_sq" (NULL for Adagrad) */
 } gt_optim_desc;
 
+/* Every kind of the family.  The hyper-parameters are doubles, as torch.optim keeps them (python floats): the per-step
+ * scalars (1 - beta, 1 - alpha, lr / (1 - beta1^t), ...) are formed in double and rounded to float once, as torch's
+ * single-tensor code path does.  lr alone is rounded to float first, so that gt_bind_optimizer_ex and gt_set_lr agree.
+ * State buffers (flat float32, same layout as params; a buffer the kind / flags do not use may be NULL):
+ *   kind       state0          state1                              state2
+ *   ADAGRAD    sum             -                                   -
+ *   ADAM(W)    exp_avg         exp_avg_sq                          max_exp_avg_sq (AMSGRAD)
+ *   SGD        momentum_buffer (momentum != 0)  -                  -
+ *   RMSPROP    square_avg      momentum_buffer (momentum > 0)      grad_avg (CENTERED)
+ *   ADADELTA   square_avg      acc_delta                           -
+ *   ADAMAX     exp_avg         exp_inf                             - */
+typedef struct {
+  int32_t kind;              /* GT_OPT_ADAGRAD .. GT_OPT_ADAMAX */
+  uint32_t flags;            /* GT_OPTF_* */
+  double lr, weight_decay, eps;
+  double lr_decay;           /* Adagrad */
+  double beta1, beta2;       /* Adam, AdamW, Adamax */
+  double momentum;           /* SGD, RMSprop */
+  double dampening;          /* SGD */
+  double alpha;              /* RMSprop alpha, Adadelta rho */
+  float max_grad_norm;       /* as in gt_optim_desc */
+  int32_t reserved_;
+  int64_t step;              /* number of steps already taken */
+  float* state0;
+  float* state1;
+  float* state2;
+} gt_optim_desc_ex;
+
 typedef struct {             /* return values of update_discriminator, train.py:278-279 (same order) */
   float loss_d, loss_fake_d, loss_real_d, real_correct_count, fake_correct_count;
   float grad_norm;           /* pre-clip ||grad D||_2 from the split-phase gt_update_discriminator_end; 0 from the fused call,
@@ -121,6 +160,10 @@ void gt_engine_destroy(gt_engine* e);
 int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc);
 /* getattr(optim, hp.optimizer_*)(model.parameters(), **params) (train.py:796-799) */
 int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* desc);
+/* The same for every GT_OPT_* kind.  Checks per kind which state buffers must be given and rejects what torch's constructors
+ * reject (GT_ERR_INVALID): negative lr / eps / weight_decay / momentum / alpha, betas or rho outside their interval, nesterov
+ * with zero momentum or non-zero dampening, a flag that does not belong to the kind. */
+int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_ex* desc);
 /* model.train() / model.eval()                                 (train.py:481-486) */
 int gt_set_training(gt_engine* e, int role, int training);
 /* exp_lr_scheduler writes param_group["lr"]                     (train.py:323-333) */
@@ -354,6 +397,12 @@ int gt_op_sequence_mask(const int64_t* lengths, int B, int T, float* mask, void*
  * grad_input (optional) receives d loss / d input */
 int gt_op_masked_mse(const float* input, const float* target, const float* mask, int B, int T, int D,
                      float* loss_out, float* grad_input, void* stream);
+/* clip_grad_norm_(params, desc->max_grad_norm) + one optimizer step over the caller's flat buffers of n floats: the engine's own
+ * two launches (squared-norm partials, then the fused clip + update kernel of desc->kind / flags), without an engine.  desc->step
+ * is the number of steps already taken.  gscale (device, may be NULL): the gradient is that of a loss still to be multiplied by
+ * *gscale.  grads receives the clipped gradient.  grad_norm_out (host, may be NULL): the pre-clip norm; synchronises if given. */
+int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
+                     float* grad_norm_out, void* stream);
 /* Device-side collate: padding (train.py:139-159 `_pad_2d` / collate_fn) and the descending length sort of the batch
  * (train.py:494-501) without a padded host copy.  `ragged`: the batch's utterances un-padded, back to back, [total][D] (device);
  * start[b] / len[b] (device int64, B entries): first frame and frame count of the utterance that becomes OUTPUT sequence b (the
