@@ -159,7 +159,9 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
     if (e->len_host[i]) (void)hipHostFree(e->len_host[i]);
     if (e->len_ev[i]) (void)hipEventDestroy(e->len_ev[i]);
   }
-  for (auto* v : {&e->s_u, &e->s_h, &e->s_c, &e->s_xdrop, &e->s_xmask, &e->s_wt}) for (auto& s : *v) s.release();
+  for (auto* v : {&e->s_u, &e->s_h, &e->s_c, &e->s_xdrop, &e->s_xmask, &e->s_wt, &e->ds_u, &e->ds_h, &e->ds_c, &e->ds_xdrop, &e->ds_xmask, &e->ds_wt,
+                  &e->ds_omask})
+    for (auto& s : *v) s.release();
   e->s_du.release(); e->s_dx.release(); e->s_dbias.release();
   Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial,
                     &e->headp, &e->headw, &e->gx_dense, &e->cx_dense, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp};
@@ -222,9 +224,9 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   if (desc->n_params != expected_params(*desc))
     return fail(GT_ERR_INVALID, "n_params %ld does not match the architecture (%ld)", (long)desc->n_params, expected_params(*desc));
   if (desc->arch == GT_ARCH_LSTM && desc->hidden_dim < 1) return fail(GT_ERR_INVALID, "hidden_dim must be positive");
-  if (role == GT_ROLE_D && ((desc->arch != GT_ARCH_MLP && desc->arch != GT_ARCH_LSTM) || desc->out_dim != 1 || !desc->last_sigmoid))
-    return fail(GT_ERR_INVALID, "discriminator must be MLP or LSTMRNN with out_dim=1, last_sigmoid=True (hparams.py:56-64,230-239; train.py:773-774)");
-  if (role == GT_ROLE_D && desc->arch == GT_ARCH_LSTM && desc->hidden_dim * (desc->bidirectional ? 2 : 1) > 1024)
+  if (role == GT_ROLE_D && ((desc->arch != GT_ARCH_MLP && desc->arch != GT_ARCH_LSTM && desc->arch != GT_ARCH_SRU) || desc->out_dim != 1 || !desc->last_sigmoid))
+    return fail(GT_ERR_INVALID, "discriminator must be MLP, LSTMRNN or SRURNN with out_dim=1, last_sigmoid=True (hparams.py:56-64,230-239; train.py:773-774)");
+  if (role == GT_ROLE_D && (desc->arch == GT_ARCH_LSTM || desc->arch == GT_ARCH_SRU) && desc->hidden_dim * (desc->bidirectional ? 2 : 1) > 1024)
     return fail(GT_ERR_INVALID, "recurrent discriminator: hidden_dim x directions > 1024 is not supported by the fused head kernel");
   Net& n = e->net[role];
   n.d = *desc;
@@ -283,8 +285,12 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
       n.sru.push_back(L);
     }
     n.last = take(desc->out_dim, ncols);
-    e->s_u.resize(desc->num_hidden); e->s_h.resize(desc->num_hidden);
-    e->s_c.resize(desc->num_hidden); e->s_xdrop.resize(desc->num_hidden); e->s_xmask.resize(desc->num_hidden); e->s_wt.resize(desc->num_hidden);
+    if (role == GT_ROLE_G) {
+      e->s_u.resize(desc->num_hidden); e->s_h.resize(desc->num_hidden);
+      e->s_c.resize(desc->num_hidden); e->s_xdrop.resize(desc->num_hidden); e->s_xmask.resize(desc->num_hidden); e->s_wt.resize(desc->num_hidden);
+    } else {
+      for (auto* v : {&e->ds_u, &e->ds_h, &e->ds_c, &e->ds_xdrop, &e->ds_xmask, &e->ds_wt, &e->ds_omask}) v->resize(desc->num_hidden);
+    }
   } else {
     if (desc->arch == GT_ARCH_IN2OUT) n.gate = take(desc->static_dim, desc->static_dim);
     int in = desc->in_dim;

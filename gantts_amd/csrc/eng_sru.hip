@@ -1,38 +1,77 @@
-// libgantts_hip.so -- recurrent generator (GT_ARCH_SRU)
+// libgantts_hip.so -- the SRU stack (GT_ARCH_SRU) of either role: the recurrent generator, an SRURNN in the discriminator slot
 #include "engine_internal.hip.h"
 #include "sru_cs_kernels.hip.h"
 #include "sru_kernels.hip.h"
 using namespace gt;
 // ------------------------------------------------------------------------------------------
-// recurrent generator (GT_ARCH_SRU)
+// SRU stack (GT_ARCH_SRU), role-generic
 // ------------------------------------------------------------------------------------------
-static void sru_keys(gt_engine* e, int layer, int which, uint32_t* k0, uint32_t* k1) {
+static void sru_keys(gt_engine* e, int role, int pass, int layer, int which, uint32_t* k0, uint32_t* k1) {
   // data parallel: the masks are per (sequence, column); the kernels count sequences globally (SruArgs::seq_mul / seq_add), so a
   // world-k run draws the whole minibatch's masks of a world-1 run -- no rank in the key
   const uint64_t site = e->step_counter * 64ULL + 40 + (uint64_t)(layer * 2 + which);
   *k0 = (uint32_t)(e->seed ^ (site * 0x9E3779B97F4A7C15ULL));
   *k1 = (uint32_t)((e->seed >> 32) ^ (site >> 7) ^ 0x5A5A5A5Au) + (uint32_t)site;
+  if (role != GT_ROLE_G || pass != 0) {      // a discriminator's three passes: never the generator's bits, never another pass's (G's keys are the ones above)
+    const uint32_t salt = 0x85EBCA6Bu * (uint32_t)(1 + role * 3 + pass);
+    *k0 ^= salt;
+    *k1 += (salt >> 5) | 1u;
+  }
 }
 static uint32_t drop_thresh(float p) {
   const double th = (double)p * 4294967296.0;
   return th >= 4294967295.0 ? 4294967295u : (uint32_t)th;
 }
 
-static SruArgs sru_args(gt_engine* e, const Net& G, int l, int B, int T, const float* in, int ld_in) {
+// The stashes of one role's SRU stack.  The discriminator has its own: the generator's forward stash has to survive both discriminator
+// passes of a step (update_generator back-propagates it last); the D-step stash is dead after the D step and the G-step pass reuses it.
+// omask: the discriminator's output-dropout keep tables [nseq][ncols] (0 / 1), one table for all row groups of a launch.
+struct SruBufs {
+  std::vector<Scratch>&u, &h, &c, &xdrop, &xmask, &wt;
+  std::vector<Scratch>* omask;
+  Scratch& dout;
+};
+static SruBufs sru_bufs(gt_engine* e, int role) {
+  if (role == GT_ROLE_G) return SruBufs{e->s_u, e->s_h, e->s_c, e->s_xdrop, e->s_xmask, e->s_wt, nullptr, e->l_dout};
+  return SruBufs{e->ds_u, e->ds_h, e->ds_c, e->ds_xdrop, e->ds_xmask, e->ds_wt, &e->ds_omask, e->dl_dout};
+}
+
+// One variational dropout table [nseq][width] of layer `l` (which: 0 input, 1 output): every row group of the launch (the D step runs
+// D(real) and D(fake) as ONE batch of 2B sequences) draws from its own pass -- its own Philox key, or its own injected 0/1 mask.
+// Sequence ids stay global: group q starts at local sequence q * nseq / npass.
+static int sru_draw_table(gt_engine* e, const Net& G, int role, int l, int which, float* tab, int nseq, int width, float p, float keep_scale,
+                          const int* passes, int npass, hipStream_t s) {
+  const int Bg = nseq / npass;
+  for (int q = 0; q < npass; ++q) {
+    uint32_t k0, k1;
+    sru_keys(e, role, passes[q], l, which, &k0, &k1);
+    hipLaunchKernelGGL(sru_input_mask_kernel, dim3(cdiv((long)Bg * width, 256)), dim3(256), 0, s, tab + (size_t)q * Bg * width, Bg, width, keep_scale,
+                       drop_thresh(p), k0, k1, (const float*)G.inj[passes[q]][2 * l + which], e->dp_world, e->dp_rank + e->dp_world * q * Bg);
+    LAUNCH_CHECK();
+  }
+  return GT_OK;
+}
+
+static SruArgs sru_args(gt_engine* e, int role, const SruBufs& W, int l, int B, int T, const float* in, int ld_in) {
+  const Net& G = e->net[role];
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs;
   const SruLayerP& L = G.sru[l];
   SruArgs a;
   memset(&a, 0, sizeof(a));
   a.B = B; a.T = T; a.H = H; a.dirs = dirs; a.k = L.k; a.act = G.d.use_relu ? SRU_RELU : SRU_TANH;
-  a.U = e->s_u[l].as<float>(); a.ldu = ncols * L.k;
+  a.U = W.u[l].as<float>(); a.ldu = ncols * L.k;
   a.x = in; a.ldx = ld_in;
   a.bias = L.b;
-  a.h = e->s_h[l].as<float>(); a.c = e->s_c[l].as<float>();
+  a.h = W.h[l].as<float>(); a.c = W.c[l].as<float>();
   a.seq_mul = e->dp_world; a.seq_add = e->dp_rank;
   if (G.training && G.d.dropout > 0.f && l + 1 < G.d.num_hidden) {   // the last layer has dropout 0 (SRU.__init__)
     a.use_mask = 1; a.keep_scale = 1.f / (1.f - G.d.dropout); a.thresh = drop_thresh(G.d.dropout);
-    sru_keys(e, l, 1, &a.key0, &a.key1);
-    a.mask_buf = G.inj[0][2 * l + 1];                                // gt_set_dropout_mask(G, 0, 2*l + 1): [B][ncols]
+    if (role == GT_ROLE_G) {
+      sru_keys(e, GT_ROLE_G, 0, l, 1, &a.key0, &a.key1);
+      a.mask_buf = G.inj[0][2 * l + 1];                              // gt_set_dropout_mask(G, 0, 2*l + 1): [B][ncols]
+    } else {
+      a.mask_buf = (*W.omask)[l].as<float>();                        // drawn per pass by the forward (sru_draw_table): [nseq][ncols] of 0 / 1
+    }
   }
   return a;
 }
@@ -50,60 +89,84 @@ static int sru_coop_waves(long B, int ncols) {
 // Measured and dropped (round 4, gpurun_out/r4k): 32 columns per workgroup (twice the recurrence waves per CU, half of every wave
 // idle) for the shapes that give fewer than three 64-column workgroups per CU -- cfg4 (B = 16, T = 2048) 11.36 vs 10.84 ms, the
 // hparams-default generator at B = 32 9.49 vs 9.32 ms: the scan is not bound by one wave's per-frame latency.
-static bool sru_b16(const gt_engine* e) { return e->matmul_bf16 && (e->net[GT_ROLE_G].d.hidden_dim & 7) == 0; }
-int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s) {
-  Net& G = e->net[GT_ROLE_G];
+// GT_OPT_MATMUL_BF16 per role: the generator's stack takes the bf16 images; a discriminator's keeps float32 products and stashes
+static bool sru_b16(const gt_engine* e, int role) { return role == GT_ROLE_G && e->matmul_bf16 && (e->net[GT_ROLE_G].d.hidden_dim & 7) == 0; }
+// (a discriminator's products stay in the float32 family for the duration of its stack calls)
+struct SruPrecScope {
+  int saved;
+  explicit SruPrecScope(int role) : saved(tl_gemm_prec) { if (role != GT_ROLE_G) tl_gemm_prec = PREC_F32; }
+  ~SruPrecScope() { tl_gemm_prec = saved; }
+};
+// ... with the cooperative scans on whole 8-frame blocks and whole workgroups: the scans write the bf16 images of the next product's input
+static bool sru_fold(const gt_engine* e, int role, int nseq, int T) {
+  const Net& G = e->net[role];
+  const int H = G.d.hidden_dim, ncols = H * (G.d.bidirectional ? 2 : 1);
+  return sru_b16(e, role) && sru_coop() && T % 8 == 0 && H % 64 == 0 && ((long)nseq * ncols) % 64 == 0;
+}
+// The SRU stack of network `role` over nseq sequences (rows = nseq * T of x, row pitch ld_x): per layer the U product and the scan, the
+// variational dropout of both sites; stashes U / h / c (and the dropped inputs and mask tables) in the role's buffers.  passes / npass:
+// the dropout passes of the row groups (the D step runs the natural and the generated sequences as ONE batch of 2B: two groups of
+// nseq / 2 sequences).  Sequence lengths are ignored, as in the reference.  *top / *ld_top: the top layer's h.
+int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
+                      const float** top, int* ld_top) {
+  Net& G = e->net[role];
+  SruBufs W = sru_bufs(e, role);
+  const SruPrecScope prec(role);
+  const int B = nseq;
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs;
+  if (npass < 1 || nseq % npass) return fail(GT_ERR_INVALID, "SRU stack: %d sequences do not split into %d passes", nseq, npass);
   const float* in = x;
-  int ld_in = G.d.in_dim;
+  int ld_in = ld_x;
   // GT_OPT_MATMUL_BF16: the (dropped) layer inputs go through bf16 images in both orientations, W through bf16 shadows in
   // both orientations: U = xin . WT^T, dW = xinT . dUT^T, d in = dU . W^T are all the k-contiguous bf16 product
-  const bool b16 = sru_b16(e);
+  const bool b16 = sru_b16(e, role);
   const bool want_t = G.d.grads != nullptr;
   const int Lc_ = G.d.num_hidden;
   if (b16) {
     e->s_in_b.resize(Lc_ + 1); e->ssh.resize(Lc_ + 1);
     for (int l = 0; l <= Lc_; ++l) {
       LinShadow& w = e->ssh[l];
-      const float* W = l < Lc_ ? G.sru[l].W : G.last.W;
+      const float* Wl = l < Lc_ ? G.sru[l].W : G.last.W;
       const int rows = l < Lc_ ? G.sru[l].in : G.last.out, cols = l < Lc_ ? ncols * G.sru[l].k : G.last.in;
       w.ldw = pad8(cols); w.ldwt = pad8(rows);
       CHK(w.w.ensure((size_t)rows * w.ldw * 2 + 64)); CHK(w.wt.ensure((size_t)cols * w.ldwt * 2 + 64));
-      CHK(cast_transpose(W, cols, rows, cols, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt, nullptr, false, &e->colp, s));
+      CHK(cast_transpose(Wl, cols, rows, cols, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt, nullptr, false, &e->colp, s));
     }
   }
   // bf16 storage + cooperative scans: layer l's scan writes the bf16 input images of the product behind it (layer l + 1's U product, or
   // hidden2out) itself -- with that layer's variational input dropout applied -- so the multiplier tables of ALL layers are drawn first
   const bool rdrop_all = G.training && G.d.rnn_dropout > 0.f;
-  const bool fold = b16 && sru_coop() && T % 8 == 0 && H % 64 == 0 && ((long)B * ncols) % 64 == 0;
+  const bool fold = sru_fold(e, role, nseq, T);
   if (rdrop_all) {
     for (int l = 0; l < G.d.num_hidden; ++l) {
       const SruLayerP& L = G.sru[l];
-      CHK(e->s_xmask[l].ensure((size_t)B * L.in * sizeof(float)));
-      uint32_t k0, k1;
-      sru_keys(e, l, 0, &k0, &k1);
-      hipLaunchKernelGGL(sru_input_mask_kernel, dim3(cdiv((long)B * L.in, 256)), dim3(256), 0, s, e->s_xmask[l].as<float>(), B, L.in,
-                         1.f / (1.f - G.d.rnn_dropout), drop_thresh(G.d.rnn_dropout), k0, k1,
-                         (const float*)G.inj[0][2 * l], e->dp_world, e->dp_rank);     // gt_set_dropout_mask(G, 0, 2*l): [B][n_in]
-      LAUNCH_CHECK();
+      CHK(W.xmask[l].ensure((size_t)B * L.in * sizeof(float)));
+      // gt_set_dropout_mask(role, pass, 2*l): [B][n_in]
+      CHK(sru_draw_table(e, G, role, l, 0, W.xmask[l].as<float>(), B, L.in, G.d.rnn_dropout, 1.f / (1.f - G.d.rnn_dropout), passes, npass, s));
+    }
+  }
+  if (W.omask && G.training && G.d.dropout > 0.f) {      // a discriminator's output-dropout keep tables (the generator's scans draw theirs inline)
+    for (int l = 0; l + 1 < G.d.num_hidden; ++l) {
+      CHK((*W.omask)[l].ensure((size_t)B * ncols * sizeof(float)));
+      CHK(sru_draw_table(e, G, role, l, 1, (*W.omask)[l].as<float>(), B, ncols, G.d.dropout, 1.f, passes, npass, s));
     }
   }
   bool img_ready = false;       // the current layer's input images were written by the scan underneath
   for (int l = 0; l < G.d.num_hidden; ++l) {
     const SruLayerP& L = G.sru[l];
-    CHK(e->s_u[l].ensure((size_t)N * ncols * L.k * sizeof(float)));
-    CHK(e->s_h[l].ensure((size_t)N * ncols * sizeof(float)));
-    CHK(e->s_c[l].ensure((size_t)N * ncols * sizeof(float)));
+    CHK(W.u[l].ensure((size_t)N * ncols * L.k * sizeof(float)));
+    CHK(W.h[l].ensure((size_t)N * ncols * sizeof(float)));
+    CHK(W.c[l].ensure((size_t)N * ncols * sizeof(float)));
     const float* xin = in;
     int ld_xin = ld_in;
     const bool rdrop = rdrop_all;      // (variational input dropout, mask shared over time: the multipliers [B][n_in] were drawn above)
     if (rdrop && !b16) {      // float32 products read a dropped float32 copy
-      CHK(e->s_xdrop[l].ensure((size_t)N * L.in * sizeof(float)));
-      hipLaunchKernelGGL(sru_input_dropout_kernel, dim3(cdiv(N * L.in, 256)), dim3(256), 0, s, in, ld_in, e->s_xdrop[l].as<float>(),
-                         L.in, B, T, L.in, (const float*)e->s_xmask[l].as<float>());
+      CHK(W.xdrop[l].ensure((size_t)N * L.in * sizeof(float)));
+      hipLaunchKernelGGL(sru_input_dropout_kernel, dim3(cdiv(N * L.in, 256)), dim3(256), 0, s, in, ld_in, W.xdrop[l].as<float>(),
+                         L.in, B, T, L.in, (const float*)W.xmask[l].as<float>());
       LAUNCH_CHECK();
-      xin = e->s_xdrop[l].as<float>();
+      xin = W.xdrop[l].as<float>();
       ld_xin = L.in;
     }
     if (b16) {
@@ -112,7 +175,7 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
       if (img_ready) {
         // written by the scan of the layer underneath (SruArgs::nx_*): no cast pass
       } else if (rdrop) {            // bf16 products: dropout rides in the cast, the dropped input exists as bf16 images only
-        const SeqDropSrc src{in, ld_in, e->s_xmask[l].as<float>(), T, L.in};
+        const SeqDropSrc src{in, ld_in, W.xmask[l].as<float>(), T, L.in};
         hipLaunchKernelGGL(seqdrop_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, src, N, L.in, I.r(), I.ld,
                            want_t ? I.t() : (__bf16*)nullptr, I.ldt);
         LAUNCH_CHECK();
@@ -121,29 +184,29 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
       }
       GemmB16Args g = b16_args();
       g.A = I.r(); g.lda = I.ld; g.B = e->ssh[l].wt.as<__bf16>(); g.ldb = e->ssh[l].ldwt;     // WT [ncols*k][n_in]: k = n_in contiguous
-      g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE; g.C = e->s_u[l].as<float>(); g.ldc = ncols * L.k;
+      g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
       CHK(launch_gemm_b16(g, 1, s));
     } else if ((L.in & 3) == 0 && N >= 4096) {
       // U = xin W with W (n_in, ncols*k): the k-contiguous (NT) product runs at 146 TFLOP/s on these shapes, the n-contiguous (NN)
       // one at 114 (profiles/r03_sru_fp32_summary.md: 1.41 vs 1.80 ms per layer) -- multiply by a transposed copy of W, re-made
       // from the caller's parameter buffer before every pass (12 MB, ~10 us)
-      CHK(e->s_wt[l].ensure((size_t)ncols * L.k * L.in * sizeof(float)));
+      CHK(W.wt[l].ensure((size_t)ncols * L.k * L.in * sizeof(float)));
       hipLaunchKernelGGL(transpose_f32_kernel, dim3(cdiv(ncols * L.k, 32), cdiv(L.in, 32)), dim3(256), 0, s, L.W, L.in, ncols * L.k, ncols * L.k,
-                         e->s_wt[l].as<float>(), L.in);
+                         W.wt[l].as<float>(), L.in);
       LAUNCH_CHECK();
       GemmArgs g;
       memset(&g, 0, sizeof(g));
-      g.A = xin; g.lda = ld_xin; g.B = e->s_wt[l].as<float>(); g.ldb = L.in; g.C = e->s_u[l].as<float>(); g.ldc = ncols * L.k;
+      g.A = xin; g.lda = ld_xin; g.B = W.wt[l].as<float>(); g.ldb = L.in; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
       g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.act = ACT_NONE; g.drop = no_drop();
       CHK(launch_gemm(GEMM_NT, g, 1, s));
     } else {  // U = xin W   (W is (n_in, ncols*k): n-contiguous rows -> NN orientation)
       GemmArgs g;
       memset(&g, 0, sizeof(g));
-      g.A = xin; g.lda = ld_xin; g.B = L.W; g.ldb = ncols * L.k; g.C = e->s_u[l].as<float>(); g.ldc = ncols * L.k;
+      g.A = xin; g.lda = ld_xin; g.B = L.W; g.ldb = ncols * L.k; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
       g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.act = ACT_NONE; g.drop = no_drop();
       CHK(launch_gemm(GEMM_NN, g, 1, s));
     }
-    SruArgs a = sru_args(e, G, l, B, T, in, ld_in);
+    SruArgs a = sru_args(e, role, W, l, B, T, in, ld_in);
     img_ready = false;
     if (fold) {       // the images of the product behind this layer: layer l + 1's input (its dropout applied), or hidden2out's
       const int nl = l + 1;
@@ -152,7 +215,7 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
         B16Img& NI = e->s_in_b[nl];
         CHK(NI.ensure(N, ncols, want_t));
         a.nx_b = NI.r(); a.ld_nxb = NI.ld; a.nx_bt = want_t ? NI.t() : (__bf16*)nullptr; a.ld_nxbt = NI.ldt;
-        a.nx_mul = (nl < Lc_ && rdrop_all) ? e->s_xmask[nl].as<float>() : (const float*)nullptr;
+        a.nx_mul = (nl < Lc_ && rdrop_all) ? W.xmask[nl].as<float>() : (const float*)nullptr;
         img_ready = true;
       }
     }
@@ -169,9 +232,25 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
       hipLaunchKernelGGL(sru_fwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
     }
     LAUNCH_CHECK();
-    in = e->s_h[l].as<float>();
+    in = W.h[l].as<float>();
     ld_in = ncols;
   }
+  *top = in; *ld_top = ld_in;
+  return GT_OK;
+}
+
+// x (N, in_dim) -> y_hat (N, out_dim): the generator's stack + hidden2out
+int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s) {
+  Net& G = e->net[GT_ROLE_G];
+  const long N = (long)B * T;
+  const int Lc_ = G.d.num_hidden;
+  const bool b16 = sru_b16(e, GT_ROLE_G);
+  const bool want_t = G.d.grads != nullptr;
+  const bool img_ready = sru_fold(e, GT_ROLE_G, B, T);      // hidden2out's input images were written by the last layer's scan
+  const int passes[1] = {0};
+  const float* in = nullptr;
+  int ld_in = 0;
+  CHK(sru_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &in, &ld_in));
   if (b16) {
     B16Img& I = e->s_in_b[Lc_];
     CHK(I.ensure(N, G.last.in, want_t));
@@ -187,20 +266,17 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
                         G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
 }
 
+// gy (N, out_dim) = dL/dy_hat -> parameter gradients of hidden2out and of every SRU layer of the generator
 int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Do = G.d.out_dim, Lc = G.d.num_hidden;
   const bool acc = G.grads_dirty;
-  int kmax = 3, inmax = ncols;
-  for (auto& L : G.sru) { kmax = std::max(kmax, L.k); inmax = std::max(inmax, L.in); }
+  int inmax = ncols;
+  for (auto& L : G.sru) inmax = std::max(inmax, L.in);
   CHK(e->l_dout.ensure((size_t)2 * N * std::max(ncols, inmax) * sizeof(float)));
-  CHK(e->s_du.ensure((size_t)N * ncols * kmax * sizeof(float)));
-  CHK(e->s_dx.ensure((size_t)2 * N * ncols * sizeof(float)));     // highway gradients of two consecutive layers (read by the layer underneath)
-  CHK(e->s_dbias.ensure((size_t)B * 2 * ncols * sizeof(float)));
   float* dh = e->l_dout.as<float>();
-  float* dh_other = dh + (size_t)N * std::max(ncols, inmax);
-  const bool b16 = sru_b16(e) && (int)e->s_in_b.size() == Lc + 1 && (int)e->ssh.size() == Lc + 1;
+  const bool b16 = sru_b16(e, GT_ROLE_G) && (int)e->s_in_b.size() == Lc + 1 && (int)e->ssh.size() == Lc + 1;
   if (b16) {
     CHK(e->gy_b.ensure(N, Do, true));
     CHK(cast_transpose(gy, Do, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
@@ -216,12 +292,42 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
   CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * ncols + Do, s));
   CHK(linear_backward_data(gy, Do, G.last.W, G.last.in, 0, dh, ncols, N, Do, ncols, ACT_NONE, nullptr, 0, no_drop(), s));
   }
+  const int passes[1] = {0};
+  return sru_stack_backward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, true, nullptr, s);
+}
+
+// From the gradient w.r.t. the top layer's h (first half of the role's `dout` buffer, row pitch ncols) down through the stack: weight and
+// bias gradients of every layer (want_w), and -- dx_adv != null, what a discriminator hands back to the generator -- the gradient w.r.t.
+// the adversarial columns [col0, col0 + Da) of the LAST row group's input rows (the generated sequences), written at pitch Da.  Only that
+// slice of d input is ever read (train.py:265,274,307-308), so only that slice is formed.
+int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, bool want_w,
+                       float* dx_adv, hipStream_t s) {
+  (void)passes;      // (the passes' dropout tables are the forward's stash)
+  Net& G = e->net[role];
+  SruBufs W = sru_bufs(e, role);
+  const SruPrecScope prec(role);
+  const int B = nseq;
+  const long N = (long)B * T;
+  const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Lc = G.d.num_hidden;
+  const bool acc = G.grads_dirty;
+  if (npass < 1 || nseq % npass) return fail(GT_ERR_INVALID, "SRU stack: %d sequences do not split into %d passes", nseq, npass);
+  int kmax = 3, inmax = ncols;
+  for (auto& L : G.sru) { kmax = std::max(kmax, L.k); inmax = std::max(inmax, L.in); }
+  // the generator's buffer is sized by sru_backward; a discriminator's holds two [N][ncols] halves (the head wrote the first one)
+  const size_t dh_pitch = role == GT_ROLE_G ? (size_t)std::max(ncols, inmax) : (size_t)ncols;
+  CHK(W.dout.ensure((size_t)2 * N * dh_pitch * sizeof(float)));
+  CHK(e->s_du.ensure((size_t)N * ncols * kmax * sizeof(float)));
+  CHK(e->s_dx.ensure((size_t)2 * N * ncols * sizeof(float)));     // highway gradients of two consecutive layers (read by the layer underneath)
+  CHK(e->s_dbias.ensure((size_t)B * 2 * ncols * sizeof(float)));
+  float* dh = W.dout.as<float>();
+  float* dh_other = dh + (size_t)N * dh_pitch;
+  const bool b16 = sru_b16(e, role) && (int)e->s_in_b.size() == Lc + 1 && (int)e->ssh.size() == Lc + 1;
   for (int l = Lc - 1; l >= 0; --l) {
     const SruLayerP& L = G.sru[l];
-    const float* in = l == 0 ? x : e->s_h[l - 1].as<float>();
-    const int ld_in = l == 0 ? G.d.in_dim : ncols;
+    const float* in = l == 0 ? x : W.h[l - 1].as<float>();
+    const int ld_in = l == 0 ? ld_x : ncols;
     const bool rdrop = G.training && G.d.rnn_dropout > 0.f;
-    SruArgs a = sru_args(e, G, l, B, T, in, ld_in);
+    SruArgs a = sru_args(e, role, W, l, B, T, in, ld_in);
     a.dh = dh; a.dU = e->s_du.as<float>();
     // k == 3: the highway gradient goes straight to the layer input.  Without input dropout it is
     // written into the next dh buffer and the GEMM below accumulates onto it.
@@ -229,9 +335,9 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
     float* dx_res = L.k == 3 ? (rdrop ? dx_of(l) : dh_other) : nullptr;
     a.dx = dx_res; a.lddx = ncols;
     if (rdrop && l + 1 < Lc) {      // dh is the raw dU.W^T of the layer above: its input dropout and highway gradient are applied by the scan
-      if (G.sru[l + 1].in != ncols || !e->s_xmask[l + 1].p)
+      if (G.sru[l + 1].in != ncols || !W.xmask[l + 1].p)
         return fail(GT_ERR_STATE, "SRU backward: layer %d's input-dropout table is missing or not %d wide", l + 1, ncols);
-      a.up_mul = e->s_xmask[l + 1].as<float>();
+      a.up_mul = W.xmask[l + 1].as<float>();
       a.up_add = G.sru[l + 1].k == 3 ? dx_of(l + 1) : nullptr;
       a.ld_up_add = ncols;
     }
@@ -259,10 +365,11 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
       hipLaunchKernelGGL(sru_bwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
     }
     LAUNCH_CHECK();
+    if (want_w) {      // (the generator step's pass through a discriminator launches no weight-gradient kernel: train.py:307-308)
     hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(2 * ncols, 64)), dim3(1024), 0, s, e->s_dbias.as<float>(), (long)2 * ncols, B,
                        2 * ncols, L.db, acc ? 1 : 0);
     LAUNCH_CHECK();
-    const float* xin = rdrop ? e->s_xdrop[l].as<float>() : in;
+    const float* xin = rdrop ? W.xdrop[l].as<float>() : in;
     const int ld_xin = rdrop ? L.in : ld_in;
     if (b16) {
       // dU -> bf16 image in both orientations (one pass); dW = xinT . dUT^T over the frames, d in = dU . W^T
@@ -278,8 +385,9 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
     CHK(linear_backward_weight(xin, ld_xin, e->s_du.as<float>(), ncols * L.k, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs,
                                e->colp, s));
     }
-    CHK(comm_grads_ready(e, GT_ROLE_G, L.dW, (long)L.in * ncols * L.k + 2L * ncols, s));
-    if (l > 0) CHK(comm_flush(e, GT_ROLE_G, s));
+    CHK(comm_grads_ready(e, role, L.dW, (long)L.in * ncols * L.k + 2L * ncols, s));
+    if (l > 0 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
+    }
     if (l > 0) {
       if (b16) {
         GemmB16Args g = b16_args();
@@ -298,9 +406,32 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
       }
       std::swap(dh, dh_other);         // (with input dropout: finished by the scan of layer l - 1, SruArgs::up_mul / up_add)
     }
-    // l == 0: no gradient with respect to the network input is produced on this path (nothing upstream of the generator
+    // l == 0, the generator: no gradient with respect to the network input is produced (nothing upstream of the generator
     // takes one: x is data, train.py:542).  NOTE for anything that wants to read `dh` between layers: with rnn_dropout it
     // is the RAW dU.W^T -- the input-dropout mask and the k = 3 highway term are applied by the next scan's loads.
+    if (l == 0 && dx_adv) {
+      // l == 0, a discriminator: d input of the generated rows' adversarial columns = dU0[generated rows] . W0[col0 .. col0 + Da, :]^T
+      // (NT, M = rows of the last group, N = Da, K = ncols * k) straight into the caller's [rows][Da] buffer, finished per element with
+      // layer 0's input-dropout multiplier and, k == 3, the highway gradient of the layer-0 scan (which by-passes the input dropout)
+      const int Da = e->Da, col0 = cond_dim(e);
+      if (col0 < 0 || col0 + Da > L.in) return fail(GT_ERR_DIM, "SRU discriminator: adversarial columns [%d, %d) outside in_dim %d", col0, col0 + Da, L.in);
+      const int Bf = nseq / npass;
+      const long Nf = (long)Bf * T, row0 = N - Nf;
+      GemmArgs g;
+      memset(&g, 0, sizeof(g));
+      g.A = e->s_du.as<float>() + (size_t)row0 * ncols * L.k; g.lda = ncols * L.k;
+      g.B = L.W + (size_t)col0 * ncols * L.k; g.ldb = ncols * L.k; g.C = dx_adv; g.ldc = Da;
+      g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
+      CHK(launch_gemm(GEMM_NT, g, 1, s));
+      if (rdrop || L.k == 3) {
+        SruDxAdvArgs f;
+        f.dx_adv = dx_adv; f.rows = Nf; f.Da = Da; f.T = T;
+        f.mul = rdrop ? W.xmask[0].as<float>() + (size_t)(nseq - Bf) * L.in + col0 : nullptr; f.ld_mul = L.in;
+        f.hw = L.k == 3 ? dx_res + (size_t)row0 * ncols + col0 : nullptr; f.ld_hw = ncols;
+        hipLaunchKernelGGL(sru_dx_adv_finish_kernel, dim3(cdiv(cdiv(Nf * Da, 4), 256)), dim3(256), 0, s, f);
+        LAUNCH_CHECK();
+      }
+    }
   }
   return GT_OK;
 }

@@ -840,11 +840,15 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   e->dcat_b_x = x; e->dcat_b_yhs = y_hat_static;
   // a recurrent discriminator (LSTMRNN in the discriminator slot, train.py:773-774): the natural and the generated sequences run as ONE
   // batch of 2B sequences through its stack (lengths twice), the fused head reads the top layer's output (hidden2out is its weight)
-  const bool d_rec = has_lstm_body(D.d.arch);
+  // (SRURNN in that slot: the same, sequence lengths ignored as in the reference)
+  const bool d_sru = D.d.arch == GT_ARCH_SRU;
+  const bool d_rec = has_lstm_body(D.d.arch) || d_sru;
   const bool fused = !d_rec && d_fused_ok(e, b16, 2 * N);        // layers 1 .. L-1 + the head as ONE launch (dstack_f32.hip.h)
   const float* rec_top = nullptr;
   int rec_ld = 0;
-  if (d_rec) {
+  if (d_sru) {
+    CHK(sru_stack_forward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, s, &rec_top, &rec_ld));
+  } else if (d_rec) {
     CHK(lstm_check_lengths(e, B, T));
     CHK(lstm_stack_forward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, s, &rec_top, &rec_ld));
   } else if (b16) {
@@ -897,7 +901,9 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     float* leak = nullptr;
     if (want_leak) { CHK(e->leak.ensure((size_t)N * e->Da * sizeof(float))); leak = e->leak.as<float>(); }
     const int col0 = cond_dim(e);
-    if (d_rec) {   // through the recurrent stack: weight gradients, and the gradient w.r.t. the [x | adv] rows when the generator wants it
+    if (d_sru) {   // through the SRU stack: weight gradients, and the generated rows' adversarial columns of d input straight into `leak`
+      CHK(sru_stack_backward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, true, leak, s));
+    } else if (d_rec) {   // through the recurrent stack: weight gradients, and the gradient w.r.t. the [x | adv] rows when the generator wants it
       float* dx0 = nullptr;
       if (leak) { CHK(e->d_dx0.ensure((size_t)2 * N * K0 * sizeof(float))); dx0 = e->d_dx0.as<float>(); }
       CHK(lstm_stack_backward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, true, dx0, s));
@@ -1170,12 +1176,15 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
       }
       cat = e->dcat.as<float>() + N * ldc;
     }
-    const bool d_rec = has_lstm_body(D.d.arch);
+    const bool d_sru = D.d.arch == GT_ARCH_SRU;
+    const bool d_rec = has_lstm_body(D.d.arch) || d_sru;
     // layers 1 .. L-1, the head and the backward-data chain down to the adversarial columns as ONE launch (dstack_f32.hip.h)
     const bool fused = !d_rec && d_fused_ok(e, b16, N);
     const float* rec_top = nullptr;
     int rec_ld = 0;
-    if (d_rec) {
+    if (d_sru) {
+      CHK(sru_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld));
+    } else if (d_rec) {
       CHK(lstm_check_lengths(e, B, T));
       CHK(lstm_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld));
     } else
@@ -1216,7 +1225,9 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
       CHK(e->gadv.ensure((size_t)N * e->Da * sizeof(float)));
       gadv = e->gadv.as<float>();
       const int col0 = cond_dim(e);
-      if (d_rec) {   // back through the recurrent stack to the generated rows' adversarial columns; no weight gradients (train.py:307-308)
+      if (d_sru) {   // back through the SRU stack to the generated rows' adversarial columns; no weight gradients (train.py:307-308)
+        CHK(sru_stack_backward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, false, gadv, s));
+      } else if (d_rec) {   // back through the recurrent stack to the generated rows' adversarial columns; no weight gradients (train.py:307-308)
         CHK(e->d_dx0.ensure((size_t)2 * N * K0 * sizeof(float)));
         float* dx0 = e->d_dx0.as<float>();
         CHK(lstm_stack_backward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, false, dx0, s));
@@ -1381,12 +1392,16 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
   const int pass0d[1] = {0};
   if (n.d.arch == GT_ARCH_LSTM || n.d.arch == GT_ARCH_SRU) {
     if (role != GT_ROLE_G) {
-      if (n.d.arch != GT_ARCH_LSTM) return fail(GT_ERR_INVALID, "the discriminator slot takes MLP and LSTMRNN networks");
       // the recurrent discriminator's plain forward: its stack, then hidden2out (+ sigmoid)
-      CHK(lstm_check_lengths(e, B, T));
       const float* top = nullptr;
       int ld = 0;
-      CHK(lstm_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));
+      if (n.d.arch == GT_ARCH_SRU) {
+        CHK(sru_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));
+        tl_gemm_prec = PREC_F32;      // GT_OPT_MATMUL_BF16: an SRU discriminator keeps float32 products, hidden2out included
+      } else {
+        CHK(lstm_check_lengths(e, B, T));
+        CHK(lstm_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));
+      }
       return linear_forward(top, ld, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in, n.last.out,
                             n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
     }

@@ -12,7 +12,7 @@
 //   * every reduction is two-stage with a fixed order => run-to-run bit-reproducible.
 //
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
-// of the two product families), eng_step (the G+D step and the MLP stacks), eng_lstm / eng_sru (recurrent generators),
+// of the two product families), eng_step (the G+D step and the MLP stacks), eng_lstm / eng_sru (recurrent stacks of either role),
 // eng_comm (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the
 // non-template ones have internal linkage (GT_KERNEL) so that several units may include them.
 #pragma once
@@ -322,7 +322,10 @@ struct gt_engine {
   int* d_lengths() { return len_slot < 0 ? nullptr : len_dev[len_slot].as<int>(); }
   std::vector<Scratch> s_wt;                                 // SRU float32 mode: transposed copies of the layers' W
   std::vector<Scratch> s_u, s_h, s_c, s_xdrop, s_xmask;     // SRU per-layer stashes (s_xmask: input-dropout multipliers [B][n_in])
-  Scratch s_du, s_dx, s_dbias;
+  Scratch s_du, s_dx, s_dbias;                                // backward temporaries of the layer in hand (either role)
+  // an SRU DISCRIMINATOR: its own stashes (the generator's must survive the discriminator passes of a step); ds_omask: output-dropout
+  // keep tables [nseq][ncols], one per layer, each row group of a launch drawn from its own pass
+  std::vector<Scratch> ds_wt, ds_u, ds_h, ds_c, ds_xdrop, ds_xmask, ds_omask;
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
@@ -452,3 +455,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
 int lstm_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s);
 int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s);
 int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s);
+int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
+                      const float** top, int* ld_top);
+int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, bool want_w,
+                       float* dx_adv, hipStream_t s);

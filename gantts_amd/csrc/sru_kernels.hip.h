@@ -239,4 +239,41 @@ __global__ void sru_input_dropout_kernel(const float* __restrict__ x, int ldx, f
   y[row * ldy + i] = x[row * ldx + i] * mul[(row / T) * n + i];
 }
 
+// The last step of a discriminator's gradient w.r.t. its input (eng_sru.hip: sru_stack_backward): g = dU0 . W0^T of the generated rows'
+// adversarial columns, dense [rows][Da], becomes  g * mul[b][j] + hw[row][j]  in place -- layer 0's variational input-dropout multiplier
+// (one per (sequence, column), shared over time; null: 1) and the k = 3 highway gradient of the layer-0 scan (null: 0).  mul / hw point at
+// the first generated sequence / row and the first adversarial column.  One lane owns four consecutive elements of the dense buffer:
+// one 16-byte load and store of g where the buffer allows, the gathered operands element by element.
+struct SruDxAdvArgs {
+  float* dx_adv; long rows; int Da, T;
+  const float* mul; int ld_mul;
+  const float* hw; int ld_hw;
+};
+__global__ __launch_bounds__(256) void sru_dx_adv_finish_kernel(const SruDxAdvArgs a) {
+  const long total = a.rows * a.Da;
+  const long e0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (e0 >= total) return;
+  const bool vec = e0 + 4 <= total && (((uintptr_t)a.dx_adv & 15) == 0);
+  float g[4];
+  if (vec) { const float4 v = *(const float4*)(a.dx_adv + e0); g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w; }
+  else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q] = e0 + q < total ? a.dx_adv[e0 + q] : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const long e = min(e0 + q, total - 1);
+    const long row = e / a.Da;
+    const int j = (int)(e - row * a.Da);
+    const float m = a.mul ? a.mul[(row / a.T) * a.ld_mul + j] : 1.f;
+    const float h = a.hw ? a.hw[row * a.ld_hw + j] : 0.f;
+    g[q] = fmaf(g[q], m, h);
+  }
+  if (vec) *(float4*)(a.dx_adv + e0) = make_float4(g[0], g[1], g[2], g[3]);
+  else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (e0 + q < total) a.dx_adv[e0 + q] = g[q];
+  }
+}
+
 }  // namespace gt

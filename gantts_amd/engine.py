@@ -347,7 +347,8 @@ class StepEngine(object):
         return mask
 
     def _d_lengths(self, model_d, lengths, B, T):
-        """A recurrent discriminator (LSTMRNN in the discriminator slot, train.py:773-774) packs by `lengths` (train.py:262, 268, 307)."""
+        """A recurrent discriminator (train.py:773-774) that packs by `lengths` (LSTMRNN; train.py:262, 268, 307) gets them; an
+        MLP or an SRURNN in that slot ignores them, as in the reference."""
         if getattr(model_d, "needs_lengths", False):
             self.set_lengths(lengths, B, T)
 

@@ -333,9 +333,11 @@ class SRURNN(_FlatNetwork):
     def set_dropout_masks(self, pass_index, masks):
         """Parity hook for the SRU cell's variational dropout: ``masks`` in the order a forward pass draws them --
         per layer the input mask (B, n_in) if ``rnn_dropout > 0``, then the output mask (B, H*dirs) if ``dropout > 0``
-        and the layer is not the last -- as 0/1 keep tensors; ``None`` restores the Philox stream."""
-        if pass_index != 0:
-            raise ValueError("recurrent generators have a single forward pass (index 0)")
+        and the layer is not the last -- as 0/1 keep tensors; ``None`` restores the Philox stream of that pass.
+        ``pass_index`` 0: a generator's pass / D(real); 1, 2: D(fake) of the D and of the G step (an SRURNN in the
+        discriminator slot); the passes are kept apart."""
+        if pass_index not in (0, 1, 2):
+            raise ValueError("pass_index must be 0, 1 or 2")
         masks = list(masks) if masks is not None else None
         ncols = self.hidden_dim * self.num_direction
         for layer in range(self.num_hidden):
@@ -348,7 +350,7 @@ class SRURNN(_FlatNetwork):
                     m = masks.pop(0).to(self._flat.device, torch.float32).contiguous()
                     if m.dim() != 2 or m.size(1) != width:
                         raise ValueError("SRU layer %d %s mask must be (B, %d), got %s" % (layer, "input" if which == 0 else "output", width, tuple(m.shape)))
-                self._masks[(0, 2 * layer + which)] = m
+                self._masks[(pass_index, 2 * layer + which)] = m
         if masks:
             raise ValueError("too many dropout masks for this SRURNN")
         self._version += 1

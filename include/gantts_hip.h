@@ -155,8 +155,10 @@ const char* gt_version(void);
 int gt_engine_create(const gt_stream_config* cfg, gt_engine** out);
 void gt_engine_destroy(gt_engine* e);
 
-/* getattr(gantts.models, name)(**params) + .cuda()            (train.py:773-793).  GT_ROLE_G: every architecture; GT_ROLE_D: GT_ARCH_MLP
- * or GT_ARCH_LSTM (an LSTMRNN scoring frames), out_dim 1, last_sigmoid set; other combinations are rejected (GT_ERR_INVALID). */
+/* getattr(gantts.models, name)(**params) + .cuda()            (train.py:773-793).  GT_ROLE_G: every architecture; GT_ROLE_D: GT_ARCH_MLP,
+ * GT_ARCH_LSTM (an LSTMRNN scoring frames) or GT_ARCH_SRU (an SRURNN scoring frames: sequence lengths ignored as in the reference, at
+ * most 8 layers; parity unpinned like every SRU path), out_dim 1, last_sigmoid set, for the recurrent ones hidden_dim x directions
+ * <= 1024; other combinations (the tuple-returning In2Out* among them) are rejected (GT_ERR_INVALID). */
 int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc);
 /* getattr(optim, hp.optimizer_*)(model.parameters(), **params) (train.py:796-799) */
 int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* desc);
@@ -175,7 +177,8 @@ int gt_set_seed(gt_engine* e, uint64_t seed);
  * passes: G: 0 = apply_generator.  D: 0 = real rows of the D step, 1 = generated rows of the
  * D step, 2 = generated rows of the G step (the order nn.Dropout is consumed in train.py:261-307).
  * SRURNN (models.py:152-154: rnn_dropout / dropout of the SRU cell are VARIATIONAL masks, one per sequence and shared
- * over time): `layer` = 2*l selects the input mask of SRU layer l, shape (B, n_in_l); 2*l + 1 its output mask, (B, H*dirs). */
+ * over time): `layer` = 2*l selects the input mask of SRU layer l, shape (B, n_in_l); 2*l + 1 its output mask, (B, H*dirs); an
+ * SRURNN in the discriminator slot takes them per pass like every discriminator. */
 int gt_set_dropout_mask(gt_engine* e, int role, int pass, int layer, const float* mask);
 /* Parity hook for the production (Philox) dropout path, nn.Dropout inside gantts/models.py:132-139: writes the 0/1 keep
  * mask ((rows, cols) contiguous, device) that the engine's counter-based stream assigns to dropout site (role, pass,
@@ -245,7 +248,9 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
 /* GT_OPT_MATMUL_BF16 (default 0): mixed precision for the frame x weight products of BOTH networks (BASELINE.json
  * configs[2]): operands are rounded to bfloat16 inside the GEMM and multiplied on the bf16 matrix cores with float32
  * accumulation; parameters ("master weights"), optimizer state, activations in memory, the recurrent state and every
- * reduction stay float32.  Results differ from the float32 path at the 1e-2 relative level (tests/test_gpu_parity.py). */
+ * reduction stay float32.  Results differ from the float32 path at the 1e-2 relative level (tests/test_gpu_parity.py).
+ * An SRURNN in the discriminator slot keeps float32 products and float32 stashes under this option (an SRURNN generator takes the
+ * bf16 path). */
 #define GT_OPT_MATMUL_BF16 5
 /* GT_OPT_SPLIT_FIRST_LAYER (default 1): the conditioned float32 discriminator evaluates its first layer as x . W_x^T (once per
  * D step, shared by the real and the generated rows) + adv . W_adv^T instead of one product over a concatenated [x | adv] image

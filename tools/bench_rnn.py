@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """cfg3-shaped measurement (BASELINE.json configs[2], fp32 here): BiLSTM generator 3x256 + conditioned MLP D,
-B sequences x T frames, variable lengths.  Prints ms/step and frames/s (GPU box only)."""
+B sequences x T frames, variable lengths.  --disc puts a recurrent network of equal widths (2 x 256 bidirectional LSTM or SRU,
+483 -> 1) into the discriminator slot.  Prints ms/step and frames/s (GPU box only)."""
 import argparse
 import os
 import sys
@@ -19,7 +20,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
 ap.add_argument("--frames", type=int, default=1024)
 ap.add_argument("--steps", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=1, help="untimed steps in front of the timed ones")
 ap.add_argument("--gen", default="lstm", choices=["lstm", "sru", "mlp"])
+ap.add_argument("--disc", default="mlp", choices=["mlp", "lstm", "sru"], help="the discriminator (default: cfg2 / cfg3's conditioned 3 x 256 MLP)")
 ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                 help="bf16: GEMM operands rounded to bfloat16, f32 accumulation, f32 master weights / state (GT_OPT_MATMUL_BF16)")
 args = ap.parse_args()
@@ -33,7 +36,12 @@ elif args.gen == "lstm":
 else:   # hparams.tts_acoustic default generator (hparams.py:211-222)
     mg = models.SRURNN(in_dim=425, out_dim=187, num_hidden=6, hidden_dim=512, bidirectional=True, dropout=0.2,
                        use_relu=1, rnn_dropout=0.2).cuda().train()
-md = models.MLP(in_dim=483, out_dim=1, num_hidden=3, hidden_dim=256, dropout=0.5, last_sigmoid=True).cuda().train()
+if args.disc == "mlp":
+    md = models.MLP(in_dim=483, out_dim=1, num_hidden=3, hidden_dim=256, dropout=0.5, last_sigmoid=True).cuda().train()
+elif args.disc == "lstm":
+    md = models.LSTMRNN(483, 1, num_hidden=2, hidden_dim=256, bidirectional=True, last_sigmoid=True).cuda().train()
+else:
+    md = models.SRURNN(483, 1, num_hidden=2, hidden_dim=256, bidirectional=True, last_sigmoid=True, use_relu=1).cuda().train()
 og, od = optim.Adagrad(mg.parameters(), lr=0.01, weight_decay=1e-7), optim.Adagrad(md.parameters(), lr=0.01, weight_decay=1e-7)
 g = torch.Generator().manual_seed(0)
 x = torch.rand(B, Tn, 425, generator=g).cuda()
@@ -57,7 +65,8 @@ def step():
     return d, gg
 
 
-step()
+for _ in range(max(1, args.warmup)):
+    step()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(args.steps):
@@ -65,4 +74,5 @@ for _ in range(args.steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / args.steps
 name = {"lstm": "cfg3 BiLSTM 3x256", "sru": "SRU 6x512 bi (hparams default G)", "mlp": "cfg2 MLP 3x512"}[args.gen]
-print("%s %s B=%d T=%d: %.2f ms/step, %.0f padded frames/s, scalars %s" % (name, args.dtype, B, Tn, dt * 1e3, B * Tn / dt, out))
+dname = {"mlp": "MLP 3x256", "lstm": "BiLSTM 2x256", "sru": "SRU 2x256 bi"}[args.disc]
+print("%s + D %s %s B=%d T=%d: %.2f ms/step, %.0f padded frames/s, scalars %s" % (name, dname, args.dtype, B, Tn, dt * 1e3, B * Tn / dt, out))
