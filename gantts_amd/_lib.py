@@ -22,6 +22,7 @@ OPT_LSTM_PERSISTENT, OPT_LSTM_FWD_UNITS, OPT_LSTM_XCD_LOCAL, OPT_MATMUL_BF16, OP
 OPT_COMM_D_ONE_MSG, OPT_COMM_EARLY_G, OPT_COMM_FORCE = 10, 11, 13      # (7, 8, 9, 12: retired, not reused)
 OPT_LAUNCH_RIDERS, OPT_COMM_CLOSE_INLINE, OPT_POLL_RESULTS = 14, 15, 16
 OPT_COMM_TV_IN_SUMS, OPT_COMM_IPC, OPT_FUSED_DSTACK = 17, 18, 19
+OPT_SRU_D_BF16 = 20
 IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts

@@ -175,6 +175,9 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   for (auto& b : e->s_in_b) b.release();
   e->s_du_b.release();
   for (auto& w : e->ssh) { w.w.release(); w.wt.release(); }
+  for (auto& b : e->ds_in_b) b.release();
+  e->ds_du_b.release();
+  for (auto& w : e->dssh) { w.w.release(); w.wt.release(); }
   for (auto& b : e->l_dg_b) b.release();
   e->l_hs_b.release();
   for (auto& w : e->lsh) { w.w.release(); w.wt.release(); }
@@ -400,6 +403,12 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
         e->d_begin_done = false; e->g_begin_done = false;
       }
       e->matmul_bf16 = value != 0;
+      return GT_OK;
+    case GT_OPT_SRU_D_BF16:
+      if (value != 0 && value != 1) return fail(GT_ERR_INVALID, "GT_OPT_SRU_D_BF16 takes 0 or 1, not %d", value);
+      // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
+      if (e->sru_d_bf16 != (value != 0)) { e->fake_cat_valid = false; e->leak_pending = false; e->d_begin_done = false; e->g_begin_done = false; }
+      e->sru_d_bf16 = value != 0;
       return GT_OK;
   }
   return fail(GT_ERR_INVALID, "unknown option %d", option);

@@ -26,15 +26,23 @@ static uint32_t drop_thresh(float p) {
 // The stashes of one role's SRU stack.  The discriminator has its own: the generator's forward stash has to survive both discriminator
 // passes of a step (update_generator back-propagates it last); the D-step stash is dead after the D step and the G-step pass reuses it.
 // omask: the discriminator's output-dropout keep tables [nseq][ncols] (0 / 1), one table for all row groups of a launch.
+// in_b / ssh / du_b: the bf16 images, weight shadows and dU image of the role's bf16 path -- role-owned as well: the generator's
+// in_b[l].t() and ssh[l] are read by sru_backward after both discriminator passes of a step.
 struct SruBufs {
   std::vector<Scratch>&u, &h, &c, &xdrop, &xmask, &wt;
   std::vector<Scratch>* omask;
   Scratch& dout;
+  std::vector<B16Img>& in_b;
+  std::vector<LinShadow>& ssh;
+  B16Img& du_b;
 };
 static SruBufs sru_bufs(gt_engine* e, int role) {
-  if (role == GT_ROLE_G) return SruBufs{e->s_u, e->s_h, e->s_c, e->s_xdrop, e->s_xmask, e->s_wt, nullptr, e->l_dout};
-  return SruBufs{e->ds_u, e->ds_h, e->ds_c, e->ds_xdrop, e->ds_xmask, e->ds_wt, &e->ds_omask, e->dl_dout};
+  if (role == GT_ROLE_G) return SruBufs{e->s_u, e->s_h, e->s_c, e->s_xdrop, e->s_xmask, e->s_wt, nullptr, e->l_dout, e->s_in_b, e->ssh, e->s_du_b};
+  return SruBufs{e->ds_u, e->ds_h, e->ds_c, e->ds_xdrop, e->ds_xmask, e->ds_wt, &e->ds_omask, e->dl_dout, e->ds_in_b, e->dssh, e->ds_du_b};
 }
+// entries of in_b / ssh: one per layer; the generator has one more for hidden2out's product (a discriminator's top h goes to the fused
+// head as float32, which holds hidden2out and its gradient)
+static int sru_b16_entries(const gt_engine* e, int role) { return e->net[role].d.num_hidden + (role == GT_ROLE_G ? 1 : 0); }
 
 // One variational dropout table [nseq][width] of layer `l` (which: 0 input, 1 output): every row group of the launch (the D step runs
 // D(real) and D(fake) as ONE batch of 2B sequences) draws from its own pass -- its own Philox key, or its own injected 0/1 mask.
@@ -89,9 +97,17 @@ static int sru_coop_waves(long B, int ncols) {
 // Measured and dropped (round 4, gpurun_out/r4k): 32 columns per workgroup (twice the recurrence waves per CU, half of every wave
 // idle) for the shapes that give fewer than three 64-column workgroups per CU -- cfg4 (B = 16, T = 2048) 11.36 vs 10.84 ms, the
 // hparams-default generator at B = 32 9.49 vs 9.32 ms: the scan is not bound by one wave's per-frame latency.
-// GT_OPT_MATMUL_BF16 per role: the generator's stack takes the bf16 images; a discriminator's keeps float32 products and stashes
-static bool sru_b16(const gt_engine* e, int role) { return role == GT_ROLE_G && e->matmul_bf16 && (e->net[GT_ROLE_G].d.hidden_dim & 7) == 0; }
-// (a discriminator's products stay in the float32 family for the duration of its stack calls)
+// bf16 storage per role: GT_OPT_MATMUL_BF16 puts the generator's stack on the bf16 images; a discriminator's stays float32 under it and
+// has its own switch, GT_OPT_SRU_D_BF16.  Either needs hidden_dim % 8 == 0 (16-byte rows of the images), else float32.
+bool sru_b16(const gt_engine* e, int role) {
+  return (role == GT_ROLE_G ? e->matmul_bf16 : e->sru_d_bf16) && (e->net[role].d.hidden_dim & 7) == 0;
+}
+// a discriminator on the bf16 path reads its [x | adv] rows as float32 only where layer 0's scan takes them as the highway input x'
+bool sru_d_needs_f32_input(const gt_engine* e) {
+  const Net& D = e->net[GT_ROLE_D];
+  return !sru_b16(e, GT_ROLE_D) || D.sru.empty() || D.sru[0].k == 3;
+}
+// (whatever a discriminator's stack calls through the precision-dispatched float32 helpers stays in the float32 family)
 struct SruPrecScope {
   int saved;
   explicit SruPrecScope(int role) : saved(tl_gemm_prec) { if (role != GT_ROLE_G) tl_gemm_prec = PREC_F32; }
@@ -108,7 +124,7 @@ static bool sru_fold(const gt_engine* e, int role, int nseq, int T) {
 // the dropout passes of the row groups (the D step runs the natural and the generated sequences as ONE batch of 2B: two groups of
 // nseq / 2 sequences).  Sequence lengths are ignored, as in the reference.  *top / *ld_top: the top layer's h.
 int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
-                      const float** top, int* ld_top) {
+                      const float** top, int* ld_top, const CatSrc* cat0, bool want_w) {
   Net& G = e->net[role];
   SruBufs W = sru_bufs(e, role);
   const SruPrecScope prec(role);
@@ -121,12 +137,13 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
   // GT_OPT_MATMUL_BF16: the (dropped) layer inputs go through bf16 images in both orientations, W through bf16 shadows in
   // both orientations: U = xin . WT^T, dW = xinT . dUT^T, d in = dU . W^T are all the k-contiguous bf16 product
   const bool b16 = sru_b16(e, role);
-  const bool want_t = G.d.grads != nullptr;
-  const int Lc_ = G.d.num_hidden;
-  if (b16) {
-    e->s_in_b.resize(Lc_ + 1); e->ssh.resize(Lc_ + 1);
-    for (int l = 0; l <= Lc_; ++l) {
-      LinShadow& w = e->ssh[l];
+  const bool want_t = G.d.grads != nullptr && want_w;      // the transposed images feed the weight gradients only
+  const int Lc_ = G.d.num_hidden, nent = sru_b16_entries(e, role);
+  if (!(b16 && cat0) && !x) return fail(GT_ERR_INVALID, "SRU stack: null input");
+  if (b16) {      // the shadows are re-made at every call: a discriminator's weights change between the two passes of one step
+    W.in_b.resize(nent); W.ssh.resize(nent);
+    for (int l = 0; l < nent; ++l) {
+      LinShadow& w = W.ssh[l];
       const float* Wl = l < Lc_ ? G.sru[l].W : G.last.W;
       const int rows = l < Lc_ ? G.sru[l].in : G.last.out, cols = l < Lc_ ? ncols * G.sru[l].k : G.last.in;
       w.ldw = pad8(cols); w.ldwt = pad8(rows);
@@ -170,10 +187,20 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       ld_xin = L.in;
     }
     if (b16) {
-      B16Img& I = e->s_in_b[l];
+      B16Img& I = W.in_b[l];
       CHK(I.ensure(N, L.in, want_t));
       if (img_ready) {
         // written by the scan of the layer underneath (SruArgs::nx_*): no cast pass
+      } else if (l == 0 && cat0) {   // a discriminator's [x | adv] rows: one pass from the caller's tensors to both images, dropout riding along
+        if (rdrop) {
+          const CatDropSrc src{*cat0, W.xmask[0].as<float>(), T, L.in};
+          hipLaunchKernelGGL(catdrop_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, src, N, L.in, I.r(), I.ld,
+                             want_t ? I.t() : (__bf16*)nullptr, I.ldt);
+        } else {
+          hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, *cat0, N, L.in, I.r(), I.ld,
+                             want_t ? I.t() : (__bf16*)nullptr, I.ldt);
+        }
+        LAUNCH_CHECK();
       } else if (rdrop) {            // bf16 products: dropout rides in the cast, the dropped input exists as bf16 images only
         const SeqDropSrc src{in, ld_in, W.xmask[l].as<float>(), T, L.in};
         hipLaunchKernelGGL(seqdrop_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, src, N, L.in, I.r(), I.ld,
@@ -183,7 +210,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
         CHK(cast_transpose(xin, ld_xin, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
       }
       GemmB16Args g = b16_args();
-      g.A = I.r(); g.lda = I.ld; g.B = e->ssh[l].wt.as<__bf16>(); g.ldb = e->ssh[l].ldwt;     // WT [ncols*k][n_in]: k = n_in contiguous
+      g.A = I.r(); g.lda = I.ld; g.B = W.ssh[l].wt.as<__bf16>(); g.ldb = W.ssh[l].ldwt;     // WT [ncols*k][n_in]: k = n_in contiguous
       g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
       CHK(launch_gemm_b16(g, 1, s));
     } else if ((L.in & 3) == 0 && N >= 4096) {
@@ -211,8 +238,8 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
     if (fold) {       // the images of the product behind this layer: layer l + 1's input (its dropout applied), or hidden2out's
       const int nl = l + 1;
       const int n_in_next = nl < Lc_ ? G.sru[nl].in : G.last.in;
-      if (n_in_next == ncols) {
-        B16Img& NI = e->s_in_b[nl];
+      if (nl < nent && n_in_next == ncols) {      // (a discriminator's top layer writes none: the fused head reads the float32 h)
+        B16Img& NI = W.in_b[nl];
         CHK(NI.ensure(N, ncols, want_t));
         a.nx_b = NI.r(); a.ld_nxb = NI.ld; a.nx_bt = want_t ? NI.t() : (__bf16*)nullptr; a.ld_nxbt = NI.ldt;
         a.nx_mul = (nl < Lc_ && rdrop_all) ? W.xmask[nl].as<float>() : (const float*)nullptr;
@@ -321,7 +348,8 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
   CHK(e->s_dbias.ensure((size_t)B * 2 * ncols * sizeof(float)));
   float* dh = W.dout.as<float>();
   float* dh_other = dh + (size_t)N * dh_pitch;
-  const bool b16 = sru_b16(e, role) && (int)e->s_in_b.size() == Lc + 1 && (int)e->ssh.size() == Lc + 1;
+  const int nent = sru_b16_entries(e, role);
+  const bool b16 = sru_b16(e, role) && (int)W.in_b.size() == nent && (int)W.ssh.size() == nent;
   for (int l = Lc - 1; l >= 0; --l) {
     const SruLayerP& L = G.sru[l];
     const float* in = l == 0 ? x : W.h[l - 1].as<float>();
@@ -345,10 +373,11 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
     // bf16 storage with the cooperative scans, whole blocks of 8 frames, whole workgroups inside one sequence and one direction: dU
     // leaves the scan as the bf16 images the two products read (no float32 dU, no cast pass)
     const bool du_b16 = b16 && sru_coop() && T % 8 == 0 && H % 64 == 0;
+    // (want_w == false, the generator step's pass through a discriminator: the transposed image feeds dW alone and is not written)
     if (du_b16) {
-      B16Img& DU = e->s_du_b;
-      CHK(DU.ensure(N, ncols * L.k, true));
-      a.dU = nullptr; a.dU_b = DU.r(); a.ld_dub = DU.ld; a.dU_bt = DU.t(); a.ld_dubt = DU.ldt;
+      B16Img& DU = W.du_b;
+      CHK(DU.ensure(N, ncols * L.k, want_w));
+      a.dU = nullptr; a.dU_b = DU.r(); a.ld_dub = DU.ld; a.dU_bt = want_w ? DU.t() : (__bf16*)nullptr; a.ld_dubt = DU.ldt;
     }
     if (sru_coop()) {
       const int grid = cdiv((long)B * ncols, 64);
@@ -365,6 +394,12 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
       hipLaunchKernelGGL(sru_bwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
     }
     LAUNCH_CHECK();
+    if (b16 && !du_b16) {      // dU -> bf16 image in both orientations (one pass)
+      B16Img& DU = W.du_b;
+      CHK(DU.ensure(N, ncols * L.k, want_w));
+      CHK(cast_transpose(e->s_du.as<float>(), ncols * L.k, N, ncols * L.k, DU.r(), DU.ld, want_w ? DU.t() : (__bf16*)nullptr, DU.ldt, nullptr, false,
+                         &e->colp, s));
+    }
     if (want_w) {      // (the generator step's pass through a discriminator launches no weight-gradient kernel: train.py:307-308)
     hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(2 * ncols, 64)), dim3(1024), 0, s, e->s_dbias.as<float>(), (long)2 * ncols, B,
                        2 * ncols, L.db, acc ? 1 : 0);
@@ -372,13 +407,9 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
     const float* xin = rdrop ? W.xdrop[l].as<float>() : in;
     const int ld_xin = rdrop ? L.in : ld_in;
     if (b16) {
-      // dU -> bf16 image in both orientations (one pass); dW = xinT . dUT^T over the frames, d in = dU . W^T
-      B16Img& DU = e->s_du_b;
-      if (!du_b16) {
-        CHK(DU.ensure(N, ncols * L.k, true));
-        CHK(cast_transpose(e->s_du.as<float>(), ncols * L.k, N, ncols * L.k, DU.r(), DU.ld, DU.t(), DU.ldt, nullptr, false, &e->colp, s));
-      }
-      B16Img& I = e->s_in_b[l];
+      // dW = xinT . dUT^T over the frames, d in = dU . W^T
+      B16Img& DU = W.du_b;
+      B16Img& I = W.in_b[l];
       CHK(weight_grad_b16(I.t(), I.ldt, DU.t(), DU.ldt, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs, s));
     } else {
     // dW = xin^T dU   (TN: A = xin is m-contiguous over n_in, B = dU)
@@ -391,7 +422,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
     if (l > 0) {
       if (b16) {
         GemmB16Args g = b16_args();
-        g.A = e->s_du_b.r(); g.lda = e->s_du_b.ld; g.B = e->ssh[l].w.as<__bf16>(); g.ldb = e->ssh[l].ldw;    // W [n_in][ncols*k]: k contiguous
+        g.A = W.du_b.r(); g.lda = W.du_b.ld; g.B = W.ssh[l].w.as<__bf16>(); g.ldb = W.ssh[l].ldw;    // W [n_in][ncols*k]: k contiguous
         g.M = (int)N; g.N = L.in; g.K = ncols * L.k; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dh_other; g.ldc = L.in;
         g.accumulate = (L.k == 3 && !rdrop) ? 1 : 0;
         CHK(launch_gemm_b16(g, 1, s));
@@ -417,12 +448,20 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
       if (col0 < 0 || col0 + Da > L.in) return fail(GT_ERR_DIM, "SRU discriminator: adversarial columns [%d, %d) outside in_dim %d", col0, col0 + Da, L.in);
       const int Bf = nseq / npass;
       const long Nf = (long)Bf * T, row0 = N - Nf;
+      if (b16) {      // the bf16 product from the dU image's row offset and the row slice of the layer-0 shadow (both 16-byte aligned: pitches % 8 == 0)
+        GemmB16Args g = b16_args();
+        g.A = W.du_b.r() + (size_t)row0 * W.du_b.ld; g.lda = W.du_b.ld;
+        g.B = W.ssh[0].w.as<__bf16>() + (size_t)col0 * W.ssh[0].ldw; g.ldb = W.ssh[0].ldw;
+        g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dx_adv; g.ldc = Da;
+        CHK(launch_gemm_b16(g, 1, s));
+      } else {
       GemmArgs g;
       memset(&g, 0, sizeof(g));
       g.A = e->s_du.as<float>() + (size_t)row0 * ncols * L.k; g.lda = ncols * L.k;
       g.B = L.W + (size_t)col0 * ncols * L.k; g.ldb = ncols * L.k; g.C = dx_adv; g.ldc = Da;
       g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
       CHK(launch_gemm(GEMM_NT, g, 1, s));
+      }
       if (rdrop || L.k == 3) {
         SruDxAdvArgs f;
         f.dx_adv = dx_adv; f.rows = Nf; f.Da = Da; f.T = T;

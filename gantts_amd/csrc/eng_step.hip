@@ -792,6 +792,21 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   if (!split) CHK(dense_cx(e, &x, N, s));        // pitched rows are read in place by the split first layer only
   FirstSplit fs;
   memset(&fs, 0, sizeof(fs));
+  // GT_OPT_SRU_D_BF16: the SRU stack writes layer 0's bf16 images straight from x / y_static / y_hat_static (sru_cat0); the float32
+  // image is built only where layer 0's scan reads it (k == 3: the undropped rows are its highway input x')
+  const bool sru_d16 = D.d.arch == GT_ARCH_SRU && sru_b16(e, GT_ROLE_D);
+  CatSrc sru_cat0;
+  memset(&sru_cat0, 0, sizeof(sru_cat0));
+  if (sru_d16) {
+    if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
+      return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
+    sru_cat0.x = x; sru_cat0.cd = cond_dim(e); sru_cat0.fa = y_static; sru_cat0.fb = y_hat_static; sru_cat0.ldf = e->Ds; sru_cat0.idx = e->d_adv_cols;
+    sru_cat0.N = N; sru_cat0.row_off = 0;
+  }
+  if (sru_d16 && !sru_d_needs_f32_input(e)) {
+    e->fake_cat_valid = false;                   // the float32 image was not built
+    e->adv2_fake_ok = false;
+  } else
   if (b16) {
     // bf16 storage: the image is written ONCE, as bf16, in both orientations (no float32 image at all)
     if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
@@ -847,7 +862,8 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   const float* rec_top = nullptr;
   int rec_ld = 0;
   if (d_sru) {
-    CHK(sru_stack_forward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, s, &rec_top, &rec_ld));
+    CHK(sru_stack_forward(e, GT_ROLE_D, sru_d_needs_f32_input(e) ? e->dcat.as<float>() : (const float*)nullptr, ldc, 2 * B, T, passes, 2, s, &rec_top,
+                          &rec_ld, sru_d16 ? &sru_cat0 : nullptr, tr));
   } else if (d_rec) {
     CHK(lstm_check_lengths(e, B, T));
     CHK(lstm_stack_forward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, s, &rec_top, &rec_ld));
@@ -902,7 +918,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     if (want_leak) { CHK(e->leak.ensure((size_t)N * e->Da * sizeof(float))); leak = e->leak.as<float>(); }
     const int col0 = cond_dim(e);
     if (d_sru) {   // through the SRU stack: weight gradients, and the generated rows' adversarial columns of d input straight into `leak`
-      CHK(sru_stack_backward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, true, leak, s));
+      CHK(sru_stack_backward(e, GT_ROLE_D, sru_d_needs_f32_input(e) ? e->dcat.as<float>() : (const float*)nullptr, ldc, 2 * B, T, passes, 2, true, leak, s));
     } else if (d_rec) {   // through the recurrent stack: weight gradients, and the gradient w.r.t. the [x | adv] rows when the generator wants it
       float* dx0 = nullptr;
       if (leak) { CHK(e->d_dx0.ensure((size_t)2 * N * K0 * sizeof(float))); dx0 = e->d_dx0.as<float>(); }
@@ -1168,7 +1184,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
         e->adv2_fake_ok = true; e->adv2_yhs = y_hat_static;
       }
       fs.x = x; fs.ldx = cx_pitch(e); fs.cd = cond_dim(e); fs.adv = fake; fs.ld_adv = e->ld_adv2; fs.wrap = N;
-    } else if (!b16) {
+    } else if (!b16 && !(D.d.arch == GT_ARCH_SRU && !sru_d_needs_f32_input(e))) {
       CHK(e->dcat.ensure((size_t)2 * N * ldc * sizeof(float)));
       if (!(e->fake_cat_valid && e->fake_cat_x == x && e->fake_cat_yhs == y_hat_static)) {
         CHK(build_cat(e, x, y_hat_static, Ds, N, N, ldc, s));
@@ -1183,7 +1199,16 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     const float* rec_top = nullptr;
     int rec_ld = 0;
     if (d_sru) {
-      CHK(sru_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld));
+      // GT_OPT_SRU_D_BF16: layer 0's row-major image of the generated rows straight from x / y_hat_static; no transposed images (no weight gradients)
+      CatSrc src;
+      memset(&src, 0, sizeof(src));
+      const bool d16 = sru_b16(e, GT_ROLE_D);
+      if (d16) {
+        if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
+          return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
+        src.x = x; src.cd = cond_dim(e); src.fa = y_hat_static; src.fb = y_hat_static; src.ldf = Ds; src.idx = e->d_adv_cols; src.N = N; src.row_off = N;
+      }
+      CHK(sru_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld, d16 ? &src : nullptr, false));
     } else if (d_rec) {
       CHK(lstm_check_lengths(e, B, T));
       CHK(lstm_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld));
@@ -1396,8 +1421,8 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
       const float* top = nullptr;
       int ld = 0;
       if (n.d.arch == GT_ARCH_SRU) {
-        CHK(sru_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));
-        tl_gemm_prec = PREC_F32;      // GT_OPT_MATMUL_BF16: an SRU discriminator keeps float32 products, hidden2out included
+        CHK(sru_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld, nullptr, false));      // (GT_OPT_SRU_D_BF16: the stack's products on bf16 images)
+        tl_gemm_prec = PREC_F32;      // hidden2out stays a float32 product under either bf16 option
       } else {
         CHK(lstm_check_lengths(e, B, T));
         CHK(lstm_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));

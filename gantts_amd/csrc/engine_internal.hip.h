@@ -326,6 +326,13 @@ struct gt_engine {
   // an SRU DISCRIMINATOR: its own stashes (the generator's must survive the discriminator passes of a step); ds_omask: output-dropout
   // keep tables [nseq][ncols], one per layer, each row group of a launch drawn from its own pass
   std::vector<Scratch> ds_wt, ds_u, ds_h, ds_c, ds_xdrop, ds_xmask, ds_omask;
+  // GT_OPT_SRU_D_BF16: that discriminator's products through the bf16-storage family.  Its images, shadows and dU image are its OWN:
+  // the generator's s_in_b[l].t() and ssh[l] are read by sru_backward AFTER both discriminator passes of a step.  ds_in_b has no
+  // top entry (the fused head reads the float32 h) and dssh none for hidden2out (its product lives in the head kernel).
+  bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);
+  std::vector<B16Img> ds_in_b;
+  B16Img ds_du_b;
+  std::vector<LinShadow> dssh;
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
@@ -455,7 +462,11 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
 int lstm_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s);
 int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s);
 int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s);
+// cat0 (a discriminator on the bf16 path): layer 0's input images are written straight from [x | feats[:, idx]] (x may then be null
+// unless layer 0 has k == 3: its scan reads the float32 rows as x').  want_w = false: no transposed images (no weight gradients follow).
 int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
-                      const float** top, int* ld_top);
+                      const float** top, int* ld_top, const gt::CatSrc* cat0 = nullptr, bool want_w = true);
+bool sru_b16(const gt_engine* e, int role);
+bool sru_d_needs_f32_input(const gt_engine* e);
 int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, bool want_w,
                        float* dx_adv, hipStream_t s);

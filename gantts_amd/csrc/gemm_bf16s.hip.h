@@ -664,6 +664,18 @@ static __global__ __launch_bounds__(256) void cat_cast_transpose_kernel(const Ca
   __shared__ float tile[64][65];
   cast_transpose_tile(tile, src, nullptr, 0, rows, cols, out, ldo, outT, ldt, nullptr, (int)blockIdx.x, (int)blockIdx.y);
 }
+// ... times a variational (per-sequence) multiplier: image row r belongs to sequence r / T of the launch, element (r, c) =
+// cat(r, c) * mul[r / T][c] -- layer 0 of an SRU discriminator on the bf16 path (the two row groups of a D step have their own
+// rows of the table, drawn from their own passes)
+struct CatDropSrc {
+  CatSrc cat; const float* mul; int T, n;
+  __device__ __forceinline__ float operator()(long r, int c) const { return cat(r, c) * mul[(r / T) * n + c]; }
+};
+static __global__ __launch_bounds__(256) void catdrop_cast_transpose_kernel(const CatDropSrc src, long rows, int cols, __bf16* __restrict__ out, int ldo,
+                                                                     __bf16* __restrict__ outT, long ldt) {
+  __shared__ float tile[64][65];
+  cast_transpose_tile(tile, src, nullptr, 0, rows, cols, out, ldo, outT, ldt, nullptr, (int)blockIdx.x, (int)blockIdx.y);
+}
 
 // out[r][c] (contiguous float32) = in[r][c] of a bf16 image with row pitch ld (inspection / parity hooks)
 static __global__ void bf16_to_f32_kernel(const __bf16* __restrict__ in, long ld, long rows, int cols, float* __restrict__ out) {

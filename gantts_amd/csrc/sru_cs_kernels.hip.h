@@ -258,10 +258,10 @@ __global__ __launch_bounds__(64 * NW) void sru_bwd_cs_kernel(const SruArgs a) {
 #pragma unroll
         for (int q = 0; q < S; ++q) dxb[(long)(flip ? t_lo + q : t_lo + S - 1 - q) * a.lddx] = o3[q];
       }
-      // transposed image: gate column (col, jv), eight frames ascending in t = 16 contiguous bytes
+      // transposed image (null: no weight gradient follows): gate column (col, jv), eight frames ascending in t = 16 contiguous bytes
 #pragma unroll
       for (int jv = 0; jv < 4; ++jv) {
-        if (jv < k) {
+        if (jv < k && a.dU_bt) {
           float e[S];
 #pragma unroll
           for (int fr = 0; fr < S; ++fr) { const int q = flip ? fr : S - 1 - fr; e[fr] = jv == 0 ? o0[q] : jv == 1 ? o1[q] : jv == 2 ? o2[q] : o3[q]; }

@@ -44,7 +44,7 @@ struct SruArgs {
   // backward, GT_OPT_MATMUL_BF16 with the cooperative scans (T % 8 == 0, H % 64 == 0, B * ncols % 64 == 0): dU leaves the scan as the two
   // bf16 images the products read (row-major [N][ld_dub], transposed [ncols*k][ld_dubt]) instead of float32 + a cast pass
   __bf16* dU_b; int ld_dub;
-  __bf16* dU_bt; long ld_dubt;
+  __bf16* dU_bt; long ld_dubt;    // (null: not written -- the generator step's pass through a discriminator forms no weight gradient)
   // forward, GT_OPT_MATMUL_BF16 with the cooperative scans (T % 8 == 0, H % 64 == 0, B * ncols % 64 == 0): the scan writes the bf16
   // images of the NEXT product's input (the next SRU layer's dropped input, or hidden2out's input) itself -- row-major [N][ld_nxb] and,
   // when the backward pass will want it, transposed [ncols][ld_nxbt] -- value h * nx_mul[b][col] rounded as the cast pass rounds it

@@ -261,14 +261,18 @@ class StepEngine(object):
         """Engine switches (results unchanged up to fp32 summation order): ``"lstm_persistent"``,
         ``"lstm_fwd_units"``, ``"lstm_xcd_local"``, ``"split_first_layer"`` (conditioned D: x product once per D step);
         ``"matmul_bf16"`` switches the GEMMs to bf16 products
-        with float32 accumulation."""
+        with float32 accumulation (an SRURNN discriminator keeps float32 under it);
+        ``"sru_d_bf16"`` (0 / 1, default 0 or ``GT_SRU_D_BF16``; independent of ``"matmul_bf16"``) runs the products of an SRURNN in
+        the discriminator slot on bf16 images with float32 accumulation -- ``hidden_dim % 8 == 0`` is needed, any other width
+        silently keeps the float32 path."""
         opts = {"lstm_persistent": L.OPT_LSTM_PERSISTENT,
                 "lstm_fwd_units": L.OPT_LSTM_FWD_UNITS, "lstm_xcd_local": L.OPT_LSTM_XCD_LOCAL,
                 "matmul_bf16": L.OPT_MATMUL_BF16, "split_first_layer": L.OPT_SPLIT_FIRST_LAYER,
                 "comm_d_one_msg": L.OPT_COMM_D_ONE_MSG, "comm_early_g": L.OPT_COMM_EARLY_G,
                 "comm_force": L.OPT_COMM_FORCE, "launch_riders": L.OPT_LAUNCH_RIDERS,
                 "comm_close_inline": L.OPT_COMM_CLOSE_INLINE, "poll_results": L.OPT_POLL_RESULTS,
-                "comm_tv_in_sums": L.OPT_COMM_TV_IN_SUMS, "comm_ipc": L.OPT_COMM_IPC, "fused_dstack": L.OPT_FUSED_DSTACK}
+                "comm_tv_in_sums": L.OPT_COMM_TV_IN_SUMS, "comm_ipc": L.OPT_COMM_IPC, "fused_dstack": L.OPT_FUSED_DSTACK,
+                "sru_d_bf16": L.OPT_SRU_D_BF16}
         if name not in opts:
             raise ValueError("unknown engine option %r" % (name,))
         check(lib.gt_set_option(self._h, opts[name], int(value)))

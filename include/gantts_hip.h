@@ -250,7 +250,7 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  * accumulation; parameters ("master weights"), optimizer state, activations in memory, the recurrent state and every
  * reduction stay float32.  Results differ from the float32 path at the 1e-2 relative level (tests/test_gpu_parity.py).
  * An SRURNN in the discriminator slot keeps float32 products and float32 stashes under this option (an SRURNN generator takes the
- * bf16 path). */
+ * bf16 path).  GT_OPT_SRU_D_BF16 is the separate switch for that discriminator's products. */
 #define GT_OPT_MATMUL_BF16 5
 /* GT_OPT_SPLIT_FIRST_LAYER (default 1): the conditioned float32 discriminator evaluates its first layer as x . W_x^T (once per
  * D step, shared by the real and the generated rows) + adv . W_adv^T instead of one product over a concatenated [x | adv] image
@@ -283,6 +283,14 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  * walked by ONE workgroup: small per-rank batches are faster as per-layer launches); 2: always; 0: one launch per layer + the head
  * kernel.  Same sums up to float32 association. */
 #define GT_OPT_FUSED_DSTACK 19
+/* GT_OPT_SRU_D_BF16 (default 0; 0 or 1; GT_SRU_D_BF16 in the environment provides the default at engine creation): an SRURNN in the
+ * discriminator slot runs the three products of every layer (U = xin . W, dW, d input -- the gradient towards the generator
+ * included) through the bf16-storage family of GT_OPT_MATMUL_BF16: operands live as bfloat16 images, float32 accumulation.  U, the
+ * cell state, h, c, every reduction, the master weights and the optimizer state stay float32; hidden2out stays in the float32 head
+ * kernel.  Independent of GT_OPT_MATMUL_BF16 (a float32 generator with a bf16 SRU discriminator is a supported pair).  Needs
+ * hidden_dim % 8 == 0, the generator's rule: any other width silently keeps the float32 path.  LSTMRNN discriminators are not
+ * affected.  Results differ from the float32 path at the 1e-2 relative level (tests/test_gpu_sru_d_bf16.py). */
+#define GT_OPT_SRU_D_BF16 20
 int gt_set_option(gt_engine* e, int option, int value);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,

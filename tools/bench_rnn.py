@@ -25,6 +25,8 @@ ap.add_argument("--gen", default="lstm", choices=["lstm", "sru", "mlp"])
 ap.add_argument("--disc", default="mlp", choices=["mlp", "lstm", "sru"], help="the discriminator (default: cfg2 / cfg3's conditioned 3 x 256 MLP)")
 ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                 help="bf16: GEMM operands rounded to bfloat16, f32 accumulation, f32 master weights / state (GT_OPT_MATMUL_BF16)")
+ap.add_argument("--disc-bf16", action="store_true",
+                help="with --disc sru: the discriminator's products on bf16 images, f32 accumulation (GT_OPT_SRU_D_BF16; independent of --dtype)")
 args = ap.parse_args()
 B, Tn = args.batch, args.frames
 hp = types.SimpleNamespace(**hparams.tts_acoustic.values())
@@ -52,9 +54,11 @@ R = paramgen.unit_variance_mlpg_matrix_cuda(hp.windows, Tn)
 ys = get_static_features(y, 3, hp.stream_sizes, hp.has_dynamic_features)
 mask = sequence_mask(lengths.cuda()).unsqueeze(-1)
 cl = [int(v) for v in lengths]
+from gantts_amd.engine import engine_for  # noqa: E402
 if args.dtype == "bf16":
-    from gantts_amd.engine import engine_for  # noqa: E402
     engine_for(hp, mg).set_option("matmul_bf16", 1)
+if args.disc_bf16:
+    engine_for(hp, mg).set_option("sru_d_bf16", 1)
 
 
 def step():
@@ -74,5 +78,5 @@ for _ in range(args.steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / args.steps
 name = {"lstm": "cfg3 BiLSTM 3x256", "sru": "SRU 6x512 bi (hparams default G)", "mlp": "cfg2 MLP 3x512"}[args.gen]
-dname = {"mlp": "MLP 3x256", "lstm": "BiLSTM 2x256", "sru": "SRU 2x256 bi"}[args.disc]
+dname = {"mlp": "MLP 3x256", "lstm": "BiLSTM 2x256", "sru": "SRU 2x256 bi"}[args.disc] + (" (bf16 products)" if args.disc_bf16 else "")
 print("%s + D %s %s B=%d T=%d: %.2f ms/step, %.0f padded frames/s, scalars %s" % (name, dname, args.dtype, B, Tn, dt * 1e3, B * Tn / dt, out))
