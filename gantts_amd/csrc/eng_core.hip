@@ -382,7 +382,7 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
     case GT_OPT_LSTM_FWD_UNITS: e->lstm_fwd_upc = value; return GT_OK;
     case GT_OPT_LSTM_XCD_LOCAL: e->lstm_xcd_local = value != 0; return GT_OK;
     case GT_OPT_SPLIT_FIRST_LAYER:
-      if (e->opt_split_first != (value != 0)) { e->fake_cat_valid = false; e->adv2_fake_ok = false; }
+      if (e->opt_split_first != (value != 0)) invalidate_d_images(e);
       e->opt_split_first = value != 0;
       return GT_OK;
     case GT_OPT_COMM_D_ONE_MSG: e->opt_comm_d_one_msg = value != 0; return GT_OK;
@@ -399,7 +399,8 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       // interchangeable, so a change drops whatever is stashed -- the next update_* then asks for a fresh apply_generator
       // instead of back-propagating through buffers the forward never filled
       if (e->matmul_bf16 != (value != 0)) {
-        e->g_pass_valid = false; e->fake_cat_valid = false; e->dcat_b_ok = false; e->adv2_fake_ok = false; e->leak_pending = false; e->cxd_src = nullptr;
+        invalidate_d_images(e);
+        e->g_pass_valid = false; e->leak_pending = false; e->cxd_src = nullptr;
         e->d_begin_done = false; e->g_begin_done = false;
       }
       e->matmul_bf16 = value != 0;
@@ -407,7 +408,7 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
     case GT_OPT_SRU_D_BF16:
       if (value != 0 && value != 1) return fail(GT_ERR_INVALID, "GT_OPT_SRU_D_BF16 takes 0 or 1, not %d", value);
       // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
-      if (e->sru_d_bf16 != (value != 0)) { e->fake_cat_valid = false; e->leak_pending = false; e->d_begin_done = false; e->g_begin_done = false; }
+      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak_pending = false; e->d_begin_done = false; e->g_begin_done = false; }
       e->sru_d_bf16 = value != 0;
       return GT_OK;
   }
@@ -606,7 +607,8 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
     if (e->h_fault[2 + r] && n.step <= n.bound_step) n.buf_live = (n.od.flags & GT_OPTF_BUFFER_LIVE) != 0;
   }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
-  e->g_pass_valid = false; e->leak_pending = false; e->fake_cat_valid = false; e->adv2_fake_ok = false; e->cxd_src = nullptr;
+  invalidate_d_images(e);
+  e->g_pass_valid = false; e->leak_pending = false; e->cxd_src = nullptr;
   e->d_begin_done = e->g_begin_done = false; e->early_done = false;
   return GT_OK;
 }

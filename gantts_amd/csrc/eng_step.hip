@@ -58,17 +58,12 @@ extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
 // batches whose 32-frame tiles leave CUs empty (a rank's share of a strong-scaling run: B * ceil(T / 32) = 64 workgroups at 4 sequences of
 // 512 frames), at (16 + 2 kb) / 16 staged rows per output frame.  (64-frame tiles -- half the halo re-reads, one workgroup per CU instead of two --
 // measured no gain in round 4, 1.404 / 1.398 vs 1.393 / 1.398 ms, and left the library in round 6.)
-static int mlpg_tile_frames(gt_engine* e, int B, int T) {
-  (void)e;
-  const int tt = gt_tuning().mlpg_tt;
-  if (tt == 16) return 16;
-  return 32;
-}
+static int mlpg_tile_frames() { return gt_tuning().mlpg_tt == 16 ? 16 : 32; }
 int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const int* sstride, int Ds,
                  float* ys, int ldys, int B, int T, hipStream_t s) {
   const int nW = e->cfg.num_windows, kb = e->mlpg.cur->kb;
   auto lds_of = [&](int tt) { return ((size_t)(tt + 2 * kb) * nW * MLPG_CC + (size_t)tt * nW * (2 * kb + 1 + 2 * MLPG_PAD)) * sizeof(float); };
-  const int tt = mlpg_tile_frames(e, B, T);
+  const int tt = mlpg_tile_frames();
   const size_t lds = lds_of(tt);
   dim3 grid(B * cdiv(T, tt), cdiv(Ds, MLPG_CC));
   const int fpl = gt_tuning().mlpg_fpl;   // frames per lane of the compute phase: 2 measured best (round 4: 4: 24.7 us, 2: 21.8, 1: 26.6; round 5, unrolled tap loops: forward 18.5 / 17.2 / 18.3, backward 24.9 / 19.5 / 20.6)
@@ -85,7 +80,7 @@ int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, cons
                   const float* mask, hipStream_t s) {
   const int nW = e->cfg.num_windows, kb = e->mlpg.cur->kb;
   auto lds_of = [&](int tt) { return ((size_t)(tt + 2 * kb) * MLPG_CC + (size_t)(tt + 2 * kb) * nW * (2 * kb + 1 + 2 * MLPG_PAD)) * sizeof(float); };
-  const int tt = mlpg_tile_frames(e, B, T);
+  const int tt = mlpg_tile_frames();
   const size_t lds = lds_of(tt);
   dim3 grid(B * cdiv(T, tt), cdiv(Ds, MLPG_CC));
   const int fpl = gt_tuning().mlpg_fpl;
@@ -229,41 +224,39 @@ static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, lo
                           float* dX, int lddx, int col0, int ncols, long row0, long nrows, hipStream_t s, const FirstSplit* fs = nullptr) {
   Net& n = e->net[role];
   const int L = (int)n.hidden.size();
-  {
-    // per-layer launches: each layer's weight gradient right behind the product that made its dZ (still warm in L2 / MALL)
-    for (int l = L - 1; l >= 0; --l) {
-      const Lin& Lr = n.hidden[l];
-      const float* Xin = l > 0 ? acts[l - 1].as<float>() : in;
-      const int ldx = l > 0 ? n.hidden[l - 1].out : ld_in;
-      bool rode = false;
-      GemmArgs nn;
-      if (l > 0) nn = backward_data_args(cur, Lr.out, Lr.W, Lr.in, 0, other, Lr.in, rows, Lr.out, Lr.in, ACT_LEAKY_DROPOUT,
-                                         acts[l - 1].as<float>(), Lr.in, specs[l - 1]);
-      if (want_w && l == 0 && fs) {
-        // the kept gradient w.r.t. the generated rows' adversarial columns (no activation derivative) rides in the same launch
-        GemmArgs leak;
-        if (dX) leak = backward_data_args(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0, no_drop());
-        CHK(linear_backward_weight_split(cur, Lr.out, rows, fs->wrap, fs->xp, fs->ldxp, fs->cd, fs->adv, fs->ld_adv, Lr.in - fs->cd, Lr.out,
-                                         Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->sdefer[role], dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
-        CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
-      } else if (want_w) {
-        CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, s, &e->sdefer[role],
-                                   l > 0 ? &nn : nullptr, &rode));
-        CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
-        // generator: all layers above the first leave as one message under the first layer's backward; the discriminator's
-        // whole gradient (1 MB) is ONE message at the end of its backward pass (a second launch costs more than it hides)
-        if (l == 1 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
-      }
-      if (l > 0) {
-        if (!rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
-        std::swap(cur, other);
-      } else if (dX && !rode) {
-        CHK(linear_backward_data(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0,
-                                 no_drop(), s));
-      }
+  // per-layer launches: each layer's weight gradient right behind the product that made its dZ (still warm in L2 / MALL)
+  for (int l = L - 1; l >= 0; --l) {
+    const Lin& Lr = n.hidden[l];
+    const float* Xin = l > 0 ? acts[l - 1].as<float>() : in;
+    const int ldx = l > 0 ? n.hidden[l - 1].out : ld_in;
+    bool rode = false;
+    GemmArgs nn;
+    if (l > 0) nn = backward_data_args(cur, Lr.out, Lr.W, Lr.in, 0, other, Lr.in, rows, Lr.out, Lr.in, ACT_LEAKY_DROPOUT,
+                                       acts[l - 1].as<float>(), Lr.in, specs[l - 1]);
+    if (want_w && l == 0 && fs) {
+      // the kept gradient w.r.t. the generated rows' adversarial columns (no activation derivative) rides in the same launch
+      GemmArgs leak;
+      if (dX) leak = backward_data_args(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0, no_drop());
+      CHK(linear_backward_weight_split(cur, Lr.out, rows, fs->wrap, fs->xp, fs->ldxp, fs->cd, fs->adv, fs->ld_adv, Lr.in - fs->cd, Lr.out,
+                                       Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->sdefer[role], dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
+      CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
+    } else if (want_w) {
+      CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, s, &e->sdefer[role],
+                                 l > 0 ? &nn : nullptr, &rode));
+      CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
+      // generator: all layers above the first leave as one message under the first layer's backward; the discriminator's
+      // whole gradient (1 MB) is ONE message at the end of its backward pass (a second launch costs more than it hides)
+      if (l == 1 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
     }
-    return GT_OK;
+    if (l > 0) {
+      if (!rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+      std::swap(cur, other);
+    } else if (dX && !rode) {
+      CHK(linear_backward_data(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0,
+                               no_drop(), s));
+    }
   }
+  return GT_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -371,7 +364,16 @@ static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long l
   }
   return GT_OK;
 }
-
+// last_linear of a bf16-storage MLP: out [rows][out_dim] (float32) = act(acts.back() . W_last^T + b), W_last's shadow from refresh_shadows(with_last)
+static int last_forward_b16(gt_engine* e, int role, std::vector<B16Img>& acts, long rows, float* out, hipStream_t s) {
+  Net& n = e->net[role];
+  const LinShadow& ws = e->wsh[role][n.hidden.size()];
+  GemmB16Args g = b16_args();
+  g.A = acts.back().r(); g.lda = acts.back().ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
+  g.M = (int)rows; g.N = n.last.out; g.K = n.last.in; g.bias = n.last.b; g.epi = B16_FWD;
+  g.act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = out; g.ldc = n.d.out_dim;
+  return launch_gemm_b16(g, 1, s);
+}
 
 // row pitch of the generator's input / of the conditioning x (gt_set_x_pitch; dense by default)
 static int gx_pitch(const gt_engine* e) { return (e->ld_gx > 0 && !e->gx_dense_on) ? e->ld_gx : e->net[GT_ROLE_G].d.in_dim; }
@@ -397,8 +399,8 @@ static int dense_cx(gt_engine* e, const float** x, long N, hipStream_t s) {
   if (!*x || !e->cfg.discriminator_linguistic_condition || e->ld_cx <= 0 || e->ld_cx == cond_dim(e)) return GT_OK;
   const int cd = cond_dim(e);
   if (e->ld_cx < cd) return fail(GT_ERR_INVALID, "gt_set_x_pitch: pitch %d for %d conditioning columns", e->ld_cx, cd);
-  // (the copy is keyed on everything it depends on -- ADVICE r5: the pointer and the step alone served a stale or too small copy to a caller that
-  //  refilled x in place or changed B*T between two update_* calls of one step)
+  // (the key: source pointer, step, rows, pitch, columns -- ADVICE r5: the pointer and the step alone served a too small copy to a caller that
+  //  changed B*T between two update_* calls of one step.  The CONTENTS of x are not part of it: x refilled in place within a step is not seen.)
   if (!(e->cxd_src == *x && e->cxd_step == e->step_counter && e->cxd_rows == N && e->cxd_ld == e->ld_cx && e->cxd_cols == cd && e->cx_dense.p)) {
     CHK(e->cx_dense.ensure((size_t)N * cd * sizeof(float)));
     hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * cd, 256)), dim3(256), 0, s, *x, e->ld_cx, 0, (const int*)nullptr,
@@ -437,12 +439,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
                                 nullptr, false, &e->colp, s));
       CHK(refresh_shadows(e, GT_ROLE_G, true, s));
       CHK(stack_forward_b16(e, GT_ROLE_G, e->xin_b.r(), e->xin_b.ld, N, e->g_actb, pass0, 1, N, specs, want_t, s));
-      const LinShadow& ws = e->wsh[GT_ROLE_G][G.hidden.size()];
-      GemmB16Args g = b16_args();
-      g.A = e->g_actb.back().r(); g.lda = e->g_actb.back().ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
-      g.M = (int)N; g.N = G.last.out; g.K = G.last.in; g.bias = G.last.b; g.epi = B16_FWD;
-      g.act = G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = y_hat; g.ldc = G.d.out_dim;
-      CHK(launch_gemm_b16(g, 1, s));
+      CHK(last_forward_b16(e, GT_ROLE_G, e->g_actb, N, y_hat, s));
     } else {
       CHK(stack_forward(e, GT_ROLE_G, x, gx_pitch(e), N, e->g_act, pass0, 1, N, specs, s));
       const Lin& Lh = G.hidden.back();
@@ -493,7 +490,7 @@ extern "C" int gt_apply_generator(gt_engine* e, const float* x, const float* R, 
   e->step_counter++;
   e->B = B; e->T = T; e->N = (long)B * T;
   e->g_pass_valid = false;
-  e->fake_cat_valid = false; e->dcat_b_ok = false; e->adv2_fake_ok = false; e->cxd_src = nullptr;
+  invalidate_d_images(e); e->cxd_src = nullptr;
   e->tv_mask = nullptr; e->tv_inflight = false;             // a new batch: the mask contents may have changed
   CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->g_specs));
   e->last_x = e->gx_dense_on ? e->gx_dense.as<float>() : x;      // (what the backward pass reads: the dense copy when one was made)
@@ -510,34 +507,46 @@ int cond_dim(gt_engine* e) {
 }
 static int d_in_dim(gt_engine* e) { return e->Da + cond_dim(e); }
 
-// rows [row0, row0+N) of dcat <- [x | feats[:, adv_cols]]
+// rows [row0, row0+N) of dcat <- [x | feats[:, adv_cols]]   (x: checked by d_pass_plan)
 static int build_cat(gt_engine* e, const float* x, const float* feats, int ld_feats, long row0, long N, int ldc, hipStream_t s) {
   float* dst = e->dcat.as<float>() + row0 * ldc;
-  int off = 0;
-  if (e->cfg.discriminator_linguistic_condition) {
-    if (!x) return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
-    const int cd = cond_dim(e);
-    if (cd <= 0) return fail(GT_ERR_DIM, "discriminator in_dim too small for linguistic conditioning");
+  const int cd = cond_dim(e);
+  if (cd > 0) {
     hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * cd, 256)), dim3(256), 0, s, x, cd, 0, (const int*)nullptr, dst, ldc, 0,
                        (int)N, cd);
     LAUNCH_CHECK();
-    off = cd;
   }
   hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, feats, ld_feats, 0, e->d_adv_cols, dst, ldc,
-                     off, (int)N, e->Da);
+                     cd, (int)N, e->Da);
   LAUNCH_CHECK();
   return GT_OK;
 }
 
+// What the discriminator's head is asked for: shared by the per-layer head (run_head) and the fused stack (run_dstack).  Zero-initialise,
+// then set by name.
+struct HeadCall {
+  int mode;                    // HEAD_D_STEP: rows = natural then generated; HEAD_G_ADV: generated rows only
+  long rows, n_real;
+  const float* mask; long n_mask;
+  float eps;
+  bool want_grad;              // seed the backward pass (phase == "train")
+  bool want_w;                 // ... with weight gradients: d last_linear is reduced from the partials
+  StepResults* early_res;      // the finalising launch also writes the step's results here
+  int* defer_scalars;          // HEAD_G_ADV without weight gradients: the caller reduces the partials; <- their count
+  const double* tv_dev;        // the valid-frame count when it is not in the step's scalars yet
+  unsigned ticket;             // early_res in host memory: the ticket that announces it
+  bool unit_tv;                // seed the backward pass of the UNNORMALISED loss (GT_OPT_COMM_TV_IN_SUMS)
+};
 // the head's per-workgroup partials (e->headp, e->headw: nblk of them) -> the step's scalars and d last_linear
-static int head_finalize(gt_engine* e, int mode, int nblk, int K, bool w, hipStream_t s, StepResults* early_res, int* defer_scalars, unsigned ticket) {
+static int head_finalize(gt_engine* e, const HeadCall& c, int nblk, int K, hipStream_t s) {
   Net& D = e->net[GT_ROLE_D];
-  if (defer_scalars && !w) { *defer_scalars = nblk; return GT_OK; }
+  const bool w = c.want_grad && c.want_w;
+  if (c.defer_scalars && !w) { *c.defer_scalars = nblk; return GT_OK; }
   const int cgw = (w && nblk >= 512) ? 16 : 64;       // many rows of partials: narrower column groups, more workgroups (frame_kernels.hip.h)
   const int n_dw = cdiv(K, cgw), extra = cgw == 16 ? 1 : 0;       // (with many partials the scalars get a workgroup of their own, beside the dw ones)
   hipLaunchKernelGGL(d_head_finalize_kernel, dim3(n_dw + extra), dim3(1024), 0, s, e->headp.as<HeadPartials>(), e->headw.as<float>(),
-                     nblk, K, mode, e->sc(), w ? D.last.dW : (float*)nullptr, w ? D.last.db : (float*)nullptr, D.grads_dirty ? 1 : 0,
-                     early_res, ticket ? e->ticket_dev() : (unsigned*)nullptr, ticket, cgw, extra ? n_dw : 0);
+                     nblk, K, c.mode, e->sc(), w ? D.last.dW : (float*)nullptr, w ? D.last.db : (float*)nullptr, D.grads_dirty ? 1 : 0,
+                     c.early_res, c.ticket ? e->ticket_dev() : (unsigned*)nullptr, c.ticket, cgw, extra ? n_dw : 0);
   LAUNCH_CHECK();
   return GT_OK;
 }
@@ -549,83 +558,82 @@ static int head_finalize(gt_engine* e, int mode, int nblk, int K, bool w, hipStr
 // launch pays when the pass has at least one panel per CU; below that (per-rank batches of a few sequences) the per-layer launches,
 // which spread every layer over all CUs, are faster (b = 4: 0.413 vs 0.417 ms per step).  GT_OPT_FUSED_DSTACK = 2 forces the fused
 // path at any size (tests).
-static bool d_fused_ok(gt_engine* e, bool b16, long rows) {
+static bool d_fused_ok(gt_engine* e, long rows) {
   Net& D = e->net[GT_ROLE_D];
   if (e->opt_fused_dstack < 2 && dstack_panels(rows) < gemm_cu_count()) return false;
-  if (!e->opt_fused_dstack || b16 || D.d.arch != GT_ARCH_MLP || tl_gemm_prec != PREC_F32 || !dstack_hidden_ok(D.d.hidden_dim)) return false;
+  if (!e->opt_fused_dstack || D.d.arch != GT_ARCH_MLP || tl_gemm_prec != PREC_F32 || !dstack_hidden_ok(D.d.hidden_dim)) return false;
   if (D.hidden.empty() || (int)D.hidden.size() > DS_MAXL || D.last.out != 1 || e->Da < 1 || e->Da > 64) return false;
   for (size_t l = 0; l < D.hidden.size(); ++l)
     if (D.hidden[l].out != D.d.hidden_dim || (l > 0 && D.hidden[l].in != D.d.hidden_dim)) return false;
   return true;
 }
-// mode DSTACK_D_STEP: rows = 2N (natural then generated), writes the stashes e->d_act[1 ..], the seed gradient e->dzA and the head's
-// partials, then finalises them (as run_head does).  mode DSTACK_G_ADV: rows = N, writes gadv (want_grad) and the partials.
-static int run_dstack(gt_engine* e, int mode, long rows, long n_real, const float* mask, long n_mask, float eps, bool want_grad,
-                      float* gadv, hipStream_t s, StepResults* early_res, int* defer_scalars, const double* tv_dev, unsigned ticket, bool unit_tv) {
+// c.mode HEAD_D_STEP (DSTACK_D_STEP): rows = 2N (natural then generated), writes the stashes e->d_act[1 ..], the seed gradient e->dzA and the
+// head's partials, then finalises them (as run_head does).  HEAD_G_ADV (DSTACK_G_ADV): rows = N, writes gadv (want_grad) and the partials.
+static int run_dstack(gt_engine* e, const HeadCall& c, float* gadv, hipStream_t s) {
   Net& D = e->net[GT_ROLE_D];
   const int H = D.d.hidden_dim, L = (int)D.hidden.size();
-  const int nblk = dstack_panels(rows);
+  const bool d_step = c.mode == HEAD_D_STEP;
+  const int nblk = dstack_panels(c.rows);
   CHK(e->headp.ensure((size_t)nblk * sizeof(HeadPartials)));
-  CHK(e->dout.ensure((size_t)rows * sizeof(float)));
+  CHK(e->dout.ensure((size_t)c.rows * sizeof(float)));
   DStackArgs a;
   memset(&a, 0, sizeof(a));
-  a.mode = mode; a.L = L; a.rows = (int)rows; a.n_real = (int)n_real;
+  a.mode = d_step ? DSTACK_D_STEP : DSTACK_G_ADV; a.L = L; a.rows = (int)c.rows; a.n_real = (int)c.n_real;
   a.H0 = e->d_act[0].as<float>();
   for (int l = 0; l < L; ++l) {
     a.W[l] = D.hidden[l].W; a.b[l] = D.hidden[l].b; a.drop[l] = e->d_specs[l];
     if (a.drop[l].mode == DROP_BUFFER && a.drop[l].ld_mask != H) return fail(GT_ERR_INVALID, "injected dropout mask pitch");
   }
-  a.w_last = D.last.W; a.b_last = D.last.b; a.mask = mask; a.n_mask = (int)n_mask; a.eps = eps; a.unit_tv = unit_tv ? 1 : 0; a.tv_dev = tv_dev;
-  a.sc = e->sc(); a.want_grad = want_grad ? 1 : 0; a.Dout = e->dout.as<float>(); a.hp = e->headp.as<HeadPartials>();
-  if (mode == DSTACK_D_STEP) {
+  a.w_last = D.last.W; a.b_last = D.last.b; a.mask = c.mask; a.n_mask = (int)c.n_mask; a.eps = c.eps; a.unit_tv = c.unit_tv ? 1 : 0; a.tv_dev = c.tv_dev;
+  a.sc = e->sc(); a.want_grad = c.want_grad ? 1 : 0; a.Dout = e->dout.as<float>(); a.hp = e->headp.as<HeadPartials>();
+  if (d_step) {
     for (int l = 1; l + 1 < L; ++l) a.Hout[l] = e->d_act[l].as<float>();      // (the top layer's activation only feeds the head, which is fused: no stash)
     a.dZtop = e->dzA.as<float>();
-    if (want_grad) { CHK(e->headw.ensure((size_t)nblk * H * sizeof(float))); a.dw_partial = e->headw.as<float>(); }
+    if (c.want_grad) { CHK(e->headw.ensure((size_t)nblk * H * sizeof(float))); a.dw_partial = e->headw.as<float>(); }
   } else {
     a.W0 = D.hidden[0].W; a.ldw0 = D.hidden[0].in; a.col0 = cond_dim(e); a.Da = e->Da; a.gadv = gadv; a.ld_gadv = e->Da;
-    if (want_grad && !gadv) return fail(GT_ERR_INVALID, "fused discriminator stack: no gradient buffer");
+    if (c.want_grad && !gadv) return fail(GT_ERR_INVALID, "fused discriminator stack: no gradient buffer");
   }
   CHK(launch_dstack(a, H, s));
-  return head_finalize(e, mode == DSTACK_D_STEP ? HEAD_D_STEP : HEAD_G_ADV, nblk, H, mode == DSTACK_D_STEP && want_grad, s, early_res, defer_scalars, ticket);
+  return head_finalize(e, c, nblk, H, s);
 }
 
-// H: the top hidden activation, float32 [n_rows][K] or (h_ld > 0) its bf16 image with row pitch h_ld
-static int run_head(gt_engine* e, int mode, const void* H, int K, long n_rows, long n_real, const float* mask, long n_mask,
-                    float eps, bool want_grad, float* dH, const DropoutSpec& spec, bool want_w, hipStream_t s,
-                    StepResults* early_res = nullptr, int h_ld = 0, B16Img* dz_img = nullptr, bool dz_t = false,
-                    int* defer_scalars = nullptr /* HEAD_G_ADV without weight gradients: the caller reduces the partials; <- their count */,
-                    const double* tv_dev = nullptr /* the valid-frame count when it is not in the step's scalars yet */,
-                    unsigned ticket = 0 /* early_res in host memory: the ticket that announces it */,
-                    bool unit_tv = false /* seed the backward pass of the UNNORMALISED loss (GT_OPT_COMM_TV_IN_SUMS) */,
-                    bool has_act = true /* H is LeakyReLU + dropout of a pre-activation (MLP); false: a recurrent stack's output */) {
+// what the per-layer head reads and where its seed gradient goes
+struct HeadAct {
+  const void* H; int K;        // the top hidden activation, float32 [rows][K] ...
+  int h_ld;                    // ... or (h_ld > 0) its bf16 image with row pitch h_ld
+  bool has_act;                // H is LeakyReLU + dropout of a pre-activation (MLP); false: a recurrent stack's output
+  DropoutSpec spec;            // the top layer's dropout site
+  float* dH;                   // float32 seed gradient, or
+  B16Img* dz_img; bool dz_t;   // (bf16 storage) the top dZ image, transposed twin too when dz_t
+};
+template <int KP, typename TH, bool IMG, bool VEC = false>
+static void head_launch(gt_engine* e, const HeadCall& c, const HeadAct& a, int nblk, hipStream_t s) {
   Net& D = e->net[GT_ROLE_D];
-  const int nblk = (int)std::min<long>(1024, (n_rows + 31) / 32);
+  B16Img* z = IMG ? a.dz_img : nullptr;
+  hipLaunchKernelGGL((d_head_kernel<KP, TH, IMG, VEC>), dim3(nblk), dim3(256), (size_t)4 * a.K * sizeof(float), s, (const TH*)a.H, IMG ? a.h_ld : a.K, a.K,
+                     D.last.W, D.last.b, c.mask, (int)c.n_mask, (int)c.n_real, (int)c.rows, c.mode, c.eps, e->dout.as<float>(), z ? (float*)nullptr : a.dH, a.K,
+                     c.want_grad ? 1 : 0, a.spec, a.has_act ? 1 : 0, e->sc(), e->headp.as<HeadPartials>(), e->headw.as<float>(),
+                     z ? z->r() : (__bf16*)nullptr, z ? z->ld : 0, (z && a.dz_t) ? z->t() : (__bf16*)nullptr, z ? z->ldt : 0L, c.tv_dev, c.unit_tv ? 1 : 0);
+}
+template <int KP>
+static void head_launch_k(gt_engine* e, const HeadCall& c, const HeadAct& a, int nblk, hipStream_t s) {
+  if (a.h_ld > 0) head_launch<KP, __bf16, true>(e, c, a, nblk, s);
+  else if (KP % 4 == 0 && gt_tuning().head_vec) head_launch<(KP % 4 == 0 ? KP : 4), float, false, true>(e, c, a, nblk, s);
+  else head_launch<KP, float, false>(e, c, a, nblk, s);
+}
+static int run_head(gt_engine* e, const HeadCall& c, const HeadAct& a, hipStream_t s) {
+  const int nblk = (int)std::min<long>(1024, (c.rows + 31) / 32);
   CHK(e->headp.ensure((size_t)nblk * sizeof(HeadPartials)));
-  CHK(e->headw.ensure((size_t)nblk * K * sizeof(float)));
-  CHK(e->dout.ensure((size_t)n_rows * sizeof(float)));
-  const size_t lds = (size_t)4 * K * sizeof(float);
-#define GT_HEAD_LAUNCH(KP_)                                                                                              \
-  if (h_ld > 0)                                                                                                          \
-    hipLaunchKernelGGL((d_head_kernel<KP_, __bf16, true>), dim3(nblk), dim3(256), lds, s, (const __bf16*)H, h_ld, K, D.last.W, D.last.b, mask, (int)n_mask, \
-                       (int)n_real, (int)n_rows, mode, eps, e->dout.as<float>(), dz_img ? (float*)nullptr : dH, K, want_grad ? 1 : 0, spec, has_act ? 1 : 0, e->sc(), \
-                       e->headp.as<HeadPartials>(), e->headw.as<float>(), dz_img ? dz_img->r() : (__bf16*)nullptr, dz_img ? dz_img->ld : 0,  \
-                       (dz_img && dz_t) ? dz_img->t() : (__bf16*)nullptr, dz_img ? dz_img->ldt : 0L, tv_dev, unit_tv ? 1 : 0);            \
-  else if ((KP_) % 4 == 0 && gt_tuning().head_vec)                                                                       \
-    hipLaunchKernelGGL((d_head_kernel<((KP_) % 4 == 0 ? (KP_) : 4), float, false, true>), dim3(nblk), dim3(256), lds, s, (const float*)H, K, K, D.last.W, D.last.b, mask, (int)n_mask,  \
-                       (int)n_real, (int)n_rows, mode, eps, e->dout.as<float>(), dH, K, want_grad ? 1 : 0, spec, has_act ? 1 : 0, e->sc(), \
-                       e->headp.as<HeadPartials>(), e->headw.as<float>(), (__bf16*)nullptr, 0, (__bf16*)nullptr, 0L, tv_dev, unit_tv ? 1 : 0); \
-  else                                                                                                                   \
-    hipLaunchKernelGGL((d_head_kernel<KP_, float, false>), dim3(nblk), dim3(256), lds, s, (const float*)H, K, K, D.last.W, D.last.b, mask, (int)n_mask,  \
-                       (int)n_real, (int)n_rows, mode, eps, e->dout.as<float>(), dH, K, want_grad ? 1 : 0, spec, has_act ? 1 : 0, e->sc(), \
-                       e->headp.as<HeadPartials>(), e->headw.as<float>(), (__bf16*)nullptr, 0, (__bf16*)nullptr, 0L, tv_dev, unit_tv ? 1 : 0)
-  if (K <= 128) { GT_HEAD_LAUNCH(2); }
-  else if (K <= 256) { GT_HEAD_LAUNCH(4); }
-  else if (K <= 512) { GT_HEAD_LAUNCH(8); }
-  else if (K <= 1024) { GT_HEAD_LAUNCH(16); }
+  CHK(e->headw.ensure((size_t)nblk * a.K * sizeof(float)));
+  CHK(e->dout.ensure((size_t)c.rows * sizeof(float)));
+  if (a.K <= 128) head_launch_k<2>(e, c, a, nblk, s);
+  else if (a.K <= 256) head_launch_k<4>(e, c, a, nblk, s);
+  else if (a.K <= 512) head_launch_k<8>(e, c, a, nblk, s);
+  else if (a.K <= 1024) head_launch_k<16>(e, c, a, nblk, s);
   else return fail(GT_ERR_INVALID, "discriminator hidden_dim > 1024 is not supported by the fused head kernel");
-#undef GT_HEAD_LAUNCH
   LAUNCH_CHECK();
-  return head_finalize(e, mode, nblk, K, want_grad && want_w, s, early_res, defer_scalars, ticket);
+  return head_finalize(e, c, nblk, a.K, s);
 }
 
 static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t s) {
@@ -675,7 +683,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
       hipLaunchKernelGGL(slab_reduce_norm_kernel, dim3(sd.blocks + rest_blocks), dim3(256), 0, s, sd.jobs, sd.blocks, rest, n.d.grads, part);
       LAUNCH_CHECK();
       const int n_partial = sd.blocks + rest_blocks;
-      sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; sd.active = false;
+      sd.reset(false);
       n.step += 1;
       CHK(launch_optim_step(n.od, n.step, n.buf_live, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
                             (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
@@ -748,163 +756,257 @@ int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket) {
 }
 
 // ------------------------------------------------------------------------------------------
-// update_discriminator
+// one pass through the discriminator: the D step (natural then generated rows, weight gradients) and the adversarial term of the
+// generator step (generated rows, backward-data only) are the same four stages over a DPass that d_pass_plan() fills once
 // ------------------------------------------------------------------------------------------
-// the split first layer (FirstSplit) applies to the conditioned discriminator on the float32 path
-static bool d_split_ok(gt_engine* e, const float* x, bool b16) {
-  return e->opt_split_first && !b16 && e->net[GT_ROLE_D].d.arch == GT_ARCH_MLP && tl_gemm_prec == PREC_F32 && e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0 &&
+// the split first layer (FirstSplit) applies to the conditioned float32 MLP discriminator
+static bool d_split_ok(gt_engine* e, const float* x) {
+  return e->opt_split_first && tl_gemm_prec == PREC_F32 && e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0 &&
          e->Da > 0 && gemm_small_tiles_ok() && (e->net[GT_ROLE_D].d.hidden_dim & 3) == 0;     // (dZ as a 16-byte loadable operand)
 }
+// A recurrent discriminator (LSTMRNN / SRURNN in the discriminator slot, train.py:773-774) runs the natural and the generated sequences of
+// a D step as ONE batch of 2B sequences through its stack; the fused head reads the top layer's output (hidden2out is its weight).
+enum DKind { D_MLP_F32, D_MLP_B16, D_LSTM, D_SRU };
+struct DPass {
+  DKind kind;
+  bool split;                  // D_MLP_F32: split first layer, no image of x (fs)
+  bool fused;                  // D_MLP_F32: layers 1 .. L-1 + the head (+ the G step's backward-data chain) as ONE launch (dstack_f32.hip.h)
+  bool sru_d16;                // D_SRU under GT_OPT_SRU_D_BF16: the stack writes layer 0's bf16 images straight from cat0
+  bool needs_f32_image;        // the float32 [x | adv] image is read (every float32 route but the split one; an SRU-bf16 layer 0 with k == 3)
+  bool want_w;                 // weight gradients follow: transposed images, pitched x
+  int passes[2], npass;        // dropout passes: {0, 1} for the D step, {2} for the adversarial term
+  long N, rows;                // frames of the batch; rows of the pass = npass * N
+  int B, nseq, T, K0, ldc, H;  // nseq = npass * B; K0 = D's in_dim, ldc its image's pitch; H: width of what the head reads
+  const float* x;              // conditioning input (d_pass_input: its dense copy unless split)
+  const float* real; const float* fake; int ldf;      // y_static (D step only), y_hat_static, their pitch
+  FirstSplit fs;               // split
+  CatSrc cat0;                 // D_MLP_B16, sru_d16: the rows of the pass as [x | feats[:, adv_cols]]
+  const float* img;            // needs_f32_image: the pass's rows of e->dcat (d_pass_input)
+  const float* top; int ld_top;      // recurrent: the stack's output (d_pass_forward)
+};
+static int d_pass_plan(gt_engine* e, const float* x, const float* real, const float* fake, int ldf, int npass, int B, int T, bool want_w, DPass* out) {
+  Net& D = e->net[GT_ROLE_D];
+  if (D.d.in_dim != d_in_dim(e))
+    return fail(GT_ERR_DIM, "discriminator in_dim %d != adversarial input width %d (train.py:760-768)", D.d.in_dim, d_in_dim(e));
+  const int cd = cond_dim(e);
+  if (e->cfg.discriminator_linguistic_condition) {
+    if (!x) return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
+    if (cd <= 0) return fail(GT_ERR_DIM, "discriminator in_dim too small for linguistic conditioning");
+  }
+  DPass& p = *out;
+  memset(&p, 0, sizeof(p));
+  p.kind = D.d.arch == GT_ARCH_SRU ? D_SRU : has_lstm_body(D.d.arch) ? D_LSTM : use_b16(e, GT_ROLE_D) ? D_MLP_B16 : D_MLP_F32;
+  p.npass = npass; p.passes[0] = npass == 2 ? 0 : 2; p.passes[1] = 1;
+  p.B = B; p.T = T; p.N = (long)B * T; p.rows = npass * p.N; p.nseq = npass * B;
+  p.K0 = D.d.in_dim; p.ldc = (p.K0 + 3) & ~3; p.H = D.d.hidden_dim;
+  p.want_w = want_w; p.x = x; p.real = real; p.fake = fake; p.ldf = ldf;
+  p.split = p.kind == D_MLP_F32 && d_split_ok(e, x);
+  p.fused = p.kind == D_MLP_F32 && d_fused_ok(e, p.rows);
+  p.sru_d16 = p.kind == D_SRU && sru_b16(e, GT_ROLE_D);
+  p.needs_f32_image = p.kind == D_LSTM || (p.kind == D_SRU && sru_d_needs_f32_input(e)) || (p.kind == D_MLP_F32 && !p.split);
+  if (p.split) { p.fs.x = x; p.fs.ldx = cx_pitch(e); p.fs.cd = cd; p.fs.ld_adv = (e->Da + 3) & ~3; p.fs.wrap = p.N; }
+  CatSrc& c = p.cat0;
+  c.x = x; c.cd = cd; c.fa = npass == 2 ? real : fake; c.fb = fake; c.ldf = ldf; c.idx = e->d_adv_cols; c.N = p.N; c.row_off = npass == 2 ? 0 : p.N;
+  return GT_OK;
+}
 
+// The valid-frame count as an extra workgroup of the adversarial-column gather (D step, split first layer): decided by the caller.
+struct AdvRiders {
+  const float* mask;
+  bool tv_ride;                // fused single-GPU call: the count is not known yet
+  bool tv_ride_dp;             // data parallel: the local term of the global count, all-reduced right behind the launch
+  bool unnorm;                 // GT_OPT_COMM_TV_IN_SUMS: the local count leaves with the loss sums
+};
+// What the backend reads: the float32 [x | adv] image, its bf16 image (transposed twin too when want_w), the adversarial columns alone
+// (split), or nothing (an SRU-bf16 discriminator that does not read float32 rows).  The D step writes both halves; the adversarial term
+// writes the generated half (rows N .. 2N of the same buffers) unless the D step of the same batch left it there.
+static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t s) {
+  const long N = p.N;
+  const bool both = p.npass == 2;
+  const long row0 = both ? 0 : N;
+  if (!p.split) {        // pitched rows are read in place by the split first layer only
+    CHK(dense_cx(e, &p.x, N, s));
+    p.cat0.x = p.x;
+  }
+  if (both) invalidate_d_images(e);
+  if (p.kind == D_MLP_B16) {
+    CHK(e->dcat_b.ensure(2 * N, p.K0, p.want_w));
+    if (both || !e->img_cat_b.holds(p.x, p.fake)) {
+      hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(p.rows, 64), cdiv(p.K0, 64)), dim3(256), 0, s, p.cat0, p.rows, p.K0,
+                         e->dcat_b.r() + row0 * e->dcat_b.ld, e->dcat_b.ld, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr, p.want_w ? e->dcat_b.ldt : 0L);
+      LAUNCH_CHECK();
+      e->img_cat_b.built(p.x, p.fake);
+    }
+  } else if (p.split) {
+    // only the adversarial columns are gathered (58 of 483 columns at cfg2)
+    const int ld = e->ld_adv2 = p.fs.ld_adv;
+    CHK(e->adv2.ensure((size_t)2 * N * ld * sizeof(float)));
+    float* dst = e->adv2.as<float>() + row0 * ld;
+    if (both || !e->img_adv2.holds(nullptr, p.fake)) {
+      const bool any_ride = r.tv_ride || r.tv_ride_dp || r.unnorm;
+      hipLaunchKernelGGL(build_adv_kernel, dim3(cdiv(p.rows * (ld / 4), 256) + (any_ride ? 1 : 0)), dim3(256), 0, s, p.cat0.fa, p.cat0.fb, p.ldf,
+                         e->d_adv_cols, e->Da, dst, ld, N, p.rows, any_ride ? r.mask : (const float*)nullptr, (int)N, e->tv_override, e->sc(),
+                         r.unnorm ? &e->sc()->tv_sum : r.tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr);
+      LAUNCH_CHECK();
+      if (r.tv_ride) { e->tv_mask = r.mask; e->tv_n = N; e->tv_ovr = e->tv_override; }
+      if (r.tv_ride_dp) CHK(comm_tv_sent(e, s));          // all-reduce of the count on the communicator's stream, joined in front of the head
+      e->img_adv2.built(nullptr, p.fake);
+    }
+    p.fs.adv = dst;
+    if (p.want_w) CHK(pitched_rows(e, 0, p.x, p.fs.ldx, p.fs.cd, N, &p.fs.xp, &p.fs.ldxp, s));
+  } else if (p.needs_f32_image) {
+    CHK(e->dcat.ensure((size_t)2 * N * p.ldc * sizeof(float)));
+    if (both && p.cat0.cd > 0) {
+      hipLaunchKernelGGL(build_cat2_kernel, dim3(cdiv(N * p.K0, 256)), dim3(256), 0, s, p.x, p.cat0.cd, p.real, p.fake, p.ldf,
+                         e->d_adv_cols, e->Da, e->dcat.as<float>(), p.ldc, N);
+      LAUNCH_CHECK();
+    } else {
+      if (both) CHK(build_cat(e, p.x, p.real, p.ldf, 0, N, p.ldc, s));
+      if (both || !e->img_cat.holds(p.x, p.fake)) CHK(build_cat(e, p.x, p.fake, p.ldf, N, N, p.ldc, s));
+    }
+    e->img_cat.built(p.x, p.fake);
+    p.img = e->dcat.as<float>() + row0 * p.ldc;
+  }
+  return GT_OK;
+}
+
+// the stack forward; a recurrent stack leaves its output in p.top / p.ld_top (= p.H)
+static int d_pass_forward(gt_engine* e, DPass& p, hipStream_t s) {
+  switch (p.kind) {
+    case D_SRU:        // (sequence lengths ignored as in the reference)
+      CHK(sru_stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, s, &p.top, &p.ld_top, p.sru_d16 ? &p.cat0 : nullptr, p.want_w));
+      p.H = p.ld_top;
+      break;
+    case D_LSTM:
+      CHK(lstm_check_lengths(e, p.B, p.T));
+      CHK(lstm_stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, s, &p.top, &p.ld_top));
+      p.H = p.ld_top;
+      break;
+    case D_MLP_B16:
+      CHK(refresh_shadows(e, GT_ROLE_D, false, s));        // (G step: D has just been stepped, train.py:276 before :307)
+      CHK(stack_forward_b16(e, GT_ROLE_D, e->dcat_b.r() + (p.npass == 2 ? 0 : p.N) * e->dcat_b.ld, e->dcat_b.ld, p.rows, e->d_actb, p.passes, p.npass, p.N,
+                            e->d_specs, p.want_w, s));
+      break;
+    case D_MLP_F32:      // fused: layer 0 alone, the fused stack launch (d_pass_head) takes over from there
+      CHK(stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.rows, e->d_act, p.passes, p.npass, p.N, e->d_specs, s, p.split ? &p.fs : nullptr, p.fused ? 1 : 1 << 30));
+      break;
+  }
+  return GT_OK;
+}
+
+// the head on what the stack left, seeding the backward pass where that backend's stack backward reads it (c.want_grad).
+// dst: where the fused launch of the adversarial term writes the generated rows' adversarial-column gradient (it IS that pass's backward).
+static int d_pass_head(gt_engine* e, DPass& p, const HeadCall& c, float* dst, hipStream_t s) {
+  const int H = p.H;
+  CHK(e->dzA.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
+  CHK(e->dzB.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
+  if (p.fused) return run_dstack(e, c, p.npass == 1 ? dst : nullptr, s);
+  HeadAct a;
+  memset(&a, 0, sizeof(a));
+  a.K = H; a.has_act = true; a.dH = e->dzA.as<float>();
+  switch (p.kind) {
+    case D_SRU: case D_LSTM:
+      CHK(e->dl_dout.ensure((size_t)2 * p.rows * H * sizeof(float)));
+      a.H = p.top; a.has_act = false; a.spec = no_drop(); a.dH = e->dl_dout.as<float>();
+      break;
+    case D_MLP_B16:      // the head writes its seed gradient as the top dZ image (both orientations for the weight gradients)
+      a.H = e->d_actb.back().r(); a.h_ld = e->d_actb.back().ld; a.spec = e->d_specs.back();
+      if (c.want_grad) { CHK(e->dz_b[0].ensure(p.rows, H, p.want_w)); a.dz_img = &e->dz_b[0]; a.dz_t = p.want_w; }
+      break;
+    case D_MLP_F32:
+      a.H = e->d_act.back().as<float>(); a.spec = e->d_specs.back();
+      break;
+  }
+  return run_head(e, c, a, s);
+}
+
+// the stack backward (phase == "train"): weight gradients when p.want_w, and the gradient w.r.t. the generated rows' adversarial columns
+// -> dst [N][Da] (the kept leak of the D step, may be null; gadv of the adversarial term)
+static int d_pass_backward(gt_engine* e, DPass& p, float* dst, hipStream_t s) {
+  if (p.fused && p.npass == 1) return GT_OK;      // done inside the fused launch
+  const long N = p.N, row0 = p.npass == 2 ? N : 0;      // the generated rows of the pass
+  const int col0 = cond_dim(e), Da = e->Da;
+  switch (p.kind) {
+    case D_SRU:
+      return sru_stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, p.want_w, dst, s);
+    case D_LSTM: {     // the gradient w.r.t. the [x | adv] rows, then its generated rows' adversarial columns (train.py:265, 274, 307-308)
+      float* dx0 = nullptr;
+      if (dst) { CHK(e->d_dx0.ensure((size_t)2 * N * p.K0 * sizeof(float))); dx0 = e->d_dx0.as<float>(); }
+      CHK(lstm_stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, p.want_w, dx0, s));
+      if (dst) {
+        hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * Da, 256)), dim3(256), 0, s, dx0 + row0 * p.K0, p.K0, col0, (const int*)nullptr, dst, Da, 0,
+                           (int)N, Da);
+        LAUNCH_CHECK();
+      }
+      return GT_OK;
+    }
+    case D_MLP_B16:
+      return stack_backward_b16(e, GT_ROLE_D, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr, p.want_w ? e->dcat_b.ldt : 0, p.rows, e->d_actb, e->d_specs, 0,
+                                p.want_w, dst, Da, col0, Da, row0, N, s);
+    case D_MLP_F32:
+      return stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.rows, e->d_act, e->d_specs, e->dzA.as<float>(), e->dzB.as<float>(), p.want_w, dst, Da, col0, Da,
+                            row0, N, s, p.split ? &p.fs : nullptr);
+  }
+  return GT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// update_discriminator
+// ------------------------------------------------------------------------------------------
 extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const float* y_static, const float* y_hat_static,
                                              const float* mask, int B, int T, int train, float eps, void* stream) {
   CHK(check_common(e, B, T));
   Net& D = e->net[GT_ROLE_D];
   if (!D.bound) return fail(GT_ERR_STATE, "discriminator not bound");
   if (!y_static || !y_hat_static || !mask) return fail(GT_ERR_INVALID, "null tensor");
-  if (D.d.in_dim != d_in_dim(e))
-    return fail(GT_ERR_DIM, "discriminator in_dim %d != adversarial input width %d (train.py:760-768)", D.d.in_dim, d_in_dim(e));
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
-  const int K0 = D.d.in_dim, ldc = (K0 + 3) & ~3;
   const bool tr = train != 0;
+  DPass p;
+  CHK(d_pass_plan(e, x, y_static, y_hat_static, e->Ds, 2, B, T, tr, &p));
   if (comm_on(e) && tr && D.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_d.zero_grad() must precede update_discriminator (the gradient buckets are summed over the ranks in place)");
-  { SlabDefer& sd = e->sdefer[GT_ROLE_D]; sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; sd.active = e->early && tr && D.has_opt; }
+  e->sdefer[GT_ROLE_D].reset(e->early && tr && D.has_opt);
   // data parallel: the global count travels under the D forward pass.  With the split first layer its local term is summed by a
-  // rider of the gather launch below (tv_ride_dp), else by a launch of its own right here.
+  // rider of the gather launch (tv_ride_dp), else by a launch of its own right here.
   const bool tv_known = e->tv_mask == mask && e->tv_n == N && e->tv_ovr == e->tv_override;
   const bool dp_count = e->early && e->opt_launch_riders && comm_on(e) && !tv_known && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight;
   // GT_OPT_COMM_TV_IN_SUMS: no collective for the count at all -- it leaves with the loss sums (engine_internal.hip.h)
   const bool unnorm = dp_count && e->opt_comm_tv_in_sums && tr && D.has_opt && D.d.grads;
   e->d_unnorm = unnorm;
-  const bool split_gather = !use_b16(e, GT_ROLE_D) && d_split_ok(e, x, false);
-  const bool tv_ride_dp = dp_count && !unnorm && split_gather;
-  if (!tv_ride_dp && !unnorm) CHK(ensure_tv_begin(e, mask, N, s));
-  if (unnorm && !split_gather) {
+  AdvRiders ride;
+  ride.mask = mask; ride.unnorm = unnorm;
+  ride.tv_ride_dp = dp_count && !unnorm && p.split;
+  ride.tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_known;      // fused single-GPU call: the count is not known yet
+  if (!ride.tv_ride_dp && !unnorm) CHK(ensure_tv_begin(e, mask, N, s));
+  if (unnorm && !p.split) {
     hipLaunchKernelGGL(mask_total_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, &e->sc()->tv_sum);
     LAUNCH_CHECK();
   }
-  const int passes[2] = {0, 1};
-  // the [x | adv] image of both halves: real rows, then generated rows
-  const bool b16 = use_b16(e, GT_ROLE_D);
-  const bool split = d_split_ok(e, x, b16);
-  if (!split) CHK(dense_cx(e, &x, N, s));        // pitched rows are read in place by the split first layer only
-  FirstSplit fs;
-  memset(&fs, 0, sizeof(fs));
-  // GT_OPT_SRU_D_BF16: the SRU stack writes layer 0's bf16 images straight from x / y_static / y_hat_static (sru_cat0); the float32
-  // image is built only where layer 0's scan reads it (k == 3: the undropped rows are its highway input x')
-  const bool sru_d16 = D.d.arch == GT_ARCH_SRU && sru_b16(e, GT_ROLE_D);
-  CatSrc sru_cat0;
-  memset(&sru_cat0, 0, sizeof(sru_cat0));
-  if (sru_d16) {
-    if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
-      return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
-    sru_cat0.x = x; sru_cat0.cd = cond_dim(e); sru_cat0.fa = y_static; sru_cat0.fb = y_hat_static; sru_cat0.ldf = e->Ds; sru_cat0.idx = e->d_adv_cols;
-    sru_cat0.N = N; sru_cat0.row_off = 0;
-  }
-  if (sru_d16 && !sru_d_needs_f32_input(e)) {
-    e->fake_cat_valid = false;                   // the float32 image was not built
-    e->adv2_fake_ok = false;
-  } else
-  if (b16) {
-    // bf16 storage: the image is written ONCE, as bf16, in both orientations (no float32 image at all)
-    if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
-      return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
-    CHK(e->dcat_b.ensure(2 * N, K0, tr));
-    CatSrc src;
-    src.x = x; src.cd = cond_dim(e); src.fa = y_static; src.fb = y_hat_static; src.ldf = e->Ds; src.idx = e->d_adv_cols; src.N = N; src.row_off = 0;
-    hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(2 * N, 64), cdiv(K0, 64)), dim3(256), 0, s, src, 2 * N, K0, e->dcat_b.r(), e->dcat_b.ld,
-                       tr ? e->dcat_b.t() : (__bf16*)nullptr, e->dcat_b.ldt);
-    LAUNCH_CHECK();
-    e->dcat_b_ok = true;
-    e->fake_cat_valid = false;                 // the float32 image was not built
-  } else {
-  if (split) {
-    // split first layer (FirstSplit): only the adversarial columns of the two halves are gathered (58 of 483 columns at cfg2)
-    e->ld_adv2 = (e->Da + 3) & ~3;
-    CHK(e->adv2.ensure((size_t)2 * N * e->ld_adv2 * sizeof(float)));
-    // (the valid-frame count rides in this launch when it is not known yet: fused single-GPU call)
-    const bool tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_known;
-    const bool any_ride = tv_ride || tv_ride_dp || unnorm;
-    hipLaunchKernelGGL(build_adv_kernel, dim3(cdiv(2 * N * (e->ld_adv2 / 4), 256) + (any_ride ? 1 : 0)), dim3(256), 0, s, y_static, y_hat_static,
-                       e->Ds, e->d_adv_cols, e->Da, e->adv2.as<float>(), e->ld_adv2, N, 2 * N, any_ride ? mask : (const float*)nullptr,
-                       (int)N, e->tv_override, e->sc(), unnorm ? &e->sc()->tv_sum : tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr);
-    LAUNCH_CHECK();
-    if (tv_ride) { e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override; }
-    if (tv_ride_dp) CHK(comm_tv_sent(e, s));          // all-reduce of the count on the communicator's stream, joined in front of the head
-    e->adv2_fake_ok = true; e->adv2_yhs = y_hat_static;
-    e->fake_cat_valid = false;
-    fs.x = x; fs.ldx = cx_pitch(e); fs.cd = cond_dim(e); fs.adv = e->adv2.as<float>(); fs.ld_adv = e->ld_adv2; fs.wrap = N;
-    fs.xp = nullptr; fs.ldxp = 0;
-    if (tr) CHK(pitched_rows(e, 0, x, fs.ldx, fs.cd, N, &fs.xp, &fs.ldxp, s));
-  } else {
-  CHK(e->dcat.ensure((size_t)2 * N * ldc * sizeof(float)));
-  if (e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0) {
-    hipLaunchKernelGGL(build_cat2_kernel, dim3(cdiv(N * K0, 256)), dim3(256), 0, s, x, cond_dim(e), y_static, y_hat_static, e->Ds,
-                       e->d_adv_cols, e->Da, e->dcat.as<float>(), ldc, N);
-    LAUNCH_CHECK();
-  } else {
-    CHK(build_cat(e, x, y_static, e->Ds, 0, N, ldc, s));
-    CHK(build_cat(e, x, y_hat_static, e->Ds, N, N, ldc, s));
-  }
-  e->fake_cat_valid = true; e->fake_cat_x = x; e->fake_cat_yhs = y_hat_static;
-  e->adv2_fake_ok = false;
-  }
-  }
-  e->dcat_b_x = x; e->dcat_b_yhs = y_hat_static;
-  // a recurrent discriminator (LSTMRNN in the discriminator slot, train.py:773-774): the natural and the generated sequences run as ONE
-  // batch of 2B sequences through its stack (lengths twice), the fused head reads the top layer's output (hidden2out is its weight)
-  // (SRURNN in that slot: the same, sequence lengths ignored as in the reference)
-  const bool d_sru = D.d.arch == GT_ARCH_SRU;
-  const bool d_rec = has_lstm_body(D.d.arch) || d_sru;
-  const bool fused = !d_rec && d_fused_ok(e, b16, 2 * N);        // layers 1 .. L-1 + the head as ONE launch (dstack_f32.hip.h)
-  const float* rec_top = nullptr;
-  int rec_ld = 0;
-  if (d_sru) {
-    CHK(sru_stack_forward(e, GT_ROLE_D, sru_d_needs_f32_input(e) ? e->dcat.as<float>() : (const float*)nullptr, ldc, 2 * B, T, passes, 2, s, &rec_top,
-                          &rec_ld, sru_d16 ? &sru_cat0 : nullptr, tr));
-  } else if (d_rec) {
-    CHK(lstm_check_lengths(e, B, T));
-    CHK(lstm_stack_forward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, s, &rec_top, &rec_ld));
-  } else if (b16) {
-    CHK(refresh_shadows(e, GT_ROLE_D, false, s));
-    CHK(stack_forward_b16(e, GT_ROLE_D, e->dcat_b.r(), e->dcat_b.ld, 2 * N, e->d_actb, passes, 2, N, e->d_specs, tr, s));
-  } else {
-    CHK(stack_forward(e, GT_ROLE_D, split ? nullptr : e->dcat.as<float>(), ldc, 2 * N, e->d_act, passes, 2, N, e->d_specs, s, split ? &fs : nullptr,
-                      fused ? 1 : 1 << 30));
-  }
-  const int H = d_rec ? rec_ld : D.d.hidden_dim;
-  if (d_rec) CHK(e->dl_dout.ensure((size_t)2 * 2 * N * H * sizeof(float)));
+  CHK(d_pass_input(e, p, ride, s));
+  CHK(d_pass_forward(e, p, s));
   if (tr && !D.d.grads) return fail(GT_ERR_STATE, "phase == \"train\" but the discriminator was bound without grads");
-  CHK(e->dzA.ensure((size_t)2 * N * std::max(H, 1) * sizeof(float)));
-  CHK(e->dzB.ensure((size_t)2 * N * std::max(H, 1) * sizeof(float)));
   // fused call: losses and counts are final after the head (the gradient norm is not: reported as 0), so the head's
   // reduction kernel also writes the result struct and the scalars start their way to the host right behind it
   const bool plain_early = e->early && !comm_on(e), comm_early = e->early && comm_on(e);
-  // data parallel + riders: the head reads the all-reduced count where the collective left it (and files it in the step's scalars):
-  // no conversion launch between the join and the head
-  const unsigned d_ticket = plain_early ? take_ticket(e) : 0;
-  const double* head_tv = nullptr;
+  HeadCall hc;
+  memset(&hc, 0, sizeof(hc));
+  hc.mode = HEAD_D_STEP; hc.rows = p.rows; hc.n_real = N; hc.mask = mask; hc.n_mask = N; hc.eps = eps; hc.want_grad = tr; hc.want_w = tr;
+  hc.early_res = plain_early ? early_res_target(e) : nullptr;
+  hc.ticket = plain_early ? take_ticket(e) : 0;
+  hc.unit_tv = unnorm;
   if (unnorm) {      // the normaliser arrives with the sums (finalize_d_kernel on the communicator's stream files it); valid from the join on
     e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override;
   } else if (comm_on(e) && e->opt_launch_riders && e->tv_inflight && !tv_known) {
+    // data parallel + riders: the head reads the all-reduced count where the collective left it (and files it in the step's scalars):
+    // no conversion launch between the join and the head
     CHK(comm_tv_join(e, s));
-    head_tv = e->comm_tv.as<double>();
+    hc.tv_dev = e->comm_tv.as<double>();
     e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override;
   } else CHK(ensure_tv(e, mask, N, s));
-  if (b16 && tr) CHK(e->dz_b[0].ensure(2 * N, H, true));
-  if (d_rec)
-    CHK(run_head(e, HEAD_D_STEP, (const void*)rec_top, H, 2 * N, N, mask, N, eps, tr, e->dl_dout.as<float>(), no_drop(), true, s,
-                 plain_early ? early_res_target(e) : nullptr, 0, nullptr, true, nullptr, head_tv, d_ticket, unnorm, false));
-  else if (fused)
-    CHK(run_dstack(e, DSTACK_D_STEP, 2 * N, N, mask, N, eps, tr, nullptr, s, plain_early ? early_res_target(e) : nullptr, nullptr, head_tv, d_ticket, unnorm));
-  else
-  CHK(run_head(e, HEAD_D_STEP, b16 ? (const void*)e->d_actb.back().r() : (const void*)e->d_act.back().as<float>(), H, 2 * N, N, mask, N, eps, tr,
-               e->dzA.as<float>(), e->d_specs.back(), true, s, plain_early ? early_res_target(e) : nullptr, b16 ? e->d_actb.back().ld : 0,
-               (b16 && tr) ? &e->dz_b[0] : nullptr, true, nullptr, head_tv, d_ticket, unnorm));
+  CHK(d_pass_head(e, p, hc, nullptr, s));
   e->early_done = false;
-  if (plain_early) CHK(post_early_results(e, s, d_ticket));
+  if (plain_early) CHK(post_early_results(e, s, hc.ticket));
   if (comm_early) CHK(comm_early_results(e, GT_ROLE_D, unnorm ? &e->sc()->tv_sum : &e->sc()->s_real, unnorm ? 5 : 4, 0.f, 0.f, 0.f, s));
   if (tr) {
     CHK(comm_grads_ready(e, GT_ROLE_D, D.last.dW, (long)D.last.in * D.last.out + D.last.out, s));
@@ -916,24 +1018,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
       return fail(GT_ERR_STATE, "update_discriminator called twice without optimizer_g.zero_grad() (train.py:538)");
     float* leak = nullptr;
     if (want_leak) { CHK(e->leak.ensure((size_t)N * e->Da * sizeof(float))); leak = e->leak.as<float>(); }
-    const int col0 = cond_dim(e);
-    if (d_sru) {   // through the SRU stack: weight gradients, and the generated rows' adversarial columns of d input straight into `leak`
-      CHK(sru_stack_backward(e, GT_ROLE_D, sru_d_needs_f32_input(e) ? e->dcat.as<float>() : (const float*)nullptr, ldc, 2 * B, T, passes, 2, true, leak, s));
-    } else if (d_rec) {   // through the recurrent stack: weight gradients, and the gradient w.r.t. the [x | adv] rows when the generator wants it
-      float* dx0 = nullptr;
-      if (leak) { CHK(e->d_dx0.ensure((size_t)2 * N * K0 * sizeof(float))); dx0 = e->d_dx0.as<float>(); }
-      CHK(lstm_stack_backward(e, GT_ROLE_D, e->dcat.as<float>(), ldc, 2 * B, T, passes, 2, true, dx0, s));
-      if (leak) {   // the generated rows' adversarial columns (train.py:265, 274)
-        hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, dx0 + N * K0, K0, col0, (const int*)nullptr, leak, e->Da, 0,
-                           (int)N, e->Da);
-        LAUNCH_CHECK();
-      }
-    } else if (b16) {   // the head wrote its seed gradient as the top dZ image, both orientations
-      CHK(stack_backward_b16(e, GT_ROLE_D, e->dcat_b.t(), e->dcat_b.ldt, 2 * N, e->d_actb, e->d_specs, 0, true, leak, e->Da, col0, e->Da, N, N, s));
-    } else {
-      CHK(stack_backward(e, GT_ROLE_D, split ? nullptr : e->dcat.as<float>(), ldc, 2 * N, e->d_act, e->d_specs, e->dzA.as<float>(),
-                         e->dzB.as<float>(), true, leak, e->Da, col0, e->Da, N, N, s, split ? &fs : nullptr));
-    }
+    CHK(d_pass_backward(e, p, leak, s));
     D.grads_dirty = true;
     if (want_leak) { e->leak_pending = true; e->leak_unnorm = unnorm; }
   }
@@ -958,21 +1043,16 @@ extern "C" int gt_update_discriminator_end(gt_engine* e, int train, gt_d_result*
   if (!e->d_begin_done) return fail(GT_ERR_STATE, "gt_update_discriminator_end without _begin");
   hipStream_t s = (hipStream_t)stream;
   e->d_begin_done = false;
-  if (!out) {   // deferred: enqueue everything, synchronise nothing; gt_update_discriminator_result collects
-    if (e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
-    if (train) CHK(optimizer_step(e, GT_ROLE_D, &e->sc()->gnorm2_d, s));
-    hipLaunchKernelGGL(finalize_d_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), train ? 0 : 1);
-    LAUNCH_CHECK();
-    return post_deferred_results(e, GT_ROLE_D, s);
-  }
+  // out == null: deferred -- enqueue everything, synchronise nothing; gt_update_discriminator_result collects
+  if (!out && e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
+  if (train) CHK(optimizer_step(e, GT_ROLE_D, &e->sc()->gnorm2_d, s));
   if (e->early_done) {
-    if (train) CHK(optimizer_step(e, GT_ROLE_D, &e->sc()->gnorm2_d, s));
     CHK(wait_early_results(e));                   // only the scalars; backward + step stay queued
     e->early_done = false;
   } else {
-    if (train) CHK(optimizer_step(e, GT_ROLE_D, &e->sc()->gnorm2_d, s));
     hipLaunchKernelGGL(finalize_d_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), train ? 0 : 1);
     LAUNCH_CHECK();
+    if (!out) return post_deferred_results(e, GT_ROLE_D, s);
     CHK(fetch_results(e, s));
   }
   fill_d_result(e->h_res, out);
@@ -1092,9 +1172,6 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
                              e->slabs, e->colp, s, &e->sdefer[GT_ROLE_G], &nn_last, &rode));
   CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * G.last.in + Do, s));
   if (!rode) CHK(launch_gemm(GEMM_NN, nn_last, 1, s));
-  // The first layer's weight gradient reads G's input as its frame operand.  When the discriminator's input image of
-  // this step holds the very same x (linguistic conditioning on the generator's own input, no noise channels), the x
-  // columns of its rows are a bit-exact copy with a 16-byte row pitch: use it, and the product takes the 16-byte loader.
   // The first layer's weight gradient reads G's input as its n-contiguous frame operand: with a 16-byte pitch it takes the
   // 16-byte loader and the 64 x 64 tiles.  The caller's tensor when it has one, else the discriminator's input image of this step
   // when that holds the very same x (bit-exact copy), else a pitched copy made once per step (shared with the split first layer
@@ -1102,9 +1179,9 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   const float* xin = x;
   int ldxin = gx_pitch(e);
   if (!gemm_vec_ok(x, ldxin) && tl_gemm_prec == PREC_F32) {
-    if (e->fake_cat_valid && e->fake_cat_x == x && e->cfg.discriminator_linguistic_condition && cond_dim(e) == G.d.in_dim && e->dcat.p) {
+    if (e->img_cat.valid && e->img_cat.x == x && e->cfg.discriminator_linguistic_condition && cond_dim(e) == G.d.in_dim && e->dcat.p) {
       ldxin = (d_in_dim(e) + 3) & ~3;
-      xin = e->dcat.as<float>() + N * ldxin;      // the generated half: the one that is valid whenever fake_cat_valid is
+      xin = e->dcat.as<float>() + N * ldxin;      // the generated half: the one that is valid whenever img_cat is
     } else {
       const int slot = (e->pitched[0].src == x && e->pitched[0].ld == gx_pitch(e) && e->pitched[0].cols == G.d.in_dim && e->pitched[0].step == e->step_counter) ? 0 : 1;
       CHK(pitched_rows(e, slot, x, gx_pitch(e), G.d.in_dim, N, &xin, &ldxin, s));
@@ -1136,7 +1213,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   if (comm_on(e) && tr && G.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_g.zero_grad() must precede update_generator");
-  { SlabDefer& sd = e->sdefer[GT_ROLE_G]; sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; sd.active = e->early && tr && G.has_opt; }
+  e->sdefer[GT_ROLE_G].reset(e->early && tr && G.has_opt);
   CHK(ensure_tv(e, mask, N, s));
   // loss_mse (always reported, train.py:294); its gradient is fused into the MLPG^T kernel
   const bool direct = !is_i2o(G.d.arch) && !e->g_used_mlpg;
@@ -1164,108 +1241,19 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   int head_blocks = 0;
   if (adv_w > 0.f) {
     if (!D.bound) return fail(GT_ERR_STATE, "adv_w > 0 but no discriminator bound");
-    if (D.d.in_dim != d_in_dim(e)) return fail(GT_ERR_DIM, "discriminator in_dim mismatch");
-    const int K0 = D.d.in_dim, ldc = (K0 + 3) & ~3;
-    const int passes[1] = {2};
-    const bool b16 = use_b16(e, GT_ROLE_D);
-    const float* cat = nullptr;
-    const bool split = d_split_ok(e, x, b16);
-    if (!split) CHK(dense_cx(e, &x, N, s));
-    FirstSplit fs;
-    memset(&fs, 0, sizeof(fs));
-    if (split) {     // the generated rows' adversarial columns: kept from the D step of the same batch, or gathered here
-      e->ld_adv2 = (e->Da + 3) & ~3;
-      CHK(e->adv2.ensure((size_t)2 * N * e->ld_adv2 * sizeof(float)));
-      float* fake = e->adv2.as<float>() + N * e->ld_adv2;
-      if (!(e->adv2_fake_ok && e->adv2_yhs == y_hat_static)) {
-        hipLaunchKernelGGL(build_adv_kernel, dim3(cdiv(N * (e->ld_adv2 / 4), 256)), dim3(256), 0, s, y_hat_static, y_hat_static, Ds, e->d_adv_cols, e->Da,
-                           fake, e->ld_adv2, N, N, (const float*)nullptr, 0, 0.f, (StepScalars*)nullptr, (double*)nullptr);
-        LAUNCH_CHECK();
-        e->adv2_fake_ok = true; e->adv2_yhs = y_hat_static;
-      }
-      fs.x = x; fs.ldx = cx_pitch(e); fs.cd = cond_dim(e); fs.adv = fake; fs.ld_adv = e->ld_adv2; fs.wrap = N;
-    } else if (!b16 && !(D.d.arch == GT_ARCH_SRU && !sru_d_needs_f32_input(e))) {
-      CHK(e->dcat.ensure((size_t)2 * N * ldc * sizeof(float)));
-      if (!(e->fake_cat_valid && e->fake_cat_x == x && e->fake_cat_yhs == y_hat_static)) {
-        CHK(build_cat(e, x, y_hat_static, Ds, N, N, ldc, s));
-        e->fake_cat_valid = true; e->fake_cat_x = x; e->fake_cat_yhs = y_hat_static;
-      }
-      cat = e->dcat.as<float>() + N * ldc;
-    }
-    const bool d_sru = D.d.arch == GT_ARCH_SRU;
-    const bool d_rec = has_lstm_body(D.d.arch) || d_sru;
-    // layers 1 .. L-1, the head and the backward-data chain down to the adversarial columns as ONE launch (dstack_f32.hip.h)
-    const bool fused = !d_rec && d_fused_ok(e, b16, N);
-    const float* rec_top = nullptr;
-    int rec_ld = 0;
-    if (d_sru) {
-      // GT_OPT_SRU_D_BF16: layer 0's row-major image of the generated rows straight from x / y_hat_static; no transposed images (no weight gradients)
-      CatSrc src;
-      memset(&src, 0, sizeof(src));
-      const bool d16 = sru_b16(e, GT_ROLE_D);
-      if (d16) {
-        if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
-          return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
-        src.x = x; src.cd = cond_dim(e); src.fa = y_hat_static; src.fb = y_hat_static; src.ldf = Ds; src.idx = e->d_adv_cols; src.N = N; src.row_off = N;
-      }
-      CHK(sru_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld, d16 ? &src : nullptr, false));
-    } else if (d_rec) {
-      CHK(lstm_check_lengths(e, B, T));
-      CHK(lstm_stack_forward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, s, &rec_top, &rec_ld));
-    } else
-    if (b16) {   // the generated half of the bf16 image: rows N .. 2N, kept from the D step of the same batch or built here
-      CHK(e->dcat_b.ensure(2 * N, K0, false));
-      if (!(e->dcat_b_ok && e->dcat_b_x == x && e->dcat_b_yhs == y_hat_static)) {
-        if (e->cfg.discriminator_linguistic_condition && (!x || cond_dim(e) <= 0))
-          return fail(GT_ERR_INVALID, "discriminator_linguistic_condition is set but x is null");
-        CatSrc src;
-        src.x = x; src.cd = cond_dim(e); src.fa = y_hat_static; src.fb = y_hat_static; src.ldf = Ds; src.idx = e->d_adv_cols; src.N = N; src.row_off = N;
-        hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(K0, 64)), dim3(256), 0, s, src, N, K0,
-                           e->dcat_b.r() + N * e->dcat_b.ld, e->dcat_b.ld, (__bf16*)nullptr, 0L);
-        LAUNCH_CHECK();
-        e->dcat_b_ok = true; e->dcat_b_x = x; e->dcat_b_yhs = y_hat_static;
-      }
-      CHK(refresh_shadows(e, GT_ROLE_D, false, s));        // D has just been stepped (train.py:276 before :307)
-      CHK(stack_forward_b16(e, GT_ROLE_D, e->dcat_b.r() + N * e->dcat_b.ld, e->dcat_b.ld, N, e->d_actb, passes, 1, N, e->d_specs, false, s));
-    } else {
-      CHK(stack_forward(e, GT_ROLE_D, cat, ldc, N, e->d_act, passes, 1, N, e->d_specs, s, split ? &fs : nullptr, fused ? 1 : 1 << 30));
-    }
-    const int H = d_rec ? rec_ld : D.d.hidden_dim;
-    CHK(e->dzA.ensure((size_t)2 * N * H * sizeof(float)));
-    CHK(e->dzB.ensure((size_t)2 * N * H * sizeof(float)));
-    if (b16 && tr) CHK(e->dz_b[0].ensure(N, H, false));
-    if (fused) {
-      if (tr) { CHK(e->gadv.ensure((size_t)N * e->Da * sizeof(float))); gadv = e->gadv.as<float>(); }
-      CHK(run_dstack(e, DSTACK_G_ADV, N, N, mask, N, eps, tr, gadv, s, nullptr, riders || riders_dp ? &head_blocks : nullptr, nullptr, 0, false));
-    } else
-    if (d_rec) {
-      CHK(e->dl_dout.ensure((size_t)2 * N * H * sizeof(float)));
-      CHK(run_head(e, HEAD_G_ADV, (const void*)rec_top, H, N, N, mask, N, eps, tr, e->dl_dout.as<float>(), no_drop(), false, s, nullptr, 0, nullptr,
-                   false, riders || riders_dp ? &head_blocks : nullptr, nullptr, 0, false, false));
-    } else
-    CHK(run_head(e, HEAD_G_ADV, b16 ? (const void*)e->d_actb.back().r() : (const void*)e->d_act.back().as<float>(), H, N, N, mask, N, eps, tr,
-                 e->dzA.as<float>(), e->d_specs.back(), false, s, nullptr, b16 ? e->d_actb.back().ld : 0, (b16 && tr) ? &e->dz_b[0] : nullptr, false,
-                 riders || riders_dp ? &head_blocks : nullptr));
-    if (tr && !fused) {
-      CHK(e->gadv.ensure((size_t)N * e->Da * sizeof(float)));
-      gadv = e->gadv.as<float>();
-      const int col0 = cond_dim(e);
-      if (d_sru) {   // back through the SRU stack to the generated rows' adversarial columns; no weight gradients (train.py:307-308)
-        CHK(sru_stack_backward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, false, gadv, s));
-      } else if (d_rec) {   // back through the recurrent stack to the generated rows' adversarial columns; no weight gradients (train.py:307-308)
-        CHK(e->d_dx0.ensure((size_t)2 * N * K0 * sizeof(float)));
-        float* dx0 = e->d_dx0.as<float>();
-        CHK(lstm_stack_backward(e, GT_ROLE_D, cat, ldc, B, T, passes, 1, false, dx0, s));
-        hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, dx0, K0, col0, (const int*)nullptr, gadv, e->Da, 0, (int)N,
-                           e->Da);
-        LAUNCH_CHECK();
-      } else if (b16) {
-        CHK(stack_backward_b16(e, GT_ROLE_D, nullptr, 0, N, e->d_actb, e->d_specs, 0, false, gadv, e->Da, col0, e->Da, 0, N, s));
-      } else {
-        CHK(stack_backward(e, GT_ROLE_D, cat, ldc, N, e->d_act, e->d_specs, e->dzA.as<float>(), e->dzB.as<float>(), false, gadv,
-                           e->Da, col0, e->Da, 0, N, s));
-      }
-    }
+    DPass p;
+    CHK(d_pass_plan(e, x, nullptr, y_hat_static, Ds, 1, B, T, false, &p));
+    AdvRiders none;
+    memset(&none, 0, sizeof(none));
+    CHK(d_pass_input(e, p, none, s));      // the generated half: kept from the D step of the same batch, or built here
+    CHK(d_pass_forward(e, p, s));
+    if (tr) { CHK(e->gadv.ensure((size_t)N * e->Da * sizeof(float))); gadv = e->gadv.as<float>(); }
+    HeadCall hc;
+    memset(&hc, 0, sizeof(hc));
+    hc.mode = HEAD_G_ADV; hc.rows = p.rows; hc.n_real = N; hc.mask = mask; hc.n_mask = N; hc.eps = eps; hc.want_grad = tr; hc.want_w = false;
+    hc.defer_scalars = riders || riders_dp ? &head_blocks : nullptr;
+    CHK(d_pass_head(e, p, hc, gadv, s));
+    if (tr) CHK(d_pass_backward(e, p, gadv, s));      // no weight gradients (train.py:307-308)
   }
   // MGE loss + gradient assembly at y_hat_static
   const bool early_ok = e->early && !(tr && direct && mse_w != 0.f);
@@ -1326,23 +1314,16 @@ extern "C" int gt_update_generator_end(gt_engine* e, int train, float adv_w, flo
   if (!e->g_begin_done) return fail(GT_ERR_STATE, "gt_update_generator_end without _begin");
   hipStream_t s = (hipStream_t)stream;
   e->g_begin_done = false;
-  if (!out) {
-    if (e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
-    if (train) CHK(optimizer_step(e, GT_ROLE_G, &e->sc()->gnorm2_g, s));
-    hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0,
-                       train ? 0 : 1, (const double*)nullptr, 0, (const double*)nullptr, 0);
-    LAUNCH_CHECK();
-    return post_deferred_results(e, GT_ROLE_G, s);
-  }
+  if (!out && e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
+  if (train) CHK(optimizer_step(e, GT_ROLE_G, &e->sc()->gnorm2_g, s));
   if (e->early_done) {
-    if (train) CHK(optimizer_step(e, GT_ROLE_G, &e->sc()->gnorm2_g, s));
     CHK(wait_early_results(e));
     e->early_done = false;
   } else {
-    if (train) CHK(optimizer_step(e, GT_ROLE_G, &e->sc()->gnorm2_g, s));
     hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0,
                        train ? 0 : 1, (const double*)nullptr, 0, (const double*)nullptr, 0);
     LAUNCH_CHECK();
+    if (!out) return post_deferred_results(e, GT_ROLE_G, s);
     CHK(fetch_results(e, s));
   }
   fill_g_result(e->h_res, out);
@@ -1375,7 +1356,7 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   tl_gemm_prec = e->matmul_bf16 ? PREC_BF16 : PREC_F32;      // this entry point launches GEMMs without check_common
   CHK(fault_seen(e));
-  { SlabDefer& sd = e->sdefer[GT_ROLE_G]; sd.active = false; sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; }   // combines run in place here
+  e->sdefer[GT_ROLE_G].reset(false);      // combines run in place here
   const long N = e->N;
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   CHK(e->gs.ensure((size_t)N * Ds * sizeof(float)));
@@ -1414,19 +1395,18 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
     e->g_pass_valid = false;
     return generator_forward(e, x, R, B, T, out, out2, false, s, specs);
   }
-  const int pass0d[1] = {0};
   if (n.d.arch == GT_ARCH_LSTM || n.d.arch == GT_ARCH_SRU) {
     if (role != GT_ROLE_G) {
-      // the recurrent discriminator's plain forward: its stack, then hidden2out (+ sigmoid)
-      const float* top = nullptr;
-      int ld = 0;
-      if (n.d.arch == GT_ARCH_SRU) {
-        CHK(sru_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld, nullptr, false));      // (GT_OPT_SRU_D_BF16: the stack's products on bf16 images)
-        tl_gemm_prec = PREC_F32;      // hidden2out stays a float32 product under either bf16 option
-      } else {
-        CHK(lstm_check_lengths(e, B, T));
-        CHK(lstm_stack_forward(e, role, x, n.d.in_dim, B, T, pass0d, 1, s, &top, &ld));
-      }
+      // the recurrent discriminator's plain forward: its stack over the caller's rows as they are (no image, no layer-0 CatSrc:
+      // GT_OPT_SRU_D_BF16 then casts them itself), then hidden2out (+ sigmoid)
+      DPass p;
+      memset(&p, 0, sizeof(p));
+      p.kind = n.d.arch == GT_ARCH_SRU ? D_SRU : D_LSTM;
+      p.npass = 1; p.passes[0] = 0; p.B = p.nseq = B; p.T = T; p.img = x; p.ldc = n.d.in_dim;
+      CHK(d_pass_forward(e, p, s));
+      if (p.kind == D_SRU) tl_gemm_prec = PREC_F32;      // hidden2out stays a float32 product under either bf16 option
+      const float* top = p.top;
+      const int ld = p.ld_top;
       return linear_forward(top, ld, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in, n.last.out,
                             n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
     }
@@ -1442,12 +1422,7 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
     CHK(cast_transpose(x, n.d.in_dim, N, n.d.in_dim, e->fwd_b.r(), e->fwd_b.ld, (__bf16*)nullptr, 0, nullptr, false, &e->colp, s));
     CHK(refresh_shadows(e, role, true, s));
     CHK(stack_forward_b16(e, role, e->fwd_b.r(), e->fwd_b.ld, N, actb, pass0, 1, N, specs, false, s));
-    const LinShadow& ws = e->wsh[role][n.hidden.size()];
-    GemmB16Args g = b16_args();
-    g.A = actb.back().r(); g.lda = actb.back().ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
-    g.M = (int)N; g.N = n.last.out; g.K = n.last.in; g.bias = n.last.b; g.epi = B16_FWD;
-    g.act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = out; g.ldc = n.d.out_dim;
-    return launch_gemm_b16(g, 1, s);
+    return last_forward_b16(e, role, actb, N, out, s);
   }
   CHK(stack_forward(e, role, x, n.d.in_dim, N, acts, pass0, 1, N, specs, s));      // (plain forward: dense rows)
   return linear_forward(acts.back().as<float>(), n.hidden.back().out, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in,

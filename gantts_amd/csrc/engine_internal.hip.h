@@ -131,6 +131,7 @@ struct SlabDefer {
   int blocks = 0;
   bool active = false;
   SlabDefer() { jobs.n = 0; jobs.pad_ = 0; }
+  void reset(bool on) { jobs.n = 0; blocks = 0; used = 0; active = on; }      // nothing recorded; record (on) or combine in place
 };
 
 // ------------------------------------------------------------------------------------------
@@ -221,8 +222,15 @@ struct gt_engine {
   // per-step state
   int B = 0, T = 0; long N = 0;
   const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;
-  bool g_pass_valid = false, leak_pending = false, fake_cat_valid = false;
-  const float* fake_cat_x = nullptr; const float* fake_cat_yhs = nullptr;
+  bool g_pass_valid = false, leak_pending = false;
+  // "the generated half of this image of D's input is built", and from which x / y_hat_static: the generator step's adversarial term
+  // reuses what the D step of the same batch left behind.  One record per image kind; all dropped by invalidate_d_images().
+  struct DImage {
+    bool valid = false; const float* x = nullptr; const float* yhs = nullptr;
+    bool holds(const float* x_, const float* yhs_) const { return valid && x == x_ && yhs == yhs_; }
+    void built(const float* x_, const float* yhs_) { valid = true; x = x_; yhs = yhs_; }
+  };
+  DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
   bool d_begin_done = false, g_begin_done = false, g_has_adv = false, g_used_mlpg = false;
   const float* tv_mask = nullptr; long tv_n = 0; float tv_ovr = 0.f;   // sum(mask) already on the device for this step
   // early results (single-GPU fused entry points): the step scalars are final right after the loss
@@ -268,13 +276,10 @@ struct gt_engine {
   std::vector<B16Img> l_dg_b;                      // per layer: dG image (both orientations; every product that reads it runs on the step stream)
   B16Img l_hs_b;                                   // h that entered each frame (transposed)
   std::vector<LinShadow> lsh;                      // per LSTM layer: W_ih of all directions stacked [dirs*4H][in]; last entry: hidden2out
-  bool dcat_b_ok = false;                          // dcat_b's generated half holds [x | adv(y_hat_static)] of the tensors below
-  const float* dcat_b_x = nullptr; const float* dcat_b_yhs = nullptr;
   std::vector<LinShadow> wsh[2];                   // per role: bf16 shadows of the hidden layers' weights, then of the last layer's
   SlabDefer sdefer[2];                             // per role: deferred weight-gradient combines of the fused step
   Scratch d_pre;                                   // split first layer of the conditioned D: P = x . W[:, :cd]^T + b  (eng_step.hip: FirstSplit)
   Scratch adv2; int ld_adv2 = 0;                   // ... and the adversarial columns of a pass's rows, [real | generated], 16-byte pitch
-  bool adv2_fake_ok = false; const float* adv2_yhs = nullptr;   // its generated half holds adv(y_hat_static) of this tensor
   struct Pitched { Scratch buf; const float* src = nullptr; int ld = 0, cols = 0; long rows = 0; uint64_t step = ~0ULL; };
   Pitched pitched[2];                              // 16-byte-pitch copies of caller tensors (slot 0: D's x, 1: G's input), once per step
   // GT_OPT_SPLIT_FIRST_LAYER (per engine; the environment only provides the default at creation)
@@ -337,7 +342,8 @@ struct gt_engine {
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
 };
-
+// a new batch, another storage form or first-layer route, a cleared fault: whatever image of D's input is kept gets rebuilt
+static inline void invalidate_d_images(gt_engine* e) { e->img_cat.valid = e->img_cat_b.valid = e->img_adv2.valid = false; }
 
 // ------------------------------------------------------------------------------------------
 // eng_core.hip

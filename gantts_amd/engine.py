@@ -339,7 +339,7 @@ class StepEngine(object):
     def _cond_x(self, x, model_d):
         """The conditioning x of D (train.py:254-256): dense or pitched rows.  The split first layer of the conditioned float32 MLP
         discriminator reads pitched rows in place; for every other discriminator (recurrent, bf16 storage, split switched off) the
-        engine densifies them once per step (eng_step.hip: dense_cx) -- the decision lives in ONE place, next to d_split_ok()."""
+        engine densifies them once per step (eng_step.hip: d_pass_input -> dense_cx) -- the decision lives in ONE place, d_pass_plan()."""
         x, ld = _check_x(x, "x", model_d.in_dim - self._adv_width())
         self._set_pitch(cx=ld)
         return x

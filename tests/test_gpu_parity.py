@@ -1754,3 +1754,52 @@ def test_tiny_batches_match_oracle(B, T):
             assert np.abs(a - b).max() <= 2.1 * lr, (k, float(np.abs(a - b).max()))
         else:
             _close(a, b, msg=k)
+
+
+def _adv_term_cases():
+    from test_gpu_sru_discriminator import SRUD_CASES
+    srud = SRUD_CASES["srud_uni_k4_cond"]
+    return {"mlp_split": (C.CASES["acoustic_chain_d"], None), "mlp_cat": (C.CASES["acoustic_chain_d"], {"split_first_layer": 0}),
+            "mlp_bf16": (C.CASES["acoustic_mlp_dropout"], {"matmul_bf16": 1}), "lstm": (C.CASES["acoustic_lstm_d"], None),
+            "sru": (srud, None), "sru_bf16": (srud, {"sru_d_bf16": 1})}
+
+
+@pytest.mark.parametrize("backend", ["mlp_split", "mlp_cat", "mlp_bf16", "lstm", "sru", "sru_bf16"])
+def test_adversarial_term_without_a_d_step_equals_the_one_behind_a_d_step(backend):
+    """The generator step's adversarial term builds the generated half of D's input itself when no D step of the same batch left it
+    behind (a miss of the engine's image cache), and reuses it otherwise.  Eval phase, eval-mode networks (no dropout, no update),
+    every discriminator backend: apply_generator + update_generator on a fresh engine against apply_generator +
+    update_discriminator + update_generator on a second fresh engine with the same seed.  Both builders only copy (or round to bf16)
+    the same values and an eval D step changes no weight, so loss_adv and loss_g are bit-identical."""
+    import gantts_amd.train as T
+    from gantts_amd import optim, paramgen
+    from gantts_amd.engine import engine_for
+    from gantts_amd.multistream import get_static_features
+    from gantts_amd.seqloss import sequence_mask
+    from hip_runner import build_model, make_hp
+    case, options = _adv_term_cases()[backend]
+    hp = make_hp(case)
+    x_np, y_np, lengths = C.make_batch(case)
+    res = {}
+    for with_d in (False, True):
+        T.hp = hp
+        mg, md = build_model(case["g"], 11).eval(), build_model(case["d"], 22).eval()
+        og = getattr(optim, case["opt_g"][0])(mg.parameters(), **case["opt_g"][1])
+        od = getattr(optim, case["opt_d"][0])(md.parameters(), **case["opt_d"][1])
+        eng = engine_for(hp, mg)
+        eng.set_seed(4711)
+        for k, v in (options or {}).items():
+            eng.set_option(k, v)
+        x, y = torch.from_numpy(x_np).cuda(), torch.from_numpy(y_np).cuda()
+        R = paramgen.unit_variance_mlpg_matrix_cuda(hp.windows, case["T"])
+        ys = get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
+        mask = sequence_mask(torch.from_numpy(np.ascontiguousarray(lengths)).cuda(), max_len=case["T"]).unsqueeze(-1)
+        yh, yhs = T.apply_generator(mg, x, R, list(lengths))
+        if with_d:
+            T.update_discriminator(md, od, x, ys, yhs, list(lengths), mask, "test")
+        g = T.update_generator(mg, md, og, x, y, yh, ys, yhs, case["adv_w"], list(lengths), mask, "test", mse_w=case["mse_w"],
+                               mge_w=case["mge_w"])
+        res[with_d] = np.array(g, dtype=np.float64)
+    print("%s G scalars alone %s behind a D step %s" % (backend, res[False], res[True]))
+    assert np.isfinite(res[False]).all() and res[False][2] > 0
+    assert res[False][2] == res[True][2] and res[False][3] == res[True][3], (backend, res[False], res[True])
