@@ -27,6 +27,9 @@ IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts
 GEMM_PATH_SLOTS = 588                                                   # gt_gemm_path_counts
+GEMM_B16_PATH_SLOTS = 66                                                # gt_gemm_b16_path_counts
+CAST_PLAIN_F32, CAST_PLAIN_BF16, CAST_SEQDROP, CAST_CAT, CAST_CATDROP, CAST_MULTI = 0, 1, 2, 3, 4, 5      # CastCase.kind
+CAST_MAX_JOBS = 8
 GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
 ARCH_MLP, ARCH_IN2OUT, ARCH_LSTM, ARCH_SRU, ARCH_IN2OUT_RNN = 0, 1, 2, 3, 4
 OPT_ADAGRAD, OPT_ADAM = 0, 1
@@ -88,6 +91,25 @@ class GemmCase(C.Structure):
                 + [(n, C.c_void_p) for n in ("x", "w", "bias", "y", "dy", "h", "mask", "addm", "adv", "dx", "dw", "db")])
 
 
+class GemmB16Case(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("route", "rows", "in_dim", "out_dim", "act", "drop")] + [("p", C.c_float)]
+                + [("key0", C.c_uint32), ("key1", C.c_uint32)]
+                + [(n, C.c_int32) for n in ("accumulate", "ldx", "ldw", "ld_dy", "ldh", "ld_mask", "ldc", "ldcb", "ldcbt")]
+                + [(n, C.c_void_p) for n in ("x", "w", "bias", "dy", "h", "mask", "c", "cb", "cbt", "dw", "db")])
+
+
+class CastJob(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
+                + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
+
+
+class CastCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "cols", "ldi", "ldo", "colsum_accumulate", "T", "cd", "ldf", "n_jobs", "pad_")]
+                + [(n, C.c_int64) for n in ("rows", "ldt", "N", "row_off")]
+                + [(n, C.c_void_p) for n in ("in_", "out", "outT", "colsum", "mul", "x", "fa", "fb", "idx")]
+                + [("jobs", CastJob * CAST_MAX_JOBS)])
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 
 # name -> (restype, argtypes); every symbol declared in include/gantts_hip.h
@@ -126,6 +148,9 @@ SIGNATURES = {
     "gt_lstm_path_counts": (_I, [_P, C.POINTER(_L), _I]),
     "gt_gemm_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_gemm_f32": (_I, [C.POINTER(GemmCase), _P]),
+    "gt_gemm_b16_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_op_gemm_b16": (_I, [C.POINTER(GemmB16Case), _P]),
+    "gt_op_cast_image": (_I, [C.POINTER(CastCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -1,7 +1,18 @@
 // libgantts_hip.so -- dispatch of the bf16-storage product family (gemm_bf16s.hip.h; GT_OPT_MATMUL_BF16)
+#include <atomic>
 #include "engine_internal.hip.h"
 
 using namespace gt;
+// gt_gemm_b16_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
+static std::atomic<int64_t> g_b16_paths[GT_GEMM_B16_PATH_SLOTS];
+void b16_path_count(int slot) { g_b16_paths[slot].fetch_add(1, std::memory_order_relaxed); }
+extern "C" int gt_gemm_b16_path_counts(int64_t* counts, int reset) {
+  for (int i = 0; i < GT_GEMM_B16_PATH_SLOTS; ++i) {
+    const int64_t v = reset ? g_b16_paths[i].exchange(0, std::memory_order_relaxed) : g_b16_paths[i].load(std::memory_order_relaxed);
+    if (counts) counts[i] = v;
+  }
+  return GT_OK;
+}
 // ------------------------------------------------------------------------------------------
 // bf16-storage products (gemm_bf16s.hip.h; GT_OPT_MATMUL_BF16)
 // ------------------------------------------------------------------------------------------
@@ -21,6 +32,7 @@ static int launch_gemm_b16_t(GemmB16Args g, int nslab, hipStream_t s) {
     rec.e0 = g_prof.get(); rec.e1 = g_prof.get();
     HIPCHK(hipEventRecord(rec.e0, s));
   }
+  b16_path_count(b16_path_slot(EPI, AMODE, BM == 64 ? 0 : 1));
   hipLaunchKernelGGL((gemm_b16_kernel<BM, BN, EPI, AMODE>), dim3(grid), dim3(GEMM_THREADS), lds, s, g);
   LAUNCH_CHECK();
   if (g_prof.wants(g.epi)) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }
@@ -47,6 +59,7 @@ static int launch_gemm_b16_dma(GemmB16Args g, int nslab, hipStream_t s) {
     rec.e0 = g_prof.get(); rec.e1 = g_prof.get();
     HIPCHK(hipEventRecord(rec.e0, s));
   }
+  b16_path_count(b16_path_slot(EPI, AMODE, T == 128 ? 2 : 3));
   hipLaunchKernelGGL((gemm_b16_dma_kernel<T, T, EPI, AMODE, 2, 2, WGN>), dim3(grid), dim3(64 * 2 * WGN), lds, s, g);
   LAUNCH_CHECK();
   if (g_prof.wants(g.epi)) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }
@@ -60,9 +73,9 @@ int launch_gemm_b16(const GemmB16Args& g, int nslab, hipStream_t s, int tile) {
   if (g.CbT && ((g.ldcbt & 3) || (((uintptr_t)g.CbT) & 7))) return fail(GT_ERR_INVALID, "bf16 product: transposed result must be 8-byte aligned");
   // 128 x 128 tiles once they still give every CU two workgroups (one resident round), else 64 x 64 (four per CU)
   const long t128 = (long)cdiv(g.M, 128) * cdiv(g.N, 128) * nslab;
-  const int force_tiles = gt_tuning().b16_tiles;      // measurement knob: 64 / 128 / 256
+  const int force_tiles = gt_tuning().b16_tiles;      // measurement knob: 64 / 128 / 256, taken whenever that form is legal
   const bool big = tile ? tile >= 128
-                        : (force_tiles == 64 ? false : (g.epi != B16_SLAB && g.M >= 128 && g.N >= 128 && (force_tiles == 128 || t128 >= 2L * gemm_cu_count())));
+                        : (force_tiles == 64 ? false : (g.epi != B16_SLAB && g.M >= 128 && g.N >= 128 && (force_tiles >= 128 || t128 >= 2L * gemm_cu_count())));
   // operand stages by LDS-DMA when no element of a stage needs masking and no row sums ride in the loader
   const bool dma_on = gt_tuning().b16_dma != 0;
   const bool dma = dma_on && big && g.K % 64 == 0 && (g.epi != B16_SLAB || (g.k_chunk % 64 == 0 && !g.rowsum_slab));
@@ -105,9 +118,11 @@ static int cast_transpose_t(const TIN* in, int ld_in, long rows, int cols, __bf1
   const int gx = cdiv(rows, 64);
   float* part = nullptr;
   if (colsum) { CHK(colp->ensure((size_t)gx * cols * sizeof(float))); part = colp->as<float>(); }
+  b16_path_count(sizeof(TIN) == 4 ? B16_PATH_CAST_F32 : B16_PATH_CAST_BF16);
   hipLaunchKernelGGL((cast_transpose_kernel<TIN>), dim3(gx, cdiv(cols, 64)), dim3(256), 0, s, in, ld_in, rows, cols, out, ldo, outT, ldt, part);
   LAUNCH_CHECK();
   if (colsum) {
+    gemm_path_count(GEMM_PATH_COLSUM_FINALIZE);
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(cols, 256)), dim3(256), 0, s, (const float*)part, gx, cols, colsum, colsum_accumulate ? 1 : 0);
     LAUNCH_CHECK();
   }
@@ -120,6 +135,40 @@ int cast_transpose(const float* in, int ld_in, long rows, int cols, __bf16* out,
 int cast_transpose(const __bf16* in, int ld_in, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt,
                    float* colsum, bool colsum_accumulate, Scratch* colp, hipStream_t s) {
   return cast_transpose_t<__bf16>(in, ld_in, rows, cols, out, ldo, outT, ldt, colsum, colsum_accumulate, colp, s);
+}
+// the image builders whose source is not a plain matrix: one launch site each for the engine and gt_op_cast_image
+int cast_jobs_add(CastJobs& jobs, int& blocks, const float* in, int ldi, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt) {
+  if (jobs.n >= CAST_MAX_JOBS) return fail(GT_ERR_STATE, "cast job table is full");
+  CastJob& J = jobs.j[jobs.n++];
+  J.in = in; J.ldi = ldi; J.rows = rows; J.cols = cols; J.out = out; J.ldo = ldo; J.outT = outT; J.ldt = ldt;
+  J.gy = cdiv(cols, 64); J.block0 = blocks; J.pad_ = 0;
+  blocks += cdiv(rows, 64) * J.gy;
+  return GT_OK;
+}
+int cast_transpose_multi(const CastJobs& jobs, int blocks, hipStream_t s) {
+  if (jobs.n <= 0 || blocks <= 0) return GT_OK;
+  b16_path_count(B16_PATH_CAST_MULTI);
+  hipLaunchKernelGGL(cast_transpose_multi_kernel, dim3(blocks), dim3(256), 0, s, jobs);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int seqdrop_cast_transpose(const SeqDropSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s) {
+  b16_path_count(B16_PATH_CAST_SEQDROP);
+  hipLaunchKernelGGL(seqdrop_cast_transpose_kernel, dim3(cdiv(rows, 64), cdiv(cols, 64)), dim3(256), 0, s, src, rows, cols, out, ldo, outT, ldt);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int cat_cast_transpose(const CatSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s) {
+  b16_path_count(B16_PATH_CAST_CAT);
+  hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(rows, 64), cdiv(cols, 64)), dim3(256), 0, s, src, rows, cols, out, ldo, outT, ldt);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int catdrop_cast_transpose(const CatDropSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s) {
+  b16_path_count(B16_PATH_CAST_CATDROP);
+  hipLaunchKernelGGL(catdrop_cast_transpose_kernel, dim3(cdiv(rows, 64), cdiv(cols, 64)), dim3(256), 0, s, src, rows, cols, out, ldo, outT, ldt);
+  LAUNCH_CHECK();
+  return GT_OK;
 }
 // dW (+)= dZT . XT^T over the frame dimension (K = rows), db (+)= row sums of dZT; split into float32 slabs, fixed-order combine
 // defer (optional, fused single-GPU step): the slabs go to the network's pool and the combine is only recorded; all
@@ -182,14 +231,17 @@ int weight_grad_b16(const __bf16* dZT, long lddzt, const __bf16* XT, long ldxt, 
       defer->blocks += main_blocks + bias_blocks;
       return GT_OK;
     }
+    gemm_path_count(GEMM_PATH_REDUCE4);
     hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride / 4,
                        dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
     LAUNCH_CHECK();
   } else {
+    gemm_path_count(GEMM_PATH_REDUCE);
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride, dW,
                        accumulate ? 1 : 0);
     LAUNCH_CHECK();
     if (db) {
+      gemm_path_count(GEMM_PATH_REDUCE_SMALL);
       hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db, accumulate ? 1 : 0);
       LAUNCH_CHECK();
     }

@@ -220,6 +220,20 @@ extern "C" int gt_op_linear_bf16(const float* X, const float* W, const float* bi
   return GT_OK;
 }
 
+// the dropout of a parity-hook case: none, the caller's Philox keys (as philox_site_spec) or the caller's mask
+static DropoutSpec case_drop_spec(int mode, const float* mask, int ld_mask, float p, uint32_t key0, uint32_t key1) {
+  DropoutSpec drop = no_drop();
+  if (mode == DROP_BUFFER) {
+    drop = buffer_spec(mask, p, ld_mask);
+  } else if (mode == DROP_PHILOX) {
+    drop.mode = DROP_PHILOX; drop.p = p; drop.scale = 1.f / (1.f - p);
+    const double th = (double)p * 65536.0 + 0.5;
+    drop.thresh = th >= 65535.0 ? 65535u : (uint32_t)th;
+    drop.key0 = key0; drop.key1 = key1;
+  }
+  return drop;
+}
+
 // One product of the float32 MFMA family through the engine's own dispatch (linear_forward / launch_gemm / linear_backward_data /
 // linear_backward_weight / linear_backward_weight_split): parity hook of tests/test_gpu_gemm_f32.py.  Forms the engine builds in
 // place (the added-matrix and two-segment forward of the split first layer, eng_step.hip: stack_forward; accumulate) are built
@@ -245,15 +259,7 @@ extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
   if (data && c->act != ACT_NONE && !c->h) return fail(GT_ERR_INVALID, "activation derivative without h");
   if (wgrad && (!c->dy || (!c->dw && !c->db) || (c->dw && !c->x) || (split && !c->dw))) return fail(GT_ERR_INVALID, "weight gradient needs dy, x and dw / db");
   hipStream_t s = (hipStream_t)stream;
-  DropoutSpec drop = no_drop();
-  if (c->drop == DROP_BUFFER) {
-    drop = buffer_spec(c->mask, c->p, c->ld_mask);
-  } else if (c->drop == DROP_PHILOX) {     // as philox_site_spec, with the caller's keys
-    drop.mode = DROP_PHILOX; drop.p = c->p; drop.scale = 1.f / (1.f - c->p);
-    const double th = (double)c->p * 65536.0 + 0.5;
-    drop.thresh = th >= 65535.0 ? 65535u : (uint32_t)th;
-    drop.key0 = c->key0; drop.key1 = c->key1;
-  }
+  const DropoutSpec drop = case_drop_spec(c->drop, c->mask, c->ld_mask, c->p, c->key0, c->key1);
   Scratch slabs, colp;
   SlabDefer sd;
   sd.active = c->defer != 0;
@@ -312,6 +318,150 @@ extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
   slabs.release(); colp.release(); sd.pool.release();
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_f32: %s", hipGetErrorString(err));
+  return GT_OK;
+}
+
+// One product of the bf16-storage family through the production dispatch (launch_gemm_b16 / weight_grad_b16): parity hook of
+// tests/test_gpu_gemm_b16.py.  The operand images are built by cast_transpose into buffers filled with 0xFF bytes (bf16 NaN), so a
+// loader that uses a pad element shows in the result.
+extern "C" int gt_op_gemm_b16(const gt_gemm_b16_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  const int route = c->route;
+  if (route != GT_GEMM_ROUTE_FORWARD && route != GT_GEMM_ROUTE_BACKWARD_DATA && route != GT_GEMM_ROUTE_WEIGHT_GRAD)
+    return fail(GT_ERR_INVALID, "bf16 product hook: unknown route %d", route);
+  if (c->rows < 1 || c->in_dim < 1 || c->out_dim < 1) return fail(GT_ERR_INVALID, "bf16 product hook: bad sizes");
+  if (c->act < ACT_NONE || c->act > ACT_SIGMOID || c->drop < DROP_NONE || c->drop > DROP_BUFFER)
+    return fail(GT_ERR_INVALID, "bf16 product hook: unknown activation / dropout");
+  if (c->drop != DROP_NONE && (c->act != ACT_LEAKY_DROPOUT || !(c->p > 0.f && c->p < 1.f) || (c->drop == DROP_BUFFER && !c->mask)))
+    return fail(GT_ERR_INVALID, "bf16 product hook: dropout needs act 1, 0 < p < 1 and (buffer) a mask");
+  const bool wg = route == GT_GEMM_ROUTE_WEIGHT_GRAD, fwd = route == GT_GEMM_ROUTE_FORWARD;
+  const int M = c->rows, N = fwd ? c->out_dim : c->in_dim;
+  for (const void* q : {(const void*)c->x, (const void*)c->w, (const void*)c->bias, (const void*)c->dy, (const void*)c->h, (const void*)c->mask,
+                        (const void*)c->c, (const void*)c->dw, (const void*)c->db})
+    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "bf16 product hook: misaligned float32 operand");
+  if (fwd && (!c->x || !c->w || c->ldx < c->in_dim || c->ldw < c->in_dim)) return fail(GT_ERR_INVALID, "bf16 product hook: forward needs x and w");
+  if (route == GT_GEMM_ROUTE_BACKWARD_DATA && (!c->dy || !c->w || c->ld_dy < c->out_dim || c->ldw < c->in_dim))
+    return fail(GT_ERR_INVALID, "bf16 product hook: backward-data needs dy and w");
+  if (route == GT_GEMM_ROUTE_BACKWARD_DATA && c->act != ACT_NONE && (!c->h || c->ldh < c->in_dim))
+    return fail(GT_ERR_INVALID, "bf16 product hook: activation derivative without h");
+  if (wg && (!c->dy || !c->x || !c->dw || c->ld_dy < c->out_dim || c->ldx < c->in_dim || c->act != ACT_NONE))
+    return fail(GT_ERR_INVALID, "bf16 product hook: weight gradient needs dy, x and dw, and no activation");
+  if (c->drop == DROP_BUFFER && c->ld_mask < N) return fail(GT_ERR_INVALID, "bf16 product hook: mask pitch");
+  if (!wg) {
+    if (!c->c && !c->cb && !c->cbt) return fail(GT_ERR_INVALID, "bf16 product hook: no result requested");
+    if ((c->c && c->ldc < N) || (c->cb && c->ldcb < N) || (c->cbt && c->ldcbt < M)) return fail(GT_ERR_INVALID, "bf16 product hook: result pitch");
+    if (((uintptr_t)c->cb) & 1) return fail(GT_ERR_INVALID, "bf16 product hook: misaligned bf16 result");
+    if (c->cbt && ((c->ldcbt & 3) || (((uintptr_t)c->cbt) & 7)))
+      return fail(GT_ERR_INVALID, "bf16 product hook: transposed result must be 8-byte aligned with a pitch that is a multiple of 4");
+    if (c->accumulate && !c->c) return fail(GT_ERR_INVALID, "bf16 product hook: accumulate needs the float32 result");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int in8 = pad8(c->in_dim), out8 = pad8(c->out_dim);
+  const long rows8 = pad8((long)c->rows);
+  Scratch ab, bb, hb, slabs, colp;
+  auto poisoned = [&](Scratch& q, size_t bytes) -> int {
+    CHK(q.ensure(bytes));
+    HIPCHK(hipMemsetAsync(q.p, 0xFF, bytes, s));
+    return GT_OK;
+  };
+  auto body = [&]() -> int {
+    __bf16* const none = nullptr;
+    if (wg) {      // dZT [out][rows8], XT [in][rows8]
+      CHK(poisoned(ab, (size_t)c->out_dim * rows8 * 2)); CHK(poisoned(bb, (size_t)c->in_dim * rows8 * 2));
+      CHK(cast_transpose(c->dy, c->ld_dy, c->rows, c->out_dim, none, 0, ab.as<__bf16>(), rows8, nullptr, false, &colp, s));
+      CHK(cast_transpose(c->x, c->ldx, c->rows, c->in_dim, none, 0, bb.as<__bf16>(), rows8, nullptr, false, &colp, s));
+      return weight_grad_b16(ab.as<__bf16>(), rows8, bb.as<__bf16>(), rows8, c->rows, c->out_dim, c->in_dim, c->dw, c->db, c->accumulate != 0, slabs, s);
+    }
+    GemmB16Args g = b16_args();
+    if (fwd) {     // X [rows][in8], W [out][in8]
+      CHK(poisoned(ab, (size_t)c->rows * in8 * 2)); CHK(poisoned(bb, (size_t)c->out_dim * in8 * 2));
+      CHK(cast_transpose(c->x, c->ldx, c->rows, c->in_dim, ab.as<__bf16>(), in8, none, 0, nullptr, false, &colp, s));
+      CHK(cast_transpose(c->w, c->ldw, c->out_dim, c->in_dim, bb.as<__bf16>(), in8, none, 0, nullptr, false, &colp, s));
+      g.lda = g.ldb = in8; g.K = c->in_dim; g.bias = c->bias; g.epi = B16_FWD;
+    } else {       // dZ [rows][out8], WT [in][out8], H [rows][in8]
+      CHK(poisoned(ab, (size_t)c->rows * out8 * 2)); CHK(poisoned(bb, (size_t)c->in_dim * out8 * 2));
+      CHK(cast_transpose(c->dy, c->ld_dy, c->rows, c->out_dim, ab.as<__bf16>(), out8, none, 0, nullptr, false, &colp, s));
+      CHK(cast_transpose(c->w, c->ldw, c->out_dim, c->in_dim, none, 0, bb.as<__bf16>(), out8, nullptr, false, &colp, s));
+      g.lda = g.ldb = out8; g.K = c->out_dim; g.epi = B16_BWD_DATA;
+      if (c->act != ACT_NONE) {
+        CHK(poisoned(hb, (size_t)c->rows * in8 * 2));
+        CHK(cast_transpose(c->h, c->ldh, c->rows, c->in_dim, hb.as<__bf16>(), in8, none, 0, nullptr, false, &colp, s));
+        g.H = hb.as<__bf16>(); g.ldh = in8;
+      }
+    }
+    g.A = ab.as<__bf16>(); g.B = bb.as<__bf16>(); g.M = M; g.N = N;
+    g.C = c->c; g.ldc = c->ldc; g.Cb = (__bf16*)c->cb; g.ldcb = c->ldcb; g.CbT = (__bf16*)c->cbt; g.ldcbt = c->ldcbt;
+    g.act = c->act; g.accumulate = c->accumulate ? 1 : 0;
+    g.drop = case_drop_spec(c->drop, c->mask, c->ld_mask, c->p, c->key0, c->key1);
+    return launch_gemm_b16(g, 1, s);
+  };
+  const int r = body();
+  const hipError_t err = hipStreamSynchronize(s);
+  for (Scratch* q : {&ab, &bb, &hb, &slabs, &colp}) q->release();
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_b16: %s", hipGetErrorString(err));
+  return GT_OK;
+}
+
+// One image builder of the bf16-storage family through the engine's launch code: parity hook of tests/test_gpu_gemm_b16.py.
+extern "C" int gt_op_cast_image(const gt_cast_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (c->kind < GT_CAST_PLAIN_F32 || c->kind > GT_CAST_MULTI) return fail(GT_ERR_INVALID, "cast hook: unknown kind %d", c->kind);
+  hipStream_t s = (hipStream_t)stream;
+  if (c->kind == GT_CAST_MULTI) {
+    if (c->n_jobs < 1 || c->n_jobs > CAST_MAX_JOBS) return fail(GT_ERR_INVALID, "cast hook: 1 .. %d jobs", CAST_MAX_JOBS);
+    CastJobs jobs;
+    jobs.n = 0; jobs.pad_ = 0;
+    int blocks = 0;
+    for (int i = 0; i < c->n_jobs; ++i) {
+      const gt_cast_job& j = c->jobs[i];
+      if (!j.in || (!j.out && !j.outT) || j.rows < 1 || j.cols < 1 || j.ldi < j.cols || (j.out && j.ldo < j.cols) || (j.outT && j.ldt < j.rows))
+        return fail(GT_ERR_INVALID, "cast hook: bad job %d", i);
+      if ((((uintptr_t)j.in) & 3) || (((uintptr_t)j.out) & 1) || (((uintptr_t)j.outT) & 1)) return fail(GT_ERR_INVALID, "cast hook: misaligned job %d", i);
+      CHK(cast_jobs_add(jobs, blocks, j.in, j.ldi, j.rows, j.cols, (__bf16*)j.out, j.ldo, (__bf16*)j.outT, j.ldt));
+    }
+    CHK(cast_transpose_multi(jobs, blocks, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GT_OK;
+  }
+  if (c->rows < 1 || c->cols < 1 || (!c->out && !c->outT) || (c->out && c->ldo < c->cols) || (c->outT && c->ldt < c->rows))
+    return fail(GT_ERR_INVALID, "cast hook: bad sizes");
+  if ((((uintptr_t)c->out) & 1) || (((uintptr_t)c->outT) & 1)) return fail(GT_ERR_INVALID, "cast hook: misaligned image");
+  const bool cat = c->kind == GT_CAST_CAT || c->kind == GT_CAST_CATDROP, drop = c->kind == GT_CAST_SEQDROP || c->kind == GT_CAST_CATDROP;
+  if (!cat && (!c->in || c->ldi < c->cols || (((uintptr_t)c->in) & (c->kind == GT_CAST_PLAIN_BF16 ? 1 : 3))))
+    return fail(GT_ERR_INVALID, "cast hook: bad source");
+  if (c->colsum && c->kind != GT_CAST_PLAIN_F32) return fail(GT_ERR_INVALID, "cast hook: column sums ride with the float32 source only");
+  if (drop && (!c->mul || c->T < 1)) return fail(GT_ERR_INVALID, "cast hook: dropout needs mul and T");
+  if (cat && (c->cd < 0 || c->cd > c->cols || (c->cd > 0 && !c->x) || (c->cd < c->cols && (!c->idx || !c->fa || !c->fb || c->ldf < 1)) || c->N < 1 ||
+              c->row_off < 0 || c->row_off + c->rows > 2 * c->N))
+    return fail(GT_ERR_INVALID, "cast hook: bad [x | feats[:, idx]] source");
+  __bf16* out = (__bf16*)c->out;
+  __bf16* outT = (__bf16*)c->outT;
+  Scratch colp;
+  int r = GT_OK;
+  const CatSrc cs{c->x, c->cd, c->fa, c->fb, c->ldf, c->idx, (long)c->N, (long)c->row_off};
+  switch (c->kind) {
+    case GT_CAST_PLAIN_F32:
+      r = cast_transpose((const float*)c->in, c->ldi, c->rows, c->cols, out, c->ldo, outT, c->ldt, c->colsum, c->colsum_accumulate != 0, &colp, s);
+      break;
+    case GT_CAST_PLAIN_BF16:
+      r = cast_transpose((const __bf16*)c->in, c->ldi, c->rows, c->cols, out, c->ldo, outT, c->ldt, nullptr, false, &colp, s);
+      break;
+    case GT_CAST_SEQDROP: {
+      const SeqDropSrc src{(const float*)c->in, c->ldi, c->mul, c->T, c->cols};
+      r = seqdrop_cast_transpose(src, c->rows, c->cols, out, c->ldo, outT, c->ldt, s);
+      break;
+    }
+    case GT_CAST_CAT: r = cat_cast_transpose(cs, c->rows, c->cols, out, c->ldo, outT, c->ldt, s); break;
+    default: {
+      const CatDropSrc src{cs, c->mul, c->T, c->cols};
+      r = catdrop_cast_transpose(src, c->rows, c->cols, out, c->ldo, outT, c->ldt, s);
+    }
+  }
+  const hipError_t err = hipStreamSynchronize(s);
+  colp.release();
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "cast_image: %s", hipGetErrorString(err));
   return GT_OK;
 }
 

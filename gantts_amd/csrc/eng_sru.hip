@@ -194,18 +194,13 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       } else if (l == 0 && cat0) {   // a discriminator's [x | adv] rows: one pass from the caller's tensors to both images, dropout riding along
         if (rdrop) {
           const CatDropSrc src{*cat0, W.xmask[0].as<float>(), T, L.in};
-          hipLaunchKernelGGL(catdrop_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, src, N, L.in, I.r(), I.ld,
-                             want_t ? I.t() : (__bf16*)nullptr, I.ldt);
+          CHK(catdrop_cast_transpose(src, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, s));
         } else {
-          hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, *cat0, N, L.in, I.r(), I.ld,
-                             want_t ? I.t() : (__bf16*)nullptr, I.ldt);
+          CHK(cat_cast_transpose(*cat0, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, s));
         }
-        LAUNCH_CHECK();
       } else if (rdrop) {            // bf16 products: dropout rides in the cast, the dropped input exists as bf16 images only
         const SeqDropSrc src{in, ld_in, W.xmask[l].as<float>(), T, L.in};
-        hipLaunchKernelGGL(seqdrop_cast_transpose_kernel, dim3(cdiv(N, 64), cdiv(L.in, 64)), dim3(256), 0, s, src, N, L.in, I.r(), I.ld,
-                           want_t ? I.t() : (__bf16*)nullptr, I.ldt);
-        LAUNCH_CHECK();
+        CHK(seqdrop_cast_transpose(src, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, s));
       } else {
         CHK(cast_transpose(xin, ld_xin, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
       }

@@ -277,10 +277,7 @@ static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s
   jobs.n = 0; jobs.pad_ = 0;
   int blocks = 0;
   auto flush = [&]() -> int {
-    if (jobs.n > 0) {
-      hipLaunchKernelGGL(cast_transpose_multi_kernel, dim3(blocks), dim3(256), 0, s, jobs);
-      LAUNCH_CHECK();
-    }
+    CHK(cast_transpose_multi(jobs, blocks, s));
     jobs.n = 0; blocks = 0;
     return GT_OK;
   };
@@ -292,10 +289,7 @@ static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s
     CHK(w.w.ensure((size_t)L.out * w.ldw * 2 + 64));
     CHK(w.wt.ensure((size_t)L.in * w.ldwt * 2 + 64));
     if (jobs.n == CAST_MAX_JOBS) CHK(flush());
-    CastJob& J = jobs.j[jobs.n++];
-    J.in = L.W; J.ldi = L.in; J.rows = L.out; J.cols = L.in; J.out = w.w.as<__bf16>(); J.ldo = w.ldw; J.outT = w.wt.as<__bf16>(); J.ldt = w.ldwt;
-    J.gy = cdiv(L.in, 64); J.block0 = blocks; J.pad_ = 0;
-    blocks += cdiv(L.out, 64) * J.gy;
+    CHK(cast_jobs_add(jobs, blocks, L.W, L.in, L.out, L.in, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt));
   }
   return flush();
 }
@@ -832,9 +826,8 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
   if (p.kind == D_MLP_B16) {
     CHK(e->dcat_b.ensure(2 * N, p.K0, p.want_w));
     if (both || !e->img_cat_b.holds(p.x, p.fake)) {
-      hipLaunchKernelGGL(cat_cast_transpose_kernel, dim3(cdiv(p.rows, 64), cdiv(p.K0, 64)), dim3(256), 0, s, p.cat0, p.rows, p.K0,
-                         e->dcat_b.r() + row0 * e->dcat_b.ld, e->dcat_b.ld, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr, p.want_w ? e->dcat_b.ldt : 0L);
-      LAUNCH_CHECK();
+      CHK(cat_cast_transpose(p.cat0, p.rows, p.K0, e->dcat_b.r() + row0 * e->dcat_b.ld, e->dcat_b.ld, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr,
+                             p.want_w ? e->dcat_b.ldt : 0L, s));
       e->img_cat_b.built(p.x, p.fake);
     }
   } else if (p.split) {

@@ -404,12 +404,23 @@ int linear_backward_weight_split(const float* dZ, int lddz, long rows, long wrap
 // eng_gemm_b16.hip
 // ------------------------------------------------------------------------------------------
 gt::GemmB16Args b16_args();
+// gt_gemm_b16_path_counts: launches of the family by kernel, counted on the host where they are issued (slot layout in gantts_hip.h)
+enum { B16_PATH_CAST_F32 = 60, B16_PATH_CAST_BF16 = 61, B16_PATH_CAST_SEQDROP = 62, B16_PATH_CAST_MULTI = 63, B16_PATH_CAST_CAT = 64,
+       B16_PATH_CAST_CATDROP = 65 };
+static_assert(B16_PATH_CAST_CATDROP + 1 == GT_GEMM_B16_PATH_SLOTS, "gt_gemm_b16_path_counts slots");
+constexpr int b16_path_slot(int epi, int amode, int form) { return (epi * 5 + amode) * 4 + form; }
+void b16_path_count(int slot);
 int launch_gemm_b16(const gt::GemmB16Args& g, int nslab, hipStream_t s, int tile = 0);
 // [rows][ld_in] float32 / bf16 -> bf16 [rows][ldo] and / or its transpose [cols][ldt] (+ per-column sums -> colsum)
 int cast_transpose(const float* in, int ld_in, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt,
                    float* colsum, bool colsum_accumulate, Scratch* colp, hipStream_t s);
 int cast_transpose(const __bf16* in, int ld_in, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt,
                    float* colsum, bool colsum_accumulate, Scratch* colp, hipStream_t s);
+int cast_jobs_add(gt::CastJobs& jobs, int& blocks, const float* in, int ldi, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt);
+int cast_transpose_multi(const gt::CastJobs& jobs, int blocks, hipStream_t s);
+int seqdrop_cast_transpose(const gt::SeqDropSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s);
+int cat_cast_transpose(const gt::CatSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s);
+int catdrop_cast_transpose(const gt::CatDropSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s);
 int weight_grad_b16(const __bf16* dZT, long lddzt, const __bf16* XT, long ldxt, long rows, int out, int in, float* dW, float* db,
                     bool accumulate, Scratch& slabs, hipStream_t s, SlabDefer* defer = nullptr);
 

@@ -532,6 +532,92 @@ int gt_op_gemm_f32(const gt_gemm_case* c, void* stream);
 #define GT_GEMM_PATH_SLOTS 588
 int gt_gemm_path_counts(int64_t* counts, int reset);
 
+/* Launches of the bf16-storage product family (gemm_bf16s.hip.h; GT_OPT_MATMUL_BF16 / GT_OPT_SRU_D_BF16) by kernel, process-wide,
+ * counted on the host where each launch is issued (no device work, no synchronisation).  Slots:
+ *   product   (epi * 5 + amode) * 4 + form                                                                            (0..59)
+ *             epi 0 forward, 1 backward-data, 2 weight-gradient slab (amode 0 only); amode (GemmB16Amode) 0 none, 1 LeakyReLU +
+ *             Philox, 2 LeakyReLU + buffer mask, 3 LeakyReLU, 4 sigmoid; form 0 64 x 64, 1 128 x 128 register loader,
+ *             2 128 x 128 LDS-DMA, 3 256 x 256 LDS-DMA (8 waves)
+ *   60..65    image builders: cast_transpose<float>, cast_transpose<bf16>, seqdrop, multi, cat, catdrop
+ * The combines of the weight gradient (slab_reduce4, slab_reduce, slab_reduce_small, the deferred multi combine) and the column-sum
+ * finalize of cast_transpose are counted in slots 582..587 of gt_gemm_path_counts.
+ * Copies the GT_GEMM_B16_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
+#define GT_GEMM_B16_PATH_SLOTS 66
+int gt_gemm_b16_path_counts(int64_t* counts, int reset);
+
+/* Parity hook of the bf16-storage products: one product through the production dispatch (launch_gemm_b16 for FORWARD and
+ * BACKWARD_DATA, weight_grad_b16 for WEIGHT_GRAD).  Operands are float32 device matrices (pitches in floats); the hook builds their
+ * bf16 images with cast_transpose into buffers it has filled with 0xFF bytes (bf16 NaN) first, so every pad of an image is poisoned.
+ *   FORWARD        M = rows, N = out_dim, K = in_dim:  act(x[rows][ldx] . w[out][ldw]^T + bias) with the dropout of `drop`
+ *   BACKWARD_DATA  M = rows, N = in_dim, K = out_dim:  (dy[rows][ld_dy] . w[out][ldw]) (.) f'(h[rows][ldh]); act is the PRODUCER's
+ *                  activation, the dropout its dropout (mask [rows][ld_mask], in_dim wide)
+ *   WEIGHT_GRAD    dw[out][in] (+= if accumulate) dy^T . x over rows frames, db[out] (+=) the column sums of the bf16 dy, or null
+ * FORWARD / BACKWARD_DATA results, any of them null: c float32 [M][ldc] (+= if accumulate), cb the bf16 image [M][ldcb], cbt its
+ * transposed twin [N][ldcbt] (raw 16-bit elements, pitches in elements; ldcbt % 4 == 0 and cbt 8-byte aligned).  act 0 none,
+ * 1 LeakyReLU (+ dropout), 2 sigmoid; drop 0 none, 1 Philox keep bits of (key0, key1), 2 the 0/1 float mask.
+ * Scratch is allocated, synchronised and released inside the call.  A malformed case returns GT_ERR_INVALID. */
+typedef struct gt_gemm_b16_case {
+  int32_t route;             /* GT_GEMM_ROUTE_FORWARD / _BACKWARD_DATA / _WEIGHT_GRAD */
+  int32_t rows, in_dim, out_dim;
+  int32_t act, drop;
+  float p;
+  uint32_t key0, key1;
+  int32_t accumulate;
+  int32_t ldx, ldw, ld_dy, ldh, ld_mask, ldc, ldcb, ldcbt;
+  const float* x;
+  const float* w;
+  const float* bias;
+  const float* dy;
+  const float* h;
+  const float* mask;
+  float* c;
+  uint16_t* cb;
+  uint16_t* cbt;
+  float* dw;
+  float* db;
+} gt_gemm_b16_case;
+int gt_op_gemm_b16(const gt_gemm_b16_case* c, void* stream);
+
+/* Parity hook of the bf16 image builders: one launch of the named kind through the engine's own launch code.  out [rows][ldo] and
+ * outT [cols][ldt] are the caller's 16-bit buffers (either may be null); pads are not written.
+ *   PLAIN_F32   in float32 [rows][ldi]; colsum (optional) [cols] (+= if colsum_accumulate) the column sums of the float32 values
+ *   PLAIN_BF16  in a bf16 image [rows][ldi]
+ *   SEQDROP     in float32 [rows][ldi] times mul[r / T][c], mul [rows / T][cols]
+ *   CAT         image row r (g = r + row_off) = [x[g mod N][cd] | (g < N ? fa : fb)[g mod N][ldf] gathered by idx[cols - cd]]
+ *   CATDROP     ... times mul[r / T][c]
+ *   MULTI       jobs[0 .. n_jobs) float32 matrices in one launch (n_jobs <= 8) */
+#define GT_CAST_PLAIN_F32 0
+#define GT_CAST_PLAIN_BF16 1
+#define GT_CAST_SEQDROP 2
+#define GT_CAST_CAT 3
+#define GT_CAST_CATDROP 4
+#define GT_CAST_MULTI 5
+#define GT_CAST_MAX_JOBS 8
+typedef struct gt_cast_job {
+  const float* in;
+  uint16_t* out;
+  uint16_t* outT;
+  int64_t rows, ldt;
+  int32_t ldi, cols, ldo, pad_;
+} gt_cast_job;
+typedef struct gt_cast_case {
+  int32_t kind, cols, ldi, ldo;
+  int32_t colsum_accumulate, T, cd, ldf;
+  int32_t n_jobs, pad_;
+  int64_t rows, ldt, N, row_off;
+  const void* in;
+  uint16_t* out;
+  uint16_t* outT;
+  float* colsum;
+  const float* mul;
+  const float* x;
+  const float* fa;
+  const float* fb;
+  const int32_t* idx;
+  gt_cast_job jobs[GT_CAST_MAX_JOBS];
+} gt_cast_case;
+int gt_op_cast_image(const gt_cast_case* c, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

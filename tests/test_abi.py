@@ -40,6 +40,11 @@ def test_ctypes_structs_match_header_layout():
     assert _lib.ModelDesc.params.offset == 48 and C.sizeof(_lib.ModelDesc) == 72
     assert _lib.OptimDesc.step.offset == 32 and C.sizeof(_lib.OptimDesc) == 56
     assert _lib.GemmCase.x.offset == 104 and _lib.GemmCase.db.offset == 192 and C.sizeof(_lib.GemmCase) == 200
+    assert _lib.GemmB16Case.ldcbt.offset == 68 and _lib.GemmB16Case.x.offset == 72 and _lib.GemmB16Case.db.offset == 152
+    assert C.sizeof(_lib.GemmB16Case) == 160
+    assert C.sizeof(_lib.CastJob) == 56 and _lib.CastJob.rows.offset == 24 and _lib.CastJob.ldi.offset == 40
+    assert _lib.CastCase.rows.offset == 40 and _lib.CastCase.in_.offset == 72 and _lib.CastCase.idx.offset == 136
+    assert _lib.CastCase.jobs.offset == 144 and C.sizeof(_lib.CastCase) == 144 + 8 * 56
 
 
 def test_invalid_arguments_are_reported_not_crashing():
