@@ -28,6 +28,7 @@ PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts
 GEMM_PATH_SLOTS = 588                                                   # gt_gemm_path_counts
 GEMM_B16_PATH_SLOTS = 66                                                # gt_gemm_b16_path_counts
+SRU_PATH_SLOTS = 13                                                     # gt_sru_path_counts
 CAST_PLAIN_F32, CAST_PLAIN_BF16, CAST_SEQDROP, CAST_CAT, CAST_CATDROP, CAST_MULTI = 0, 1, 2, 3, 4, 5      # CastCase.kind
 CAST_MAX_JOBS = 8
 GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
@@ -98,6 +99,15 @@ class GemmB16Case(C.Structure):
                 + [(n, C.c_void_p) for n in ("x", "w", "bias", "dy", "h", "mask", "c", "cb", "cbt", "dw", "db")])
 
 
+class SruScanCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("backward", "B", "T", "H", "dirs", "k", "act", "mask_mode")]
+                + [("keep_scale", C.c_float), ("p", C.c_float), ("key0", C.c_uint32), ("key1", C.c_uint32)]
+                + [(n, C.c_int32) for n in ("seq_mul", "seq_add", "ldu", "ldx", "lddx", "ld_up_add", "ld_nxb", "ld_dub")]
+                + [("ld_nxbt", C.c_int64), ("ld_dubt", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("U", "x", "bias", "h", "c", "dh", "dU", "dx", "dbias_part", "mask", "up_mul", "up_add", "nx_mul",
+                                             "nx_b", "nx_bt", "dU_b", "dU_bt")])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -151,6 +161,11 @@ SIGNATURES = {
     "gt_gemm_b16_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_gemm_b16": (_I, [C.POINTER(GemmB16Case), _P]),
     "gt_op_cast_image": (_I, [C.POINTER(CastCase), _P]),
+    "gt_sru_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_op_sru_scan": (_I, [C.POINTER(SruScanCase), _P]),
+    "gt_op_sru_dx_adv_finish": (_I, [_P, _L, _I, _I, _P, _I, _P, _I, _P]),
+    "gt_op_sru_input_mask": (_I, [_P, _I, _I, _F, C.c_uint32, C.c_uint32, _P, _I, _I, _P]),
+    "gt_op_sru_input_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -465,6 +465,101 @@ extern "C" int gt_op_cast_image(const gt_cast_case* c, void* stream) {
   return GT_OK;
 }
 
+// One SRU scan launch through the stacks' launch functions (sru_launch_fwd / _bwd, eng_sru.hip): parity hook of
+// tests/test_gpu_sru_scan.py.  Everything a kernel would index with is checked first: no case reaches a launch it could fault in.
+extern "C" int gt_op_sru_scan(const gt_sru_scan_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (c->B < 1 || c->T < 1 || c->H < 1 || (c->dirs != 1 && c->dirs != 2)) return fail(GT_ERR_INVALID, "SRU scan hook: bad sizes");
+  if (c->k != 3 && c->k != 4) return fail(GT_ERR_INVALID, "SRU scan hook: k = %d (3 or 4)", c->k);
+  if (c->act < SRU_ID || c->act > SRU_RELU || c->mask_mode < 0 || c->mask_mode > 2) return fail(GT_ERR_INVALID, "SRU scan hook: unknown activation / mask mode");
+  const long ncols = (long)c->H * c->dirs, N = (long)c->B * c->T;
+  if (ncols * c->k > 0x7FFFFFFFL || N > 0x7FFFFFFFL) return fail(GT_ERR_INVALID, "SRU scan hook: sizes beyond the kernels' int indices");
+  const bool bwd = c->backward != 0;
+  for (const void* q : {(const void*)c->U, (const void*)c->x, (const void*)c->bias, (const void*)c->h, (const void*)c->c, (const void*)c->dh,
+                        (const void*)c->dU, (const void*)c->dx, (const void*)c->dbias_part, (const void*)c->mask, (const void*)c->up_mul,
+                        (const void*)c->up_add, (const void*)c->nx_mul})
+    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "SRU scan hook: misaligned float32 operand");
+  if (!c->U || !c->bias || !c->c || c->ldu < ncols * c->k) return fail(GT_ERR_INVALID, "SRU scan hook: needs U (ldu >= ncols * k), bias and c");
+  if (c->k == 3 && (!c->x || c->ldx < ncols)) return fail(GT_ERR_INVALID, "SRU scan hook: k = 3 needs x with ldx >= ncols");
+  if (c->mask_mode == 1 && !c->mask) return fail(GT_ERR_INVALID, "SRU scan hook: mask mode 1 without a mask");
+  if (c->mask_mode == 2 && !(c->p > 0.f && c->p < 1.f)) return fail(GT_ERR_INVALID, "SRU scan hook: Philox mask needs 0 < p < 1");
+  const int waves = sru_scan_waves(c->B, (int)ncols);
+  auto image_ok = [&](const uint16_t* r, long ldr, long wr, const uint16_t* t, long ldt) {
+    return waves != 0 && c->T % 8 == 0 && c->H % 64 == 0 && r && !(((uintptr_t)r) & 15) && !(((uintptr_t)t) & 15) && ldr >= wr && ldr % 8 == 0 &&
+           ldr <= 0x7FFFFFFFL && (!t || (ldt >= N && ldt % 8 == 0));
+  };
+  if (!bwd) {
+    if (!c->h) return fail(GT_ERR_INVALID, "SRU scan hook: forward needs h");
+    if (c->dU_b || c->dU_bt) return fail(GT_ERR_INVALID, "SRU scan hook: dU images belong to the backward scan");
+    if ((c->nx_b || c->nx_bt) && !image_ok(c->nx_b, c->ld_nxb, ncols, c->nx_bt, c->ld_nxbt))
+      return fail(GT_ERR_INVALID, "SRU scan hook: forward images need a cooperative form, T %% 8 == 0, H %% 64 == 0, 16-byte aligned buffers and pitches");
+  } else {
+    if (!c->dh || !c->dbias_part) return fail(GT_ERR_INVALID, "SRU scan hook: backward needs dh and dbias_part");
+    if (c->nx_b || c->nx_bt) return fail(GT_ERR_INVALID, "SRU scan hook: nx images belong to the forward scan");
+    if (c->k == 3 && (!c->dx || c->lddx < ncols)) return fail(GT_ERR_INVALID, "SRU scan hook: k = 3 needs dx with lddx >= ncols");
+    if (c->up_add && c->ld_up_add < ncols) return fail(GT_ERR_INVALID, "SRU scan hook: up_add pitch");
+    if ((c->dU_b || c->dU_bt) && !image_ok(c->dU_b, c->ld_dub, ncols * c->k, c->dU_bt, c->ld_dubt))
+      return fail(GT_ERR_INVALID, "SRU scan hook: dU images need a cooperative form, T %% 8 == 0, H %% 64 == 0, 16-byte aligned buffers and pitches");
+    if (!c->dU_b && !c->dU) return fail(GT_ERR_INVALID, "SRU scan hook: backward needs dU or its images");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  SruArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = c->B; a.T = c->T; a.H = c->H; a.dirs = c->dirs; a.k = c->k; a.act = c->act;
+  a.U = c->U; a.ldu = c->ldu; a.x = c->x; a.ldx = c->ldx; a.bias = c->bias; a.h = c->h; a.c = c->c;
+  a.seq_mul = c->seq_mul; a.seq_add = c->seq_add;
+  if (c->mask_mode == 1) { a.use_mask = 1; a.keep_scale = c->keep_scale; a.mask_buf = c->mask; }
+  if (c->mask_mode == 2) { a.use_mask = 1; a.keep_scale = 1.f / (1.f - c->p); a.thresh = sru_drop_thresh(c->p); a.key0 = c->key0; a.key1 = c->key1; }
+  int r;
+  if (!bwd) {
+    if (c->nx_b) { a.nx_b = (__bf16*)c->nx_b; a.ld_nxb = c->ld_nxb; a.nx_bt = (__bf16*)c->nx_bt; a.ld_nxbt = (long)c->ld_nxbt; a.nx_mul = c->nx_mul; }
+    r = sru_launch_fwd(a, s);
+  } else {
+    a.dh = c->dh; a.dU = c->dU_b ? nullptr : c->dU; a.dx = c->k == 3 ? c->dx : nullptr; a.lddx = c->lddx; a.dbias_part = c->dbias_part;
+    a.up_mul = c->up_mul; a.up_add = c->up_add; a.ld_up_add = c->ld_up_add;
+    if (c->dU_b) { a.dU_b = (__bf16*)c->dU_b; a.ld_dub = c->ld_dub; a.dU_bt = (__bf16*)c->dU_bt; a.ld_dubt = (long)c->ld_dubt; }
+    r = sru_launch_bwd(a, s);
+  }
+  const hipError_t err = hipStreamSynchronize(s);
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "sru_scan: %s", hipGetErrorString(err));
+  return GT_OK;
+}
+
+// The three helper kernels of the SRU stack, each through the engine's launch function: parity hooks of tests/test_gpu_sru_scan.py.
+extern "C" int gt_op_sru_dx_adv_finish(float* dx_adv, int64_t rows, int Da, int T, const float* mul, int ld_mul, const float* hw, int ld_hw,
+                                       void* stream) {
+  if (!dx_adv || rows < 1 || Da < 1 || T < 1 || rows % T) return fail(GT_ERR_INVALID, "dx finish hook: needs dx_adv and rows = sequences x T");
+  if ((((uintptr_t)dx_adv) | ((uintptr_t)mul) | ((uintptr_t)hw)) & 3) return fail(GT_ERR_INVALID, "dx finish hook: misaligned float32 operand");
+  if ((mul && ld_mul < Da) || (hw && ld_hw < Da)) return fail(GT_ERR_INVALID, "dx finish hook: operand pitch below Da");
+  if (rows * Da > 0x7FFFFFFFL * 256) return fail(GT_ERR_INVALID, "dx finish hook: too many elements for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  SruDxAdvArgs f;
+  f.dx_adv = dx_adv; f.rows = (long)rows; f.Da = Da; f.T = T; f.mul = mul; f.ld_mul = ld_mul; f.hw = hw; f.ld_hw = ld_hw;
+  CHK(sru_launch_dx_adv_finish(f, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return GT_OK;
+}
+extern "C" int gt_op_sru_input_mask(float* mul, int B, int n, float p, uint32_t key0, uint32_t key1, const float* inj, int seq_mul, int seq_add,
+                                    void* stream) {
+  if (!mul || B < 1 || n < 1 || (long)B * n > 0x7FFFFFFFL - 256) return fail(GT_ERR_INVALID, "input mask hook: bad sizes");
+  if (!(p > 0.f && p < 1.f)) return fail(GT_ERR_INVALID, "input mask hook: needs 0 < p < 1");
+  if ((((uintptr_t)mul) | ((uintptr_t)inj)) & 3) return fail(GT_ERR_INVALID, "input mask hook: misaligned float32 operand");
+  hipStream_t s = (hipStream_t)stream;
+  CHK(sru_launch_input_mask(mul, B, n, 1.f / (1.f - p), sru_drop_thresh(p), key0, key1, inj, seq_mul, seq_add, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return GT_OK;
+}
+extern "C" int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ldy, int B, int T, int n, const float* mul, void* stream) {
+  if (!x || !y || !mul || B < 1 || T < 1 || n < 1 || ldx < n || ldy < n) return fail(GT_ERR_INVALID, "input dropout hook: bad argument");
+  if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)mul)) & 3) return fail(GT_ERR_INVALID, "input dropout hook: misaligned float32 operand");
+  if ((long)B * T * n > 0x7FFFFFFFL * 256) return fail(GT_ERR_INVALID, "input dropout hook: too many elements for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  CHK(sru_launch_input_dropout(x, ldx, y, ldy, B, T, n, mul, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return GT_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // the optimizer family: validation, the step's scalars, the launch (engine and stand-alone operator alike)
 // ------------------------------------------------------------------------------------------

@@ -1,8 +1,19 @@
 // libgantts_hip.so -- the SRU stack (GT_ARCH_SRU) of either role: the recurrent generator, an SRURNN in the discriminator slot
+#include <atomic>
 #include "engine_internal.hip.h"
 #include "sru_cs_kernels.hip.h"
 #include "sru_kernels.hip.h"
 using namespace gt;
+// gt_sru_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
+static std::atomic<int64_t> g_sru_paths[GT_SRU_PATH_SLOTS];
+static void sru_path_count(int slot) { g_sru_paths[slot].fetch_add(1, std::memory_order_relaxed); }
+extern "C" int gt_sru_path_counts(int64_t* counts, int reset) {
+  for (int i = 0; i < GT_SRU_PATH_SLOTS; ++i) {
+    const int64_t v = reset ? g_sru_paths[i].exchange(0, std::memory_order_relaxed) : g_sru_paths[i].load(std::memory_order_relaxed);
+    if (counts) counts[i] = v;
+  }
+  return GT_OK;
+}
 // ------------------------------------------------------------------------------------------
 // SRU stack (GT_ARCH_SRU), role-generic
 // ------------------------------------------------------------------------------------------
@@ -18,7 +29,7 @@ static void sru_keys(gt_engine* e, int role, int pass, int layer, int which, uin
     *k1 += (salt >> 5) | 1u;
   }
 }
-static uint32_t drop_thresh(float p) {
+uint32_t sru_drop_thresh(float p) {
   const double th = (double)p * 4294967296.0;
   return th >= 4294967295.0 ? 4294967295u : (uint32_t)th;
 }
@@ -53,9 +64,8 @@ static int sru_draw_table(gt_engine* e, const Net& G, int role, int l, int which
   for (int q = 0; q < npass; ++q) {
     uint32_t k0, k1;
     sru_keys(e, role, passes[q], l, which, &k0, &k1);
-    hipLaunchKernelGGL(sru_input_mask_kernel, dim3(cdiv((long)Bg * width, 256)), dim3(256), 0, s, tab + (size_t)q * Bg * width, Bg, width, keep_scale,
-                       drop_thresh(p), k0, k1, (const float*)G.inj[passes[q]][2 * l + which], e->dp_world, e->dp_rank + e->dp_world * q * Bg);
-    LAUNCH_CHECK();
+    CHK(sru_launch_input_mask(tab + (size_t)q * Bg * width, Bg, width, keep_scale, sru_drop_thresh(p), k0, k1,
+                              (const float*)G.inj[passes[q]][2 * l + which], e->dp_world, e->dp_rank + e->dp_world * q * Bg, s));
   }
   return GT_OK;
 }
@@ -73,7 +83,7 @@ static SruArgs sru_args(gt_engine* e, int role, const SruBufs& W, int l, int B, 
   a.h = W.h[l].as<float>(); a.c = W.c[l].as<float>();
   a.seq_mul = e->dp_world; a.seq_add = e->dp_rank;
   if (G.training && G.d.dropout > 0.f && l + 1 < G.d.num_hidden) {   // the last layer has dropout 0 (SRU.__init__)
-    a.use_mask = 1; a.keep_scale = 1.f / (1.f - G.d.dropout); a.thresh = drop_thresh(G.d.dropout);
+    a.use_mask = 1; a.keep_scale = 1.f / (1.f - G.d.dropout); a.thresh = sru_drop_thresh(G.d.dropout);
     if (role == GT_ROLE_G) {
       sru_keys(e, GT_ROLE_G, 0, l, 1, &a.key0, &a.key1);
       a.mask_buf = G.inj[0][2 * l + 1];                              // gt_set_dropout_mask(G, 0, 2*l + 1): [B][ncols]
@@ -93,6 +103,71 @@ static int sru_coop_waves(long B, int ncols) {
   const int forced = gt_tuning().sru_cs_waves;      // (tests: both instantiations on every shape)
   if (forced == 4 || forced == 8) return forced;
   return cdiv(B * ncols, 64) <= 2 * gemm_cu_count() ? 8 : 4;      // (measured: cfg4 B = 16 7.39 vs 7.85 ms; hparams-default generator B = 32, T = 1024 8.07 vs 8.32 ms)
+}
+int sru_scan_waves(long B, int ncols) { return sru_coop() ? sru_coop_waves(B, ncols) : 0; }
+// The one launch site of every scan kernel, for the stacks below and the parity hook (gt_op_sru_scan) alike: the form (sequential, four
+// or eight waves) from the tuning knobs and the shape, the image forms from a.nx_b / a.dU_b being set (the caller has checked their
+// conditions: sru_fold / du_b16).  Each launch is counted in its slot of gt_sru_path_counts.
+int sru_launch_fwd(const SruArgs& a, hipStream_t s) {
+  const int ncols = a.H * a.dirs;
+  if (sru_coop()) {
+    const int grid = cdiv((long)a.B * ncols, 64);
+    const bool w8 = sru_coop_waves(a.B, ncols) == 8, img = a.nx_b != nullptr;
+    if (img) {
+      if (w8) { CHK(ensure_dyn_lds((const void*)sru_fwd_cs_kernel<8, true>, sru_fwd_cs_lds<8>(true)));
+                hipLaunchKernelGGL((sru_fwd_cs_kernel<8, true>), dim3(grid), dim3(512), sru_fwd_cs_lds<8>(true), s, a); }
+      else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, true>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(true), s, a);
+    } else if (w8) hipLaunchKernelGGL((sru_fwd_cs_kernel<8, false>), dim3(grid), dim3(512), sru_fwd_cs_lds<8>(), s, a);
+    else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, false>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(), s, a);
+    sru_path_count(SRU_PATH_FWD_CS + 2 * (w8 ? 1 : 0) + (img ? 1 : 0));
+  } else {
+    hipLaunchKernelGGL(sru_fwd_kernel, dim3(cdiv((long)a.B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
+    sru_path_count(SRU_PATH_FWD);
+  }
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int sru_launch_bwd(const SruArgs& a, hipStream_t s) {
+  const int ncols = a.H * a.dirs;
+  if (sru_coop()) {
+    const int grid = cdiv((long)a.B * ncols, 64);
+    const bool w8 = sru_coop_waves(a.B, ncols) == 8, img = a.dU_b != nullptr;
+#define GT_SRU_CS_LAUNCH(NW_, B16_)                                                                                           \
+    do {                                                                                                                     \
+      CHK(ensure_dyn_lds((const void*)sru_bwd_cs_kernel<NW_, B16_>, sru_bwd_cs_lds<NW_>(B16_)));                             \
+      hipLaunchKernelGGL((sru_bwd_cs_kernel<NW_, B16_>), dim3(grid), dim3(64 * NW_), sru_bwd_cs_lds<NW_>(B16_), s, a);        \
+    } while (0)
+    if (img) { if (w8) GT_SRU_CS_LAUNCH(8, true); else GT_SRU_CS_LAUNCH(4, true); }
+    else { if (w8) GT_SRU_CS_LAUNCH(8, false); else GT_SRU_CS_LAUNCH(4, false); }
+#undef GT_SRU_CS_LAUNCH
+    sru_path_count(SRU_PATH_BWD_CS + 2 * (w8 ? 1 : 0) + (img ? 1 : 0));
+  } else {
+    hipLaunchKernelGGL(sru_bwd_kernel, dim3(cdiv((long)a.B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
+    sru_path_count(SRU_PATH_BWD);
+  }
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+// ... and of the three helper kernels
+int sru_launch_input_mask(float* mul, int B, int n, float keep_scale, uint32_t thresh, uint32_t key0, uint32_t key1, const float* inj,
+                          int seq_mul, int seq_add, hipStream_t s) {
+  hipLaunchKernelGGL(sru_input_mask_kernel, dim3(cdiv((long)B * n, 256)), dim3(256), 0, s, mul, B, n, keep_scale, thresh, key0, key1, inj, seq_mul,
+                     seq_add);
+  sru_path_count(SRU_PATH_INPUT_MASK);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int sru_launch_input_dropout(const float* x, int ldx, float* y, int ldy, int B, int T, int n, const float* mul, hipStream_t s) {
+  hipLaunchKernelGGL(sru_input_dropout_kernel, dim3(cdiv((long)B * T * n, 256)), dim3(256), 0, s, x, ldx, y, ldy, B, T, n, mul);
+  sru_path_count(SRU_PATH_INPUT_DROPOUT);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+int sru_launch_dx_adv_finish(const SruDxAdvArgs& f, hipStream_t s) {
+  hipLaunchKernelGGL(sru_dx_adv_finish_kernel, dim3(cdiv(cdiv(f.rows * f.Da, 4), 256)), dim3(256), 0, s, f);
+  sru_path_count(SRU_PATH_DX_ADV_FINISH);
+  LAUNCH_CHECK();
+  return GT_OK;
 }
 // Measured and dropped (round 4, gpurun_out/r4k): 32 columns per workgroup (twice the recurrence waves per CU, half of every wave
 // idle) for the shapes that give fewer than three 64-column workgroups per CU -- cfg4 (B = 16, T = 2048) 11.36 vs 10.84 ms, the
@@ -180,9 +255,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
     const bool rdrop = rdrop_all;      // (variational input dropout, mask shared over time: the multipliers [B][n_in] were drawn above)
     if (rdrop && !b16) {      // float32 products read a dropped float32 copy
       CHK(W.xdrop[l].ensure((size_t)N * L.in * sizeof(float)));
-      hipLaunchKernelGGL(sru_input_dropout_kernel, dim3(cdiv(N * L.in, 256)), dim3(256), 0, s, in, ld_in, W.xdrop[l].as<float>(),
-                         L.in, B, T, L.in, (const float*)W.xmask[l].as<float>());
-      LAUNCH_CHECK();
+      CHK(sru_launch_input_dropout(in, ld_in, W.xdrop[l].as<float>(), L.in, B, T, L.in, (const float*)W.xmask[l].as<float>(), s));
       xin = W.xdrop[l].as<float>();
       ld_xin = L.in;
     }
@@ -241,19 +314,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
         img_ready = true;
       }
     }
-    if (sru_coop()) {
-      const int grid = cdiv((long)B * ncols, 64);
-      const bool w8 = sru_coop_waves(B, ncols) == 8;
-      if (img_ready) {
-        if (w8) { CHK(ensure_dyn_lds((const void*)sru_fwd_cs_kernel<8, true>, sru_fwd_cs_lds<8>(true)));
-                  hipLaunchKernelGGL((sru_fwd_cs_kernel<8, true>), dim3(grid), dim3(512), sru_fwd_cs_lds<8>(true), s, a); }
-        else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, true>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(true), s, a);
-      } else if (w8) hipLaunchKernelGGL((sru_fwd_cs_kernel<8, false>), dim3(grid), dim3(512), sru_fwd_cs_lds<8>(), s, a);
-      else hipLaunchKernelGGL((sru_fwd_cs_kernel<4, false>), dim3(grid), dim3(256), sru_fwd_cs_lds<4>(), s, a);
-    } else {
-      hipLaunchKernelGGL(sru_fwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
-    }
-    LAUNCH_CHECK();
+    CHK(sru_launch_fwd(a, s));      // (the image form: a.nx_b is set)
     in = W.h[l].as<float>();
     ld_in = ncols;
   }
@@ -374,21 +435,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
       CHK(DU.ensure(N, ncols * L.k, want_w));
       a.dU = nullptr; a.dU_b = DU.r(); a.ld_dub = DU.ld; a.dU_bt = want_w ? DU.t() : (__bf16*)nullptr; a.ld_dubt = DU.ldt;
     }
-    if (sru_coop()) {
-      const int grid = cdiv((long)B * ncols, 64);
-      const bool w8 = sru_coop_waves(B, ncols) == 8;
-#define GT_SRU_CS_LAUNCH(NW_, B16_)                                                                                           \
-      do {                                                                                                                     \
-        CHK(ensure_dyn_lds((const void*)sru_bwd_cs_kernel<NW_, B16_>, sru_bwd_cs_lds<NW_>(B16_)));                             \
-        hipLaunchKernelGGL((sru_bwd_cs_kernel<NW_, B16_>), dim3(grid), dim3(64 * NW_), sru_bwd_cs_lds<NW_>(B16_), s, a);        \
-      } while (0)
-      if (du_b16) { if (w8) GT_SRU_CS_LAUNCH(8, true); else GT_SRU_CS_LAUNCH(4, true); }
-      else { if (w8) GT_SRU_CS_LAUNCH(8, false); else GT_SRU_CS_LAUNCH(4, false); }
-#undef GT_SRU_CS_LAUNCH
-    } else {
-      hipLaunchKernelGGL(sru_bwd_kernel, dim3(cdiv((long)B * ncols, SRU_THREADS)), dim3(SRU_THREADS), 0, s, a);
-    }
-    LAUNCH_CHECK();
+    CHK(sru_launch_bwd(a, s));      // (the image form: a.dU_b is set)
     if (b16 && !du_b16) {      // dU -> bf16 image in both orientations (one pass)
       B16Img& DU = W.du_b;
       CHK(DU.ensure(N, ncols * L.k, want_w));
@@ -462,8 +509,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
         f.dx_adv = dx_adv; f.rows = Nf; f.Da = Da; f.T = T;
         f.mul = rdrop ? W.xmask[0].as<float>() + (size_t)(nseq - Bf) * L.in + col0 : nullptr; f.ld_mul = L.in;
         f.hw = L.k == 3 ? dx_res + (size_t)row0 * ncols + col0 : nullptr; f.ld_hw = ncols;
-        hipLaunchKernelGGL(sru_dx_adv_finish_kernel, dim3(cdiv(cdiv(Nf * Da, 4), 256)), dim3(256), 0, s, f);
-        LAUNCH_CHECK();
+        CHK(sru_launch_dx_adv_finish(f, s));
       }
     }
   }

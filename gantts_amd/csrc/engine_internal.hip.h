@@ -34,6 +34,7 @@
 #include "frame_kernels.hip.h"
 #include "gemm_f32.hip.h"
 #include "gemm_bf16s.hip.h"
+#include "sru_args.hip.h"
 
 using namespace gt;
 
@@ -85,7 +86,7 @@ struct GtTuning {
                               //                   at-size case (a cold-Adagrad update, lr * g / |g|) then lands 1.2x outside its 1e-4
   int mlpg_tt = 0;            // GT_MLPG_TT        output frames per MLPG workgroup (0 = by shape, 16, 32)
   int leak_rider = 1;         // GT_LEAK_RIDER     D step: the kept dloss_d / dy_hat_static product rides in the split first layer's weight-gradient launch
-  int sru_cs_waves = 0;       // GT_SRU_CS_WAVES   waves per 64 columns of the cooperative SRU scans: 0 = by shape (8 where B x ncols / 64 <= CUs, else 4), 4, 8
+  int sru_cs_waves = 0;       // GT_SRU_CS_WAVES   waves per 64 columns of the cooperative SRU scans: 0 = by shape (8 up to two 64-column workgroups per CU, i.e. B x ncols / 64 <= 2 CUs, else 4), 4, 8
   int sru_coop = 1;           // GT_SRU_COOP       1: cooperative block scans (sru_cs_kernels.hip.h); 0: one-wave kernels (sru_kernels.hip.h: the sequential reference)
   int lstm_bt = 0;            // GT_LSTM_BT        sequences per batch tile of the persistent LSTM kernels: 0 = by shape, 8, 16 (still subject to co-residency)
 };
@@ -484,6 +485,20 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
 int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
                       const float** top, int* ld_top, const gt::CatSrc* cat0 = nullptr, bool want_w = true);
 bool sru_b16(const gt_engine* e, int role);
+// gt_sru_path_counts: launches of the SRU scans and their helper kernels by kernel, counted on the host where they are issued (slot
+// layout in gantts_hip.h).  sru_launch_*: the one launch site of each kernel, shared by the stacks and the parity hooks (eng_ops.hip);
+// sru_scan_waves: the form sru_launch_fwd / _bwd pick for a shape under the current knobs (0 sequential, 4 / 8 waves per 64 columns).
+enum { SRU_PATH_FWD = 0, SRU_PATH_FWD_CS = 1, SRU_PATH_BWD = 5, SRU_PATH_BWD_CS = 6, SRU_PATH_INPUT_MASK = 10, SRU_PATH_INPUT_DROPOUT = 11,
+       SRU_PATH_DX_ADV_FINISH = 12 };
+static_assert(SRU_PATH_DX_ADV_FINISH + 1 == GT_SRU_PATH_SLOTS, "gt_sru_path_counts slots");
+int sru_scan_waves(long B, int ncols);
+uint32_t sru_drop_thresh(float p);
+int sru_launch_fwd(const gt::SruArgs& a, hipStream_t s);
+int sru_launch_bwd(const gt::SruArgs& a, hipStream_t s);
+int sru_launch_input_mask(float* mul, int B, int n, float keep_scale, uint32_t thresh, uint32_t key0, uint32_t key1, const float* inj,
+                          int seq_mul, int seq_add, hipStream_t s);
+int sru_launch_input_dropout(const float* x, int ldx, float* y, int ldy, int B, int T, int n, const float* mul, hipStream_t s);
+int sru_launch_dx_adv_finish(const gt::SruDxAdvArgs& f, hipStream_t s);
 bool sru_d_needs_f32_input(const gt_engine* e);
 int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, bool want_w,
                        float* dx_adv, hipStream_t s);

@@ -618,6 +618,73 @@ typedef struct gt_cast_case {
 } gt_cast_case;
 int gt_op_cast_image(const gt_cast_case* c, void* stream);
 
+/* Launches of the SRU recurrence (sru_kernels.hip.h, sru_cs_kernels.hip.h) by kernel, process-wide, counted on the host where each
+ * launch is issued (no device work, no synchronisation).  Slots:
+ *   0        sru_fwd_kernel (the sequential scan)
+ *   1..4     sru_fwd_cs_kernel<NW, NXOUT>: 1 + 2 * (NW == 8) + NXOUT     (NXOUT: the scan writes the next product's bf16 images)
+ *   5        sru_bwd_kernel
+ *   6..9     sru_bwd_cs_kernel<NW, B16OUT>: 6 + 2 * (NW == 8) + B16OUT   (B16OUT: dU leaves as bf16 images)
+ *   10..12   sru_input_mask_kernel, sru_input_dropout_kernel, sru_dx_adv_finish_kernel
+ * Copies the GT_SRU_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
+#define GT_SRU_PATH_SLOTS 13
+int gt_sru_path_counts(int64_t* counts, int reset);
+
+/* Parity hook of the SRU scans: ONE scan launch through the launch functions the engine's stacks use.  The form -- sequential, four or
+ * eight waves per 64 columns -- follows from the tuning knobs sru_coop / sru_cs_waves and the shape exactly as in a step; the image
+ * forms follow from nx_b / dU_b being set.  All pointers are the caller's device buffers; ncols = H * dirs, N = B * T, row = b * T + t,
+ * columns >= H of a two-direction layer walk time backwards.
+ *   forward  (backward == 0): reads U [N][ldu] (column j owns U[.., j*k .. j*k+k-1]), x [N][ldx] (k == 3: the highway input), bias
+ *            [2 * ncols] = b_f | b_r; writes h and c, dense [N][ncols]; with nx_b also the bf16 images of h * nx_mul[b][col]
+ *            (nx_mul [B][ncols] or null = 1): nx_b [N][ld_nxb] and, unless null, nx_bt [ncols][ld_nxbt]
+ *   backward (backward != 0): reads U, x, bias, the stash c [N][ncols], dh [N][ncols] -- taken as dh * up_mul[b][col] + up_add[row][col]
+ *            (up_mul [B][ncols] / up_add [N][ld_up_add], either null) --; writes dU [N][ldu] (the pitch of U), k == 3: dx [N][lddx],
+ *            dbias_part [B][2 * ncols]; with dU_b the bf16 images dU_b [N][ld_dub] and, unless null, dU_bt [ncols * k][ld_dubt]
+ *            INSTEAD of dU (dx is still written)
+ * act: 0 identity, 1 tanh, 2 relu.  mask_mode: 0 none; 1 `mask` [B][ncols] of 0 / 1 scaled by keep_scale; 2 the Philox stream of
+ * (key0, key1): column col of sequence seq_add + seq_mul * b is kept iff the first word of philox4x32_10(sequence, col, key0, key1)
+ * >= p * 2^32, and scaled by 1 / (1 - p).
+ * Images are raw 16-bit elements, pitches in elements; they need a cooperative form, T % 8 == 0, H % 64 == 0, 16-byte aligned
+ * pointers and pitches that are multiples of 8.  Synchronises the stream.  A malformed case returns GT_ERR_INVALID before any launch. */
+typedef struct gt_sru_scan_case {
+  int32_t backward;
+  int32_t B, T, H, dirs, k, act;
+  int32_t mask_mode;
+  float keep_scale, p;
+  uint32_t key0, key1;
+  int32_t seq_mul, seq_add;
+  int32_t ldu, ldx, lddx, ld_up_add, ld_nxb, ld_dub;
+  int64_t ld_nxbt, ld_dubt;
+  const float* U;
+  const float* x;
+  const float* bias;
+  float* h;
+  float* c;
+  const float* dh;
+  float* dU;
+  float* dx;
+  float* dbias_part;
+  const float* mask;
+  const float* up_mul;
+  const float* up_add;
+  const float* nx_mul;
+  uint16_t* nx_b;
+  uint16_t* nx_bt;
+  uint16_t* dU_b;
+  uint16_t* dU_bt;
+} gt_sru_scan_case;
+int gt_op_sru_scan(const gt_sru_scan_case* c, void* stream);
+/* Parity hooks of the helper kernels of the SRU stack, each one launch through the engine's launch function; they synchronise the stream.
+ *   dx_adv_finish  dx_adv [rows][Da] dense, in place: dx_adv * mul[row / T][j] + hw[row][j]; mul [rows / T][ld_mul] or null (1),
+ *                  hw [rows][ld_hw] or null (0)
+ *   input_mask     mul [B][n] = inj[b][j] != 0 (inj [B][n] of 0 / 1), or without inj the Philox stream of the scans' mask_mode 2, times
+ *                  1 / (1 - p), else 0
+ *   input_dropout  y [B * T][ldy] = x [B * T][ldx] * mul[row / T][j], n columns */
+int gt_op_sru_dx_adv_finish(float* dx_adv, int64_t rows, int Da, int T, const float* mul, int ld_mul, const float* hw, int ld_hw,
+                            void* stream);
+int gt_op_sru_input_mask(float* mul, int B, int n, float p, uint32_t key0, uint32_t key1, const float* inj, int seq_mul, int seq_add,
+                         void* stream);
+int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ldy, int B, int T, int n, const float* mul, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

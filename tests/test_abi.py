@@ -45,6 +45,8 @@ def test_ctypes_structs_match_header_layout():
     assert C.sizeof(_lib.CastJob) == 56 and _lib.CastJob.rows.offset == 24 and _lib.CastJob.ldi.offset == 40
     assert _lib.CastCase.rows.offset == 40 and _lib.CastCase.in_.offset == 72 and _lib.CastCase.idx.offset == 136
     assert _lib.CastCase.jobs.offset == 144 and C.sizeof(_lib.CastCase) == 144 + 8 * 56
+    assert _lib.SruScanCase.keep_scale.offset == 32 and _lib.SruScanCase.ldu.offset == 56 and _lib.SruScanCase.ld_nxbt.offset == 80
+    assert _lib.SruScanCase.U.offset == 96 and _lib.SruScanCase.dU_bt.offset == 224 and C.sizeof(_lib.SruScanCase) == 232
 
 
 def test_invalid_arguments_are_reported_not_crashing():

@@ -1131,7 +1131,8 @@ def test_bf16_storage_sru_step_tracks_the_float32_oracle():
 
 @pytest.mark.parametrize("waves", [8, 4])
 @pytest.mark.parametrize("name,bf16", [("acoustic_sru_at_size", 0), ("acoustic_sru_uni_k3_dropout", 0), ("vc_sru_multistream", 0), ("acoustic_sru_uni_k3", 0),
-                                       ("acoustic_sru_bi_saturated", 0), ("acoustic_sru_at_size", 1), ("acoustic_sru_dropout", 1)])
+                                       ("acoustic_sru_bi_saturated", 0), ("acoustic_sru_at_size", 1), ("acoustic_sru_dropout", 1),
+                                       ("acoustic_sru_dropout@T133", 0), ("acoustic_sru_dropout@T133", 1)])
 def test_sru_cooperative_block_scans_match_the_sequential_scans(name, bf16, waves):
     """The cooperative block scans (sru_cs_kernels.hip.h, the default: every wave of a workgroup walks eight frames of a block from a
     zero state, the waves' composites (prod f, end state) are combined through LDS, each wave corrects its frames by prefix
@@ -1139,9 +1140,14 @@ def test_sru_cooperative_block_scans_match_the_sequential_scans(name, bf16, wave
     products, so a whole G+D step agrees to rounding -- 1e-4 like every float32 comparison of the suite (bf16 storage: the products
     around the scans round their operands to bf16, where a last-bit difference of a scan output can flip a rounding: 2e-2) --
     forward and backward, both directions, k = 3 and 4, tanh / relu, saturated gates, ragged T (partial blocks: frames past T are
-    the identity), partial workgroups, dU as float32 and as bf16 images."""
+    the identity), partial workgroups, dU as float32 and as bf16 images.  "@T133": the case at T = 133, three ragged blocks for both
+    wave counts (2 x 32 + 5 + 64, 2 x 64 + 5) -- the carried state crosses two block boundaries, the trailing block has no pair; built here,
+    not in ORACLE_ONLY_CASES (the oracle's python time loop is not needed for a comparison of two kernels)."""
     from hip_runner import run_hip_case
+    name, _, t_over = name.partition("@T")
     case = C.ORACLE_ONLY_CASES[name]
+    if t_over:
+        case = dict(case, T=int(t_over))
     from gantts_amd import _lib as L
     opts = {"matmul_bf16": 1} if bf16 else None
     try:
