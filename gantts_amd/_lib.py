@@ -35,7 +35,9 @@ GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE
 ARCH_MLP, ARCH_IN2OUT, ARCH_LSTM, ARCH_SRU, ARCH_IN2OUT_RNN = 0, 1, 2, 3, 4
 OPT_ADAGRAD, OPT_ADAM = 0, 1
 OPT_SGD, OPT_RMSPROP, OPT_ADADELTA, OPT_ADAMW, OPT_ADAMAX = 2, 3, 4, 5, 6
+OPT_NADAM, OPT_RADAM, OPT_RPROP, OPT_ASGD = 7, 8, 9, 10
 OPTF_NESTEROV, OPTF_CENTERED, OPTF_AMSGRAD, OPTF_BUFFER_LIVE = 1, 2, 4, 8      # OptimDescEx.flags
+OPTF_DECOUPLED_WD = 32                                                         # NAdam, RAdam
 MAX_STREAMS = 8
 COMM_ID_BYTES = 128
 
@@ -72,6 +74,13 @@ class OptimDescEx(C.Structure):
                 + [(n, C.c_double) for n in ("lr", "weight_decay", "eps", "lr_decay", "beta1", "beta2", "momentum", "dampening", "alpha")]
                 + [("max_grad_norm", C.c_float), ("reserved_", C.c_int32), ("step", C.c_int64),
                    ("state0", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p)])
+
+
+class OptimDescEx2(OptimDescEx):
+    """The whole gt_optim_desc_ex.  OptimDescEx is its head up to state2: all the library reads for OPT_ADAGRAD .. OPT_ADAMAX, and
+    what a caller of the first family passes; OPT_NADAM .. OPT_ASGD need the tail."""
+    _fields_ = [(n, C.c_double) for n in ("momentum_decay", "etaminus", "etaplus", "step_size_min", "step_size_max", "lambd", "t0",
+                                          "host_state0", "host_state1")]
 
 
 class DResult(C.Structure):
@@ -140,6 +149,8 @@ SIGNATURES = {
     "gt_set_training": (_I, [_P, _I, _I]),
     "gt_set_lr": (_I, [_P, _I, _F]),
     "gt_get_optimizer_step": (_I, [_P, _I, C.POINTER(_L)]),
+    "gt_get_optimizer_scalars": (_I, [_P, _I, C.POINTER(C.c_double)]),
+    "gt_op_optim_scalars": (_I, [C.POINTER(OptimDescEx), _L, C.POINTER(C.c_double)]),
     "gt_set_seed": (_I, [_P, C.c_uint64]),
     "gt_set_dropout_mask": (_I, [_P, _I, _I, _I, _P]),
     "gt_op_philox_mask": (_I, [_P, _I, _I, _I, _L, _F, _L, _I, _P, _P]),

@@ -333,6 +333,7 @@ extern "C" int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* od
   n.od = x;
   n.step = n.bound_step = od->step;
   n.buf_live = false;
+  n.hs_cache = OptimScalarCache();
   n.has_opt = true;
   return GT_OK;
 }
@@ -342,9 +343,10 @@ extern "C" int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_
   if (!n.bound) return fail(GT_ERR_STATE, "bind the model before its optimizer");
   if (!n.d.grads) return fail(GT_ERR_INVALID, "model was bound without a grads buffer");
   CHK(optim_check_desc(od));
-  n.od = *od;
-  n.od.lr = (double)(float)od->lr;      // what gt_set_lr would store
+  optim_desc_copy(od, &n.od);
+  if (od->kind != GT_OPT_ASGD) n.od.lr = (double)(float)od->lr;      // what gt_set_lr would store (ASGD: include/gantts_hip.h, host scalar state)
   n.step = n.bound_step = od->step;
+  n.hs_cache = OptimScalarCache();
   n.buf_live = (od->flags & GT_OPTF_BUFFER_LIVE) != 0;
   n.has_opt = true;
   return GT_OK;
@@ -362,6 +364,13 @@ extern "C" int gt_set_lr(gt_engine* e, int role, float lr) {
 extern "C" int gt_get_optimizer_step(gt_engine* e, int role, int64_t* step) {
   if (!e || role < 0 || role > 1 || !step) return fail(GT_ERR_INVALID, "bad argument");
   *step = e->net[role].step;
+  return GT_OK;
+}
+extern "C" int gt_get_optimizer_scalars(gt_engine* e, int role, double out[2]) {
+  if (!e || role < 0 || role > 1 || !out) return fail(GT_ERR_INVALID, "bad argument");
+  Net& n = e->net[role];
+  if (!n.has_opt) return fail(GT_ERR_INVALID, "no optimizer bound");
+  optim_host_scalars(n.od, n.step, &n.hs_cache, out);
   return GT_OK;
 }
 extern "C" int gt_set_seed(gt_engine* e, uint64_t seed) {

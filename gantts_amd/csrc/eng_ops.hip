@@ -563,18 +563,20 @@ extern "C" int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ld
 // ------------------------------------------------------------------------------------------
 // the optimizer family: validation, the step's scalars, the launch (engine and stand-alone operator alike)
 // ------------------------------------------------------------------------------------------
-int optim_check_desc(const gt_optim_desc_ex* od) {
+// what the descriptor's head (up to state2) decides, the state buffers aside
+static int optim_check_head(const gt_optim_desc_ex* od) {
   const int k = od->kind;
-  if (k < GT_OPT_ADAGRAD || k > GT_OPT_ADAMAX) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", k);
+  if (k < GT_OPT_ADAGRAD || k > GT_OPT_ASGD) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", k);
   const unsigned allowed = GT_OPTF_BUFFER_LIVE | (k == GT_OPT_SGD ? GT_OPTF_NESTEROV : 0u) | (k == GT_OPT_RMSPROP ? GT_OPTF_CENTERED : 0u) |
-                           ((k == GT_OPT_ADAM || k == GT_OPT_ADAMW) ? GT_OPTF_AMSGRAD : 0u);
+                           ((k == GT_OPT_ADAM || k == GT_OPT_ADAMW) ? GT_OPTF_AMSGRAD : 0u) |
+                           ((k == GT_OPT_NADAM || k == GT_OPT_RADAM) ? GT_OPTF_DECOUPLED_WD : 0u);
   if (od->flags & ~allowed) return fail(GT_ERR_INVALID, "optimizer flags 0x%x do not belong to kind %d", od->flags, k);
   // the checks of torch.optim's constructors (written so that a NaN fails them)
   if (!(od->lr >= 0.0)) return fail(GT_ERR_INVALID, "Invalid learning rate: %g", od->lr);
   if (!(od->weight_decay >= 0.0)) return fail(GT_ERR_INVALID, "Invalid weight_decay value: %g", od->weight_decay);
-  if (k != GT_OPT_SGD && !(od->eps >= 0.0)) return fail(GT_ERR_INVALID, "Invalid epsilon value: %g", od->eps);
+  if (k != GT_OPT_SGD && k != GT_OPT_RPROP && k != GT_OPT_ASGD && !(od->eps >= 0.0)) return fail(GT_ERR_INVALID, "Invalid epsilon value: %g", od->eps);
   if (k == GT_OPT_ADAGRAD && !(od->lr_decay >= 0.0)) return fail(GT_ERR_INVALID, "Invalid lr_decay value: %g", od->lr_decay);
-  if (k == GT_OPT_ADAM || k == GT_OPT_ADAMW || k == GT_OPT_ADAMAX) {
+  if (k == GT_OPT_ADAM || k == GT_OPT_ADAMW || k == GT_OPT_ADAMAX || k == GT_OPT_NADAM || k == GT_OPT_RADAM) {
     if (!(od->beta1 >= 0.0 && od->beta1 < 1.0)) return fail(GT_ERR_INVALID, "Invalid beta parameter at index 0: %g", od->beta1);
     if (!(od->beta2 >= 0.0 && od->beta2 < 1.0)) return fail(GT_ERR_INVALID, "Invalid beta parameter at index 1: %g", od->beta2);
   }
@@ -584,19 +586,74 @@ int optim_check_desc(const gt_optim_desc_ex* od) {
   if (k == GT_OPT_RMSPROP && !(od->alpha >= 0.0)) return fail(GT_ERR_INVALID, "Invalid alpha value: %g", od->alpha);
   if (k == GT_OPT_ADADELTA && !(od->alpha >= 0.0 && od->alpha <= 1.0)) return fail(GT_ERR_INVALID, "Invalid rho value: %g", od->alpha);
   if (od->step < 0) return fail(GT_ERR_INVALID, "negative step count");
+  return GT_OK;
+}
+// the descriptor's tail, which exists for GT_OPT_NADAM .. GT_OPT_ASGD only
+static int optim_check_tail(const gt_optim_desc_ex* od) {
+  const int k = od->kind;
+  if (k == GT_OPT_NADAM) {
+    if (!(od->momentum_decay >= 0.0)) return fail(GT_ERR_INVALID, "Invalid momentum_decay value: %g", od->momentum_decay);
+    // (0 is a legitimate value: the float32 product of factors near 0.45 underflows to it after some 135 updates, and torch goes on with 1 - 0)
+    if (!(od->host_state0 >= 0.0 && od->host_state0 <= 1.0) || (od->step == 0 && od->host_state0 != 1.0))
+      return fail(GT_ERR_INVALID, "NAdam: host_state0 (mu_product) is %g: 1 before the first update, in [0, 1] after", od->host_state0);
+  }
+  if (k == GT_OPT_RPROP) {
+    if (!(0.0 < od->etaminus && od->etaminus < 1.0 && 1.0 < od->etaplus))
+      return fail(GT_ERR_INVALID, "Invalid eta values: %g, %g", od->etaminus, od->etaplus);
+    if (od->weight_decay != 0.0) return fail(GT_ERR_INVALID, "Rprop has no weight_decay");
+  }
+  if (k == GT_OPT_ASGD && !(od->host_state1 > 0.0 && od->host_state1 <= 1.0 && od->host_state0 >= 0.0))
+    return fail(GT_ERR_INVALID, "ASGD: host_state0 (eta) is %g and host_state1 (mu) is %g: (float)lr and 1 before the first update", od->host_state0,
+                od->host_state1);
+  return GT_OK;
+}
+int optim_check_desc(const gt_optim_desc_ex* od) {
+  CHK(optim_check_head(od));
+  const int k = od->kind;
   const bool mom = (k == GT_OPT_SGD || k == GT_OPT_RMSPROP) && od->momentum != 0.0;
   const bool need0 = k != GT_OPT_SGD || mom;
-  const bool need1 = k == GT_OPT_RMSPROP ? mom : k != GT_OPT_ADAGRAD && k != GT_OPT_SGD;
+  const bool need1 = k == GT_OPT_RMSPROP ? mom : k != GT_OPT_ADAGRAD && k != GT_OPT_SGD && k != GT_OPT_ASGD;
   const bool need2 = (od->flags & (GT_OPTF_CENTERED | GT_OPTF_AMSGRAD)) != 0;
   if ((need0 && !od->state0) || (need1 && !od->state1) || (need2 && !od->state2))
     return fail(GT_ERR_INVALID, "optimizer state buffer is null (kind %d, flags 0x%x needs state%s%s%s)", k, od->flags, need0 ? " 0" : "",
                 need1 ? " 1" : "", need2 ? " 2" : "");
-  return GT_OK;
+  return optim_check_tail(od);      // after everything that the head alone decides: a null buffer is reported without reading the tail
+}
+
+// The descriptor as the library keeps it: the first family's kinds are copied up to state2 (a caller built against that
+// 120-byte struct passes no more) with a zero tail, the kinds that have a tail whole.
+void optim_desc_copy(const gt_optim_desc_ex* in, gt_optim_desc_ex* out) {
+  memset(out, 0, sizeof(*out));
+  memcpy(out, in, (in->kind >= GT_OPT_NADAM && in->kind <= GT_OPT_ASGD) ? sizeof(*out) : offsetof(gt_optim_desc_ex, momentum_decay));
+}
+
+// NAdam's momentum cache mu_t (python floats in torch: double)
+static double nadam_mu(const gt_optim_desc_ex& od, long t) { return od.beta1 * (1.0 - 0.5 * pow(0.96, (double)t * od.momentum_decay)); }
+
+// The host scalar state after `t` updates (t >= od.step): torch's 0-dim float32 state tensors mu_product (NAdam) and eta, mu (ASGD).
+// A pure function of the descriptor (its step and host_state* are those of the bind) and t, so that a step counter that
+// gt_clear_faults moved back needs no undo here; `cache` only shortens NAdam's running product and may be null.
+void optim_host_scalars(const gt_optim_desc_ex& od, long t, OptimScalarCache* cache, double out[2]) {
+  out[0] = out[1] = 0.0;
+  if (od.kind == GT_OPT_NADAM) {
+    long s = (long)od.step;
+    float mp = (float)od.host_state0;
+    if (cache && cache->valid && cache->step >= s && cache->step <= t) { s = cache->step; mp = cache->mu_product; }
+    for (; s < t; ++s) mp = mp * (float)nadam_mu(od, s + 1);      // mu_product *= mu: a float32 tensor times a python float, in float32
+    if (cache) { cache->valid = true; cache->step = t; cache->mu_product = mp; }
+    out[0] = (double)mp;
+  } else if (od.kind == GT_OPT_ASGD) {
+    if (t == (long)od.step) { out[0] = od.host_state0; out[1] = od.host_state1; return; }
+    // eta.copy_(lr / (1 + lambd lr step) ** alpha), mu.copy_(1 / max(1, step - t0)): python floats stored into float32 tensors
+    out[0] = (double)(float)(od.lr / pow(1.0 + od.lambd * od.lr * (double)t, od.alpha));
+    out[1] = (double)(float)(1.0 / std::max(1.0, (double)t - od.t0));
+  }
 }
 
 // The scalars of update number `step` (1-based), formed in double from the double hyper-parameters and rounded to float
-// once -- python arithmetic followed by a Scalar -> float conversion in torch's single-tensor code paths.
-static OptimSpecEx optim_spec_ex(const gt_optim_desc_ex& od, long step, bool buf_live) {
+// once -- python arithmetic followed by a Scalar -> float conversion in torch's single-tensor code paths.  `flags` receives
+// what the host decides for this update beyond the descriptor's flags (OPTI_RECTIFIED, OPTI_AVERAGE).
+static OptimSpecEx optim_spec_ex(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, unsigned* flags) {
   OptimSpecEx o;
   memset(&o, 0, sizeof(o));
   const double lr = od.lr;
@@ -623,12 +680,51 @@ static OptimSpecEx optim_spec_ex(const gt_optim_desc_ex& od, long step, bool buf
       o.w1 = (float)(1.0 - od.beta1); o.a = (float)od.beta2;
       o.neg_step = (float)-(lr / (1.0 - pow(od.beta1, (double)step)));
       break;
+    case GT_OPT_NADAM: {
+      double hs[2];
+      optim_host_scalars(od, step, cache, hs);                  // mu_product after this update's `mu_product *= mu`
+      const double mu = nadam_mu(od, step), mu_next = nadam_mu(od, step + 1), mu_product = hs[0];
+      o.w1 = (float)(1.0 - od.beta1); o.a = (float)od.beta2; o.oma = (float)(1.0 - od.beta2);
+      o.bc2 = (float)(1.0 - pow(od.beta2, (double)step));
+      o.c_g = (float)(-lr * (1.0 - mu) / (1.0 - mu_product));
+      o.c_m = (float)((-lr * mu_next) / (1.0 - mu_product * mu_next));
+      o.decay = (float)(1.0 - lr * od.weight_decay);
+      break;
+    }
+    case GT_OPT_RADAM: {
+      const double t = (double)step, b2t = pow(od.beta2, t);
+      const double bc1 = 1.0 - pow(od.beta1, t), bc2 = 1.0 - b2t;
+      const double rho_inf = 2.0 / (1.0 - od.beta2) - 1.0;
+      const double rho_t = rho_inf - 2.0 * t * b2t / bc2;
+      o.w1 = (float)(1.0 - od.beta1); o.a = (float)od.beta2; o.oma = (float)(1.0 - od.beta2);
+      o.bc1 = (float)bc1; o.lr = (float)lr; o.bc2_sqrt = (float)sqrt(bc2);
+      o.decay = (float)(1.0 - lr * od.weight_decay);
+      if (rho_t > 5.0) {
+        *flags |= OPTI_RECTIFIED;
+        o.rect = (float)sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t));
+      }
+      break;
+    }
+    case GT_OPT_RPROP:
+      o.wd = 0.f;
+      o.eta_minus = (float)od.etaminus; o.eta_plus = (float)od.etaplus;
+      o.step_min = (float)od.step_size_min; o.step_max = (float)od.step_size_max;
+      break;
+    case GT_OPT_ASGD: {
+      double hs[2];
+      optim_host_scalars(od, step - 1, cache, hs);              // eta and mu as the previous update left them
+      o.decay = (float)(1.0 - od.lambd * hs[0]);
+      o.neg_step = (float)-hs[0];
+      o.mu = (float)hs[1];
+      if (hs[1] != 1.0) *flags |= OPTI_AVERAGE;
+      break;
+    }
   }
   return o;
 }
 
-int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, float* params, float* grads, long n, const double* part,
-                      int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
+int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
+                      const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
                       unsigned int* skipped_host, const float* gscale, hipStream_t s) {
   const dim3 grid((unsigned)std::min<long>(1024, cdiv(n, RED_THREADS))), block(RED_THREADS);
   const bool ams = (od.flags & GT_OPTF_AMSGRAD) != 0;
@@ -641,11 +737,13 @@ int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, floa
     LAUNCH_CHECK();
     return GT_OK;
   }
-  const OptimSpecEx o = optim_spec_ex(od, step, buf_live);
+  unsigned hostf = 0u;
+  const OptimSpecEx o = optim_spec_ex(od, step, buf_live, cache, &hostf);
 #define GT_OPTIM_LAUNCH(KIND, F)                                                                                                      \
   hipLaunchKernelGGL((optim_step_ex_kernel<KIND, F>), grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, \
                      n_partial, norm2_out, o, fault_dev, fault_host, skipped_host, gscale)
   const bool mom = od.momentum != 0.0, nest = (od.flags & GT_OPTF_NESTEROV) != 0, cen = (od.flags & GT_OPTF_CENTERED) != 0;
+  const bool dec = (od.flags & GT_OPTF_DECOUPLED_WD) != 0, rect = (hostf & OPTI_RECTIFIED) != 0;
   switch (od.kind) {
     case GT_OPT_SGD:
       if (!mom) GT_OPTIM_LAUNCH(OPTK_SGD, 0u);
@@ -665,10 +763,38 @@ int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, floa
       else GT_OPTIM_LAUNCH(OPTK_ADAMW, 0u);
       break;
     case GT_OPT_ADAMAX: GT_OPTIM_LAUNCH(OPTK_ADAMAX, 0u); break;
+    case GT_OPT_NADAM:
+      if (dec) GT_OPTIM_LAUNCH(OPTK_NADAM, OPTI_DECOUPLED);
+      else GT_OPTIM_LAUNCH(OPTK_NADAM, 0u);
+      break;
+    case GT_OPT_RADAM:
+      if (dec && rect) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_DECOUPLED | OPTI_RECTIFIED);
+      else if (dec) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_DECOUPLED);
+      else if (rect) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_RECTIFIED);
+      else GT_OPTIM_LAUNCH(OPTK_RADAM, 0u);
+      break;
+    case GT_OPT_RPROP: GT_OPTIM_LAUNCH(OPTK_RPROP, 0u); break;
+    case GT_OPT_ASGD:
+      if (hostf & OPTI_AVERAGE) GT_OPTIM_LAUNCH(OPTK_ASGD, OPTI_AVERAGE);
+      else GT_OPTIM_LAUNCH(OPTK_ASGD, 0u);
+      break;
     default: return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
   }
 #undef GT_OPTIM_LAUNCH
   LAUNCH_CHECK();
+  return GT_OK;
+}
+
+extern "C" int gt_op_optim_scalars(const gt_optim_desc_ex* desc, int64_t t, double out[2]) {
+  if (!desc || !out) return fail(GT_ERR_INVALID, "bad argument");
+  CHK(optim_check_head(desc));      // everything gt_bind_optimizer_ex checks but the state buffers
+  CHK(optim_check_tail(desc));
+  if (desc->step < 0 || t < desc->step) return fail(GT_ERR_INVALID, "the scalars are defined from the descriptor's step (%lld) on, not at %lld",
+                                                     (long long)desc->step, (long long)t);
+  gt_optim_desc_ex od;
+  optim_desc_copy(desc, &od);
+  if (od.kind != GT_OPT_ASGD) od.lr = (double)(float)desc->lr;
+  optim_host_scalars(od, (long)t, (OptimScalarCache*)nullptr, out);
   return GT_OK;
 }
 
@@ -680,13 +806,14 @@ extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, flo
   static thread_local Scratch tls_ws;     // [0, 512) squared-norm partials, [512] the squared norm
   CHK(tls_ws.ensure(513 * sizeof(double)));
   double* part = (double*)tls_ws.p;
-  gt_optim_desc_ex od = *desc;
-  od.lr = (double)(float)desc->lr;        // as gt_bind_optimizer_ex keeps it
+  gt_optim_desc_ex od;
+  optim_desc_copy(desc, &od);
+  if (od.kind != GT_OPT_ASGD) od.lr = (double)(float)desc->lr;        // as gt_bind_optimizer_ex keeps it
   // the engine's fallback branch (optimizer_step, eng_step.hip): partials, then clip + update
   const int nblk = (int)std::min<long>(512, cdiv(n, RED_THREADS * 4));
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, (const float*)grads, (long)n, part);
   LAUNCH_CHECK();
-  CHK(launch_optim_step(od, (long)desc->step + 1, (desc->flags & GT_OPTF_BUFFER_LIVE) != 0, params, grads, (long)n, part, nblk,
+  CHK(launch_optim_step(od, (long)desc->step + 1, (desc->flags & GT_OPTF_BUFFER_LIVE) != 0, (OptimScalarCache*)nullptr, params, grads, (long)n, part, nblk,
                         grad_norm_out ? part + 512 : (double*)nullptr, (const unsigned int*)nullptr, (unsigned int*)nullptr,
                         (unsigned int*)nullptr, gscale, s));
   if (grad_norm_out) {

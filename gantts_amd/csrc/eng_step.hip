@@ -679,7 +679,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
       const int n_partial = sd.blocks + rest_blocks;
       sd.reset(false);
       n.step += 1;
-      CHK(launch_optim_step(n.od, n.step, n.buf_live, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
+      CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
                             (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
       n.buf_live = true;
       return GT_OK;
@@ -691,7 +691,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, n.d.grads, np, part);
   LAUNCH_CHECK();
   n.step += 1;
-  CHK(launch_optim_step(n.od, n.step, n.buf_live, n.d.params, n.d.grads, np, part, nblk, norm2_out,
+  CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, nblk, norm2_out,
                         (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
   n.buf_live = true;
   return GT_OK;

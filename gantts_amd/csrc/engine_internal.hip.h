@@ -161,6 +161,9 @@ struct LstmDirP { float *Wih, *Whh, *bih, *bhh, *dWih, *dWhh, *dbih, *dbhh; };
 struct LstmLayerP { int in; LstmDirP d[2]; };
 struct SruLayerP { int in, k; float *W, *b, *dW, *db; };
 
+// NAdam's mu_product after `step` updates, kept so that the running float32 product is not redone from the bind every step
+struct OptimScalarCache { bool valid = false; long step = 0; float mu_product = 1.f; };
+
 struct Net {
   bool bound = false;
   gt_model_desc d;
@@ -175,6 +178,7 @@ struct Net {
   long step = 0;
   long bound_step = 0;            // `step` at the bind
   bool buf_live = false;          // SGD: momentum_buffer holds a value (GT_OPTF_BUFFER_LIVE at the bind, or an update since)
+  OptimScalarCache hs_cache;      // reset by every bind
   // injected dropout masks [pass][layer]
   const float* inj[3][16];
   Net() { memset(inj, 0, sizeof(inj)); }
@@ -354,9 +358,12 @@ int fault_seen(gt_engine* e);
 // the optimizer family (eng_ops.hip): validation shared by gt_bind_optimizer_ex / gt_op_optim_step, and the one place that
 // launches the fused clip + update kernel.  `step`: 1-based count of THIS update; `part`: n_partial squared-norm partials.
 int optim_check_desc(const gt_optim_desc_ex* od);
-int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, float* params, float* grads, long n, const double* part,
-                      int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
+void optim_desc_copy(const gt_optim_desc_ex* in, gt_optim_desc_ex* out);      // head only for the first family's kinds
+int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
+                      const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
                       unsigned int* skipped_host, const float* gscale, hipStream_t s);
+// NAdam's mu_product / ASGD's eta and mu after `t` updates (t >= od.step); `cache` may be null
+void optim_host_scalars(const gt_optim_desc_ex& od, long t, OptimScalarCache* cache, double out[2]);
 gt::DropoutSpec philox_site_spec(gt_engine* e, int role, int pass, int layer, uint64_t step, float p, long half_rows = 0);
 gt::DropoutSpec drop_spec(gt_engine* e, int role, int pass, int layer, const float* stacked_mask, int ld, long half_rows = 0);
 

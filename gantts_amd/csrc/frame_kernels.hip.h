@@ -1343,33 +1343,44 @@ static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// The rest of torch.optim's family behind the same clip: SGD, RMSprop, Adadelta, Adam / AdamW with amsgrad, AdamW, Adamax.
+// The rest of torch.optim's family behind the same clip: SGD, RMSprop, Adadelta, Adam / AdamW with amsgrad, AdamW, Adamax,
+// NAdam, RAdam, Rprop, ASGD.
 // One instantiation per (kind, flags): nothing is decided per element, and optim_step_kernel above (Adagrad, Adam: the
 // headline step) is not touched.  Each rule restates torch's single-tensor code path (torch/optim/<name>.py,
 // _single_tensor_<name>, foreach=False), operation by operation in float32; the step's scalars are formed on the host in
 // double and rounded once, as python does there (optim_spec_ex, engine_internal.hip.h).
 // HBM traffic: 16 B per parameter (p and g, read and written) + 8 B per live state buffer, up to three of them (40 B).
 // ---------------------------------------------------------------------------------------
-enum OptimKind { OPTK_ADAGRAD = 0, OPTK_ADAM = 1, OPTK_SGD = 2, OPTK_RMSPROP = 3, OPTK_ADADELTA = 4, OPTK_ADAMW = 5, OPTK_ADAMAX = 6 };
+enum OptimKind { OPTK_ADAGRAD = 0, OPTK_ADAM = 1, OPTK_SGD = 2, OPTK_RMSPROP = 3, OPTK_ADADELTA = 4, OPTK_ADAMW = 5, OPTK_ADAMAX = 6,
+                 OPTK_NADAM = 7, OPTK_RADAM = 8, OPTK_RPROP = 9, OPTK_ASGD = 10 };
 constexpr unsigned OPTI_NESTEROV = 1u, OPTI_CENTERED = 2u, OPTI_AMSGRAD = 4u;   // GT_OPTF_* of the C ABI
 constexpr unsigned OPTI_MOMENTUM = 16u;                                         // momentum != 0 (SGD, RMSprop): decided by the host
+constexpr unsigned OPTI_DECOUPLED = 32u;                                        // GT_OPTF_DECOUPLED_WD (NAdam, RAdam)
+constexpr unsigned OPTI_RECTIFIED = 64u;                                        // RAdam: rho_t > 5 at this step; decided by the host
+constexpr unsigned OPTI_AVERAGE = 128u;                                         // ASGD: mu != 1 at this step; decided by the host
 struct OptimSpecEx {
   float max_norm;      // clip threshold; <= 0 disables clipping
   float wd;            // weight_decay
   float eps;
-  float neg_step;      // -lr (SGD, RMSprop, Adadelta), -lr / (1 - beta1^t) (Adam, AdamW, Adamax)
-  float decay;         // AdamW: 1 - lr * weight_decay
-  float mu;            // momentum
+  float neg_step;      // -lr (SGD, RMSprop, Adadelta), -lr / (1 - beta1^t) (Adam, AdamW, Adamax), -eta (ASGD)
+  float decay;         // AdamW, decoupled NAdam / RAdam: 1 - lr * weight_decay; ASGD: 1 - lambd * eta
+  float mu;            // momentum; ASGD: the averaging weight mu
   float omd;           // SGD: 1 - dampening
   float a, oma;        // RMSprop alpha, Adadelta rho, Adam / Adamax beta2, and one minus it
   float w1;            // Adam / Adamax: 1 - beta1 (the lerp weight)
   float bc2_sqrt;      // Adam: sqrt(1 - beta2^t)
   int live;            // SGD: momentum_buffer holds a value (not the first update)
+  float lr;            // RAdam: lr
+  float bc1;           // RAdam: 1 - beta1^t
+  float bc2;           // NAdam: 1 - beta2^t
+  float rect;          // RAdam: the variance rectification term (OPTI_RECTIFIED)
+  float c_g, c_m;      // NAdam: -lr (1 - mu_t) / (1 - mu_product_t), -lr mu_{t+1} / (1 - mu_product_t mu_{t+1})
+  float eta_minus, eta_plus, step_min, step_max;      // Rprop
 };
 // which of the three state streams a (kind, flags) pair reads and writes
 template <int KIND, unsigned F> struct OptimStreams {
   static constexpr bool s0 = KIND != OPTK_SGD || (F & OPTI_MOMENTUM) != 0;
-  static constexpr bool s1 = KIND == OPTK_SGD ? false : KIND == OPTK_RMSPROP ? (F & OPTI_MOMENTUM) != 0 : true;
+  static constexpr bool s1 = (KIND == OPTK_SGD || KIND == OPTK_ASGD) ? false : KIND == OPTK_RMSPROP ? (F & OPTI_MOMENTUM) != 0 : true;
   static constexpr bool s2 = KIND == OPTK_RMSPROP ? (F & OPTI_CENTERED) != 0 : (KIND == OPTK_ADAM || KIND == OPTK_ADAMW) && (F & OPTI_AMSGRAD) != 0;
 };
 // Tensor.lerp_(end, weight) as ATen evaluates it (aten/src/ATen/native/Lerp.h): the form that is exact at the nearer end
@@ -1380,7 +1391,7 @@ __device__ __forceinline__ void optim_update_ex(float& p, float& g, float& s0, f
   float gi = g * coef;
   g = gi;                                     // clip_grad_norm_ scales .grad in place
   float pi = p;
-  if (KIND == OPTK_ADAMW) {                   // _single_tensor_adam, decoupled_weight_decay: param.mul_(1 - lr * weight_decay)
+  if (KIND == OPTK_ADAMW || (F & OPTI_DECOUPLED)) {      // decoupled_weight_decay: param.mul_(1 - lr * weight_decay)
     if (o.wd != 0.f) pi *= o.decay;
   } else if (o.wd != 0.f) {
     gi = gi + o.wd * pi;                      // grad.add(param, alpha=weight_decay)
@@ -1425,11 +1436,42 @@ __device__ __forceinline__ void optim_update_ex(float& p, float& g, float& s0, f
     if (F & OPTI_AMSGRAD) { vd = fmaxf(s2, v); s2 = vd; }         // torch.maximum(max_exp_avg_sq, exp_avg_sq, out=max_exp_avg_sq)
     const float denom = sqrtf(vd) / o.bc2_sqrt + o.eps;
     p = pi + (o.neg_step * m) / denom;                            // param.addcdiv_(exp_avg, denom, value=-step_size)
-  } else {                                    // _single_tensor_adamax
+  } else if (KIND == OPTK_ADAMAX) {           // _single_tensor_adamax
     const float m = torch_lerp(s0, gi, o.w1);
     const float u = fmaxf(s1 * o.a, fabsf(gi) + o.eps);           // torch.maximum(exp_inf.mul_(beta2), grad.abs().add_(eps), out=exp_inf)
     s0 = m; s1 = u;
     p = pi + (o.neg_step * m) / u;                                // param.addcdiv_(exp_avg, exp_inf, value=-clr)
+  } else if (KIND == OPTK_NADAM) {            // _single_tensor_nadam
+    const float m = torch_lerp(s0, gi, o.w1);
+    const float v = s1 * o.a + (o.oma * gi) * gi;
+    s0 = m; s1 = v;
+    const float denom = sqrtf(v / o.bc2) + o.eps;                 // exp_avg_sq.div(bias_correction2).sqrt().add_(eps)
+    pi = pi + (o.c_g * gi) / denom;                               // param.addcdiv_(grad, denom, value=-lr (1 - mu) / (1 - mu_product))
+    p = pi + (o.c_m * m) / denom;                                 // param.addcdiv_(exp_avg, denom, value=-lr mu_next / (1 - mu_product_next))
+  } else if (KIND == OPTK_RADAM) {            // _single_tensor_radam
+    const float m = torch_lerp(s0, gi, o.w1);
+    const float v = s1 * o.a + (o.oma * gi) * gi;
+    s0 = m; s1 = v;
+    const float upd = (m / o.bc1) * o.lr;                         // bias_corrected_exp_avg * lr
+    if (F & OPTI_RECTIFIED) {
+      const float adaptive = (1.f / (sqrtf(v) + o.eps)) * o.bc2_sqrt;      // bias_correction2 ** 0.5 / exp_avg_sq.sqrt().add_(eps): reciprocal, then the scalar
+      p = pi - (upd * adaptive) * o.rect;
+    } else {
+      p = pi - upd;
+    }
+  } else if (KIND == OPTK_RPROP) {            // _single_tensor_rprop: s0 = prev, s1 = step_size
+    const float dir = gi * s0;                                    // grad.mul(prev).sign(), as the float32 product
+    const float factor = dir > 0.f ? o.eta_plus : dir < 0.f ? o.eta_minus : 1.f;
+    const float st = fminf(fmaxf(s1 * factor, o.step_min), o.step_max);      // step_size.mul_(sign).clamp_(min, max)
+    const float gz = dir < 0.f ? 0.f : gi;                        // grad[sign.eq(etaminus)] = 0
+    const float sg = gz > 0.f ? 1.f : gz < 0.f ? -1.f : 0.f;
+    p = pi - sg * st;                                             // param.addcmul_(grad.sign(), step_size, value=-1)
+    s0 = gz; s1 = st;                                             // prev.copy_(grad)
+  } else {                                    // _single_tensor_asgd: s0 = ax
+    pi = pi * o.decay;                                            // param.mul_(1 - lambd * eta)
+    pi = pi + o.neg_step * gi;                                    // param.add_(grad, alpha=-eta)
+    p = pi;
+    s0 = (F & OPTI_AVERAGE) ? s0 + (pi - s0) * o.mu : pi;         // ax.add_(param.sub(ax).mul_(mu)), or ax.copy_(param) while mu == 1
   }
 }
 

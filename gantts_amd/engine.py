@@ -136,7 +136,7 @@ class StepEngine(object):
 
     def bind_optimizer(self, role, optimizer):
         """torch.optim reads ``param_groups`` on every step: any hyper-parameter edited since the last bind (weight_decay,
-        eps, betas, lr_decay, momentum, dampening, nesterov, alpha, centered, rho, amsgrad, ``max_grad_norm``) re-binds; a change of ``lr`` alone (exp_lr_scheduler, train.py:323-333)
+        eps, betas, lr_decay, momentum, dampening, nesterov, alpha, centered, rho, amsgrad, momentum_decay, etas, step_sizes, lambd, t0, ``max_grad_norm``) re-binds; a change of ``lr`` alone (exp_lr_scheduler, train.py:323-333)
         takes the cheap ``gt_set_lr`` path."""
         ref, ver, hyper = self._bound_opt[role]
         now = optimizer._hyper()
@@ -242,6 +242,13 @@ class StepEngine(object):
         n = C.c_int64()
         check(lib.gt_get_optimizer_step(self._h, role, C.byref(n)))
         return n.value
+
+    def optimizer_scalars(self, role):
+        """Host scalar state of the bound optimizer after the updates taken so far (gt_get_optimizer_scalars): NAdam
+        (mu_product, 0), ASGD (eta, mu)."""
+        out = (C.c_double * 2)()
+        check(lib.gt_get_optimizer_scalars(self._h, role, out))
+        return out[0], out[1]
 
     def zero_grad(self, role):
         check(lib.gt_zero_grad(self._h, role))

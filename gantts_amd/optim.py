@@ -7,7 +7,10 @@ store ``optimizer.state_dict()``, train.py:162-171).
 The update itself is the fused clip-norm + optimizer HIP kernel over the network's flat
 parameter buffer (one launch per network, executed inside ``update_discriminator`` /
 ``update_generator`` exactly where the reference calls ``clip_grad_norm_`` + ``step()``,
-train.py:275-276, 317-318).  State lives in flat float32 device buffers owned here.
+train.py:275-276, 317-318).  State lives in flat float32 device buffers owned here; the 0-dim float32 state tensors torch
+keeps beside ``step`` (NAdam ``mu_product``, ASGD ``eta`` and ``mu``) are host values that the engine advances with its step
+counter (``gt_get_optimizer_scalars``).  ``NAdam``, ``RAdam``, ``Rprop`` and ``ASGD`` are in ``gantts_amd.optim_full``, which has
+every name of this module as well.  Not covered: ``LBFGS``, ``maximize``, more than one parameter group.
 """
 import torch
 
@@ -34,6 +37,8 @@ def _owner_of(params):
 class _FlatOptimizer(object):
     KIND = None
     STATE_KEYS = ()
+    SCALAR_KEYS = ()      # 0-dim float32 state tensors of torch's class, in state_dict order behind "step": host values here
+    LR_REBINDS = False    # a changed lr re-binds (the kind keeps lr as a double) instead of taking gt_set_lr
     HAS_STEP = True       # torch keeps a "step" entry in the per-parameter state (every class but SGD)
 
     def __init__(self, params, defaults):
@@ -45,6 +50,7 @@ class _FlatOptimizer(object):
         self._state = [None, None, None]
         self._step = 0
         self._step0 = 0               # step count at construction / load_state_dict
+        self._scalars = [0.0, 0.0]    # values of SCALAR_KEYS after self._step updates (set by _desc_ex / _note_step / load_state_dict)
         self._live0 = False           # SGD: a loaded checkpoint carried momentum_buffer
         self._version = 0
         self._engines = {}
@@ -91,10 +97,17 @@ class _FlatOptimizer(object):
                 float(b1), float(b2), float(self.max_grad_norm),
                 float(g.get("momentum", 0.0)), float(g.get("dampening", 0.0)), bool(g.get("nesterov", False)),
                 float(g.get("alpha", g.get("rho", 0.0))), bool(g.get("centered", False)), bool(g.get("amsgrad", False)),
-                bool(g.get("decoupled_weight_decay", False)))
+                bool(g.get("decoupled_weight_decay", False)), float(g.get("momentum_decay", 0.0)),
+                tuple(float(v) for v in g.get("etas", ())), tuple(float(v) for v in g.get("step_sizes", ())),
+                float(g.get("lambd", 0.0)), float(g.get("t0", 0.0)), float(g["lr"]) if self.LR_REBINDS else 0.0)
+
+    def _initial_scalars(self):
+        return [0.0, 0.0]
 
     def _note_step(self, engine, role):
         self._step = engine.optimizer_step_count(role)
+        if self.SCALAR_KEYS:
+            self._scalars = list(engine.optimizer_scalars(role))
 
     # -- torch.optim API --------------------------------------------------------------------
     def zero_grad(self, set_to_none=True):
@@ -127,10 +140,10 @@ class _FlatOptimizer(object):
         """SGD's "momentum_buffer holds a value": a step was taken since construction / load, or the loaded checkpoint had it."""
         return self._live0 or self._step > self._step0
 
-    def _desc_ex(self, kind, flags=0, momentum=0.0, dampening=0.0, alpha=0.0):
+    def _desc_ex(self, kind, flags=0, momentum=0.0, dampening=0.0, alpha=0.0, **more):
         self._ensure_state()
         g = self.param_groups[0]
-        d = L.OptimDescEx()
+        d = L.OptimDescEx2() if more else L.OptimDescEx()      # the kinds of gantts_amd.optim_full carry the descriptor's tail
         d.kind, d.flags = kind, flags
         d.lr = float(g["lr"])
         d.weight_decay = float(g.get("weight_decay", 0.0))
@@ -140,6 +153,12 @@ class _FlatOptimizer(object):
         d.momentum, d.dampening, d.alpha = float(momentum), float(dampening), float(alpha)
         d.max_grad_norm = float(self.max_grad_norm)
         d.step = int(self._step)
+        if not self._has_state():      # torch creates them on the first step(), from the group's lr of that moment
+            self._scalars = self._initial_scalars()
+        if more:                       # the tail fields of the four last kinds, and the host scalar state
+            d.host_state0, d.host_state1 = float(self._scalars[0]), float(self._scalars[1])
+            for k, v in more.items():
+                setattr(d, k, float(v))
         slots = self._slots()
         for k in range(3):
             setattr(d, "state%d" % k, self._state[k].data_ptr() if k in slots else None)
@@ -154,6 +173,8 @@ class _FlatOptimizer(object):
             views = [self._views(self._state[k]) for k in slots]
             for i in range(len(self._params)):
                 st = {"step": torch.tensor(float(self._step))} if self.HAS_STEP else {}
+                for k, key in enumerate(self.SCALAR_KEYS):
+                    st[key] = torch.tensor(self._scalars[k], dtype=torch.float32)
                 for k, key in enumerate(keys):
                     st[key] = views[k][i].clone()
                 state[i] = st
@@ -172,17 +193,22 @@ class _FlatOptimizer(object):
             self._ensure_state()
             keys, slots = self.STATE_KEYS, self._slots()
             views = [self._views(self._state[k]) for k in slots]
-            steps = set()
+            steps, scalars = set(), set()
             for i in range(len(self._params)):
                 st = state[i]
                 if self.HAS_STEP:
                     steps.add(int(float(st["step"])))
+                scalars.add(tuple(float(torch.as_tensor(st[key], dtype=torch.float32)) for key in self.SCALAR_KEYS))
                 for k, key in enumerate(keys):
                     views[k][i].copy_(st[key])
             if self.HAS_STEP:
                 if len(steps) != 1:
                     raise ValueError("per-parameter step counts differ; not a checkpoint of this optimizer")
                 self._step = steps.pop()
+            if self.SCALAR_KEYS:
+                if len(scalars) != 1:
+                    raise ValueError("per-parameter %s differ; not a checkpoint of this optimizer" % " / ".join(self.SCALAR_KEYS))
+                self._scalars = (list(scalars.pop()) + [0.0])[:2]
             self._live0 = len(keys) > 0
         self._step0 = self._step
         self._version += 1

@@ -52,11 +52,17 @@ extern "C" {
 #define GT_OPT_ADADELTA 4     /* torch.optim.Adadelta (rho) */
 #define GT_OPT_ADAMW 5        /* torch.optim.AdamW == Adam(decoupled_weight_decay=True) */
 #define GT_OPT_ADAMAX 6       /* torch.optim.Adamax */
+/* (optimizer kinds are a namespace of their own: these numbers are unrelated to the gt_set_option ids further down) */
+#define GT_OPT_NADAM  7       /* torch.optim.NAdam    (momentum_decay, decoupled_weight_decay) */
+#define GT_OPT_RADAM  8       /* torch.optim.RAdam    (decoupled_weight_decay) */
+#define GT_OPT_RPROP  9       /* torch.optim.Rprop    (etas, step_sizes) */
+#define GT_OPT_ASGD   10      /* torch.optim.ASGD     (lambd, alpha, t0) */
 /* gt_optim_desc_ex.flags */
 #define GT_OPTF_NESTEROV 1u     /* SGD */
 #define GT_OPTF_CENTERED 2u     /* RMSprop */
 #define GT_OPTF_AMSGRAD 4u      /* Adam, AdamW */
 #define GT_OPTF_BUFFER_LIVE 8u  /* SGD: momentum_buffer holds a value (a step was taken, or a checkpoint that has it was loaded) */
+#define GT_OPTF_DECOUPLED_WD 32u /* NAdam, RAdam: decoupled_weight_decay=True (16u is taken inside the library) */
 
 #define GT_MAX_STREAMS 8
 
@@ -120,22 +126,40 @@ typedef struct {
  *   SGD        momentum_buffer (momentum != 0)  -                  -
  *   RMSPROP    square_avg      momentum_buffer (momentum > 0)      grad_avg (CENTERED)
  *   ADADELTA   square_avg      acc_delta                           -
- *   ADAMAX     exp_avg         exp_inf                             - */
+ *   ADAMAX     exp_avg         exp_inf                             -
+ *   NADAM      exp_avg         exp_avg_sq                          -
+ *   RADAM      exp_avg         exp_avg_sq                          -
+ *   RPROP      prev            step_size (the CALLER fills it with lr when it creates it)   -
+ *   ASGD       ax              -                                   -
+ * Host scalar state: torch keeps NAdam's mu_product and ASGD's eta and mu as 0-dim float32 tensors next to `step`.  They are
+ * host values here: host_state0 / host_state1 give them as they stand after `step` updates (NADAM: mu_product, 1 at step 0, and
+ * nothing -- the float32 product underflows to 0 after some 135 updates, as in torch, and 0 is accepted --; ASGD: eta, (float)lr at step 0, and mu, 1 at step 0), gt_get_optimizer_scalars returns them after the updates taken
+ * since.  They are float32 values carried in doubles.  The value used by update t is a function of these bind-time values, the
+ * bound step and t alone.  ASGD derives eta from lr in double and rounds it to float32 once, as torch does: for this kind lr is
+ * kept as given, not rounded to float first (gt_set_lr still stores a float). */
 typedef struct {
-  int32_t kind;              /* GT_OPT_ADAGRAD .. GT_OPT_ADAMAX */
+  int32_t kind;              /* GT_OPT_ADAGRAD .. GT_OPT_ASGD */
   uint32_t flags;            /* GT_OPTF_* */
   double lr, weight_decay, eps;
   double lr_decay;           /* Adagrad */
   double beta1, beta2;       /* Adam, AdamW, Adamax */
   double momentum;           /* SGD, RMSprop */
   double dampening;          /* SGD */
-  double alpha;              /* RMSprop alpha, Adadelta rho */
+  double alpha;              /* RMSprop alpha, Adadelta rho, ASGD alpha */
   float max_grad_norm;       /* as in gt_optim_desc */
   int32_t reserved_;
   int64_t step;              /* number of steps already taken */
   float* state0;
   float* state1;
   float* state2;
+  /* The fields below exist since GT_OPT_NADAM .. GT_OPT_ASGD and are read for those kinds ONLY: for GT_OPT_ADAGRAD .. GT_OPT_ADAMAX the
+   * library never looks past state2, so a caller built against the 120-byte struct of the first family keeps working unchanged. */
+  double momentum_decay;     /* NAdam */
+  double etaminus, etaplus;  /* Rprop etas */
+  double step_size_min, step_size_max;   /* Rprop step_sizes */
+  double lambd, t0;          /* ASGD */
+  double host_state0;        /* NAdam mu_product / ASGD eta, as they stand after `step` updates */
+  double host_state1;        /* ASGD mu */
 } gt_optim_desc_ex;
 
 typedef struct {             /* return values of update_discriminator, train.py:278-279 (same order) */
@@ -163,14 +187,18 @@ int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc);
 /* getattr(optim, hp.optimizer_*)(model.parameters(), **params) (train.py:796-799) */
 int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* desc);
 /* The same for every GT_OPT_* kind.  Checks per kind which state buffers must be given and rejects what torch's constructors
- * reject (GT_ERR_INVALID): negative lr / eps / weight_decay / momentum / alpha, betas or rho outside their interval, nesterov
- * with zero momentum or non-zero dampening, a flag that does not belong to the kind. */
+ * reject (GT_ERR_INVALID): negative lr / eps / weight_decay / momentum / alpha / momentum_decay, betas or rho outside their
+ * interval, etas that are not 0 < etaminus < 1 < etaplus, nesterov with zero momentum or non-zero dampening, a flag that does
+ * not belong to the kind. */
 int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_ex* desc);
 /* model.train() / model.eval()                                 (train.py:481-486) */
 int gt_set_training(gt_engine* e, int role, int training);
 /* exp_lr_scheduler writes param_group["lr"]                     (train.py:323-333) */
 int gt_set_lr(gt_engine* e, int role, float lr);
 int gt_get_optimizer_step(gt_engine* e, int role, int64_t* step);
+/* The host scalar state of the bound optimizer after the updates taken so far (what optimizer.state_dict() holds beside
+ * "step"): NADAM out[0] = mu_product; ASGD out[0] = eta, out[1] = mu; 0 for every other kind. */
+int gt_get_optimizer_scalars(gt_engine* e, int role, double out[2]);
 int gt_set_seed(gt_engine* e, uint64_t seed);
 /* Parity hook: use the caller's 0/1 float mask ((rows, hidden) contiguous, device) instead of the
  * Philox stream for dropout site `layer` of forward pass `pass` of `role`; NULL restores Philox.
@@ -416,6 +444,10 @@ int gt_op_masked_mse(const float* input, const float* target, const float* mask,
  * *gscale.  grads receives the clipped gradient.  grad_norm_out (host, may be NULL): the pre-clip norm; synchronises if given. */
 int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
                      float* grad_norm_out, void* stream);
+/* Host only, no device: the host scalar state of desc's kind after `t` >= desc->step updates, from desc's hyper-parameters, step and
+ * host_state* (the routine behind gt_get_optimizer_scalars and the update's own scalars; the descriptor is checked as by gt_bind_optimizer_ex, its state buffers aside, which are not looked at).  A caller
+ * that steps through gt_op_optim_step passes out[] back in as host_state* of the next step's descriptor. */
+int gt_op_optim_scalars(const gt_optim_desc_ex* desc, int64_t t, double out[2]);
 /* Device-side collate: padding (train.py:139-159 `_pad_2d` / collate_fn) and the descending length sort of the batch
  * (train.py:494-501) without a padded host copy.  `ragged`: the batch's utterances un-padded, back to back, [total][D] (device);
  * start[b] / len[b] (device int64, B entries): first frame and frame count of the utterance that becomes OUTPUT sequence b (the
