@@ -318,25 +318,6 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   return GT_OK;
 }
 
-extern "C" int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* od) {
-  if (!e || !od || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
-  Net& n = e->net[role];
-  if (!n.bound) return fail(GT_ERR_STATE, "bind the model before its optimizer");
-  if (!n.d.grads) return fail(GT_ERR_INVALID, "model was bound without a grads buffer");
-  if (od->kind != GT_OPT_ADAGRAD && od->kind != GT_OPT_ADAM) return fail(GT_ERR_INVALID, "unknown optimizer kind");
-  if (!od->state0 || (od->kind == GT_OPT_ADAM && !od->state1)) return fail(GT_ERR_INVALID, "optimizer state buffer is null");
-  gt_optim_desc_ex x;
-  memset(&x, 0, sizeof(x));
-  x.kind = od->kind; x.lr = od->lr; x.weight_decay = od->weight_decay; x.eps = od->eps; x.lr_decay = od->lr_decay;
-  x.beta1 = od->beta1; x.beta2 = od->beta2; x.max_grad_norm = od->max_grad_norm; x.step = od->step;
-  x.state0 = od->state0; x.state1 = od->state1;
-  n.od = x;
-  n.step = n.bound_step = od->step;
-  n.buf_live = false;
-  n.hs_cache = OptimScalarCache();
-  n.has_opt = true;
-  return GT_OK;
-}
 extern "C" int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_ex* od) {
   if (!e || !od || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
   Net& n = e->net[role];
@@ -350,6 +331,18 @@ extern "C" int gt_bind_optimizer_ex(gt_engine* e, int role, const gt_optim_desc_
   n.buf_live = (od->flags & GT_OPTF_BUFFER_LIVE) != 0;
   n.has_opt = true;
   return GT_OK;
+}
+// The first descriptor (Adagrad, Adam; float hyper-parameters): widened, then bound as gt_bind_optimizer_ex binds it, its checks
+// of the hyper-parameters included (torch's constructors' own: include/gantts_hip.h).
+extern "C" int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* od) {
+  if (!od) return fail(GT_ERR_INVALID, "bad argument");
+  if (od->kind != GT_OPT_ADAGRAD && od->kind != GT_OPT_ADAM) return fail(GT_ERR_INVALID, "unknown optimizer kind");
+  gt_optim_desc_ex x;
+  memset(&x, 0, sizeof(x));
+  x.kind = od->kind; x.lr = od->lr; x.weight_decay = od->weight_decay; x.eps = od->eps; x.lr_decay = od->lr_decay;
+  x.beta1 = od->beta1; x.beta2 = od->beta2; x.max_grad_norm = od->max_grad_norm; x.step = od->step;
+  x.state0 = od->state0; x.state1 = od->state1;
+  return gt_bind_optimizer_ex(e, role, &x);
 }
 extern "C" int gt_set_training(gt_engine* e, int role, int training) {
   if (!e || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
@@ -600,9 +593,10 @@ int fault_seen(gt_engine* e) {
   return GT_OK;
 }
 // After a fault: parameters, gradients and optimizer state were left untouched by every optimizer launch that saw the
-// raised word (optim_step_kernel returns before its first write and counts the skipped step in pinned memory).  This
-// call waits for the stream, takes the skipped steps back out of the host-side step counters, and clears the word, so
-// that the engine is usable again (typically after gt_set_option(GT_OPT_LSTM_PERSISTENT, 0)).
+// raised word (optim_step_kernel<KIND, F>, optim_kernels.hip.h, returns before its first write and counts the skipped
+// step in pinned memory).  This call waits for the stream, takes the skipped steps back out of the host-side step
+// counters, and clears the word, so that the engine is usable again (typically after
+// gt_set_option(GT_OPT_LSTM_PERSISTENT, 0)).
 extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));

@@ -1,5 +1,6 @@
 // libgantts_hip.so -- stand-alone operators of the C ABI (gt_op_*, gt_compute_distortions)
 #include "engine_internal.hip.h"
+#include "optim_kernels.hip.h"
 
 using namespace gt;
 // ------------------------------------------------------------------------------------------
@@ -607,16 +608,54 @@ static int optim_check_tail(const gt_optim_desc_ex* od) {
                 od->host_state1);
   return GT_OK;
 }
+
+// The variants of optim_step_kernel: one row per legal (kind, internal flags) pair, with the state streams it
+// reads and writes.
+typedef void (*OptimKernel)(float*, float*, float*, float*, float*, long, const double*, int, double*, OptimSpec, const unsigned int*,
+                            unsigned int*, unsigned int*, const float*);
+struct OptimVariant { int kind; unsigned flags; bool s0, s1, s2; OptimKernel kernel; };
+#define OPTIM_ROW(KIND, F) \
+  {KIND, (F), OptimStreams<KIND, (F)>::s0, OptimStreams<KIND, (F)>::s1, OptimStreams<KIND, (F)>::s2, optim_step_kernel<KIND, (F)>}
+static const OptimVariant OPTIM_VARIANTS[] = {
+  OPTIM_ROW(OPTK_ADAGRAD, OPTI_ORIGINAL),
+  OPTIM_ROW(OPTK_ADAM, OPTI_ORIGINAL), OPTIM_ROW(OPTK_ADAM, OPTI_AMSGRAD),
+  OPTIM_ROW(OPTK_SGD, 0u), OPTIM_ROW(OPTK_SGD, OPTI_MOMENTUM), OPTIM_ROW(OPTK_SGD, OPTI_NESTEROV | OPTI_MOMENTUM),
+  OPTIM_ROW(OPTK_RMSPROP, 0u), OPTIM_ROW(OPTK_RMSPROP, OPTI_CENTERED),
+  OPTIM_ROW(OPTK_RMSPROP, OPTI_MOMENTUM), OPTIM_ROW(OPTK_RMSPROP, OPTI_CENTERED | OPTI_MOMENTUM),
+  OPTIM_ROW(OPTK_ADADELTA, 0u),
+  OPTIM_ROW(OPTK_ADAMW, 0u), OPTIM_ROW(OPTK_ADAMW, OPTI_AMSGRAD),
+  OPTIM_ROW(OPTK_ADAMAX, 0u),
+  OPTIM_ROW(OPTK_NADAM, 0u), OPTIM_ROW(OPTK_NADAM, OPTI_DECOUPLED),
+  OPTIM_ROW(OPTK_RADAM, 0u), OPTIM_ROW(OPTK_RADAM, OPTI_RECTIFIED),
+  OPTIM_ROW(OPTK_RADAM, OPTI_DECOUPLED), OPTIM_ROW(OPTK_RADAM, OPTI_DECOUPLED | OPTI_RECTIFIED),
+  OPTIM_ROW(OPTK_RPROP, 0u),
+  OPTIM_ROW(OPTK_ASGD, 0u), OPTIM_ROW(OPTK_ASGD, OPTI_AVERAGE),
+};
+#undef OPTIM_ROW
+// The internal flags of a descriptor's update: its GT_OPTF_* (the OPTI_* of the same values), what its hyper-parameters decide
+// (OPTI_MOMENTUM, OPTI_ORIGINAL) and what the host decides for the step at hand (`step_flags`: OPTI_RECTIFIED, OPTI_AVERAGE, which
+// change no stream: a descriptor's row with step_flags = 0 tells its state buffers).
+static unsigned optim_flags(const gt_optim_desc_ex& od, unsigned step_flags) {
+  const int k = od.kind;
+  unsigned f = (od.flags & (OPTI_NESTEROV | OPTI_CENTERED | OPTI_AMSGRAD | OPTI_DECOUPLED)) | step_flags;
+  if ((k == GT_OPT_SGD || k == GT_OPT_RMSPROP) && od.momentum != 0.0) f |= OPTI_MOMENTUM;
+  if (k == GT_OPT_ADAGRAD || (k == GT_OPT_ADAM && !(f & OPTI_AMSGRAD))) f |= OPTI_ORIGINAL;
+  return f;
+}
+static const OptimVariant* optim_variant(int kind, unsigned flags) {
+  for (const OptimVariant& v : OPTIM_VARIANTS)
+    if (v.kind == kind && v.flags == flags) return &v;
+  return nullptr;
+}
+
 int optim_check_desc(const gt_optim_desc_ex* od) {
   CHK(optim_check_head(od));
   const int k = od->kind;
-  const bool mom = (k == GT_OPT_SGD || k == GT_OPT_RMSPROP) && od->momentum != 0.0;
-  const bool need0 = k != GT_OPT_SGD || mom;
-  const bool need1 = k == GT_OPT_RMSPROP ? mom : k != GT_OPT_ADAGRAD && k != GT_OPT_SGD && k != GT_OPT_ASGD;
-  const bool need2 = (od->flags & (GT_OPTF_CENTERED | GT_OPTF_AMSGRAD)) != 0;
-  if ((need0 && !od->state0) || (need1 && !od->state1) || (need2 && !od->state2))
-    return fail(GT_ERR_INVALID, "optimizer state buffer is null (kind %d, flags 0x%x needs state%s%s%s)", k, od->flags, need0 ? " 0" : "",
-                need1 ? " 1" : "", need2 ? " 2" : "");
+  const OptimVariant* v = optim_variant(k, optim_flags(*od, 0u));
+  if (!v) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", k);
+  if ((v->s0 && !od->state0) || (v->s1 && !od->state1) || (v->s2 && !od->state2))
+    return fail(GT_ERR_INVALID, "optimizer state buffer is null (kind %d, flags 0x%x needs state%s%s%s)", k, od->flags, v->s0 ? " 0" : "",
+                v->s1 ? " 1" : "", v->s2 ? " 2" : "");
   return optim_check_tail(od);      // after everything that the head alone decides: a null buffer is reported without reading the tail
 }
 
@@ -652,14 +691,19 @@ void optim_host_scalars(const gt_optim_desc_ex& od, long t, OptimScalarCache* ca
 
 // The scalars of update number `step` (1-based), formed in double from the double hyper-parameters and rounded to float
 // once -- python arithmetic followed by a Scalar -> float conversion in torch's single-tensor code paths.  `flags` receives
-// what the host decides for this update beyond the descriptor's flags (OPTI_RECTIFIED, OPTI_AVERAGE).
-static OptimSpecEx optim_spec_ex(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, unsigned* flags) {
-  OptimSpecEx o;
+// what the host decides for this update beyond the descriptor's flags (OPTI_RECTIFIED, OPTI_AVERAGE).  The OPTI_ORIGINAL kinds
+// alone get their hyper-parameters rounded to float and the step count: they form their scalars in the kernel.
+static OptimSpec optim_spec(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, unsigned* flags) {
+  OptimSpec o;
   memset(&o, 0, sizeof(o));
   const double lr = od.lr;
   o.max_norm = od.max_grad_norm; o.wd = (float)od.weight_decay; o.eps = (float)od.eps;
   o.neg_step = (float)-lr;
   o.live = buf_live ? 1 : 0;
+  if (optim_flags(od, 0u) & OPTI_ORIGINAL) {
+    o.lr = (float)lr; o.lr_decay = (float)od.lr_decay; o.beta1 = (float)od.beta1; o.beta2 = (float)od.beta2; o.step = step;
+    return o;
+  }
   switch (od.kind) {
     case GT_OPT_SGD:
       o.mu = (float)od.momentum; o.omd = (float)(1.0 - od.dampening);
@@ -727,60 +771,12 @@ int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, Opti
                       const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
                       unsigned int* skipped_host, const float* gscale, hipStream_t s) {
   const dim3 grid((unsigned)std::min<long>(1024, cdiv(n, RED_THREADS))), block(RED_THREADS);
-  const bool ams = (od.flags & GT_OPTF_AMSGRAD) != 0;
-  if (od.kind == GT_OPT_ADAGRAD || (od.kind == GT_OPT_ADAM && !ams)) {      // the two kinds of gt_bind_optimizer: their own kernel
-    OptimSpec o;
-    o.kind = od.kind; o.lr = (float)od.lr; o.weight_decay = (float)od.weight_decay; o.eps = (float)od.eps; o.lr_decay = (float)od.lr_decay;
-    o.beta1 = (float)od.beta1; o.beta2 = (float)od.beta2; o.step = step; o.max_norm = od.max_grad_norm;
-    hipLaunchKernelGGL(optim_step_kernel, grid, block, 0, s, params, grads, od.state0, od.state1, n, part, n_partial, norm2_out, o,
-                       fault_dev, fault_host, skipped_host, gscale);
-    LAUNCH_CHECK();
-    return GT_OK;
-  }
-  unsigned hostf = 0u;
-  const OptimSpecEx o = optim_spec_ex(od, step, buf_live, cache, &hostf);
-#define GT_OPTIM_LAUNCH(KIND, F)                                                                                                      \
-  hipLaunchKernelGGL((optim_step_ex_kernel<KIND, F>), grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, \
-                     n_partial, norm2_out, o, fault_dev, fault_host, skipped_host, gscale)
-  const bool mom = od.momentum != 0.0, nest = (od.flags & GT_OPTF_NESTEROV) != 0, cen = (od.flags & GT_OPTF_CENTERED) != 0;
-  const bool dec = (od.flags & GT_OPTF_DECOUPLED_WD) != 0, rect = (hostf & OPTI_RECTIFIED) != 0;
-  switch (od.kind) {
-    case GT_OPT_SGD:
-      if (!mom) GT_OPTIM_LAUNCH(OPTK_SGD, 0u);
-      else if (!nest) GT_OPTIM_LAUNCH(OPTK_SGD, OPTI_MOMENTUM);
-      else GT_OPTIM_LAUNCH(OPTK_SGD, OPTI_MOMENTUM | OPTI_NESTEROV);
-      break;
-    case GT_OPT_RMSPROP:
-      if (!mom && !cen) GT_OPTIM_LAUNCH(OPTK_RMSPROP, 0u);
-      else if (!mom) GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_CENTERED);
-      else if (!cen) GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_MOMENTUM);
-      else GT_OPTIM_LAUNCH(OPTK_RMSPROP, OPTI_MOMENTUM | OPTI_CENTERED);
-      break;
-    case GT_OPT_ADADELTA: GT_OPTIM_LAUNCH(OPTK_ADADELTA, 0u); break;
-    case GT_OPT_ADAM: GT_OPTIM_LAUNCH(OPTK_ADAM, OPTI_AMSGRAD); break;
-    case GT_OPT_ADAMW:
-      if (ams) GT_OPTIM_LAUNCH(OPTK_ADAMW, OPTI_AMSGRAD);
-      else GT_OPTIM_LAUNCH(OPTK_ADAMW, 0u);
-      break;
-    case GT_OPT_ADAMAX: GT_OPTIM_LAUNCH(OPTK_ADAMAX, 0u); break;
-    case GT_OPT_NADAM:
-      if (dec) GT_OPTIM_LAUNCH(OPTK_NADAM, OPTI_DECOUPLED);
-      else GT_OPTIM_LAUNCH(OPTK_NADAM, 0u);
-      break;
-    case GT_OPT_RADAM:
-      if (dec && rect) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_DECOUPLED | OPTI_RECTIFIED);
-      else if (dec) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_DECOUPLED);
-      else if (rect) GT_OPTIM_LAUNCH(OPTK_RADAM, OPTI_RECTIFIED);
-      else GT_OPTIM_LAUNCH(OPTK_RADAM, 0u);
-      break;
-    case GT_OPT_RPROP: GT_OPTIM_LAUNCH(OPTK_RPROP, 0u); break;
-    case GT_OPT_ASGD:
-      if (hostf & OPTI_AVERAGE) GT_OPTIM_LAUNCH(OPTK_ASGD, OPTI_AVERAGE);
-      else GT_OPTIM_LAUNCH(OPTK_ASGD, 0u);
-      break;
-    default: return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
-  }
-#undef GT_OPTIM_LAUNCH
+  unsigned step_flags = 0u;
+  const OptimSpec o = optim_spec(od, step, buf_live, cache, &step_flags);
+  const OptimVariant* v = optim_variant(od.kind, optim_flags(od, step_flags));
+  if (!v) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
+  hipLaunchKernelGGL(v->kernel, grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, n_partial, norm2_out, o,
+                     fault_dev, fault_host, skipped_host, gscale);
   LAUNCH_CHECK();
   return GT_OK;
 }

@@ -145,9 +145,7 @@ class StepEngine(object):
                 check(lib.gt_set_lr(self._h, role, now[0]))
                 self._bound_opt[role] = (ref, ver, now)
             return
-        desc = optimizer._desc()
-        bind = lib.gt_bind_optimizer_ex if isinstance(desc, L.OptimDescEx) else lib.gt_bind_optimizer
-        check(bind(self._h, role, C.byref(desc)))
+        check(lib.gt_bind_optimizer_ex(self._h, role, C.byref(optimizer._desc())))
         self._bound_opt[role] = (weakref.ref(optimizer), optimizer._version, now)
         optimizer._engines[id(self)] = (weakref.ref(self), role)
 

@@ -72,23 +72,6 @@ class _FlatOptimizer(object):
                 self._state[i] = st.to(flat.device)
                 self._version += 1
 
-    def _desc(self):
-        self._ensure_state()
-        g = self.param_groups[0]
-        d = L.OptimDesc()
-        d.kind = self.KIND
-        d.lr = float(g["lr"])
-        d.weight_decay = float(g.get("weight_decay", 0.0))
-        d.eps = float(g["eps"])
-        d.lr_decay = float(g.get("lr_decay", 0.0))
-        b1, b2 = g.get("betas", (0.0, 0.0))
-        d.beta1, d.beta2 = float(b1), float(b2)
-        d.max_grad_norm = float(self.max_grad_norm)
-        d.step = int(self._step)
-        d.state0 = self._state[0].data_ptr()
-        d.state1 = self._state[1].data_ptr() if len(self.STATE_KEYS) > 1 else None
-        return d
-
     def _hyper(self):
         """(lr, everything else the fused update kernel reads) -- compared by StepEngine.bind_optimizer on every step."""
         g = self.param_groups[0]
@@ -148,6 +131,7 @@ class _FlatOptimizer(object):
         d.lr = float(g["lr"])
         d.weight_decay = float(g.get("weight_decay", 0.0))
         d.eps = float(g.get("eps", 0.0))
+        d.lr_decay = float(g.get("lr_decay", 0.0))
         b1, b2 = g.get("betas", (0.0, 0.0))
         d.beta1, d.beta2 = float(b1), float(b2)
         d.momentum, d.dampening, d.alpha = float(momentum), float(dampening), float(alpha)
@@ -236,6 +220,9 @@ class Adagrad(_FlatOptimizer):
         if fresh and self._init_acc != 0.0:
             self._state[0].fill_(self._init_acc)
 
+    def _desc(self):
+        return self._desc_ex(L.OPT_ADAGRAD)
+
 
 def _reject(maximize):
     if maximize:
@@ -267,10 +254,8 @@ class Adam(_FlatOptimizer):
 
     def _desc(self):
         g = self.param_groups[0]
-        ams, dec = bool(g.get("amsgrad")), bool(g.get("decoupled_weight_decay"))
-        if not ams and not dec:
-            return super(Adam, self)._desc()      # the kernel of the two original kinds
-        return self._desc_ex(L.OPT_ADAMW if dec else L.OPT_ADAM, L.OPTF_AMSGRAD if ams else 0)
+        dec = bool(g.get("decoupled_weight_decay"))
+        return self._desc_ex(L.OPT_ADAMW if dec else L.OPT_ADAM, L.OPTF_AMSGRAD if g.get("amsgrad") else 0)
 
 
 class AdamW(Adam):

@@ -184,7 +184,9 @@ void gt_engine_destroy(gt_engine* e);
  * most 8 layers; parity unpinned like every SRU path), out_dim 1, last_sigmoid set, for the recurrent ones hidden_dim x directions
  * <= 1024; other combinations (the tuple-returning In2Out* among them) are rejected (GT_ERR_INVALID). */
 int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc);
-/* getattr(optim, hp.optimizer_*)(model.parameters(), **params) (train.py:796-799) */
+/* getattr(optim, hp.optimizer_*)(model.parameters(), **params) (train.py:796-799).  GT_OPT_ADAGRAD and GT_OPT_ADAM through the first
+ * descriptor: it is widened to gt_optim_desc_ex and bound by gt_bind_optimizer_ex, whose checks apply -- a negative lr / eps /
+ * weight_decay / lr_decay or a beta outside [0, 1), which this entry once took unlooked at, is GT_ERR_INVALID. */
 int gt_bind_optimizer(gt_engine* e, int role, const gt_optim_desc* desc);
 /* The same for every GT_OPT_* kind.  Checks per kind which state buffers must be given and rejects what torch's constructors
  * reject (GT_ERR_INVALID): negative lr / eps / weight_decay / momentum / alpha / momentum_decay, betas or rho outside their

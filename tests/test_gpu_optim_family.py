@@ -1,5 +1,5 @@
-"""-m gpu: the fused clip + update kernel of every optimizer kind (optim_step_kernel / optim_step_ex_kernel,
-gantts_amd/csrc/frame_kernels.hip.h) against torch.optim on the CPU.
+"""-m gpu: the fused clip + update kernel of every optimizer kind (optim_step_kernel<KIND, F>,
+gantts_amd/csrc/optim_kernels.hip.h) against torch.optim on the CPU.
 
 The oracle is the torch class itself (``foreach=False``) behind ``clip_grad_norm_``, once in float64 (the truth) and once in
 float32 (the reference's own error).  Rule, per case and compared tensor (parameters and every state buffer):

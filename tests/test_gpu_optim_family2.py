@@ -1,5 +1,5 @@
-"""-m gpu: the fused clip + update kernel of NAdam, RAdam, Rprop and ASGD (optim_step_ex_kernel<OPTK_NADAM .. OPTK_ASGD>,
-gantts_amd/csrc/frame_kernels.hip.h) against torch.optim on the CPU, by the protocol and the rule of
+"""-m gpu: the fused clip + update kernel of NAdam, RAdam, Rprop and ASGD (optim_step_kernel<OPTK_NADAM .. OPTK_ASGD>,
+gantts_amd/csrc/optim_kernels.hip.h) against torch.optim on the CPU, by the protocol and the rule of
 tests/test_gpu_optim_family.py (whose helpers are imported, not restated):
 
     rms(engine - ref64) <= 3 x rms(torch32 - ref64)      per case and tensor (parameters and every full-size state buffer)
