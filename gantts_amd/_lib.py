@@ -29,6 +29,7 @@ LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm
 GEMM_PATH_SLOTS = 588                                                   # gt_gemm_path_counts
 GEMM_B16_PATH_SLOTS = 66                                                # gt_gemm_b16_path_counts
 SRU_PATH_SLOTS = 13                                                     # gt_sru_path_counts
+HEAD_PATH_SLOTS = 15                                                    # gt_head_path_counts
 CAST_PLAIN_F32, CAST_PLAIN_BF16, CAST_SEQDROP, CAST_CAT, CAST_CATDROP, CAST_MULTI = 0, 1, 2, 3, 4, 5      # CastCase.kind
 CAST_MAX_JOBS = 8
 GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
@@ -117,6 +118,34 @@ class SruScanCase(C.Structure):
                                              "nx_b", "nx_bt", "dU_b", "dU_bt")])
 
 
+class DropSite(C.Structure):
+    _fields_ = ([("mode", C.c_int32), ("p", C.c_float), ("key0", C.c_uint32), ("key1", C.c_uint32)]
+                + [(n, C.c_uint32) for n in ("dp_t16", "dp_nl16", "dp_half", "dp_add", "dp_mul")]
+                + [("dp_inv_t16", C.c_float), ("ld_mask", C.c_int32), ("pad_", C.c_int32), ("mask", C.c_void_p)])
+
+
+class DHeadCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("mode", "K", "ldh", "h_ld", "has_act", "want_grad", "want_w", "defer_scalars", "accumulate", "unit_tv",
+                                          "has_tv", "lddh", "lddhb", "pad_")]
+                + [("eps", C.c_float), ("tv", C.c_float)]
+                + [(n, C.c_int64) for n in ("rows", "n_real", "n_mask", "lddhbt")]
+                + [("drop", DropSite)]
+                + [(n, C.c_void_p) for n in ("H", "w", "bias", "mask", "tv_dev", "Dout", "dH", "dHb", "dHbT", "dW", "db")]
+                + [("scalars", C.POINTER(C.c_double))])
+
+
+class DStackCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("mode", "L", "hidden_dim", "want_grad", "accumulate", "unit_tv", "has_tv", "ldw0", "col0", "Da",
+                                          "ld_gadv", "pad_")]
+                + [("eps", C.c_float), ("tv", C.c_float)]
+                + [(n, C.c_int64) for n in ("rows", "n_real", "n_mask")]
+                + [("drop", DropSite * 4), ("H0", C.c_void_p), ("W", C.c_void_p * 4), ("b", C.c_void_p * 4)]
+                + [(n, C.c_void_p) for n in ("w_last", "b_last", "mask", "tv_dev")]
+                + [("Hout", C.c_void_p * 4)]
+                + [(n, C.c_void_p) for n in ("dZtop", "Dout", "dW_last", "db_last", "W0", "gadv")]
+                + [("scalars", C.POINTER(C.c_double))])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -177,6 +206,9 @@ SIGNATURES = {
     "gt_op_sru_dx_adv_finish": (_I, [_P, _L, _I, _I, _P, _I, _P, _I, _P]),
     "gt_op_sru_input_mask": (_I, [_P, _I, _I, _F, C.c_uint32, C.c_uint32, _P, _I, _I, _P]),
     "gt_op_sru_input_dropout": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "gt_head_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_op_d_head": (_I, [C.POINTER(DHeadCase), _P]),
+    "gt_op_dstack": (_I, [C.POINTER(DStackCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -26,6 +26,7 @@ static int launch_dstack_t(const DStackArgs& a, hipStream_t s) {
   }
   hipLaunchKernelGGL((dstack_kernel<HD>), dim3(grid), dim3(DS_THREADS), lds, s, a);
   LAUNCH_CHECK();
+  head_path_count(HD == 128 ? HEAD_PATH_DSTACK128 : HEAD_PATH_DSTACK256);
   if (prof) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }
   return GT_OK;
 }

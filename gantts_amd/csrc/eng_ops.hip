@@ -1,6 +1,8 @@
 // libgantts_hip.so -- stand-alone operators of the C ABI (gt_op_*, gt_compute_distortions)
 #include "engine_internal.hip.h"
 #include "optim_kernels.hip.h"
+#include "d_tail_args.hip.h"
+#include <stddef.h>
 
 using namespace gt;
 // ------------------------------------------------------------------------------------------
@@ -559,6 +561,173 @@ extern "C" int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ld
   CHK(sru_launch_input_dropout(x, ldx, y, ldy, B, T, n, mul, s));
   HIPCHK(hipStreamSynchronize(s));
   return GT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// parity hooks of the discriminator's tail (tests/test_gpu_d_tail.py): one head pass / one fused pass plus its finalising launch
+// through launch_d_head / launch_dstack_pass (eng_step.hip).  Everything a kernel would index with is checked first.
+// ------------------------------------------------------------------------------------------
+static bool tail_site_ok(const gt_drop_site& d, int width, long rows, bool exact_pitch, const char** why) {
+  *why = nullptr;
+  if (d.mode < DROP_NONE || d.mode > DROP_BUFFER) *why = "unknown dropout mode";
+  else if (d.mode != DROP_NONE && !(d.p > 0.f && d.p < 1.f)) *why = "dropout needs 0 < p < 1";
+  else if (d.mode == DROP_BUFFER && (!d.mask || (((uintptr_t)d.mask) & 3))) *why = "injected dropout mask missing or misaligned";
+  else if (d.mode == DROP_BUFFER && (exact_pitch ? d.ld_mask != width : d.ld_mask < width)) *why = "injected dropout mask pitch";
+  else if (d.mode == DROP_PHILOX && d.dp_t16 != 0u && (rows / 16 >= (1L << 21) || !(d.dp_inv_t16 > 0.f))) *why = "data-parallel Philox map out of range";
+  return *why == nullptr;
+}
+static DropoutSpec tail_site_spec(const gt_drop_site& d) {
+  DropoutSpec s = case_drop_spec(d.mode, d.mask, d.ld_mask, d.p, d.key0, d.key1);
+  if (d.mode == DROP_PHILOX) {
+    s.dp_t16 = d.dp_t16; s.dp_nl16 = d.dp_nl16; s.dp_half = d.dp_half; s.dp_add = d.dp_add; s.dp_mul = d.dp_mul; s.dp_inv_t16 = d.dp_inv_t16;
+  }
+  return s;
+}
+// the scratch of one tail hook call: the step's scalars and the partial buffers, all NaN (0xFF bytes) until something writes them
+struct TailScratch {
+  Scratch mem;
+  StepScalars* sc = nullptr;
+  HeadSums o;
+  float tv_host[2];
+  int init(int nblk, int K, int has_tv, float tv, float* dW, float* db, int accumulate, hipStream_t s) {
+    const size_t off_hp = 256, off_dw = off_hp + (((size_t)nblk * sizeof(HeadPartials) + 255) & ~(size_t)255);
+    const size_t total = off_dw + (size_t)nblk * K * sizeof(float);
+    static_assert(sizeof(StepScalars) <= 256, "scratch layout");
+    CHK(mem.ensure(total));
+    HIPCHK(hipMemsetAsync(mem.p, 0xFF, total, s));
+    sc = (StepScalars*)mem.p;
+    if (has_tv) {
+      tv_host[0] = tv; tv_host[1] = 1.0f / tv;
+      HIPCHK(hipMemcpyAsync(mem.p, tv_host, sizeof(tv_host), hipMemcpyHostToDevice, s));      // StepScalars: tv, inv_tv lead
+    }
+    memset(&o, 0, sizeof(o));
+    o.sc = sc;
+    o.hp = (HeadPartials*)((char*)mem.p + off_hp); o.hp_cap = nblk;
+    o.dw_partial = (float*)((char*)mem.p + off_dw); o.dw_cap = (long)nblk * K;
+    o.dW = dW; o.db = db; o.accumulate = accumulate;
+    return GT_OK;
+  }
+  // synchronises, reports the scalars, releases; r: the launch function's status
+  int finish(int r, int nblk, double* scalars, const char* what, hipStream_t s) {
+    hipError_t err = hipStreamSynchronize(s);
+    StepScalars h;
+    if (err == hipSuccess && r == GT_OK && scalars) {
+      err = hipMemcpy(&h, sc, sizeof(h), hipMemcpyDeviceToHost);
+      if (err == hipSuccess) {
+        scalars[0] = h.s_real; scalars[1] = h.s_fake; scalars[2] = h.n_real_ok; scalars[3] = h.n_fake_ok; scalars[4] = h.s_adv;
+        scalars[5] = (double)h.tv; scalars[6] = (double)h.inv_tv; scalars[7] = (double)nblk;
+      }
+    }
+    mem.release();
+    if (r) return r;
+    if (err != hipSuccess) return fail(GT_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
+    return GT_OK;
+  }
+};
+static_assert(offsetof(StepScalars, tv) == 0 && offsetof(StepScalars, inv_tv) == 4, "TailScratch::init writes tv, inv_tv at the front");
+
+// mask, n_real, normaliser: what both tail hooks share
+static const char* tail_common_bad(int mode, int64_t rows, int64_t n_real, int64_t n_mask, const float* mask, int has_tv, float tv,
+                                   const double* tv_dev, int unit_tv) {
+  if (mode != HEAD_D_STEP && mode != HEAD_G_ADV) return "mode 0 (D step) or 1 (adversarial term)";
+  if (rows < 1 || rows > 0x7FFFFFFFL - 64) return "rows out of range";
+  if (!mask || (((uintptr_t)mask) & 3) || n_mask < 1 || n_mask > 0x7FFFFFFFL) return "needs a mask and 1 <= n_mask";
+  if (mode == HEAD_D_STEP && (n_real < 0 || n_real > rows)) return "0 <= n_real <= rows";
+  const int given = (has_tv ? 1 : 0) + (tv_dev ? 1 : 0) + (unit_tv ? 1 : 0);
+  if (given != 1) return "exactly one normaliser: has_tv, tv_dev or unit_tv";
+  if (has_tv && !(tv > 0.f)) return "tv must be positive";
+  if (((uintptr_t)tv_dev) & 7) return "misaligned tv_dev";
+  return nullptr;
+}
+
+extern "C" int gt_op_d_head(const gt_d_head_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
+    return fail(GT_ERR_INVALID, "head hook: %s", why);
+  if (c->K < 1 || c->K > 1024) return fail(GT_ERR_INVALID, "head hook: K = %d (1 .. 1024)", c->K);
+  if (!c->H || !c->w || !c->bias) return fail(GT_ERR_INVALID, "head hook: needs H, w and bias");
+  const bool img = c->h_ld > 0;
+  if (c->h_ld < 0 || (img ? c->h_ld < c->K : c->ldh < c->K)) return fail(GT_ERR_INVALID, "head hook: pitch of H below K");
+  if ((((uintptr_t)c->H) & (img ? 1 : 3)) || ((((uintptr_t)c->w) | ((uintptr_t)c->bias) | ((uintptr_t)c->Dout) | ((uintptr_t)c->dH) | ((uintptr_t)c->dW) |
+                                                 ((uintptr_t)c->db)) & 3))
+    return fail(GT_ERR_INVALID, "head hook: misaligned operand");
+  const char* why;
+  if (!tail_site_ok(c->drop, c->K, c->rows, false, &why)) return fail(GT_ERR_INVALID, "head hook: %s", why);
+  if (c->drop.mode != DROP_NONE && !c->has_act) return fail(GT_ERR_INVALID, "head hook: a dropout site needs has_act");
+  if (c->dH && c->lddh < c->K) return fail(GT_ERR_INVALID, "head hook: pitch of dH below K");
+  if ((c->dHb || c->dHbT) && !img) return fail(GT_ERR_INVALID, "head hook: bf16 results belong to the image form (h_ld > 0)");
+  if (c->dHb && ((((uintptr_t)c->dHb) & 1) || c->lddhb < c->K)) return fail(GT_ERR_INVALID, "head hook: dHb misaligned or its pitch below K");
+  if (c->dHbT && ((((uintptr_t)c->dHbT) & 7) || c->lddhbt % 4 != 0 || c->lddhbt < c->rows))
+    return fail(GT_ERR_INVALID, "head hook: dHbT needs 8-byte alignment and a pitch >= rows that is a multiple of 4");
+  const bool w = c->want_grad && c->want_w;
+  if (w && (!c->dW || !c->db)) return fail(GT_ERR_INVALID, "head hook: weight gradients need dW and db");
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = d_head_blocks((long)c->rows);
+  TailScratch t;
+  int r = t.init(nblk, c->K, c->has_tv, c->tv, c->dW, c->db, c->accumulate ? 1 : 0, s);
+  int deferred = -1;
+  if (r == GT_OK) {
+    HeadArgs h;
+    memset(&h, 0, sizeof(h));
+    h.c.mode = c->mode; h.c.rows = (long)c->rows; h.c.n_real = (long)c->n_real; h.c.mask = c->mask; h.c.n_mask = (long)c->n_mask; h.c.eps = c->eps;
+    h.c.want_grad = c->want_grad != 0; h.c.want_w = c->want_w != 0; h.c.defer_scalars = c->defer_scalars ? &deferred : nullptr;
+    h.c.tv_dev = c->tv_dev; h.c.unit_tv = c->unit_tv != 0;
+    h.o = t.o;
+    h.H = c->H; h.K = c->K; h.ldh = c->ldh; h.h_ld = c->h_ld; h.has_act = c->has_act != 0; h.spec = tail_site_spec(c->drop);
+    h.w = c->w; h.bias = c->bias; h.Dout = c->Dout; h.dH = c->dH; h.lddh = c->lddh;
+    h.dHb = (__bf16*)c->dHb; h.lddhb = c->lddhb; h.dHbT = (__bf16*)c->dHbT; h.lddhbt = (long)c->lddhbt;
+    r = launch_d_head(h, s);
+  }
+  return t.finish(r, deferred >= 0 ? deferred : nblk, c->scalars, "d_head", s);
+}
+
+extern "C" int gt_op_dstack(const gt_dstack_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
+    return fail(GT_ERR_INVALID, "fused stack hook: %s", why);
+  if (c->L < 1 || c->L > DS_MAXL) return fail(GT_ERR_INVALID, "fused stack hook: L = %d (1 .. %d)", c->L, DS_MAXL);
+  if (!dstack_hidden_ok(c->hidden_dim)) return fail(GT_ERR_INVALID, "fused stack hook: hidden_dim 128 or 256");
+  const int H = c->hidden_dim;
+  const bool g_mode = c->mode == HEAD_G_ADV, grad = c->want_grad != 0;
+  uintptr_t bits = ((uintptr_t)c->H0) | ((uintptr_t)c->w_last) | ((uintptr_t)c->b_last) | ((uintptr_t)c->dZtop) | ((uintptr_t)c->Dout) |
+                   ((uintptr_t)c->dW_last) | ((uintptr_t)c->db_last) | ((uintptr_t)c->W0) | ((uintptr_t)c->gadv);
+  if (!c->H0 || !c->w_last || !c->b_last) return fail(GT_ERR_INVALID, "fused stack hook: needs H0, w_last and b_last");
+  for (int l = 0; l < c->L; ++l) {
+    if (l > 0 && (!c->W[l] || !c->b[l])) return fail(GT_ERR_INVALID, "fused stack hook: layer %d needs W and b", l);
+    bits |= ((uintptr_t)c->W[l]) | ((uintptr_t)c->b[l]) | ((uintptr_t)c->Hout[l]);
+    const char* why;
+    if (!tail_site_ok(c->drop[l], H, c->rows, true, &why)) return fail(GT_ERR_INVALID, "fused stack hook: layer %d: %s", l, why);
+  }
+  if (bits & 3) return fail(GT_ERR_INVALID, "fused stack hook: misaligned float32 operand");
+  if (!g_mode && grad && (!c->dZtop || !c->dW_last || !c->db_last)) return fail(GT_ERR_INVALID, "fused stack hook: the D step's gradients need dZtop, dW_last and db_last");
+  if (g_mode && grad) {
+    if (c->Da < 1 || c->Da > 64) return fail(GT_ERR_INVALID, "fused stack hook: Da = %d (1 .. 64)", c->Da);
+    if (!c->W0 || !c->gadv || c->col0 < 0 || (long)c->col0 + c->Da > c->ldw0 || c->ld_gadv < c->Da)
+      return fail(GT_ERR_INVALID, "fused stack hook: the G step's gradient needs W0 (col0 + Da <= ldw0) and gadv (ld_gadv >= Da)");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = dstack_panels((long)c->rows);
+  TailScratch t;
+  int r = t.init(nblk, H, c->has_tv, c->tv, c->dW_last, c->db_last, c->accumulate ? 1 : 0, s);
+  if (r == GT_OK) {
+    DStackCall k;
+    memset(&k, 0, sizeof(k));
+    k.c.mode = c->mode; k.c.rows = (long)c->rows; k.c.n_real = (long)c->n_real; k.c.mask = c->mask; k.c.n_mask = (long)c->n_mask; k.c.eps = c->eps;
+    k.c.want_grad = grad; k.c.want_w = grad && !g_mode; k.c.tv_dev = c->tv_dev; k.c.unit_tv = c->unit_tv != 0;
+    k.o = t.o; k.hidden_dim = H;
+    DStackArgs& a = k.a;
+    a.L = c->L; a.H0 = c->H0;
+    for (int l = 0; l < c->L; ++l) { a.W[l] = c->W[l]; a.b[l] = c->b[l]; a.drop[l] = tail_site_spec(c->drop[l]); }
+    a.w_last = c->w_last; a.b_last = c->b_last; a.Dout = c->Dout;
+    if (!g_mode) {
+      for (int l = 1; l < c->L; ++l) a.Hout[l] = c->Hout[l];
+      a.dZtop = c->dZtop;
+    } else {
+      a.W0 = c->W0; a.ldw0 = c->ldw0; a.col0 = c->col0; a.Da = c->Da; a.gadv = c->gadv; a.ld_gadv = c->ld_gadv;
+    }
+    r = launch_dstack_pass(k, s);
+  }
+  return t.finish(r, nblk, c->scalars, "dstack", s);
 }
 
 // ------------------------------------------------------------------------------------------

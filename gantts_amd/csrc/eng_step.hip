@@ -1,6 +1,7 @@
 // libgantts_hip.so -- the G+D step: MLPG, MLP stacks, apply_generator / update_discriminator / update_generator (reference train.py:245-355), plain forward
 #include "engine_internal.hip.h"
-#include "dstack_f32.hip.h"
+#include "d_tail_args.hip.h"
+#include <atomic>
 
 using namespace gt;
 // ------------------------------------------------------------------------------------------
@@ -516,32 +517,95 @@ static int build_cat(gt_engine* e, const float* x, const float* feats, int ld_fe
   return GT_OK;
 }
 
-// What the discriminator's head is asked for: shared by the per-layer head (run_head) and the fused stack (run_dstack).  Zero-initialise,
-// then set by name.
-struct HeadCall {
-  int mode;                    // HEAD_D_STEP: rows = natural then generated; HEAD_G_ADV: generated rows only
-  long rows, n_real;
-  const float* mask; long n_mask;
-  float eps;
-  bool want_grad;              // seed the backward pass (phase == "train")
-  bool want_w;                 // ... with weight gradients: d last_linear is reduced from the partials
-  StepResults* early_res;      // the finalising launch also writes the step's results here
-  int* defer_scalars;          // HEAD_G_ADV without weight gradients: the caller reduces the partials; <- their count
-  const double* tv_dev;        // the valid-frame count when it is not in the step's scalars yet
-  unsigned ticket;             // early_res in host memory: the ticket that announces it
-  bool unit_tv;                // seed the backward pass of the UNNORMALISED loss (GT_OPT_COMM_TV_IN_SUMS)
-};
-// the head's per-workgroup partials (e->headp, e->headw: nblk of them) -> the step's scalars and d last_linear
-static int head_finalize(gt_engine* e, const HeadCall& c, int nblk, int K, hipStream_t s) {
-  Net& D = e->net[GT_ROLE_D];
+// ------------------------------------------------------------------------------------------
+// the discriminator's tail: launch functions over plain argument blocks (d_tail_args.hip.h), shared by the engine's wrappers below and the
+// parity hooks gt_op_d_head / gt_op_dstack (eng_ops.hip).  The whole dispatch lives here; the wrappers only fill the blocks from the engine.
+// ------------------------------------------------------------------------------------------
+// gt_head_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
+static std::atomic<int64_t> g_head_paths[GT_HEAD_PATH_SLOTS];
+void head_path_count(int slot) { g_head_paths[slot].fetch_add(1, std::memory_order_relaxed); }
+extern "C" int gt_head_path_counts(int64_t* counts, int reset) {
+  for (int i = 0; i < GT_HEAD_PATH_SLOTS; ++i) {
+    const int64_t v = reset ? g_head_paths[i].exchange(0, std::memory_order_relaxed) : g_head_paths[i].load(std::memory_order_relaxed);
+    if (counts) counts[i] = v;
+  }
+  return GT_OK;
+}
+
+// the pass's per-workgroup partials (o.hp, o.dw_partial: nblk of them) -> the step's scalars and d last_linear
+int launch_head_finalize(const HeadCall& c, const HeadSums& o, int nblk, int K, hipStream_t s) {
   const bool w = c.want_grad && c.want_w;
   if (c.defer_scalars && !w) { *c.defer_scalars = nblk; return GT_OK; }
+  if (nblk > o.hp_cap || (w && (long)nblk * K > o.dw_cap)) return fail(GT_ERR_INVALID, "discriminator head: partial buffers too small for %d workgroups", nblk);
   const int cgw = (w && nblk >= 512) ? 16 : 64;       // many rows of partials: narrower column groups, more workgroups (frame_kernels.hip.h)
   const int n_dw = cdiv(K, cgw), extra = cgw == 16 ? 1 : 0;       // (with many partials the scalars get a workgroup of their own, beside the dw ones)
-  hipLaunchKernelGGL(d_head_finalize_kernel, dim3(n_dw + extra), dim3(1024), 0, s, e->headp.as<HeadPartials>(), e->headw.as<float>(),
-                     nblk, K, c.mode, e->sc(), w ? D.last.dW : (float*)nullptr, w ? D.last.db : (float*)nullptr, D.grads_dirty ? 1 : 0,
-                     c.early_res, c.ticket ? e->ticket_dev() : (unsigned*)nullptr, c.ticket, cgw, extra ? n_dw : 0);
+  hipLaunchKernelGGL(d_head_finalize_kernel, dim3(n_dw + extra), dim3(1024), 0, s, o.hp, o.dw_partial, nblk, K, c.mode, o.sc,
+                     w ? o.dW : (float*)nullptr, w ? o.db : (float*)nullptr, o.accumulate, c.early_res,
+                     c.ticket ? o.ticket_dev : (unsigned*)nullptr, c.ticket, cgw, extra ? n_dw : 0);
   LAUNCH_CHECK();
+  head_path_count(cgw == 16 ? HEAD_PATH_FINALIZE16 : HEAD_PATH_FINALIZE64);
+  return GT_OK;
+}
+
+// c.mode HEAD_D_STEP (DSTACK_D_STEP): rows = 2N (natural then generated), writes the stashes a.Hout[1 ..], the seed gradient a.dZtop and the
+// head's partials, then finalises them (as launch_d_head does).  HEAD_G_ADV (DSTACK_G_ADV): rows = N, writes a.gadv (want_grad) and the partials.
+int launch_dstack_pass(const DStackCall& k, hipStream_t s) {
+  const HeadCall& c = k.c;
+  const int H = k.hidden_dim;
+  const bool d_step = c.mode == HEAD_D_STEP;
+  const int nblk = dstack_panels(c.rows);
+  if (nblk > k.o.hp_cap || (d_step && c.want_grad && (long)nblk * H > k.o.dw_cap))
+    return fail(GT_ERR_INVALID, "fused discriminator stack: partial buffers too small for %d panels", nblk);
+  DStackArgs a = k.a;
+  a.mode = d_step ? DSTACK_D_STEP : DSTACK_G_ADV; a.rows = (int)c.rows; a.n_real = (int)c.n_real;
+  for (int l = 0; l < a.L && l < DS_MAXL; ++l)
+    if (a.drop[l].mode == DROP_BUFFER && a.drop[l].ld_mask != H) return fail(GT_ERR_INVALID, "injected dropout mask pitch");
+  a.mask = c.mask; a.n_mask = (int)c.n_mask; a.eps = c.eps; a.unit_tv = c.unit_tv ? 1 : 0; a.tv_dev = c.tv_dev;
+  a.sc = k.o.sc; a.want_grad = c.want_grad ? 1 : 0; a.hp = k.o.hp;
+  a.dw_partial = (d_step && c.want_grad) ? k.o.dw_partial : (float*)nullptr;
+  if (!d_step && c.want_grad && !a.gadv) return fail(GT_ERR_INVALID, "fused discriminator stack: no gradient buffer");
+  CHK(launch_dstack(a, H, s));
+  return launch_head_finalize(c, k.o, nblk, H, s);
+}
+
+template <int KP, typename TH, bool IMG, bool VEC = false>
+static void head_launch(const HeadArgs& a, int nblk, hipStream_t s) {
+  const HeadCall& c = a.c;
+  hipLaunchKernelGGL((d_head_kernel<KP, TH, IMG, VEC>), dim3(nblk), dim3(256), (size_t)4 * a.K * sizeof(float), s, (const TH*)a.H, IMG ? a.h_ld : a.ldh, a.K,
+                     a.w, a.bias, c.mask, (int)c.n_mask, (int)c.n_real, (int)c.rows, c.mode, c.eps, a.Dout, a.dH, a.lddh,
+                     c.want_grad ? 1 : 0, a.spec, a.has_act ? 1 : 0, a.o.sc, a.o.hp, a.o.dw_partial,
+                     IMG ? a.dHb : (__bf16*)nullptr, IMG ? a.lddhb : 0, IMG ? a.dHbT : (__bf16*)nullptr, IMG ? a.lddhbt : 0L, c.tv_dev, c.unit_tv ? 1 : 0);
+  constexpr int kp = KP == 2 ? 0 : KP == 4 ? 1 : KP == 8 ? 2 : 3;
+  head_path_count(IMG ? HEAD_PATH_IMG + kp : VEC ? HEAD_PATH_VEC + kp - 1 : HEAD_PATH_F32 + kp);
+}
+template <int KP>
+static void head_launch_k(const HeadArgs& a, int nblk, hipStream_t s) {
+  if (a.h_ld > 0) head_launch<KP, __bf16, true>(a, nblk, s);
+  else if (KP % 4 == 0 && gt_tuning().head_vec) head_launch<(KP % 4 == 0 ? KP : 4), float, false, true>(a, nblk, s);
+  else head_launch<KP, float, false>(a, nblk, s);
+}
+int launch_d_head(const HeadArgs& a, hipStream_t s) {
+  const int nblk = d_head_blocks(a.c.rows);
+  if (nblk > a.o.hp_cap || (long)nblk * a.K > a.o.dw_cap) return fail(GT_ERR_INVALID, "discriminator head: partial buffers too small for %d workgroups", nblk);
+  if (a.K <= 128) head_launch_k<2>(a, nblk, s);
+  else if (a.K <= 256) head_launch_k<4>(a, nblk, s);
+  else if (a.K <= 512) head_launch_k<8>(a, nblk, s);
+  else if (a.K <= 1024) head_launch_k<16>(a, nblk, s);
+  else return fail(GT_ERR_INVALID, "discriminator hidden_dim > 1024 is not supported by the fused head kernel");
+  LAUNCH_CHECK();
+  return launch_head_finalize(a.c, a.o, nblk, a.K, s);
+}
+
+// the engine's partial buffers (grown to `nblk` workgroups of K columns) and where their sums go
+static int head_sums(gt_engine* e, int nblk, int K, bool dw, HeadSums* o) {
+  Net& D = e->net[GT_ROLE_D];
+  CHK(e->headp.ensure((size_t)nblk * sizeof(HeadPartials)));
+  if (dw) CHK(e->headw.ensure((size_t)nblk * K * sizeof(float)));
+  o->sc = e->sc();
+  o->hp = e->headp.as<HeadPartials>(); o->hp_cap = (long)(e->headp.bytes / sizeof(HeadPartials));
+  o->dw_partial = e->headw.as<float>(); o->dw_cap = (long)(e->headw.bytes / sizeof(float));
+  o->dW = D.last.dW; o->db = D.last.db; o->accumulate = D.grads_dirty ? 1 : 0;
+  o->ticket_dev = e->ticket_dev();
   return GT_OK;
 }
 
@@ -561,35 +625,28 @@ static bool d_fused_ok(gt_engine* e, long rows) {
     if (D.hidden[l].out != D.d.hidden_dim || (l > 0 && D.hidden[l].in != D.d.hidden_dim)) return false;
   return true;
 }
-// c.mode HEAD_D_STEP (DSTACK_D_STEP): rows = 2N (natural then generated), writes the stashes e->d_act[1 ..], the seed gradient e->dzA and the
-// head's partials, then finalises them (as run_head does).  HEAD_G_ADV (DSTACK_G_ADV): rows = N, writes gadv (want_grad) and the partials.
+// the fused pass over the engine's discriminator (launch_dstack_pass): the stashes go to e->d_act[1 ..], the seed gradient to e->dzA
 static int run_dstack(gt_engine* e, const HeadCall& c, float* gadv, hipStream_t s) {
   Net& D = e->net[GT_ROLE_D];
   const int H = D.d.hidden_dim, L = (int)D.hidden.size();
   const bool d_step = c.mode == HEAD_D_STEP;
-  const int nblk = dstack_panels(c.rows);
-  CHK(e->headp.ensure((size_t)nblk * sizeof(HeadPartials)));
+  DStackCall k;
+  memset(&k, 0, sizeof(k));
+  k.c = c; k.hidden_dim = H;
+  CHK(head_sums(e, dstack_panels(c.rows), H, d_step && c.want_grad, &k.o));
   CHK(e->dout.ensure((size_t)c.rows * sizeof(float)));
-  DStackArgs a;
-  memset(&a, 0, sizeof(a));
-  a.mode = d_step ? DSTACK_D_STEP : DSTACK_G_ADV; a.L = L; a.rows = (int)c.rows; a.n_real = (int)c.n_real;
+  DStackArgs& a = k.a;
+  a.L = L;
   a.H0 = e->d_act[0].as<float>();
-  for (int l = 0; l < L; ++l) {
-    a.W[l] = D.hidden[l].W; a.b[l] = D.hidden[l].b; a.drop[l] = e->d_specs[l];
-    if (a.drop[l].mode == DROP_BUFFER && a.drop[l].ld_mask != H) return fail(GT_ERR_INVALID, "injected dropout mask pitch");
-  }
-  a.w_last = D.last.W; a.b_last = D.last.b; a.mask = c.mask; a.n_mask = (int)c.n_mask; a.eps = c.eps; a.unit_tv = c.unit_tv ? 1 : 0; a.tv_dev = c.tv_dev;
-  a.sc = e->sc(); a.want_grad = c.want_grad ? 1 : 0; a.Dout = e->dout.as<float>(); a.hp = e->headp.as<HeadPartials>();
+  for (int l = 0; l < L; ++l) { a.W[l] = D.hidden[l].W; a.b[l] = D.hidden[l].b; a.drop[l] = e->d_specs[l]; }
+  a.w_last = D.last.W; a.b_last = D.last.b; a.Dout = e->dout.as<float>();
   if (d_step) {
     for (int l = 1; l + 1 < L; ++l) a.Hout[l] = e->d_act[l].as<float>();      // (the top layer's activation only feeds the head, which is fused: no stash)
     a.dZtop = e->dzA.as<float>();
-    if (c.want_grad) { CHK(e->headw.ensure((size_t)nblk * H * sizeof(float))); a.dw_partial = e->headw.as<float>(); }
   } else {
     a.W0 = D.hidden[0].W; a.ldw0 = D.hidden[0].in; a.col0 = cond_dim(e); a.Da = e->Da; a.gadv = gadv; a.ld_gadv = e->Da;
-    if (c.want_grad && !gadv) return fail(GT_ERR_INVALID, "fused discriminator stack: no gradient buffer");
   }
-  CHK(launch_dstack(a, H, s));
-  return head_finalize(e, c, nblk, H, s);
+  return launch_dstack_pass(k, s);
 }
 
 // what the per-layer head reads and where its seed gradient goes
@@ -601,33 +658,20 @@ struct HeadAct {
   float* dH;                   // float32 seed gradient, or
   B16Img* dz_img; bool dz_t;   // (bf16 storage) the top dZ image, transposed twin too when dz_t
 };
-template <int KP, typename TH, bool IMG, bool VEC = false>
-static void head_launch(gt_engine* e, const HeadCall& c, const HeadAct& a, int nblk, hipStream_t s) {
-  Net& D = e->net[GT_ROLE_D];
-  B16Img* z = IMG ? a.dz_img : nullptr;
-  hipLaunchKernelGGL((d_head_kernel<KP, TH, IMG, VEC>), dim3(nblk), dim3(256), (size_t)4 * a.K * sizeof(float), s, (const TH*)a.H, IMG ? a.h_ld : a.K, a.K,
-                     D.last.W, D.last.b, c.mask, (int)c.n_mask, (int)c.n_real, (int)c.rows, c.mode, c.eps, e->dout.as<float>(), z ? (float*)nullptr : a.dH, a.K,
-                     c.want_grad ? 1 : 0, a.spec, a.has_act ? 1 : 0, e->sc(), e->headp.as<HeadPartials>(), e->headw.as<float>(),
-                     z ? z->r() : (__bf16*)nullptr, z ? z->ld : 0, (z && a.dz_t) ? z->t() : (__bf16*)nullptr, z ? z->ldt : 0L, c.tv_dev, c.unit_tv ? 1 : 0);
-}
-template <int KP>
-static void head_launch_k(gt_engine* e, const HeadCall& c, const HeadAct& a, int nblk, hipStream_t s) {
-  if (a.h_ld > 0) head_launch<KP, __bf16, true>(e, c, a, nblk, s);
-  else if (KP % 4 == 0 && gt_tuning().head_vec) head_launch<(KP % 4 == 0 ? KP : 4), float, false, true>(e, c, a, nblk, s);
-  else head_launch<KP, float, false>(e, c, a, nblk, s);
-}
+// the per-layer head over the engine's discriminator (launch_d_head)
 static int run_head(gt_engine* e, const HeadCall& c, const HeadAct& a, hipStream_t s) {
-  const int nblk = (int)std::min<long>(1024, (c.rows + 31) / 32);
-  CHK(e->headp.ensure((size_t)nblk * sizeof(HeadPartials)));
-  CHK(e->headw.ensure((size_t)nblk * a.K * sizeof(float)));
+  Net& D = e->net[GT_ROLE_D];
+  HeadArgs h;
+  memset(&h, 0, sizeof(h));
+  h.c = c;
+  CHK(head_sums(e, d_head_blocks(c.rows), a.K, true, &h.o));
   CHK(e->dout.ensure((size_t)c.rows * sizeof(float)));
-  if (a.K <= 128) head_launch_k<2>(e, c, a, nblk, s);
-  else if (a.K <= 256) head_launch_k<4>(e, c, a, nblk, s);
-  else if (a.K <= 512) head_launch_k<8>(e, c, a, nblk, s);
-  else if (a.K <= 1024) head_launch_k<16>(e, c, a, nblk, s);
-  else return fail(GT_ERR_INVALID, "discriminator hidden_dim > 1024 is not supported by the fused head kernel");
-  LAUNCH_CHECK();
-  return head_finalize(e, c, nblk, a.K, s);
+  B16Img* z = a.h_ld > 0 ? a.dz_img : nullptr;
+  h.H = a.H; h.K = a.K; h.ldh = a.K; h.h_ld = a.h_ld; h.has_act = a.has_act; h.spec = a.spec;
+  h.w = D.last.W; h.bias = D.last.b; h.Dout = e->dout.as<float>();
+  h.dH = z ? (float*)nullptr : a.dH; h.lddh = a.K;
+  if (z) { h.dHb = z->r(); h.lddhb = z->ld; if (a.dz_t) { h.dHbT = z->t(); h.lddhbt = z->ldt; } }
+  return launch_d_head(h, s);
 }
 
 static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t s) {

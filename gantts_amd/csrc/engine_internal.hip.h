@@ -391,6 +391,17 @@ namespace gt { struct DStackArgs; }
 bool dstack_hidden_ok(int hidden_dim);
 int dstack_panels(long rows);
 int launch_dstack(const gt::DStackArgs& a, int hidden_dim, hipStream_t s);
+// gt_head_path_counts: launches of the discriminator's tail by kernel, counted on the host where they are issued (slot layout in
+// gantts_hip.h).  launch_d_head / launch_dstack_pass / launch_head_finalize (eng_step.hip, d_tail_args.hip.h): the one launch site of each
+// kernel, shared by the engine's run_head / run_dstack and the parity hooks (eng_ops.hip).
+enum { HEAD_PATH_F32 = 0, HEAD_PATH_VEC = 4, HEAD_PATH_IMG = 7, HEAD_PATH_DSTACK128 = 11, HEAD_PATH_DSTACK256 = 12, HEAD_PATH_FINALIZE64 = 13,
+       HEAD_PATH_FINALIZE16 = 14 };
+static_assert(HEAD_PATH_FINALIZE16 + 1 == GT_HEAD_PATH_SLOTS, "gt_head_path_counts slots");
+void head_path_count(int slot);
+namespace gt { struct HeadCall; struct HeadSums; struct HeadArgs; struct DStackCall; }
+int launch_head_finalize(const gt::HeadCall& c, const gt::HeadSums& o, int nblk, int K, hipStream_t s);
+int launch_d_head(const gt::HeadArgs& a, hipStream_t s);
+int launch_dstack_pass(const gt::DStackCall& k, hipStream_t s);
 gt::DropoutSpec no_drop();
 int launch_gemm(int kind, const gt::GemmArgs& g, int nslab, hipStream_t s);
 int linear_forward(const float* X, int ldx, const float* W, int ldw, const float* b, float* Y, int ldy,

@@ -719,6 +719,103 @@ int gt_op_sru_input_mask(float* mul, int B, int n, float p, uint32_t key0, uint3
                          void* stream);
 int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ldy, int B, int T, int n, const float* mul, void* stream);
 
+/* Launches of the discriminator's tail (frame_kernels.hip.h: d_head_kernel, d_head_finalize_kernel; dstack_f32.hip.h: dstack_kernel) by
+ * kernel, process-wide, counted on the host where each launch is issued (no device work, no synchronisation).  Slots:
+ *   0..3     d_head_kernel<KP, float>, 4-byte accesses:        log2(KP) - 1, KP = 2, 4, 8, 16   (K <= 64 KP)
+ *   4..6     d_head_kernel<KP, float, false, VEC>, head_vec:   4 + log2(KP) - 2, KP = 4, 8, 16
+ *   7..10    d_head_kernel<KP, bf16, B16OUT>, the image form:  7 + log2(KP) - 1, KP = 2, 4, 8, 16
+ *   11, 12   dstack_kernel<128>, dstack_kernel<256>
+ *   13, 14   d_head_finalize_kernel with 64 / with 16 columns per workgroup (the latter with the extra scalar workgroup)
+ * Copies the GT_HEAD_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
+#define GT_HEAD_PATH_SLOTS 15
+int gt_head_path_counts(int64_t* counts, int reset);
+
+/* One dropout site of the tail hooks: mode 0 none, 1 the Philox keep bits of (key0, key1) at drop probability p, 2 the 0 / 1 float
+ * `mask` [rows][ld_mask] (p still gives the scale 1 / (1 - p)).  dp_*: the data-parallel row-group map of the Philox counter
+ * (dp_t16 == 0: identity), the fields of the same name of the engine's dropout sites: dp_t16 = T / 16, dp_nl16 = 16-row groups per half
+ * (0xffffffff: one block of rows), dp_half = B_global T / 16 - dp_nl16, dp_add = rank T / 16, dp_mul = (world - 1) T / 16,
+ * dp_inv_t16 = 1 / dp_t16. */
+typedef struct gt_drop_site {
+  int32_t mode;
+  float p;
+  uint32_t key0, key1;
+  uint32_t dp_t16, dp_nl16, dp_half, dp_add, dp_mul;
+  float dp_inv_t16;
+  int32_t ld_mask, pad_;
+  const float* mask;
+} gt_drop_site;
+
+/* Parity hook of the discriminator's per-layer head: ONE head pass plus its finalising launch through the launch function the engine
+ * uses (launch_d_head), so the kernel form follows from K (KP), h_ld (> 0: the bf16 image form) and the tuning knob head_vec exactly as
+ * in a step.  All pointers but `scalars` are the caller's device buffers.
+ *   reads    H: float32 [rows][ldh], or (h_ld > 0) raw 16-bit bf16 [rows][h_ld]; w [K], bias [1]; mask [n_mask], row r -> mask[r % n_mask];
+ *            mode 0 (D step): rows [0, n_real) natural, the rest generated; mode 1 (adversarial term): every row scored as natural.
+ *            has_act: H is LeakyReLU + dropout (site `drop`) of a pre-activation, and dH carries its derivative.
+ *   normaliser, exactly one of: has_tv (the hook puts tv and 1 / tv into its scratch scalars), tv_dev (a device double the kernel reads
+ *            and copies into the scalars), unit_tv (1)
+ *   writes   Dout [rows] or null; with want_grad dH [rows][lddh] (float32), and in the image form dHb [rows][lddhb] / dHbT [K][lddhbt]
+ *            (raw 16-bit, either null; dHbT 8-byte aligned, lddhbt % 4 == 0); with want_grad && want_w dW [K] and db [1] (+= if
+ *            accumulate).  defer_scalars: the finalising launch is left to the caller (as the generator step's riders do) unless
+ *            weight gradients are wanted.
+ *   scalars  host, 8 doubles or null, filled after the stream is synchronised: s_real, s_fake, n_real_ok, n_fake_ok, s_adv, tv, inv_tv
+ *            as the scratch scalars hold them (what no launch wrote stays NaN), and the number of partials (workgroups of the pass).
+ * The partial buffers are scratch of the call, filled with NaN first.  A malformed case returns GT_ERR_INVALID before any launch. */
+typedef struct gt_d_head_case {
+  int32_t mode, K, ldh, h_ld;
+  int32_t has_act, want_grad, want_w, defer_scalars;
+  int32_t accumulate, unit_tv, has_tv, lddh;
+  int32_t lddhb, pad_;
+  float eps, tv;
+  int64_t rows, n_real, n_mask, lddhbt;
+  gt_drop_site drop;
+  const void* H;
+  const float* w;
+  const float* bias;
+  const float* mask;
+  const double* tv_dev;
+  float* Dout;
+  float* dH;
+  uint16_t* dHb;
+  uint16_t* dHbT;
+  float* dW;
+  float* db;
+  double* scalars;
+} gt_d_head_case;
+int gt_op_d_head(const gt_d_head_case* c, void* stream);
+
+/* Parity hook of the fused discriminator stack: ONE fused pass plus its finalising launch through launch_dstack_pass.  hidden_dim 128 or
+ * 256, L = 1 .. 4 hidden layers of which layer 0's OUTPUT H0 [rows][hidden_dim] (dropout applied) is the input; W[l] [hidden][hidden],
+ * b[l] for l = 1 .. L-1; drop[l] the dropout site of layer l = 0 .. L-1 (an injected mask has pitch hidden_dim); w_last [hidden],
+ * b_last [1]; mask, n_real, eps, the normaliser and `scalars` as in gt_d_head_case.
+ *   mode 0 (D step)  writes Hout[l] [rows][hidden] for every l = 1 .. L-1 that is given, Dout [rows] or null, and with want_grad dZtop
+ *                    [rows][hidden], dW_last [hidden], db_last [1] (+= if accumulate)
+ *   mode 1 (G step)  writes Dout and with want_grad gadv [rows][ld_gadv] = dZ_0 . W0[:, col0 .. col0 + Da), W0 [hidden][ldw0], Da 1 .. 64
+ * A malformed case returns GT_ERR_INVALID before any launch. */
+typedef struct gt_dstack_case {
+  int32_t mode, L, hidden_dim, want_grad;
+  int32_t accumulate, unit_tv, has_tv, ldw0;
+  int32_t col0, Da, ld_gadv, pad_;
+  float eps, tv;
+  int64_t rows, n_real, n_mask;
+  gt_drop_site drop[4];
+  const float* H0;
+  const float* W[4];
+  const float* b[4];
+  const float* w_last;
+  const float* b_last;
+  const float* mask;
+  const double* tv_dev;
+  float* Hout[4];
+  float* dZtop;
+  float* Dout;
+  float* dW_last;
+  float* db_last;
+  const float* W0;
+  float* gadv;
+  double* scalars;
+} gt_dstack_case;
+int gt_op_dstack(const gt_dstack_case* c, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

@@ -47,6 +47,12 @@ def test_ctypes_structs_match_header_layout():
     assert _lib.CastCase.jobs.offset == 144 and C.sizeof(_lib.CastCase) == 144 + 8 * 56
     assert _lib.SruScanCase.keep_scale.offset == 32 and _lib.SruScanCase.ldu.offset == 56 and _lib.SruScanCase.ld_nxbt.offset == 80
     assert _lib.SruScanCase.U.offset == 96 and _lib.SruScanCase.dU_bt.offset == 224 and C.sizeof(_lib.SruScanCase) == 232
+    assert C.sizeof(_lib.DropSite) == 56 and _lib.DropSite.dp_inv_t16.offset == 36 and _lib.DropSite.mask.offset == 48
+    assert _lib.DHeadCase.eps.offset == 56 and _lib.DHeadCase.rows.offset == 64 and _lib.DHeadCase.drop.offset == 96
+    assert _lib.DHeadCase.H.offset == 152 and _lib.DHeadCase.scalars.offset == 240 and C.sizeof(_lib.DHeadCase) == 248
+    assert _lib.DStackCase.eps.offset == 48 and _lib.DStackCase.rows.offset == 56 and _lib.DStackCase.drop.offset == 80
+    assert _lib.DStackCase.H0.offset == 304 and _lib.DStackCase.W.offset == 312 and _lib.DStackCase.Hout.offset == 408
+    assert _lib.DStackCase.gadv.offset == 480 and _lib.DStackCase.scalars.offset == 488 and C.sizeof(_lib.DStackCase) == 496
 
 
 def test_invalid_arguments_are_reported_not_crashing():
