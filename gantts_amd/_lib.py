@@ -146,6 +146,12 @@ class DStackCase(C.Structure):
                 + [("scalars", C.POINTER(C.c_double))])
 
 
+class MlpgCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("backward", "B", "T", "Ds", "ldy", "ldys", "ldgs", "ldgy", "ldt")] + [("mse_w", C.c_float)]
+                + [(n, C.c_void_p) for n in ("e", "R", "scol", "sstride", "y", "ys", "gs", "gy", "yhat", "ytgt", "mask")]
+                + [("kb", C.POINTER(C.c_int32))])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -209,6 +215,7 @@ SIGNATURES = {
     "gt_head_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_d_head": (_I, [C.POINTER(DHeadCase), _P]),
     "gt_op_dstack": (_I, [C.POINTER(DStackCase), _P]),
+    "gt_op_mlpg": (_I, [C.POINTER(MlpgCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -123,6 +123,66 @@ extern "C" int gt_op_mlpg_backward(gt_engine* e, const float* g_static, const fl
   return mlpg_backward(e, g_static, e->Ds, e->d_scol, e->d_sstride, e->Ds, g_y, e->Dout_cfg, B, T, 0.f, nullptr, nullptr, 0, nullptr, s);
 }
 
+// One MLPG launch with the step's freedom in the arguments (column maps, pitches, the fused masked-MSE gradient) through ensure_band and
+// mlpg_forward / mlpg_backward: parity hook of tests/test_gpu_mlpg.py.  Everything a kernel would index with is checked first.
+static_assert(offsetof(gt_mlpg_case, e) == 40 && offsetof(gt_mlpg_case, kb) == 128 && sizeof(gt_mlpg_case) == 136, "layout bound by gantts_amd/_lib.py");
+extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  gt_engine* e = c->e;
+  CHK(check_common(e, c->B, c->T));
+  const bool bwd = c->backward != 0, own = !c->scol && !c->sstride, mse = bwd && c->mse_w != 0.f;
+  if (c->backward != 0 && c->backward != 1) return fail(GT_ERR_INVALID, "MLPG hook: backward is 0 or 1");
+  if (!c->R) return fail(GT_ERR_INVALID, "MLPG hook: null R");
+  if (!own && (!c->scol || !c->sstride)) return fail(GT_ERR_INVALID, "MLPG hook: scol and sstride come together");
+  if (own && c->Ds != 0 && c->Ds != e->Ds) return fail(GT_ERR_INVALID, "MLPG hook: Ds = %d with the engine's maps (%d)", c->Ds, e->Ds);
+  const int Ds = own ? e->Ds : c->Ds;
+  if (Ds < 1 || Ds > (1 << 20)) return fail(GT_ERR_INVALID, "MLPG hook: Ds = %d", Ds);
+  if (bwd ? (!c->gs || !c->gy) : (!c->y || !c->ys)) return fail(GT_ERR_INVALID, "MLPG hook: null tensor");
+  if (mse && (!c->yhat || !c->ytgt || !c->mask)) return fail(GT_ERR_INVALID, "MLPG hook: the masked-MSE gradient needs yhat, ytgt and mask");
+  for (const void* q : {(const void*)c->R, (const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->ys, (const void*)c->gs,
+                        (const void*)c->gy, (const void*)c->yhat, (const void*)c->ytgt, (const void*)c->mask})
+    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "MLPG hook: misaligned operand");
+  if (bwd ? c->ldgs < Ds : c->ldys < Ds) return fail(GT_ERR_INVALID, "MLPG hook: pitch of the static side below Ds = %d", Ds);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h_scol, h_sstride;
+  if (own) { h_scol = e->h_scol; h_sstride = e->h_sstride; }
+  else {
+    h_scol.resize(Ds); h_sstride.resize(Ds);
+    HIPCHK(hipMemcpyAsync(h_scol.data(), c->scol, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_sstride.data(), c->sstride, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  const int nW = e->cfg.num_windows;
+  const long ld_full = bwd ? c->ldgy : c->ldy;
+  for (int i = 0; i < Ds; ++i) {
+    const long col = h_scol[i], st = h_sstride[i];
+    if (col < 0 || st < 0) return fail(GT_ERR_INVALID, "MLPG hook: negative entry in the column maps at %d", i);
+    const long last = col + (long)(nW - 1) * st;      // pass-through (st == 0): its own column only
+    if (last >= ld_full) return fail(GT_ERR_INVALID, "MLPG hook: static column %d reaches column %ld, the pitch is %ld", i, last, ld_full);
+    if (mse && last >= c->ldt) return fail(GT_ERR_INVALID, "MLPG hook: static column %d reaches column %ld, ldt is %d", i, last, c->ldt);
+  }
+  CHK(ensure_band(e, c->R, c->T, s));
+  if (c->kb) *c->kb = e->mlpg.cur->kb;
+  const int* scol = own ? e->d_scol : (const int*)c->scol;
+  const int* sstride = own ? e->d_sstride : (const int*)c->sstride;
+  int r;
+  if (!bwd) {
+    r = mlpg_forward(e, c->y, c->ldy, scol, sstride, Ds, c->ys, c->ldys, c->B, c->T, s);
+  } else {
+    if (mse) {      // sum(mask) and its reciprocal, as ensure_tv puts them there; the step's memo of it no longer holds
+      hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, c->mask, c->B * c->T, -1.f, (const double*)nullptr, e->sc());
+      LAUNCH_CHECK();
+      e->tv_mask = nullptr; e->tv_n = 0;
+    }
+    r = mlpg_backward(e, c->gs, c->ldgs, scol, sstride, Ds, c->gy, c->ldgy, c->B, c->T, mse ? c->mse_w : 0.f, mse ? c->yhat : nullptr,
+                      mse ? c->ytgt : nullptr, mse ? c->ldt : 0, mse ? c->mask : nullptr, s);
+  }
+  const hipError_t err = hipStreamSynchronize(s);
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "mlpg: %s", hipGetErrorString(err));
+  return GT_OK;
+}
+
 static DropoutSpec buffer_spec(const float* keep_mask, float p, int ld) {
   DropoutSpec d = no_drop();
   if (keep_mask && p > 0.f) { d.mode = DROP_BUFFER; d.mask = keep_mask; d.ld_mask = ld; d.p = p; d.scale = 1.f / (1.f - p); }

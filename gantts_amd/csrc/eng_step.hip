@@ -21,8 +21,9 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s) {
   HIPCHK(hipMemcpyAsync(off.data(), m.tmp.p, off.size() * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   float peak = 0.f;
-  for (float v : off) peak = fmaxf(peak, v);
-  if (!(peak > 0.f) || !isfinite(peak)) return fail(GT_ERR_INVALID, "MLPG matrix R is empty or not finite");
+  bool has_nan = false;
+  for (float v : off) { has_nan |= v != v; peak = fmaxf(peak, v); }      // fmaxf drops a NaN: counted apart
+  if (has_nan || !(peak > 0.f) || !isfinite(peak)) return fail(GT_ERR_INVALID, "MLPG matrix R is empty or not finite");
   int kb = 0;
   for (int o = -(T - 1); o <= T - 1; ++o)
     if (off[o + T - 1] > 1e-9f * peak) kb = std::max(kb, abs(o));
@@ -60,12 +61,38 @@ extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
 // 512 frames), at (16 + 2 kb) / 16 staged rows per output frame.  (64-frame tiles -- half the halo re-reads, one workgroup per CU instead of two --
 // measured no gain in round 4, 1.404 / 1.398 vs 1.393 / 1.398 ms, and left the library in round 6.)
 static int mlpg_tile_frames() { return gt_tuning().mlpg_tt == 16 ? 16 : 32; }
+// ensure_band accepts half-widths up to 63, and both kernels stage (tile + 2 kb) rows: a slowly decaying R asks for more dynamic LDS than a
+// workgroup can have (nW = 4, kb = 39: 156 160 bytes forward, 177 760 transposed, of 160 KiB).  Checked here, per launcher and before anything
+// is launched or any function attribute is raised, so that a window set whose forward fits still serves inference.  The limit is the
+// device's own figure, read once per device.
+static int mlpg_lds_fits(const char* which, int kb, int nW, int tt, size_t lds) {
+  static std::mutex mu;
+  static std::map<int, size_t> limits;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  size_t limit;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = limits.find(dev);
+    if (it == limits.end()) {
+      int v = 0;
+      HIPCHK(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+      it = limits.emplace(dev, (size_t)v).first;
+    }
+    limit = it->second;
+  }
+  if (lds > limit)
+    return fail(GT_ERR_INVALID, "MLPG %s: half-width %d with %d windows needs %zu bytes of LDS per %d-frame tile, the device allows %zu: "
+                "this window set's R = (W^T W)^-1 W^T decays too slowly for the banded kernels", which, kb, nW, lds, tt, limit);
+  return GT_OK;
+}
 int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const int* sstride, int Ds,
                  float* ys, int ldys, int B, int T, hipStream_t s) {
   const int nW = e->cfg.num_windows, kb = e->mlpg.cur->kb;
   auto lds_of = [&](int tt) { return ((size_t)(tt + 2 * kb) * nW * MLPG_CC + (size_t)tt * nW * (2 * kb + 1 + 2 * MLPG_PAD)) * sizeof(float); };
   const int tt = mlpg_tile_frames();
   const size_t lds = lds_of(tt);
+  CHK(mlpg_lds_fits("forward", kb, nW, tt, lds));
   dim3 grid(B * cdiv(T, tt), cdiv(Ds, MLPG_CC));
   const int fpl = gt_tuning().mlpg_fpl;   // frames per lane of the compute phase: 2 measured best (round 4: 4: 24.7 us, 2: 21.8, 1: 26.6; round 5, unrolled tap loops: forward 18.5 / 17.2 / 18.3, backward 24.9 / 19.5 / 20.6)
 #define GT_MLPG_FWD(F, TTV) { CHK(ensure_dyn_lds((const void*)mlpg_forward_kernel<F, TTV>, lds)); \
@@ -83,6 +110,7 @@ int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, cons
   auto lds_of = [&](int tt) { return ((size_t)(tt + 2 * kb) * MLPG_CC + (size_t)(tt + 2 * kb) * nW * (2 * kb + 1 + 2 * MLPG_PAD)) * sizeof(float); };
   const int tt = mlpg_tile_frames();
   const size_t lds = lds_of(tt);
+  CHK(mlpg_lds_fits("transpose", kb, nW, tt, lds));
   dim3 grid(B * cdiv(T, tt), cdiv(Ds, MLPG_CC));
   const int fpl = gt_tuning().mlpg_fpl;
 #define GT_MLPG_BWD(F, TTV) { CHK(ensure_dyn_lds((const void*)mlpg_backward_kernel<F, TTV>, lds)); \

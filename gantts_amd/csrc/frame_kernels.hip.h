@@ -294,7 +294,9 @@ static __global__ void pad_rows_kernel(const float* __restrict__ in, int cols, i
 // banded; the engine extracts band[t][w][j] = R[t][w*T + t + j - kb] from the caller's dense R
 // and verifies that everything outside the band is negligible before using the O(T*kb) form.
 // ---------------------------------------------------------------------------------------
-// per-offset max |R[t][w*T + t + o]| , o in [-(T-1), T-1]  ->  offmax[o + T - 1]
+// max that keeps a NaN once it has seen one (fmaxf returns the other operand): a NaN in R must reach ensure_band's finiteness check
+__device__ __forceinline__ float max_or_nan(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
+// per-offset max |R[t][w*T + t + o]| , o in [-(T-1), T-1]  ->  offmax[o + T - 1]; NaN if any of them is
 static __global__ void mlpg_offset_max_kernel(const float* __restrict__ R, int T, int nW, float* __restrict__ offmax) {
   const int o = blockIdx.x - (T - 1);
   __shared__ float sh[16];
@@ -302,15 +304,15 @@ static __global__ void mlpg_offset_max_kernel(const float* __restrict__ R, int T
   for (int i = threadIdx.x; i < T * nW; i += blockDim.x) {
     const int w = i / T, t = i - w * T;
     const int tt = t + o;
-    if (tt >= 0 && tt < T) mx = fmaxf(mx, fabsf(R[(long)t * nW * T + (long)w * T + tt]));
+    if (tt >= 0 && tt < T) mx = max_or_nan(mx, fabsf(R[(long)t * nW * T + (long)w * T + tt]));
   }
 #pragma unroll
-  for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+  for (int s = 32; s > 0; s >>= 1) mx = max_or_nan(mx, __shfl_xor(mx, s, 64));
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0) sh[wv] = mx;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, sh[i]);
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = max_or_nan(mx, sh[i]);
     offmax[blockIdx.x] = mx;
   }
 }

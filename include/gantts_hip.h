@@ -816,6 +816,39 @@ typedef struct gt_dstack_case {
 } gt_dstack_case;
 int gt_op_dstack(const gt_dstack_case* c, void* stream);
 
+/* Parity hook of banded MLPG: ONE forward or transpose launch through ensure_band and mlpg_forward / mlpg_backward, the functions the
+ * step calls, with the step's own freedom in the arguments: column maps, pitches, and the masked-MSE gradient fused into the transpose.
+ *   e        the engine: num_windows, the band cache and (mse_w != 0) the scalars; R [T][num_windows * T] as in gt_op_mlpg_forward
+ *   scol, sstride   device int32 [Ds]: static column c reads / writes full-layout columns scol[c] + w * sstride[c], w < num_windows;
+ *            sstride[c] == 0: a pass-through column (copied).  Both null: the engine's own maps (Ds is then the engine's, 0 accepted).
+ *   forward  (backward == 0) reads y [B*T][ldy], writes ys [B*T][ldys] columns [0, Ds)
+ *   backward reads gs [B*T][ldgs] columns [0, Ds), writes gy [B*T][ldgy] at the mapped columns only.  mse_w != 0 adds
+ *            2 mse_w (yhat m - ytgt m) m / sum(m) with yhat, ytgt [B*T][ldt] and mask m [B*T]: the hook first puts sum(m) and its
+ *            reciprocal into the engine's scalars with the launch the step uses.  mse_w == 0: yhat, ytgt, mask may be null.
+ *   kb       host, or null: receives the half-width the band cache holds for (R, T), before the launchers' checks
+ * Every pointer is checked, every pitch against the widest column the maps reach (the maps are copied to the host for this).  A
+ * malformed case, and a band whose tiles exceed the device's LDS (see gt_op_mlpg_forward's launchers), returns GT_ERR_INVALID before
+ * any MLPG launch. */
+typedef struct gt_mlpg_case {
+  int32_t backward, B, T, Ds;
+  int32_t ldy, ldys, ldgs, ldgy;
+  int32_t ldt;
+  float mse_w;
+  gt_engine* e;
+  const float* R;
+  const int32_t* scol;
+  const int32_t* sstride;
+  const float* y;
+  float* ys;
+  const float* gs;
+  float* gy;
+  const float* yhat;
+  const float* ytgt;
+  const float* mask;
+  int32_t* kb;
+} gt_mlpg_case;
+int gt_op_mlpg(const gt_mlpg_case* c, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the
