@@ -40,6 +40,8 @@ OPT_NADAM, OPT_RADAM, OPT_RPROP, OPT_ASGD = 7, 8, 9, 10
 OPTF_NESTEROV, OPTF_CENTERED, OPTF_AMSGRAD, OPTF_BUFFER_LIVE = 1, 2, 4, 8      # OptimDescEx.flags
 OPTF_DECOUPLED_WD = 32                                                         # NAdam, RAdam
 MAX_STREAMS = 8
+MLPG_R_FROM_WINDOWS = 1                 # GT_MLPG_R_FROM_WINDOWS: "build the band from the registered windows", passed in place of R
+MLPG_MAX_WINDOW_SPAN = 32               # GT_MLPG_MAX_WINDOW_SPAN
 COMM_ID_BYTES = 128
 
 
@@ -191,6 +193,7 @@ SIGNATURES = {
     "gt_op_philox_mask": (_I, [_P, _I, _I, _I, _L, _F, _L, _I, _P, _P]),
     "gt_set_lengths": (_I, [_P, C.POINTER(_L), _I, _P]),
     "gt_invalidate_mlpg_cache": (_I, [_P]),
+    "gt_set_mlpg_windows": (_I, [_P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "gt_zero_grad": (_I, [_P, _I]),
     "gt_apply_generator": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "gt_update_discriminator": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, C.POINTER(DResult), _P]),
@@ -216,6 +219,7 @@ SIGNATURES = {
     "gt_op_d_head": (_I, [C.POINTER(DHeadCase), _P]),
     "gt_op_dstack": (_I, [C.POINTER(DStackCase), _P]),
     "gt_op_mlpg": (_I, [C.POINTER(MlpgCase), _P]),
+    "gt_op_mlpg_band": (_I, [_P, _P, _I, C.POINTER(_F), _L, C.POINTER(C.c_int32), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

@@ -164,7 +164,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
     for (auto& s : *v) s.release();
   e->s_du.release(); e->s_dx.release(); e->s_dbias.release();
   Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial,
-                    &e->headp, &e->headw, &e->gx_dense, &e->cx_dense, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp};
+                    &e->headp, &e->headw, &e->gx_dense, &e->cx_dense, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp, &e->mlpg.fac, &e->mlpg.wide};
   for (auto* s : all) s->release();
   e->w0pad[0].release(); e->w0pad[1].release();
   e->d_pre.release(); e->adv2.release(); e->pitched[0].buf.release(); e->pitched[1].buf.release();

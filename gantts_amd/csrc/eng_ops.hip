@@ -139,7 +139,8 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
   if (Ds < 1 || Ds > (1 << 20)) return fail(GT_ERR_INVALID, "MLPG hook: Ds = %d", Ds);
   if (bwd ? (!c->gs || !c->gy) : (!c->y || !c->ys)) return fail(GT_ERR_INVALID, "MLPG hook: null tensor");
   if (mse && (!c->yhat || !c->ytgt || !c->mask)) return fail(GT_ERR_INVALID, "MLPG hook: the masked-MSE gradient needs yhat, ytgt and mask");
-  for (const void* q : {(const void*)c->R, (const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->ys, (const void*)c->gs,
+  const bool built = c->R == GT_MLPG_R_FROM_WINDOWS;      // the sentinel is no address: ensure_band never dereferences it
+  for (const void* q : {built ? nullptr : (const void*)c->R, (const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->ys, (const void*)c->gs,
                         (const void*)c->gy, (const void*)c->yhat, (const void*)c->ytgt, (const void*)c->mask})
     if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "MLPG hook: misaligned operand");
   if (bwd ? c->ldgs < Ds : c->ldys < Ds) return fail(GT_ERR_INVALID, "MLPG hook: pitch of the static side below Ds = %d", Ds);
@@ -180,6 +181,21 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
   const hipError_t err = hipStreamSynchronize(s);
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "mlpg: %s", hipGetErrorString(err));
+  return GT_OK;
+}
+
+extern "C" int gt_op_mlpg_band(gt_engine* e, const float* R, int T, float* band_host, int64_t capacity, int32_t* kb, void* stream) {
+  CHK(check_common(e, 1, T));
+  if (!R) return fail(GT_ERR_INVALID, "MLPG band hook: null R");
+  if (R != GT_MLPG_R_FROM_WINDOWS && (((uintptr_t)R) & 3)) return fail(GT_ERR_INVALID, "MLPG band hook: misaligned R");
+  hipStream_t s = (hipStream_t)stream;
+  CHK(ensure_band(e, R, T, s));
+  const MlpgBand* b = e->mlpg.cur;
+  if (kb) *kb = b->kb;
+  const int64_t need = (int64_t)T * e->cfg.num_windows * (2 * b->kb + 1);
+  if (!band_host || capacity < need) return fail(GT_ERR_INVALID, "MLPG band hook: the band has %ld floats, band_host holds %ld", (long)need, (long)capacity);
+  HIPCHK(hipMemcpyAsync(band_host, b->band.p, (size_t)need * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return GT_OK;
 }
 

@@ -1,32 +1,72 @@
 // libgantts_hip.so -- the G+D step: MLPG, MLP stacks, apply_generator / update_discriminator / update_generator (reference train.py:245-355), plain forward
 #include "engine_internal.hip.h"
 #include "d_tail_args.hip.h"
+#include "mlpg_band_kernels.hip.h"
 #include <atomic>
 
 using namespace gt;
 // ------------------------------------------------------------------------------------------
 // MLPG band cache
 // ------------------------------------------------------------------------------------------
+// first sight of (GT_MLPG_R_FROM_WINDOWS, T): Cholesky factor and selected inverse of W^T W in one workgroup, then the taps at the candidate
+// half-width K and their per-offset maxima -> m.tmp [2 K + 1] floats and the pivot flag behind them.  No O(T^2) memory, no host work.
+static int build_taps_from_windows(gt_engine* e, int T, int K, hipStream_t s) {
+  MlpgCache& m = e->mlpg;
+  const MlpgWindows& win = m.win;
+  if (T > (1 << 20)) return fail(GT_ERR_INVALID, "MLPG band from windows: T = %d is beyond 2^20 frames", T);
+  int hb = 0, reach = 0;
+  for (int w = 0; w < win.n; ++w) { hb = std::max(hb, win.l[w] + win.u[w]); reach = std::max(reach, std::max(win.l[w], win.u[w])); }
+  const int KS = std::min(std::max(K + reach, hb), T - 1);
+  const int nk = 2 * K + 1;
+  const size_t n_fac = (size_t)T * (hb + 1), n_inv = (size_t)T * (KS + 1);
+  CHK(m.tmp.ensure((size_t)(nk + 1) * sizeof(float)));
+  CHK(m.fac.ensure((n_fac + n_inv) * sizeof(double)));
+  CHK(m.wide.ensure((size_t)T * win.n * nk * sizeof(float)));
+  double* Lb = m.fac.as<double>();
+  double* Sb = Lb + n_fac;
+  int* flag = (int*)(m.tmp.as<float>() + nk);
+  hipLaunchKernelGGL(mlpg_build_inverse_kernel, dim3(1), dim3(MLPG_BUILD_THREADS), 0, s, win, T, hb, KS, Lb, Sb, flag);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(mlpg_build_taps_kernel, dim3(cdiv((long)T * win.n * nk, 256)), dim3(256), 0, s, win, T, K, KS, Sb, flag, m.wide.as<float>());
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(mlpg_build_offset_max_kernel, dim3(nk), dim3(256), 0, s, m.wide.as<float>(), T, win.n, K, m.tmp.as<float>());
+  LAUNCH_CHECK();
+  return GT_OK;
+}
 int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s) {
   MlpgCache& m = e->mlpg;
   ++m.tick;
   for (auto* b : m.entries)
     if (b->R == R && b->T == T) { b->last_use = m.tick; m.cur = b; return GT_OK; }
   const int nW = e->cfg.num_windows;
-  // first sight of this (R, T): per-offset maxima -> host, pick the smallest half-width whose outside is negligible
-  CHK(m.tmp.ensure((size_t)(2 * T - 1) * sizeof(float)));
-  hipLaunchKernelGGL(mlpg_offset_max_kernel, dim3(2 * T - 1), dim3(256), 0, s, R, T, nW, m.tmp.as<float>());
-  LAUNCH_CHECK();
-  std::vector<float> off(2 * T - 1);
-  HIPCHK(hipMemcpyAsync(off.data(), m.tmp.p, off.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  const bool built = R == GT_MLPG_R_FROM_WINDOWS;      // never dereferenced
+  if (built && !m.has_win) return fail(GT_ERR_INVALID, "GT_MLPG_R_FROM_WINDOWS without a window set: call gt_set_mlpg_windows first");
+  // first sight of this (R, T): per-offset maxima -> host, pick the smallest half-width whose outside is negligible.  A dense R shows
+  // every offset; a built one the offsets up to MLPG_BUILD_K, one beyond the widest half-width accepted below
+  const int K = built ? std::min(MLPG_BUILD_K, T - 1) : T - 1;
+  if (built) {
+    CHK(build_taps_from_windows(e, T, K, s));
+  } else {
+    CHK(m.tmp.ensure((size_t)(2 * K + 2) * sizeof(float)));
+    hipLaunchKernelGGL(mlpg_offset_max_kernel, dim3(2 * T - 1), dim3(256), 0, s, R, T, nW, m.tmp.as<float>());
+    LAUNCH_CHECK();
+  }
+  std::vector<float> off(2 * K + 2);      // the last word: the pivot flag of a build
+  HIPCHK(hipMemcpyAsync(off.data(), m.tmp.p, (size_t)(2 * K + 1 + (built ? 1 : 0)) * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  if (built) {
+    int flag;
+    memcpy(&flag, &off[2 * K + 1], sizeof(flag));
+    if (flag) return fail(GT_ERR_INVALID, "window set does not determine the static features (W^T W is not positive definite at T=%d)", T);
+  }
+  off.resize(2 * K + 1);
   float peak = 0.f;
   bool has_nan = false;
   for (float v : off) { has_nan |= v != v; peak = fmaxf(peak, v); }      // fmaxf drops a NaN: counted apart
   if (has_nan || !(peak > 0.f) || !isfinite(peak)) return fail(GT_ERR_INVALID, "MLPG matrix R is empty or not finite");
   int kb = 0;
-  for (int o = -(T - 1); o <= T - 1; ++o)
-    if (off[o + T - 1] > 1e-9f * peak) kb = std::max(kb, abs(o));
+  for (int o = -K; o <= K; ++o)
+    if (off[o + K] > 1e-9f * peak) kb = std::max(kb, abs(o));
   if (kb > 63 || (kb > 48 && kb > T / 4))
     return fail(GT_ERR_INVALID, "MLPG matrix R is not banded (half-width %d of T=%d): only window sets whose "
                 "R = (W^T W)^-1 W^T decays (hparams.py:22-26) are supported", kb, T);
@@ -43,7 +83,8 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s) {
   const int nb = 2 * kb + 1;
   b->R = nullptr;
   CHK(b->band.ensure((size_t)T * nW * nb * sizeof(float)));
-  hipLaunchKernelGGL(mlpg_extract_band_kernel, dim3(cdiv((long)T * nW * nb, 256)), dim3(256), 0, s, R, T, nW, kb, b->band.as<float>());
+  if (built) hipLaunchKernelGGL(mlpg_build_band_kernel, dim3(cdiv((long)T * nW * nb, 256)), dim3(256), 0, s, m.wide.as<float>(), T, nW, K, kb, b->band.as<float>());
+  else hipLaunchKernelGGL(mlpg_extract_band_kernel, dim3(cdiv((long)T * nW * nb, 256)), dim3(256), 0, s, R, T, nW, kb, b->band.as<float>());
   LAUNCH_CHECK();
   b->R = R; b->T = T; b->kb = kb; b->last_use = m.tick;
   m.cur = b;
@@ -53,6 +94,39 @@ extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   HIPCHK(hipDeviceSynchronize());
   e->mlpg.clear();
+  return GT_OK;
+}
+extern "C" int gt_set_mlpg_windows(gt_engine* e, int n, const int32_t* l, const int32_t* u, const double* coef_concat) {
+  if (!e) return fail(GT_ERR_INVALID, "null engine");
+  if (n != e->cfg.num_windows) return fail(GT_ERR_INVALID, "gt_set_mlpg_windows: %d windows, the engine was created with num_windows = %d", n, e->cfg.num_windows);
+  if (!l || !u || !coef_concat) return fail(GT_ERR_INVALID, "gt_set_mlpg_windows: null argument");
+  MlpgWindows win;
+  memset(&win, 0, sizeof(win));
+  win.n = n;
+  const double* c = coef_concat;
+  for (int w = 0; w < n; ++w) {
+    if (l[w] < 0 || u[w] < 0 || (long)l[w] + u[w] > MLPG_WIN_SPAN)
+      return fail(GT_ERR_INVALID, "gt_set_mlpg_windows: window %d reaches (%d, %d): l, u >= 0 and l + u <= %d", w, l[w], u[w], MLPG_WIN_SPAN);
+    win.l[w] = l[w]; win.u[w] = u[w];
+    for (int k = 0; k <= l[w] + u[w]; ++k, ++c) {
+      if (!isfinite(*c)) return fail(GT_ERR_INVALID, "gt_set_mlpg_windows: coefficient %d of window %d is not finite", k, w);
+      win.coef[w][k] = *c == 0.0 ? 0.0 : *c;      // -0.0 and 0.0 are the same set
+    }
+  }
+  MlpgCache& m = e->mlpg;
+  if (m.has_win && memcmp(&m.win, &win, sizeof(win)) == 0) return GT_OK;
+  // another set: the built entries go (a dense R's stay), with gt_invalidate_mlpg_cache's synchronisation -- queued kernels may read them
+  HIPCHK(hipDeviceSynchronize());
+  for (size_t i = 0; i < m.entries.size();) {
+    MlpgBand* b = m.entries[i];
+    if (b->R != GT_MLPG_R_FROM_WINDOWS) { ++i; continue; }
+    if (m.cur == b) { m.cur = nullptr; e->g_pass_valid = false; e->leak_pending = false; }      // the stashed generator pass would transpose through it
+    b->band.release();
+    delete b;
+    m.entries.erase(m.entries.begin() + i);
+  }
+  memcpy(&m.win, &win, sizeof(win));      // padding included: the comparison above is a memcmp
+  m.has_win = true;
   return GT_OK;
 }
 

@@ -194,12 +194,23 @@ struct MlpgBand {
   uint64_t last_use = 0;
   Scratch band;
 };
+// The window set of gt_set_mlpg_windows, as the build kernels take it (by value): entries whose R is GT_MLPG_R_FROM_WINDOWS are built from
+// it on the device (mlpg_band_kernels.hip.h) instead of being extracted from a dense R, and can be rebuilt after an eviction.
+constexpr int MLPG_WIN_SPAN = GT_MLPG_MAX_WINDOW_SPAN;      // l + u of a registered window
+struct MlpgWindows {
+  int n;
+  int l[MLPG_MAXW], u[MLPG_MAXW];
+  double coef[MLPG_MAXW][MLPG_WIN_SPAN + 1];
+};
 struct MlpgCache {
   static constexpr size_t MAX_ENTRIES = 256;
   std::vector<MlpgBand*> entries;
   MlpgBand* cur = nullptr;
   uint64_t tick = 0;
   Scratch tmp;                      // per-offset maxima of a new R (persistent: no hipFree on the step path)
+  bool has_win = false;
+  MlpgWindows win;                  // zero-filled beyond the registered windows and coefficients: compared with memcmp
+  Scratch fac, wide;                // device build: Cholesky factor and selected inverse (float64), the taps at the candidate width
   void clear() { for (auto* b : entries) { b->band.release(); delete b; } entries.clear(); cur = nullptr; }
 };
 

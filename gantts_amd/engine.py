@@ -9,6 +9,7 @@ import torch
 
 from . import _lib as L
 from ._lib import check, lib, ptr
+from .paramgen import MLPGBand
 
 
 def stream_config_from_hp(hp):
@@ -112,6 +113,7 @@ class StepEngine(object):
         ss = [s // nW if d else s for s, d in zip(hp.stream_sizes, hp.has_dynamic_features)]
         self.static_dim = int(sum(ss))
         self.num_windows = nW
+        self._windows_sent = None                # window signature registered through gt_set_mlpg_windows
 
     @classmethod
     def for_forward_only(cls, model):
@@ -297,6 +299,35 @@ class StepEngine(object):
             check(lib.gt_set_loss_normalizer(self._h, float(tv)))
 
     # ---- step functions -------------------------------------------------------------------
+    def _mlpg_operand(self, R, T):
+        """(what the C ABI takes for R, what to keep alive).  A dense R is checked as before; an ``MLPGBand`` is checked against the batch,
+        its windows are registered (once per engine and window set) and GT_MLPG_R_FROM_WINDOWS stands in for the pointer."""
+        if not isinstance(R, MLPGBand):
+            R = _check_frames(R, "R")
+            return ptr(R), R
+        if R.T != T:
+            raise RuntimeError("MLPGBand was made for T = %d, the batch has T = %d" % (R.T, T))
+        if R.num_windows != self.num_windows:
+            raise RuntimeError("MLPGBand has %d windows, the engine %d" % (R.num_windows, self.num_windows))
+        if self._windows_sent != R.window_signature:
+            n = R.num_windows
+            coef = np.concatenate([c for (_, _, c) in R.windows])
+            check(lib.gt_set_mlpg_windows(self._h, n, (C.c_int32 * n)(*[l for (l, _, _) in R.windows]),
+                                          (C.c_int32 * n)(*[u for (_, u, _) in R.windows]), (C.c_double * coef.size)(*coef.tolist())))
+            self._windows_sent = R.window_signature
+        return C.c_void_p(L.MLPG_R_FROM_WINDOWS), R
+
+    def mlpg_band(self, R, T=None):
+        """Parity hook (gt_op_mlpg_band): ``(band, kb)`` of the band cache's entry for a dense device R or an ``MLPGBand`` --
+        band (T, num_windows, 2 kb + 1) float32 numpy, band[t, w, j] = R[t, w * T + t + j - kb]."""
+        T = int(R.size(0) if T is None else T)
+        Rp, keep = self._mlpg_operand(R, T)
+        buf = np.empty(T * self.num_windows * (2 * min(T - 1, 64) + 1), dtype=np.float32)
+        kb = C.c_int32(-1)
+        check(lib.gt_op_mlpg_band(self._h, Rp, T, buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size, C.byref(kb), L.current_stream()))
+        nb = 2 * kb.value + 1
+        return buf[:T * self.num_windows * nb].reshape(T, self.num_windows, nb).copy(), kb.value
+
     def set_lengths(self, lengths, B, T):
         """`lengths` as the reference passes them (list of ints / 0-dim tensors, LongTensor, numpy)."""
         if lengths is None:
@@ -323,11 +354,12 @@ class StepEngine(object):
         static_w = model_g.static_dim if model_g.include_parameter_generation() else self.static_dim
         y_hat = torch.empty(B, T, model_g.out_dim, device=x.device, dtype=torch.float32)
         y_hat_static = torch.empty(B, T, static_w, device=x.device, dtype=torch.float32)
+        Rp = None
         if R is not None:
-            R = _check_frames(R, "R")
+            Rp, R = self._mlpg_operand(R, T)
             if R.dim() != 2 or R.size(0) != T or R.size(1) != self.num_windows * T:
                 raise RuntimeError("R must be (T, num_windows*T) = (%d, %d), got %s" % (T, self.num_windows * T, tuple(R.shape)))
-        check(lib.gt_apply_generator(self._h, ptr(x), ptr(R), B, T, ptr(y_hat), ptr(y_hat_static), L.current_stream()))
+        check(lib.gt_apply_generator(self._h, ptr(x), Rp, B, T, ptr(y_hat), ptr(y_hat_static), L.current_stream()))
         self._keep["g"] = (x, R, y_hat, y_hat_static)
         y_hat._gt_engine = y_hat_static._gt_engine = self
         return y_hat, y_hat_static
@@ -518,9 +550,11 @@ class StepEngine(object):
         if model.include_parameter_generation():
             if R is None:
                 raise RuntimeError("In2OutHighwayNet.forward needs R")
-            R = _check_frames(R, "R")
+            Rp, R = self._mlpg_operand(R, T)
             out2 = torch.empty(B, T, model.static_dim, device=x.device, dtype=torch.float32)
-        check(lib.gt_model_forward(self._h, L.ROLE_G, ptr(x), ptr(R), B, T, ptr(out), ptr(out2), L.current_stream()))
+        else:
+            Rp = None if R is None or isinstance(R, MLPGBand) else ptr(R)      # ignored by the library
+        check(lib.gt_model_forward(self._h, L.ROLE_G, ptr(x), Rp, B, T, ptr(out), ptr(out2), L.current_stream()))
         if out2 is not None:
             return out, out2
         return out.squeeze(0) if squeeze else out
@@ -528,18 +562,18 @@ class StepEngine(object):
     # ---- stand-alone ops that need the stream config --------------------------------------
     def mlpg_forward(self, y, R):
         y = _check_frames(y, "inputs")
-        R = _check_frames(R, "R")
         B, T, _ = y.shape
+        Rp, R = self._mlpg_operand(R, T)
         out = torch.empty(B, T, self.static_dim, device=y.device, dtype=torch.float32)
-        check(lib.gt_op_mlpg_forward(self._h, ptr(y), ptr(R), B, T, ptr(out), L.current_stream()))
+        check(lib.gt_op_mlpg_forward(self._h, ptr(y), Rp, B, T, ptr(out), L.current_stream()))
         return out
 
     def mlpg_backward(self, g_static, R, full_dim):
         g = _check_frames(g_static, "grad")
-        R = _check_frames(R, "R")
         B, T, _ = g.shape
+        Rp, R = self._mlpg_operand(R, T)
         out = torch.empty(B, T, full_dim, device=g.device, dtype=torch.float32)
-        check(lib.gt_op_mlpg_backward(self._h, ptr(g), ptr(R), B, T, ptr(out), L.current_stream()))
+        check(lib.gt_op_mlpg_backward(self._h, ptr(g), Rp, B, T, ptr(out), L.current_stream()))
         return out
 
 

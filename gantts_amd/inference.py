@@ -22,7 +22,7 @@ from . import hparams
 from .data import minmax_scale
 from .engine import StepEngine
 from .multistream import get_static_stream_sizes
-from .paramgen import unit_variance_mlpg_matrix_cuda
+from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
 
 hp_acoustic = hparams.tts_acoustic
 hp_duration = hparams.tts_duration
@@ -78,10 +78,17 @@ def predict_acoustic(acoustic_model, linguistic_features, X_min, X_max):
     return _forward(acoustic_model.cuda(), hp_duration, feats)
 
 
-def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True):
+def _mlpg_matrix(windows, T, device_band):
+    """R of an utterance: the cached dense device matrix, or (``device_band``) its weightless stand-in -- the engine then builds
+    the band on the device, with no O(T^2) host work or copy for an utterance length it has not seen."""
+    return unit_variance_mlpg_band(windows, T) if device_band else unit_variance_mlpg_matrix_cuda(windows, T)
+
+
+def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True, device_band=False):
     """(mgc, lf0, vuv, bap): multi-stream MLPG on the normalised features (the banded device kernel,
     unit variance) followed by inverse scaling with statistics indexed in the static+dynamic domain.
-    ``Y_mean`` / ``Y_std`` are the reference's dicts (``["acoustic"]``) or plain arrays."""
+    ``Y_mean`` / ``Y_std`` are the reference's dicts (``["acoustic"]``) or plain arrays.
+    ``device_band``: build the MLPG band on the device from ``hp.windows`` instead of from a dense host R."""
     if not mge_training:
         raise NotImplementedError("the reference's non-MGE branch multiplies a dict (evaluation_tts.py:86) and "
                                   "cannot run; GAN generators are MGE-trained")
@@ -94,7 +101,7 @@ def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True):
     y = y_predicted if isinstance(y_predicted, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y_predicted))
     y = y.float().cuda().view(1, -1, y.shape[-1])
     T = y.size(1)
-    static = _engine(hp).mlpg_forward(y, unit_variance_mlpg_matrix_cuda(hp.windows, T))[0].double().cpu().numpy()
+    static = _engine(hp).mlpg_forward(y, _mlpg_matrix(hp.windows, T, device_band))[0].double().cpu().numpy()
     smgc, slf0, svuv, sbap = [int(v) for v in get_static_stream_sizes(hp.stream_sizes, hp.has_dynamic_features, nw)]
     mean, std = np.asarray(mean), np.asarray(std)
     mgc = static[:, :smgc] * std[:mgc_dim // nw] + mean[:mgc_dim // nw]
@@ -104,11 +111,11 @@ def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True):
     return mgc, lf0, vuv, bap
 
 
-def vc_convert(model, mc, data_mean, data_std, diffvc=True):
+def vc_convert(model, mc, data_mean, data_std, diffvc=True, device_band=False):
     """Static mel-cepstrum conversion of one utterance.  ``mc`` (T, 3*order) = delta_features of the
     smoothed source mel-cepstrum (without c0).  Returns ``(inputs, outputs, mc_static_for_synthesis)``:
     the source statics, the converted statics, and what the reference hands to the synthesis filter
-    (the difference to the source when ``diffvc``)."""
+    (the difference to the source when ``diffvc``).  ``device_band``: as in ``gen_parameters``."""
     hp = hp_vc
     model = model.cuda()
     model.eval()
@@ -117,7 +124,7 @@ def vc_convert(model, mc, data_mean, data_std, diffvc=True):
     static_dim = mc.shape[-1] // len(hp.windows)
     inputs = mc[:, :static_dim].copy()
     mc_scaled = torch.from_numpy(((mc - data_mean) / data_std).astype(np.float32)).cuda().view(1, T, -1)
-    R = unit_variance_mlpg_matrix_cuda(hp.windows, T)
+    R = _mlpg_matrix(hp.windows, T, device_band)
     if model.include_parameter_generation():
         _, y_hat_static = model(mc_scaled, R, lengths=[T])
     else:

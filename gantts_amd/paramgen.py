@@ -6,6 +6,10 @@ Differences from the reference call pattern (results identical): W^T W is banded
 solved with a banded Cholesky in float64 (O(T^2) instead of a dense inverse), and the result is
 cached per (windows, T) together with its device copy -- the reference rebuilds it on the host
 and uploads T x 3T floats every batch.
+
+``MLPGBand`` / ``unit_variance_mlpg_band`` stand for the same matrix without forming it: the engine builds the taps its
+kernels read on the device from the windows (gt_set_mlpg_windows, GT_MLPG_R_FROM_WINDOWS) -- no O(T^2) host work, upload or
+cache entry per padded length.
 """
 import numpy as np
 import scipy.linalg
@@ -56,3 +60,56 @@ def unit_variance_mlpg_matrix_cuda(windows, T, device="cuda"):
     if hit is None:
         hit = _dev_cache[key] = torch.from_numpy(np.array(unit_variance_mlpg_matrix(windows, T))).to(device)
     return hit
+
+
+class MLPGBand(object):
+    """``R = (W^T W)^-1 W^T`` of ``unit_variance_mlpg_matrix(windows, T)`` as a weightless stand-in: it holds the windows and ``T``,
+    and quacks like the (T, num_windows * T) matrix where the reference asks for its shape (``R.size(1) // R.size(0)``,
+    multistream.py:88).  Accepted wherever the step functions take R; the engine builds the band on the device."""
+
+    def __init__(self, windows, T):
+        T = int(T)
+        if T < 1:
+            raise ValueError("MLPGBand: T must be positive, got %d" % T)
+        if len(windows) < 1:
+            raise ValueError("MLPGBand: no windows")
+        self.windows = [(int(l), int(u), np.array(np.asarray(c, dtype=np.float64).ravel())) for (l, u, c) in windows]
+        for l, u, c in self.windows:
+            if l < 0 or u < 0 or c.size != l + u + 1:
+                raise ValueError("MLPGBand: a window is (l, u, l + u + 1 coefficients), got (%d, %d, %d coefficients)" % (l, u, c.size))
+        self.T = T
+        self.num_windows = len(self.windows)
+        self.shape = (T, self.num_windows * T)
+        self.signature = _signature(self.windows, T)
+
+    @property
+    def window_signature(self):
+        """the windows alone (what an engine registers once): equal for every T"""
+        return self.signature[1:]
+
+    def size(self, i=None):
+        return self.shape if i is None else self.shape[i]
+
+    def dim(self):
+        return 2
+
+    def dense(self):
+        """today's host matrix (float32, read-only, cached)"""
+        return unit_variance_mlpg_matrix(self.windows, self.T)
+
+    def __eq__(self, other):
+        return isinstance(other, MLPGBand) and self.signature == other.signature
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self.signature)
+
+    def __repr__(self):
+        return "MLPGBand(num_windows=%d, T=%d)" % (self.num_windows, self.T)
+
+
+def unit_variance_mlpg_band(windows, T):
+    """Drop-in for ``unit_variance_mlpg_matrix_cuda`` that never forms R."""
+    return MLPGBand(windows, T)

@@ -248,13 +248,17 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     logged names/values and checkpoint cadence.  Differences are all on the data path: batches arrive
     through ``DevicePrefetcher`` (pinned, double-buffered H2D overlapped with the previous step), the
     MLPG matrix is cached per T on the device instead of being rebuilt and uploaded every batch
-    (train.py:509-513), and the distortion metrics come from one fused reduction."""
+    (train.py:509-513) -- or, with ``hp.mlpg_device_band``, never formed: the band is built on the device from
+    ``hp.windows`` -- and the distortion metrics come from one fused reduction."""
     from .data import DevicePrefetcher
     from .multistream import get_static_features
-    from .paramgen import unit_variance_mlpg_matrix_cuda
+    from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
     from .seqloss import sequence_mask
     import numpy as np
     global global_epoch
+    # hp.mlpg_device_band: the engine builds the MLPG band of every new padded length on the device from hp.windows; no dense R is
+    # formed, uploaded or cached per length (paramgen.MLPGBand)
+    mlpg_matrix = unit_variance_mlpg_band if getattr(hp, "mlpg_device_band", False) else unit_variance_mlpg_matrix_cuda
     model_g, model_d = models
     optimizer_g, optimizer_d = optimizers
     model_g, model_d = model_g.cuda(), model_d.cuda()
@@ -303,7 +307,7 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
                 # generator noise z ~ U[0,1) (train.py:504-506), drawn on the device
                 z = torch.rand(x.size(0), max_len, hp.generator_noise_dim, device=x.device, generator=noise_gen) \
                     if hp.generator_add_noise else None
-                R = unit_variance_mlpg_matrix_cuda(hp.windows, max_len) if has_dynamic else None
+                R = mlpg_matrix(hp.windows, max_len) if has_dynamic else None
                 y_static = get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
                 total_num_frames += float(sum(cpu_sorted_lengths))
                 mask = sequence_mask(sorted_lengths).unsqueeze(-1)

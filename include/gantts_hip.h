@@ -230,6 +230,19 @@ int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, void* strea
  * rebuilds and uploads R every batch, train.py:511-513; callers of this library keep one device R per padded length).
  * R must not be rewritten in place or freed-and-reused while cached: call this first (drops all cached bands). */
 int gt_invalidate_mlpg_cache(gt_engine* e);
+/* The MLPG band built on the device from the window set, without a dense R.  Register the windows once: window w is
+ * (l[w], u[w], its l[w] + u[w] + 1 coefficients), (W_w x)[t] = sum_k coef_w[k + l[w]] x[t + k], the coefficients of all windows one
+ * after the other in coef_concat (copied).  n must be the engine's num_windows; l, u >= 0, l + u <= GT_MLPG_MAX_WINDOW_SPAN, finite
+ * coefficients.  Registering a DIFFERENT set drops the entries built from the former one (synchronises the device like
+ * the invalidation above; entries of dense matrices stay); the same set again is free.
+ * GT_MLPG_R_FROM_WINDOWS is then accepted wherever a dense R is: the apply_generator, model_forward and MLPG entry points below.  It is never
+ * dereferenced.  The band cache keeps such entries under (GT_MLPG_R_FROM_WINDOWS, T) beside those of dense matrices; a miss builds the
+ * taps in O(T) memory (banded Cholesky of W^T W and a selected inversion in float64, rounded to float32 once) and applies the same
+ * half-width rule and refusals as for a dense R.  A window set whose W^T W is not positive definite returns GT_ERR_INVALID
+ * ("window set does not determine the static features") and caches nothing; so does the sentinel without registered windows. */
+#define GT_MLPG_MAX_WINDOW_SPAN 32
+#define GT_MLPG_R_FROM_WINDOWS ((const float*)(uintptr_t)1)
+int gt_set_mlpg_windows(gt_engine* e, int n, const int32_t* l, const int32_t* u, const double* coef_concat);
 
 /* ---- hot path -------------------------------------------------------------------------- */
 /* optimizer.zero_grad()                                         (train.py:538-539) */
@@ -848,6 +861,11 @@ typedef struct gt_mlpg_case {
   int32_t* kb;
 } gt_mlpg_case;
 int gt_op_mlpg(const gt_mlpg_case* c, void* stream);
+/* Parity hook of the band cache: ensures the entry of (R or GT_MLPG_R_FROM_WINDOWS, T) as the MLPG entry points do, writes its half-width
+ * to *kb (host, may be null) and copies the band image [T][num_windows][2 kb + 1] (band[t][w][j] = R[t][w*T + t + j - kb], zero where
+ * t + j - kb is outside [0, T)) to band_host.  capacity: floats band_host holds; too few return GT_ERR_INVALID after *kb is written.
+ * Synchronises the stream. */
+int gt_op_mlpg_band(gt_engine* e, const float* R, int T, float* band_host, int64_t capacity, int32_t* kb, void* stream);
 
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
