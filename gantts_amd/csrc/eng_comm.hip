@@ -226,7 +226,7 @@ int comm_flush(gt_engine* e, int role, hipStream_t compute, bool closing) {
   if (!comm_on(e)) return GT_OK;
   // the fused step only RECORDS its weight-gradient combines (SlabDefer): the ranges about to leave must be final, so the recorded
   // combines run now, as ONE launch per message instead of one per layer
-  CHK(slab_defer_flush(e->sdefer[role], compute));
+  CHK(slab_defer_flush(e->ws[role].sdefer, compute));
   auto& pend = e->comm_pending[role];
   if (pend.empty()) return GT_OK;
   Net& n = e->net[role];
@@ -289,7 +289,7 @@ int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float a
 // Two halves so that the all-reduce of the count runs under the forward pass that precedes its first use:
 // ensure_tv_begin where the mask is first seen, ensure_tv right before the first kernel that reads the normaliser.
 int ensure_tv_begin(gt_engine* e, const float* mask, long N, hipStream_t s) {
-  if (e->tv_mask == mask && e->tv_n == N && e->tv_ovr == e->tv_override) return GT_OK;
+  if (e->tv.known(mask, N, e->tv_override)) return GT_OK;
   if (comm_on(e) && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight) {
     hipLaunchKernelGGL(mask_total_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, e->comm_tv.as<double>());
     LAUNCH_CHECK();
@@ -310,17 +310,16 @@ int comm_tv_join(gt_engine* e, hipStream_t s) {
   return GT_OK;
 }
 int ensure_tv(gt_engine* e, const float* mask, long N, hipStream_t s) {
-  if (e->tv_mask == mask && e->tv_n == N && e->tv_ovr == e->tv_override) return GT_OK;
+  if (e->tv.known(mask, N, e->tv_override)) return GT_OK;
   const double* tv_dev = e->tv_dev;
   if (comm_on(e) && !tv_dev && !(e->tv_override > 0.f)) {
     CHK(ensure_tv_begin(e, mask, N, s));
-    CHK(comm_join(e, s));
-    e->tv_inflight = false;
+    CHK(comm_tv_join(e, s));
     tv_dev = e->comm_tv.as<double>();
   }
   hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, e->tv_override, tv_dev, e->sc());
   LAUNCH_CHECK();
-  e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override;
+  e->tv.note(mask, N, e->tv_override);
   return GT_OK;
 }
 

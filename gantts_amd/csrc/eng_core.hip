@@ -143,15 +143,8 @@ extern "C" int gt_engine_create(const gt_stream_config* cfg, gt_engine** out) {
 extern "C" void gt_engine_destroy(gt_engine* e) {
   if (!e) return;
   (void)hipDeviceSynchronize();
-  for (auto& s : e->g_act) s.release();
-  for (auto& s : e->d_act) s.release();
-  for (auto* v : {&e->l_xproj, &e->l_gates, &e->l_cst, &e->l_out, &e->l_outd, &e->dl_xproj, &e->dl_gates, &e->dl_cst, &e->dl_out, &e->dl_outd})
-    for (auto& s : *v) s.release();
-  e->dl_dout.release(); e->dl_hshift.release(); e->d_dx0.release();
-  e->i2o_gout.release();
+  e->ws[GT_ROLE_G].release(); e->ws[GT_ROLE_D].release();
   (void)gt_comm_destroy(e);
-  e->comm_tv.release();
-  e->l_state.release(); e->l_dout.release(); e->l_hshift.release(); e->l_xch.release();
   if (e->d_fault) (void)hipFree(e->d_fault);
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   for (int i = 0; i < gt_engine::LEN_RING; ++i) {
@@ -159,29 +152,11 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
     if (e->len_host[i]) (void)hipHostFree(e->len_host[i]);
     if (e->len_ev[i]) (void)hipEventDestroy(e->len_ev[i]);
   }
-  for (auto* v : {&e->s_u, &e->s_h, &e->s_c, &e->s_xdrop, &e->s_xmask, &e->s_wt, &e->ds_u, &e->ds_h, &e->ds_c, &e->ds_xdrop, &e->ds_xmask, &e->ds_wt,
-                  &e->ds_omask})
-    for (auto& s : *v) s.release();
-  e->s_du.release(); e->s_dx.release(); e->s_dbias.release();
-  Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial,
-                    &e->headp, &e->headw, &e->gx_dense, &e->cx_dense, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp, &e->mlpg.fac, &e->mlpg.wide};
+  Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
+                    &e->cx_dense.buf, &e->dx_pitched.buf, &e->gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
+                    &e->mlpg.fac, &e->mlpg.wide, &e->comm_tv, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2};
   for (auto* s : all) s->release();
-  e->w0pad[0].release(); e->w0pad[1].release();
-  e->d_pre.release(); e->adv2.release(); e->pitched[0].buf.release(); e->pitched[1].buf.release();
-  for (auto* v : {&e->g_actb, &e->d_actb}) for (auto& b : *v) b.release();
   e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
-  for (int r = 0; r < 2; ++r) for (auto& w : e->wsh[r]) { w.w.release(); w.wt.release(); }
-  for (auto& b : e->l_in_b) b.release();
-  for (auto& b : e->s_in_b) b.release();
-  e->s_du_b.release();
-  for (auto& w : e->ssh) { w.w.release(); w.wt.release(); }
-  for (auto& b : e->ds_in_b) b.release();
-  e->ds_du_b.release();
-  for (auto& w : e->dssh) { w.w.release(); w.wt.release(); }
-  for (auto& b : e->l_dg_b) b.release();
-  e->l_hs_b.release();
-  for (auto& w : e->lsh) { w.w.release(); w.wt.release(); }
-  e->sdefer[0].pool.release(); e->sdefer[1].pool.release();
   e->mlpg.clear();
   int* ints[] = {e->d_scol, e->d_sstride, e->d_adv_cols, e->d_adv_inv, e->d_scol_i2o, e->d_sstride_i2o};
   for (int* p : ints) if (p) (void)hipFree(p);
@@ -232,6 +207,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   if (role == GT_ROLE_D && (desc->arch == GT_ARCH_LSTM || desc->arch == GT_ARCH_SRU) && desc->hidden_dim * (desc->bidirectional ? 2 : 1) > 1024)
     return fail(GT_ERR_INVALID, "recurrent discriminator: hidden_dim x directions > 1024 is not supported by the fused head kernel");
   Net& n = e->net[role];
+  NetWs& W = e->ws[role];
   n.d = *desc;
   n.hidden.clear();
   float* p = desc->params;
@@ -266,13 +242,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
       n.lstm.push_back(L);
     }
     n.last = take(desc->out_dim, H * dirs);
-    if (role == GT_ROLE_G) {
-      e->l_xproj.resize(desc->num_hidden); e->l_gates.resize(desc->num_hidden);
-      e->l_cst.resize(desc->num_hidden); e->l_out.resize(desc->num_hidden); e->l_outd.resize(desc->num_hidden);
-    } else {
-      e->dl_xproj.resize(desc->num_hidden); e->dl_gates.resize(desc->num_hidden);
-      e->dl_cst.resize(desc->num_hidden); e->dl_out.resize(desc->num_hidden); e->dl_outd.resize(desc->num_hidden);
-    }
+    for (auto* v : {&W.xproj, &W.gates, &W.cst, &W.out, &W.outd}) v->resize(desc->num_hidden);
   } else if (desc->arch == GT_ARCH_SRU) {
     if (desc->rnn_dropout < 0.f || desc->rnn_dropout >= 1.f) return fail(GT_ERR_INVALID, "rnn_dropout must be in [0,1)");
     if (desc->num_hidden > 8) return fail(GT_ERR_INVALID, "SRURNN: at most 8 layers (two dropout sites per layer)");
@@ -288,12 +258,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
       n.sru.push_back(L);
     }
     n.last = take(desc->out_dim, ncols);
-    if (role == GT_ROLE_G) {
-      e->s_u.resize(desc->num_hidden); e->s_h.resize(desc->num_hidden);
-      e->s_c.resize(desc->num_hidden); e->s_xdrop.resize(desc->num_hidden); e->s_xmask.resize(desc->num_hidden); e->s_wt.resize(desc->num_hidden);
-    } else {
-      for (auto* v : {&e->ds_u, &e->ds_h, &e->ds_c, &e->ds_xdrop, &e->ds_xmask, &e->ds_wt, &e->ds_omask}) v->resize(desc->num_hidden);
-    }
+    for (auto* v : {&W.u, &W.h, &W.c, &W.xdrop, &W.xmask, &W.wt, &W.omask}) v->resize(desc->num_hidden);      // (the generator's omask entries stay empty)
   } else {
     if (desc->arch == GT_ARCH_IN2OUT) n.gate = take(desc->static_dim, desc->static_dim);
     int in = desc->in_dim;
@@ -302,8 +267,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   }
   n.bound = true;
   n.grads_dirty = false;
-  auto& acts = role == GT_ROLE_G ? e->g_act : e->d_act;
-  acts.resize(desc->num_hidden);
+  W.act.resize(desc->num_hidden);
   if (role == GT_ROLE_G && is_i2o(desc->arch)) {
     // single dynamic stream of width out_dim (models.py:66,115)
     const int sd = desc->out_dim / e->cfg.num_windows;
@@ -402,7 +366,7 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       // instead of back-propagating through buffers the forward never filled
       if (e->matmul_bf16 != (value != 0)) {
         invalidate_d_images(e);
-        e->g_pass_valid = false; e->leak_pending = false; e->cxd_src = nullptr;
+        e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget();
         e->d_begin_done = false; e->g_begin_done = false;
       }
       e->matmul_bf16 = value != 0;
@@ -462,7 +426,7 @@ extern "C" int gt_set_loss_normalizer(gt_engine* e, float tv) {
 extern "C" int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_dev) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   e->tv_dev = tv_dev;
-  e->tv_mask = nullptr; e->tv_inflight = false;          // re-read on the next step function
+  e->tv.forget(); e->tv_inflight = false;          // re-read on the next step function
   return GT_OK;
 }
 extern "C" int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, void* stream) {
@@ -500,8 +464,8 @@ extern "C" int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, 
 extern "C" int gt_zero_grad(gt_engine* e, int role) {
   if (!e || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
   e->net[role].grads_dirty = false;   // lazily: the next backward overwrites
-  { SlabDefer& sd = e->sdefer[role]; sd.active = false; sd.jobs.n = 0; sd.blocks = 0; sd.used = 0; }   // nothing recorded survives a zero_grad
-  e->tv_mask = nullptr; e->tv_inflight = false;
+  e->ws[role].sdefer.reset(false);      // nothing recorded survives a zero_grad
+  e->tv.forget(); e->tv_inflight = false;
   if (role == GT_ROLE_G) { e->leak_pending = false; e->leak_unnorm = false; }
   return GT_OK;
 }
@@ -611,7 +575,7 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   invalidate_d_images(e);
-  e->g_pass_valid = false; e->leak_pending = false; e->cxd_src = nullptr;
+  e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget();
   e->d_begin_done = e->g_begin_done = false; e->early_done = false;
   return GT_OK;
 }

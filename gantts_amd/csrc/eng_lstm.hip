@@ -6,16 +6,7 @@ using namespace gt;
 // ------------------------------------------------------------------------------------------
 // recurrent generator (GT_ARCH_LSTM): forward / backward of the LSTM stack
 // ------------------------------------------------------------------------------------------
-// Per-role stashes of a recurrent network: the generator's must survive the discriminator passes of a step (its backward runs last),
-// so a recurrent discriminator has its own set
-struct LstmBufs {
-  std::vector<Scratch>& xproj; std::vector<Scratch>& gates; std::vector<Scratch>& cst; std::vector<Scratch>& out; std::vector<Scratch>& outd;
-  Scratch& dout; Scratch& hshift;
-};
-static LstmBufs lstm_bufs(gt_engine* e, int role) {
-  if (role == GT_ROLE_G) return LstmBufs{e->l_xproj, e->l_gates, e->l_cst, e->l_out, e->l_outd, e->l_dout, e->l_hshift};
-  return LstmBufs{e->dl_xproj, e->dl_gates, e->dl_cst, e->dl_out, e->dl_outd, e->dl_dout, e->dl_hshift};
-}
+// (the stashes are the role's own, e->ws[role]: NetWs in engine_internal.hip.h)
 int lstm_check_lengths(gt_engine* e, int B, int T) {
   if ((int)e->h_lengths.size() != B)
     return fail(GT_ERR_STATE, "recurrent network: call with lengths (gt_set_lengths) for this batch of %d sequences "
@@ -27,7 +18,7 @@ int lstm_check_lengths(gt_engine* e, int B, int T) {
 
 enum { GT_LSTM_PATH_STEPS = 32, GT_LSTM_PATH_DECLINED = 33 };    // gt_lstm_path_counts: per-step kernels / no persistent grid fitted
 
-static int lstm_launch_steps(gt_engine* e, const Net& G, const LstmBufs& W, int layer, int B, int T, bool backward, const float* dout, hipStream_t s) {
+static int lstm_launch_steps(gt_engine* e, const Net& G, NetWs& W, int layer, int B, int T, bool backward, const float* dout, hipStream_t s) {
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1;
   const int Bpad = cdiv(B, 32) * 32;
   e->lstm_paths[GT_LSTM_PATH_STEPS]++;
@@ -116,7 +107,7 @@ static int launch_bwd_seq(LstmSeqArgs& a, int bt, bool bf16, hipStream_t s, bool
 
 // Runs one layer's recurrence (forward, or backward when `backward`) as ONE persistent launch when the shape fits
 // (H <= 512, grid co-resident); *launched = false leaves the work to the per-step kernels.
-static int lstm_launch_seq(gt_engine* e, const Net& G, const LstmBufs& W, bool bf16, int layer, int B, int T, bool backward, const float* dout,
+static int lstm_launch_seq(gt_engine* e, const Net& G, NetWs& W, bool bf16, int layer, int B, int T, bool backward, const float* dout,
                            hipStream_t s, bool* launched) {
   *launched = false;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1;
@@ -178,7 +169,7 @@ static bool lstm_b16(const gt_engine* e) { return e->matmul_bf16 && (e->net[GT_R
 int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
                        const float** top, int* ld_top) {
   Net& G = e->net[role];
-  LstmBufs W = lstm_bufs(e, role);
+  NetWs& W = e->ws[role];
   const int B = nseq;
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1;
@@ -190,9 +181,9 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
   const bool want_t = G.d.grads != nullptr;
   const int Lc_ = G.d.num_hidden;
   if (b16) {
-    e->l_in_b.resize(Lc_ + 1); e->lsh.resize(Lc_ + 1);
+    W.l_in_b.resize(Lc_ + 1); W.lsh.resize(Lc_ + 1);
     for (int l = 0; l <= Lc_; ++l) {
-      LinShadow& w = e->lsh[l];
+      LinShadow& w = W.lsh[l];
       if (l == Lc_) {
         w.ldw = pad8(G.last.in); w.ldwt = pad8(G.last.out);
         CHK(w.w.ensure((size_t)G.last.out * w.ldw * 2 + 64)); CHK(w.wt.ensure((size_t)G.last.in * w.ldwt * 2 + 64));
@@ -214,11 +205,11 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
     CHK(W.cst[l].ensure((size_t)N * dirs * H * sizeof(float)));
     CHK(W.out[l].ensure((size_t)N * dirs * H * sizeof(float)));
     if (b16) {
-      B16Img& I = e->l_in_b[l];
+      B16Img& I = W.l_in_b[l];
       CHK(I.ensure(N, L.in, want_t));
       CHK(cast_transpose(in, ld_in, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
       GemmB16Args g = b16_args();
-      g.A = I.r(); g.lda = I.ld; g.B = e->lsh[l].w.as<__bf16>(); g.ldb = e->lsh[l].ldw;
+      g.A = I.r(); g.lda = I.ld; g.B = W.lsh[l].w.as<__bf16>(); g.ldb = W.lsh[l].ldw;
       g.M = (int)N; g.N = dirs * 4 * H; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE;
       g.C = W.xproj[l].as<float>(); g.ldc = dirs * 4 * H;
       CHK(launch_gemm_b16(g, 1, s));
@@ -253,6 +244,7 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
 int lstm_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
   CHK(lstm_check_lengths(e, B, T));
+  NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
   const int Lc_ = G.d.num_hidden;
   const bool b16 = lstm_b16(e);
@@ -262,11 +254,11 @@ int lstm_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipSt
   int ld_in = 0;
   CHK(lstm_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &in, &ld_in));
   if (b16) {
-    B16Img& I = e->l_in_b[Lc_];
+    B16Img& I = W.l_in_b[Lc_];
     CHK(I.ensure(N, G.last.in, want_t));
     CHK(cast_transpose(in, ld_in, N, G.last.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
     GemmB16Args g = b16_args();
-    g.A = I.r(); g.lda = I.ld; g.B = e->lsh[Lc_].w.as<__bf16>(); g.ldb = e->lsh[Lc_].ldw;
+    g.A = I.r(); g.lda = I.ld; g.B = W.lsh[Lc_].w.as<__bf16>(); g.ldb = W.lsh[Lc_].ldw;
     g.M = (int)N; g.N = G.last.out; g.K = G.last.in; g.bias = G.last.b; g.epi = B16_FWD;
     g.act = G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = y_hat; g.ldc = G.d.out_dim;
     return launch_gemm_b16(g, 1, s);
@@ -278,26 +270,27 @@ int lstm_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipSt
 // gy (N, out_dim) = dL/dy_hat -> parameter gradients of hidden2out and of every LSTM layer
 int lstm_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
+  NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, Do = G.d.out_dim, Lc = G.d.num_hidden;
   const bool acc = G.grads_dirty;
-  CHK(e->l_dout.ensure((size_t)2 * N * dirs * H * sizeof(float)));
-  float* dout = e->l_dout.as<float>();                       // gradient w.r.t. the top layer's output
-  const bool b16 = lstm_b16(e) && (int)e->l_in_b.size() == Lc + 1 && (int)e->lsh.size() == Lc + 1;
+  CHK(W.dout.ensure((size_t)2 * N * dirs * H * sizeof(float)));
+  float* dout = W.dout.as<float>();                       // gradient w.r.t. the top layer's output
+  const bool b16 = lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1;
   if (b16) {
     // hidden2out through the bf16 images: gy -> (gy, gyT); dW = gyT . topT^T, d out_top = gy . W_lastT^T
     CHK(e->gy_b.ensure(N, Do, true));
     CHK(cast_transpose(gy, Do, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = e->l_in_b[Lc];
+    B16Img& top = W.l_in_b[Lc];
     CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, dirs * H, G.last.dW, G.last.db, acc, e->slabs, s));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * dirs * H + Do, s));
     GemmB16Args g = b16_args();
-    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = e->lsh[Lc].wt.as<__bf16>(); g.ldb = e->lsh[Lc].ldwt;
+    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = W.lsh[Lc].wt.as<__bf16>(); g.ldb = W.lsh[Lc].ldwt;
     g.M = (int)N; g.N = dirs * H; g.K = Do; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dout; g.ldc = dirs * H;
     CHK(launch_gemm_b16(g, 1, s));
   } else {
   // hidden2out: dW = gy^T out_top, db, d out_top = gy W
-  CHK(linear_backward_weight(gy, Do, e->l_out[Lc - 1].as<float>(), dirs * H, N, Do, dirs * H, G.last.dW, G.last.db, acc, e->slabs,
+  CHK(linear_backward_weight(gy, Do, W.out[Lc - 1].as<float>(), dirs * H, N, Do, dirs * H, G.last.dW, G.last.db, acc, e->slabs,
                              e->colp, s));
   CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * dirs * H + Do, s));
   CHK(linear_backward_data(gy, Do, G.last.W, G.last.in, 0, dout, dirs * H, N, Do, dirs * H, ACT_NONE, nullptr, 0, no_drop(), s));
@@ -312,7 +305,7 @@ int lstm_backward(gt_engine* e, const float* x, const float* gy, int B, int T, h
 int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, bool want_w,
                         float* dx0, hipStream_t s) {
   Net& G = e->net[role];
-  LstmBufs W = lstm_bufs(e, role);
+  NetWs& W = e->ws[role];
   const int B = nseq;
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, Lc = G.d.num_hidden;
@@ -321,14 +314,14 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
   CHK(W.hshift.ensure((size_t)N * H * sizeof(float)));
   float* dout = W.dout.as<float>();                          // gradient w.r.t. the current layer's output
   float* dout_other = dout + (size_t)N * dirs * H;
-  const bool b16 = role == GT_ROLE_G && lstm_b16(e) && (int)e->l_in_b.size() == Lc + 1 && (int)e->lsh.size() == Lc + 1;
+  const bool b16 = role == GT_ROLE_G && lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1;
   // (A side stream for a layer's weight-gradient products -- beside the recurrence of the layer below -- was built in round 3, measured not to
   //  pay (cfg3 fp32 25.74 vs 25.68 ms, bf16 19.04 vs 18.14: the products' operand traffic slows every step of the recurrence by what the
   //  overlap hides) and left the library in round 6.)
   hipStream_t ws = s;
   Scratch& wsl = e->slabs;
   Scratch& wcp = e->colp;
-  if (b16) e->l_dg_b.resize(Lc);
+  if (b16) W.l_dg_b.resize(Lc);
   for (int l = Lc - 1; l >= 0; --l) {
     const LstmLayerP& L = G.lstm[l];
     bool seq = false;
@@ -337,18 +330,18 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
     const float* dG = W.xproj[l].as<float>();
     const bool dropped_in = l > 0 && G.training && G.d.dropout > 0.f;
     if (b16) {
-      B16Img& DG0 = e->l_dg_b[l];
+      B16Img& DG0 = W.l_dg_b[l];
       CHK(DG0.ensure(N, dirs * 4 * H, true));
       CHK(cast_transpose(dG, dirs * 4 * H, N, dirs * 4 * H, DG0.r(), DG0.ld, DG0.t(), DG0.ldt, nullptr, false, &e->colp, s));
     }
     if (b16) {
       // dG -> bf16 image in both orientations (one pass), then every product of this layer reads bf16:
       // dW_ih_d = dGT_d . inT^T (+ db from the loader), dW_hh_d = dGT_d . hshiftT^T, d in = dG . W_ihT^T (all directions in ONE product)
-      B16Img& DG = e->l_dg_b[l];
-      B16Img& I = e->l_in_b[l];
+      B16Img& DG = W.l_dg_b[l];
+      B16Img& I = W.l_in_b[l];
       if (l > 0) {      // the step stream's part first: d(layer input), all directions in ONE product
         GemmB16Args g = b16_args();
-        g.A = DG.r(); g.lda = DG.ld; g.B = e->lsh[l].wt.as<__bf16>(); g.ldb = e->lsh[l].ldwt;
+        g.A = DG.r(); g.lda = DG.ld; g.B = W.lsh[l].wt.as<__bf16>(); g.ldb = W.lsh[l].ldwt;
         g.M = (int)N; g.N = L.in; g.K = dirs * 4 * H; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dout_other; g.ldc = L.in;
         CHK(launch_gemm_b16(g, 1, s));
         if (dropped_in) {
@@ -371,9 +364,9 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
         hipLaunchKernelGGL(lstm_shift_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, ws, W.out[l].as<float>(), dirs * H, d, H, B, T,
                            e->d_lengths(), W.hshift.as<float>());
         LAUNCH_CHECK();
-        CHK(e->l_hs_b.ensure(N, H, true));
-        CHK(cast_transpose(W.hshift.as<float>(), H, N, H, (__bf16*)nullptr, 0, e->l_hs_b.t(), e->l_hs_b.ldt, nullptr, false, &wcp, ws));
-        CHK(weight_grad_b16(dgt, DG.ldt, e->l_hs_b.t(), e->l_hs_b.ldt, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, wsl, ws));
+        CHK(W.l_hs_b.ensure(N, H, true));
+        CHK(cast_transpose(W.hshift.as<float>(), H, N, H, (__bf16*)nullptr, 0, W.l_hs_b.t(), W.l_hs_b.ldt, nullptr, false, &wcp, ws));
+        CHK(weight_grad_b16(dgt, DG.ldt, W.l_hs_b.t(), W.l_hs_b.ldt, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, wsl, ws));
       }
       CHK(comm_grads_ready(e, role, L.d[0].dWih, (long)dirs * (4L * H * L.in + 4L * H * H + 8L * H), ws));
       CHK(comm_flush(e, role, ws));

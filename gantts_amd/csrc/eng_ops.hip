@@ -173,7 +173,7 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
     if (mse) {      // sum(mask) and its reciprocal, as ensure_tv puts them there; the step's memo of it no longer holds
       hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, c->mask, c->B * c->T, -1.f, (const double*)nullptr, e->sc());
       LAUNCH_CHECK();
-      e->tv_mask = nullptr; e->tv_n = 0;
+      e->tv.forget();
     }
     r = mlpg_backward(e, c->gs, c->ldgs, scol, sstride, Ds, c->gy, c->ldgy, c->B, c->T, mse ? c->mse_w : 0.f, mse ? c->yhat : nullptr,
                       mse ? c->ytgt : nullptr, mse ? c->ldt : 0, mse ? c->mask : nullptr, s);

@@ -34,24 +34,8 @@ uint32_t sru_drop_thresh(float p) {
   return th >= 4294967295.0 ? 4294967295u : (uint32_t)th;
 }
 
-// The stashes of one role's SRU stack.  The discriminator has its own: the generator's forward stash has to survive both discriminator
-// passes of a step (update_generator back-propagates it last); the D-step stash is dead after the D step and the G-step pass reuses it.
-// omask: the discriminator's output-dropout keep tables [nseq][ncols] (0 / 1), one table for all row groups of a launch.
-// in_b / ssh / du_b: the bf16 images, weight shadows and dU image of the role's bf16 path -- role-owned as well: the generator's
-// in_b[l].t() and ssh[l] are read by sru_backward after both discriminator passes of a step.
-struct SruBufs {
-  std::vector<Scratch>&u, &h, &c, &xdrop, &xmask, &wt;
-  std::vector<Scratch>* omask;
-  Scratch& dout;
-  std::vector<B16Img>& in_b;
-  std::vector<LinShadow>& ssh;
-  B16Img& du_b;
-};
-static SruBufs sru_bufs(gt_engine* e, int role) {
-  if (role == GT_ROLE_G) return SruBufs{e->s_u, e->s_h, e->s_c, e->s_xdrop, e->s_xmask, e->s_wt, nullptr, e->l_dout, e->s_in_b, e->ssh, e->s_du_b};
-  return SruBufs{e->ds_u, e->ds_h, e->ds_c, e->ds_xdrop, e->ds_xmask, e->ds_wt, &e->ds_omask, e->dl_dout, e->ds_in_b, e->dssh, e->ds_du_b};
-}
-// entries of in_b / ssh: one per layer; the generator has one more for hidden2out's product (a discriminator's top h goes to the fused
+// (the stashes, images and shadows are the role's own, e->ws[role]: NetWs in engine_internal.hip.h)
+// entries of s_in_b / ssh: one per layer; the generator has one more for hidden2out's product (a discriminator's top h goes to the fused
 // head as float32, which holds hidden2out and its gradient)
 static int sru_b16_entries(const gt_engine* e, int role) { return e->net[role].d.num_hidden + (role == GT_ROLE_G ? 1 : 0); }
 
@@ -70,7 +54,7 @@ static int sru_draw_table(gt_engine* e, const Net& G, int role, int l, int which
   return GT_OK;
 }
 
-static SruArgs sru_args(gt_engine* e, int role, const SruBufs& W, int l, int B, int T, const float* in, int ld_in) {
+static SruArgs sru_args(gt_engine* e, int role, NetWs& W, int l, int B, int T, const float* in, int ld_in) {
   const Net& G = e->net[role];
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs;
   const SruLayerP& L = G.sru[l];
@@ -88,7 +72,7 @@ static SruArgs sru_args(gt_engine* e, int role, const SruBufs& W, int l, int B, 
       sru_keys(e, GT_ROLE_G, 0, l, 1, &a.key0, &a.key1);
       a.mask_buf = G.inj[0][2 * l + 1];                              // gt_set_dropout_mask(G, 0, 2*l + 1): [B][ncols]
     } else {
-      a.mask_buf = (*W.omask)[l].as<float>();                        // drawn per pass by the forward (sru_draw_table): [nseq][ncols] of 0 / 1
+      a.mask_buf = W.omask[l].as<float>();                           // drawn per pass by the forward (sru_draw_table): [nseq][ncols] of 0 / 1
     }
   }
   return a;
@@ -201,7 +185,7 @@ static bool sru_fold(const gt_engine* e, int role, int nseq, int T) {
 int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq, int T, const int* passes, int npass, hipStream_t s,
                       const float** top, int* ld_top, const CatSrc* cat0, bool want_w) {
   Net& G = e->net[role];
-  SruBufs W = sru_bufs(e, role);
+  NetWs& W = e->ws[role];
   const SruPrecScope prec(role);
   const int B = nseq;
   const long N = (long)B * T;
@@ -216,7 +200,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
   const int Lc_ = G.d.num_hidden, nent = sru_b16_entries(e, role);
   if (!(b16 && cat0) && !x) return fail(GT_ERR_INVALID, "SRU stack: null input");
   if (b16) {      // the shadows are re-made at every call: a discriminator's weights change between the two passes of one step
-    W.in_b.resize(nent); W.ssh.resize(nent);
+    W.s_in_b.resize(nent); W.ssh.resize(nent);
     for (int l = 0; l < nent; ++l) {
       LinShadow& w = W.ssh[l];
       const float* Wl = l < Lc_ ? G.sru[l].W : G.last.W;
@@ -238,10 +222,10 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       CHK(sru_draw_table(e, G, role, l, 0, W.xmask[l].as<float>(), B, L.in, G.d.rnn_dropout, 1.f / (1.f - G.d.rnn_dropout), passes, npass, s));
     }
   }
-  if (W.omask && G.training && G.d.dropout > 0.f) {      // a discriminator's output-dropout keep tables (the generator's scans draw theirs inline)
+  if (role != GT_ROLE_G && G.training && G.d.dropout > 0.f) {      // a discriminator's output-dropout keep tables (the generator's scans draw theirs inline)
     for (int l = 0; l + 1 < G.d.num_hidden; ++l) {
-      CHK((*W.omask)[l].ensure((size_t)B * ncols * sizeof(float)));
-      CHK(sru_draw_table(e, G, role, l, 1, (*W.omask)[l].as<float>(), B, ncols, G.d.dropout, 1.f, passes, npass, s));
+      CHK(W.omask[l].ensure((size_t)B * ncols * sizeof(float)));
+      CHK(sru_draw_table(e, G, role, l, 1, W.omask[l].as<float>(), B, ncols, G.d.dropout, 1.f, passes, npass, s));
     }
   }
   bool img_ready = false;       // the current layer's input images were written by the scan underneath
@@ -260,7 +244,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       ld_xin = L.in;
     }
     if (b16) {
-      B16Img& I = W.in_b[l];
+      B16Img& I = W.s_in_b[l];
       CHK(I.ensure(N, L.in, want_t));
       if (img_ready) {
         // written by the scan of the layer underneath (SruArgs::nx_*): no cast pass
@@ -307,7 +291,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       const int nl = l + 1;
       const int n_in_next = nl < Lc_ ? G.sru[nl].in : G.last.in;
       if (nl < nent && n_in_next == ncols) {      // (a discriminator's top layer writes none: the fused head reads the float32 h)
-        B16Img& NI = W.in_b[nl];
+        B16Img& NI = W.s_in_b[nl];
         CHK(NI.ensure(N, ncols, want_t));
         a.nx_b = NI.r(); a.ld_nxb = NI.ld; a.nx_bt = want_t ? NI.t() : (__bf16*)nullptr; a.ld_nxbt = NI.ldt;
         a.nx_mul = (nl < Lc_ && rdrop_all) ? W.xmask[nl].as<float>() : (const float*)nullptr;
@@ -325,6 +309,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
 // x (N, in_dim) -> y_hat (N, out_dim): the generator's stack + hidden2out
 int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
+  NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
   const int Lc_ = G.d.num_hidden;
   const bool b16 = sru_b16(e, GT_ROLE_G);
@@ -335,12 +320,12 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
   int ld_in = 0;
   CHK(sru_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &in, &ld_in));
   if (b16) {
-    B16Img& I = e->s_in_b[Lc_];
+    B16Img& I = W.s_in_b[Lc_];
     CHK(I.ensure(N, G.last.in, want_t));
     if (!img_ready)      // (else: written by the last layer's scan)
       CHK(cast_transpose(in, ld_in, N, G.last.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
     GemmB16Args g = b16_args();
-    g.A = I.r(); g.lda = I.ld; g.B = e->ssh[Lc_].w.as<__bf16>(); g.ldb = e->ssh[Lc_].ldw;    // hidden2out.weight (out, ncols): k = ncols contiguous
+    g.A = I.r(); g.lda = I.ld; g.B = W.ssh[Lc_].w.as<__bf16>(); g.ldb = W.ssh[Lc_].ldw;    // hidden2out.weight (out, ncols): k = ncols contiguous
     g.M = (int)N; g.N = G.last.out; g.K = G.last.in; g.bias = G.last.b; g.epi = B16_FWD;
     g.act = G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = y_hat; g.ldc = G.d.out_dim;
     return launch_gemm_b16(g, 1, s);
@@ -352,26 +337,27 @@ int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStr
 // gy (N, out_dim) = dL/dy_hat -> parameter gradients of hidden2out and of every SRU layer of the generator
 int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
+  NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Do = G.d.out_dim, Lc = G.d.num_hidden;
   const bool acc = G.grads_dirty;
   int inmax = ncols;
   for (auto& L : G.sru) inmax = std::max(inmax, L.in);
-  CHK(e->l_dout.ensure((size_t)2 * N * std::max(ncols, inmax) * sizeof(float)));
-  float* dh = e->l_dout.as<float>();
-  const bool b16 = sru_b16(e, GT_ROLE_G) && (int)e->s_in_b.size() == Lc + 1 && (int)e->ssh.size() == Lc + 1;
+  CHK(W.dout.ensure((size_t)2 * N * std::max(ncols, inmax) * sizeof(float)));
+  float* dh = W.dout.as<float>();
+  const bool b16 = sru_b16(e, GT_ROLE_G) && (int)W.s_in_b.size() == Lc + 1 && (int)W.ssh.size() == Lc + 1;
   if (b16) {
     CHK(e->gy_b.ensure(N, Do, true));
     CHK(cast_transpose(gy, Do, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = e->s_in_b[Lc];
+    B16Img& top = W.s_in_b[Lc];
     CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, ncols, G.last.dW, G.last.db, acc, e->slabs, s));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * ncols + Do, s));
     GemmB16Args g = b16_args();
-    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = e->ssh[Lc].wt.as<__bf16>(); g.ldb = e->ssh[Lc].ldwt;   // hidden2out.weight^T [ncols][Do]
+    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = W.ssh[Lc].wt.as<__bf16>(); g.ldb = W.ssh[Lc].ldwt;   // hidden2out.weight^T [ncols][Do]
     g.M = (int)N; g.N = ncols; g.K = Do; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dh; g.ldc = ncols;
     CHK(launch_gemm_b16(g, 1, s));
   } else {
-  CHK(linear_backward_weight(gy, Do, e->s_h[Lc - 1].as<float>(), ncols, N, Do, ncols, G.last.dW, G.last.db, acc, e->slabs, e->colp, s));
+  CHK(linear_backward_weight(gy, Do, W.h[Lc - 1].as<float>(), ncols, N, Do, ncols, G.last.dW, G.last.db, acc, e->slabs, e->colp, s));
   CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * ncols + Do, s));
   CHK(linear_backward_data(gy, Do, G.last.W, G.last.in, 0, dh, ncols, N, Do, ncols, ACT_NONE, nullptr, 0, no_drop(), s));
   }
@@ -387,7 +373,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
                        float* dx_adv, hipStream_t s) {
   (void)passes;      // (the passes' dropout tables are the forward's stash)
   Net& G = e->net[role];
-  SruBufs W = sru_bufs(e, role);
+  NetWs& W = e->ws[role];
   const SruPrecScope prec(role);
   const int B = nseq;
   const long N = (long)B * T;
@@ -405,7 +391,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
   float* dh = W.dout.as<float>();
   float* dh_other = dh + (size_t)N * dh_pitch;
   const int nent = sru_b16_entries(e, role);
-  const bool b16 = sru_b16(e, role) && (int)W.in_b.size() == nent && (int)W.ssh.size() == nent;
+  const bool b16 = sru_b16(e, role) && (int)W.s_in_b.size() == nent && (int)W.ssh.size() == nent;
   for (int l = Lc - 1; l >= 0; --l) {
     const SruLayerP& L = G.sru[l];
     const float* in = l == 0 ? x : W.h[l - 1].as<float>();
@@ -451,7 +437,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
     if (b16) {
       // dW = xinT . dUT^T over the frames, d in = dU . W^T
       B16Img& DU = W.du_b;
-      B16Img& I = W.in_b[l];
+      B16Img& I = W.s_in_b[l];
       CHK(weight_grad_b16(I.t(), I.ldt, DU.t(), DU.ldt, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs, s));
     } else {
     // dW = xin^T dU   (TN: A = xin is m-contiguous over n_in, B = dU)

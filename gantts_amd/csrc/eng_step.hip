@@ -234,27 +234,33 @@ struct FirstSplit {
   const float* adv; int ld_adv;        // [rows][ld_adv]: the pass's adversarial columns, 16-byte pitch
   long wrap;
 };
-// a caller tensor's rows with a 16-byte pitch: the tensor itself when it already has one, else a copy made once per step
-static int pitched_rows(gt_engine* e, int slot, const float* p, int ld, int cols, long rows, const float** out, int* ldo, hipStream_t s) {
-  if (gemm_vec_ok(p, ld)) { *out = p; *ldo = ld; return GT_OK; }
-  gt_engine::Pitched& P = e->pitched[slot];
-  const int ldp = (cols + 3) & ~3;
-  if (!(P.src == p && P.ld == ld && P.cols == cols && P.rows == rows && P.step == e->step_counter)) {
-    CHK(P.buf.ensure((size_t)rows * ldp * sizeof(float)));
-    hipLaunchKernelGGL(repitch_kernel, dim3(cdiv(rows * (ldp / 4), 256)), dim3(256), 0, s, p, ld, cols, rows, P.buf.as<float>(), ldp);
+// M's copy of p [rows][cols] (row pitch ld) with row pitch ldo, dense or with a 16-byte pitch: made unless M holds it already, i.e. once per step.
+// (the key: source pointer, pitch, columns, rows, step -- ADVICE r5: the pointer and the step alone served a too small copy to a caller that
+//  changed B*T between two update_* calls of one step.  The CONTENTS of p are not part of it: a tensor refilled in place within a step is not seen.)
+static int step_copy(gt_engine* e, StepCopy& M, const float* p, int ld, int cols, long rows, int ldo, bool dense, const float** out, hipStream_t s) {
+  if (!M.holds(p, ld, cols, rows, e->step_counter)) {
+    CHK(M.buf.ensure((size_t)rows * ldo * sizeof(float)));
+    if (dense) hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(rows * cols, 256)), dim3(256), 0, s, p, ld, 0, (const int*)nullptr, M.buf.as<float>(), ldo, 0, (int)rows, cols);
+    else hipLaunchKernelGGL(repitch_kernel, dim3(cdiv(rows * (ldo / 4), 256)), dim3(256), 0, s, p, ld, cols, rows, M.buf.as<float>(), ldo);
     LAUNCH_CHECK();
-    P.src = p; P.ld = ld; P.cols = cols; P.rows = rows; P.step = e->step_counter;
+    M.built(p, ld, cols, rows, e->step_counter);
   }
-  *out = P.buf.as<float>(); *ldo = ldp;
+  *out = M.buf.as<float>();
   return GT_OK;
+}
+// a caller tensor's rows with a 16-byte pitch: the tensor itself when it already has one, else M's copy
+static int pitched_rows(gt_engine* e, StepCopy& M, const float* p, int ld, int cols, long rows, const float** out, int* ldo, hipStream_t s) {
+  if (gemm_vec_ok(p, ld)) { *out = p; *ldo = ld; return GT_OK; }
+  *ldo = (cols + 3) & ~3;
+  return step_copy(e, M, p, ld, cols, rows, *ldo, false, out, s);
 }
 
 // hidden stack forward: in -> acts[0..L-1]; returns specs used (for backward)
-static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, long rows, std::vector<Scratch>& acts,
-                         const int* passes, int npass, long rows_each, std::vector<DropoutSpec>& specs, hipStream_t s,
+static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, long rows, const int* passes, int npass, long rows_each, std::vector<DropoutSpec>& specs, hipStream_t s,
                          const FirstSplit* fs = nullptr, int max_layers = 1 << 30 /* launch only the first max_layers layers (the dropout
                          sites and the stash buffers of ALL layers are still set up: the fused stack launch takes over from there) */) {
   Net& n = e->net[role];
+  std::vector<Scratch>& acts = e->ws[role].act;
   specs.resize(n.hidden.size());
   const float* cur = in;
   int ld = ld_in;
@@ -302,10 +308,10 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
       // floats) do not: multiply by a copy of W with its row pitch rounded up to 4 floats, re-made from the caller's
       // parameter buffer before every pass (it may have been stepped, loaded or broadcast since).
       ldw = (L.in + 3) & ~3;
-      CHK(e->w0pad[role].ensure((size_t)L.out * ldw * sizeof(float)));
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv((long)L.out * ldw, 256)), dim3(256), 0, s, L.W, L.in, L.out, e->w0pad[role].as<float>(), ldw);
+      CHK(e->ws[role].w0pad.ensure((size_t)L.out * ldw * sizeof(float)));
+      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv((long)L.out * ldw, 256)), dim3(256), 0, s, L.W, L.in, L.out, e->ws[role].w0pad.as<float>(), ldw);
       LAUNCH_CHECK();
-      W = e->w0pad[role].as<float>();
+      W = e->ws[role].w0pad.as<float>();
     }
     CHK(linear_forward(cur, ld, W, ldw, L.b, acts[l].as<float>(), L.out, rows, L.in, L.out, ACT_LEAKY_DROPOUT, specs[l], s));
     cur = acts[l].as<float>();
@@ -322,10 +328,10 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
 // hidden stack backward.  dz_top: gradient w.r.t. the pre-activation of the TOP hidden layer
 // (already multiplied by f'), in buffer `cur` (rows x hidden).  Produces dW/db (if want_w) and,
 // optionally, dX[:, col0:col0+ncols] of the stack input for rows [row0, row0+nrows).
-static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, long rows, std::vector<Scratch>& acts,
-                          const std::vector<DropoutSpec>& specs, float* cur, float* other, bool want_w,
+static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, long rows, const std::vector<DropoutSpec>& specs, float* cur, float* other, bool want_w,
                           float* dX, int lddx, int col0, int ncols, long row0, long nrows, hipStream_t s, const FirstSplit* fs = nullptr) {
   Net& n = e->net[role];
+  std::vector<Scratch>& acts = e->ws[role].act;
   const int L = (int)n.hidden.size();
   // per-layer launches: each layer's weight gradient right behind the product that made its dZ (still warm in L2 / MALL)
   for (int l = L - 1; l >= 0; --l) {
@@ -341,10 +347,10 @@ static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, lo
       GemmArgs leak;
       if (dX) leak = backward_data_args(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0, no_drop());
       CHK(linear_backward_weight_split(cur, Lr.out, rows, fs->wrap, fs->xp, fs->ldxp, fs->cd, fs->adv, fs->ld_adv, Lr.in - fs->cd, Lr.out,
-                                       Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->sdefer[role], dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
+                                       Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->ws[role].sdefer, dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
       CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
     } else if (want_w) {
-      CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, s, &e->sdefer[role],
+      CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, s, &e->ws[role].sdefer,
                                  l > 0 ? &nn : nullptr, &rode));
       CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
       // generator: all layers above the first leave as one message under the first layer's backward; the discriminator's
@@ -374,7 +380,7 @@ static bool use_b16(const gt_engine* e, int role) {
 // re-made from the caller's float32 parameters before every pass (they may have been stepped, loaded or broadcast since)
 static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s) {
   Net& n = e->net[role];
-  auto& sh = e->wsh[role];
+  auto& sh = e->ws[role].wsh;
   sh.resize(n.hidden.size() + 1);
   CastJobs jobs;
   jobs.n = 0; jobs.pad_ = 0;
@@ -397,9 +403,11 @@ static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s
   return flush();
 }
 // in_b [rows][ld_in] bf16 -> acts[l] (bf16, + transposed twin when want_t: the weight gradients read it)
-static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_in, long rows, std::vector<B16Img>& acts,
-                             const int* passes, int npass, long rows_each, std::vector<DropoutSpec>& specs, bool want_t, hipStream_t s) {
+static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_in, long rows, const int* passes, int npass, long rows_each,
+                             std::vector<DropoutSpec>& specs, bool want_t, hipStream_t s) {
   Net& n = e->net[role];
+  std::vector<B16Img>& acts = e->ws[role].actb;
+  const std::vector<LinShadow>& wsh = e->ws[role].wsh;
   specs.resize(n.hidden.size());
   acts.resize(n.hidden.size());
   const __bf16* cur = in_b;
@@ -411,7 +419,7 @@ static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_
     CHK(stage_injected(e, role, (int)l, passes, npass, rows_each, L.out, &inj, s));
     specs[l] = drop_spec(e, role, passes[0], (int)l, inj, L.out, npass == 2 ? rows_each : 0);
     GemmB16Args g = b16_args();
-    g.A = cur; g.lda = ld; g.B = e->wsh[role][l].w.as<__bf16>(); g.ldb = e->wsh[role][l].ldw;
+    g.A = cur; g.lda = ld; g.B = wsh[l].w.as<__bf16>(); g.ldb = wsh[l].ldw;
     g.M = (int)rows; g.N = L.out; g.K = L.in; g.bias = L.b; g.epi = B16_FWD; g.act = ACT_LEAKY_DROPOUT; g.drop = specs[l];
     g.Cb = acts[l].r(); g.ldcb = acts[l].ld;
     if (want_t) { g.CbT = acts[l].t(); g.ldcbt = (int)acts[l].ldt; }
@@ -424,18 +432,18 @@ static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_
 // dz[cur]: gradient w.r.t. the pre-activation of the TOP hidden layer (both orientations when want_w).  in_t: transposed
 // image of the stack input [in][rows8] (weight gradient of layer 0).  dX (float32, optional): d loss / d input columns
 // [col0, col0 + ncols) for rows [row0, row0 + nrows).
-static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long ld_int, long rows, std::vector<B16Img>& acts,
-                              const std::vector<DropoutSpec>& specs, int cur, bool want_w, float* dX, int lddx, int col0, int ncols,
-                              long row0, long nrows, hipStream_t s) {
+static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long ld_int, long rows, const std::vector<DropoutSpec>& specs, int cur, bool want_w,
+                              float* dX, int lddx, int col0, int ncols, long row0, long nrows, hipStream_t s) {
   Net& n = e->net[role];
-  const int L = (int)n.hidden.size();
-  for (int l = L - 1; l >= 0; --l) {
+  std::vector<B16Img>& acts = e->ws[role].actb;
+  const std::vector<LinShadow>& wsh = e->ws[role].wsh;
+  for (int l = (int)n.hidden.size() - 1; l >= 0; --l) {
     const Lin& Lr = n.hidden[l];
     B16Img& dz = e->dz_b[cur];
     if (want_w) {
       const __bf16* XT = l > 0 ? acts[l - 1].t() : in_t;
       const long ldxt = l > 0 ? acts[l - 1].ldt : ld_int;
-      CHK(weight_grad_b16(dz.t(), dz.ldt, XT, ldxt, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->sdefer[role]));
+      CHK(weight_grad_b16(dz.t(), dz.ldt, XT, ldxt, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->ws[role].sdefer));
       CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
       if (l == 1 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
     }
@@ -443,7 +451,7 @@ static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long l
       B16Img& nx = e->dz_b[cur ^ 1];
       CHK(nx.ensure(rows, Lr.in, want_w));
       GemmB16Args g = b16_args();
-      g.A = dz.r(); g.lda = dz.ld; g.B = e->wsh[role][l].wt.as<__bf16>(); g.ldb = e->wsh[role][l].ldwt;
+      g.A = dz.r(); g.lda = dz.ld; g.B = wsh[l].wt.as<__bf16>(); g.ldb = wsh[l].ldwt;
       g.M = (int)rows; g.N = Lr.in; g.K = Lr.out; g.epi = B16_BWD_DATA; g.act = ACT_LEAKY_DROPOUT;
       g.H = acts[l - 1].r(); g.ldh = acts[l - 1].ld; g.drop = specs[l - 1];
       g.Cb = nx.r(); g.ldcb = nx.ld;
@@ -453,7 +461,7 @@ static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long l
     } else if (dX) {
       GemmB16Args g = b16_args();
       g.A = dz.r() + row0 * dz.ld; g.lda = dz.ld;
-      g.B = e->wsh[role][0].wt.as<__bf16>() + (long)col0 * e->wsh[role][0].ldwt; g.ldb = e->wsh[role][0].ldwt;
+      g.B = wsh[0].wt.as<__bf16>() + (long)col0 * wsh[0].ldwt; g.ldb = wsh[0].ldwt;
       g.M = (int)nrows; g.N = ncols; g.K = Lr.out; g.epi = B16_BWD_DATA; g.act = ACT_NONE;
       g.C = dX; g.ldc = lddx;
       CHK(launch_gemm_b16(g, 1, s));
@@ -462,11 +470,12 @@ static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long l
   return GT_OK;
 }
 // last_linear of a bf16-storage MLP: out [rows][out_dim] (float32) = act(acts.back() . W_last^T + b), W_last's shadow from refresh_shadows(with_last)
-static int last_forward_b16(gt_engine* e, int role, std::vector<B16Img>& acts, long rows, float* out, hipStream_t s) {
+static int last_forward_b16(gt_engine* e, int role, long rows, float* out, hipStream_t s) {
   Net& n = e->net[role];
-  const LinShadow& ws = e->wsh[role][n.hidden.size()];
+  B16Img& top = e->ws[role].actb.back();
+  const LinShadow& ws = e->ws[role].wsh[n.hidden.size()];
   GemmB16Args g = b16_args();
-  g.A = acts.back().r(); g.lda = acts.back().ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
+  g.A = top.r(); g.lda = top.ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
   g.M = (int)rows; g.N = n.last.out; g.K = n.last.in; g.bias = n.last.b; g.epi = B16_FWD;
   g.act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = out; g.ldc = n.d.out_dim;
   return launch_gemm_b16(g, 1, s);
@@ -496,17 +505,7 @@ static int dense_cx(gt_engine* e, const float** x, long N, hipStream_t s) {
   if (!*x || !e->cfg.discriminator_linguistic_condition || e->ld_cx <= 0 || e->ld_cx == cond_dim(e)) return GT_OK;
   const int cd = cond_dim(e);
   if (e->ld_cx < cd) return fail(GT_ERR_INVALID, "gt_set_x_pitch: pitch %d for %d conditioning columns", e->ld_cx, cd);
-  // (the key: source pointer, step, rows, pitch, columns -- ADVICE r5: the pointer and the step alone served a too small copy to a caller that
-  //  changed B*T between two update_* calls of one step.  The CONTENTS of x are not part of it: x refilled in place within a step is not seen.)
-  if (!(e->cxd_src == *x && e->cxd_step == e->step_counter && e->cxd_rows == N && e->cxd_ld == e->ld_cx && e->cxd_cols == cd && e->cx_dense.p)) {
-    CHK(e->cx_dense.ensure((size_t)N * cd * sizeof(float)));
-    hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * cd, 256)), dim3(256), 0, s, *x, e->ld_cx, 0, (const int*)nullptr,
-                       e->cx_dense.as<float>(), cd, 0, (int)N, cd);
-    LAUNCH_CHECK();
-    e->cxd_src = *x; e->cxd_step = e->step_counter; e->cxd_rows = N; e->cxd_ld = e->ld_cx; e->cxd_cols = cd;
-  }
-  *x = e->cx_dense.as<float>();
-  return GT_OK;
+  return step_copy(e, e->cx_dense, *x, e->ld_cx, cd, N, cd, true, x, s);
 }
 
 static int generator_forward(gt_engine* e, const float* x, const float* R, int B, int T, float* y_hat, float* y_hat_static,
@@ -535,12 +534,12 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
       CHK(cast_transpose(x, G.d.in_dim, N, G.d.in_dim, e->xin_b.r(), e->xin_b.ld, want_t ? e->xin_b.t() : (__bf16*)nullptr, e->xin_b.ldt,
                                 nullptr, false, &e->colp, s));
       CHK(refresh_shadows(e, GT_ROLE_G, true, s));
-      CHK(stack_forward_b16(e, GT_ROLE_G, e->xin_b.r(), e->xin_b.ld, N, e->g_actb, pass0, 1, N, specs, want_t, s));
-      CHK(last_forward_b16(e, GT_ROLE_G, e->g_actb, N, y_hat, s));
+      CHK(stack_forward_b16(e, GT_ROLE_G, e->xin_b.r(), e->xin_b.ld, N, pass0, 1, N, specs, want_t, s));
+      CHK(last_forward_b16(e, GT_ROLE_G, N, y_hat, s));
     } else {
-      CHK(stack_forward(e, GT_ROLE_G, x, gx_pitch(e), N, e->g_act, pass0, 1, N, specs, s));
+      CHK(stack_forward(e, GT_ROLE_G, x, gx_pitch(e), N, pass0, 1, N, specs, s));
       const Lin& Lh = G.hidden.back();
-      CHK(linear_forward(e->g_act.back().as<float>(), Lh.out, G.last.W, G.last.in, G.last.b, y_hat, G.d.out_dim, N, G.last.in,
+      CHK(linear_forward(e->ws[GT_ROLE_G].act.back().as<float>(), Lh.out, G.last.W, G.last.in, G.last.b, y_hat, G.d.out_dim, N, G.last.in,
                          G.last.out, G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s));
     }
   }
@@ -587,9 +586,9 @@ extern "C" int gt_apply_generator(gt_engine* e, const float* x, const float* R, 
   e->step_counter++;
   e->B = B; e->T = T; e->N = (long)B * T;
   e->g_pass_valid = false;
-  invalidate_d_images(e); e->cxd_src = nullptr;
-  e->tv_mask = nullptr; e->tv_inflight = false;             // a new batch: the mask contents may have changed
-  CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->g_specs));
+  invalidate_d_images(e); e->cx_dense.forget();
+  e->tv.forget(); e->tv_inflight = false;             // a new batch: the mask contents may have changed
+  CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->ws[GT_ROLE_G].specs));
   e->last_x = e->gx_dense_on ? e->gx_dense.as<float>() : x;      // (what the backward pass reads: the dense copy when one was made)
   e->last_yhat = y_hat; e->last_yhs = y_hat_static;
   e->g_pass_valid = true;
@@ -727,9 +726,10 @@ static bool d_fused_ok(gt_engine* e, long rows) {
     if (D.hidden[l].out != D.d.hidden_dim || (l > 0 && D.hidden[l].in != D.d.hidden_dim)) return false;
   return true;
 }
-// the fused pass over the engine's discriminator (launch_dstack_pass): the stashes go to e->d_act[1 ..], the seed gradient to e->dzA
+// the fused pass over the engine's discriminator (launch_dstack_pass): the stashes go to the discriminator's act[1 ..], the seed gradient to e->dzA
 static int run_dstack(gt_engine* e, const HeadCall& c, float* gadv, hipStream_t s) {
   Net& D = e->net[GT_ROLE_D];
+  NetWs& W = e->ws[GT_ROLE_D];
   const int H = D.d.hidden_dim, L = (int)D.hidden.size();
   const bool d_step = c.mode == HEAD_D_STEP;
   DStackCall k;
@@ -739,11 +739,11 @@ static int run_dstack(gt_engine* e, const HeadCall& c, float* gadv, hipStream_t 
   CHK(e->dout.ensure((size_t)c.rows * sizeof(float)));
   DStackArgs& a = k.a;
   a.L = L;
-  a.H0 = e->d_act[0].as<float>();
-  for (int l = 0; l < L; ++l) { a.W[l] = D.hidden[l].W; a.b[l] = D.hidden[l].b; a.drop[l] = e->d_specs[l]; }
+  a.H0 = W.act[0].as<float>();
+  for (int l = 0; l < L; ++l) { a.W[l] = D.hidden[l].W; a.b[l] = D.hidden[l].b; a.drop[l] = W.specs[l]; }
   a.w_last = D.last.W; a.b_last = D.last.b; a.Dout = e->dout.as<float>();
   if (d_step) {
-    for (int l = 1; l + 1 < L; ++l) a.Hout[l] = e->d_act[l].as<float>();      // (the top layer's activation only feeds the head, which is fused: no stash)
+    for (int l = 1; l + 1 < L; ++l) a.Hout[l] = W.act[l].as<float>();      // (the top layer's activation only feeds the head, which is fused: no stash)
     a.dZtop = e->dzA.as<float>();
   } else {
     a.W0 = D.hidden[0].W; a.ldw0 = D.hidden[0].in; a.col0 = cond_dim(e); a.Da = e->Da; a.gadv = gadv; a.ld_gadv = e->Da;
@@ -786,7 +786,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   // the discriminator's gradient of a GT_OPT_COMM_TV_IN_SUMS step is that of the unnormalised loss: x 1 / Tv in the update kernel
   const float* gscale = (role == GT_ROLE_D && e->d_unnorm) ? &e->sc()->inv_tv : (const float*)nullptr;
   if (role == GT_ROLE_D) e->d_unnorm = false;
-  SlabDefer& sd = e->sdefer[role];
+  SlabDefer& sd = e->ws[role].sdefer;
   if (sd.active && sd.jobs.n > 0) {
     // The fused step recorded this network's weight-gradient combines.  They write disjoint ranges of the flat gradient; whatever
     // they do not cover (the discriminator's last layer, written by the head's reduction) still counts for the norm and is
@@ -832,8 +832,8 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
     }
   }
   const int nblk = (int)std::min<long>(512, cdiv(np, RED_THREADS * 4));
-  CHK(slab_defer_flush(e->sdefer[role], s));            // the fused step's recorded weight-gradient combines, one launch
-  e->sdefer[role].active = false;
+  CHK(slab_defer_flush(sd, s));            // the fused step's recorded weight-gradient combines, one launch
+  sd.active = false;
   hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, n.d.grads, np, part);
   LAUNCH_CHECK();
   n.step += 1;
@@ -987,12 +987,12 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
                          e->d_adv_cols, e->Da, dst, ld, N, p.rows, any_ride ? r.mask : (const float*)nullptr, (int)N, e->tv_override, e->sc(),
                          r.unnorm ? &e->sc()->tv_sum : r.tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr);
       LAUNCH_CHECK();
-      if (r.tv_ride) { e->tv_mask = r.mask; e->tv_n = N; e->tv_ovr = e->tv_override; }
+      if (r.tv_ride) e->tv.note(r.mask, N, e->tv_override);
       if (r.tv_ride_dp) CHK(comm_tv_sent(e, s));          // all-reduce of the count on the communicator's stream, joined in front of the head
       e->img_adv2.built(nullptr, p.fake);
     }
     p.fs.adv = dst;
-    if (p.want_w) CHK(pitched_rows(e, 0, p.x, p.fs.ldx, p.fs.cd, N, &p.fs.xp, &p.fs.ldxp, s));
+    if (p.want_w) CHK(pitched_rows(e, e->dx_pitched, p.x, p.fs.ldx, p.fs.cd, N, &p.fs.xp, &p.fs.ldxp, s));
   } else if (p.needs_f32_image) {
     CHK(e->dcat.ensure((size_t)2 * N * p.ldc * sizeof(float)));
     if (both && p.cat0.cd > 0) {
@@ -1023,11 +1023,11 @@ static int d_pass_forward(gt_engine* e, DPass& p, hipStream_t s) {
       break;
     case D_MLP_B16:
       CHK(refresh_shadows(e, GT_ROLE_D, false, s));        // (G step: D has just been stepped, train.py:276 before :307)
-      CHK(stack_forward_b16(e, GT_ROLE_D, e->dcat_b.r() + (p.npass == 2 ? 0 : p.N) * e->dcat_b.ld, e->dcat_b.ld, p.rows, e->d_actb, p.passes, p.npass, p.N,
-                            e->d_specs, p.want_w, s));
+      CHK(stack_forward_b16(e, GT_ROLE_D, e->dcat_b.r() + (p.npass == 2 ? 0 : p.N) * e->dcat_b.ld, e->dcat_b.ld, p.rows, p.passes, p.npass, p.N,
+                            e->ws[GT_ROLE_D].specs, p.want_w, s));
       break;
     case D_MLP_F32:      // fused: layer 0 alone, the fused stack launch (d_pass_head) takes over from there
-      CHK(stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.rows, e->d_act, p.passes, p.npass, p.N, e->d_specs, s, p.split ? &p.fs : nullptr, p.fused ? 1 : 1 << 30));
+      CHK(stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.rows, p.passes, p.npass, p.N, e->ws[GT_ROLE_D].specs, s, p.split ? &p.fs : nullptr, p.fused ? 1 : 1 << 30));
       break;
   }
   return GT_OK;
@@ -1037,6 +1037,7 @@ static int d_pass_forward(gt_engine* e, DPass& p, hipStream_t s) {
 // dst: where the fused launch of the adversarial term writes the generated rows' adversarial-column gradient (it IS that pass's backward).
 static int d_pass_head(gt_engine* e, DPass& p, const HeadCall& c, float* dst, hipStream_t s) {
   const int H = p.H;
+  NetWs& W = e->ws[GT_ROLE_D];
   CHK(e->dzA.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
   CHK(e->dzB.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
   if (p.fused) return run_dstack(e, c, p.npass == 1 ? dst : nullptr, s);
@@ -1045,15 +1046,15 @@ static int d_pass_head(gt_engine* e, DPass& p, const HeadCall& c, float* dst, hi
   a.K = H; a.has_act = true; a.dH = e->dzA.as<float>();
   switch (p.kind) {
     case D_SRU: case D_LSTM:
-      CHK(e->dl_dout.ensure((size_t)2 * p.rows * H * sizeof(float)));
-      a.H = p.top; a.has_act = false; a.spec = no_drop(); a.dH = e->dl_dout.as<float>();
+      CHK(W.dout.ensure((size_t)2 * p.rows * H * sizeof(float)));
+      a.H = p.top; a.has_act = false; a.spec = no_drop(); a.dH = W.dout.as<float>();
       break;
     case D_MLP_B16:      // the head writes its seed gradient as the top dZ image (both orientations for the weight gradients)
-      a.H = e->d_actb.back().r(); a.h_ld = e->d_actb.back().ld; a.spec = e->d_specs.back();
+      a.H = W.actb.back().r(); a.h_ld = W.actb.back().ld; a.spec = W.specs.back();
       if (c.want_grad) { CHK(e->dz_b[0].ensure(p.rows, H, p.want_w)); a.dz_img = &e->dz_b[0]; a.dz_t = p.want_w; }
       break;
     case D_MLP_F32:
-      a.H = e->d_act.back().as<float>(); a.spec = e->d_specs.back();
+      a.H = W.act.back().as<float>(); a.spec = W.specs.back();
       break;
   }
   return run_head(e, c, a, s);
@@ -1080,10 +1081,10 @@ static int d_pass_backward(gt_engine* e, DPass& p, float* dst, hipStream_t s) {
       return GT_OK;
     }
     case D_MLP_B16:
-      return stack_backward_b16(e, GT_ROLE_D, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr, p.want_w ? e->dcat_b.ldt : 0, p.rows, e->d_actb, e->d_specs, 0,
+      return stack_backward_b16(e, GT_ROLE_D, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr, p.want_w ? e->dcat_b.ldt : 0, p.rows, e->ws[GT_ROLE_D].specs, 0,
                                 p.want_w, dst, Da, col0, Da, row0, N, s);
     case D_MLP_F32:
-      return stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.rows, e->d_act, e->d_specs, e->dzA.as<float>(), e->dzB.as<float>(), p.want_w, dst, Da, col0, Da,
+      return stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.rows, e->ws[GT_ROLE_D].specs, e->dzA.as<float>(), e->dzB.as<float>(), p.want_w, dst, Da, col0, Da,
                             row0, N, s, p.split ? &p.fs : nullptr);
   }
   return GT_OK;
@@ -1105,10 +1106,10 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   CHK(d_pass_plan(e, x, y_static, y_hat_static, e->Ds, 2, B, T, tr, &p));
   if (comm_on(e) && tr && D.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_d.zero_grad() must precede update_discriminator (the gradient buckets are summed over the ranks in place)");
-  e->sdefer[GT_ROLE_D].reset(e->early && tr && D.has_opt);
+  e->ws[GT_ROLE_D].sdefer.reset(e->early && tr && D.has_opt);
   // data parallel: the global count travels under the D forward pass.  With the split first layer its local term is summed by a
   // rider of the gather launch (tv_ride_dp), else by a launch of its own right here.
-  const bool tv_known = e->tv_mask == mask && e->tv_n == N && e->tv_ovr == e->tv_override;
+  const bool tv_known = e->tv.known(mask, N, e->tv_override);
   const bool dp_count = e->early && e->opt_launch_riders && comm_on(e) && !tv_known && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight;
   // GT_OPT_COMM_TV_IN_SUMS: no collective for the count at all -- it leaves with the loss sums (engine_internal.hip.h)
   const bool unnorm = dp_count && e->opt_comm_tv_in_sums && tr && D.has_opt && D.d.grads;
@@ -1135,13 +1136,13 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   hc.ticket = plain_early ? take_ticket(e) : 0;
   hc.unit_tv = unnorm;
   if (unnorm) {      // the normaliser arrives with the sums (finalize_d_kernel on the communicator's stream files it); valid from the join on
-    e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override;
+    e->tv.note(mask, N, e->tv_override);
   } else if (comm_on(e) && e->opt_launch_riders && e->tv_inflight && !tv_known) {
     // data parallel + riders: the head reads the all-reduced count where the collective left it (and files it in the step's scalars):
     // no conversion launch between the join and the head
     CHK(comm_tv_join(e, s));
     hc.tv_dev = e->comm_tv.as<double>();
-    e->tv_mask = mask; e->tv_n = N; e->tv_ovr = e->tv_override;
+    e->tv.note(mask, N, e->tv_override);
   } else CHK(ensure_tv(e, mask, N, s));
   CHK(d_pass_head(e, p, hc, nullptr, s));
   e->early_done = false;
@@ -1239,6 +1240,7 @@ static int sum_sqerr(gt_engine* e, const float* a, int lda, const float* b, int 
 static int generator_backward(gt_engine* e, const float* x, const float* y, const float* y_hat, const float* mask,
                               float mse_w, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
+  NetWs& W = e->ws[GT_ROLE_G];
   const long N = e->N;
   const int B = e->B, T = e->T, Do = G.d.out_dim;
   // dloss/dy_hat is an engine buffer: for the MLP stacks its row pitch is rounded up to 4 floats, so that the last layer's
@@ -1257,8 +1259,7 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     hipLaunchKernelGGL(highway_backward_kernel, dim3(cdiv(N * sd, 256)), dim3(256), 0, s, gs, sd, e->tx.as<float>(), sd,
                        e->gx.as<float>(), sd, e->dgx.as<float>(), sd, e->dtz.as<float>(), sd, N, sd);
     LAUNCH_CHECK();
-    CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs,
-                               e->colp, s, &e->sdefer[GT_ROLE_G]));
+    CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, s, &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.gate.dW, (long)sd * sd + sd, s));
     CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o, e->d_sstride_i2o, sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, s));
   } else if (e->g_used_mlpg) {
@@ -1284,18 +1285,17 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     const int H = G.d.hidden_dim;
     CHK(e->gy_b.ensure(N, Do, true));
     CHK(cast_transpose(gy, ldgy, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = e->g_actb.back();
-    CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty, e->slabs, s,
-                        &e->sdefer[GT_ROLE_G]));
+    B16Img& top = W.actb.back();
+    CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty, e->slabs, s, &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * G.last.in + Do, s));
-    const LinShadow& ws = e->wsh[GT_ROLE_G][G.hidden.size()];
+    const LinShadow& ws = W.wsh[G.hidden.size()];
     CHK(e->dz_b[0].ensure(N, H, true));
     GemmB16Args g = b16_args();
     g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = ws.wt.as<__bf16>(); g.ldb = ws.ldwt; g.M = (int)N; g.N = H; g.K = Do;
-    g.epi = B16_BWD_DATA; g.act = ACT_LEAKY_DROPOUT; g.H = top.r(); g.ldh = top.ld; g.drop = e->g_specs.back();
+    g.epi = B16_BWD_DATA; g.act = ACT_LEAKY_DROPOUT; g.H = top.r(); g.ldh = top.ld; g.drop = W.specs.back();
     g.Cb = e->dz_b[0].r(); g.ldcb = e->dz_b[0].ld; g.CbT = e->dz_b[0].t(); g.ldcbt = (int)e->dz_b[0].ldt;
     CHK(launch_gemm_b16(g, 1, s));
-    CHK(stack_backward_b16(e, GT_ROLE_G, e->xin_b.t(), e->xin_b.ldt, N, e->g_actb, e->g_specs, 0, true, nullptr, 0, 0, 0, 0, 0, s));
+    CHK(stack_backward_b16(e, GT_ROLE_G, e->xin_b.t(), e->xin_b.ldt, N, W.specs, 0, true, nullptr, 0, 0, 0, 0, 0, s));
     G.grads_dirty = true;
     return GT_OK;
   }
@@ -1305,10 +1305,10 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   CHK(e->dzA.ensure((size_t)2 * N * H * sizeof(float)));
   CHK(e->dzB.ensure((size_t)2 * N * H * sizeof(float)));
   const GemmArgs nn_last = backward_data_args(gy, ldgy, G.last.W, G.last.in, 0, e->dzA.as<float>(), H, N, Do, H, ACT_LEAKY_DROPOUT,
-                                              e->g_act.back().as<float>(), H, e->g_specs.back());
+                                              W.act.back().as<float>(), H, W.specs.back());
   bool rode = false;
-  CHK(linear_backward_weight(gy, ldgy, e->g_act.back().as<float>(), Lt.out, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty,
-                             e->slabs, e->colp, s, &e->sdefer[GT_ROLE_G], &nn_last, &rode));
+  CHK(linear_backward_weight(gy, ldgy, W.act.back().as<float>(), Lt.out, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty,
+                             e->slabs, e->colp, s, &W.sdefer, &nn_last, &rode));
   CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * G.last.in + Do, s));
   if (!rode) CHK(launch_gemm(GEMM_NN, nn_last, 1, s));
   // The first layer's weight gradient reads G's input as its n-contiguous frame operand: with a 16-byte pitch it takes the
@@ -1322,11 +1322,11 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
       ldxin = (d_in_dim(e) + 3) & ~3;
       xin = e->dcat.as<float>() + N * ldxin;      // the generated half: the one that is valid whenever img_cat is
     } else {
-      const int slot = (e->pitched[0].src == x && e->pitched[0].ld == gx_pitch(e) && e->pitched[0].cols == G.d.in_dim && e->pitched[0].step == e->step_counter) ? 0 : 1;
-      CHK(pitched_rows(e, slot, x, gx_pitch(e), G.d.in_dim, N, &xin, &ldxin, s));
+      StepCopy& M = e->dx_pitched.holds(x, gx_pitch(e), G.d.in_dim, N, e->step_counter) ? e->dx_pitched : e->gx_pitched;
+      CHK(pitched_rows(e, M, x, gx_pitch(e), G.d.in_dim, N, &xin, &ldxin, s));
     }
   }
-  CHK(stack_backward(e, GT_ROLE_G, xin, ldxin, N, e->g_act, e->g_specs, e->dzA.as<float>(), e->dzB.as<float>(), true,
+  CHK(stack_backward(e, GT_ROLE_G, xin, ldxin, N, W.specs, e->dzA.as<float>(), e->dzB.as<float>(), true,
                      nullptr, 0, 0, 0, 0, 0, s));
   G.grads_dirty = true;
   return GT_OK;
@@ -1352,7 +1352,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   if (comm_on(e) && tr && G.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_g.zero_grad() must precede update_generator");
-  e->sdefer[GT_ROLE_G].reset(e->early && tr && G.has_opt);
+  e->ws[GT_ROLE_G].sdefer.reset(e->early && tr && G.has_opt);
   CHK(ensure_tv(e, mask, N, s));
   // loss_mse (always reported, train.py:294); its gradient is fused into the MLPG^T kernel
   const bool direct = !is_i2o(G.d.arch) && !e->g_used_mlpg;
@@ -1495,7 +1495,7 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   tl_gemm_prec = e->matmul_bf16 ? PREC_BF16 : PREC_F32;      // this entry point launches GEMMs without check_common
   CHK(fault_seen(e));
-  e->sdefer[GT_ROLE_G].reset(false);      // combines run in place here
+  e->ws[GT_ROLE_G].sdefer.reset(false);      // combines run in place here
   const long N = e->N;
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   CHK(e->gs.ensure((size_t)N * Ds * sizeof(float)));
@@ -1553,18 +1553,16 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
     return n.d.arch == GT_ARCH_LSTM ? lstm_forward(e, x, B, T, out, s) : sru_forward(e, x, B, T, out, s);
   }
   const int pass0[1] = {0};
-  auto& acts = role == GT_ROLE_G ? e->g_act : e->d_act;
   if (role == GT_ROLE_G) e->g_pass_valid = false;
   if (use_b16(e, role)) {
-    auto& actb = role == GT_ROLE_G ? e->g_actb : e->d_actb;
     CHK(e->fwd_b.ensure(N, n.d.in_dim, false));
     CHK(cast_transpose(x, n.d.in_dim, N, n.d.in_dim, e->fwd_b.r(), e->fwd_b.ld, (__bf16*)nullptr, 0, nullptr, false, &e->colp, s));
     CHK(refresh_shadows(e, role, true, s));
-    CHK(stack_forward_b16(e, role, e->fwd_b.r(), e->fwd_b.ld, N, actb, pass0, 1, N, specs, false, s));
-    return last_forward_b16(e, role, actb, N, out, s);
+    CHK(stack_forward_b16(e, role, e->fwd_b.r(), e->fwd_b.ld, N, pass0, 1, N, specs, false, s));
+    return last_forward_b16(e, role, N, out, s);
   }
-  CHK(stack_forward(e, role, x, n.d.in_dim, N, acts, pass0, 1, N, specs, s));      // (plain forward: dense rows)
-  return linear_forward(acts.back().as<float>(), n.hidden.back().out, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in,
+  CHK(stack_forward(e, role, x, n.d.in_dim, N, pass0, 1, N, specs, s));      // (plain forward: dense rows)
+  return linear_forward(e->ws[role].act.back().as<float>(), n.hidden.back().out, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in,
                         n.last.out, n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
 }
 

@@ -154,7 +154,7 @@ struct B16Img {
   void release() { rm.release(); tr.release(); }
 };
 // bf16 shadows of one nn.Linear weight (out, in): w [out][ldw] feeds the forward product, wt [in][ldwt] backward-data
-struct LinShadow { Scratch w, wt; int ldw = 0, ldwt = 0; };
+struct LinShadow { Scratch w, wt; int ldw = 0, ldwt = 0; void release() { w.release(); wt.release(); } };
 static inline bool is_i2o(int arch) { return arch == GT_ARCH_IN2OUT || arch == GT_ARCH_IN2OUT_RNN; }
 static inline bool has_lstm_body(int arch) { return arch == GT_ARCH_LSTM || arch == GT_ARCH_IN2OUT_RNN; }
 struct LstmDirP { float *Wih, *Whh, *bih, *bhh, *dWih, *dWhh, *dbih, *dbhh; };
@@ -184,6 +184,36 @@ struct Net {
   Net() { memset(inj, 0, sizeof(inj)); }
 };
 
+// One network's device workspace, gt_engine::ws[role].  Per role is whatever must survive the OTHER role's passes inside a step: the generator's forward
+// stash has to outlive both discriminator passes (update_generator back-propagates it last), so a discriminator has its own (its D-step stash is dead after
+// the D step; the G-step pass reuses it).  Transient within one call and shared by both roles, hence on the engine: l_state, l_xch, s_du, s_dx, s_dbias, dzA,
+// dzB, dz_b, slabs, colp, d_dx0, i2o_gout, the step workspace.  Unused members stay empty.  LSTM and SRU images / shadows stay apart: size() == layers + 1 catches a stale rebind.
+struct NetWs {
+  std::vector<Scratch> act; std::vector<B16Img> actb;     // MLP: hidden activations; under GT_OPT_MATMUL_BF16 their bf16 images (both orientations)
+  std::vector<DropoutSpec> specs; std::vector<LinShadow> wsh;      // dropout sites of the stashed pass; bf16 shadows of the hidden layers' weights, then of the last layer's
+  Scratch w0pad; SlabDefer sdefer;                 // first hidden layer's weight with a 16-byte row pitch (stack_forward); deferred weight-gradient combines of the fused step
+  std::vector<Scratch> xproj, gates, cst, out, outd;      // LSTM, per layer (outd: inter-layer-dropped outputs)
+  Scratch hshift, dout;                            // dout, either recurrent stack: gradient w.r.t. the current layer's output (a discriminator's head seeds it)
+  // ... its bf16 path, the generator's alone: images of every layer's input (+ the top output, last entry), dG, h that entered each frame (transposed); W_ih of all directions stacked [dirs*4H][in] (last entry: hidden2out)
+  std::vector<B16Img> l_in_b, l_dg_b; B16Img l_hs_b; std::vector<LinShadow> lsh;
+  // SRU, per layer: stashes; xmask: input-dropout multipliers [B][n_in]; wt: float32 mode's transposed W; omask: a discriminator's output-dropout keep
+  // tables [nseq][ncols], each row group of a launch drawn from its own pass (the generator's scans draw theirs inline: empty).  The bf16 path is role-owned
+  // too: the generator's s_in_b[l].t() and ssh[l] are read by sru_backward AFTER both discriminator passes.  A discriminator (GT_OPT_SRU_D_BF16) has no top
+  // s_in_b entry (the fused head reads the float32 h) and no hidden2out ssh (that product lives in the head kernel)
+  std::vector<Scratch> u, h, c, xdrop, xmask, wt, omask;
+  std::vector<B16Img> s_in_b; B16Img du_b;         // image of every layer's (dropped) input (+ the top output); dU of the current layer, both orientations
+  std::vector<LinShadow> ssh;                      // per layer W (n_in, ncols*k) as w [n_in][..] and wt [ncols*k][n_in]; last entry: hidden2out
+  template <typename... V> static void release_all(V&... v) { auto rel = [](auto& m) { for (auto& x : m) x.release(); }; (rel(v), ...); }
+  void release() {      // every member
+    release_all(act, actb, wsh, xproj, gates, cst, out, outd, l_in_b, l_dg_b, lsh, u, h, c, xdrop, xmask, wt, omask, s_in_b, ssh);
+    w0pad.release(); sdefer.pool.release(); hshift.release(); dout.release(); l_hs_b.release(); du_b.release();
+  }
+};
+struct StepCopy {      // a copy of a caller tensor made once per step (with a 16-byte pitch, or dense), keyed by what it was made from
+  Scratch buf; const float* src = nullptr; int ld = 0, cols = 0; long rows = 0; uint64_t step = ~0ULL;
+  bool holds(const float* s, int l, int c, long r, uint64_t st) const { return src == s && ld == l && cols == c && rows == r && step == st; }
+  void built(const float* s, int l, int c, long r, uint64_t st) { src = s; ld = l; cols = c; rows = r; step = st; }      void forget() { src = nullptr; }
+};
 // Banded images of the MLPG matrices the caller has passed so far, one per (R pointer, T): batches of a corpus come in
 // many padded lengths and the caller (gantts_amd.paramgen / the reference's per-batch R) keeps one R per T, so after the
 // first sight of a T there is no extraction kernel, no D2H copy and no host synchronisation on the step path.
@@ -228,8 +258,7 @@ struct gt_engine {
   // In2Out uses a single dynamic stream of width out_dim
   int *d_scol_i2o = nullptr, *d_sstride_i2o = nullptr; int i2o_ds = 0;
   MlpgCache mlpg;
-  // workspace
-  std::vector<Scratch> g_act, d_act;       // hidden activations
+  NetWs ws[2];                             // workspace: per role, then (below) what one call uses and both roles share
   Scratch dcat, dzA, dzB, leak, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
   Scratch scal;                            // StepScalars + StepResults
   StepResults* h_res = nullptr;            // pinned
@@ -248,7 +277,11 @@ struct gt_engine {
   };
   DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
   bool d_begin_done = false, g_begin_done = false, g_has_adv = false, g_used_mlpg = false;
-  const float* tv_mask = nullptr; long tv_n = 0; float tv_ovr = 0.f;   // sum(mask) already on the device for this step
+  struct TvMemo {      // sum(mask) is already on the device for this step: of which mask, over how many frames, under which override
+    const float* mask = nullptr; long n = 0; float ovr = 0.f;
+    bool known(const float* m, long N, float o) const { return mask == m && n == N && ovr == o; }
+    void note(const float* m, long N, float o) { mask = m; n = N; ovr = o; }      void forget() { mask = nullptr; }
+  } tv;
   // early results (single-GPU fused entry points): the step scalars are final right after the loss
   // kernels, long before backward + optimizer finish; they are copied out then, and the call returns
   // as soon as THAT copy has landed, leaving the rest of the step queued on the stream.
@@ -262,16 +295,8 @@ struct gt_engine {
   volatile unsigned* ticket_host() { return (volatile unsigned*)((char*)h_res + 64); }
   // deferred results of the split-phase calls (out == NULL): own pinned copy + event per role, fetched by gt_*_result
   StepResults* h_def[2] = {nullptr, nullptr}; hipEvent_t ev_def[2] = {nullptr, nullptr}; bool def_pending[2] = {false, false};
-  std::vector<DropoutSpec> g_specs, d_specs;   // dropout sites of the stashed passes
-  // recurrent generator workspace (per layer) and the lengths of the current batch
-  std::vector<Scratch> l_xproj, l_gates, l_cst, l_out, l_outd;   // l_outd: inter-layer-dropped outputs
-  Scratch i2o_gout;                                              // In2OutRNNHighwayNet: hidden2out output G(x)
-  Scratch l_state, l_dout, l_hshift;
-  // a recurrent DISCRIMINATOR (train.py:773-774 allows any model class): its own stashes (the generator's must survive the
-  // discriminator passes of a step), the gradient w.r.t. its [x | adv] input
-  std::vector<Scratch> dl_xproj, dl_gates, dl_cst, dl_out, dl_outd;
-  Scratch dl_dout, dl_hshift, d_dx0;
-  Scratch l_xch;                                   // persistent recurrence: exchange granules
+  Scratch i2o_gout, d_dx0;                         // In2OutRNNHighwayNet: hidden2out output G(x); a recurrent DISCRIMINATOR (train.py:773-774 allows any model class): gradient w.r.t. its [x | adv] input
+  Scratch l_state, l_xch, s_du, s_dx, s_dbias;     // recurrent layer in hand (either role): LSTM per-step kernels' state, persistent kernels' exchange granules; SRU backward temporaries
   struct GtComm* comm = nullptr;                   // gt_comm_init: RCCL communicator + comm stream (data parallel)
   struct GtIpc* ipc = nullptr;                     // gt_comm_ipc_*: interprocess arenas of the two-shot all-reduce (eng_ipc.hip)
   bool opt_comm_ipc = env_flag("GT_COMM_IPC", true);      // GT_OPT_COMM_IPC: messages that fit the arena's slots take that path once the arenas are attached
@@ -283,21 +308,9 @@ struct gt_engine {
   Scratch comm_tv;                                 // device double: global valid-frame count
   bool tv_inflight = false;                        // its all-reduce has been issued for the current mask
   // GT_OPT_MATMUL_BF16 on MLP stacks: bf16 images (both orientations) of everything that only feeds products
-  std::vector<B16Img> g_actb, d_actb;              // hidden activations
   B16Img xin_b, dcat_b, gy_b, dz_b[2], fwd_b;      // G's input, D's [x | adv] image (2N rows), dloss/dy_hat, dZ ping-pong, gt_model_forward's input
-  std::vector<B16Img> l_in_b;                      // recurrent generator: image of every layer's input (+ the top output, last entry)
-  std::vector<B16Img> s_in_b;                      // SRU generator: image of every layer's (dropped) input (+ the top output, last entry)
-  B16Img s_du_b;                                   // SRU: dU of the current layer, both orientations
-  std::vector<LinShadow> ssh;                      // SRU: per layer W (n_in, ncols*k) as w [n_in][..] and wt [ncols*k][n_in]; last entry: hidden2out
-  std::vector<B16Img> l_dg_b;                      // per layer: dG image (both orientations; every product that reads it runs on the step stream)
-  B16Img l_hs_b;                                   // h that entered each frame (transposed)
-  std::vector<LinShadow> lsh;                      // per LSTM layer: W_ih of all directions stacked [dirs*4H][in]; last entry: hidden2out
-  std::vector<LinShadow> wsh[2];                   // per role: bf16 shadows of the hidden layers' weights, then of the last layer's
-  SlabDefer sdefer[2];                             // per role: deferred weight-gradient combines of the fused step
   Scratch d_pre;                                   // split first layer of the conditioned D: P = x . W[:, :cd]^T + b  (eng_step.hip: FirstSplit)
   Scratch adv2; int ld_adv2 = 0;                   // ... and the adversarial columns of a pass's rows, [real | generated], 16-byte pitch
-  struct Pitched { Scratch buf; const float* src = nullptr; int ld = 0, cols = 0; long rows = 0; uint64_t step = ~0ULL; };
-  Pitched pitched[2];                              // 16-byte-pitch copies of caller tensors (slot 0: D's x, 1: G's input), once per step
   // GT_OPT_SPLIT_FIRST_LAYER (per engine; the environment only provides the default at creation)
   // GT_OPT_FUSED_DSTACK: the float32 MLP discriminator's layers above the first one + the head (+, in the generator step, the
   // backward-data chain down to the adversarial columns) as ONE launch per pass (dstack_f32.hip.h)
@@ -318,13 +331,11 @@ struct gt_engine {
                                                                   // 1.319 / 1.315 / 1.3175 / 1.3206 ms, b = 4 0.400 vs 0.406 -- the two 5.8 us holes behind the finalising launches now show
   bool opt_launch_riders = env_flag("GT_LAUNCH_RIDERS", true);     // GT_OPT_LAUNCH_RIDERS: small reductions as extra workgroups of neighbouring launches
   int ld_gx = 0, ld_cx = 0;                        // gt_set_x_pitch: row pitch of the generator input / the conditioning x (0 = dense)
-  // Pitched rows are read in place by the float32 MLP generator and by the split first layer of the conditioned float32 MLP
+  // gt_set_x_pitch: pitched rows are read in place by the float32 MLP generator and by the split first layer of the conditioned float32 MLP
   // discriminator.  Every other network gets a DENSE copy made by the engine, once per step (dense_gx / dense_cx in eng_step.hip):
   // gt_set_x_pitch never makes a step fail (DevicePrefetcher(pitch_x=True) with a recurrent discriminator did).
-  Scratch gx_dense, cx_dense;
-  bool gx_dense_on = false;                        // this step's generator input is the dense copy: gx_pitch() == in_dim
-  const float* cxd_src = nullptr; uint64_t cxd_step = ~0ull; long cxd_rows = 0; int cxd_ld = 0, cxd_cols = 0;     // what cx_dense holds
-  Scratch w0pad[2];                                // per role: first hidden layer's weight with a 16-byte row pitch (stack_forward)
+  StepCopy dx_pitched, gx_pitched, cx_dense;       // 16-byte-pitch copies of D's conditioning x / G's input (pitched_rows), the dense conditioning x (dense_cx)
+  Scratch gx_dense; bool gx_dense_on = false;      // gx_dense_on: this step's generator input is the dense copy, gx_pitch() == in_dim
   unsigned int* h_fault_dev = nullptr;             // device view of h_fault[1]: the optimizer kernel mirrors a raised fault word
   unsigned int* d_fault = nullptr;                 // device fault word of the persistent kernels (0 = ok)
   unsigned int* h_fault = nullptr;                 // pinned mirror, refreshed behind every persistent launch
@@ -341,19 +352,7 @@ struct gt_engine {
   hipEvent_t len_ev[LEN_RING] = {nullptr, nullptr, nullptr, nullptr};
   int len_cap = 0, len_slot = -1;
   int* d_lengths() { return len_slot < 0 ? nullptr : len_dev[len_slot].as<int>(); }
-  std::vector<Scratch> s_wt;                                 // SRU float32 mode: transposed copies of the layers' W
-  std::vector<Scratch> s_u, s_h, s_c, s_xdrop, s_xmask;     // SRU per-layer stashes (s_xmask: input-dropout multipliers [B][n_in])
-  Scratch s_du, s_dx, s_dbias;                                // backward temporaries of the layer in hand (either role)
-  // an SRU DISCRIMINATOR: its own stashes (the generator's must survive the discriminator passes of a step); ds_omask: output-dropout
-  // keep tables [nseq][ncols], one per layer, each row group of a launch drawn from its own pass
-  std::vector<Scratch> ds_wt, ds_u, ds_h, ds_c, ds_xdrop, ds_xmask, ds_omask;
-  // GT_OPT_SRU_D_BF16: that discriminator's products through the bf16-storage family.  Its images, shadows and dU image are its OWN:
-  // the generator's s_in_b[l].t() and ssh[l] are read by sru_backward AFTER both discriminator passes of a step.  ds_in_b has no
-  // top entry (the fused head reads the float32 h) and dssh none for hidden2out (its product lives in the head kernel).
-  bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);
-  std::vector<B16Img> ds_in_b;
-  B16Img ds_du_b;
-  std::vector<LinShadow> dssh;
+  bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);      // GT_OPT_SRU_D_BF16: an SRU discriminator's products through the bf16-storage family
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
