@@ -30,6 +30,10 @@ GEMM_PATH_SLOTS = 588                                                   # gt_gem
 GEMM_B16_PATH_SLOTS = 66                                                # gt_gemm_b16_path_counts
 SRU_PATH_SLOTS = 13                                                     # gt_sru_path_counts
 HEAD_PATH_SLOTS = 15                                                    # gt_head_path_counts
+(FRAME_MASK_SUM, FRAME_MASK_TOTAL, FRAME_SQERR, FRAME_G_LOSSES, FRAME_STATIC_GRAD, FRAME_FINALIZE_G, FRAME_FINALIZE_G_RIDER, FRAME_FINALIZE_D,
+ FRAME_SCALE_INV_TV, FRAME_HIGHWAY_FWD, FRAME_HIGHWAY_BWD, FRAME_SIGMOID_GRAD, FRAME_DROPOUT_APPLY, FRAME_BUILD_ADV, FRAME_BUILD_CAT2, FRAME_REPITCH,
+ FRAME_DENSE_COPY, FRAME_PAD_ROWS, FRAME_TRANSPOSE) = range(19)         # FrameCase.op
+FRAME_SCALARS = 26                                                      # doubles gt_op_frame reports
 CAST_PLAIN_F32, CAST_PLAIN_BF16, CAST_SEQDROP, CAST_CAT, CAST_CATDROP, CAST_MULTI = 0, 1, 2, 3, 4, 5      # CastCase.kind
 CAST_MAX_JOBS = 8
 GEMM_ROUTE_FORWARD, GEMM_ROUTE_FORWARD_SEG, GEMM_ROUTE_BACKWARD_DATA, GEMM_ROUTE_WEIGHT_GRAD, GEMM_ROUTE_WEIGHT_GRAD_SPLIT = 0, 1, 2, 3, 4
@@ -148,6 +152,16 @@ class DStackCase(C.Structure):
                 + [("scalars", C.POINTER(C.c_double))])
 
 
+class FrameCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("op", "max_blocks", "cols", "cols2", "lda", "ldb", "ldc", "ldd", "ldo", "ldo2", "has_tv", "want_partial",
+                                          "leak_unnorm", "rider", "fin_out", "has_adv", "zero_gnorm", "tv_from_sum", "n_mge", "n_mse", "n_hp", "pad_")]
+                + [(n, C.c_float) for n in ("tv", "tv_override", "w0", "adv_w", "mse_w", "mge_w")]
+                + [(n, C.c_int64) for n in ("rows", "split", "n_mask", "partials_cap")]
+                + [("drop", DropSite)]
+                + [(n, C.c_void_p) for n in ("a", "b", "c", "d", "mask", "idx", "tv_dev", "part_mge", "part_mse", "hp", "out", "out2")]
+                + [("sums", C.POINTER(C.c_double)), ("partials", C.POINTER(C.c_double)), ("scalars", C.POINTER(C.c_double))])
+
+
 class MlpgCase(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("backward", "B", "T", "Ds", "ldy", "ldys", "ldgs", "ldgy", "ldt")] + [("mse_w", C.c_float)]
                 + [(n, C.c_void_p) for n in ("e", "R", "scol", "sstride", "y", "ys", "gs", "gy", "yhat", "ytgt", "mask")]
@@ -218,6 +232,7 @@ SIGNATURES = {
     "gt_head_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_d_head": (_I, [C.POINTER(DHeadCase), _P]),
     "gt_op_dstack": (_I, [C.POINTER(DStackCase), _P]),
+    "gt_op_frame": (_I, [C.POINTER(FrameCase), _P]),
     "gt_op_mlpg": (_I, [C.POINTER(MlpgCase), _P]),
     "gt_op_mlpg_band": (_I, [_P, _P, _I, C.POINTER(_F), _L, C.POINTER(C.c_int32), _P]),
     "gt_clear_faults": (_I, [_P, _P]),

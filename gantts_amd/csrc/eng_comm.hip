@@ -277,9 +277,8 @@ int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float a
   GtComm* c = e->comm;
   CHK(comm_allreduce_after(e, sums, (size_t)n_sums, GT_NCCL_DOUBLE, compute));
   StepResults* target = e->h_res_dev ? e->h_res_dev : e->res();     // see post_early_results
-  if (role == GT_ROLE_D) hipLaunchKernelGGL(finalize_d_kernel, dim3(1), dim3(1), 0, c->stream, e->sc(), target, 1, e->d_unnorm ? 1 : 0);
-  else hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(1), 0, c->stream, e->sc(), target, adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1,
-                          (const double*)nullptr, 0, (const double*)nullptr, 0);
+  if (role == GT_ROLE_D) launch_finalize_d(e->sc(), target, 1, e->d_unnorm ? 1 : 0, c->stream);
+  else launch_finalize_g(e->sc(), target, adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, nullptr, 0, nullptr, 0, c->stream);
   LAUNCH_CHECK();
   return post_early_results(e, c->stream);
 }
@@ -291,7 +290,7 @@ int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float a
 int ensure_tv_begin(gt_engine* e, const float* mask, long N, hipStream_t s) {
   if (e->tv.known(mask, N, e->tv_override)) return GT_OK;
   if (comm_on(e) && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight) {
-    hipLaunchKernelGGL(mask_total_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, e->comm_tv.as<double>());
+    launch_mask_total(mask, N, e->comm_tv.as<double>(), s);
     LAUNCH_CHECK();
     CHK(comm_allreduce_after(e, e->comm_tv.p, 1, GT_NCCL_DOUBLE, s));
     e->tv_inflight = true;
@@ -317,7 +316,7 @@ int ensure_tv(gt_engine* e, const float* mask, long N, hipStream_t s) {
     CHK(comm_tv_join(e, s));
     tv_dev = e->comm_tv.as<double>();
   }
-  hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, e->tv_override, tv_dev, e->sc());
+  launch_mask_sum(mask, N, e->tv_override, tv_dev, e->sc(), s);
   LAUNCH_CHECK();
   e->tv.note(mask, N, e->tv_override);
   return GT_OK;

@@ -229,8 +229,7 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
       const long Ng = N / npass;                        // rows of one pass (its own dropout site)
       for (int q = 0; q < npass; ++q) {
         const DropoutSpec ds = drop_spec(e, role, passes[q], l, G.inj[passes[q]][l], dirs * H);
-        hipLaunchKernelGGL(dropout_apply_kernel, dim3(cdiv(Ng * dirs * H, 256)), dim3(256), 0, s, in + q * Ng * dirs * H,
-                           W.outd[l].as<float>() + q * Ng * dirs * H, Ng, dirs * H, ds);
+        launch_dropout_apply(in + q * Ng * dirs * H, W.outd[l].as<float>() + q * Ng * dirs * H, Ng, dirs * H, ds, s);
       }
       LAUNCH_CHECK();
       in = W.outd[l].as<float>();
@@ -348,8 +347,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
           const long Ng = N / npass;
           for (int q = 0; q < npass; ++q) {
             const DropoutSpec ds = drop_spec(e, role, passes[q], l - 1, G.inj[passes[q]][l - 1], dirs * H);
-            hipLaunchKernelGGL(dropout_apply_kernel, dim3(cdiv(Ng * dirs * H, 256)), dim3(256), 0, s, dout_other + q * Ng * dirs * H,
-                               dout_other + q * Ng * dirs * H, Ng, dirs * H, ds);
+            launch_dropout_apply(dout_other + q * Ng * dirs * H, dout_other + q * Ng * dirs * H, Ng, dirs * H, ds, s);
           }
           LAUNCH_CHECK();
         }
@@ -407,8 +405,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
         const long Ng = N / npass;
         for (int q = 0; q < npass; ++q) {
           const DropoutSpec ds = drop_spec(e, role, passes[q], l - 1, G.inj[passes[q]][l - 1], dirs * H);
-          hipLaunchKernelGGL(dropout_apply_kernel, dim3(cdiv(Ng * dirs * H, 256)), dim3(256), 0, s, dout_other + q * Ng * dirs * H,
-                           dout_other + q * Ng * dirs * H, Ng, dirs * H, ds);
+          launch_dropout_apply(dout_other + q * Ng * dirs * H, dout_other + q * Ng * dirs * H, Ng, dirs * H, ds, s);
       }
         LAUNCH_CHECK();
       }

@@ -26,11 +26,12 @@ extern "C" int gt_op_masked_mse(const float* input, const float* target, const f
   void* ws = tls_ws.p;
   StepScalars* sc = (StepScalars*)ws;
   double* part = (double*)((char*)ws + 1024);
-  hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, -1.f, (const double*)nullptr, sc);
-  const int nblk = (int)std::min<long>(1000, cdiv(N * D, RED_THREADS * 4));
-  hipLaunchKernelGGL(masked_sqerr_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, input, D, target, D, mask, N, D, part, grad_input, D,
-                     1.f, sc);
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, nblk, &sc->s_mse);
+  launch_mask_sum(mask, N, -1.f, nullptr, sc, s);
+  SqerrArgs q;
+  memset(&q, 0, sizeof(q));
+  q.a = input; q.lda = D; q.b = target; q.ldb = D; q.mask = mask; q.rows = N; q.D = D; q.partial = part; q.g = grad_input; q.ldg = D; q.gscale = 1.f; q.sc = sc;
+  const int nblk = launch_masked_sqerr(q, s, 1000);
+  launch_sum_partials(part, nblk, &sc->s_mse, s);
   StepScalars h;
   hipError_t err = hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipStreamSynchronize(s);
@@ -171,7 +172,7 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
     r = mlpg_forward(e, c->y, c->ldy, scol, sstride, Ds, c->ys, c->ldys, c->B, c->T, s);
   } else {
     if (mse) {      // sum(mask) and its reciprocal, as ensure_tv puts them there; the step's memo of it no longer holds
-      hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, s, c->mask, c->B * c->T, -1.f, (const double*)nullptr, e->sc());
+      launch_mask_sum(c->mask, (long)c->B * c->T, -1.f, nullptr, e->sc(), s);
       LAUNCH_CHECK();
       e->tv.forget();
     }
@@ -804,6 +805,235 @@ extern "C" int gt_op_dstack(const gt_dstack_case* c, void* stream) {
     r = launch_dstack_pass(k, s);
   }
   return t.finish(r, nblk, c->scalars, "dstack", s);
+}
+
+// ------------------------------------------------------------------------------------------
+// parity hook of the per-frame kernels between the products of a step (tests/test_gpu_frame_kernels.py): ONE launch function of
+// frame_args.hip.h -- the functions the step itself calls -- on the caller's buffers.  Everything a kernel would index with is checked first.
+// ------------------------------------------------------------------------------------------
+static_assert(offsetof(StepScalars, tv_sum) == 8 && offsetof(StepScalars, gnorm2_g) == 80 && sizeof(StepScalars) == 88, "gt_op_frame: layout of `sums` / `scalars`");
+static_assert(sizeof(StepResults) == 12 * sizeof(float), "gt_op_frame: layout of `scalars`");
+static_assert(sizeof(HeadPartials) == 5 * sizeof(double), "gt_op_frame: hp is [n_hp][5] doubles");
+static_assert(sizeof(gt_frame_case) == 320 && offsetof(gt_frame_case, tv) == 88 && offsetof(gt_frame_case, rows) == 112 && offsetof(gt_frame_case, drop) == 144 &&
+              offsetof(gt_frame_case, a) == 200 && offsetof(gt_frame_case, scalars) == 312, "gt_frame_case: the layout tests/test_abi.py and gantts_amd/_lib.py state");
+
+static bool frame_mat_ok(const void* p, long ld, long cols) { return p && !(((uintptr_t)p) & 3) && ld >= cols; }
+// device int32 map -> host, every entry in [lo, hi)
+static int frame_map_check(const int32_t* idx, int n, long lo, long hi, const char* what) {
+  if (!idx || (((uintptr_t)idx) & 3) || n < 1) return fail(GT_ERR_INVALID, "frame hook: %s missing or misaligned", what);
+  std::vector<int32_t> h((size_t)n);
+  HIPCHK(hipMemcpy(h.data(), idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i)
+    if (h[i] < lo || h[i] >= hi) return fail(GT_ERR_INVALID, "frame hook: %s[%d] = %d outside [%ld, %ld)", what, i, h[i], lo, hi);
+  return GT_OK;
+}
+
+extern "C" int gt_op_frame(const gt_frame_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  const int op = c->op;
+  if (op < GT_FRAME_MASK_SUM || op > GT_FRAME_TRANSPOSE) return fail(GT_ERR_INVALID, "frame hook: unknown op %d", op);
+  hipStream_t s = (hipStream_t)stream;
+  const int max_blocks = c->max_blocks ? c->max_blocks : FRAME_RED_MAX_BLOCKS;
+  if (max_blocks < 1 || max_blocks > FRAME_RED_MAX_BLOCKS) return fail(GT_ERR_INVALID, "frame hook: max_blocks = %d (0, or 1 .. %d)", c->max_blocks, FRAME_RED_MAX_BLOCKS);
+  const long rows = (long)c->rows, n_mask = (long)c->n_mask;
+  const int cols = c->cols, cols2 = c->cols2;
+  const bool reduction = op == GT_FRAME_SQERR || op == GT_FRAME_G_LOSSES || op == GT_FRAME_STATIC_GRAD;
+  const bool finalizer = op == GT_FRAME_FINALIZE_G || op == GT_FRAME_FINALIZE_G_RIDER || op == GT_FRAME_FINALIZE_D;
+  const bool mask_op = op == GT_FRAME_MASK_SUM || op == GT_FRAME_MASK_TOTAL;
+  if (!finalizer && !mask_op) {
+    if (rows < 1 || rows > 0x7FFFFFFFL - 64) return fail(GT_ERR_INVALID, "frame hook: rows out of range");
+    if (cols < 1 || rows * cols > (1L << 36)) return fail(GT_ERR_INVALID, "frame hook: cols out of range");
+  }
+  // ---- the normaliser --------------------------------------------------------------------------
+  const bool fin_rider = op == GT_FRAME_STATIC_GRAD && c->rider != 0;
+  const bool needs_tv = (op == GT_FRAME_SQERR && c->out) || op == GT_FRAME_STATIC_GRAD || op == GT_FRAME_SCALE_INV_TV || op == GT_FRAME_FINALIZE_G ||
+                        op == GT_FRAME_FINALIZE_G_RIDER || (op == GT_FRAME_FINALIZE_D && !c->tv_from_sum);
+  const bool has_mask = c->mask != nullptr;
+  if (has_mask && ((((uintptr_t)c->mask) & 3) || n_mask < 1 || n_mask > 0x7FFFFFFFL)) return fail(GT_ERR_INVALID, "frame hook: mask misaligned or n_mask out of range");
+  if (((uintptr_t)c->tv_dev) & 7) return fail(GT_ERR_INVALID, "frame hook: misaligned tv_dev");
+  if (c->has_tv && !(c->tv > 0.f)) return fail(GT_ERR_INVALID, "frame hook: tv must be positive");
+  if (c->has_tv && c->tv_dev) return fail(GT_ERR_INVALID, "frame hook: has_tv and tv_dev exclude each other");
+  if (reduction && (!has_mask || n_mask != rows)) return fail(GT_ERR_INVALID, "frame hook: a reduction needs a mask of n_mask == rows entries");
+  if (mask_op && !has_mask) return fail(GT_ERR_INVALID, "frame hook: needs a mask");
+  bool tv_from_mask = false;
+  if (needs_tv) {
+    if (!c->has_tv && !has_mask) return fail(GT_ERR_INVALID, "frame hook: needs a normaliser: has_tv, or a mask (with tv_override / tv_dev)");
+    tv_from_mask = !c->has_tv;
+  } else if (c->tv_dev && op != GT_FRAME_MASK_SUM) return fail(GT_ERR_INVALID, "frame hook: tv_dev is read by the mask sum only");
+  // ---- per-op checks -----------------------------------------------------------------------------
+  int n_part = 0, n1 = 0;
+  if (op == GT_FRAME_SQERR) {
+    if (!frame_mat_ok(c->a, c->lda, cols) || !frame_mat_ok(c->b, c->ldb, cols)) return fail(GT_ERR_INVALID, "frame hook: sqerr needs a and b with pitches >= cols");
+    if (c->out && !frame_mat_ok(c->out, c->ldo, cols)) return fail(GT_ERR_INVALID, "frame hook: gradient misaligned or its pitch below cols");
+    n_part = frame_red_blocks(rows * cols, max_blocks);
+  } else if (op == GT_FRAME_G_LOSSES) {
+    if (cols2 < 1 || rows * cols2 > (1L << 36)) return fail(GT_ERR_INVALID, "frame hook: cols2 out of range");
+    if (!frame_mat_ok(c->a, c->lda, cols) || !frame_mat_ok(c->b, c->ldb, cols) || !frame_mat_ok(c->c, c->ldc, cols2) || !frame_mat_ok(c->d, c->ldd, cols2))
+      return fail(GT_ERR_INVALID, "frame hook: g_losses needs a, b (cols) and c, d (cols2) with pitches >= their widths");
+    n1 = frame_red_blocks(rows * cols, max_blocks);
+    n_part = n1 + frame_red_blocks(rows * cols2, max_blocks);
+  } else if (op == GT_FRAME_STATIC_GRAD) {
+    if (!frame_mat_ok(c->a, c->lda, cols) || !frame_mat_ok(c->b, c->ldb, cols)) return fail(GT_ERR_INVALID, "frame hook: static_grad needs a and b with pitches >= cols");
+    if (c->out && !frame_mat_ok(c->out, c->ldo, cols)) return fail(GT_ERR_INVALID, "frame hook: gs misaligned or its pitch below cols");
+    if (c->idx) {
+      if (cols2 < 1) return fail(GT_ERR_INVALID, "frame hook: a column map needs cols2 = the number of adversarial columns");
+      CHK(frame_map_check(c->idx, cols, -1, cols2, "adv_inv"));
+    }
+    if (c->c && !frame_mat_ok(c->c, c->ldc, c->idx ? cols2 : 0)) return fail(GT_ERR_INVALID, "frame hook: leak misaligned or its pitch below cols2");
+    if (c->d && !frame_mat_ok(c->d, c->ldd, c->idx ? cols2 : 0)) return fail(GT_ERR_INVALID, "frame hook: gadv misaligned or its pitch below cols2");
+    n_part = c->want_partial ? frame_red_blocks(rows * cols, max_blocks) : 0;
+  }
+  if (fin_rider || op == GT_FRAME_FINALIZE_G || op == GT_FRAME_FINALIZE_G_RIDER) {
+    const bool with_hp = op != GT_FRAME_FINALIZE_G;
+    if ((c->part_mge ? (c->n_mge < 1 || c->n_mge > (1 << 20)) : c->n_mge != 0) || (c->part_mse ? (c->n_mse < 1 || c->n_mse > (1 << 20)) : c->n_mse != 0) ||
+        (c->hp ? (!with_hp || c->n_hp < 1 || c->n_hp > (1 << 20)) : c->n_hp != 0))
+      return fail(GT_ERR_INVALID, "frame hook: partials come with a count of 1 .. 2^20, none with 0 (hp: the rider forms only)");
+    if ((((uintptr_t)c->part_mge) | ((uintptr_t)c->part_mse) | ((uintptr_t)c->hp)) & 7) return fail(GT_ERR_INVALID, "frame hook: misaligned partials");
+  }
+  if (op == GT_FRAME_SCALE_INV_TV && !frame_mat_ok(c->out, cols, cols)) return fail(GT_ERR_INVALID, "frame hook: scale_inv_tv needs out [rows * cols]");
+  if (op == GT_FRAME_HIGHWAY_FWD && !(frame_mat_ok(c->a, c->lda, cols) && frame_mat_ok(c->b, c->ldb, cols) && frame_mat_ok(c->c, c->ldc, cols) && frame_mat_ok(c->out, c->ldo, cols)))
+    return fail(GT_ERR_INVALID, "frame hook: highway_fwd needs a (x), b (Tx), c (Gx) and out with pitches >= cols");
+  if (op == GT_FRAME_HIGHWAY_BWD && !(frame_mat_ok(c->a, c->lda, cols) && frame_mat_ok(c->b, c->ldb, cols) && frame_mat_ok(c->c, c->ldc, cols) && frame_mat_ok(c->out, c->ldo, cols) &&
+                                      frame_mat_ok(c->out2, c->ldo2, cols)))
+    return fail(GT_ERR_INVALID, "frame hook: highway_bwd needs a (g), b (Tx), c (Gx), out (dGx) and out2 (dTz) with pitches >= cols");
+  if (op == GT_FRAME_SIGMOID_GRAD && !(frame_mat_ok(c->a, c->lda, cols) && frame_mat_ok(c->out, c->ldo, cols)))
+    return fail(GT_ERR_INVALID, "frame hook: sigmoid_grad needs a (y) and out (g, in place) with pitches >= cols");
+  if (op == GT_FRAME_DROPOUT_APPLY) {
+    if (!frame_mat_ok(c->a, cols, cols) || !frame_mat_ok(c->out, cols, cols)) return fail(GT_ERR_INVALID, "frame hook: dropout_apply needs dense a and out");
+    const char* why;
+    if (!tail_site_ok(c->drop, cols, rows, false, &why)) return fail(GT_ERR_INVALID, "frame hook: %s", why);
+  }
+  if (op == GT_FRAME_BUILD_ADV) {
+    if (c->split < 0 || c->split > rows) return fail(GT_ERR_INVALID, "frame hook: 0 <= split <= rows");
+    if (c->lda < 1 || (c->split > 0 && !frame_mat_ok(c->a, c->lda, 1)) || (c->split < rows && !frame_mat_ok(c->b, c->lda, 1)))
+      return fail(GT_ERR_INVALID, "frame hook: build_adv needs a (rows below split) and b (the rest), both with pitch lda");
+    CHK(frame_map_check(c->idx, cols, 0, c->lda, "idx"));
+    if (!c->out || (((uintptr_t)c->out) & 15) || c->ldo < cols || (c->ldo & 3)) return fail(GT_ERR_INVALID, "frame hook: build_adv needs a 16-byte aligned out with a pitch >= cols that is a multiple of 4");
+    if (c->rider < 0 || c->rider > 2 || (c->rider && !has_mask)) return fail(GT_ERR_INVALID, "frame hook: rider 0, 1 (scalars) or 2 (the count alone), with a mask");
+  }
+  if (op == GT_FRAME_BUILD_CAT2) {
+    if (cols2 < 1 || !frame_mat_ok(c->a, cols, cols) || c->ldb < 1 || !frame_mat_ok(c->b, c->ldb, 1) || !frame_mat_ok(c->c, c->ldb, 1))
+      return fail(GT_ERR_INVALID, "frame hook: build_cat2 needs a (x, dense [rows][cols]), b and c (pitch ldb) and cols2 mapped columns");
+    CHK(frame_map_check(c->idx, cols2, 0, c->ldb, "idx"));
+    if (!frame_mat_ok(c->out, c->ldo, (long)cols + cols2)) return fail(GT_ERR_INVALID, "frame hook: out misaligned or its pitch below cols + cols2");
+  }
+  if (op == GT_FRAME_REPITCH && (!frame_mat_ok(c->a, c->lda, cols) || !c->out || (((uintptr_t)c->out) & 15) || c->ldo < cols || (c->ldo & 3)))
+    return fail(GT_ERR_INVALID, "frame hook: repitch needs a and a 16-byte aligned out with a pitch >= cols that is a multiple of 4");
+  if (op == GT_FRAME_DENSE_COPY && !(frame_mat_ok(c->a, c->lda, cols) && frame_mat_ok(c->out, c->ldo, cols))) return fail(GT_ERR_INVALID, "frame hook: dense_copy needs a and out with pitches >= cols");
+  if (op == GT_FRAME_PAD_ROWS && !(frame_mat_ok(c->a, cols, cols) && frame_mat_ok(c->out, c->ldo, cols))) return fail(GT_ERR_INVALID, "frame hook: pad_rows needs dense a and out with a pitch >= cols");
+  if (op == GT_FRAME_TRANSPOSE && !(frame_mat_ok(c->a, c->lda, cols) && frame_mat_ok(c->out, c->ldo, rows))) return fail(GT_ERR_INVALID, "frame hook: transpose needs a (pitch >= cols) and out (pitch >= rows)");
+  if (c->partials && c->partials_cap < n_part) return fail(GT_ERR_INVALID, "frame hook: %d partials for a buffer of %lld", n_part, (long long)c->partials_cap);
+  // ---- scratch: the step's scalars, its results, the two partial regions of the engine -- all NaN (0xFF bytes) until something writes them ----
+  const size_t off_res = 256, off_part = 512, total = off_part + 2 * FRAME_RED_MAX_BLOCKS * sizeof(double);
+  static thread_local Scratch mem;     // grow-only, no per-call hipMalloc / hipFree (both synchronise the device)
+  CHK(mem.ensure(total));
+  StepScalars* sc = (StepScalars*)mem.p;
+  StepResults* res = (StepResults*)((char*)mem.p + off_res);
+  double* part_mge = (double*)((char*)mem.p + off_part);
+  double* part_mse = part_mge + FRAME_RED_MAX_BLOCKS;
+  float tv_host[2] = {c->tv, 1.0f / c->tv};
+  auto body = [&]() -> int {
+    HIPCHK(hipMemsetAsync(mem.p, 0xFF, total, s));
+    if (c->has_tv) HIPCHK(hipMemcpyAsync(mem.p, tv_host, sizeof(tv_host), hipMemcpyHostToDevice, s));
+    if (c->sums) HIPCHK(hipMemcpyAsync((char*)mem.p + offsetof(StepScalars, tv_sum), c->sums, 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (tv_from_mask) { launch_mask_sum(c->mask, n_mask, c->tv_override, c->tv_dev, sc, s); LAUNCH_CHECK(); }
+    GFinalize fin;
+    memset(&fin, 0, sizeof(fin));
+    if (fin_rider || op == GT_FRAME_FINALIZE_G_RIDER) {
+      fin.on = 1; fin.sc = sc; fin.out = c->fin_out ? res : (StepResults*)nullptr; fin.adv_w = c->adv_w; fin.mse_w = c->mse_w; fin.mge_w = c->mge_w;
+      fin.has_adv = c->has_adv ? 1 : 0; fin.part_mge = c->part_mge; fin.n_mge = c->n_mge; fin.part_mse = c->part_mse; fin.n_mse = c->n_mse;
+      fin.hp = (const HeadPartials*)c->hp; fin.n_hp = c->n_hp;
+    }
+    switch (op) {
+      case GT_FRAME_MASK_SUM: launch_mask_sum(c->mask, n_mask, c->tv_override, c->tv_dev, sc, s); break;
+      case GT_FRAME_MASK_TOTAL: launch_mask_total(c->mask, n_mask, &sc->tv_sum, s); break;
+      case GT_FRAME_SQERR: {
+        SqerrArgs q;
+        memset(&q, 0, sizeof(q));
+        q.a = c->a; q.lda = c->lda; q.b = c->b; q.ldb = c->ldb; q.mask = c->mask; q.rows = rows; q.D = cols; q.partial = part_mse; q.g = c->out; q.ldg = c->ldo;
+        q.gscale = c->w0; q.sc = sc;
+        const int nblk = launch_masked_sqerr(q, s, max_blocks);
+        LAUNCH_CHECK();
+        launch_sum_partials(part_mse, nblk, &sc->s_mse, s);
+        break;
+      }
+      case GT_FRAME_G_LOSSES: {
+        GLossesArgs q;
+        memset(&q, 0, sizeof(q));
+        q.a1 = c->a; q.lda1 = c->lda; q.b1 = c->b; q.ldb1 = c->ldb; q.D1 = cols; q.partial1 = part_mse;
+        q.a2 = c->c; q.lda2 = c->ldc; q.b2 = c->d; q.ldb2 = c->ldd; q.D2 = cols2; q.partial2 = part_mge;
+        q.mask = c->mask; q.rows = rows;
+        int m1 = 0, m2 = 0;
+        launch_g_losses(q, &m1, &m2, s, max_blocks);
+        LAUNCH_CHECK();
+        launch_sum_partials(part_mse, m1, &sc->s_mse, s);
+        LAUNCH_CHECK();
+        launch_sum_partials(part_mge, m2, &sc->s_mge, s);
+        break;
+      }
+      case GT_FRAME_STATIC_GRAD: {
+        StaticGradArgs q;
+        memset(&q, 0, sizeof(q));
+        q.yhs = c->a; q.ld1 = c->lda; q.ys = c->b; q.ld2 = c->ldb; q.mask = c->mask; q.rows = rows; q.Ds = cols; q.mge_w = c->w0;
+        q.adv_inv = c->idx; q.leak = c->c; q.ldl = c->ldc; q.gadv = c->d; q.lda = c->ldd; q.adv_w = c->adv_w; q.gs = c->out; q.ldg = c->ldo;
+        q.partial = c->want_partial ? part_mge : (double*)nullptr; q.sc = sc; q.fin = fin; q.leak_unnorm = c->leak_unnorm ? 1 : 0;
+        const int nblk = launch_static_grad(q, s, max_blocks);
+        if (c->want_partial && !fin_rider) { LAUNCH_CHECK(); launch_sum_partials(part_mge, nblk, &sc->s_mge, s); }
+        break;
+      }
+      case GT_FRAME_FINALIZE_G:
+        launch_finalize_g(sc, res, c->adv_w, c->mse_w, c->mge_w, c->has_adv ? 1 : 0, c->zero_gnorm ? 1 : 0, c->part_mge, c->n_mge, c->part_mse, c->n_mse, s);
+        break;
+      case GT_FRAME_FINALIZE_G_RIDER: launch_finalize_g_rider(fin, s); break;
+      case GT_FRAME_FINALIZE_D: launch_finalize_d(sc, res, c->zero_gnorm ? 1 : 0, c->tv_from_sum ? 1 : 0, s); break;
+      case GT_FRAME_SCALE_INV_TV: launch_scale_by_inv_tv(c->out, rows * cols, sc, s); break;
+      case GT_FRAME_HIGHWAY_FWD: launch_highway_forward(c->a, c->lda, c->b, c->ldb, c->c, c->ldc, c->out, c->ldo, rows, cols, s); break;
+      case GT_FRAME_HIGHWAY_BWD: launch_highway_backward(c->a, c->lda, c->b, c->ldb, c->c, c->ldc, c->out, c->ldo, c->out2, c->ldo2, rows, cols, s); break;
+      case GT_FRAME_SIGMOID_GRAD: launch_sigmoid_grad(c->out, c->ldo, c->a, c->lda, rows, cols, s); break;
+      case GT_FRAME_DROPOUT_APPLY: launch_dropout_apply(c->a, c->out, rows, cols, tail_site_spec(c->drop), s); break;
+      case GT_FRAME_BUILD_ADV: {
+        BuildAdvArgs q;
+        memset(&q, 0, sizeof(q));
+        q.fa = c->a; q.fb = c->b; q.ldf = c->lda; q.idx = c->idx; q.na = cols; q.out = c->out; q.ldo = c->ldo; q.split = (long)c->split; q.rows = rows;
+        q.tv_mask = c->rider ? c->mask : (const float*)nullptr; q.tv_n = n_mask; q.tv_override = c->tv_override; q.sc = sc;
+        q.tv_total = c->rider == 2 ? &sc->tv_sum : (double*)nullptr;
+        launch_build_adv(q, s);
+        break;
+      }
+      case GT_FRAME_BUILD_CAT2: launch_build_cat2(c->a, cols, c->b, c->c, c->ldb, c->idx, cols2, c->out, c->ldo, rows, s); break;
+      case GT_FRAME_REPITCH: launch_repitch(c->a, c->lda, cols, rows, c->out, c->ldo, s); break;
+      case GT_FRAME_DENSE_COPY: launch_copy_cols(c->a, c->lda, 0, c->out, c->ldo, 0, rows, cols, s); break;
+      case GT_FRAME_PAD_ROWS: launch_pad_rows(c->a, cols, (int)rows, c->out, c->ldo, s); break;
+      case GT_FRAME_TRANSPOSE: launch_transpose_f32(c->a, (int)rows, cols, c->lda, c->out, c->ldo, s); break;
+    }
+    LAUNCH_CHECK();
+    return GT_OK;
+  };
+  const int r = body();
+  hipError_t err = hipStreamSynchronize(s);
+  if (err == hipSuccess && r == GT_OK && c->scalars) {
+    StepScalars h;
+    StepResults hr;
+    err = hipMemcpy(&h, sc, sizeof(h), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(&hr, res, sizeof(hr), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) {
+      double* o = c->scalars;
+      o[0] = (double)h.tv; o[1] = (double)h.inv_tv; o[2] = h.tv_sum; o[3] = h.s_real; o[4] = h.s_fake; o[5] = h.n_real_ok; o[6] = h.n_fake_ok;
+      o[7] = h.s_adv; o[8] = h.s_mge; o[9] = h.s_mse; o[10] = h.gnorm2_d; o[11] = h.gnorm2_g;
+      const float* f = (const float*)&hr;
+      for (int i = 0; i < 12; ++i) o[12 + i] = (double)f[i];
+      o[24] = (double)n_part; o[25] = (double)n1;
+    }
+  }
+  if (err == hipSuccess && r == GT_OK && c->partials && n_part > 0) {
+    if (op == GT_FRAME_G_LOSSES) {
+      err = hipMemcpy(c->partials, part_mse, (size_t)n1 * sizeof(double), hipMemcpyDeviceToHost);
+      if (err == hipSuccess) err = hipMemcpy(c->partials + n1, part_mge, (size_t)(n_part - n1) * sizeof(double), hipMemcpyDeviceToHost);
+    } else err = hipMemcpy(c->partials, op == GT_FRAME_SQERR ? part_mse : part_mge, (size_t)n_part * sizeof(double), hipMemcpyDeviceToHost);
+  }
+  if (r) return r;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "frame hook: %s", hipGetErrorString(err));
+  return GT_OK;
 }
 
 // ------------------------------------------------------------------------------------------

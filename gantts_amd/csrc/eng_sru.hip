@@ -270,8 +270,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       // one at 114 (profiles/r03_sru_fp32_summary.md: 1.41 vs 1.80 ms per layer) -- multiply by a transposed copy of W, re-made
       // from the caller's parameter buffer before every pass (12 MB, ~10 us)
       CHK(W.wt[l].ensure((size_t)ncols * L.k * L.in * sizeof(float)));
-      hipLaunchKernelGGL(transpose_f32_kernel, dim3(cdiv(ncols * L.k, 32), cdiv(L.in, 32)), dim3(256), 0, s, L.W, L.in, ncols * L.k, ncols * L.k,
-                         W.wt[l].as<float>(), L.in);
+      launch_transpose_f32(L.W, L.in, ncols * L.k, ncols * L.k, W.wt[l].as<float>(), L.in, s);
       LAUNCH_CHECK();
       GemmArgs g;
       memset(&g, 0, sizeof(g));

@@ -240,8 +240,8 @@ struct FirstSplit {
 static int step_copy(gt_engine* e, StepCopy& M, const float* p, int ld, int cols, long rows, int ldo, bool dense, const float** out, hipStream_t s) {
   if (!M.holds(p, ld, cols, rows, e->step_counter)) {
     CHK(M.buf.ensure((size_t)rows * ldo * sizeof(float)));
-    if (dense) hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(rows * cols, 256)), dim3(256), 0, s, p, ld, 0, (const int*)nullptr, M.buf.as<float>(), ldo, 0, (int)rows, cols);
-    else hipLaunchKernelGGL(repitch_kernel, dim3(cdiv(rows * (ldo / 4), 256)), dim3(256), 0, s, p, ld, cols, rows, M.buf.as<float>(), ldo);
+    if (dense) launch_copy_cols(p, ld, 0, M.buf.as<float>(), ldo, 0, rows, cols, s);
+    else launch_repitch(p, ld, cols, rows, M.buf.as<float>(), ldo, s);
     LAUNCH_CHECK();
     M.built(p, ld, cols, rows, e->step_counter);
   }
@@ -309,7 +309,7 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
       // parameter buffer before every pass (it may have been stepped, loaded or broadcast since).
       ldw = (L.in + 3) & ~3;
       CHK(e->ws[role].w0pad.ensure((size_t)L.out * ldw * sizeof(float)));
-      hipLaunchKernelGGL(pad_rows_kernel, dim3(cdiv((long)L.out * ldw, 256)), dim3(256), 0, s, L.W, L.in, L.out, e->ws[role].w0pad.as<float>(), ldw);
+      launch_pad_rows(L.W, L.in, L.out, e->ws[role].w0pad.as<float>(), ldw, s);
       LAUNCH_CHECK();
       W = e->ws[role].w0pad.as<float>();
     }
@@ -493,8 +493,7 @@ static int dense_gx(gt_engine* e, const float** x, long N, hipStream_t s) {
   if (e->ld_gx < G.d.in_dim) return fail(GT_ERR_INVALID, "gt_set_x_pitch: pitch %d for %d generator input columns", e->ld_gx, G.d.in_dim);
   if (G.d.arch == GT_ARCH_MLP && !use_b16(e, GT_ROLE_G)) return GT_OK;
   CHK(e->gx_dense.ensure((size_t)N * G.d.in_dim * sizeof(float)));
-  hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * G.d.in_dim, 256)), dim3(256), 0, s, *x, e->ld_gx, 0, (const int*)nullptr,
-                     e->gx_dense.as<float>(), G.d.in_dim, 0, (int)N, G.d.in_dim);
+  launch_copy_cols(*x, e->ld_gx, 0, e->gx_dense.as<float>(), G.d.in_dim, 0, N, G.d.in_dim, s);
   LAUNCH_CHECK();
   *x = e->gx_dense.as<float>();
   e->gx_dense_on = true;
@@ -521,8 +520,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     // G(x) = hidden2out(LSTM(x)) stays internal; the model returns its INPUT as y_hat (models.py:118)
     CHK(e->i2o_gout.ensure((size_t)N * G.d.out_dim * sizeof(float)));
     CHK(lstm_forward(e, x, B, T, e->i2o_gout.as<float>(), s));
-    hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * G.d.in_dim, 256)), dim3(256), 0, s, x, G.d.in_dim, 0, (const int*)nullptr,
-                       y_hat, G.d.in_dim, 0, (int)N, G.d.in_dim);
+    launch_copy_cols(x, G.d.in_dim, 0, y_hat, G.d.in_dim, 0, N, G.d.in_dim, s);
     LAUNCH_CHECK();
     gsrc = e->i2o_gout.as<float>();
   } else if (G.d.arch == GT_ARCH_SRU) {
@@ -553,8 +551,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     CHK(linear_forward(x, G.d.in_dim, G.gate.W, sd, G.gate.b, e->tx.as<float>(), sd, N, sd, sd, ACT_SIGMOID, no_drop(), s));
     CHK(mlpg_forward(e, gsrc, G.d.out_dim, e->d_scol_i2o, e->d_sstride_i2o, sd, e->gx.as<float>(), sd, B, T, s));
     if (stash) e->g_used_mlpg = true;
-    hipLaunchKernelGGL(highway_forward_kernel, dim3(cdiv(N * sd, 256)), dim3(256), 0, s, x, G.d.in_dim, e->tx.as<float>(), sd,
-                       e->gx.as<float>(), sd, y_hat_static, sd, N, sd);
+    launch_highway_forward(x, G.d.in_dim, e->tx.as<float>(), sd, e->gx.as<float>(), sd, y_hat_static, sd, N, sd, s);
     LAUNCH_CHECK();
   } else {
     if (G.d.out_dim != e->Dout_cfg)
@@ -567,8 +564,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
       if (e->Ds != G.d.out_dim) return fail(GT_ERR_INVALID, "R is None but the stream config has dynamic features");
       if (stash) e->g_used_mlpg = false;
       // R is None: num_windows = 1, every stream passes through (multistream.py:88-89,119-120)
-      hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * G.d.out_dim, 256)), dim3(256), 0, s, y_hat, G.d.out_dim, 0,
-                         (const int*)nullptr, y_hat_static, G.d.out_dim, 0, (int)N, G.d.out_dim);
+      launch_copy_cols(y_hat, G.d.out_dim, 0, y_hat_static, G.d.out_dim, 0, N, G.d.out_dim, s);
       LAUNCH_CHECK();
     }
   }
@@ -608,8 +604,7 @@ static int build_cat(gt_engine* e, const float* x, const float* feats, int ld_fe
   float* dst = e->dcat.as<float>() + row0 * ldc;
   const int cd = cond_dim(e);
   if (cd > 0) {
-    hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * cd, 256)), dim3(256), 0, s, x, cd, 0, (const int*)nullptr, dst, ldc, 0,
-                       (int)N, cd);
+    launch_copy_cols(x, cd, 0, dst, ldc, 0, N, cd, s);
     LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, feats, ld_feats, 0, e->d_adv_cols, dst, ldc,
@@ -983,9 +978,12 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
     float* dst = e->adv2.as<float>() + row0 * ld;
     if (both || !e->img_adv2.holds(nullptr, p.fake)) {
       const bool any_ride = r.tv_ride || r.tv_ride_dp || r.unnorm;
-      hipLaunchKernelGGL(build_adv_kernel, dim3(cdiv(p.rows * (ld / 4), 256) + (any_ride ? 1 : 0)), dim3(256), 0, s, p.cat0.fa, p.cat0.fb, p.ldf,
-                         e->d_adv_cols, e->Da, dst, ld, N, p.rows, any_ride ? r.mask : (const float*)nullptr, (int)N, e->tv_override, e->sc(),
-                         r.unnorm ? &e->sc()->tv_sum : r.tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr);
+      BuildAdvArgs ba;
+      memset(&ba, 0, sizeof(ba));
+      ba.fa = p.cat0.fa; ba.fb = p.cat0.fb; ba.ldf = p.ldf; ba.idx = e->d_adv_cols; ba.na = e->Da; ba.out = dst; ba.ldo = ld; ba.split = N; ba.rows = p.rows;
+      ba.tv_mask = any_ride ? r.mask : (const float*)nullptr; ba.tv_n = N; ba.tv_override = e->tv_override; ba.sc = e->sc();
+      ba.tv_total = r.unnorm ? &e->sc()->tv_sum : r.tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr;
+      launch_build_adv(ba, s);
       LAUNCH_CHECK();
       if (r.tv_ride) e->tv.note(r.mask, N, e->tv_override);
       if (r.tv_ride_dp) CHK(comm_tv_sent(e, s));          // all-reduce of the count on the communicator's stream, joined in front of the head
@@ -996,8 +994,7 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
   } else if (p.needs_f32_image) {
     CHK(e->dcat.ensure((size_t)2 * N * p.ldc * sizeof(float)));
     if (both && p.cat0.cd > 0) {
-      hipLaunchKernelGGL(build_cat2_kernel, dim3(cdiv(N * p.K0, 256)), dim3(256), 0, s, p.x, p.cat0.cd, p.real, p.fake, p.ldf,
-                         e->d_adv_cols, e->Da, e->dcat.as<float>(), p.ldc, N);
+      launch_build_cat2(p.x, p.cat0.cd, p.real, p.fake, p.ldf, e->d_adv_cols, e->Da, e->dcat.as<float>(), p.ldc, N, s);
       LAUNCH_CHECK();
     } else {
       if (both) CHK(build_cat(e, p.x, p.real, p.ldf, 0, N, p.ldc, s));
@@ -1074,8 +1071,7 @@ static int d_pass_backward(gt_engine* e, DPass& p, float* dst, hipStream_t s) {
       if (dst) { CHK(e->d_dx0.ensure((size_t)2 * N * p.K0 * sizeof(float))); dx0 = e->d_dx0.as<float>(); }
       CHK(lstm_stack_backward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, p.want_w, dx0, s));
       if (dst) {
-        hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * Da, 256)), dim3(256), 0, s, dx0 + row0 * p.K0, p.K0, col0, (const int*)nullptr, dst, Da, 0,
-                           (int)N, Da);
+        launch_copy_cols(dx0 + row0 * p.K0, p.K0, col0, dst, Da, 0, N, Da, s);
         LAUNCH_CHECK();
       }
       return GT_OK;
@@ -1120,7 +1116,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   ride.tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_known;      // fused single-GPU call: the count is not known yet
   if (!ride.tv_ride_dp && !unnorm) CHK(ensure_tv_begin(e, mask, N, s));
   if (unnorm && !p.split) {
-    hipLaunchKernelGGL(mask_total_kernel, dim3(1), dim3(1024), 0, s, mask, (int)N, &e->sc()->tv_sum);
+    launch_mask_total(mask, N, &e->sc()->tv_sum, s);
     LAUNCH_CHECK();
   }
   CHK(d_pass_input(e, p, ride, s));
@@ -1190,7 +1186,7 @@ extern "C" int gt_update_discriminator_end(gt_engine* e, int train, gt_d_result*
     CHK(wait_early_results(e));                   // only the scalars; backward + step stay queued
     e->early_done = false;
   } else {
-    hipLaunchKernelGGL(finalize_d_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), train ? 0 : 1);
+    launch_finalize_d(e->sc(), e->res(), train ? 0 : 1, 0, s);
     LAUNCH_CHECK();
     if (!out) return post_deferred_results(e, GT_ROLE_D, s);
     CHK(fetch_results(e, s));
@@ -1225,13 +1221,15 @@ extern "C" int gt_update_discriminator(gt_engine* e, const float* x, const float
 // caller folds their reduction into a later launch (finalize_g_kernel) instead of paying a launch for it here.
 static int sum_sqerr(gt_engine* e, const float* a, int lda, const float* b, int ldb, const float* mask, long rows, int D,
                      double* out, float* g, int ldg, float gscale, hipStream_t s, int* deferred_blocks = nullptr) {
-  const int nblk = (int)std::min<long>(1024, cdiv(rows * D, RED_THREADS * 4));
   CHK(e->partial.ensure(4096 * sizeof(double)));
   double* part = e->partial.as<double>() + 1024;
-  hipLaunchKernelGGL(masked_sqerr_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, a, lda, b, ldb, mask, rows, D, part, g, ldg, gscale, e->sc());
+  SqerrArgs q;
+  memset(&q, 0, sizeof(q));
+  q.a = a; q.lda = lda; q.b = b; q.ldb = ldb; q.mask = mask; q.rows = rows; q.D = D; q.partial = part; q.g = g; q.ldg = ldg; q.gscale = gscale; q.sc = e->sc();
+  const int nblk = launch_masked_sqerr(q, s);
   LAUNCH_CHECK();
   if (deferred_blocks) { *deferred_blocks = nblk; return GT_OK; }
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, part, nblk, out);
+  launch_sum_partials(part, nblk, out, s);
   LAUNCH_CHECK();
   return GT_OK;
 }
@@ -1256,8 +1254,7 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     if (G.d.arch == GT_ARCH_IN2OUT_RNN) mse_w = 0.f;   // y_hat is the input x there: the MSE term has no path into G
     CHK(e->dgx.ensure((size_t)N * sd * sizeof(float)));
     CHK(e->dtz.ensure((size_t)N * sd * sizeof(float)));
-    hipLaunchKernelGGL(highway_backward_kernel, dim3(cdiv(N * sd, 256)), dim3(256), 0, s, gs, sd, e->tx.as<float>(), sd,
-                       e->gx.as<float>(), sd, e->dgx.as<float>(), sd, e->dtz.as<float>(), sd, N, sd);
+    launch_highway_backward(gs, sd, e->tx.as<float>(), sd, e->gx.as<float>(), sd, e->dgx.as<float>(), sd, e->dtz.as<float>(), sd, N, sd, s);
     LAUNCH_CHECK();
     CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, s, &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.gate.dW, (long)sd * sd + sd, s));
@@ -1272,7 +1269,7 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     LAUNCH_CHECK();
   }
   if (G.d.last_sigmoid && !is_i2o(G.d.arch)) {      // y_hat = sigmoid(last layer) (models.py:141, 167, 190, 213): through s (1 - s)
-    hipLaunchKernelGGL(sigmoid_grad_kernel, dim3(cdiv(N * Do, 256)), dim3(256), 0, s, gy, ldgy, y_hat, Do, N, Do);
+    launch_sigmoid_grad(gy, ldgy, y_hat, Do, N, Do, s);
     LAUNCH_CHECK();
   }
   if (has_lstm_body(G.d.arch) || G.d.arch == GT_ARCH_SRU) {
@@ -1365,11 +1362,13 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   // data parallel: the same launches, the rider then only files the three sums for the collective (nothing is reported from it)
   const bool riders_dp = e->early && comm_on(e) && e->opt_launch_riders && !(tr && direct && mse_w != 0.f);
   if (riders || riders_dp) {
-    mse_blocks = (int)std::min<long>(1024, cdiv(N * Do, RED_THREADS * 4));
-    mge_pre_blocks = (int)std::min<long>(1024, cdiv(N * Ds, RED_THREADS * 4));
     CHK(e->partial.ensure(4096 * sizeof(double)));
-    hipLaunchKernelGGL(g_losses_kernel, dim3(mse_blocks + mge_pre_blocks), dim3(RED_THREADS), 0, s, y_hat, Do, y, Do, Do, mse_blocks,
-                       e->partial.as<double>() + 1024, y_hat_static, Ds, y_static, Ds, Ds, e->partial.as<double>(), mask, N);
+    GLossesArgs q;
+    memset(&q, 0, sizeof(q));
+    q.a1 = y_hat; q.lda1 = Do; q.b1 = y; q.ldb1 = Do; q.D1 = Do; q.partial1 = e->partial.as<double>() + 1024;
+    q.a2 = y_hat_static; q.lda2 = Ds; q.b2 = y_static; q.ldb2 = Ds; q.D2 = Ds; q.partial2 = e->partial.as<double>();
+    q.mask = mask; q.rows = N;
+    launch_g_losses(q, &mse_blocks, &mge_pre_blocks, s);
     LAUNCH_CHECK();
   } else if (!(tr && direct && mse_w != 0.f)) {
     CHK(sum_sqerr(e, y_hat, Do, y, Do, mask, N, Do, &e->sc()->s_mse, nullptr, 0, 0.f, s, early_fold ? &mse_blocks : nullptr));
@@ -1400,7 +1399,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   int mge_blocks = 0;
   e->early_done = false;
   {
-    const int nblk = (int)std::min<long>(1024, cdiv(N * Ds, RED_THREADS * 4));
+    int nblk = frame_red_blocks(N * Ds);
     CHK(e->partial.ensure(4096 * sizeof(double)));
     float* gs = nullptr;
     if (tr) { CHK(e->gs.ensure((size_t)N * Ds * sizeof(float))); gs = e->gs.as<float>(); }
@@ -1416,24 +1415,26 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
       fin.hp = head_blocks ? e->headp.as<HeadPartials>() : (const HeadPartials*)nullptr; fin.n_hp = head_blocks;
       if (riders) { fin.ticket_value = take_ticket(e); fin.ticket = fin.ticket_value ? e->ticket_dev() : (unsigned*)nullptr; }
     }
-    if (tr || !rid)
-      hipLaunchKernelGGL(static_grad_kernel, dim3(nblk + (rid ? 1 : 0)), dim3(RED_THREADS), 0, s, y_hat_static, Ds,
-                         y_static, Ds, mask, N, Ds, mge_w, e->d_adv_inv, leak, e->Da, gadv, e->Da, adv_w, gs, Ds,
-                         rid ? (double*)nullptr : e->partial.as<double>(), e->sc(), fin, leak && e->leak_unnorm ? 1 : 0);
-    else      // phase != "train": no gradient to assemble, the finalisation alone
-      hipLaunchKernelGGL(finalize_g_rider_kernel, dim3(1), dim3(RED_THREADS), 0, s, fin);
+    if (tr || !rid) {
+      StaticGradArgs q;
+      memset(&q, 0, sizeof(q));
+      q.yhs = y_hat_static; q.ld1 = Ds; q.ys = y_static; q.ld2 = Ds; q.mask = mask; q.rows = N; q.Ds = Ds; q.mge_w = mge_w;
+      q.adv_inv = e->d_adv_inv; q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
+      q.partial = rid ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak_unnorm ? 1 : 0;
+      nblk = launch_static_grad(q, s);
+    } else      // phase != "train": no gradient to assemble, the finalisation alone
+      launch_finalize_g_rider(fin, s);
     LAUNCH_CHECK();
     mge_blocks = nblk;
     if (riders) CHK(post_early_results(e, s, fin.ticket_value));
     else if (!early_now && !riders_dp) {   // the split-phase (data-parallel) caller all-reduces the sum itself: it must exist now
-      hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, e->partial.as<double>(), nblk, &e->sc()->s_mge);
+      launch_sum_partials(e->partial.as<double>(), nblk, &e->sc()->s_mge, s);
       LAUNCH_CHECK();
     }
   }
   if (early_now && !riders) {   // all four losses are final here; the MGE partials are reduced inside the finalisation launch
-    hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(256), 0, s, e->sc(), early_res_target(e), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1,
-                       (const double*)e->partial.as<double>(), mge_blocks,
-                       mse_blocks ? (const double*)(e->partial.as<double>() + 1024) : (const double*)nullptr, mse_blocks);
+    launch_finalize_g(e->sc(), early_res_target(e), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, e->partial.as<double>(), mge_blocks,
+                      mse_blocks ? (const double*)(e->partial.as<double>() + 1024) : (const double*)nullptr, mse_blocks, s);
     LAUNCH_CHECK();
     CHK(post_early_results(e, s));
   }
@@ -1459,8 +1460,7 @@ extern "C" int gt_update_generator_end(gt_engine* e, int train, float adv_w, flo
     CHK(wait_early_results(e));
     e->early_done = false;
   } else {
-    hipLaunchKernelGGL(finalize_g_kernel, dim3(1), dim3(1), 0, s, e->sc(), e->res(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0,
-                       train ? 0 : 1, (const double*)nullptr, 0, (const double*)nullptr, 0);
+    launch_finalize_g(e->sc(), e->res(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, train ? 0 : 1, nullptr, 0, nullptr, 0, s);
     LAUNCH_CHECK();
     if (!out) return post_deferred_results(e, GT_ROLE_G, s);
     CHK(fetch_results(e, s));
@@ -1504,10 +1504,9 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
     // scatter leak[:, j] -> gs[:, adv_cols[j]]  (gather with swapped roles: one column at a time is fine here)
     std::vector<int>& cols = e->h_adv_cols;
     for (int j = 0; j < e->Da; ++j) {
-      hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, e->leak.as<float>(), e->Da, j, (const int*)nullptr,
-                         e->gs.as<float>(), Ds, cols[j], (int)N, 1);
+      launch_copy_cols(e->leak.as<float>(), e->Da, j, e->gs.as<float>(), Ds, cols[j], N, 1, s);
     }
-    if (e->leak_unnorm) hipLaunchKernelGGL(scale_by_inv_tv_kernel, dim3(cdiv(N * Ds, 256)), dim3(256), 0, s, e->gs.as<float>(), N * Ds, e->sc());
+    if (e->leak_unnorm) launch_scale_by_inv_tv(e->gs.as<float>(), N * Ds, e->sc(), s);
     LAUNCH_CHECK();
   }
   CHK(generator_backward(e, e->last_x, e->last_yhat, e->last_yhat, (const float*)nullptr, 0.f, s));

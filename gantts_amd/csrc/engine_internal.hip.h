@@ -32,6 +32,7 @@
 #include "../../include/gantts_hip.h"
 #pragma GCC visibility pop
 #include "frame_kernels.hip.h"
+#include "frame_args.hip.h"
 #include "gemm_f32.hip.h"
 #include "gemm_bf16s.hip.h"
 #include "sru_args.hip.h"

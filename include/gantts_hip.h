@@ -829,6 +829,74 @@ typedef struct gt_dstack_case {
 } gt_dstack_case;
 int gt_op_dstack(const gt_dstack_case* c, void* stream);
 
+/* Parity hook of the per-frame kernels between the products of a G+D step (frame_kernels.hip.h): ONE launch function of frame_args.hip.h,
+ * the function the step itself calls, with the step's freedom in the arguments.  `op` selects it; a, b, c, d, mask, idx, tv_dev, part_mge,
+ * part_mse, hp, out, out2 are the caller's device buffers, every matrix with its row pitch in floats; sums, partials, scalars are host arrays.
+ *   MASK_SUM       mask [n_mask], tv_override (> 0 wins over the sum), tv_dev (a device double, wins over both) -> scalars tv, inv_tv
+ *   MASK_TOTAL     mask [n_mask] -> scalars tv_sum
+ *   SQERR          a, b [rows][lda / ldb] over cols columns, mask [rows] -> partials, scalars s_mse (sum_partials_kernel); out != null: the
+ *                  gradient [rows][ldo] = 2 w0 (a m - b m) m / tv
+ *   G_LOSSES       (a, b) over cols columns -> the first n1 partials and s_mse, (c, d) over cols2 columns -> the rest and s_mge
+ *   STATIC_GRAD    a = y_hat_static, b = y_static over cols columns, w0 = mge_w, idx = adv_inv [cols] with entries in [-1, cols2), c = leak,
+ *                  d = gadv [rows][ldc / ldd] (each may be null), adv_w, leak_unnorm; out = gs [rows][ldo] or null; want_partial: partials
+ *                  (and, without the rider, s_mge).  rider != 0: the finalisation workgroup, as FINALIZE_G_RIDER
+ *   FINALIZE_G     finalize_g_kernel: 256 threads with part_mge / part_mse (device, n_mge / n_mse entries), one thread without; zero_gnorm
+ *   FINALIZE_G_RIDER   finalize_g_rider_kernel; hp: device [n_hp][5] doubles (HeadPartials) or null; fin_out == 0: the sums only
+ *   FINALIZE_D     finalize_d_kernel; zero_gnorm, tv_from_sum
+ *   SCALE_INV_TV   out [rows * cols] *= 1 / tv
+ *   HIGHWAY_FWD    out = a + b c (x, Tx, Gx); HIGHWAY_BWD: a = g, b = Tx, c = Gx -> out = dGx, out2 = dTz
+ *   SIGMOID_GRAD   out (g, in place) *= a (1 - a)
+ *   DROPOUT_APPLY  dense a -> out [rows][cols] (a == out allowed), site `drop`
+ *   BUILD_ADV      a = fa (rows below split), b = fb (the rest), pitch lda, idx [cols] with entries in [0, lda) -> out [rows][ldo], ldo % 4 == 0,
+ *                  16-byte aligned; rider 1: mask [n_mask] -> scalars tv, inv_tv (tv_override); rider 2: -> scalars tv_sum
+ *   BUILD_CAT2     a = x dense [rows][cols], b = fa, c = fb (pitch ldb), idx [cols2] -> out [2 rows][ldo], columns [0, cols + cols2)
+ *   REPITCH, DENSE_COPY   a [rows][lda] -> out [rows][ldo] (repitch: ldo % 4 == 0, 16-byte aligned, pad columns 0)
+ *   PAD_ROWS       dense a [rows][cols] -> out [rows][ldo], pad columns 0;  TRANSPOSE: a [rows][lda] -> out [cols][ldo]
+ * max_blocks: the cap on a reduction's workgroups, 0 for the engine's 1024.
+ * The normaliser of an op that reads one: has_tv (the hook puts tv and 1 / tv into its scratch scalars), else mask [n_mask] with tv_override
+ * / tv_dev, summed by the launch the step uses.  A reduction's mask has n_mask == rows entries.
+ *   sums      host, 10 doubles or null: tv_sum, s_real, s_fake, n_real_ok, n_fake_ok, s_adv, s_mge, s_mse, gnorm2_d, gnorm2_g put into the
+ *             scratch scalars before the launch (what a finalisation without partials reads)
+ *   partials  host, partials_cap doubles, or null: the reduction's per-workgroup sums
+ *   scalars   host, 26 doubles or null, filled after the stream is synchronised: tv, inv_tv and the ten sums as the scratch scalars hold
+ *             them, the twelve results (loss_d, loss_fake_d, loss_real_d, real_correct, fake_correct, loss_mse, loss_mge, loss_adv, loss_g,
+ *             gnorm_d, gnorm_g, tv), the number of partials, and G_LOSSES' n1.  What nothing wrote stays NaN.
+ * The scratch scalars, results and partial buffers are filled with NaN first.  A malformed case returns GT_ERR_INVALID before any launch. */
+enum {
+  GT_FRAME_MASK_SUM = 0, GT_FRAME_MASK_TOTAL = 1, GT_FRAME_SQERR = 2, GT_FRAME_G_LOSSES = 3, GT_FRAME_STATIC_GRAD = 4, GT_FRAME_FINALIZE_G = 5,
+  GT_FRAME_FINALIZE_G_RIDER = 6, GT_FRAME_FINALIZE_D = 7, GT_FRAME_SCALE_INV_TV = 8, GT_FRAME_HIGHWAY_FWD = 9, GT_FRAME_HIGHWAY_BWD = 10,
+  GT_FRAME_SIGMOID_GRAD = 11, GT_FRAME_DROPOUT_APPLY = 12, GT_FRAME_BUILD_ADV = 13, GT_FRAME_BUILD_CAT2 = 14, GT_FRAME_REPITCH = 15,
+  GT_FRAME_DENSE_COPY = 16, GT_FRAME_PAD_ROWS = 17, GT_FRAME_TRANSPOSE = 18
+};
+typedef struct gt_frame_case {
+  int32_t op, max_blocks, cols, cols2;
+  int32_t lda, ldb, ldc, ldd;
+  int32_t ldo, ldo2, has_tv, want_partial;
+  int32_t leak_unnorm, rider, fin_out, has_adv;
+  int32_t zero_gnorm, tv_from_sum, n_mge, n_mse;
+  int32_t n_hp, pad_;
+  float tv, tv_override;
+  float w0, adv_w, mse_w, mge_w;
+  int64_t rows, split, n_mask, partials_cap;
+  gt_drop_site drop;
+  const float* a;
+  const float* b;
+  const float* c;
+  const float* d;
+  const float* mask;
+  const int32_t* idx;
+  const double* tv_dev;
+  const double* part_mge;
+  const double* part_mse;
+  const double* hp;
+  float* out;
+  float* out2;
+  const double* sums;
+  double* partials;
+  double* scalars;
+} gt_frame_case;
+int gt_op_frame(const gt_frame_case* c, void* stream);
+
 /* Parity hook of banded MLPG: ONE forward or transpose launch through ensure_band and mlpg_forward / mlpg_backward, the functions the
  * step calls, with the step's own freedom in the arguments: column maps, pitches, and the masked-MSE gradient fused into the transpose.
  *   e        the engine: num_windows, the band cache and (mse_w != 0) the scalars; R [T][num_windows * T] as in gt_op_mlpg_forward

@@ -53,6 +53,8 @@ def test_ctypes_structs_match_header_layout():
     assert _lib.DStackCase.eps.offset == 48 and _lib.DStackCase.rows.offset == 56 and _lib.DStackCase.drop.offset == 80
     assert _lib.DStackCase.H0.offset == 304 and _lib.DStackCase.W.offset == 312 and _lib.DStackCase.Hout.offset == 408
     assert _lib.DStackCase.gadv.offset == 480 and _lib.DStackCase.scalars.offset == 488 and C.sizeof(_lib.DStackCase) == 496
+    assert _lib.FrameCase.tv.offset == 88 and _lib.FrameCase.rows.offset == 112 and _lib.FrameCase.drop.offset == 144 and _lib.FrameCase.a.offset == 200
+    assert _lib.FrameCase.out.offset == 280 and _lib.FrameCase.scalars.offset == 312 and C.sizeof(_lib.FrameCase) == 320
     assert _lib.MlpgCase.ldy.offset == 16 and _lib.MlpgCase.ldt.offset == 32 and _lib.MlpgCase.mse_w.offset == 36 and _lib.MlpgCase.e.offset == 40
     assert _lib.MlpgCase.R.offset == 48 and _lib.MlpgCase.scol.offset == 56 and _lib.MlpgCase.y.offset == 72 and _lib.MlpgCase.gs.offset == 88
     assert _lib.MlpgCase.yhat.offset == 104 and _lib.MlpgCase.mask.offset == 120 and _lib.MlpgCase.kb.offset == 128 and C.sizeof(_lib.MlpgCase) == 136
