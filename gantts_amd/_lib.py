@@ -43,6 +43,7 @@ OPT_SGD, OPT_RMSPROP, OPT_ADADELTA, OPT_ADAMW, OPT_ADAMAX = 2, 3, 4, 5, 6
 OPT_NADAM, OPT_RADAM, OPT_RPROP, OPT_ASGD = 7, 8, 9, 10
 OPTF_NESTEROV, OPTF_CENTERED, OPTF_AMSGRAD, OPTF_BUFFER_LIVE = 1, 2, 4, 8      # OptimDescEx.flags
 OPTF_DECOUPLED_WD = 32                                                         # NAdam, RAdam
+MLPG_VAR_PATH_SLOTS = 3                                                 # gt_mlpg_var_path_counts: solve<1>, solve<2>, generic
 MAX_STREAMS = 8
 MLPG_R_FROM_WINDOWS = 1                 # GT_MLPG_R_FROM_WINDOWS: "build the band from the registered windows", passed in place of R
 MLPG_MAX_WINDOW_SPAN = 32               # GT_MLPG_MAX_WINDOW_SPAN
@@ -168,6 +169,12 @@ class MlpgCase(C.Structure):
                 + [("kb", C.POINTER(C.c_int32))])
 
 
+class MlpgVarCase(C.Structure):
+    _fields_ = ([("e", C.c_void_p)] + [(n, C.c_int32) for n in ("B", "T", "Ds", "ldy", "ldv", "ldys")]
+                + [(n, C.c_void_p) for n in ("scol", "sstride")] + [("lengths", C.POINTER(C.c_int64))]
+                + [(n, C.c_void_p) for n in ("y", "var", "ys")] + [("max_ws_bytes", C.c_int64)])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -235,6 +242,8 @@ SIGNATURES = {
     "gt_op_frame": (_I, [C.POINTER(FrameCase), _P]),
     "gt_op_mlpg": (_I, [C.POINTER(MlpgCase), _P]),
     "gt_op_mlpg_band": (_I, [_P, _P, _I, C.POINTER(_F), _L, C.POINTER(C.c_int32), _P]),
+    "gt_op_mlpg_var": (_I, [C.POINTER(MlpgVarCase), _P]),
+    "gt_mlpg_var_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

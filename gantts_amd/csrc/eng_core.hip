@@ -154,7 +154,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   }
   Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
                     &e->cx_dense.buf, &e->dx_pitched.buf, &e->gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
-                    &e->mlpg.fac, &e->mlpg.wide, &e->comm_tv, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2};
+                    &e->mlpg.fac, &e->mlpg.wide, &e->comm_tv, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2, &e->mlpg_var_ws};
   for (auto* s : all) s->release();
   e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
   e->mlpg.clear();

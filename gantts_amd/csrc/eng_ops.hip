@@ -200,6 +200,49 @@ extern "C" int gt_op_mlpg_band(gt_engine* e, const float* R, int T, float* band_
   return GT_OK;
 }
 
+// nnmnkwii.paramgen.mlpg for a batch (launch_mlpg_var, eng_step.hip).  Everything a kernel would index with is checked first.
+static_assert(offsetof(gt_mlpg_var_case, B) == 8 && offsetof(gt_mlpg_var_case, scol) == 32 && offsetof(gt_mlpg_var_case, max_ws_bytes) == 80 &&
+              sizeof(gt_mlpg_var_case) == 88, "layout bound by gantts_amd/_lib.py");
+extern "C" int gt_op_mlpg_var(const gt_mlpg_var_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  gt_engine* e = c->e;
+  CHK(check_common(e, c->B, c->T));
+  if (!e->mlpg.has_win) return fail(GT_ERR_INVALID, "variance-weighted MLPG without a window set: call gt_set_mlpg_windows first");
+  const bool own = !c->scol && !c->sstride;
+  if (!own && (!c->scol || !c->sstride)) return fail(GT_ERR_INVALID, "variance-weighted MLPG: scol and sstride come together");
+  if (own && c->Ds != 0 && c->Ds != e->Ds) return fail(GT_ERR_INVALID, "variance-weighted MLPG: Ds = %d with the engine's maps (%d)", c->Ds, e->Ds);
+  const int Ds = own ? e->Ds : c->Ds;
+  if (Ds < 1 || Ds > (1 << 20)) return fail(GT_ERR_INVALID, "variance-weighted MLPG: Ds = %d", Ds);
+  if (!c->y || !c->var || !c->ys) return fail(GT_ERR_INVALID, "variance-weighted MLPG: null tensor");
+  for (const void* q : {(const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->var, (const void*)c->ys})
+    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "variance-weighted MLPG: misaligned operand");
+  if (c->max_ws_bytes < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: negative max_ws_bytes");
+  if (c->ldys < Ds) return fail(GT_ERR_INVALID, "variance-weighted MLPG: pitch of the static side below Ds = %d", Ds);
+  if (c->ldy < 1 || c->ldv < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: ldy = %d, ldv = %d", c->ldy, c->ldv);
+  if (c->lengths)
+    for (int b = 0; b < c->B; ++b)
+      if (c->lengths[b] < 1 || c->lengths[b] > c->T) return fail(GT_ERR_INVALID, "variance-weighted MLPG: length %lld outside [1, T=%d]", (long long)c->lengths[b], c->T);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> h_scol, h_sstride;
+  if (own) { h_scol = e->h_scol; h_sstride = e->h_sstride; }
+  else {
+    h_scol.resize(Ds); h_sstride.resize(Ds);
+    HIPCHK(hipMemcpyAsync(h_scol.data(), c->scol, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_sstride.data(), c->sstride, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  const int nW = e->cfg.num_windows;
+  for (int i = 0; i < Ds; ++i) {
+    const long col = h_scol[i], st = h_sstride[i];
+    if (col < 0 || st < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: negative entry in the column maps at %d", i);
+    const long last = col + (long)(nW - 1) * st;      // pass-through (st == 0): its own column only
+    if (last >= c->ldy) return fail(GT_ERR_INVALID, "variance-weighted MLPG: static column %d reaches column %ld, ldy is %d", i, last, c->ldy);
+    if (c->ldv && st && last >= c->ldv) return fail(GT_ERR_INVALID, "variance-weighted MLPG: static column %d reaches column %ld, ldv is %d", i, last, c->ldv);
+  }
+  return launch_mlpg_var(e, c->y, c->ldy, c->var, c->ldv, own ? e->d_scol : (const int*)c->scol, own ? e->d_sstride : (const int*)c->sstride, Ds,
+                         c->ys, c->ldys, c->lengths, c->B, c->T, c->max_ws_bytes, s);
+}
+
 static DropoutSpec buffer_spec(const float* keep_mask, float p, int ld) {
   DropoutSpec d = no_drop();
   if (keep_mask && p > 0.f) { d.mode = DROP_BUFFER; d.mask = keep_mask; d.ld_mask = ld; d.p = p; d.scale = 1.f / (1.f - p); }

@@ -2,6 +2,7 @@
 #include "engine_internal.hip.h"
 #include "d_tail_args.hip.h"
 #include "mlpg_band_kernels.hip.h"
+#include "mlpg_var_kernels.hip.h"
 #include <atomic>
 
 using namespace gt;
@@ -127,6 +128,77 @@ extern "C" int gt_set_mlpg_windows(gt_engine* e, int n, const int32_t* l, const 
   }
   memcpy(&m.win, &win, sizeof(win));      // padding included: the comparison above is a memcmp
   m.has_win = true;
+  return GT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// variance-weighted MLPG (mlpg_var_kernels.hip.h): a batch of independent banded solves, one thread per (sequence, static column)
+// ------------------------------------------------------------------------------------------
+// gt_mlpg_var_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
+static std::atomic<int64_t> g_mlpg_var_paths[GT_MLPG_VAR_PATH_SLOTS];
+extern "C" int gt_mlpg_var_path_counts(int64_t* counts, int n) {
+  for (int i = 0; i < GT_MLPG_VAR_PATH_SLOTS; ++i) {
+    if (!counts) g_mlpg_var_paths[i].store(0, std::memory_order_relaxed);
+    else if (i < n) counts[i] = g_mlpg_var_paths[i].load(std::memory_order_relaxed);
+  }
+  return GT_OK;
+}
+template <int HB> static MlpgVarTaps<HB> mlpg_var_taps(const MlpgWindows& win) {
+  MlpgVarTaps<HB> t;
+  memset(&t, 0, sizeof(t));
+  t.n = win.n;
+  for (int w = 0; w < win.n; ++w) {
+    t.l[w] = win.l[w];
+    for (int q = 0; q <= win.l[w] + win.u[w]; ++q) t.c[w][q] = win.coef[w][q];
+  }
+  return t;
+}
+// y [B*T][ldy], var [B*T][ldv] (ldv == 0: one row), ys [B*T][ldys]; scol, sstride device [Ds]; lengths: host, B entries in [1, T] (checked by
+// the caller, like every pointer and pitch).  The batch goes in groups of whole sequences whose scratch 8 (hb + 2) T nseq Ds stays within
+// max_ws_bytes (0: 64 MB); the stream is synchronised, because the refusal flag is read.
+int launch_mlpg_var(gt_engine* e, const float* y, int ldy, const float* var, int ldv, const int* scol, const int* sstride, int Ds, float* ys, int ldys,
+                    const int64_t* lengths, int B, int T, int64_t max_ws_bytes, hipStream_t s) {
+  const MlpgCache& m = e->mlpg;
+  if (!m.has_win) return fail(GT_ERR_INVALID, "variance-weighted MLPG without a window set: call gt_set_mlpg_windows first");
+  const MlpgWindows& win = m.win;
+  int hb = 0;
+  for (int w = 0; w < win.n; ++w) hb = std::max(hb, win.l[w] + win.u[w]);
+  const size_t cap = max_ws_bytes > 0 ? (size_t)max_ws_bytes : (size_t)64 << 20;
+  const size_t per_seq = sizeof(double) * (size_t)(hb + 2) * (size_t)T * (size_t)Ds;
+  const int per_group = (int)std::min<size_t>((size_t)B, cap / per_seq);
+  if (per_group < 1)
+    return fail(GT_ERR_INVALID, "variance-weighted MLPG: one sequence of T=%d frames and %d static columns needs %zu bytes of scratch, the cap is %zu", T, Ds, per_seq, cap);
+  const size_t off_len = 256, off_ws = off_len + (((size_t)B * sizeof(int) + 255) & ~(size_t)255);
+  Scratch& q = e->mlpg_var_ws;
+  CHK(q.ensure(off_ws + per_seq * (size_t)per_group));
+  int* flag = (int*)q.p;
+  int* d_len = (int*)((char*)q.p + off_len);
+  std::vector<int> h_len(B);
+  for (int b = 0; b < B; ++b) h_len[b] = lengths ? (int)lengths[b] : T;
+  HIPCHK(hipMemsetAsync(flag, 0, sizeof(int), s));
+  HIPCHK(hipMemcpyAsync(d_len, h_len.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+  hipError_t err = hipSuccess;
+  for (int b0 = 0; b0 < B && err == hipSuccess; b0 += per_group) {
+    MlpgVarArgs a;
+    a.nseq = std::min(per_group, B - b0); a.T = T; a.Ds = Ds; a.ldy = ldy; a.ldv = ldv; a.ldys = ldys;
+    a.y = y + (size_t)b0 * T * ldy; a.var = var + (size_t)b0 * T * ldv; a.ys = ys + (size_t)b0 * T * ldys;
+    a.scol = scol; a.sstride = sstride; a.len = d_len + b0;
+    a.ws = (double*)((char*)q.p + off_ws); a.flag = flag;
+    const dim3 grid(cdiv((long)a.nseq * Ds, MLPG_VAR_THREADS)), block(MLPG_VAR_THREADS);
+    int slot;
+    if (hb == 1) { slot = 0; hipLaunchKernelGGL(mlpg_var_solve_kernel<1>, grid, block, 0, s, a, mlpg_var_taps<1>(win)); }
+    else if (hb == 2) { slot = 1; hipLaunchKernelGGL(mlpg_var_solve_kernel<2>, grid, block, 0, s, a, mlpg_var_taps<2>(win)); }
+    else { slot = 2; hipLaunchKernelGGL(mlpg_var_generic_kernel, grid, block, 0, s, a, win, hb); }
+    err = hipGetLastError();
+    if (err == hipSuccess) g_mlpg_var_paths[slot].fetch_add(1, std::memory_order_relaxed);
+  }
+  int h_flag = 0;
+  if (err == hipSuccess) err = hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s);
+  const hipError_t err_sync = hipStreamSynchronize(s);      // also keeps h_len alive until its copy is done
+  if (err == hipSuccess) err = err_sync;
+  if (err != hipSuccess) return fail(GT_ERR_HIP, "variance-weighted MLPG: %s", hipGetErrorString(err));
+  if (h_flag & MLPG_VAR_BAD_VARIANCE) return fail(GT_ERR_INVALID, "variance-weighted MLPG: variances must be finite and positive");
+  if (h_flag) return fail(GT_ERR_INVALID, "variance-weighted MLPG: variances must be finite and positive (a pivot of W^T diag(1/var) W is not: the windows do not determine the static features)");
   return GT_OK;
 }
 

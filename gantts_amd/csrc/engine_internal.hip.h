@@ -259,6 +259,7 @@ struct gt_engine {
   // In2Out uses a single dynamic stream of width out_dim
   int *d_scol_i2o = nullptr, *d_sstride_i2o = nullptr; int i2o_ds = 0;
   MlpgCache mlpg;
+  Scratch mlpg_var_ws;                     // variance-weighted MLPG: refusal flag, lengths, then L and z of one group of sequences (float64)
   NetWs ws[2];                             // workspace: per role, then (below) what one call uses and both roles share
   Scratch dcat, dzA, dzB, leak, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
   Scratch scal;                            // StepScalars + StepResults
@@ -463,6 +464,8 @@ int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const i
 int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, const int* sstride, int Ds,
                   float* gy, int ldgy, int B, int T, float mse_w, const float* yhat, const float* ytgt, int ldt,
                   const float* mask, hipStream_t s);
+int launch_mlpg_var(gt_engine* e, const float* y, int ldy, const float* var, int ldv, const int* scol, const int* sstride, int Ds, float* ys, int ldys,
+                    const int64_t* lengths, int B, int T, int64_t max_ws_bytes, hipStream_t s);      // eng_step.hip; synchronises s
 int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket = 0);
 int cond_dim(gt_engine* e);
 

@@ -114,6 +114,7 @@ class StepEngine(object):
         self.static_dim = int(sum(ss))
         self.num_windows = nW
         self._windows_sent = None                # window signature registered through gt_set_mlpg_windows
+        self._hp_windows = list(hp.windows)      # what mlpg_var registers when it is given none
 
     @classmethod
     def for_forward_only(cls, model):
@@ -309,13 +310,17 @@ class StepEngine(object):
             raise RuntimeError("MLPGBand was made for T = %d, the batch has T = %d" % (R.T, T))
         if R.num_windows != self.num_windows:
             raise RuntimeError("MLPGBand has %d windows, the engine %d" % (R.num_windows, self.num_windows))
-        if self._windows_sent != R.window_signature:
-            n = R.num_windows
-            coef = np.concatenate([c for (_, _, c) in R.windows])
-            check(lib.gt_set_mlpg_windows(self._h, n, (C.c_int32 * n)(*[l for (l, _, _) in R.windows]),
-                                          (C.c_int32 * n)(*[u for (_, u, _) in R.windows]), (C.c_double * coef.size)(*coef.tolist())))
-            self._windows_sent = R.window_signature
+        self._register_windows(R)
         return C.c_void_p(L.MLPG_R_FROM_WINDOWS), R
+
+    def _register_windows(self, band):
+        """gt_set_mlpg_windows with the windows of an ``MLPGBand``, once per engine and window set."""
+        if self._windows_sent != band.window_signature:
+            n = band.num_windows
+            coef = np.concatenate([c for (_, _, c) in band.windows])
+            check(lib.gt_set_mlpg_windows(self._h, n, (C.c_int32 * n)(*[l for (l, _, _) in band.windows]),
+                                          (C.c_int32 * n)(*[u for (_, u, _) in band.windows]), (C.c_double * coef.size)(*coef.tolist())))
+            self._windows_sent = band.window_signature
 
     def mlpg_band(self, R, T=None):
         """Parity hook (gt_op_mlpg_band): ``(band, kb)`` of the band cache's entry for a dense device R or an ``MLPGBand`` --
@@ -566,6 +571,39 @@ class StepEngine(object):
         Rp, R = self._mlpg_operand(R, T)
         out = torch.empty(B, T, self.static_dim, device=y.device, dtype=torch.float32)
         check(lib.gt_op_mlpg_forward(self._h, ptr(y), Rp, B, T, ptr(out), L.current_stream()))
+        return out
+
+    def mlpg_var(self, y, var, lengths=None, windows=None, max_ws_bytes=0):
+        """Variance-weighted MLPG (``nnmnkwii.paramgen.mlpg``) of a batch through the engine's multi-stream maps: one launch serves every
+        stream, the streams without dynamic features are copied.  ``y`` (B, T, D) float32 on the device; ``var`` (D,) -- one row for
+        every frame -- or (B, T, D); ``lengths``: B entries in [1, T], each sequence is solved over its own length and its rows beyond
+        are 0.  ``windows``: the engine's ``hp.windows`` unless given.  Returns (B, T, static_dim).  Variances that are not finite and
+        positive raise ``ValueError``."""
+        y = _check_frames(y, "means")
+        if y.dim() != 3:
+            raise ValueError("means must be (B, T, D), got %s" % (tuple(y.shape),))
+        B, T, D = y.shape
+        var = _check_frames(var, "variances")
+        if tuple(var.shape) == (D,):
+            ldv = 0
+        elif tuple(var.shape) == (B, T, D):
+            ldv = D
+        else:
+            raise ValueError("variances must be (%d,) or %s, got %s" % (D, (B, T, D), tuple(var.shape)))
+        windows = self._hp_windows if windows is None else windows
+        if any(w is None for w in windows):
+            raise ValueError("this engine's hp holds no window coefficients: pass windows")
+        self._register_windows(MLPGBand(windows, T))
+        g = L.MlpgVarCase()
+        g.e, g.B, g.T, g.Ds, g.ldy, g.ldv, g.ldys = self._h, B, T, 0, D, ldv, self.static_dim
+        if lengths is not None:
+            vals = [int(v) for v in (lengths.detach().cpu().view(-1).tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+            if len(vals) != B:
+                raise ValueError("lengths has %d entries for a batch of %d sequences" % (len(vals), B))
+            g.lengths = (C.c_int64 * B)(*vals)
+        out = torch.empty(B, T, self.static_dim, device=y.device, dtype=torch.float32)
+        g.y, g.var, g.ys, g.max_ws_bytes = y.data_ptr(), var.data_ptr(), out.data_ptr(), int(max_ws_bytes)
+        check(lib.gt_op_mlpg_var(C.byref(g), L.current_stream()))
         return out
 
     def mlpg_backward(self, g_static, R, full_dim):

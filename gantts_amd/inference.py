@@ -9,6 +9,8 @@ of these calls:
                                                       evaluation_tts.py:153-178 (gen_duration minus the label I/O)
     predict_acoustic(model, feats, X_min, X_max)      evaluation_tts.py:205-219
     gen_parameters(y_predicted, Y_mean, Y_std)        evaluation_tts.py:47-100 (MGE branch)
+    gen_parameters_without_mge(y_predicted, Y_mean, Y_std)
+                                                      evaluation_tts.py:84-99 (the other branch, as it evidently means)
     vc_convert(model, mc, data_mean, data_std)        evaluation_vc.py:56-92 (between analysis and synthesis)
 
 ``hp_acoustic`` / ``hp_duration`` / ``hp_vc`` are module globals like in the reference scripts.
@@ -85,13 +87,17 @@ def _mlpg_matrix(windows, T, device_band):
 
 
 def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True, device_band=False):
-    """(mgc, lf0, vuv, bap): multi-stream MLPG on the normalised features (the banded device kernel,
-    unit variance) followed by inverse scaling with statistics indexed in the static+dynamic domain.
-    ``Y_mean`` / ``Y_std`` are the reference's dicts (``["acoustic"]``) or plain arrays.
-    ``device_band``: build the MLPG band on the device from ``hp.windows`` instead of from a dense host R."""
+    """(mgc, lf0, vuv, bap) of one utterance.  ``Y_mean`` / ``Y_std`` are the reference's dicts (``["acoustic"]``) or plain arrays.
+
+    ``mge_training=True``: multi-stream MLPG on the normalised features (the banded device kernel, unit variance) followed by inverse
+    scaling with statistics indexed in the static+dynamic domain.  ``device_band``: build the MLPG band on the device from
+    ``hp.windows`` instead of from a dense host R.
+
+    ``mge_training=False`` raises ``NotImplementedError``, as before: the reference's own branch cannot run (it multiplies a dict,
+    evaluation_tts.py:86).  What that branch evidently means is ``gen_parameters_without_mge``."""
     if not mge_training:
-        raise NotImplementedError("the reference's non-MGE branch multiplies a dict (evaluation_tts.py:86) and "
-                                  "cannot run; GAN generators are MGE-trained")
+        raise NotImplementedError("the reference's non-MGE branch multiplies a dict (evaluation_tts.py:86) and cannot run; "
+                                  "what it evidently means is gen_parameters_without_mge(y_predicted, Y_mean, Y_std)")
     hp = hp_acoustic
     mean = Y_mean["acoustic"] if isinstance(Y_mean, dict) else Y_mean
     std = Y_std["acoustic"] if isinstance(Y_std, dict) else Y_std
@@ -108,6 +114,31 @@ def gen_parameters(y_predicted, Y_mean, Y_std, mge_training=True, device_band=Fa
     lf0 = static[:, smgc:smgc + slf0] * std[lf0_0:lf0_0 + lf0_dim // nw] + mean[lf0_0:lf0_0 + lf0_dim // nw]
     bap = static[:, smgc + slf0 + svuv:] * std[bap_0:bap_0 + bap_dim // nw] + mean[bap_0:bap_0 + bap_dim // nw]
     vuv = y[0, :, vuv_0].cpu().numpy() * std[vuv_0] + mean[vuv_0]
+    return mgc, lf0, vuv, bap
+
+
+def gen_parameters_without_mge(y_predicted, Y_mean, Y_std):
+    """(mgc, lf0, vuv, bap) of one utterance for a generator trained WITHOUT the MGE criterion (the baseline stage of train_gan.sh, any
+    plain-MSE model): evaluation_tts.py:84-99 as it evidently means -- the reference itself hands the dicts to inv_scale (line 86) and
+    indexes a plain array with a string (line 95), so the branch cannot run there, and ``gen_parameters(mge_training=False)`` keeps
+    refusing it.  The features are denormalised first; mgc, lf0 and bap come from the variance-weighted MLPG (``paramgen.mlpg``, one
+    ``StepEngine.mlpg_var`` launch for the three) with the data variance ``Y_std ** 2``; vuv is the denormalised column.  ``Y_mean`` /
+    ``Y_std`` and the return types are those of ``gen_parameters``.  The device takes the denormalised features and the variances
+    rounded to float32."""
+    hp = hp_acoustic
+    mean = np.asarray(Y_mean["acoustic"] if isinstance(Y_mean, dict) else Y_mean, dtype=np.float64)
+    std = np.asarray(Y_std["acoustic"] if isinstance(Y_std, dict) else Y_std, dtype=np.float64)
+    y = y_predicted.detach().cpu().numpy() if isinstance(y_predicted, torch.Tensor) else np.asarray(y_predicted)
+    y = y.reshape(-1, y.shape[-1]).astype(np.float64)
+    den = y * std + mean
+    mgc_dim, lf0_dim, vuv_dim, bap_dim = hp.stream_sizes
+    nw = len(hp.windows)
+    smgc, slf0, svuv, sbap = [int(v) for v in get_static_stream_sizes(hp.stream_sizes, hp.has_dynamic_features, nw)]
+    dev_y = torch.from_numpy(den.astype(np.float32)).cuda().view(1, -1, den.shape[-1])
+    dev_var = torch.from_numpy((std * std).astype(np.float32)).cuda()
+    static = _engine(hp).mlpg_var(dev_y, dev_var)[0].double().cpu().numpy()
+    mgc, lf0, bap = static[:, :smgc], static[:, smgc:smgc + slf0], static[:, smgc + slf0 + svuv:]
+    vuv = den[:, mgc_dim + lf0_dim]
     return mgc, lf0, vuv, bap
 
 

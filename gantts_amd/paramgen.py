@@ -10,6 +10,9 @@ and uploads T x 3T floats every batch.
 ``MLPGBand`` / ``unit_variance_mlpg_band`` stand for the same matrix without forming it: the engine builds the taps its
 kernels read on the device from the windows (gt_set_mlpg_windows, GT_MLPG_R_FROM_WINDOWS) -- no O(T^2) host work, upload or
 cache entry per padded length.
+
+``mlpg`` / ``mlpg_batch`` are ``nnmnkwii.paramgen.mlpg`` itself -- the general maximum-likelihood parameter generation with per-dimension
+or per-frame variances, which no R expresses -- as a batch of banded solves on the device (gt_op_mlpg_var).
 """
 import numpy as np
 import scipy.linalg
@@ -113,3 +116,70 @@ class MLPGBand(object):
 def unit_variance_mlpg_band(windows, T):
     """Drop-in for ``unit_variance_mlpg_matrix_cuda`` that never forms R."""
     return MLPGBand(windows, T)
+
+
+_var_engines = {}
+
+
+def _check_mlpg_args(means, variances, windows, batch):
+    """shapes of ``mlpg`` / ``mlpg_batch``: ValueError before anything touches the device"""
+    nd = 3 if batch else 2
+    if len(windows) < 1:
+        raise ValueError("mlpg: no windows")
+    if len(means.shape) != nd:
+        raise ValueError("mlpg: mean_frames must have %d dimensions, got shape %s" % (nd, tuple(means.shape)))
+    D = int(means.shape[-1])
+    if D % len(windows) != 0:
+        raise ValueError("mlpg: the feature dimension %d is no multiple of the %d windows" % (D, len(windows)))
+    if tuple(variances.shape) != (D,) and tuple(variances.shape) != tuple(means.shape):
+        raise ValueError("mlpg: variance_frames must be (%d,) or %s, got %s" % (D, tuple(means.shape), tuple(variances.shape)))
+    return D
+
+
+def _var_engine(D, windows):
+    """a cached engine of one stream with dynamic features, keyed by (D, windows): the idea of ``inference._engine``"""
+    from .engine import StepEngine, _SingleStreamHP
+    key = (int(D),) + _signature(windows, 0)[1:]
+    eng = _var_engines.get(key)
+    if eng is None:
+        hp = _SingleStreamHP(int(D), len(windows), True)
+        hp.windows = list(windows)
+        eng = _var_engines[key] = StepEngine(hp)
+    return eng
+
+
+def mlpg_batch(means, variances, windows, lengths=None):
+    """``mlpg`` for a padded batch: ``means`` (B, T, D), ``variances`` (D,) or (B, T, D), ``lengths`` B entries in [1, T] (all T when
+    None).  Every sequence is solved over its own length, as if evaluated alone; its rows beyond are 0.  One call to the operator.
+    Returns (B, T, D // len(windows)) in the input's dtype: numpy in, numpy out; a CUDA tensor in, a tensor out."""
+    import torch
+    as_tensor = isinstance(means, torch.Tensor)
+    if not as_tensor:
+        means, variances = np.asarray(means), np.asarray(variances)
+    D = _check_mlpg_args(means, variances, windows, True)
+    if lengths is not None and len(lengths) != means.shape[0]:
+        raise ValueError("mlpg: lengths has %d entries for a batch of %d sequences" % (len(lengths), means.shape[0]))
+    eng = _var_engine(D, windows)
+    if as_tensor:
+        y = means.detach().to(device="cuda", dtype=torch.float32)
+        v = torch.as_tensor(variances).detach().to(device="cuda", dtype=torch.float32)
+    else:
+        y = torch.from_numpy(np.ascontiguousarray(means, dtype=np.float32)).cuda()
+        v = torch.from_numpy(np.ascontiguousarray(variances, dtype=np.float32)).cuda()
+    out = eng.mlpg_var(y, v, lengths=lengths, windows=windows)
+    return out.to(means.dtype) if as_tensor else out.cpu().numpy().astype(means.dtype, copy=False)
+
+
+def mlpg(mean_frames, variance_frames, windows):
+    """``nnmnkwii.paramgen.mlpg``: for every static dimension the c that solves
+    ``(sum_w W_w^T diag(1 / var_w) W_w) c = sum_w W_w^T (mean_w / var_w)``, on the device in float64 (rounded to float32 once).
+    ``mean_frames`` (T, D) with the static and dynamic features window-major; ``variance_frames`` (D,) or (T, D); returns
+    (T, D // len(windows)) in the input's dtype: numpy in, numpy out; a CUDA tensor in, a tensor out.  ValueError for shapes that do
+    not fit and for variances that are not finite and positive; RuntimeError without a GPU."""
+    import torch
+    as_tensor = isinstance(mean_frames, torch.Tensor)
+    if not as_tensor:
+        mean_frames, variance_frames = np.asarray(mean_frames), np.asarray(variance_frames)
+    _check_mlpg_args(mean_frames, variance_frames, windows, False)
+    var = variance_frames if len(variance_frames.shape) == 1 else variance_frames[None]
+    return mlpg_batch(mean_frames[None], var, windows)[0]

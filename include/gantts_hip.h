@@ -935,6 +935,44 @@ int gt_op_mlpg(const gt_mlpg_case* c, void* stream);
  * Synchronises the stream. */
 int gt_op_mlpg_band(gt_engine* e, const float* R, int T, float* band_host, int64_t capacity, int32_t* kb, void* stream);
 
+/* Variance-weighted MLPG: nnmnkwii.paramgen.mlpg(mean_frames, variance_frames, windows) for a batch, on the device.  For every sequence b
+ * and static column c it solves, in float64 and over the sequence's OWN length len_b,
+ *     (sum_w W_w^T diag(1 / var_w) W_w) x = sum_w W_w^T (y_w / var_w)
+ * with the windows registered through gt_set_mlpg_windows, (W_w x)[t] = sum_k coef_w[k + l_w] x[t + k] (terms outside [0, len_b) dropped),
+ * y_w[t] = y[b*T + t][scol[c] + w * sstride[c]] and var_w likewise: one thread per (b, c), a banded Cholesky with the forward substitution
+ * riding along, the back substitution, the result rounded to float32 once (gantts_amd/csrc/mlpg_var_kernels.hip.h).
+ *   e        the engine: num_windows, the registered windows, the scratch (8 (hb + 2) T Ds bytes per sequence, hb = max_w (l_w + u_w))
+ *   y        device [B*T][ldy]: the means, static and dynamic features in the full layout
+ *   var      device: [B*T][ldv] per frame, or ONE row of the full layout when ldv == 0 (time-invariant: the data variance of gen_parameters)
+ *   ys       device [B*T][ldys], columns [0, Ds) written: the solution for t < len_b, 0 for t >= len_b; a pass-through column
+ *            (sstride[c] == 0) is y's column scol[c] copied for t < len_b
+ *   scol, sstride   device int32 [Ds] as in gt_mlpg_case; both null: the engine's own maps (Ds is then the engine's, 0 accepted)
+ *   lengths  host, B entries in [1, T]; null: all T
+ *   max_ws_bytes    cap of the scratch of one group of whole sequences the batch is walked in; 0: 64 MB.  A cap below one sequence's
+ *            scratch is refused.  The result does not depend on the grouping.
+ * Malformed cases -- no registered windows, a null pointer, T < 1, a length outside [1, T], a pitch below the columns the maps address --
+ * return GT_ERR_INVALID before any launch.  A variance that is not a finite positive number (or a pivot that is not) returns GT_ERR_INVALID
+ * ("variances must be finite and positive") AFTER the launch: nothing in ys is to be trusted then; the engine serves the next call.
+ * Synchronises the stream: the refusal flag is read. */
+typedef struct gt_mlpg_var_case {
+  gt_engine* e;
+  int32_t B, T, Ds;
+  int32_t ldy, ldv, ldys;
+  const int32_t* scol;
+  const int32_t* sstride;
+  const int64_t* lengths;
+  const float* y;
+  const float* var;
+  float* ys;
+  int64_t max_ws_bytes;
+} gt_mlpg_var_case;
+int gt_op_mlpg_var(const gt_mlpg_var_case* c, void* stream);
+/* Launches of the variance-weighted solve by kernel, process-wide, counted on the host where each launch is issued (one per group of
+ * sequences): 0 mlpg_var_solve_kernel<1>, 1 mlpg_var_solve_kernel<2>, 2 mlpg_var_generic_kernel.  Copies the first min(n,
+ * GT_MLPG_VAR_PATH_SLOTS) counts to `counts`; counts == NULL zeroes them instead. */
+#define GT_MLPG_VAR_PATH_SLOTS 3
+int gt_mlpg_var_path_counts(int64_t* counts, int n);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the
