@@ -1,4 +1,4 @@
-// libgantts_hip.so -- stand-alone operators of the C ABI (gt_op_*, gt_compute_distortions)
+// libgantts_hip.so -- stand-alone operators of the C ABI (gt_op_* but the MLPG hooks of eng_mlpg.hip, gt_compute_distortions)
 #include "engine_internal.hip.h"
 #include "optim_kernels.hip.h"
 #include "d_tail_args.hip.h"
@@ -107,140 +107,6 @@ extern "C" int gt_op_gather_cols(const float* in, int ld_in, const int32_t* idx,
                      ld_out, out_col_offset, (int)rows, n_idx);
   LAUNCH_CHECK();
   return GT_OK;
-}
-
-extern "C" int gt_op_mlpg_forward(gt_engine* e, const float* y, const float* R, int B, int T, float* y_static, void* stream) {
-  CHK(check_common(e, B, T));
-  if (!y || !R || !y_static) return fail(GT_ERR_INVALID, "null tensor");
-  hipStream_t s = (hipStream_t)stream;
-  CHK(ensure_band(e, R, T, s));
-  return mlpg_forward(e, y, e->Dout_cfg, e->d_scol, e->d_sstride, e->Ds, y_static, e->Ds, B, T, s);
-}
-extern "C" int gt_op_mlpg_backward(gt_engine* e, const float* g_static, const float* R, int B, int T, float* g_y, void* stream) {
-  CHK(check_common(e, B, T));
-  if (!g_static || !R || !g_y) return fail(GT_ERR_INVALID, "null tensor");
-  hipStream_t s = (hipStream_t)stream;
-  CHK(ensure_band(e, R, T, s));
-  return mlpg_backward(e, g_static, e->Ds, e->d_scol, e->d_sstride, e->Ds, g_y, e->Dout_cfg, B, T, 0.f, nullptr, nullptr, 0, nullptr, s);
-}
-
-// One MLPG launch with the step's freedom in the arguments (column maps, pitches, the fused masked-MSE gradient) through ensure_band and
-// mlpg_forward / mlpg_backward: parity hook of tests/test_gpu_mlpg.py.  Everything a kernel would index with is checked first.
-static_assert(offsetof(gt_mlpg_case, e) == 40 && offsetof(gt_mlpg_case, kb) == 128 && sizeof(gt_mlpg_case) == 136, "layout bound by gantts_amd/_lib.py");
-extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
-  if (!c) return fail(GT_ERR_INVALID, "null case");
-  gt_engine* e = c->e;
-  CHK(check_common(e, c->B, c->T));
-  const bool bwd = c->backward != 0, own = !c->scol && !c->sstride, mse = bwd && c->mse_w != 0.f;
-  if (c->backward != 0 && c->backward != 1) return fail(GT_ERR_INVALID, "MLPG hook: backward is 0 or 1");
-  if (!c->R) return fail(GT_ERR_INVALID, "MLPG hook: null R");
-  if (!own && (!c->scol || !c->sstride)) return fail(GT_ERR_INVALID, "MLPG hook: scol and sstride come together");
-  if (own && c->Ds != 0 && c->Ds != e->Ds) return fail(GT_ERR_INVALID, "MLPG hook: Ds = %d with the engine's maps (%d)", c->Ds, e->Ds);
-  const int Ds = own ? e->Ds : c->Ds;
-  if (Ds < 1 || Ds > (1 << 20)) return fail(GT_ERR_INVALID, "MLPG hook: Ds = %d", Ds);
-  if (bwd ? (!c->gs || !c->gy) : (!c->y || !c->ys)) return fail(GT_ERR_INVALID, "MLPG hook: null tensor");
-  if (mse && (!c->yhat || !c->ytgt || !c->mask)) return fail(GT_ERR_INVALID, "MLPG hook: the masked-MSE gradient needs yhat, ytgt and mask");
-  const bool built = c->R == GT_MLPG_R_FROM_WINDOWS;      // the sentinel is no address: ensure_band never dereferences it
-  for (const void* q : {built ? nullptr : (const void*)c->R, (const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->ys, (const void*)c->gs,
-                        (const void*)c->gy, (const void*)c->yhat, (const void*)c->ytgt, (const void*)c->mask})
-    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "MLPG hook: misaligned operand");
-  if (bwd ? c->ldgs < Ds : c->ldys < Ds) return fail(GT_ERR_INVALID, "MLPG hook: pitch of the static side below Ds = %d", Ds);
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<int> h_scol, h_sstride;
-  if (own) { h_scol = e->h_scol; h_sstride = e->h_sstride; }
-  else {
-    h_scol.resize(Ds); h_sstride.resize(Ds);
-    HIPCHK(hipMemcpyAsync(h_scol.data(), c->scol, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_sstride.data(), c->sstride, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  const int nW = e->cfg.num_windows;
-  const long ld_full = bwd ? c->ldgy : c->ldy;
-  for (int i = 0; i < Ds; ++i) {
-    const long col = h_scol[i], st = h_sstride[i];
-    if (col < 0 || st < 0) return fail(GT_ERR_INVALID, "MLPG hook: negative entry in the column maps at %d", i);
-    const long last = col + (long)(nW - 1) * st;      // pass-through (st == 0): its own column only
-    if (last >= ld_full) return fail(GT_ERR_INVALID, "MLPG hook: static column %d reaches column %ld, the pitch is %ld", i, last, ld_full);
-    if (mse && last >= c->ldt) return fail(GT_ERR_INVALID, "MLPG hook: static column %d reaches column %ld, ldt is %d", i, last, c->ldt);
-  }
-  CHK(ensure_band(e, c->R, c->T, s));
-  if (c->kb) *c->kb = e->mlpg.cur->kb;
-  const int* scol = own ? e->d_scol : (const int*)c->scol;
-  const int* sstride = own ? e->d_sstride : (const int*)c->sstride;
-  int r;
-  if (!bwd) {
-    r = mlpg_forward(e, c->y, c->ldy, scol, sstride, Ds, c->ys, c->ldys, c->B, c->T, s);
-  } else {
-    if (mse) {      // sum(mask) and its reciprocal, as ensure_tv puts them there; the step's memo of it no longer holds
-      launch_mask_sum(c->mask, (long)c->B * c->T, -1.f, nullptr, e->sc(), s);
-      LAUNCH_CHECK();
-      e->tv.forget();
-    }
-    r = mlpg_backward(e, c->gs, c->ldgs, scol, sstride, Ds, c->gy, c->ldgy, c->B, c->T, mse ? c->mse_w : 0.f, mse ? c->yhat : nullptr,
-                      mse ? c->ytgt : nullptr, mse ? c->ldt : 0, mse ? c->mask : nullptr, s);
-  }
-  const hipError_t err = hipStreamSynchronize(s);
-  if (r) return r;
-  if (err != hipSuccess) return fail(GT_ERR_HIP, "mlpg: %s", hipGetErrorString(err));
-  return GT_OK;
-}
-
-extern "C" int gt_op_mlpg_band(gt_engine* e, const float* R, int T, float* band_host, int64_t capacity, int32_t* kb, void* stream) {
-  CHK(check_common(e, 1, T));
-  if (!R) return fail(GT_ERR_INVALID, "MLPG band hook: null R");
-  if (R != GT_MLPG_R_FROM_WINDOWS && (((uintptr_t)R) & 3)) return fail(GT_ERR_INVALID, "MLPG band hook: misaligned R");
-  hipStream_t s = (hipStream_t)stream;
-  CHK(ensure_band(e, R, T, s));
-  const MlpgBand* b = e->mlpg.cur;
-  if (kb) *kb = b->kb;
-  const int64_t need = (int64_t)T * e->cfg.num_windows * (2 * b->kb + 1);
-  if (!band_host || capacity < need) return fail(GT_ERR_INVALID, "MLPG band hook: the band has %ld floats, band_host holds %ld", (long)need, (long)capacity);
-  HIPCHK(hipMemcpyAsync(band_host, b->band.p, (size_t)need * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return GT_OK;
-}
-
-// nnmnkwii.paramgen.mlpg for a batch (launch_mlpg_var, eng_step.hip).  Everything a kernel would index with is checked first.
-static_assert(offsetof(gt_mlpg_var_case, B) == 8 && offsetof(gt_mlpg_var_case, scol) == 32 && offsetof(gt_mlpg_var_case, max_ws_bytes) == 80 &&
-              sizeof(gt_mlpg_var_case) == 88, "layout bound by gantts_amd/_lib.py");
-extern "C" int gt_op_mlpg_var(const gt_mlpg_var_case* c, void* stream) {
-  if (!c) return fail(GT_ERR_INVALID, "null case");
-  gt_engine* e = c->e;
-  CHK(check_common(e, c->B, c->T));
-  if (!e->mlpg.has_win) return fail(GT_ERR_INVALID, "variance-weighted MLPG without a window set: call gt_set_mlpg_windows first");
-  const bool own = !c->scol && !c->sstride;
-  if (!own && (!c->scol || !c->sstride)) return fail(GT_ERR_INVALID, "variance-weighted MLPG: scol and sstride come together");
-  if (own && c->Ds != 0 && c->Ds != e->Ds) return fail(GT_ERR_INVALID, "variance-weighted MLPG: Ds = %d with the engine's maps (%d)", c->Ds, e->Ds);
-  const int Ds = own ? e->Ds : c->Ds;
-  if (Ds < 1 || Ds > (1 << 20)) return fail(GT_ERR_INVALID, "variance-weighted MLPG: Ds = %d", Ds);
-  if (!c->y || !c->var || !c->ys) return fail(GT_ERR_INVALID, "variance-weighted MLPG: null tensor");
-  for (const void* q : {(const void*)c->scol, (const void*)c->sstride, (const void*)c->y, (const void*)c->var, (const void*)c->ys})
-    if (((uintptr_t)q) & 3) return fail(GT_ERR_INVALID, "variance-weighted MLPG: misaligned operand");
-  if (c->max_ws_bytes < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: negative max_ws_bytes");
-  if (c->ldys < Ds) return fail(GT_ERR_INVALID, "variance-weighted MLPG: pitch of the static side below Ds = %d", Ds);
-  if (c->ldy < 1 || c->ldv < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: ldy = %d, ldv = %d", c->ldy, c->ldv);
-  if (c->lengths)
-    for (int b = 0; b < c->B; ++b)
-      if (c->lengths[b] < 1 || c->lengths[b] > c->T) return fail(GT_ERR_INVALID, "variance-weighted MLPG: length %lld outside [1, T=%d]", (long long)c->lengths[b], c->T);
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<int> h_scol, h_sstride;
-  if (own) { h_scol = e->h_scol; h_sstride = e->h_sstride; }
-  else {
-    h_scol.resize(Ds); h_sstride.resize(Ds);
-    HIPCHK(hipMemcpyAsync(h_scol.data(), c->scol, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_sstride.data(), c->sstride, (size_t)Ds * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  }
-  const int nW = e->cfg.num_windows;
-  for (int i = 0; i < Ds; ++i) {
-    const long col = h_scol[i], st = h_sstride[i];
-    if (col < 0 || st < 0) return fail(GT_ERR_INVALID, "variance-weighted MLPG: negative entry in the column maps at %d", i);
-    const long last = col + (long)(nW - 1) * st;      // pass-through (st == 0): its own column only
-    if (last >= c->ldy) return fail(GT_ERR_INVALID, "variance-weighted MLPG: static column %d reaches column %ld, ldy is %d", i, last, c->ldy);
-    if (c->ldv && st && last >= c->ldv) return fail(GT_ERR_INVALID, "variance-weighted MLPG: static column %d reaches column %ld, ldv is %d", i, last, c->ldv);
-  }
-  return launch_mlpg_var(e, c->y, c->ldy, c->var, c->ldv, own ? e->d_scol : (const int*)c->scol, own ? e->d_sstride : (const int*)c->sstride, Ds,
-                         c->ys, c->ldys, c->lengths, c->B, c->T, c->max_ws_bytes, s);
 }
 
 static DropoutSpec buffer_spec(const float* keep_mask, float p, int ld) {

@@ -236,13 +236,12 @@ struct MlpgWindows {
 struct MlpgCache {
   static constexpr size_t MAX_ENTRIES = 256;
   std::vector<MlpgBand*> entries;
-  MlpgBand* cur = nullptr;
   uint64_t tick = 0;
   Scratch tmp;                      // per-offset maxima of a new R (persistent: no hipFree on the step path)
   bool has_win = false;
   MlpgWindows win;                  // zero-filled beyond the registered windows and coefficients: compared with memcmp
   Scratch fac, wide;                // device build: Cholesky factor and selected inverse (float64), the taps at the candidate width
-  void clear() { for (auto* b : entries) { b->band.release(); delete b; } entries.clear(); cur = nullptr; }
+  void clear() { for (auto* b : entries) { b->band.release(); delete b; } entries.clear(); }
 };
 
 struct gt_engine {
@@ -270,6 +269,7 @@ struct gt_engine {
   int B = 0, T = 0; long N = 0;
   const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;
   bool g_pass_valid = false, leak_pending = false;
+  const MlpgBand* g_band = nullptr;        // the band the stashed generator pass went through (null: R is None); the cache never recycles it while g_pass_valid
   // "the generated half of this image of D's input is built", and from which x / y_hat_static: the generator step's adversarial term
   // reuses what the D step of the same batch left behind.  One record per image kind; all dropped by invalidate_d_images().
   struct DImage {
@@ -278,7 +278,7 @@ struct gt_engine {
     void built(const float* x_, const float* yhs_) { valid = true; x = x_; yhs = yhs_; }
   };
   DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
-  bool d_begin_done = false, g_begin_done = false, g_has_adv = false, g_used_mlpg = false;
+  bool d_begin_done = false, g_begin_done = false, g_has_adv = false;
   struct TvMemo {      // sum(mask) is already on the device for this step: of which mask, over how many frames, under which override
     const float* mask = nullptr; long n = 0; float ovr = 0.f;
     bool known(const float* m, long N, float o) const { return mask == m && n == N && ovr == o; }
@@ -455,17 +455,17 @@ int catdrop_cast_transpose(const gt::CatDropSrc& src, long rows, int cols, __bf1
 int weight_grad_b16(const __bf16* dZT, long lddzt, const __bf16* XT, long ldxt, long rows, int out, int in, float* dW, float* db,
                     bool accumulate, Scratch& slabs, hipStream_t s, SlabDefer* defer = nullptr);
 
+// eng_mlpg.hip: a launch takes the band it goes through, as ensure_band handed it back
+int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBand** out);
+int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const int* sstride, int Ds,
+                 float* ys, int ldys, int B, int T, const MlpgBand& band, hipStream_t s);
+int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, const int* sstride, int Ds,
+                  float* gy, int ldgy, int B, int T, float mse_w, const float* yhat, const float* ytgt, int ldt,
+                  const float* mask, const MlpgBand& band, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------
 // eng_step.hip
 // ------------------------------------------------------------------------------------------
-int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s);
-int mlpg_forward(gt_engine* e, const float* y, int ldy, const int* scol, const int* sstride, int Ds,
-                 float* ys, int ldys, int B, int T, hipStream_t s);
-int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, const int* sstride, int Ds,
-                  float* gy, int ldgy, int B, int T, float mse_w, const float* yhat, const float* ytgt, int ldt,
-                  const float* mask, hipStream_t s);
-int launch_mlpg_var(gt_engine* e, const float* y, int ldy, const float* var, int ldv, const int* scol, const int* sstride, int Ds, float* ys, int ldys,
-                    const int64_t* lengths, int B, int T, int64_t max_ws_bytes, hipStream_t s);      // eng_step.hip; synchronises s
 int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket = 0);
 int cond_dim(gt_engine* e);
 

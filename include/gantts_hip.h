@@ -228,7 +228,8 @@ int gt_op_philox_mask(gt_engine* e, int role, int pass, int layer, int64_t steps
 int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, void* stream);
 /* The engine keeps a banded image of every MLPG matrix R it has been given, keyed by (R pointer, T) (the reference
  * rebuilds and uploads R every batch, train.py:511-513; callers of this library keep one device R per padded length).
- * R must not be rewritten in place or freed-and-reused while cached: call this first (drops all cached bands). */
+ * R must not be rewritten in place or freed-and-reused while cached: call this first (drops all cached bands).  A stashed generator
+ * pass that used a dropped band can no longer be back-propagated: the next step starts with gt_apply_generator. */
 int gt_invalidate_mlpg_cache(gt_engine* e);
 /* The MLPG band built on the device from the window set, without a dense R.  Register the windows once: window w is
  * (l[w], u[w], its l[w] + u[w] + 1 coefficients), (W_w x)[t] = sum_k coef_w[k + l[w]] x[t + k], the coefficients of all windows one

@@ -1,5 +1,5 @@
-"""Banded MLPG (mlpg_forward_kernel / mlpg_backward_kernel, gantts_amd/csrc/frame_kernels.hip.h) against float64, every instantiation,
-and the band cache (ensure_band, eng_step.hip).
+"""Banded MLPG (mlpg_forward_kernel / mlpg_backward_kernel, gantts_amd/csrc/mlpg_kernels.hip.h) against float64, every instantiation,
+and the band cache (ensure_band, eng_mlpg.hip).
 
 gt_op_mlpg runs ONE launch through ensure_band and mlpg_forward / mlpg_backward, the functions the step calls, with the step's freedom in
 the arguments (column maps, pitches, the fused masked-MSE gradient).  Two judges:
@@ -12,7 +12,7 @@ the arguments (column maps, pitches, the fused masked-MSE gradient).  Two judges
             length of the longest fma chain (the textbook bound of a sequential fma sum; the second term is what ensure_band's own rule
             allows the band to leave out).  No element may exceed it.
 
-Half-widths, LDS sizes and tile constants are computed here from the same rules and from the kernels' header, never copied.
+Half-widths, LDS sizes and tile constants are computed here from the same rules and from the MLPG_* constants of frame_kernels.hip.h, never copied.
 The CPU self-check at the end runs a numpy model of the tiled kernels through both judges, and six mutations of it that must be caught.
 """
 import ctypes as Ct

@@ -1,4 +1,4 @@
-"""The MLPG band built on the device from the windows (gantts_amd/csrc/mlpg_band_kernels.hip.h, ensure_band's GT_MLPG_R_FROM_WINDOWS path)
+"""The MLPG band built on the device from the windows (gantts_amd/csrc/mlpg_band_kernels.hip.h, the GT_MLPG_R_FROM_WINDOWS path of ensure_band in eng_mlpg.hip)
 against the committed host path paramgen.unit_variance_mlpg_matrix, the reference of every check here.
 
   taps        band read back through gt_op_mlpg_band: every tap  |dev - host| <= 2^-24 |host| + 2^-40 peak  (one float32 rounding, and
