@@ -276,11 +276,10 @@ int comm_finish_step(gt_engine* e, int role, bool grads, double* sums, int n_sum
 int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float adv_w, float mse_w, float mge_w, hipStream_t compute) {
   GtComm* c = e->comm;
   CHK(comm_allreduce_after(e, sums, (size_t)n_sums, GT_NCCL_DOUBLE, compute));
-  StepResults* target = e->h_res_dev ? e->h_res_dev : e->res();     // see post_early_results
-  if (role == GT_ROLE_D) launch_finalize_d(e->sc(), target, 1, e->d_unnorm ? 1 : 0, c->stream);
-  else launch_finalize_g(e->sc(), target, adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, nullptr, 0, nullptr, 0, c->stream);
+  if (role == GT_ROLE_D) launch_finalize_d(e->sc(), e->results.target(), 1, e->d_unnorm ? 1 : 0, c->stream);
+  else launch_finalize_g(e->sc(), e->results.target(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, nullptr, 0, nullptr, 0, c->stream);
   LAUNCH_CHECK();
-  return post_early_results(e, c->stream);
+  return e->results.post_early(c->stream);
 }
 
 // tv = sum(mask) (or the data-parallel override) -> device scalars; once per (step, mask).  With a communicator the

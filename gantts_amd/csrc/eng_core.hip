@@ -126,11 +126,7 @@ extern "C" int gt_engine_create(const gt_stream_config* cfg, gt_engine** out) {
       (r = upload_ints(e->h_adv_cols, &e->d_adv_cols)) || (r = upload_ints(e->h_adv_inv, &e->d_adv_inv))) { delete e; return r; }
   if ((r = e->scal.ensure(1024))) { delete e; return r; }
   if (hipMemset(e->scal.p, 0, 1024) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipMemset failed"); }
-  static_assert(sizeof(StepResults) <= 64, "the result ticket sits 64 bytes behind the results");
-  if (hipHostMalloc((void**)&e->h_res, 128) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipHostMalloc failed"); }
-  memset(e->h_res, 0, 128);
-  if (hipHostGetDevicePointer((void**)&e->h_res_dev, e->h_res, 0) != hipSuccess) { (void)hipGetLastError(); e->h_res_dev = nullptr; }
-  if (!env_flag("GT_RES_HOSTMAP", true)) e->h_res_dev = nullptr;      // (measurement: results through a device -> host copy instead)
+  if ((r = e->results.create(e->res(), &e->opt_poll_results))) { delete e; return r; }
   if (hipMalloc((void**)&e->d_fault, 64) != hipSuccess || hipMemset(e->d_fault, 0, 64) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipMalloc failed"); }
   if (hipHostMalloc((void**)&e->h_fault, 64) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipHostMalloc failed"); }
   for (int i = 0; i < 16; ++i) e->h_fault[i] = 0;   // [0] copy of the device word, [1] its mirror by the optimizer kernel, [2 + role] skipped steps
@@ -160,9 +156,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   e->mlpg.clear();
   int* ints[] = {e->d_scol, e->d_sstride, e->d_adv_cols, e->d_adv_inv, e->d_scol_i2o, e->d_sstride_i2o};
   for (int* p : ints) if (p) (void)hipFree(p);
-  if (e->h_res) (void)hipHostFree(e->h_res);
-  if (e->ev_res) (void)hipEventDestroy(e->ev_res);
-  for (int r = 0; r < 2; ++r) { if (e->h_def[r]) (void)hipHostFree(e->h_def[r]); if (e->ev_def[r]) (void)hipEventDestroy(e->ev_def[r]); }
+  e->results.destroy();
   delete e;
 }
 
@@ -366,15 +360,14 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       // instead of back-propagating through buffers the forward never filled
       if (e->matmul_bf16 != (value != 0)) {
         invalidate_d_images(e);
-        e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget();
-        e->d_begin_done = false; e->g_begin_done = false;
+        e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget(); e->results.forget_begin();
       }
       e->matmul_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_SRU_D_BF16:
       if (value != 0 && value != 1) return fail(GT_ERR_INVALID, "GT_OPT_SRU_D_BF16 takes 0 or 1, not %d", value);
       // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
-      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak_pending = false; e->d_begin_done = false; e->g_begin_done = false; }
+      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak_pending = false; e->results.forget_begin(); }
       e->sru_d_bf16 = value != 0;
       return GT_OK;
   }
@@ -575,8 +568,7 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   invalidate_d_images(e);
-  e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget();
-  e->d_begin_done = e->g_begin_done = false; e->early_done = false;
+  e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget(); e->results.reset();
   return GT_OK;
 }
 extern "C" int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset) {

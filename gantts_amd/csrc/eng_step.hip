@@ -510,7 +510,7 @@ static int head_sums(gt_engine* e, int nblk, int K, bool dw, HeadSums* o) {
   o->hp = e->headp.as<HeadPartials>(); o->hp_cap = (long)(e->headp.bytes / sizeof(HeadPartials));
   o->dw_partial = e->headw.as<float>(); o->dw_cap = (long)(e->headw.bytes / sizeof(float));
   o->dW = D.last.dW; o->db = D.last.db; o->accumulate = D.grads_dirty ? 1 : 0;
-  o->ticket_dev = e->ticket_dev();
+  o->ticket_dev = e->results.ticket_dev();
   return GT_OK;
 }
 
@@ -591,6 +591,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   const float* gscale = (role == GT_ROLE_D && e->d_unnorm) ? &e->sc()->inv_tv : (const float*)nullptr;
   if (role == GT_ROLE_D) e->d_unnorm = false;
   SlabDefer& sd = e->ws[role].sdefer;
+  int n_partial = 0;      // squared-norm partials in `part`: none until one of the two routes below has launched them
   if (sd.active && sd.jobs.n > 0) {
     // The fused step recorded this network's weight-gradient combines.  They write disjoint ranges of the flat gradient; whatever
     // they do not cover (the discriminator's last layer, written by the head's reduction) still counts for the norm and is
@@ -626,52 +627,47 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
     if (ok && sd.blocks + rest_blocks <= 2048) {
       hipLaunchKernelGGL(slab_reduce_norm_kernel, dim3(sd.blocks + rest_blocks), dim3(256), 0, s, sd.jobs, sd.blocks, rest, n.d.grads, part);
       LAUNCH_CHECK();
-      const int n_partial = sd.blocks + rest_blocks;
+      n_partial = sd.blocks + rest_blocks;
       sd.reset(false);
-      n.step += 1;
-      CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
-                            (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
-      n.buf_live = true;
-      return GT_OK;
     }
   }
-  const int nblk = (int)std::min<long>(512, cdiv(np, RED_THREADS * 4));
-  CHK(slab_defer_flush(sd, s));            // the fused step's recorded weight-gradient combines, one launch
-  sd.active = false;
-  hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nblk), dim3(RED_THREADS), 0, s, n.d.grads, np, part);
-  LAUNCH_CHECK();
+  if (!n_partial) {
+    n_partial = (int)std::min<long>(512, cdiv(np, RED_THREADS * 4));
+    CHK(slab_defer_flush(sd, s));            // the fused step's recorded weight-gradient combines, one launch
+    sd.active = false;
+    hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(n_partial), dim3(RED_THREADS), 0, s, n.d.grads, np, part);
+    LAUNCH_CHECK();
+  }
   n.step += 1;
-  CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, nblk, norm2_out,
+  CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
                         (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
   n.buf_live = true;
   return GT_OK;
 }
 
-static int fetch_results(gt_engine* e, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(e->h_res, e->res(), sizeof(StepResults), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+// ResultsChannel (engine_internal.hip.h): how a step's scalars reach the host
+int ResultsChannel::create(StepResults* device_results, const bool* poll_option) {
+  static_assert(sizeof(StepResults) <= 64, "the result ticket sits 64 bytes behind the results");
+  d_res = device_results; poll = poll_option;
+  if (hipHostMalloc((void**)&h_res, 128) != hipSuccess) return fail(GT_ERR_HIP, "hipHostMalloc failed");
+  memset(h_res, 0, 128);
+  if (hipHostGetDevicePointer((void**)&h_res_dev, h_res, 0) != hipSuccess) { (void)hipGetLastError(); h_res_dev = nullptr; }
+  if (!env_flag("GT_RES_HOSTMAP", true)) h_res_dev = nullptr;      // (measurement: results through a device -> host copy instead)
   return GT_OK;
 }
-static int post_deferred_results(gt_engine* e, int role, hipStream_t s) {
-  if (!e->h_def[role]) HIPCHK(hipHostMalloc((void**)&e->h_def[role], sizeof(StepResults)));
-  if (!e->ev_def[role]) HIPCHK(hipEventCreateWithFlags(&e->ev_def[role], hipEventDisableTiming));
-  HIPCHK(hipMemcpyAsync(e->h_def[role], e->res(), sizeof(StepResults), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(e->ev_def[role], s));
-  e->def_pending[role] = true;
+int ResultsChannel::post_deferred(int role, hipStream_t s) {
+  if (!h_def[role]) HIPCHK(hipHostMalloc((void**)&h_def[role], sizeof(StepResults)));
+  if (!ev_def[role]) HIPCHK(hipEventCreateWithFlags(&ev_def[role], hipEventDisableTiming));
+  HIPCHK(hipMemcpyAsync(h_def[role], d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(ev_def[role], s));
+  def_pending[role] = true;
   return GT_OK;
 }
-static StepResults* early_res_target(gt_engine* e) { return e->h_res_dev ? e->h_res_dev : e->res(); }
-// a ticket for results that the NEXT finalising launch writes into the host page (0: not available -- the event is used)
-static unsigned take_ticket(gt_engine* e) {
-  if (!e->opt_poll_results || !e->h_res_dev) return 0;
-  if (++e->ticket_next == 0) ++e->ticket_next;
-  return e->ticket_next;
-}
-static int wait_early_results(gt_engine* e) {
-  if (e->ticket_wait) {
-    volatile unsigned* t = e->ticket_host();
-    const unsigned want = e->ticket_wait;
-    e->ticket_wait = 0;
+int ResultsChannel::wait_early() {
+  if (ticket_wait) {
+    volatile unsigned* t = ticket_host();
+    const unsigned want = ticket_wait;
+    ticket_wait = 0;
     unsigned long spins = 0;
     std::chrono::steady_clock::time_point t0;
     while (__atomic_load_n((const unsigned*)t, __ATOMIC_ACQUIRE) != want) {
@@ -684,18 +680,18 @@ static int wait_early_results(gt_engine* e) {
         }
       }
     }
-    return GT_OK;
-  }
-  HIPCHK(hipEventSynchronize(e->ev_res));
+  } else HIPCHK(hipEventSynchronize(ev_res));
+  early_done = false;
   return GT_OK;
 }
-int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket) {
-  if (ticket) { e->ticket_wait = ticket; e->early_done = true; return GT_OK; }
-  e->ticket_wait = 0;
-  if (!e->ev_res) HIPCHK(hipEventCreateWithFlags(&e->ev_res, hipEventDisableTiming));
-  if (!e->h_res_dev) HIPCHK(hipMemcpyAsync(e->h_res, e->res(), sizeof(StepResults), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(e->ev_res, s));
-  e->early_done = true;
+int ResultsChannel::post_early(hipStream_t s, unsigned ticket) {
+  ticket_wait = ticket;
+  if (!ticket) {
+    if (!ev_res) HIPCHK(hipEventCreateWithFlags(&ev_res, hipEventDisableTiming));
+    if (!h_res_dev) HIPCHK(hipMemcpyAsync(h_res, d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(ev_res, s));
+  }
+  early_done = true;
   return GT_OK;
 }
 
@@ -907,22 +903,23 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
   const bool tr = train != 0;
+  ResultsChannel& rc = e->results;
+  // fused call: losses and counts are final after the head (the gradient norm is not: reported as 0), so the head's
+  // reduction kernel also writes the result struct and the scalars start their way to the host right behind it
+  const bool plain_early = rc.early && !comm_on(e), comm_early = rc.early && comm_on(e);
   DPass p;
   CHK(d_pass_plan(e, x, y_static, y_hat_static, e->Ds, 2, B, T, tr, &p));
   if (comm_on(e) && tr && D.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_d.zero_grad() must precede update_discriminator (the gradient buckets are summed over the ranks in place)");
-  e->ws[GT_ROLE_D].sdefer.reset(e->early && tr && D.has_opt);
+  e->ws[GT_ROLE_D].sdefer.reset(rc.early && tr && D.has_opt);
   // data parallel: the global count travels under the D forward pass.  With the split first layer its local term is summed by a
   // rider of the gather launch (tv_ride_dp), else by a launch of its own right here.
   const bool tv_known = e->tv.known(mask, N, e->tv_override);
-  const bool dp_count = e->early && e->opt_launch_riders && comm_on(e) && !tv_known && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight;
+  const bool dp_count = comm_early && e->opt_launch_riders && !tv_known && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight;
   // GT_OPT_COMM_TV_IN_SUMS: no collective for the count at all -- it leaves with the loss sums (engine_internal.hip.h)
   const bool unnorm = dp_count && e->opt_comm_tv_in_sums && tr && D.has_opt && D.d.grads;
   e->d_unnorm = unnorm;
-  AdvRiders ride;
-  ride.mask = mask; ride.unnorm = unnorm;
-  ride.tv_ride_dp = dp_count && !unnorm && p.split;
-  ride.tv_ride = e->early && e->opt_launch_riders && !comm_on(e) && !tv_known;      // fused single-GPU call: the count is not known yet
+  const AdvRiders ride = {mask, /* tv_ride */ plain_early && e->opt_launch_riders && !tv_known, /* tv_ride_dp */ dp_count && !unnorm && p.split, unnorm};
   if (!ride.tv_ride_dp && !unnorm) CHK(ensure_tv_begin(e, mask, N, s));
   if (unnorm && !p.split) {
     launch_mask_total(mask, N, &e->sc()->tv_sum, s);
@@ -931,14 +928,10 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   CHK(d_pass_input(e, p, ride, s));
   CHK(d_pass_forward(e, p, s));
   if (tr && !D.d.grads) return fail(GT_ERR_STATE, "phase == \"train\" but the discriminator was bound without grads");
-  // fused call: losses and counts are final after the head (the gradient norm is not: reported as 0), so the head's
-  // reduction kernel also writes the result struct and the scalars start their way to the host right behind it
-  const bool plain_early = e->early && !comm_on(e), comm_early = e->early && comm_on(e);
   HeadCall hc;
   memset(&hc, 0, sizeof(hc));
   hc.mode = HEAD_D_STEP; hc.rows = p.rows; hc.n_real = N; hc.mask = mask; hc.n_mask = N; hc.eps = eps; hc.want_grad = tr; hc.want_w = tr;
-  hc.early_res = plain_early ? early_res_target(e) : nullptr;
-  hc.ticket = plain_early ? take_ticket(e) : 0;
+  if (plain_early) { hc.early_res = rc.target(); hc.ticket = rc.take_ticket(); }
   hc.unit_tv = unnorm;
   if (unnorm) {      // the normaliser arrives with the sums (finalize_d_kernel on the communicator's stream files it); valid from the join on
     e->tv.note(mask, N, e->tv_override);
@@ -950,8 +943,8 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     e->tv.note(mask, N, e->tv_override);
   } else CHK(ensure_tv(e, mask, N, s));
   CHK(d_pass_head(e, p, hc, nullptr, s));
-  e->early_done = false;
-  if (plain_early) CHK(post_early_results(e, s, hc.ticket));
+  rc.clear_early();
+  if (plain_early) CHK(rc.post_early(s, hc.ticket));
   if (comm_early) CHK(comm_early_results(e, GT_ROLE_D, unnorm ? &e->sc()->tv_sum : &e->sc()->s_real, unnorm ? 5 : 4, 0.f, 0.f, 0.f, s));
   if (tr) {
     CHK(comm_grads_ready(e, GT_ROLE_D, D.last.dW, (long)D.last.in * D.last.out + D.last.out, s));
@@ -969,7 +962,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   }
   // data parallel: the rest of D's gradient + the four loss / count sums, then the step stream waits for the communicator
   CHK(comm_finish_step(e, GT_ROLE_D, tr, &e->sc()->s_real, comm_early ? 0 : 4, s));
-  e->d_begin_done = true;
+  rc.begin_done[GT_ROLE_D] = true;
   return GT_OK;
 }
 
@@ -983,42 +976,43 @@ static void fill_g_result(const StepResults* h, gt_g_result* out) {
   out->loss_g = h->loss_g; out->grad_norm = h->gnorm_g;
 }
 
-extern "C" int gt_update_discriminator_end(gt_engine* e, int train, gt_d_result* out, void* stream) {
+// The second half of either step: the optimizer step, enqueued BEFORE the host waits for anything; then early results posted by _begin are waited for, else
+// `finalize` launches the role's finalisation and the results are posted as deferred (out == null: nothing synchronises) or fetched into rc.h_res.
+template <typename Finalize>
+static int step_end(gt_engine* e, int role, bool train, bool out_is_null, hipStream_t s, Finalize finalize) {
   if (!e) return fail(GT_ERR_INVALID, "null argument");
-  if (!e->d_begin_done) return fail(GT_ERR_STATE, "gt_update_discriminator_end without _begin");
+  ResultsChannel& rc = e->results;
+  if (!rc.begin_done[role]) return fail(GT_ERR_STATE, "gt_update_%s_end without _begin", role == GT_ROLE_D ? "discriminator" : "generator");
+  rc.begin_done[role] = false;
+  if (out_is_null && rc.early_posted()) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
+  if (train) CHK(optimizer_step(e, role, role == GT_ROLE_D ? &e->sc()->gnorm2_d : &e->sc()->gnorm2_g, s));
+  if (rc.early_posted()) return rc.wait_early();
+  finalize();
+  LAUNCH_CHECK();
+  return out_is_null ? rc.post_deferred(role, s) : rc.fetch(s);
+}
+static int step_result(gt_engine* e, int role) { return e->results.collect(role); }      // ... then in e->results.h_def[role]
+
+extern "C" int gt_update_discriminator_end(gt_engine* e, int train, gt_d_result* out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  e->d_begin_done = false;
-  // out == null: deferred -- enqueue everything, synchronise nothing; gt_update_discriminator_result collects
-  if (!out && e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
-  if (train) CHK(optimizer_step(e, GT_ROLE_D, &e->sc()->gnorm2_d, s));
-  if (e->early_done) {
-    CHK(wait_early_results(e));                   // only the scalars; backward + step stay queued
-    e->early_done = false;
-  } else {
-    launch_finalize_d(e->sc(), e->res(), train ? 0 : 1, 0, s);
-    LAUNCH_CHECK();
-    if (!out) return post_deferred_results(e, GT_ROLE_D, s);
-    CHK(fetch_results(e, s));
-  }
-  fill_d_result(e->h_res, out);
+  CHK(step_end(e, GT_ROLE_D, train != 0, !out, s, [&] { launch_finalize_d(e->sc(), e->res(), train ? 0 : 1, 0, s); }));
+  if (out) fill_d_result(e->results.h_res, out);
   return GT_OK;
 }
 extern "C" int gt_update_discriminator_result(gt_engine* e, gt_d_result* out) {
   if (!e || !out) return fail(GT_ERR_INVALID, "null argument");
-  if (!e->def_pending[GT_ROLE_D]) return fail(GT_ERR_STATE, "no deferred discriminator result pending");
-  HIPCHK(hipEventSynchronize(e->ev_def[GT_ROLE_D]));
-  e->def_pending[GT_ROLE_D] = false;
-  fill_d_result(e->h_def[GT_ROLE_D], out);
+  CHK(step_result(e, GT_ROLE_D));
+  fill_d_result(e->results.h_def[GT_ROLE_D], out);
   return GT_OK;
 }
 
 extern "C" int gt_update_discriminator(gt_engine* e, const float* x, const float* y_static, const float* y_hat_static,
                                        const float* mask, int B, int T, int train, float eps, gt_d_result* out, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  e->early = true;
+  e->results.early = true;
   int r = gt_update_discriminator_begin(e, x, y_static, y_hat_static, mask, B, T, train, eps, stream);
-  e->early = false;
-  if (r != GT_OK) { e->early_done = false; e->d_unnorm = false; e->ticket_wait = 0; return r; }
+  e->results.early = false;
+  if (r != GT_OK) { e->results.abandon(); e->d_unnorm = false; return r; }
   return gt_update_discriminator_end(e, train, out, stream);
 }
 
@@ -1138,6 +1132,25 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   return GT_OK;
 }
 
+// Which launches of the generator step carry which sums, and how its scalars are reported.  With X = mse_in_backward:
+//   call                               | sums                                                        | report
+//   split-phase, or X                  | own launches (with X the MSE sum comes from the backward)   | at _end
+//   fused, single GPU, riders off      | folded                                                      | early, this stream
+//   fused, single GPU, riders on       | riders (the rider writes results and ticket)                | early, this stream
+//   fused, communicator, riders off    | own launches                                                | early via the communicator iff opt_comm_early_g, else at _end
+//   fused, communicator, riders on     | riders (the rider files the sums only: no results, no ticket) | as the row above
+struct GPlan {
+  bool mse_in_backward;      // phase "train", no parameter generation in the stashed pass (In2Out always has it), mse_w != 0: generator_backward's MSE launch yields the sum
+  // where the reported sums of squares and the head's partials are reduced: launches of their own; the finalisation launch; riders -- both sums of squares in ONE launch,
+  enum { SUMS_OWN, SUMS_FOLDED, SUMS_RIDERS } sums;      // the head's scalars and the finalisation as one extra workgroup of the gradient assembly: four launches become two
+  enum { REPORT_AT_END, REPORT_EARLY, REPORT_EARLY_COMM } report;      // by _end; early from this stream; early from the communicator's stream
+  GPlan(gt_engine* e, bool train, float mse_w) : mse_in_backward(train && !e->g_band && mse_w != 0.f) {
+    const bool fused = e->results.early && !mse_in_backward, comm = comm_on(e);
+    sums = !fused ? SUMS_OWN : e->opt_launch_riders ? SUMS_RIDERS : comm ? SUMS_OWN : SUMS_FOLDED;
+    report = !fused ? REPORT_AT_END : !comm ? REPORT_EARLY : e->opt_comm_early_g ? REPORT_EARLY_COMM : REPORT_AT_END;
+  }
+};
+
 extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const float* y, const float* y_hat, const float* y_static,
                                          const float* y_hat_static, float adv_w, const float* mask, int B, int T, int train,
                                          float mse_w, float mge_w, float eps, void* stream) {
@@ -1158,29 +1171,23 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   if (comm_on(e) && tr && G.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_g.zero_grad() must precede update_generator");
-  e->ws[GT_ROLE_G].sdefer.reset(e->early && tr && G.has_opt);
+  ResultsChannel& rc = e->results;
+  e->ws[GT_ROLE_G].sdefer.reset(rc.early && tr && G.has_opt);
   CHK(ensure_tv(e, mask, N, s));
+  const GPlan plan(e, tr, mse_w);
+  const bool riders = plan.sums == GPlan::SUMS_RIDERS;
+  CHK(e->partial.ensure(4096 * sizeof(double)));
   // loss_mse (always reported, train.py:294); its gradient is fused into the MLPG^T kernel
-  const bool direct = !e->g_band;      // no parameter generation in the stashed pass (In2Out always has it)
-  // (the fused single-GPU call reduces the MSE partials inside its finalisation launch: see early_now below)
-  const bool early_fold = e->early && !comm_on(e) && !(tr && direct && mse_w != 0.f);
   int mse_blocks = 0, mge_pre_blocks = 0;
-  // launch riders (fused single-GPU call): both reported sums of squares in one launch here; the head's scalar reduction and the
-  // step's finalisation as one extra workgroup of the gradient-assembly launch -- four launches become two
-  const bool riders = early_fold && e->opt_launch_riders;
-  // data parallel: the same launches, the rider then only files the three sums for the collective (nothing is reported from it)
-  const bool riders_dp = e->early && comm_on(e) && e->opt_launch_riders && !(tr && direct && mse_w != 0.f);
-  if (riders || riders_dp) {
-    CHK(e->partial.ensure(4096 * sizeof(double)));
+  if (riders) {
     GLossesArgs q;
     memset(&q, 0, sizeof(q));
     q.a1 = y_hat; q.lda1 = Do; q.b1 = y; q.ldb1 = Do; q.D1 = Do; q.partial1 = e->partial.as<double>() + 1024;
-    q.a2 = y_hat_static; q.lda2 = Ds; q.b2 = y_static; q.ldb2 = Ds; q.D2 = Ds; q.partial2 = e->partial.as<double>();
-    q.mask = mask; q.rows = N;
+    q.a2 = y_hat_static; q.lda2 = Ds; q.b2 = y_static; q.ldb2 = Ds; q.D2 = Ds; q.partial2 = e->partial.as<double>(); q.mask = mask; q.rows = N;
     launch_g_losses(q, &mse_blocks, &mge_pre_blocks, s);
     LAUNCH_CHECK();
-  } else if (!(tr && direct && mse_w != 0.f)) {
-    CHK(sum_sqerr(e, y_hat, Do, y, Do, mask, N, Do, &e->sc()->s_mse, nullptr, 0, 0.f, s, early_fold ? &mse_blocks : nullptr));
+  } else if (!plan.mse_in_backward) {
+    CHK(sum_sqerr(e, y_hat, Do, y, Do, mask, N, Do, &e->sc()->s_mse, nullptr, 0, 0.f, s, plan.sums == GPlan::SUMS_FOLDED ? &mse_blocks : nullptr));
   }
   // adversarial term with the CURRENT (already updated) D weights and a fresh dropout mask (train.py:297-308)
   e->g_has_adv = adv_w > 0.f;
@@ -1198,91 +1205,72 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     HeadCall hc;
     memset(&hc, 0, sizeof(hc));
     hc.mode = HEAD_G_ADV; hc.rows = p.rows; hc.n_real = N; hc.mask = mask; hc.n_mask = N; hc.eps = eps; hc.want_grad = tr; hc.want_w = false;
-    hc.defer_scalars = riders || riders_dp ? &head_blocks : nullptr;
+    hc.defer_scalars = riders ? &head_blocks : nullptr;
     CHK(d_pass_head(e, p, hc, gadv, s));
     if (tr) CHK(d_pass_backward(e, p, gadv, s));      // no weight gradients (train.py:307-308)
   }
   // MGE loss + gradient assembly at y_hat_static
-  const bool early_ok = e->early && !(tr && direct && mse_w != 0.f);
-  const bool early_now = early_ok && !comm_on(e), comm_early = early_ok && comm_on(e) && e->opt_comm_early_g;
-  int mge_blocks = 0;
-  e->early_done = false;
-  {
-    int nblk = frame_red_blocks(N * Ds);
-    CHK(e->partial.ensure(4096 * sizeof(double)));
-    float* gs = nullptr;
-    if (tr) { CHK(e->gs.ensure((size_t)N * Ds * sizeof(float))); gs = e->gs.as<float>(); }
-    const float* leak = (tr && e->leak_pending) ? e->leak.as<float>() : nullptr;
-    GFinalize fin;
-    memset(&fin, 0, sizeof(fin));
-    const bool rid = riders || riders_dp;
-    if (rid) {       // (riders implies early_now: the fused single-GPU call; riders_dp: sums only)
-      fin.on = 1; fin.sc = e->sc(); fin.out = riders ? early_res_target(e) : (StepResults*)nullptr; fin.adv_w = adv_w; fin.mse_w = mse_w; fin.mge_w = mge_w;
-      fin.has_adv = e->g_has_adv ? 1 : 0;
-      fin.part_mge = e->partial.as<double>(); fin.n_mge = mge_pre_blocks;
-      fin.part_mse = e->partial.as<double>() + 1024; fin.n_mse = mse_blocks;
-      fin.hp = head_blocks ? e->headp.as<HeadPartials>() : (const HeadPartials*)nullptr; fin.n_hp = head_blocks;
-      if (riders) { fin.ticket_value = take_ticket(e); fin.ticket = fin.ticket_value ? e->ticket_dev() : (unsigned*)nullptr; }
-    }
-    if (tr || !rid) {
-      StaticGradArgs q;
-      memset(&q, 0, sizeof(q));
-      q.yhs = y_hat_static; q.ld1 = Ds; q.ys = y_static; q.ld2 = Ds; q.mask = mask; q.rows = N; q.Ds = Ds; q.mge_w = mge_w;
-      q.adv_inv = e->d_adv_inv; q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
-      q.partial = rid ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak_unnorm ? 1 : 0;
-      nblk = launch_static_grad(q, s);
-    } else      // phase != "train": no gradient to assemble, the finalisation alone
-      launch_finalize_g_rider(fin, s);
-    LAUNCH_CHECK();
-    mge_blocks = nblk;
-    if (riders) CHK(post_early_results(e, s, fin.ticket_value));
-    else if (!early_now && !riders_dp) {   // the split-phase (data-parallel) caller all-reduces the sum itself: it must exist now
-      launch_sum_partials(e->partial.as<double>(), nblk, &e->sc()->s_mge, s);
-      LAUNCH_CHECK();
-    }
+  rc.clear_early();
+  int mge_blocks = frame_red_blocks(N * Ds);
+  float* gs = nullptr;
+  if (tr) { CHK(e->gs.ensure((size_t)N * Ds * sizeof(float))); gs = e->gs.as<float>(); }
+  const float* leak = (tr && e->leak_pending) ? e->leak.as<float>() : nullptr;
+  GFinalize fin;
+  memset(&fin, 0, sizeof(fin));
+  const bool reports = riders && plan.report == GPlan::REPORT_EARLY;      // the rider writes results and ticket; else it only files the sums
+  if (riders) {
+    fin.on = 1; fin.sc = e->sc(); fin.out = reports ? rc.target() : (StepResults*)nullptr; fin.adv_w = adv_w; fin.mse_w = mse_w; fin.mge_w = mge_w;
+    fin.has_adv = e->g_has_adv ? 1 : 0; fin.part_mge = e->partial.as<double>(); fin.n_mge = mge_pre_blocks;
+    fin.part_mse = e->partial.as<double>() + 1024; fin.n_mse = mse_blocks;
+    fin.hp = head_blocks ? e->headp.as<HeadPartials>() : (const HeadPartials*)nullptr; fin.n_hp = head_blocks;
+    if (reports) { fin.ticket_value = rc.take_ticket(); fin.ticket = fin.ticket_value ? rc.ticket_dev() : (unsigned*)nullptr; }
   }
-  if (early_now && !riders) {   // all four losses are final here; the MGE partials are reduced inside the finalisation launch
-    launch_finalize_g(e->sc(), early_res_target(e), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, e->partial.as<double>(), mge_blocks,
+  if (tr || !riders) {
+    StaticGradArgs q;
+    memset(&q, 0, sizeof(q));
+    q.yhs = y_hat_static; q.ld1 = Ds; q.ys = y_static; q.ld2 = Ds; q.mask = mask; q.rows = N; q.Ds = Ds; q.mge_w = mge_w;
+    q.adv_inv = e->d_adv_inv; q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
+    q.partial = riders ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak_unnorm ? 1 : 0;
+    mge_blocks = launch_static_grad(q, s);
+  } else      // phase != "train": no gradient to assemble, the finalisation alone
+    launch_finalize_g_rider(fin, s);
+  LAUNCH_CHECK();
+  if (reports) CHK(rc.post_early(s, fin.ticket_value));
+  else if (plan.sums == GPlan::SUMS_OWN) {   // the split-phase (data-parallel) caller all-reduces the sum itself: it must exist now
+    launch_sum_partials(e->partial.as<double>(), mge_blocks, &e->sc()->s_mge, s);
+    LAUNCH_CHECK();
+  }
+  if (plan.sums == GPlan::SUMS_FOLDED) {   // all four losses are final here; the MSE and MGE partials are reduced inside the finalisation launch
+    launch_finalize_g(e->sc(), rc.target(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, e->partial.as<double>(), mge_blocks,
                       mse_blocks ? (const double*)(e->partial.as<double>() + 1024) : (const double*)nullptr, mse_blocks, s);
     LAUNCH_CHECK();
-    CHK(post_early_results(e, s));
+    CHK(rc.post_early(s));
   }
+  const bool comm_early = plan.report == GPlan::REPORT_EARLY_COMM;
   if (comm_early) CHK(comm_early_results(e, GT_ROLE_G, &e->sc()->s_adv, 3, adv_w, mse_w, mge_w, s));
   if (tr) {
     CHK(generator_backward(e, e->last_x, y, y_hat, mask, mse_w, s));  // G's own input (cat(x, z), train.py:542)
     e->leak_pending = false; e->leak_unnorm = false;
   }
   CHK(comm_finish_step(e, GT_ROLE_G, tr, &e->sc()->s_adv, comm_early ? 0 : 3, s));
-  e->g_begin_done = true;
+  rc.begin_done[GT_ROLE_G] = true;
   return GT_OK;
 }
 
 extern "C" int gt_update_generator_end(gt_engine* e, int train, float adv_w, float mse_w, float mge_w, gt_g_result* out,
                                        void* stream) {
-  if (!e) return fail(GT_ERR_INVALID, "null argument");
-  if (!e->g_begin_done) return fail(GT_ERR_STATE, "gt_update_generator_end without _begin");
   hipStream_t s = (hipStream_t)stream;
-  e->g_begin_done = false;
-  if (!out && e->early_done) return fail(GT_ERR_STATE, "deferred results are a split-phase feature");
-  if (train) CHK(optimizer_step(e, GT_ROLE_G, &e->sc()->gnorm2_g, s));
-  if (e->early_done) {
-    CHK(wait_early_results(e));
-    e->early_done = false;
-  } else {
+  CHK(step_end(e, GT_ROLE_G, train != 0, !out, s, [&] {
     launch_finalize_g(e->sc(), e->res(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, train ? 0 : 1, nullptr, 0, nullptr, 0, s);
-    LAUNCH_CHECK();
-    if (!out) return post_deferred_results(e, GT_ROLE_G, s);
-    CHK(fetch_results(e, s));
-  }
-  fill_g_result(e->h_res, out);
+  }));
+  if (!out) return GT_OK;
+  fill_g_result(e->results.h_res, out);
   return fault_seen(e);
 }
 extern "C" int gt_update_generator_result(gt_engine* e, gt_g_result* out) {
   if (!e || !out) return fail(GT_ERR_INVALID, "null argument");
-  if (!e->def_pending[GT_ROLE_G]) return fail(GT_ERR_STATE, "no deferred generator result pending");
-  HIPCHK(hipEventSynchronize(e->ev_def[GT_ROLE_G]));
-  e->def_pending[GT_ROLE_G] = false;
-  fill_g_result(e->h_def[GT_ROLE_G], out);
+  CHK(step_result(e, GT_ROLE_G));
+  fill_g_result(e->results.h_def[GT_ROLE_G], out);
   return GT_OK;
 }
 
@@ -1290,10 +1278,10 @@ extern "C" int gt_update_generator(gt_engine* e, const float* x, const float* y,
                                    const float* y_hat_static, float adv_w, const float* mask, int B, int T, int train,
                                    float mse_w, float mge_w, float eps, gt_g_result* out, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  e->early = true;
+  e->results.early = true;
   int r = gt_update_generator_begin(e, x, y, y_hat, y_static, y_hat_static, adv_w, mask, B, T, train, mse_w, mge_w, eps, stream);
-  e->early = false;
-  if (r != GT_OK) { e->early_done = false; return r; }
+  e->results.early = false;
+  if (r != GT_OK) { e->results.abandon(); return r; }
   return gt_update_generator_end(e, train, adv_w, mse_w, mge_w, out, stream);
 }
 

@@ -12,9 +12,9 @@
 //   * every reduction is two-stage with a fixed order => run-to-run bit-reproducible.
 //
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
-// of the two product families), eng_step (the G+D step and the MLP stacks), eng_lstm / eng_sru (recurrent stacks of either role),
-// eng_comm (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the
-// non-template ones have internal linkage (GT_KERNEL) so that several units may include them.
+// of the two product families), eng_step (the G+D step, its ResultsChannel and the MLP stacks), eng_mlpg (band cache, MLPG launches), eng_dstack (fused
+// discriminator stack), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc (data-parallel communicator), eng_ops (stand-alone
+// operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage (GT_KERNEL) so that several units may include them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -244,6 +244,41 @@ struct MlpgCache {
   void clear() { for (auto* b : entries) { b->band.release(); delete b; } entries.clear(); }
 };
 
+// How a step's scalars reach the host, three routes and the one owner of their state.  early: the finalising launch of a fused call writes them into
+// the pinned page and the call returns once they have landed -- seen by polling a ticket behind them (GT_OPT_POLL_RESULTS) or, ticket 0, by an event -- with the rest
+// of the step still queued; deferred (split-phase, out == NULL): own pinned copy + event per role, collected by gt_update_*_result; blocking: copy + synchronise.
+struct ResultsChannel {
+  StepResults *h_res = nullptr, *h_res_dev = nullptr;      // pinned page: the results, the ticket 64 bytes behind them; the same page as the kernels see it (null: GT_RES_HOSTMAP=0, or no device view)
+  StepResults* d_res = nullptr; const bool* poll = nullptr;      // of the engine: res(), where the finalising launches of the other routes leave the results; opt_poll_results
+  bool early = false, early_done = false;  // a fused call is running; its early results are posted and not waited for yet
+  unsigned ticket_next = 0, ticket_wait = 0; hipEvent_t ev_res = nullptr;      // last number handed out / the one the posted early results carry (0: ev_res is used)
+  StepResults* h_def[2] = {nullptr, nullptr}; hipEvent_t ev_def[2] = {nullptr, nullptr}; bool def_pending[2] = {false, false};
+  bool begin_done[2] = {false, false};     // per role: gt_update_*_begin has run, _end has not
+  int create(StepResults* device_results, const bool* poll_option);
+  void destroy() {
+    if (h_res) (void)hipHostFree(h_res);      if (ev_res) (void)hipEventDestroy(ev_res);
+    for (int r = 0; r < 2; ++r) { if (h_def[r]) (void)hipHostFree(h_def[r]); if (ev_def[r]) (void)hipEventDestroy(ev_def[r]); }
+  }
+  StepResults* target() const { return h_res_dev ? h_res_dev : d_res; }      // where a launch that reports early writes the results
+  unsigned* ticket_dev() const { return h_res_dev ? (unsigned*)((char*)h_res_dev + 64) : nullptr; }
+  volatile unsigned* ticket_host() const { return (volatile unsigned*)((char*)h_res + 64); }
+  unsigned take_ticket() { if (!*poll || !h_res_dev) return 0;      if (++ticket_next == 0) ++ticket_next;      return ticket_next; }      // for results that the NEXT finalising launch writes into the host page (0: not available)
+  int post_early(hipStream_t s, unsigned ticket = 0);
+  int wait_early();                        // only the scalars; backward + step stay queued
+  bool early_posted() const { return early_done; }      void clear_early() { early_done = false; }
+  int post_deferred(int role, hipStream_t s);
+  int collect(int role) {                  // ... then in h_def[role]
+    if (!def_pending[role]) return fail(GT_ERR_STATE, "no deferred %s result pending", role == GT_ROLE_D ? "discriminator" : "generator");
+    HIPCHK(hipEventSynchronize(ev_def[role]));
+    def_pending[role] = false;
+    return GT_OK;
+  }
+  int fetch(hipStream_t s) { HIPCHK(hipMemcpyAsync(h_res, d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); return GT_OK; }
+  void abandon() { early_done = false; ticket_wait = 0; }      // a fused call whose _begin failed
+  void forget_begin() { begin_done[0] = begin_done[1] = false; }      // an option changed what an open _begin had stashed
+  void reset() { forget_begin(); early_done = false; }         // gt_clear_faults
+};
+
 struct gt_engine {
   gt_stream_config cfg;
   Net net[2];
@@ -262,9 +297,7 @@ struct gt_engine {
   NetWs ws[2];                             // workspace: per role, then (below) what one call uses and both roles share
   Scratch dcat, dzA, dzB, leak, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
   Scratch scal;                            // StepScalars + StepResults
-  StepResults* h_res = nullptr;            // pinned
-  StepResults* h_res_dev = nullptr;        // the same page as the kernels see it: the fused calls' finalisation writes the
-                                           // scalars straight into host memory (no device -> host copy launch behind it)
+  ResultsChannel results;                  // how the step's scalars reach the host
   // per-step state
   int B = 0, T = 0; long N = 0;
   const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;
@@ -278,25 +311,12 @@ struct gt_engine {
     void built(const float* x_, const float* yhs_) { valid = true; x = x_; yhs = yhs_; }
   };
   DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
-  bool d_begin_done = false, g_begin_done = false, g_has_adv = false;
+  bool g_has_adv = false;
   struct TvMemo {      // sum(mask) is already on the device for this step: of which mask, over how many frames, under which override
     const float* mask = nullptr; long n = 0; float ovr = 0.f;
     bool known(const float* m, long N, float o) const { return mask == m && n == N && ovr == o; }
     void note(const float* m, long N, float o) { mask = m; n = N; ovr = o; }      void forget() { mask = nullptr; }
   } tv;
-  // early results (single-GPU fused entry points): the step scalars are final right after the loss
-  // kernels, long before backward + optimizer finish; they are copied out then, and the call returns
-  // as soon as THAT copy has landed, leaving the rest of the step queued on the stream.
-  bool early = false, early_done = false;
-  hipEvent_t ev_res = nullptr;
-  // GT_OPT_POLL_RESULTS: instead of an event behind the finalisation (its record is a system-scope release in the MIDDLE of the step:
-  // ~6 us of idle stream, twice per step), the finalising thread writes a ticket number behind the results in the host page and
-  // the call polls for it.  ticket_* : last number handed out / the one the pending early results carry (0 = the event is used)
-  unsigned ticket_next = 0, ticket_wait = 0;
-  unsigned* ticket_dev() { return h_res_dev ? (unsigned*)((char*)h_res_dev + 64) : nullptr; }
-  volatile unsigned* ticket_host() { return (volatile unsigned*)((char*)h_res + 64); }
-  // deferred results of the split-phase calls (out == NULL): own pinned copy + event per role, fetched by gt_*_result
-  StepResults* h_def[2] = {nullptr, nullptr}; hipEvent_t ev_def[2] = {nullptr, nullptr}; bool def_pending[2] = {false, false};
   Scratch i2o_gout, d_dx0;                         // In2OutRNNHighwayNet: hidden2out output G(x); a recurrent DISCRIMINATOR (train.py:773-774 allows any model class): gradient w.r.t. its [x | adv] input
   Scratch l_state, l_xch, s_du, s_dx, s_dbias;     // recurrent layer in hand (either role): LSTM per-step kernels' state, persistent kernels' exchange granules; SRU backward temporaries
   struct GtComm* comm = nullptr;                   // gt_comm_init: RCCL communicator + comm stream (data parallel)
@@ -329,7 +349,7 @@ struct gt_engine {
   // by the generator step's gradient assembly for the kept dloss_d/dy_hat_static.  d_unnorm / leak_unnorm: in that state right now.
   bool opt_comm_tv_in_sums = env_flag("GT_COMM_TV_IN_SUMS", true);
   bool d_unnorm = false, leak_unnorm = false;
-  bool opt_poll_results = env_flag("GT_POLL_RESULTS", true);      // round 4: no gain (1.380 / 1.384 vs 1.381 / 1.375 ms); round 5, the step 60 us shorter: 1.3125 / 1.312 vs
+  bool opt_poll_results = env_flag("GT_POLL_RESULTS", true);      // GT_OPT_POLL_RESULTS (ResultsChannel::take_ticket): round 4: no gain (1.380 / 1.384 vs 1.381 / 1.375 ms); round 5, the step 60 us shorter: 1.3125 / 1.312 vs
                                                                   // 1.319 / 1.315 / 1.3175 / 1.3206 ms, b = 4 0.400 vs 0.406 -- the two 5.8 us holes behind the finalising launches now show
   bool opt_launch_riders = env_flag("GT_LAUNCH_RIDERS", true);     // GT_OPT_LAUNCH_RIDERS: small reductions as extra workgroups of neighbouring launches
   int ld_gx = 0, ld_cx = 0;                        // gt_set_x_pitch: row pitch of the generator input / the conditioning x (0 = dense)
@@ -466,7 +486,6 @@ int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, cons
 // ------------------------------------------------------------------------------------------
 // eng_step.hip
 // ------------------------------------------------------------------------------------------
-int post_early_results(gt_engine* e, hipStream_t s, unsigned ticket = 0);
 int cond_dim(gt_engine* e);
 
 // ------------------------------------------------------------------------------------------

@@ -28,6 +28,22 @@ def build_model(spec, seed, saturate_gates=False):
     return m.cuda()
 
 
+def state_arrays(mg, md, og, od):
+    """Parameters and optimizer state of both networks as numpy arrays, keyed as run_hip_case returns them."""
+    out = {}
+    for k, v in mg.state_dict().items():
+        out["G." + k] = v.cpu().numpy()
+    for k, v in md.state_dict().items():
+        out["D." + k] = v.cpu().numpy()
+    for tag, opt, model in (("G", og, mg), ("D", od, md)):
+        names = list(model.state_dict().keys())
+        for i, st in opt.state_dict()["state"].items():
+            for key in ("sum", "exp_avg", "exp_avg_sq"):
+                if key in st:
+                    out["%s.opt.%s.%s" % (tag, key, names[i])] = st[key].cpu().numpy()
+    return out
+
+
 def run_hip_case(case, return_objects=False, engine_options=None, comm_world_1=False, shard=None, comm_id=None, extra=None,
                  philox=False, pitch_x=False):
     """shard = (rank, world): this process holds sequences rank, rank + world, ... of the case's batch (whole
@@ -113,16 +129,7 @@ def run_hip_case(case, return_objects=False, engine_options=None, comm_world_1=F
         rows = x.shape[0] * Tn
         extra["philox_g"] = eng.philox_mask(0, 0, 0, 0.5, rows, 48).cpu().numpy()
         extra["philox_d"] = eng.philox_mask(1, 0, 0, 0.5, 2 * rows, 40).cpu().numpy()
-    for k, v in mg.state_dict().items():
-        out["G." + k] = v.cpu().numpy()
-    for k, v in md.state_dict().items():
-        out["D." + k] = v.cpu().numpy()
-    for tag, opt, model in (("G", og, mg), ("D", od, md)):
-        names = list(model.state_dict().keys())
-        for i, st in opt.state_dict()["state"].items():
-            for key in ("sum", "exp_avg", "exp_avg_sq"):
-                if key in st:
-                    out["%s.opt.%s.%s" % (tag, key, names[i])] = st[key].cpu().numpy()
+    out.update(state_arrays(mg, md, og, od))
     if return_objects:
         return out, (mg, md, og, od)
     return out
