@@ -11,6 +11,9 @@ discriminator enters the generator's gradient): y_hat and every gradient tensor 
 on the same inputs (computed once per shape).  Lengths are unsorted and include 1 and T; the last batch tile is ragged
 unless the shape says otherwise.  The discriminator case does the same for a recurrent discriminator's step, whose one
 pass over 2B sequences is what picks 16-sequence tiles at B = 32.
+
+The per-step kernels beyond one batch tile and two K chunks, hidden widths that are no multiple of 4 and the adversarial
+term through a recurrent discriminator are tests/test_gpu_lstm_steps.py, on this module's helpers and shapes.
 """
 import functools
 
@@ -32,11 +35,12 @@ NXCD = 8                      # MI355X: 8 XCDs of 32 CUs (eng_lstm.hip: seq_xcds
 # every bf16 case of MATRIX against the float64 oracle.  Per tensor: relative rms, and the worst single error relative to
 # the tensor's largest magnitude -- for y_hat the worst of any one sequence over its valid frames, for a gradient (one
 # tensor per layer and direction) the worst element.  Each limit is 4x its measured worst value at most and stays under
-# the caps of test_matmul_bf16_step_tracks_the_float32_oracle (2e-2 outputs, 8e-2 gradients).
-Y_RMS_LIM = 1e-2              # measured worst 2.60e-3 (h256-bf16-btauto-upcauto)
-Y_SEQ_LIM = 1.2e-2            # measured worst 3.11e-3 (h256-bf16-btauto-upcauto, h264-bf16)
-G_RMS_LIM = 2e-2              # measured worst 5.91e-3 (h24t2-bf16)
-G_WORST_LIM = 2.5e-2          # measured worst 6.59e-3 (h24t2-bf16)
+# the caps of test_matmul_bf16_step_tracks_the_float32_oracle (2e-2 outputs, 8e-2 gradients).  h37-bf16 (test_gpu_lstm_steps.py)
+# is the mixed state of matmul_bf16 with H % 8 != 0 -- the bf16 recurrence over float32 products -- and stays below each.
+Y_RMS_LIM = 1e-2              # measured worst 2.60e-3 (h256-bf16-btauto-upcauto); h37-bf16 1.20e-3
+Y_SEQ_LIM = 1.2e-2            # measured worst 3.11e-3 (h256-bf16-btauto-upcauto, h264-bf16); h37-bf16 2.22e-3
+G_RMS_LIM = 2e-2              # measured worst 5.91e-3 (h24t2-bf16); h37-bf16 3.23e-3
+G_WORST_LIM = 2.5e-2          # measured worst 6.59e-3 (h24t2-bf16); h37-bf16 4.38e-3
 
 # Shapes of the matrix: (H, layers, bidirectional, B, T, in_dim)
 SHAPES = {
@@ -46,6 +50,12 @@ SHAPES = {
     "h512": (512, 1, False, 3, 9, 17),        # the largest HP 512 layer
     "h24t2": (24, 2, True, 4, 2, 9),          # the shortest sequence the persistent kernels take
     "h24t1": (24, 2, True, 4, 1, 9),          # T = 1: per-step kernels
+    # odd hidden widths and the per-step route beyond one batch tile / two K chunks (cases: tests/test_gpu_lstm_steps.py)
+    "h37": (37, 2, True, 37, 7, 11),          # H % 4 = 1; per-step unit tiles 4 x 8 + 5 forward, 32 + 5 backward; batch tiles 32 + 5
+    "h3": (3, 1, True, 2, 3, 5),              # H < 4: one partial tile everywhere, K = 12 in the backward
+    "h260u": (260, 2, False, 33, 5, 9),       # H % 4 = 0 with a 4-wide K tail; unidirectional stack; batch tiles 32 + 1
+    "h520": (520, 1, True, 3, 4, 9),          # H > 512: forward K chunks 256 + 256 + 8, backward K = 2080 = 8 chunks + 32
+    "h515": (515, 1, False, 3, 4, 9),         # H > 512 with H % 4 = 3
 }
 
 # Instantiations MI355X refuses for a shape (the grid is not co-resident: eng_lstm.hip launch_seq): key (shape, pass, HP,
@@ -55,6 +65,7 @@ SHAPES = {
 # the launcher takes UPC 16 instead.  The h264 / h512 cases that force UPC 8 assert exactly that fall-through.
 _HP512_UPC8 = "forward HP 512 x UPC 8: cdiv(H, 8) >= 33 workgroups per group, one per CU, 32 CUs per XCD"
 REFUSED = {(s, "fwd", 512, 8, bt, p): _HP512_UPC8 for s in ("h264", "h512") for bt in (8, 16) for p in (0, 1)}
+REFUSED[("h260u", "fwd", 512, 8, 8, 0)] = _HP512_UPC8          # cdiv(260, 8) = 33 as well (tests/test_gpu_lstm_steps.py)
 # Instantiations no case of MATRIX reaches, with the reason: slot -> why.  Which case reaches each of the other 20 slots
 # (forward 16 * 0 + ..., backward 16 + ...):
 #   0 / 1   fwd 256 UPC 8  BT 8   f32 / bf16   h40-bt8-upc8, h24t2          16 / 17  bwd 256 BT 8   h40-bt8-*, h24t2
@@ -161,15 +172,13 @@ def _hp():
 _DSPEC_MLP = dict(kind="MLP", in_dim=58, out_dim=1, num_hidden=1, hidden_dim=16, dropout=0.0, last_sigmoid=True)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(shape):
-    """The float64 oracle's generator step on the shape's inputs: y_hat and the gradient of every parameter tensor."""
+def oracle_step(spec, weights, x, y, lengths, model_cls=None, **model_kw):
+    """The float64 oracle's generator step (adv_w = 0) of an LSTMRNN with `weights` on one batch: y_hat and the gradient of
+    every parameter tensor.  model_cls: an OracleLSTMRNN subclass (the mutated recurrences of test_gpu_lstm_steps.py)."""
     from gantts_amd import paramgen
-    H, L, bi, B, T, din = SHAPES[shape]
-    x, y, lengths = _batch(B, T, din, seed=H + B + T)
-    spec = _gspec(shape)
-    o = O.OracleLSTMRNN(**{k: v for k, v in spec.items() if k != "kind"})
-    o.load_state_dict(C.make_weights(spec, 7))
+    T = x.shape[1]
+    o = (model_cls or O.OracleLSTMRNN)(**{k: v for k, v in spec.items() if k != "kind"}, **model_kw)
+    o.load_state_dict(weights)
     O.cast_model(o, torch.float64)
     o.training = False
     opt = O.OracleAdagrad(o.params, lr=0.01, initial_accumulator_value=1e-4)
@@ -183,31 +192,48 @@ def reference(shape):
     yh, yhs = O.apply_generator(cfg, o, xc, R, list(lengths))
     O.update_generator(cfg, o, None, opt, xc, yc, yh, ys, yhs, 0.0, list(lengths), mask, "train", mse_w=1.0, mge_w=1.0)
     return dict(x=x, y=y, lengths=lengths, y_hat=yh.detach().numpy().copy(), names=list(o.names),
-                grads=[p.grad.numpy().copy() for p in o.params])
+                grads=[p.grad.numpy().copy() for p in o.params], model=o)
 
 
-def run_engine(c):
-    """One generator step of the engine with the case's kernel selection; returns the path counts, y_hat, the gradients
-    split like the oracle's parameters, and hidden2out.bias as y_hat saw it."""
+@functools.lru_cache(maxsize=None)
+def reference(shape):
+    """The float64 oracle's generator step on the shape's inputs: y_hat and the gradient of every parameter tensor."""
+    H, L, bi, B, T, din = SHAPES[shape]
+    x, y, lengths = _batch(B, T, din, seed=H + B + T)
+    return oracle_step(_gspec(shape), C.make_weights(_gspec(shape), 7), x, y, lengths)
+
+
+def make_engine(c):
+    """The case's generator (weights of seed 7), an MLP discriminator, the optimizer and the engine with the case's kernel
+    selection."""
     import gantts_amd.train as T
-    from gantts_amd import _lib as L
-    from gantts_amd import optim, paramgen
+    from gantts_amd import optim
     from gantts_amd.engine import engine_for
-    from gantts_amd.multistream import get_static_features
-    from gantts_amd.seqloss import sequence_mask
     from hip_runner import build_model
-    ref = reference(c["shape"])
-    H, _, _, B, Tn, _ = SHAPES[c["shape"]]
     hp = _hp()
     T.hp = hp
     mg, md = build_model(_gspec(c["shape"]), 7).eval(), build_model(_DSPEC_MLP, 8).eval()
     og = optim.Adagrad(mg.parameters(), lr=0.01, initial_accumulator_value=1e-4)
-    bias0 = mg.state_dict()["hidden2out.bias"].cpu().numpy().copy()      # what y_hat was computed with (the step updates it)
     eng = engine_for(hp, mg)
     eng.set_option("matmul_bf16", c["bf16"])
     eng.set_option("lstm_persistent", c["persistent"])
     eng.set_option("lstm_fwd_units", c["upc"])
     eng.set_option("lstm_xcd_local", c["xcd_local"])
+    return dict(hp=hp, mg=mg, md=md, og=og, eng=eng)
+
+
+def engine_step(e, c, ref):
+    """One generator step (zero_grad, apply_generator, update_generator with adv_w = 0) of make_engine's objects on the
+    batch of `ref` (x, y, lengths; its gradients give the split of the flat gradient)."""
+    import gantts_amd.train as T
+    from gantts_amd import _lib as L
+    from gantts_amd import paramgen
+    from gantts_amd.multistream import get_static_features
+    from gantts_amd.seqloss import sequence_mask
+    hp, mg, md, og, eng = e["hp"], e["mg"], e["md"], e["og"], e["eng"]
+    T.hp = hp
+    Tn = ref["x"].shape[1]
+    bias0 = mg.state_dict()["hidden2out.bias"].cpu().numpy().copy()      # what y_hat was computed with (the step updates it)
     L.check(L.lib.gt_set_tuning(b"lstm_bt", c["bt"]))
     try:
         x, y = torch.from_numpy(ref["x"]).cuda(), torch.from_numpy(ref["y"]).cuda()
@@ -230,6 +256,12 @@ def run_engine(c):
         off += r.size
     assert off == flat.size and list(mg.state_dict().keys()) == ref["names"]
     return dict(counts=counts, y_hat=yh.cpu().numpy(), grads=grads, bias=bias0)
+
+
+def run_engine(c):
+    """One generator step of the engine with the case's kernel selection; returns the path counts, y_hat, the gradients
+    split like the oracle's parameters, and hidden2out.bias as y_hat saw it."""
+    return engine_step(make_engine(c), c, reference(c["shape"]))
 
 
 def bf16_errors(got, ref, lengths=None):
@@ -255,6 +287,24 @@ def _assert_padding_is_bias(y_hat, lengths, bias, msg):
     for b, n in enumerate(lengths):
         tail = y_hat[b, n:]
         assert np.array_equal(tail, np.broadcast_to(bias, tail.shape)), "%s: frames past length %d of sequence %d are not hidden2out.bias" % (msg, n, b)
+
+
+def assert_step(got, ref, expect, tag, bf16=False):
+    """What every case asserts of one step: the path counts, padding frames, y_hat and every gradient tensor."""
+    assert got["counts"] == expect, "%s: kernel path counts %s, expected %s" % (
+        tag, {i: n for i, n in enumerate(got["counts"]) if n}, {i: n for i, n in enumerate(expect) if n})
+    _assert_padding_is_bias(got["y_hat"], ref["lengths"], got["bias"], tag)
+    if bf16:
+        figs = [bf16_errors(got["y_hat"], ref["y_hat"], ref["lengths"])] + [bf16_errors(g, r) for g, r in zip(got["grads"], ref["grads"])]
+        print("%s bf16 vs float64: y_hat rms %.3e worst sequence %.3e; gradients worst rms %.3e worst element %.3e" % (
+            tag, figs[0][0], figs[0][1], max(f[0] for f in figs[1:]), max(f[1] for f in figs[1:])))
+        assert_bf16(got["y_hat"], ref["y_hat"], tag + " y_hat", Y_RMS_LIM, Y_SEQ_LIM, ref["lengths"])
+        for nm, g, r in zip(ref["names"], got["grads"], ref["grads"]):
+            assert_bf16(g, r, tag + " grad " + nm, G_RMS_LIM, G_WORST_LIM)
+    else:
+        _close(got["y_hat"], ref["y_hat"], msg=tag + " y_hat")
+        for nm, g, r in zip(ref["names"], got["grads"], ref["grads"]):
+            _close(g, r, msg=tag + " grad " + nm)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -316,20 +366,7 @@ def test_expected_counts_model_the_launcher():
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", MATRIX, ids=[_case_id(c) for c in MATRIX])
 def test_generator_step_vs_float64(case):
-    ref = reference(case["shape"])
-    got = run_engine(case)
-    tag = _case_id(case)
-    assert got["counts"] == _expected(case), "%s: kernel path counts %s, expected %s" % (
-        tag, {i: n for i, n in enumerate(got["counts"]) if n}, {i: n for i, n in enumerate(_expected(case)) if n})
-    _assert_padding_is_bias(got["y_hat"], ref["lengths"], got["bias"], tag)
-    if case["bf16"]:
-        assert_bf16(got["y_hat"], ref["y_hat"], tag + " y_hat", Y_RMS_LIM, Y_SEQ_LIM, ref["lengths"])
-        for nm, g, r in zip(ref["names"], got["grads"], ref["grads"]):
-            assert_bf16(g, r, tag + " grad " + nm, G_RMS_LIM, G_WORST_LIM)
-    else:
-        _close(got["y_hat"], ref["y_hat"], msg=tag + " y_hat")
-        for nm, g, r in zip(ref["names"], got["grads"], ref["grads"]):
-            _close(g, r, msg=tag + " grad " + nm)
+    assert_step(run_engine(case), reference(case["shape"]), _expected(case), _case_id(case), bf16=case["bf16"])
 
 
 # recurrent discriminator: MLP generator, bidirectional 2 x 32 LSTMRNN discriminator, B = 32.  The D step runs the natural
@@ -341,8 +378,7 @@ _GSPEC_MLP = dict(kind="MLP", in_dim=DSTEP["din"], out_dim=DOUT, num_hidden=2, h
 DSTEP_EXPECT = expected_counts("dstep", 32, 2, True, 2 * DSTEP["B"], DSTEP["T"])
 
 
-@pytest.mark.gpu
-def test_recurrent_discriminator_step_vs_float64():
+def dstep_vs_float64(dspec, B, Tn, expect, persistent=1):
     """The discriminator gradients of one D step against the float64 oracle's update_discriminator, fed the engine's own
     y_hat_static (the generator is not under test here)."""
     import gantts_amd.train as T
@@ -351,14 +387,14 @@ def test_recurrent_discriminator_step_vs_float64():
     from gantts_amd.multistream import get_static_features
     from gantts_amd.seqloss import sequence_mask
     from hip_runner import build_model
-    B, Tn = DSTEP["B"], DSTEP["T"]
     x_np, y_np, lengths = _batch(B, Tn, DSTEP["din"], seed=5)
     hp = _hp()
     T.hp = hp
-    mg, md = build_model(_GSPEC_MLP, 3).eval(), build_model(_DSPEC_RNN, 4).eval()
+    mg, md = build_model(_GSPEC_MLP, 3).eval(), build_model(dspec, 4).eval()
     od = optim.Adagrad(md.parameters(), lr=0.01, initial_accumulator_value=1e-4)
     og = optim.Adagrad(mg.parameters(), lr=0.01, initial_accumulator_value=1e-4)
     eng = engine_for(hp, mg)
+    eng.set_option("lstm_persistent", persistent)
     x, y = torch.from_numpy(x_np).cuda(), torch.from_numpy(y_np).cuda()
     R = paramgen.unit_variance_mlpg_matrix_cuda(hp.windows, Tn)
     ys = get_static_features(y, 3, hp.stream_sizes, hp.has_dynamic_features)
@@ -370,11 +406,11 @@ def test_recurrent_discriminator_step_vs_float64():
     eng.check_faults()
     counts = eng.lstm_path_counts()
     got = md.flat_grads().cpu().numpy().astype(np.float64)
-    assert counts == DSTEP_EXPECT, ({i: n for i, n in enumerate(counts) if n}, {i: n for i, n in enumerate(DSTEP_EXPECT) if n})
+    assert counts == expect, ({i: n for i, n in enumerate(counts) if n}, {i: n for i, n in enumerate(expect) if n})
 
     f64 = torch.float64
-    o = O.OracleLSTMRNN(**{k: v for k, v in _DSPEC_RNN.items() if k != "kind"})
-    o.load_state_dict(C.make_weights(_DSPEC_RNN, 4))
+    o = O.OracleLSTMRNN(**{k: v for k, v in dspec.items() if k != "kind"})
+    o.load_state_dict(C.make_weights(dspec, 4))
     O.cast_model(o, f64)
     o.training = False
     opt = O.OracleAdagrad(o.params, lr=0.01, initial_accumulator_value=1e-4)
@@ -391,3 +427,9 @@ def test_recurrent_discriminator_step_vs_float64():
         _close(got[off:off + r.size].reshape(r.shape), r, msg="recurrent D grad " + nm)
         off += r.size
     assert off == got.size
+
+
+@pytest.mark.gpu
+def test_recurrent_discriminator_step_vs_float64():
+    """The bidirectional 2 x 32 discriminator at B = 32 on the persistent kernels (16-sequence tiles)."""
+    dstep_vs_float64(_DSPEC_RNN, DSTEP["B"], DSTEP["T"], DSTEP_EXPECT)
