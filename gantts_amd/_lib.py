@@ -48,6 +48,8 @@ MAX_STREAMS = 8
 MLPG_R_FROM_WINDOWS = 1                 # GT_MLPG_R_FROM_WINDOWS: "build the band from the registered windows", passed in place of R
 MLPG_MAX_WINDOW_SPAN = 32               # GT_MLPG_MAX_WINDOW_SPAN
 COMM_ID_BYTES = 128
+SCALE_NONE, SCALE_MINMAX, SCALE_MEANVAR = 0, 1, 2      # AssembleCase.x_kind / y_kind
+ASSEMBLE_MAX_WINDOWS, ASSEMBLE_MAX_TAPS = 4, 9
 
 
 class StreamConfig(C.Structure):
@@ -175,6 +177,16 @@ class MlpgVarCase(C.Structure):
                 + [(n, C.c_void_p) for n in ("y", "var", "ys")] + [("max_ws_bytes", C.c_int64)])
 
 
+class AssembleCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("B", "T", "Dx", "Dy", "nz", "Ds", "ldX", "ldY", "ld_gi", "ld_y", "ld_ys", "x_kind", "y_kind",
+                                          "stats_f64", "n_windows")]
+                + [("key0", C.c_uint32), ("key1", C.c_uint32), ("win_len", C.c_int32 * ASSEMBLE_MAX_WINDOWS), ("pad_", C.c_int32)]
+                + [(n, C.c_int64) for n in ("F", "n_slots", "first_slot")]
+                + [("coef", (C.c_double * ASSEMBLE_MAX_TAPS) * ASSEMBLE_MAX_WINDOWS)]
+                + [(n, C.c_void_p) for n in ("X_all", "Y_all", "x_a", "x_b", "y_a", "y_b", "table", "scol", "dsrc", "dwin", "gi", "y",
+                                             "y_static", "mask", "lengths")])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -244,6 +256,7 @@ SIGNATURES = {
     "gt_op_mlpg_band": (_I, [_P, _P, _I, C.POINTER(_F), _L, C.POINTER(C.c_int32), _P]),
     "gt_op_mlpg_var": (_I, [C.POINTER(MlpgVarCase), _P]),
     "gt_mlpg_var_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_op_assemble_batch": (_I, [C.POINTER(AssembleCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

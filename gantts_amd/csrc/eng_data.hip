@@ -1,0 +1,81 @@
+// libgantts_hip.so -- the data path's stand-alone operator: gt_op_assemble_batch (one training batch out of a device-resident corpus)
+#include "engine_internal.hip.h"
+#include "data_kernels.hip.h"
+
+using namespace gt;
+
+static_assert(ASM_MAX_WINDOWS == GT_ASSEMBLE_MAX_WINDOWS && ASM_MAX_TAPS == GT_ASSEMBLE_MAX_TAPS, "window table of the kernel and of the ABI");
+
+template <typename SX, typename SY, bool DELTA>
+static int launch_assemble(const AssembleArgs& a, hipStream_t s) {
+  const size_t lds = assemble_lds_bytes(sizeof(SX), sizeof(SY), a.Dx, a.Dy, a.Ds, a.ldY, DELTA);
+  if (lds > 64 * 1024)
+    return fail(GT_ERR_INVALID, "assemble_batch: statistics of %d + %d columns need %zu bytes of LDS (limit 65536)", a.Dx, a.Dy, lds);
+  const long rows = (long)a.B * a.T;
+  hipLaunchKernelGGL((assemble_batch_kernel<SX, SY, DELTA>), dim3(cdiv(rows, ASM_ROWS_PER_WG)), dim3(ASM_WAVES * 64), lds, s, a);
+  LAUNCH_CHECK();
+  return GT_OK;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "assemble_batch: null case");
+  if (!c->X_all || !c->Y_all || !c->table) return fail(GT_ERR_INVALID, "assemble_batch: null corpus or table");
+  if (c->B < 1 || c->T < 1 || c->Dx < 1 || c->Dy < 1 || c->nz < 0 || c->Ds < 0 || c->F < 0)
+    return fail(GT_ERR_INVALID, "assemble_batch: bad sizes B=%d T=%d Dx=%d Dy=%d nz=%d Ds=%d", c->B, c->T, c->Dx, c->Dy, c->nz, c->Ds);
+  if ((long)c->B * c->T > (1L << 31) - 64) return fail(GT_ERR_INVALID, "assemble_batch: B * T = %ld rows", (long)c->B * c->T);
+  if (c->ldX < c->Dx || c->ldY < c->Dy || c->ldX % 4 || c->ldY % 4 || !aligned16(c->X_all) || !aligned16(c->Y_all))
+    return fail(GT_ERR_INVALID, "assemble_batch: the corpus rows must sit on a 16-byte pitch (ldX=%d for %d, ldY=%d for %d columns)", c->ldX,
+                c->Dx, c->ldY, c->Dy);
+  if (c->first_slot < 0 || c->n_slots < 0 || c->first_slot + c->B > c->n_slots)
+    return fail(GT_ERR_INVALID, "assemble_batch: slots [%lld, %lld) of a table of %lld", (long long)c->first_slot,
+                (long long)(c->first_slot + c->B), (long long)c->n_slots);
+  for (int k = 0; k < 2; ++k) {
+    const int kind = k ? c->y_kind : c->x_kind;
+    if (kind < GT_SCALE_NONE || kind > GT_SCALE_MEANVAR) return fail(GT_ERR_INVALID, "assemble_batch: unknown scaling kind %d", kind);
+    if (kind != GT_SCALE_NONE && (!(k ? c->y_a : c->x_a) || !(k ? c->y_b : c->x_b))) return fail(GT_ERR_INVALID, "assemble_batch: null statistics");
+  }
+  if (c->stats_f64 < 0 || c->stats_f64 > 3) return fail(GT_ERR_INVALID, "assemble_batch: stats_f64 is a mask of bits 1 (x) and 2 (y)");
+  if (c->gi && (c->ld_gi < c->Dx + c->nz || c->ld_gi % 4 || !aligned16(c->gi)))
+    return fail(GT_ERR_INVALID, "assemble_batch: gi needs a 16-byte aligned pitch of at least %d floats, got %d", c->Dx + c->nz, c->ld_gi);
+  // the Philox counter of a frame is t * ceil(nz / 4) + group: one 32-bit word
+  if (c->nz > 0 && (long)c->T * ((c->nz + 3) / 4) > 0xFFFFFFFFL) return fail(GT_ERR_INVALID, "assemble_batch: T * ceil(nz / 4) exceeds 32 bits");
+  if (c->y && c->ld_y < c->Dy) return fail(GT_ERR_INVALID, "assemble_batch: ld_y %d for %d columns", c->ld_y, c->Dy);
+  if (c->y_static && (c->ld_ys < c->Ds || (c->Ds > 0 && !c->scol))) return fail(GT_ERR_INVALID, "assemble_batch: y_static needs scol and ld_ys >= Ds");
+  const bool delta = c->dsrc || c->dwin;
+  if (delta) {
+    if (!c->dsrc || !c->dwin || c->n_windows < 1 || c->n_windows > GT_ASSEMBLE_MAX_WINDOWS)
+      return fail(GT_ERR_INVALID, "assemble_batch: delta recomputation needs dsrc, dwin and 1..%d windows", GT_ASSEMBLE_MAX_WINDOWS);
+    for (int w = 0; w < c->n_windows; ++w)
+      if (c->win_len[w] < 1 || c->win_len[w] > GT_ASSEMBLE_MAX_TAPS || c->win_len[w] % 2 == 0)
+        return fail(GT_ERR_INVALID, "assemble_batch: window %d has %d taps (odd, at most %d)", w, c->win_len[w], GT_ASSEMBLE_MAX_TAPS);
+  }
+  AssembleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = c->B; a.T = c->T; a.Dx = c->Dx; a.Dy = c->Dy; a.nz = c->nz; a.Ds = c->y_static ? c->Ds : 0;
+  a.ldX = c->ldX; a.ldY = c->ldY; a.ld_gi = c->ld_gi; a.ld_y = c->ld_y; a.ld_ys = c->ld_ys;
+  a.x_kind = c->x_kind; a.y_kind = c->y_kind; a.n_windows = delta ? c->n_windows : 0;
+  a.key0 = c->key0; a.key1 = c->key1;
+  a.F = c->F; a.first_slot = c->first_slot;
+  a.X_all = c->X_all; a.Y_all = c->Y_all;
+  a.x_a = c->x_a; a.x_b = c->x_b; a.y_a = c->y_a; a.y_b = c->y_b;
+  a.table = (const long*)c->table;
+  a.scol = c->scol; a.dsrc = c->dsrc; a.dwin = c->dwin;
+  a.gi = c->gi; a.y = c->y; a.y_static = c->y_static; a.mask = c->mask; a.lengths = (long*)c->lengths;
+  for (int w = 0; w < a.n_windows; ++w) {
+    a.win_len[w] = c->win_len[w];
+    for (int k = 0; k < c->win_len[w]; ++k) a.coef[w][k] = c->coef[w][k];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch ((c->stats_f64 & 3) * 2 + (delta ? 1 : 0)) {
+    case 0: return launch_assemble<float, float, false>(a, s);
+    case 1: return launch_assemble<float, float, true>(a, s);
+    case 2: return launch_assemble<double, float, false>(a, s);
+    case 3: return launch_assemble<double, float, true>(a, s);
+    case 4: return launch_assemble<float, double, false>(a, s);
+    case 5: return launch_assemble<float, double, true>(a, s);
+    case 6: return launch_assemble<double, double, false>(a, s);
+    default: return launch_assemble<double, double, true>(a, s);
+  }
+}

@@ -19,6 +19,10 @@ Device side (the part that matters at >10^6 frames/s): ``DevicePrefetcher`` wrap
 ``(x, y, lengths)`` host batches and hands out batches that are already resident in HBM, sorted by
 length (train.py:494-501) -- batch k+1 is staged into pinned memory and copied on a side stream
 while step k runs on the compute stream, so the step never waits for PCIe.
+
+Device-resident corpus (``hp.resident_corpus``): ``ResidentCorpus`` uploads the raw utterances once, ``ResidentLoader`` plans each epoch
+on the host (``plan_epoch``), uploads one small table and produces every batch -- scaled, padded, sorted, with the generator's noise, the
+static features and the mask -- by ONE launch (gt_op_assemble_batch), bit for bit what the host pipeline above computes.
 """
 import os
 from os.path import join, splitext
@@ -231,6 +235,9 @@ def collate_ragged(batch):
 
 def _loaders(train_dataset, test_dataset, hp):
     from torch.utils import data as data_utils
+    if bool(getattr(hp, "resident_corpus", False)):              # gantts_amd extension: the corpus lives on the device (ResidentLoader)
+        return {"train": ResidentLoader(train_dataset, hp.batch_size, True, hp),
+                "test": ResidentLoader(test_dataset, hp.batch_size, False, hp, first_draw=1 << 31)}
     ragged = bool(getattr(hp, "device_collate", False))          # gantts_amd extension: pad + sort on the device
     kw = dict(batch_size=hp.batch_size, num_workers=hp.num_workers, pin_memory=hp.pin_memory,
               collate_fn=collate_ragged if ragged else collate_fn)
@@ -256,12 +263,15 @@ def get_tts_data_loaders(X, Y, X_data_min, X_data_max, Y_data_mean, Y_data_std, 
 # ---- device side --------------------------------------------------------------------------------
 class DeviceBatch(object):
     """One length-sorted batch resident on the device (what train_loop consumes per step)."""
-    __slots__ = ("x", "y", "lengths", "cpu_lengths", "max_len", "ready")
+    __slots__ = ("x", "y", "lengths", "cpu_lengths", "max_len", "ready", "generator_input", "y_static", "mask")
 
-    def __init__(self, x, y, lengths, cpu_lengths, ready):
+    def __init__(self, x, y, lengths, cpu_lengths, ready, generator_input=None, y_static=None, mask=None):
         self.x, self.y, self.lengths, self.cpu_lengths = x, y, lengths, cpu_lengths
         self.max_len = int(cpu_lengths[0]) if len(cpu_lengths) else 0
         self.ready = ready
+        # what train_loop derives from (x, y, lengths) per batch, when the loader has made it already (ResidentLoader): [x | z] with
+        # x its prefix view, get_static_features(y), sequence_mask(lengths).unsqueeze(-1); None: train_loop derives it
+        self.generator_input, self.y_static, self.mask = generator_input, y_static, mask
 
 
 class DevicePrefetcher(object):
@@ -384,3 +394,267 @@ class DevicePrefetcher(object):
             for t in (b.x, b.y, b.lengths):
                 t.record_stream(torch.cuda.current_stream(self.device))
         return b
+
+
+# ---- device-resident corpus ---------------------------------------------------------------------
+RESIDENT_MARGIN_BYTES = 2 << 30      # device memory a resident corpus leaves free: the step's workspaces, the batches, the allocator's slack
+
+
+def plan_epoch(offsets, lengths, batches):
+    """Host plan of one epoch of a resident corpus (no device): ``(table, plan)``.  ``batches`` is an iterable of lists of corpus
+    utterance indices.  ``table`` is the int64 ``[n_slots][3]`` array gt_op_assemble_batch reads -- first frame, length and utterance
+    index of every batch slot, batches back to back, each batch in the order ``torch.sort(lengths, descending=True)`` gives it (the
+    call DevicePrefetcher makes, train.py:495, so ties fall the same way); ``plan`` has one ``(first_slot, B, T, sorted lengths)``
+    per batch."""
+    rows, plan = [], []
+    for idx in batches:
+        idx = [int(i) for i in idx]
+        if not idx:
+            continue
+        lens = torch.from_numpy(np.array([lengths[i] for i in idx], dtype=np.int64))
+        sorted_lengths, indices = torch.sort(lens, dim=0, descending=True)
+        cpu_lengths = [int(v) for v in sorted_lengths.tolist()]
+        plan.append((len(rows), len(idx), cpu_lengths[0], cpu_lengths))
+        for k in indices.tolist():
+            u = idx[k]
+            rows.append((int(offsets[u]), int(lengths[u]), u))
+    return np.array(rows, dtype=np.int64).reshape(-1, 3), plan
+
+
+def _stat_vector(v, D, name):
+    v = np.asarray(v)
+    if v.dtype not in (np.float32, np.float64):
+        raise TypeError("ResidentCorpus: %s is %s; float32 or float64 statistics only" % (name, v.dtype))
+    return np.ascontiguousarray(np.broadcast_to(v, (D,)))
+
+
+def _fill_chunks(arrays, buf, D):
+    """Packs the rows of ``arrays`` back to back into columns ``[0, D)`` of the staging buffer ``buf (chunk, ld)`` and yields the
+    number of rows filled each time the buffer is full, and once more for the rest."""
+    chunk, filled = buf.size(0), 0
+    for a in arrays:
+        pos = 0
+        while pos < len(a):
+            k = min(len(a) - pos, chunk - filled)
+            buf[filled:filled + k, :D] = torch.from_numpy(np.ascontiguousarray(a[pos:pos + k]))
+            filled, pos = filled + k, pos + k
+            if filled == chunk:
+                yield filled
+                filled = 0
+    if filled:
+        yield filled
+
+
+class ResidentCorpus(object):
+    """The raw utterances of a ``TTSDataset`` / ``VCDataset`` on the device: ``X_all [F][ldX]``, ``Y_all [F][ldY]`` float32, back to
+    back on a 16-byte row pitch, with the dataset's statistics beside them in their own dtype.  Every utterance is read once
+    (``dataset.X[i]``, ``dataset.Y[i]``) and held on the host until ``upload`` has sent it in chunks through one pinned staging
+    buffer.  A corpus that does not fit ``torch.cuda.mem_get_info()`` minus ``RESIDENT_MARGIN_BYTES`` is refused (RuntimeError)
+    before anything is allocated: there is no fallback to the host pipeline."""
+
+    def __init__(self, dataset, device="cuda", chunk_frames=1 << 16):
+        from . import _lib as L
+        self.dataset, self.chunk_frames = dataset, int(chunk_frames)
+        n = len(dataset)
+        if n < 1:
+            raise ValueError("ResidentCorpus: empty dataset")
+        self._host = []
+        for i in range(n):
+            x, y = np.asarray(dataset.X[i]), np.asarray(dataset.Y[i])
+            if x.dtype != np.float32 or y.dtype != np.float32 or x.ndim != 2 or y.ndim != 2:
+                raise TypeError("ResidentCorpus: utterance %d is %s %s / %s %s; (T, D) float32 arrays only" % (i, x.dtype, x.shape, y.dtype, y.shape))
+            if len(x) != len(y):
+                raise ValueError("ResidentCorpus: utterance %d has %d input and %d output frames" % (i, len(x), len(y)))
+            self._host.append((x, y))
+        self.Dx, self.Dy = int(self._host[0][0].shape[1]), int(self._host[0][1].shape[1])
+        if any(x.shape[1] != self.Dx or y.shape[1] != self.Dy for x, y in self._host):
+            raise ValueError("ResidentCorpus: the utterances differ in width")
+        self.lengths = np.array([len(x) for x, _ in self._host], dtype=np.int64)
+        self.offsets = np.cumsum(self.lengths) - self.lengths
+        self.F = int(self.lengths.sum())
+        self.ldX, self.ldY = (self.Dx + 3) // 4 * 4, (self.Dy + 3) // 4 * 4
+        self.nbytes = self.F * (self.ldX + self.ldY) * 4
+        # the normalisation each __getitem__ applies (train.py:96-135), as (kind, a, b) per side
+        if hasattr(dataset, "X_data_scale"):         # TTSDataset: min-max x, mean-variance y
+            self.x_kind, xa, xb = L.SCALE_MINMAX, dataset.X_data_scale, dataset.X_data_min
+            self.y_kind, ya, yb = L.SCALE_MEANVAR, dataset.Y_data_mean, dataset.Y_data_std
+        elif hasattr(dataset, "data_mean"):          # VCDataset: the same mean-variance on both sides
+            if self.Dx != self.Dy:
+                raise ValueError("ResidentCorpus: a VCDataset scales both sides with one set of statistics; widths %d / %d" % (self.Dx, self.Dy))
+            self.x_kind, xa, xb = L.SCALE_MEANVAR, dataset.data_mean, dataset.data_std
+            self.y_kind, ya, yb = L.SCALE_MEANVAR, dataset.data_mean, dataset.data_std
+        else:
+            raise TypeError("ResidentCorpus: a TTSDataset or a VCDataset, not %s" % type(dataset).__name__)
+        self._stats_host = [_stat_vector(xa, self.Dx, "x statistics"), _stat_vector(xb, self.Dx, "x statistics"),
+                            _stat_vector(ya, self.Dy, "y statistics"), _stat_vector(yb, self.Dy, "y statistics")]
+        for a, b in (self._stats_host[:2], self._stats_host[2:]):
+            if a.dtype != b.dtype:       # numpy would compute the first operation in one dtype and the second in the other
+                raise TypeError("ResidentCorpus: the two statistics of one side must share a dtype (%s / %s)" % (a.dtype, b.dtype))
+        self.stats_f64 = int(self._stats_host[0].dtype == np.float64) | (int(self._stats_host[2].dtype == np.float64) << 1)
+        # delta recomputation of a TTSDataset (gantts/multistream.py:15-30): per column of y its source column and window
+        self.windows, self.dsrc_host, self.dwin_host = None, None, None
+        dhp = getattr(dataset, "hp", None)
+        if hasattr(dataset, "X_data_scale") and dhp is not None and getattr(dhp, "recompute_delta_features", False):
+            self._plan_deltas(dhp)
+        self.X_all = self.Y_all = self.stats = self.dsrc = self.dwin = None
+        if device is not None:
+            self.upload(device)
+
+    def _plan_deltas(self, hp):
+        from . import _lib as L
+        from .multistream import get_static_stream_sizes
+        windows = [np.asarray(c, dtype=np.float64) for _, _, c in hp.windows]
+        if len(windows) > L.ASSEMBLE_MAX_WINDOWS or any(len(c) % 2 == 0 or len(c) > L.ASSEMBLE_MAX_TAPS for c in windows):
+            raise ValueError("ResidentCorpus: delta recomputation takes at most %d windows of an odd number of at most %d taps"
+                             % (L.ASSEMBLE_MAX_WINDOWS, L.ASSEMBLE_MAX_TAPS))
+        if int(self.lengths.min()) < max(len(c) for c in windows):
+            raise ValueError("ResidentCorpus: an utterance is shorter than the longest window; the host pipeline "
+                             "(np.correlate(..., 'same')) cannot recompute its deltas either")
+        if sum(hp.stream_sizes) != self.Dy:
+            raise ValueError("ResidentCorpus: stream sizes %s for %d output columns" % (list(hp.stream_sizes), self.Dy))
+        dsrc, dwin = np.arange(self.Dy, dtype=np.int32), np.full(self.Dy, -1, dtype=np.int32)
+        statics = get_static_stream_sizes(hp.stream_sizes, hp.has_dynamic_features, len(windows))
+        start = 0
+        for size, n, dyn in zip(hp.stream_sizes, statics, hp.has_dynamic_features):
+            n = int(n)
+            if dyn:
+                if n * len(windows) != size:
+                    raise ValueError("ResidentCorpus: a dynamic stream of %d columns does not hold %d windows" % (size, len(windows)))
+                for w in range(len(windows)):
+                    dsrc[start + w * n:start + (w + 1) * n] = np.arange(start, start + n)
+                    dwin[start + w * n:start + (w + 1) * n] = w
+            start += size
+        self.windows, self.dsrc_host, self.dwin_host = windows, dsrc, dwin
+
+    def upload(self, device="cuda"):
+        if self.X_all is not None:
+            return self
+        device = torch.device(device)
+        free, total = torch.cuda.mem_get_info(device)
+        if self.nbytes > free - RESIDENT_MARGIN_BYTES:
+            raise RuntimeError("ResidentCorpus: %d frames x (%d + %d) floats = %d bytes do not fit the device: %d bytes free of %d, "
+                               "of which %d stay free as margin" % (self.F, self.ldX, self.ldY, self.nbytes, free, total, RESIDENT_MARGIN_BYTES))
+        X_all = torch.empty(self.F, self.ldX, device=device, dtype=torch.float32)
+        Y_all = torch.empty(self.F, self.ldY, device=device, dtype=torch.float32)
+        chunk = max(1, min(self.chunk_frames, self.F))
+        stage = torch.zeros(chunk * max(self.ldX, self.ldY), dtype=torch.float32).pin_memory()
+        for side, (dst, D, ld) in enumerate(((X_all, self.Dx, self.ldX), (Y_all, self.Dy, self.ldY))):
+            buf = stage[:chunk * ld].view(chunk, ld)
+            buf.zero_()                                              # the pad columns
+            sent = 0
+            for filled in _fill_chunks([h[side] for h in self._host], buf, D):
+                dst[sent:sent + filled].copy_(buf[:filled], non_blocking=True)
+                torch.cuda.current_stream(device).synchronize()      # one staging buffer: drained before it is refilled
+                sent += filled
+        self.stats = [torch.from_numpy(v.copy()).to(device) for v in self._stats_host]
+        if self.dsrc_host is not None:
+            self.dsrc, self.dwin = torch.from_numpy(self.dsrc_host).to(device), torch.from_numpy(self.dwin_host).to(device)
+        self.X_all, self.Y_all, self.device = X_all, Y_all, device
+        self._host = None
+        return self
+
+
+class ResidentLoader(object):
+    """Batches of a device-resident corpus (``hp.resident_corpus``): the raw corpus is uploaded once (``ResidentCorpus``), each epoch
+    uploads one small table (``plan_epoch``), and every batch is ONE gt_op_assemble_batch launch on the current stream -- scaling,
+    padding, the length sort, the generator's noise and its concatenation, the static features and the mask, bit for bit what
+    ``DevicePrefetcher(DataLoader(dataset))`` + train_loop compute on the host and in launches of their own.  No host copy, host
+    arithmetic on frames or synchronisation per batch.  Yields ``DeviceBatch``es with ``generator_input``, ``y_static`` and ``mask``
+    set; ``x`` is the prefix view ``generator_input[:, :, :Dx]``.
+
+    Noise: Philox4x32-10 keyed by (``hp.generator_noise_seed`` low word, draw counter); the draw counter starts at ``first_draw`` and
+    advances once per epoch (per ``__iter__``); the counters are (corpus utterance index, t * ceil(nz / 4) + column group of 4), so a
+    frame's noise depends on its utterance, not on the utterance's place in the batch (data_kernels.hip.h)."""
+
+    def __init__(self, dataset, batch_size, shuffle, hp, batch_sampler=None, device="cuda", first_draw=0):
+        from torch.utils import data as data_utils
+        from .multistream import static_columns
+        self.dataset, self.hp, self.device = dataset, hp, device
+        self.corpus = dataset if isinstance(dataset, ResidentCorpus) else ResidentCorpus(dataset, device=None)
+        if isinstance(dataset, ResidentCorpus):
+            self.dataset = dataset.dataset
+        n = len(self.corpus.lengths)
+        if batch_sampler is None:
+            sampler = data_utils.RandomSampler(range(n)) if shuffle else data_utils.SequentialSampler(range(n))
+            batch_sampler = data_utils.BatchSampler(sampler, int(batch_size), drop_last=False)
+        self.batch_sampler = batch_sampler
+        self.nz = int(hp.generator_noise_dim) if getattr(hp, "generator_add_noise", False) else 0
+        self.seed = int(getattr(hp, "generator_noise_seed", 0))
+        self.draws = int(first_draw)
+        self.scol_host = np.array(static_columns(len(hp.windows), hp.stream_sizes, hp.has_dynamic_features, None, self.corpus.Dy), dtype=np.int32)
+        if len(self.scol_host) and int(self.scol_host.max()) >= self.corpus.Dy:
+            raise RuntimeError("You probably have specified wrong dimention params.")
+        self._scol = None
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def plan(self):
+        """The host plan of the next epoch (draws the sampler): see ``plan_epoch``."""
+        return plan_epoch(self.corpus.offsets, self.corpus.lengths, self.batch_sampler)
+
+    def _case(self, table, n_slots):
+        from . import _lib as L
+        c, k = self.corpus, L.AssembleCase()
+        k.Dx, k.Dy, k.nz, k.Ds = c.Dx, c.Dy, self.nz, len(self.scol_host)
+        k.ldX, k.ldY = c.ldX, c.ldY
+        k.x_kind, k.y_kind, k.stats_f64 = c.x_kind, c.y_kind, c.stats_f64
+        k.key0, k.key1 = self.seed & 0xFFFFFFFF, self.draws & 0xFFFFFFFF
+        k.F, k.n_slots = c.F, n_slots
+        k.X_all, k.Y_all = c.X_all.data_ptr(), c.Y_all.data_ptr()
+        k.x_a, k.x_b, k.y_a, k.y_b = [t.data_ptr() for t in c.stats]
+        k.table, k.scol = table.data_ptr(), self._scol.data_ptr()
+        if c.windows is not None:
+            k.n_windows = len(c.windows)
+            for w, coef in enumerate(c.windows):
+                k.win_len[w] = len(coef)
+                for j, v in enumerate(coef):
+                    k.coef[w][j] = float(v)
+            k.dsrc, k.dwin = c.dsrc.data_ptr(), c.dwin.data_ptr()
+        return k
+
+    def begin_epoch(self):
+        """Uploads the corpus if it is not resident yet, plans the next epoch on the host and uploads its table: ``(case, plan)`` for
+        ``assemble``.  Advances the draw counter."""
+        c = self.corpus.upload(self.device)
+        if self._scol is None:
+            self._scol = torch.from_numpy(self.scol_host).to(c.device) if len(self.scol_host) else torch.zeros(1, dtype=torch.int32, device=c.device)
+        table_host, plan = self.plan()
+        if not plan:
+            return None, plan
+        table = torch.from_numpy(table_host).pin_memory().to(c.device, non_blocking=True)      # the epoch's one upload
+        case = self._case(table, len(table_host))
+        case._table = table                   # the launches read it: it lives as long as the case
+        self.draws += 1
+        return case, plan
+
+    def assemble(self, case, first, B, T, out=None):
+        """One batch of the epoch in one launch on the current stream: ``(gi (B, T, ld_gi), y, y_static, mask (B, T, 1), lengths)``.
+        ``out``: the five buffers to write instead of fresh ones (dense, gi on its pitch ``roundup(Dx + nz, 4)``)."""
+        import ctypes as C
+        from . import _lib as L
+        c = self.corpus
+        Dx, nz, Dy, Ds = c.Dx, self.nz, c.Dy, len(self.scol_host)
+        ld_gi = (Dx + nz + 3) // 4 * 4
+        if out is None:
+            kw = dict(device=c.device, dtype=torch.float32)
+            out = (torch.empty(B, T, ld_gi, **kw), torch.empty(B, T, Dy, **kw), torch.empty(B, T, Ds, **kw), torch.empty(B, T, 1, **kw),
+                   torch.empty(B, device=c.device, dtype=torch.int64))
+        gi, y, ys, mask, lengths = out
+        for t, shape in ((gi, (B, T, ld_gi)), (y, (B, T, Dy)), (ys, (B, T, Ds)), (mask, (B, T, 1)), (lengths, (B,))):
+            if tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("ResidentLoader.assemble: an output buffer of shape %s where %s is needed" % (tuple(t.shape), shape))
+        case.B, case.T, case.first_slot = B, T, first
+        case.ld_gi, case.ld_y, case.ld_ys = ld_gi, Dy, Ds
+        case.gi, case.y, case.y_static = gi.data_ptr(), y.data_ptr(), ys.data_ptr() if Ds else None
+        case.mask, case.lengths = mask.data_ptr(), lengths.data_ptr()
+        L.check(L.lib.gt_op_assemble_batch(C.byref(case), L.current_stream()))
+        return out
+
+    def __iter__(self):
+        case, plan = self.begin_epoch()
+        Dx, nz = self.corpus.Dx, self.nz
+        for first, B, T, cpu_lengths in plan:
+            gi, y, ys, mask, lengths = self.assemble(case, first, B, T)
+            g = gi if gi.size(-1) == Dx + nz else gi[:, :, :Dx + nz]
+            yield DeviceBatch(gi[:, :, :Dx] if gi.size(-1) != Dx else gi, y, lengths, cpu_lengths, None, generator_input=g, y_static=ys, mask=mask)

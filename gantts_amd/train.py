@@ -249,8 +249,10 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     through ``DevicePrefetcher`` (pinned, double-buffered H2D overlapped with the previous step), the
     MLPG matrix is cached per T on the device instead of being rebuilt and uploaded every batch
     (train.py:509-513) -- or, with ``hp.mlpg_device_band``, never formed: the band is built on the device from
-    ``hp.windows`` -- and the distortion metrics come from one fused reduction."""
-    from .data import DevicePrefetcher
+    ``hp.windows`` -- and the distortion metrics come from one fused reduction.  A ``data.ResidentLoader`` (``hp.resident_corpus``) is
+    iterated as it is: its batches are assembled on the device in one launch each and bring the generator input (noise included), the
+    static features and the mask with them."""
+    from .data import DevicePrefetcher, ResidentLoader
     from .multistream import get_static_features
     from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
     from .seqloss import sequence_mask
@@ -301,20 +303,29 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
             # x is staged on a 16-byte row pitch (gt_set_x_pitch): the layout the engine reads with 16-byte loads in every product --
             # free here, the batch is being copied anyway, and every network accepts it (others get a dense copy inside the engine);
             # hp.pitch_x = False restores dense rows
-            for batch in DevicePrefetcher(dataset_loaders[phase], pitch_x=bool(getattr(hp, "pitch_x", True))):
+            # hp.resident_corpus: a ResidentLoader assembles each batch on the device in one launch and hands over the generator input
+            # (noise included), the static features and the mask with it; nothing is staged, drawn, concatenated or gathered here
+            loader = dataset_loaders[phase]
+            batches = loader if isinstance(loader, ResidentLoader) else DevicePrefetcher(loader, pitch_x=bool(getattr(hp, "pitch_x", True)))
+            for batch in batches:
                 x, y, sorted_lengths, cpu_sorted_lengths = batch.x, batch.y, batch.lengths, batch.cpu_lengths
                 max_len = batch.max_len
+                assembled = batch.generator_input is not None
                 # generator noise z ~ U[0,1) (train.py:504-506), drawn on the device
                 z = torch.rand(x.size(0), max_len, hp.generator_noise_dim, device=x.device, generator=noise_gen) \
-                    if hp.generator_add_noise else None
+                    if hp.generator_add_noise and not assembled else None
                 R = mlpg_matrix(hp.windows, max_len) if has_dynamic else None
-                y_static = get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
+                y_static = batch.y_static if batch.y_static is not None else \
+                    get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
                 total_num_frames += float(sum(cpu_sorted_lengths))
-                mask = sequence_mask(sorted_lengths).unsqueeze(-1)
+                mask = batch.mask if batch.mask is not None else sequence_mask(sorted_lengths).unsqueeze(-1)
                 optimizer_g.zero_grad()
                 optimizer_d.zero_grad()
 
-                generator_input = torch.cat((x, z), -1) if z is not None else x
+                if assembled:
+                    generator_input = batch.generator_input
+                else:
+                    generator_input = torch.cat((x, z), -1) if z is not None else x
                 y_hat, y_hat_static = apply_generator(model_g, generator_input, R, cpu_sorted_lengths)
                 assert x.size(1) == y_hat.size(1)
 

@@ -974,6 +974,58 @@ int gt_op_mlpg_var(const gt_mlpg_var_case* c, void* stream);
 #define GT_MLPG_VAR_PATH_SLOTS 3
 int gt_mlpg_var_path_counts(int64_t* counts, int n);
 
+/* Batch assembly from a device-resident corpus (gantts_amd/csrc/data_kernels.hip.h; gantts_amd/data.py: ResidentLoader): ONE launch
+ * writes what the training loop derives from a batch -- TTSDataset / VCDataset.__getitem__, collate_fn, the length sort, torch.rand
+ * + torch.cat, get_static_features and sequence_mask (train.py:111-159, 494-519) -- bit for bit as the host pipeline computes it.
+ * Stateless; every pointer is caller-owned device memory; no synchronisation.
+ *   X_all [F][ldX], Y_all [F][ldY]   the un-normalised utterances back to back; 16-byte aligned, ldX and ldY multiples of 4
+ *   x_kind / y_kind   GT_SCALE_NONE, GT_SCALE_MINMAX (v * a[c] + b[c]: a = scale_, b = min_) or GT_SCALE_MEANVAR ((v - a[c]) / b[c]:
+ *            a = mean, b = std); x_a, x_b [Dx] are float64 when stats_f64 & 1, y_a, y_b [Dy] when stats_f64 & 2, float32 otherwise.
+ *            The arithmetic of a side runs in its statistics' dtype, each operation rounded on its own (no FMA, correctly rounded division), one rounding to float32.
+ *   table    [n_slots][3] int64: first frame, length, corpus utterance index of every batch slot of the epoch; sequence b of this
+ *            call is slot first_slot + b.  A slot that does not lie inside [0, F) yields an empty sequence; a length above T is cut.
+ *   gi       (B, T, Dx + nz) on pitch ld_gi (a multiple of 4, 16-byte aligned): columns [0, Dx) the scaled x, 0 at frames
+ *            t >= length; [Dx, Dx + nz) noise z in [0, 1) on every frame; pad columns 0.  z[t][j] of utterance u is word j & 3 of
+ *            Philox4x32-10(counter = (u, t * ceil(nz / 4) + (j >> 2)), key = (key0, key1)), (word >> 8) * 2^-24.
+ *   y        (B, T, Dy) on pitch ld_y;  y_static (B, T, Ds) on pitch ld_ys: columns scol[j] (device int32 [Ds]) of that y;
+ *            mask (B, T) float 0 / 1;  lengths (B) int64.  Any output may be null.  Padded frames and pad columns are 0.
+ *   dsrc, dwin, n_windows, win_len, coef   delta recomputation (gantts/multistream.py:15-30), both lists null for none: column c of y
+ *            with dwin[c] = w >= 0 is sum_k coef[w][k] * scaled(Y)[t + k - (win_len[w] - 1) / 2][dsrc[c]] over the frames of the
+ *            UTTERANCE (zeros beyond its edges), accumulated in double and rounded once; dwin[c] < 0 is the plain scaled column.
+ * A malformed case (null corpus, sizes < 1, a pitch below its width or not a multiple of 4 where 16-byte access needs it, widths
+ * whose statistics do not fit the workgroup's LDS) returns GT_ERR_INVALID before the launch. */
+#define GT_SCALE_NONE 0
+#define GT_SCALE_MINMAX 1
+#define GT_SCALE_MEANVAR 2
+#define GT_ASSEMBLE_MAX_WINDOWS 4
+#define GT_ASSEMBLE_MAX_TAPS 9
+typedef struct gt_assemble_case {
+  int32_t B, T, Dx, Dy, nz, Ds;
+  int32_t ldX, ldY, ld_gi, ld_y, ld_ys;
+  int32_t x_kind, y_kind, stats_f64, n_windows;
+  uint32_t key0, key1;
+  int32_t win_len[GT_ASSEMBLE_MAX_WINDOWS];
+  int32_t pad_;
+  int64_t F, n_slots, first_slot;
+  double coef[GT_ASSEMBLE_MAX_WINDOWS][GT_ASSEMBLE_MAX_TAPS];
+  const float* X_all;
+  const float* Y_all;
+  const void* x_a;
+  const void* x_b;
+  const void* y_a;
+  const void* y_b;
+  const int64_t* table;
+  const int32_t* scol;
+  const int32_t* dsrc;
+  const int32_t* dwin;
+  float* gi;
+  float* y;
+  float* y_static;
+  float* mask;
+  int64_t* lengths;
+} gt_assemble_case;
+int gt_op_assemble_batch(const gt_assemble_case* c, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

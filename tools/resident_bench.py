@@ -1,0 +1,177 @@
+#!/usr/bin/env python
+"""Measurements of the device-resident batch path (gantts_amd.data.ResidentLoader, gt_op_assemble_batch) at cfg2 size; needs a GPU.
+
+1. The assembly kernel: B=32, T=512 (all utterances 512 frames), 425 (+0 noise) / 187 columns, a corpus larger than the 256 MB
+   Infinity Cache, batches drawn at random, output buffers rotated; HIP events around LAUNCHES launches.  Reported: the time, the rate
+   algorithmic bytes / time (B T (428 + 188) 4 read + B T (428 + 187 + 63 + 1) 4 written), and -- in the same process -- a device
+   copy moving the same number of bytes (half read, half written; buffers rotated the same way) and the ratio of the two.
+2. Batches per second on the same corpus through DevicePrefetcher(DataLoader) -- collate_fn and hp.device_collate -- and through
+   ResidentLoader: each loader alone (a device synchronise at the end), then each inside train_loop's G+D step (one epoch:
+   train phase + a short test phase, host clock around the call, which ends in the epoch's read-back).
+
+    python tools/resident_bench.py [--utterances 1024] [--workers 1] [--out FILE]
+
+Prints one JSON line (and writes it to --out)."""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+B, T, DX, DY = 32, 512, 425, 187
+G_SPEC = dict(in_dim=425, out_dim=187, num_hidden=3, hidden_dim=512, dropout=0.5, last_sigmoid=False)
+D_SPEC = dict(in_dim=483, out_dim=1, num_hidden=3, hidden_dim=256, dropout=0.5, last_sigmoid=True)
+
+
+def make_hp(workers):
+    from gantts_amd import hparams
+    hp = types.SimpleNamespace(**hparams.tts_acoustic.values())
+    hp.batch_size, hp.num_workers, hp.nepoch, hp.lr_decay_schedule = B, workers, 1, False
+    hp.generator_add_noise = False
+    return hp
+
+
+def make_corpus(n, seed=0):
+    """n utterances of T frames; float32 min / max of x, float64 mean / std of y (what minmax() and meanvar() return)."""
+    rng = np.random.default_rng(seed)
+    X = [rng.random((T, DX), dtype=np.float32) for _ in range(n)]
+    Y = [rng.standard_normal((T, DY), dtype=np.float32) for _ in range(n)]
+    return X, Y, np.zeros(DX, np.float32), np.ones(DX, np.float32), rng.standard_normal(DY) * 0.3, 0.5 + rng.random(DY)
+
+
+def kernel_time(ds, hp, launches, nbuf=8):
+    import torch
+    from gantts_amd import data as D
+    loader = D.ResidentLoader(ds, B, True, hp)
+    Ds = len(loader.scol_host)
+    bufs = [(torch.empty(B, T, 428, device="cuda"), torch.empty(B, T, DY, device="cuda"), torch.empty(B, T, Ds, device="cuda"),
+             torch.empty(B, T, 1, device="cuda"), torch.empty(B, device="cuda", dtype=torch.int64)) for _ in range(nbuf)]
+    nbytes = B * T * (428 + 188) * 4 + B * T * (428 + DY + Ds + 1) * 4
+    half = nbytes // 2 // 16 * 4                                       # floats: the copy reads `half` floats and writes as many
+    src = [torch.rand(half, device="cuda") for _ in range(nbuf)]
+    dst = [torch.empty(half, device="cuda") for _ in range(nbuf)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+
+    case, plan = loader.begin_epoch()                                  # one random epoch; its full batches are launched in turn
+    plan = [p for p in plan if p[1] == B]
+    busy = torch.rand(8192, 8192, device="cuda")
+
+    def occupy():                                                      # keeps the device busy while the host enqueues the window,
+        for _ in range(2):                                             # so that the events bracket back-to-back launches
+            torch.mm(busy, busy)
+
+    def run_kernel(n, record):
+        occupy()
+        if record:
+            ev[0].record()
+        for k in range(n):
+            first, b, t, _ = plan[k % len(plan)]
+            loader.assemble(case, first, b, t, out=bufs[k % nbuf])
+        if record:
+            ev[1].record()
+
+    def run_copy(n, record):
+        occupy()
+        if record:
+            ev[2].record()
+        for k in range(n):
+            dst[k % nbuf].copy_(src[k % nbuf])
+        if record:
+            ev[3].record()
+
+    res = {}
+    for rep in range(3):                                               # alternating; the first round is the warm-up
+        run_kernel(launches, True)
+        run_copy(launches, True)
+        torch.cuda.synchronize()
+        res = {"kernel_us": ev[0].elapsed_time(ev[1]) * 1e3 / launches, "copy_us": ev[2].elapsed_time(ev[3]) * 1e3 / launches}
+        res["round_%d" % rep] = [round(res["kernel_us"], 2), round(res["copy_us"], 2)]
+    res.update(algorithmic_bytes=nbytes, launches=launches, kernel_TBps=nbytes / res["kernel_us"] * 1e-6,
+               copy_TBps=2 * half * 4 / res["copy_us"] * 1e-6)
+    res["kernel_over_copy_rate"] = res["kernel_TBps"] / res["copy_TBps"]
+    return res
+
+
+def loader_alone(make_batches, n_batches):
+    """Batches per second of an iterable of DeviceBatches, nothing else on the device; the first epoch warms up."""
+    import torch
+    out = None
+    for rep in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = 0
+        for batch in make_batches():
+            n += 1
+        torch.cuda.synchronize()
+        out = n / (time.perf_counter() - t0)
+        assert n == n_batches
+    return out
+
+
+def with_step(loaders, hp):
+    """Batches per second of train_loop's epoch (train + test phase) on these loaders; the first epoch warms up."""
+    import torch
+    import gantts_amd.train as TR
+    from gantts_amd import models, optim
+    TR.hp = hp
+    torch.manual_seed(0)
+    mg, md = models.MLP(**G_SPEC).cuda(), models.MLP(**D_SPEC).cuda()
+    og = optim.Adagrad(mg.parameters(), lr=0.01, weight_decay=1e-7)
+    od = optim.Adagrad(md.parameters(), lr=0.01, weight_decay=1e-7)
+    n = len(loaders["train"]) + len(loaders["test"])
+    out = None
+    for rep in range(2):
+        TR.global_epoch = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        TR.train_loop((mg, md), (og, od), loaders, w_d=1.0, mse_w=0.0, mge_w=1.0)
+        torch.cuda.synchronize()
+        out = n / (time.perf_counter() - t0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--utterances", type=int, default=1024, help="utterances of 512 frames (1024: a 1.3 GB corpus)")
+    ap.add_argument("--test-utterances", type=int, default=64)
+    ap.add_argument("--workers", type=int, default=1, help="DataLoader workers of the host pipeline (hp.num_workers)")
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("resident_bench: needs a GPU (no CPU path)")
+    from gantts_amd import data as D
+    hp = make_hp(a.workers)
+    X, Y, lo, hi, mean, std = make_corpus(a.utterances)
+    Xs = {"train": X, "test": X[:a.test_utterances]}
+    Ys = {"train": Y, "test": Y[:a.test_utterances]}
+    res = {"B": B, "T": T, "utterances": a.utterances, "corpus_bytes": a.utterances * T * (428 + 188) * 4, "workers": a.workers}
+    ds = D.TTSDataset(X, Y, lo, hi, mean, std, hp=hp)
+    res["kernel"] = kernel_time(ds, hp, a.launches)
+    n_train = (a.utterances + B - 1) // B
+    for tag, flags in (("host_collate", {}), ("host_device_collate", {"device_collate": True}), ("resident", {"resident_corpus": True})):
+        for k in ("device_collate", "resident_corpus"):
+            setattr(hp, k, bool(flags.get(k, False)))
+        loaders = D.get_tts_data_loaders(Xs, Ys, lo, hi, mean, std, hp)
+        train = loaders["train"]
+        if flags.get("resident_corpus"):
+            alone = loader_alone(lambda: iter(train), n_train)
+        else:
+            alone = loader_alone(lambda: iter(D.DevicePrefetcher(train, pitch_x=True)), n_train)
+        res[tag] = {"loader_alone_batches_per_s": alone, "with_step_batches_per_s": with_step(loaders, hp)}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
