@@ -50,6 +50,7 @@ MLPG_MAX_WINDOW_SPAN = 32               # GT_MLPG_MAX_WINDOW_SPAN
 COMM_ID_BYTES = 128
 SCALE_NONE, SCALE_MINMAX, SCALE_MEANVAR = 0, 1, 2      # AssembleCase.x_kind / y_kind
 ASSEMBLE_MAX_WINDOWS, ASSEMBLE_MAX_TAPS = 4, 9
+CORPUS_STATS_SLAB, CORPUS_STATS_FANIN = 256, 64        # GT_CORPUS_STATS_SLAB / _FANIN: rows per workgroup, partial chains per column of the merge
 
 
 class StreamConfig(C.Structure):
@@ -187,6 +188,12 @@ class AssembleCase(C.Structure):
                                              "y_static", "mask", "lengths")])
 
 
+class CorpusStatsCase(C.Structure):
+    _fields_ = ([("D", C.c_int32), ("ld", C.c_int32)] + [(n, C.c_int64) for n in ("F", "n_seg", "prior_count")]
+                + [(n, C.c_void_p) for n in ("A", "seg", "prior_mean", "prior_var", "workspace")] + [("workspace_bytes", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("out_min", "out_max", "out_count", "out_mean", "out_m2")])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -257,6 +264,8 @@ SIGNATURES = {
     "gt_op_mlpg_var": (_I, [C.POINTER(MlpgVarCase), _P]),
     "gt_mlpg_var_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_assemble_batch": (_I, [C.POINTER(AssembleCase), _P]),
+    "gt_corpus_stats_workspace_bytes": (_L, [_L, C.c_int32]),
+    "gt_op_corpus_stats": (_I, [C.POINTER(CorpusStatsCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),
     "gt_comm_unique_id": (_I, [_P]),
     "gt_comm_init": (_I, [_P, _I, _I, _P]),

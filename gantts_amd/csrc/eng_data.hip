@@ -1,10 +1,13 @@
-// libgantts_hip.so -- the data path's stand-alone operator: gt_op_assemble_batch (one training batch out of a device-resident corpus)
+// libgantts_hip.so -- the data path's stand-alone operators: gt_op_assemble_batch (one training batch out of a device-resident corpus)
+// and gt_op_corpus_stats (the normalisation statistics of one side of that corpus)
 #include "engine_internal.hip.h"
 #include "data_kernels.hip.h"
+#include "corpus_stats_kernels.hip.h"
 
 using namespace gt;
 
 static_assert(ASM_MAX_WINDOWS == GT_ASSEMBLE_MAX_WINDOWS && ASM_MAX_TAPS == GT_ASSEMBLE_MAX_TAPS, "window table of the kernel and of the ABI");
+static_assert(CS_SLAB == GT_CORPUS_STATS_SLAB && CS_FANIN == GT_CORPUS_STATS_FANIN, "slab and fan-in of the kernels and of the ABI");
 
 template <typename SX, typename SY, bool DELTA>
 static int launch_assemble(const AssembleArgs& a, hipStream_t s) {
@@ -78,4 +81,46 @@ extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
     case 6: return launch_assemble<double, double, false>(a, s);
     default: return launch_assemble<double, double, true>(a, s);
   }
+}
+
+extern "C" int64_t gt_corpus_stats_workspace_bytes(int64_t F, int32_t D) {
+  if (F < 0 || D < 1) return 0;
+  const size_t n = corpus_stats_ws_bytes(F, (D + 3) / 4 * 4);
+  return (int64_t)(n ? n : 16);
+}
+
+extern "C" int gt_op_corpus_stats(const gt_corpus_stats_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "corpus_stats: null case");
+  if (c->D < 1 || c->F < 0 || c->n_seg < 0 || c->prior_count < 0)
+    return fail(GT_ERR_INVALID, "corpus_stats: bad sizes D=%d F=%lld n_seg=%lld prior_count=%lld", c->D, (long long)c->F, (long long)c->n_seg,
+                (long long)c->prior_count);
+  if (c->ld != (c->D + 3) / 4 * 4 || (c->F > 0 && (!c->A || !aligned16(c->A))))
+    return fail(GT_ERR_INVALID, "corpus_stats: the corpus rows must sit on the 16-byte pitch roundup(D, 4) (ld=%d for %d columns)", c->ld, c->D);
+  if (c->n_seg > 0 && !c->seg) return fail(GT_ERR_INVALID, "corpus_stats: null segment table");
+  if (!c->out_min || !c->out_max || !c->out_count || !c->out_mean || !c->out_m2) return fail(GT_ERR_INVALID, "corpus_stats: null result");
+  const long n_part = corpus_stats_parts(c->F);
+  if (n_part > (1L << 31) - 1) return fail(GT_ERR_INVALID, "corpus_stats: F = %lld rows", (long long)c->F);
+  const size_t need = corpus_stats_ws_bytes(c->F, c->ld);
+  if (need && (!c->workspace || !aligned16(c->workspace) || c->workspace_bytes < (int64_t)need))
+    return fail(GT_ERR_INVALID, "corpus_stats: a 16-byte aligned workspace of %zu bytes is needed (gt_corpus_stats_workspace_bytes), got %lld", need,
+                (long long)c->workspace_bytes);
+  CorpusStatsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.D = c->D; a.ld = c->ld;
+  while ((1 << a.lpr_log2) < (a.ld >> 2) && a.lpr_log2 < 6) ++a.lpr_log2;
+  a.F = c->F; a.n_seg = c->n_seg; a.n_part = n_part;
+  a.prior_count = (double)c->prior_count;
+  a.A = c->A; a.seg = (const long*)c->seg;
+  a.prior_mean = c->prior_mean; a.prior_var = c->prior_var;
+  a.part_d = (double*)c->workspace;
+  a.part_f = (float*)((char*)c->workspace + (size_t)n_part * 3 * a.ld * sizeof(double));
+  a.out_min = c->out_min; a.out_max = c->out_max; a.out_count = c->out_count; a.out_mean = c->out_mean; a.out_m2 = c->out_m2;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_part > 0) {
+    hipLaunchKernelGGL(corpus_stats_slab_kernel, dim3((unsigned)n_part), dim3(CS_THREADS), 0, s, a);
+    LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(corpus_stats_merge_kernel, dim3(cdiv(a.D, CS_MERGE_COLS)), dim3(CS_MERGE_THREADS), 0, s, a);
+  LAUNCH_CHECK();
+  return GT_OK;
 }

@@ -23,6 +23,9 @@ while step k runs on the compute stream, so the step never waits for PCIe.
 Device-resident corpus (``hp.resident_corpus``): ``ResidentCorpus`` uploads the raw utterances once, ``ResidentLoader`` plans each epoch
 on the host (``plan_epoch``), uploads one small table and produces every batch -- scaled, padded, sorted, with the generator's noise, the
 static features and the mask -- by ONE launch (gt_op_assemble_batch), bit for bit what the host pipeline above computes.
+``ResidentCorpus.from_arrays`` takes the raw utterances without statistics, ``corpus.minmax`` / ``corpus.meanvar`` compute them on the
+device in one pass per side (gt_op_corpus_stats), and ``resident_tts_loaders`` / ``resident_vc_loaders`` go from the raw arrays to the
+loaders (train.py:718-770) without host arithmetic on frames.
 """
 import os
 from os.path import join, splitext
@@ -453,14 +456,40 @@ class ResidentCorpus(object):
     before anything is allocated: there is no fallback to the host pipeline."""
 
     def __init__(self, dataset, device="cuda", chunk_frames=1 << 16):
-        from . import _lib as L
-        self.dataset, self.chunk_frames = dataset, int(chunk_frames)
         n = len(dataset)
         if n < 1:
             raise ValueError("ResidentCorpus: empty dataset")
+        self.chunk_frames = int(chunk_frames)
+        self._take((dataset.X[i], dataset.Y[i]) for i in range(n))
+        self._attach(dataset)
+        if device is not None:
+            self.upload(device)
+
+    @classmethod
+    def from_arrays(cls, X, Y, device="cuda", chunk_frames=1 << 16):
+        """A corpus of the raw utterances ``X[i]``, ``Y[i]`` (``(T_i, D)`` float32) that carries no statistics yet: the same validation,
+        refusal and upload as ``ResidentCorpus(dataset)``.  ``minmax`` / ``meanvar`` compute the statistics on the device; a
+        ``ResidentLoader`` takes the corpus once ``attach_statistics(dataset)`` has named the dataset that carries them."""
+        n = len(X)
+        if n < 1:
+            raise ValueError("ResidentCorpus: empty dataset")
+        if len(Y) != n:
+            raise ValueError("ResidentCorpus: %d input and %d output utterances" % (n, len(Y)))
+        self = cls.__new__(cls)
+        self.chunk_frames = int(chunk_frames)
+        self._take((X[i], Y[i]) for i in range(n))
+        self.dataset = self._stats_host = None
+        self.x_kind = self.y_kind = self.stats_f64 = None
+        self.windows, self.dsrc_host, self.dwin_host = None, None, None
+        if device is not None:
+            self.upload(device)
+        return self
+
+    def _take(self, pairs):
+        """Validates the utterances and lays the corpus out (host side): lengths, offsets, widths, pitches."""
         self._host = []
-        for i in range(n):
-            x, y = np.asarray(dataset.X[i]), np.asarray(dataset.Y[i])
+        for i, (x, y) in enumerate(pairs):
+            x, y = np.asarray(x), np.asarray(y)
             if x.dtype != np.float32 or y.dtype != np.float32 or x.ndim != 2 or y.ndim != 2:
                 raise TypeError("ResidentCorpus: utterance %d is %s %s / %s %s; (T, D) float32 arrays only" % (i, x.dtype, x.shape, y.dtype, y.shape))
             if len(x) != len(y):
@@ -474,7 +503,13 @@ class ResidentCorpus(object):
         self.F = int(self.lengths.sum())
         self.ldX, self.ldY = (self.Dx + 3) // 4 * 4, (self.Dy + 3) // 4 * 4
         self.nbytes = self.F * (self.ldX + self.ldY) * 4
-        # the normalisation each __getitem__ applies (train.py:96-135), as (kind, a, b) per side
+        self.X_all = self.Y_all = self.stats = self.dsrc = self.dwin = None
+        self._stats_ws = None
+
+    def _attach(self, dataset):
+        """The normalisation each ``dataset.__getitem__`` applies (train.py:96-135), as (kind, a, b) per side, and its delta plan."""
+        from . import _lib as L
+        self.dataset = dataset
         if hasattr(dataset, "X_data_scale"):         # TTSDataset: min-max x, mean-variance y
             self.x_kind, xa, xb = L.SCALE_MINMAX, dataset.X_data_scale, dataset.X_data_min
             self.y_kind, ya, yb = L.SCALE_MEANVAR, dataset.Y_data_mean, dataset.Y_data_std
@@ -496,9 +531,18 @@ class ResidentCorpus(object):
         dhp = getattr(dataset, "hp", None)
         if hasattr(dataset, "X_data_scale") and dhp is not None and getattr(dhp, "recompute_delta_features", False):
             self._plan_deltas(dhp)
-        self.X_all = self.Y_all = self.stats = self.dsrc = self.dwin = None
-        if device is not None:
-            self.upload(device)
+
+    def attach_statistics(self, dataset):
+        """Names the ``TTSDataset`` / ``VCDataset`` over this corpus' utterances whose statistics the batches are scaled with (a corpus
+        made by ``from_arrays``); the raw frames stay where they are -- nothing is uploaded again but the statistics themselves."""
+        if self.dataset is not None:
+            raise ValueError("ResidentCorpus: statistics are attached already")
+        if len(dataset) != len(self.lengths):
+            raise ValueError("ResidentCorpus: a dataset of %d utterances for a corpus of %d" % (len(dataset), len(self.lengths)))
+        self._attach(dataset)
+        if self.X_all is not None:
+            self._upload_stats(self.device)
+        return self
 
     def _plan_deltas(self, hp):
         from . import _lib as L
@@ -546,12 +590,81 @@ class ResidentCorpus(object):
                 dst[sent:sent + filled].copy_(buf[:filled], non_blocking=True)
                 torch.cuda.current_stream(device).synchronize()      # one staging buffer: drained before it is refilled
                 sent += filled
-        self.stats = [torch.from_numpy(v.copy()).to(device) for v in self._stats_host]
-        if self.dsrc_host is not None:
-            self.dsrc, self.dwin = torch.from_numpy(self.dsrc_host).to(device), torch.from_numpy(self.dwin_host).to(device)
+        if self._stats_host is not None:
+            self._upload_stats(device)
         self.X_all, self.Y_all, self.device = X_all, Y_all, device
         self._host = None
         return self
+
+    def _upload_stats(self, device):
+        self.stats = [torch.from_numpy(v.copy()).to(device) for v in self._stats_host]
+        if self.dsrc_host is not None:
+            self.dsrc, self.dwin = torch.from_numpy(self.dsrc_host).to(device), torch.from_numpy(self.dwin_host).to(device)
+
+    # ---- statistics on the device (gt_op_corpus_stats) ------------------------------------------------------------------------------
+    def segments(self, lengths=None):
+        """The valid rows as gt_op_corpus_stats reads them: int64 ``[n][2]`` = (first frame, valid frame count) per utterance, utterance
+        ``idx`` cut to ``lengths[idx]`` as ``x[:lengths[idx]]`` cuts it on the host (a negative length counts from the end)."""
+        n = len(self.lengths)
+        valid = self.lengths.copy()
+        if lengths is not None:
+            valid = np.array([len(range(*slice(None, int(lengths[i])).indices(int(self.lengths[i])))) for i in range(n)], dtype=np.int64)
+        return np.ascontiguousarray(np.stack((self.offsets, valid), axis=1).astype(np.int64))
+
+    def stats_case(self, side, lengths=None, prior_mean=0.0, prior_var=0.0, prior_count=0):
+        """The ``gt_corpus_stats_case`` of one pass over side "x" or "y" and its result buffers ``(out_f (2, D) float32: min, max;
+        out_d (3, D) float64: count, mean, M2)``; the case keeps the device buffers it points to alive."""
+        from . import _lib as L
+        if side not in ("x", "y"):
+            raise ValueError("ResidentCorpus: side is \"x\" or \"y\", not %r" % (side,))
+        if self.X_all is None:
+            raise RuntimeError("ResidentCorpus: the corpus is not on the device; upload() it first (the statistics have no host path here)")
+        A, D, ld = (self.X_all, self.Dx, self.ldX) if side == "x" else (self.Y_all, self.Dy, self.ldY)
+        dev = self.device
+        seg = torch.from_numpy(self.segments(lengths)).to(dev)
+        nbytes = int(L.lib.gt_corpus_stats_workspace_bytes(self.F, D))
+        if self._stats_ws is None or self._stats_ws.numel() * 8 < nbytes:
+            self._stats_ws = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.float64)
+        out_f, out_d = torch.empty(2, D, device=dev, dtype=torch.float32), torch.empty(3, D, device=dev, dtype=torch.float64)
+        k = L.CorpusStatsCase()
+        k.D, k.ld, k.F, k.n_seg, k.prior_count = D, ld, self.F, len(seg), int(prior_count)
+        k.A, k.seg = A.data_ptr(), seg.data_ptr()
+        prior = None
+        if int(prior_count) > 0 or np.any(np.asarray(prior_mean) != 0.0):
+            prior = torch.from_numpy(np.stack([np.broadcast_to(np.asarray(v, dtype=np.float64), (D,)) for v in (prior_mean, prior_var)])).to(dev)
+            k.prior_mean, k.prior_var = prior[0].data_ptr(), prior[1].data_ptr()
+        k.workspace, k.workspace_bytes = self._stats_ws.data_ptr(), self._stats_ws.numel() * 8
+        k.out_min, k.out_max = out_f[0].data_ptr(), out_f[1].data_ptr()
+        k.out_count, k.out_mean, k.out_m2 = out_d[0].data_ptr(), out_d[1].data_ptr(), out_d[2].data_ptr()
+        k._alive = (seg, prior, self._stats_ws, out_f, out_d)
+        return k, out_f, out_d
+
+    def _device_stats(self, side, lengths, prior_mean, prior_var, prior_count):
+        """One gt_op_corpus_stats pass over side "x" or "y": ``(min, max, count, mean, M2)`` as numpy arrays of shape ``(D,)``."""
+        import ctypes as C
+        from . import _lib as L
+        k, out_f, out_d = self.stats_case(side, lengths, prior_mean, prior_var, prior_count)
+        with torch.cuda.device(self.device):
+            L.check(L.lib.gt_op_corpus_stats(C.byref(k), L.current_stream()))
+            f, d = out_f.cpu().numpy(), out_d.cpu().numpy()      # the read-back waits for the two launches
+        return f[0], f[1], d[0], d[1], d[2]
+
+    def minmax(self, side, lengths=None):
+        """``data.minmax`` of side "x" or "y" on the device: ``(lo, hi)`` float32 ``(D,)``; a NaN makes its column NaN, as numpy's."""
+        lo, hi, count, _, _ = self._device_stats(side, lengths, 0.0, 0.0, 0)
+        if count[0] == 0:
+            raise ValueError("ResidentCorpus.minmax: no frame selected (numpy's min of an empty array has no identity either)")
+        return lo, hi
+
+    def meanvar(self, side, lengths=None, mean_=0.0, var_=0.0, last_sample_count=0, return_last_sample_count=False):
+        """``data.meanvar`` of side "x" or "y" on the device, the host's signature: float64 ``(mean, var[, n])`` with
+        ``var = M2 / max(n, 1)``, continued from ``(mean_, var_, last_sample_count)``; an empty selection returns that prior."""
+        _, _, count, mean, m2 = self._device_stats(side, lengths, mean_, var_, last_sample_count)
+        n = float(count[0])
+        var = m2 / max(n, 1.0)
+        if return_last_sample_count:
+            return mean, var, int(n)
+        return mean, var
 
 
 class ResidentLoader(object):
@@ -572,6 +685,9 @@ class ResidentLoader(object):
         self.dataset, self.hp, self.device = dataset, hp, device
         self.corpus = dataset if isinstance(dataset, ResidentCorpus) else ResidentCorpus(dataset, device=None)
         if isinstance(dataset, ResidentCorpus):
+            if dataset.dataset is None:
+                raise ValueError("ResidentLoader: this corpus was made from raw arrays and has no statistics attached yet; compute them "
+                                 "(corpus.minmax / corpus.meanvar) and call corpus.attach_statistics(dataset) first")
             self.dataset = dataset.dataset
         n = len(self.corpus.lengths)
         if batch_sampler is None:
@@ -658,3 +774,40 @@ class ResidentLoader(object):
             gi, y, ys, mask, lengths = self.assemble(case, first, B, T)
             g = gi if gi.size(-1) == Dx + nz else gi[:, :, :Dx + nz]
             yield DeviceBatch(gi[:, :, :Dx] if gi.size(-1) != Dx else gi, y, lengths, cpu_lengths, None, generator_input=g, y_static=ys, mask=mask)
+
+
+def _resident_loaders(corpora, datasets, hp):
+    loaders = {}
+    for ph, shuffle, first_draw in (("train", True, 0), ("test", False, 1 << 31)):      # the draw counters of _loaders
+        corpora[ph].attach_statistics(datasets[ph])
+        loaders[ph] = ResidentLoader(corpora[ph], hp.batch_size, shuffle, hp, device=corpora[ph].device, first_draw=first_draw)
+    return loaders
+
+
+def resident_tts_loaders(X, Y, hp, device="cuda"):
+    """train.py:744-770 on a device-resident corpus, raw arrays in: ``X``, ``Y`` are the reference's ``{"train": ..., "test": ...}`` of
+    utterance sequences.  Each phase is uploaded once; the TRAIN statistics -- ``minmax`` of X, ``meanvar`` of Y -- are one device
+    pass per side (gt_op_corpus_stats), no host arithmetic on frames; the ordinary ``TTSDataset``s carry them (``loader.dataset``), and
+    the uploaded corpora go to the ``ResidentLoader``s as they are.  Returns ``(loaders, stats)``, ``stats`` under the names of the
+    ``.npy`` files the reference saves: X_data_min, X_data_max, Y_data_mean, Y_data_var."""
+    corpora = {ph: ResidentCorpus.from_arrays(X[ph], Y[ph], device=device) for ph in ("train", "test")}
+    X_data_min, X_data_max = corpora["train"].minmax("x")
+    Y_data_mean, Y_data_var = corpora["train"].meanvar("y")
+    Y_data_std = np.sqrt(Y_data_var)
+    datasets = {ph: TTSDataset(MemoryCacheDataset(X[ph], cache_size=hp.cache_size), MemoryCacheDataset(Y[ph], cache_size=hp.cache_size),
+                               X_data_min, X_data_max, Y_data_mean, Y_data_std, hp=hp) for ph in corpora}
+    stats = dict(X_data_min=X_data_min, X_data_max=X_data_max, Y_data_mean=Y_data_mean, Y_data_var=Y_data_var)
+    return _resident_loaders(corpora, datasets, hp), stats
+
+
+def resident_vc_loaders(X, Y, hp, device="cuda"):
+    """train.py:725-741 on a device-resident corpus: the joint ``meanvar`` over the TRAIN X continued over the TRAIN Y, each cut to the
+    utterance lengths, on the device; ``VCDataset``s carry the result.  Returns ``(loaders, stats)`` with data_mean, data_var."""
+    corpora = {ph: ResidentCorpus.from_arrays(X[ph], Y[ph], device=device) for ph in ("train", "test")}
+    train = corpora["train"]
+    data_mean, data_var, last_sample_count = train.meanvar("x", train.lengths, return_last_sample_count=True)
+    data_mean, data_var = train.meanvar("y", train.lengths, mean_=data_mean, var_=data_var, last_sample_count=last_sample_count)
+    data_std = np.sqrt(data_var)
+    datasets = {ph: VCDataset(MemoryCacheDataset(X[ph], cache_size=hp.cache_size), MemoryCacheDataset(Y[ph], cache_size=hp.cache_size),
+                              data_mean, data_std) for ph in corpora}
+    return _resident_loaders(corpora, datasets, hp), dict(data_mean=data_mean, data_var=data_var)

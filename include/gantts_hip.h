@@ -1026,6 +1026,40 @@ typedef struct gt_assemble_case {
 } gt_assemble_case;
 int gt_op_assemble_batch(const gt_assemble_case* c, void* stream);
 
+/* Normalisation statistics of one side of a device-resident corpus in one pass (gantts_amd/csrc/corpus_stats_kernels.hip.h; gantts_amd/data.py:
+ * ResidentCorpus.minmax / .meanvar): what data.minmax and data.meanvar compute on the host (train.py:718-751).  Stateless; every pointer is
+ * caller-owned device memory; no synchronisation; two launches on `stream`, no atomics, bit-identical from run to run.
+ *   A        [F][ld] float32, ld = roundup(D, 4), 16-byte aligned; the pad columns [D, ld) reach no result
+ *   seg      [n_seg][2] int64 = (first frame, valid frame count) in ascending order, none beginning before the previous one ends: the
+ *            valid rows.  A segment that does not lie inside [0, F) counts as empty; rows outside every segment are not counted.
+ *   prior_mean, prior_var [D] float64 (null: zeros), prior_count: the statistics continue from these (M2 = prior_var * prior_count), as
+ *            meanvar(..., mean_=, var_=, last_sample_count=) does; an empty selection returns the prior.
+ *   workspace   gt_corpus_stats_workspace_bytes(F, D) bytes, 16-byte aligned: one partial per slab of GT_CORPUS_STATS_SLAB rows.
+ *   out_min, out_max [D] float32: numpy's min / max (a NaN makes its column NaN; +inf / -inf of an empty selection);
+ *   out_count, out_mean, out_m2 [D] float64: the number of valid rows (+ prior_count), the mean and M2 = sum (x - mean)^2 (Welford per lane,
+ *            Chan's pairwise update between lanes, waves, slabs -- GT_CORPUS_STATS_FANIN partial chains per column -- and with the prior; no
+ *            sum of squares anywhere: a constant column has M2 exactly 0).
+ * A malformed case returns GT_ERR_INVALID before any launch. */
+#define GT_CORPUS_STATS_SLAB 256
+#define GT_CORPUS_STATS_FANIN 64
+typedef struct gt_corpus_stats_case {
+  int32_t D, ld;
+  int64_t F, n_seg, prior_count;
+  const float* A;
+  const int64_t* seg;
+  const double* prior_mean;
+  const double* prior_var;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* out_min;
+  float* out_max;
+  double* out_count;
+  double* out_mean;
+  double* out_m2;
+} gt_corpus_stats_case;
+int64_t gt_corpus_stats_workspace_bytes(int64_t F, int32_t D);
+int gt_op_corpus_stats(const gt_corpus_stats_case* c, void* stream);
+
 /* ---- measurement (bench.py): HIP-event timing of every GEMM launch on its own stream --------
  * One slot per KERNEL (template instantiation family), so that the figures line up with a rocprofv3 kernel trace:
  *   0..5  = kind*2 + (tile N == 128), kind: 0 forward (X W^T), 1 backward-data (dZ W), 2 backward-weight (dZ^T X) -- the

@@ -5,11 +5,13 @@
    Infinity Cache, batches drawn at random, output buffers rotated; HIP events around LAUNCHES launches.  Reported: the time, the rate
    algorithmic bytes / time (B T (428 + 188) 4 read + B T (428 + 187 + 63 + 1) 4 written), and -- in the same process -- a device
    copy moving the same number of bytes (half read, half written; buffers rotated the same way) and the ratio of the two.
-2. Batches per second on the same corpus through DevicePrefetcher(DataLoader) -- collate_fn and hp.device_collate -- and through
+2. The normalisation statistics of that corpus (gt_op_corpus_stats, ResidentCorpus.minmax / .meanvar): one device pass per side between
+   HIP events against the host's data.minmax + data.meanvar on the same arrays and against the device copy's rate of part 1.
+3. Batches per second on the same corpus through DevicePrefetcher(DataLoader) -- collate_fn and hp.device_collate -- and through
    ResidentLoader: each loader alone (a device synchronise at the end), then each inside train_loop's G+D step (one epoch:
    train phase + a short test phase, host clock around the call, which ends in the epoch's read-back).
 
-    python tools/resident_bench.py [--utterances 1024] [--workers 1] [--out FILE]
+    python tools/resident_bench.py [--utterances 1024] [--workers 1] [--no-loaders] [--out FILE]
 
 Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -97,6 +99,57 @@ def kernel_time(ds, hp, launches, nbuf=8):
     return res
 
 
+def stats_time(X, Y, copy_TBps, passes=20):
+    """The normalisation statistics of the same corpus: host data.minmax / data.meanvar per side (host clock) against one
+    gt_op_corpus_stats pass per side (min, max, count, mean and M2 of every column in one read of the side; HIP events around `passes`
+    back-to-back passes behind a busy device, the last of three rounds).  Rates are algorithmic bytes F * ld * 4 over the time; the
+    corpus is larger than the Infinity Cache, so every pass reads HBM.  `copy_TBps` is kernel_time's device copy in this process."""
+    import ctypes as C
+    import torch
+    from gantts_amd import _lib as L
+    from gantts_amd import data as D
+    res, host = {}, {}
+    for side, arrays in (("x", X), ("y", Y)):
+        t0 = time.perf_counter()
+        lo, hi = D.minmax(arrays)
+        t1 = time.perf_counter()
+        mean, var = D.meanvar(arrays)
+        t2 = time.perf_counter()
+        host[side] = (lo, hi, mean, var)
+        res[side] = {"host_minmax_s": t1 - t0, "host_meanvar_s": t2 - t1}
+    t0 = time.perf_counter()
+    corpus = D.ResidentCorpus.from_arrays(X, Y)
+    torch.cuda.synchronize()
+    res["upload_s"] = time.perf_counter() - t0
+    busy = torch.rand(8192, 8192, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for side, ld in (("x", corpus.ldX), ("y", corpus.ldY)):
+        case, out_f, out_d = corpus.stats_case(side)
+        nbytes = corpus.F * ld * 4
+        rounds = []
+        for rep in range(3):
+            for _ in range(2):
+                torch.mm(busy, busy)
+            ev[0].record()
+            for _ in range(passes):
+                L.check(L.lib.gt_op_corpus_stats(C.byref(case), L.current_stream()))
+            ev[1].record()
+            torch.cuda.synchronize()
+            rounds.append(ev[0].elapsed_time(ev[1]) * 1e3 / passes)
+        lo, hi, mean, var = host[side]
+        f, d = out_f.cpu().numpy(), out_d.cpu().numpy()
+        assert np.array_equal(f[0], lo) and np.array_equal(f[1], hi) and d[0][0] == corpus.F
+        assert np.allclose(d[1], mean, rtol=1e-9, atol=1e-12) and np.allclose(d[2] / corpus.F, var, rtol=1e-9, atol=1e-12)
+        r = res[side]
+        r.update(algorithmic_bytes=nbytes, device_us=rounds[-1], rounds_us=[round(v, 2) for v in rounds], device_TBps=nbytes / rounds[-1] * 1e-6)
+        r["device_over_copy_rate"] = r["device_TBps"] / copy_TBps
+        r["host_over_device"] = (r["host_minmax_s"] + r["host_meanvar_s"]) / (rounds[-1] * 1e-6)
+    # what the start-up of a TTS run computes: minmax of x and meanvar of y
+    res["tts_startup"] = {"host_s": res["x"]["host_minmax_s"] + res["y"]["host_meanvar_s"],
+                          "device_s": (res["x"]["device_us"] + res["y"]["device_us"]) * 1e-6}
+    return res
+
+
 def loader_alone(make_batches, n_batches):
     """Batches per second of an iterable of DeviceBatches, nothing else on the device; the first epoch warms up."""
     import torch
@@ -141,6 +194,8 @@ def main():
     ap.add_argument("--test-utterances", type=int, default=64)
     ap.add_argument("--workers", type=int, default=1, help="DataLoader workers of the host pipeline (hp.num_workers)")
     ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--stats-passes", type=int, default=20)
+    ap.add_argument("--no-loaders", action="store_true", help="the kernel and the statistics only (parts 1 and 2)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -154,8 +209,9 @@ def main():
     res = {"B": B, "T": T, "utterances": a.utterances, "corpus_bytes": a.utterances * T * (428 + 188) * 4, "workers": a.workers}
     ds = D.TTSDataset(X, Y, lo, hi, mean, std, hp=hp)
     res["kernel"] = kernel_time(ds, hp, a.launches)
+    res["stats"] = stats_time(X, Y, res["kernel"]["copy_TBps"], a.stats_passes)
     n_train = (a.utterances + B - 1) // B
-    for tag, flags in (("host_collate", {}), ("host_device_collate", {"device_collate": True}), ("resident", {"resident_corpus": True})):
+    for tag, flags in () if a.no_loaders else (("host_collate", {}), ("host_device_collate", {"device_collate": True}), ("resident", {"resident_corpus": True})):
         for k in ("device_collate", "resident_corpus"):
             setattr(hp, k, bool(flags.get(k, False)))
         loaders = D.get_tts_data_loaders(Xs, Ys, lo, hi, mean, std, hp)
