@@ -109,6 +109,31 @@ GemmB16Args b16_args() {
   g.drop.mode = DROP_NONE; g.drop.scale = 1.f;
   return g;
 }
+static int b16_product(int epi, const __bf16* A, int lda, long rows, const __bf16* W, int ldw, int n, int k, const float* bias, int act,
+                       const B16Img* H, const DropoutSpec& drop, const B16Dst& dst, hipStream_t s) {
+  GemmB16Args g = b16_args();
+  g.A = A; g.lda = lda; g.B = W; g.ldb = ldw; g.M = (int)rows; g.N = n; g.K = k;
+  g.bias = bias; g.epi = epi; g.act = act; g.drop = drop;
+  if (H) { g.H = H->rm.as<__bf16>(); g.ldh = H->ld; }
+  if (dst.img) {
+    g.Cb = dst.img->r(); g.ldcb = dst.img->ld;
+    if (dst.twin) { g.CbT = dst.img->t(); g.ldcbt = (int)dst.img->ldt; }
+  } else {
+    g.C = dst.C; g.ldc = dst.ldc; g.accumulate = dst.accumulate ? 1 : 0;
+  }
+  return launch_gemm_b16(g, 1, s);
+}
+int b16_forward(const __bf16* X, int ldx, long rows, const __bf16* W, int ldw, int n, int k, const float* bias, int act,
+                const DropoutSpec& drop, const B16Dst& dst, hipStream_t s) {
+  return b16_product(B16_FWD, X, ldx, rows, W, ldw, n, k, bias, act, nullptr, drop, dst, s);
+}
+int b16_backward_data(const __bf16* dZ, int lddz, long rows, const __bf16* W, int ldw, int n, int k, int act_prev, const B16Img* H,
+                      const DropoutSpec& drop, const B16Dst& dst, hipStream_t s) {
+  return b16_product(B16_BWD_DATA, dZ, lddz, rows, W, ldw, n, k, nullptr, act_prev, H, drop, dst, s);
+}
+int shadow_cast(LinShadow& sh, const float* W, int r0, int out, int in, hipStream_t s) {
+  return cast_transpose(W, in, out, in, sh.r() + (size_t)r0 * sh.ldw, sh.ldw, sh.t() + r0, sh.ldwt, nullptr, false, nullptr, s);
+}
 // [rows][ld_in] float32 / bf16  ->  bf16 [rows][ldo] and / or its transpose [cols][ldt] (+ per-column sums -> colsum, the
 // bias gradient of a dZ that no product wrote)
 template <typename TIN>

@@ -162,6 +162,19 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, NetWs& W, bool bf16, int 
 }
 
 static bool lstm_b16(const gt_engine* e) { return e->matmul_bf16 && (e->net[GT_ROLE_G].d.hidden_dim & 7) == 0; }
+// nn.LSTM(dropout=p) between the layers: layer `layer`'s dropout applied to src's N rows into dst (in place when they are equal), every pass's
+// rows (a row group of N / npass) at its own site -- the forward's sites again in the backward
+static int lstm_interlayer_dropout(gt_engine* e, int role, int layer, const int* passes, int npass, const float* src, float* dst, long N, int width,
+                                   hipStream_t s) {
+  const Net& G = e->net[role];
+  const long Ng = N / npass;
+  for (int q = 0; q < npass; ++q) {
+    const DropoutSpec ds = drop_spec(e, role, passes[q], layer, G.inj[passes[q]][layer], width);
+    launch_dropout_apply(src + q * Ng * width, dst + q * Ng * width, Ng, width, ds, s);
+  }
+  LAUNCH_CHECK();
+  return GT_OK;
+}
 // The LSTM stack of network `role` over nseq sequences (rows = nseq * T of x, row pitch ld_x): X-projections, recurrences, inter-layer
 // dropout; stashes X-projections / gates / cell states / layer outputs in the role's buffers.  passes / npass: the dropout sites of the
 // row groups (the D step runs the natural and the generated sequences as ONE batch of 2B: two groups of nseq / 2 sequences).
@@ -182,21 +195,13 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
   const int Lc_ = G.d.num_hidden;
   if (b16) {
     W.l_in_b.resize(Lc_ + 1); W.lsh.resize(Lc_ + 1);
-    for (int l = 0; l <= Lc_; ++l) {
-      LinShadow& w = W.lsh[l];
-      if (l == Lc_) {
-        w.ldw = pad8(G.last.in); w.ldwt = pad8(G.last.out);
-        CHK(w.w.ensure((size_t)G.last.out * w.ldw * 2 + 64)); CHK(w.wt.ensure((size_t)G.last.in * w.ldwt * 2 + 64));
-        CHK(cast_transpose(G.last.W, G.last.in, G.last.out, G.last.in, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt, nullptr, false, &e->colp, s));
-        break;
-      }
+    for (int l = 0; l < Lc_; ++l) {
       const LstmLayerP& L = G.lstm[l];
-      w.ldw = pad8(L.in); w.ldwt = pad8(dirs * 4 * H);
-      CHK(w.w.ensure((size_t)dirs * 4 * H * w.ldw * 2 + 64)); CHK(w.wt.ensure((size_t)L.in * w.ldwt * 2 + 64));
-      for (int d = 0; d < dirs; ++d)
-        CHK(cast_transpose(L.d[d].Wih, L.in, 4 * H, L.in, w.w.as<__bf16>() + (size_t)d * 4 * H * w.ldw, w.ldw,
-                                  w.wt.as<__bf16>() + (size_t)d * 4 * H, w.ldwt, nullptr, false, &e->colp, s));
+      CHK(W.lsh[l].ensure(dirs * 4 * H, L.in));
+      for (int d = 0; d < dirs; ++d) CHK(shadow_cast(W.lsh[l], L.d[d].Wih, d * 4 * H, 4 * H, L.in, s));
     }
+    CHK(W.lsh[Lc_].ensure(G.last.out, G.last.in));
+    CHK(shadow_cast(W.lsh[Lc_], G.last.W, 0, G.last.out, G.last.in, s));
   }
   for (int l = 0; l < G.d.num_hidden; ++l) {
     const LstmLayerP& L = G.lstm[l];
@@ -208,11 +213,8 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
       B16Img& I = W.l_in_b[l];
       CHK(I.ensure(N, L.in, want_t));
       CHK(cast_transpose(in, ld_in, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
-      GemmB16Args g = b16_args();
-      g.A = I.r(); g.lda = I.ld; g.B = W.lsh[l].w.as<__bf16>(); g.ldb = W.lsh[l].ldw;
-      g.M = (int)N; g.N = dirs * 4 * H; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE;
-      g.C = W.xproj[l].as<float>(); g.ldc = dirs * 4 * H;
-      CHK(launch_gemm_b16(g, 1, s));
+      CHK(b16_forward(I.r(), I.ld, N, W.lsh[l].r(), W.lsh[l].ldw, dirs * 4 * H, L.in, nullptr, ACT_NONE, no_drop(),
+                      B16Dst(W.xproj[l].as<float>(), dirs * 4 * H), s));
     } else {
       for (int d = 0; d < dirs; ++d)   // Xp[:, d*4H:(d+1)*4H] = X W_ih^T (biases are added in the step kernel)
         CHK(linear_forward(in, ld_in, L.d[d].Wih, L.in, nullptr, W.xproj[l].as<float>() + (size_t)d * 4 * H, dirs * 4 * H, N, L.in,
@@ -226,12 +228,7 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
     if (G.training && G.d.dropout > 0.f && l + 1 < G.d.num_hidden) {
       // nn.LSTM(dropout=p): dropout on the outputs of every layer but the last (training only)
       CHK(W.outd[l].ensure((size_t)N * dirs * H * sizeof(float)));
-      const long Ng = N / npass;                        // rows of one pass (its own dropout site)
-      for (int q = 0; q < npass; ++q) {
-        const DropoutSpec ds = drop_spec(e, role, passes[q], l, G.inj[passes[q]][l], dirs * H);
-        launch_dropout_apply(in + q * Ng * dirs * H, W.outd[l].as<float>() + q * Ng * dirs * H, Ng, dirs * H, ds, s);
-      }
-      LAUNCH_CHECK();
+      CHK(lstm_interlayer_dropout(e, role, l, passes, npass, in, W.outd[l].as<float>(), N, dirs * H, s));
       in = W.outd[l].as<float>();
     }
   }
@@ -244,26 +241,12 @@ int lstm_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipSt
   Net& G = e->net[GT_ROLE_G];
   CHK(lstm_check_lengths(e, B, T));
   NetWs& W = e->ws[GT_ROLE_G];
-  const long N = (long)B * T;
-  const int Lc_ = G.d.num_hidden;
-  const bool b16 = lstm_b16(e);
-  const bool want_t = G.d.grads != nullptr;
+  const int Lc = G.d.num_hidden;
   const int passes[1] = {0};
-  const float* in = nullptr;
-  int ld_in = 0;
-  CHK(lstm_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &in, &ld_in));
-  if (b16) {
-    B16Img& I = W.l_in_b[Lc_];
-    CHK(I.ensure(N, G.last.in, want_t));
-    CHK(cast_transpose(in, ld_in, N, G.last.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
-    GemmB16Args g = b16_args();
-    g.A = I.r(); g.lda = I.ld; g.B = W.lsh[Lc_].w.as<__bf16>(); g.ldb = W.lsh[Lc_].ldw;
-    g.M = (int)N; g.N = G.last.out; g.K = G.last.in; g.bias = G.last.b; g.epi = B16_FWD;
-    g.act = G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = y_hat; g.ldc = G.d.out_dim;
-    return launch_gemm_b16(g, 1, s);
-  }
-  return linear_forward(in, ld_in, G.last.W, G.last.in, G.last.b, y_hat, G.d.out_dim, N, G.last.in, G.last.out,
-                        G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
+  OutTop top;
+  CHK(lstm_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &top.x, &top.ld));
+  if (lstm_b16(e)) { top.img = &W.l_in_b[Lc]; top.sh = &W.lsh[Lc]; top.want_t = G.d.grads != nullptr; }
+  return out_layer_forward(e, GT_ROLE_G, top, (long)B * T, y_hat, s);
 }
 
 // gy (N, out_dim) = dL/dy_hat -> parameter gradients of hidden2out and of every LSTM layer
@@ -271,29 +254,11 @@ int lstm_backward(gt_engine* e, const float* x, const float* gy, int B, int T, h
   Net& G = e->net[GT_ROLE_G];
   NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
-  const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, Do = G.d.out_dim, Lc = G.d.num_hidden;
-  const bool acc = G.grads_dirty;
-  CHK(W.dout.ensure((size_t)2 * N * dirs * H * sizeof(float)));
-  float* dout = W.dout.as<float>();                       // gradient w.r.t. the top layer's output
-  const bool b16 = lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1;
-  if (b16) {
-    // hidden2out through the bf16 images: gy -> (gy, gyT); dW = gyT . topT^T, d out_top = gy . W_lastT^T
-    CHK(e->gy_b.ensure(N, Do, true));
-    CHK(cast_transpose(gy, Do, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = W.l_in_b[Lc];
-    CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, dirs * H, G.last.dW, G.last.db, acc, e->slabs, s));
-    CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * dirs * H + Do, s));
-    GemmB16Args g = b16_args();
-    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = W.lsh[Lc].wt.as<__bf16>(); g.ldb = W.lsh[Lc].ldwt;
-    g.M = (int)N; g.N = dirs * H; g.K = Do; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dout; g.ldc = dirs * H;
-    CHK(launch_gemm_b16(g, 1, s));
-  } else {
-  // hidden2out: dW = gy^T out_top, db, d out_top = gy W
-  CHK(linear_backward_weight(gy, Do, W.out[Lc - 1].as<float>(), dirs * H, N, Do, dirs * H, G.last.dW, G.last.db, acc, e->slabs,
-                             e->colp, s));
-  CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * dirs * H + Do, s));
-  CHK(linear_backward_data(gy, Do, G.last.W, G.last.in, 0, dout, dirs * H, N, Do, dirs * H, ACT_NONE, nullptr, 0, no_drop(), s));
-  }
+  const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, Lc = G.d.num_hidden;
+  CHK(W.dout.ensure((size_t)2 * N * dirs * H * sizeof(float)));      // first half: gradient w.r.t. the top layer's output
+  OutTop top{W.out[Lc - 1].as<float>(), dirs * H};
+  if (lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1) { top.img = &W.l_in_b[Lc]; top.sh = &W.lsh[Lc]; }
+  CHK(out_layer_backward(e, GT_ROLE_G, gy, G.d.out_dim, N, top, OutGrad{B16Dst(W.dout.as<float>(), dirs * H), ACT_NONE, no_drop(), false}, nullptr, s));
   const int passes[1] = {0};
   return lstm_stack_backward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, true, nullptr, s);
 }
@@ -314,12 +279,6 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
   float* dout = W.dout.as<float>();                          // gradient w.r.t. the current layer's output
   float* dout_other = dout + (size_t)N * dirs * H;
   const bool b16 = role == GT_ROLE_G && lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1;
-  // (A side stream for a layer's weight-gradient products -- beside the recurrence of the layer below -- was built in round 3, measured not to
-  //  pay (cfg3 fp32 25.74 vs 25.68 ms, bf16 19.04 vs 18.14: the products' operand traffic slows every step of the recurrence by what the
-  //  overlap hides) and left the library in round 6.)
-  hipStream_t ws = s;
-  Scratch& wsl = e->slabs;
-  Scratch& wcp = e->colp;
   if (b16) W.l_dg_b.resize(Lc);
   for (int l = Lc - 1; l >= 0; --l) {
     const LstmLayerP& L = G.lstm[l];
@@ -329,45 +288,32 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
     const float* dG = W.xproj[l].as<float>();
     const bool dropped_in = l > 0 && G.training && G.d.dropout > 0.f;
     if (b16) {
-      B16Img& DG0 = W.l_dg_b[l];
-      CHK(DG0.ensure(N, dirs * 4 * H, true));
-      CHK(cast_transpose(dG, dirs * 4 * H, N, dirs * 4 * H, DG0.r(), DG0.ld, DG0.t(), DG0.ldt, nullptr, false, &e->colp, s));
-    }
-    if (b16) {
       // dG -> bf16 image in both orientations (one pass), then every product of this layer reads bf16:
       // dW_ih_d = dGT_d . inT^T (+ db from the loader), dW_hh_d = dGT_d . hshiftT^T, d in = dG . W_ihT^T (all directions in ONE product)
       B16Img& DG = W.l_dg_b[l];
       B16Img& I = W.l_in_b[l];
-      if (l > 0) {      // the step stream's part first: d(layer input), all directions in ONE product
-        GemmB16Args g = b16_args();
-        g.A = DG.r(); g.lda = DG.ld; g.B = W.lsh[l].wt.as<__bf16>(); g.ldb = W.lsh[l].ldwt;
-        g.M = (int)N; g.N = L.in; g.K = dirs * 4 * H; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dout_other; g.ldc = L.in;
-        CHK(launch_gemm_b16(g, 1, s));
-        if (dropped_in) {
-          const long Ng = N / npass;
-          for (int q = 0; q < npass; ++q) {
-            const DropoutSpec ds = drop_spec(e, role, passes[q], l - 1, G.inj[passes[q]][l - 1], dirs * H);
-            launch_dropout_apply(dout_other + q * Ng * dirs * H, dout_other + q * Ng * dirs * H, Ng, dirs * H, ds, s);
-          }
-          LAUNCH_CHECK();
-        }
+      CHK(DG.ensure(N, dirs * 4 * H, true));
+      CHK(cast_transpose(dG, dirs * 4 * H, N, dirs * 4 * H, DG.r(), DG.ld, DG.t(), DG.ldt, nullptr, false, &e->colp, s));
+      if (l > 0) {      // d(layer input) first, all directions in ONE product
+        CHK(b16_backward_data(DG.r(), DG.ld, N, W.lsh[l].t(), W.lsh[l].ldwt, L.in, dirs * 4 * H, ACT_NONE, nullptr, no_drop(), B16Dst(dout_other, L.in), s));
+        if (dropped_in) CHK(lstm_interlayer_dropout(e, role, l - 1, passes, npass, dout_other, dout_other, N, dirs * H, s));
         std::swap(dout, dout_other);
       }
       for (int d = 0; d < dirs; ++d) {
         const __bf16* dgt = DG.t() + (size_t)d * 4 * H * DG.ldt;
-        CHK(weight_grad_b16(dgt, DG.ldt, I.t(), I.ldt, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, wsl, ws));
-        hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(4 * H, 64)), dim3(1024), 0, ws, L.d[d].dbih, (long)4 * H, 1, 4 * H,
+        CHK(weight_grad_b16(dgt, DG.ldt, I.t(), I.ldt, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, e->slabs, s));
+        hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(4 * H, 64)), dim3(1024), 0, s, L.d[d].dbih, (long)4 * H, 1, 4 * H,
                            L.d[d].dbhh, 0);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(lstm_shift_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, ws, W.out[l].as<float>(), dirs * H, d, H, B, T,
+        hipLaunchKernelGGL(lstm_shift_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, s, W.out[l].as<float>(), dirs * H, d, H, B, T,
                            e->d_lengths(), W.hshift.as<float>());
         LAUNCH_CHECK();
         CHK(W.l_hs_b.ensure(N, H, true));
-        CHK(cast_transpose(W.hshift.as<float>(), H, N, H, (__bf16*)nullptr, 0, W.l_hs_b.t(), W.l_hs_b.ldt, nullptr, false, &wcp, ws));
-        CHK(weight_grad_b16(dgt, DG.ldt, W.l_hs_b.t(), W.l_hs_b.ldt, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, wsl, ws));
+        CHK(cast_transpose(W.hshift.as<float>(), H, N, H, (__bf16*)nullptr, 0, W.l_hs_b.t(), W.l_hs_b.ldt, nullptr, false, &e->colp, s));
+        CHK(weight_grad_b16(dgt, DG.ldt, W.l_hs_b.t(), W.l_hs_b.ldt, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, e->slabs, s));
       }
-      CHK(comm_grads_ready(e, role, L.d[0].dWih, (long)dirs * (4L * H * L.in + 4L * H * H + 8L * H), ws));
-      CHK(comm_flush(e, role, ws));
+      CHK(comm_grads_ready(e, role, L.d[0].dWih, (long)dirs * (4L * H * L.in + 4L * H * H + 8L * H), s));
+      CHK(comm_flush(e, role, s));
       continue;
     }
     const float* Xl = l == 0 ? x : (dropped_in ? W.outd[l - 1].as<float>() : W.out[l - 1].as<float>());
@@ -375,22 +321,22 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
     for (int d = 0; d < dirs && want_w; ++d) {
       const float* dGd = dG + (size_t)d * 4 * H;
       // dW_ih = dG_d^T X, db_ih = colsum(dG_d) (= db_hh)
-      CHK(linear_backward_weight(dGd, dirs * 4 * H, Xl, ldx, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, wsl, wcp, ws));
+      CHK(linear_backward_weight(dGd, dirs * 4 * H, Xl, ldx, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, e->slabs, e->colp, s));
       // bias_ih and bias_hh always receive the same gradient: keep them equal by copy
-      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(4 * H, 64)), dim3(1024), 0, ws, L.d[d].dbih, (long)4 * H, 1, 4 * H,
+      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(4 * H, 64)), dim3(1024), 0, s, L.d[d].dbih, (long)4 * H, 1, 4 * H,
                          L.d[d].dbhh, 0);
       LAUNCH_CHECK();
       // dW_hh = dG_d^T H_shift (h that entered each frame)
-      hipLaunchKernelGGL(lstm_shift_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, ws, W.out[l].as<float>(), dirs * H, d, H, B, T,
+      hipLaunchKernelGGL(lstm_shift_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, s, W.out[l].as<float>(), dirs * H, d, H, B, T,
                          e->d_lengths(), W.hshift.as<float>());
       LAUNCH_CHECK();
-      CHK(linear_backward_weight(dGd, dirs * 4 * H, W.hshift.as<float>(), H, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, wsl,
-                                 wcp, ws));
+      CHK(linear_backward_weight(dGd, dirs * 4 * H, W.hshift.as<float>(), H, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, e->slabs,
+                                 e->colp, s));
     }
     // this layer's parameters (both directions: W_ih, W_hh, b_ih, b_hh each) are one contiguous bucket
     if (want_w) {
-      CHK(comm_grads_ready(e, role, L.d[0].dWih, (long)dirs * (4L * H * L.in + 4L * H * H + 8L * H), ws));
-      if (role == GT_ROLE_G || !e->opt_comm_d_one_msg) CHK(comm_flush(e, role, ws));              // with hidden2out above it: under the recurrence of the layer below
+      CHK(comm_grads_ready(e, role, L.d[0].dWih, (long)dirs * (4L * H * L.in + 4L * H * H + 8L * H), s));
+      if (role == GT_ROLE_G || !e->opt_comm_d_one_msg) CHK(comm_flush(e, role, s));              // with hidden2out above it: under the recurrence of the layer below
     }
     if (l > 0 || dx0) {   // gradient w.r.t. the layer below's output (or the stack's input): sum over directions of dG_d W_ih_d
       float* const dst = l > 0 ? dout_other : dx0;
@@ -401,18 +347,11 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
         g.M = (int)N; g.N = L.in; g.K = 4 * H; g.act = ACT_NONE; g.accumulate = d > 0 ? 1 : 0; g.drop = no_drop();
         CHK(launch_gemm(GEMM_NN, g, 1, s));
       }
-      if (dropped_in) {   // through the inter-layer dropout of layer l-1 (same Philox sites as the forward)
-        const long Ng = N / npass;
-        for (int q = 0; q < npass; ++q) {
-          const DropoutSpec ds = drop_spec(e, role, passes[q], l - 1, G.inj[passes[q]][l - 1], dirs * H);
-          launch_dropout_apply(dout_other + q * Ng * dirs * H, dout_other + q * Ng * dirs * H, Ng, dirs * H, ds, s);
-      }
-        LAUNCH_CHECK();
-      }
+      // through the inter-layer dropout of layer l-1 (same Philox sites as the forward)
+      if (dropped_in) CHK(lstm_interlayer_dropout(e, role, l - 1, passes, npass, dout_other, dout_other, N, dirs * H, s));
       if (l > 0) std::swap(dout, dout_other);
     }
   }
   return GT_OK;
 }
-
 

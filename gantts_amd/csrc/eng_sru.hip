@@ -202,12 +202,10 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
   if (b16) {      // the shadows are re-made at every call: a discriminator's weights change between the two passes of one step
     W.s_in_b.resize(nent); W.ssh.resize(nent);
     for (int l = 0; l < nent; ++l) {
-      LinShadow& w = W.ssh[l];
       const float* Wl = l < Lc_ ? G.sru[l].W : G.last.W;
       const int rows = l < Lc_ ? G.sru[l].in : G.last.out, cols = l < Lc_ ? ncols * G.sru[l].k : G.last.in;
-      w.ldw = pad8(cols); w.ldwt = pad8(rows);
-      CHK(w.w.ensure((size_t)rows * w.ldw * 2 + 64)); CHK(w.wt.ensure((size_t)cols * w.ldwt * 2 + 64));
-      CHK(cast_transpose(Wl, cols, rows, cols, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt, nullptr, false, &e->colp, s));
+      CHK(W.ssh[l].ensure(rows, cols));
+      CHK(shadow_cast(W.ssh[l], Wl, 0, rows, cols, s));
     }
   }
   // bf16 storage + cooperative scans: layer l's scan writes the bf16 input images of the product behind it (layer l + 1's U product, or
@@ -261,10 +259,8 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       } else {
         CHK(cast_transpose(xin, ld_xin, N, L.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
       }
-      GemmB16Args g = b16_args();
-      g.A = I.r(); g.lda = I.ld; g.B = W.ssh[l].wt.as<__bf16>(); g.ldb = W.ssh[l].ldwt;     // WT [ncols*k][n_in]: k = n_in contiguous
-      g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.epi = B16_FWD; g.act = ACT_NONE; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
-      CHK(launch_gemm_b16(g, 1, s));
+      CHK(b16_forward(I.r(), I.ld, N, W.ssh[l].t(), W.ssh[l].ldwt, ncols * L.k, L.in, nullptr, ACT_NONE, no_drop(),      // WT [ncols*k][n_in]: k = n_in contiguous
+                      B16Dst(W.u[l].as<float>(), ncols * L.k), s));
     } else if ((L.in & 3) == 0 && N >= 4096) {
       // U = xin W with W (n_in, ncols*k): the k-contiguous (NT) product runs at 146 TFLOP/s on these shapes, the n-contiguous (NN)
       // one at 114 (profiles/r03_sru_fp32_summary.md: 1.41 vs 1.80 ms per layer) -- multiply by a transposed copy of W, re-made
@@ -309,28 +305,15 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
 int sru_forward(gt_engine* e, const float* x, int B, int T, float* y_hat, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
   NetWs& W = e->ws[GT_ROLE_G];
-  const long N = (long)B * T;
-  const int Lc_ = G.d.num_hidden;
-  const bool b16 = sru_b16(e, GT_ROLE_G);
-  const bool want_t = G.d.grads != nullptr;
-  const bool img_ready = sru_fold(e, GT_ROLE_G, B, T);      // hidden2out's input images were written by the last layer's scan
+  const int Lc = G.d.num_hidden;
   const int passes[1] = {0};
-  const float* in = nullptr;
-  int ld_in = 0;
-  CHK(sru_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &in, &ld_in));
-  if (b16) {
-    B16Img& I = W.s_in_b[Lc_];
-    CHK(I.ensure(N, G.last.in, want_t));
-    if (!img_ready)      // (else: written by the last layer's scan)
-      CHK(cast_transpose(in, ld_in, N, G.last.in, I.r(), I.ld, want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
-    GemmB16Args g = b16_args();
-    g.A = I.r(); g.lda = I.ld; g.B = W.ssh[Lc_].w.as<__bf16>(); g.ldb = W.ssh[Lc_].ldw;    // hidden2out.weight (out, ncols): k = ncols contiguous
-    g.M = (int)N; g.N = G.last.out; g.K = G.last.in; g.bias = G.last.b; g.epi = B16_FWD;
-    g.act = G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = y_hat; g.ldc = G.d.out_dim;
-    return launch_gemm_b16(g, 1, s);
+  OutTop top;
+  CHK(sru_stack_forward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, s, &top.x, &top.ld));
+  if (sru_b16(e, GT_ROLE_G)) {
+    top.img = &W.s_in_b[Lc]; top.sh = &W.ssh[Lc]; top.want_t = G.d.grads != nullptr;
+    top.img_ready = sru_fold(e, GT_ROLE_G, B, T);      // hidden2out's input images were written by the last layer's scan
   }
-  return linear_forward(in, ld_in, G.last.W, G.last.in, G.last.b, y_hat, G.d.out_dim, N, G.last.in, G.last.out,
-                        G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
+  return out_layer_forward(e, GT_ROLE_G, top, (long)B * T, y_hat, s);
 }
 
 // gy (N, out_dim) = dL/dy_hat -> parameter gradients of hidden2out and of every SRU layer of the generator
@@ -338,28 +321,13 @@ int sru_backward(gt_engine* e, const float* x, const float* gy, int B, int T, hi
   Net& G = e->net[GT_ROLE_G];
   NetWs& W = e->ws[GT_ROLE_G];
   const long N = (long)B * T;
-  const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Do = G.d.out_dim, Lc = G.d.num_hidden;
-  const bool acc = G.grads_dirty;
+  const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Lc = G.d.num_hidden;
   int inmax = ncols;
   for (auto& L : G.sru) inmax = std::max(inmax, L.in);
-  CHK(W.dout.ensure((size_t)2 * N * std::max(ncols, inmax) * sizeof(float)));
-  float* dh = W.dout.as<float>();
-  const bool b16 = sru_b16(e, GT_ROLE_G) && (int)W.s_in_b.size() == Lc + 1 && (int)W.ssh.size() == Lc + 1;
-  if (b16) {
-    CHK(e->gy_b.ensure(N, Do, true));
-    CHK(cast_transpose(gy, Do, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = W.s_in_b[Lc];
-    CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, ncols, G.last.dW, G.last.db, acc, e->slabs, s));
-    CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * ncols + Do, s));
-    GemmB16Args g = b16_args();
-    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = W.ssh[Lc].wt.as<__bf16>(); g.ldb = W.ssh[Lc].ldwt;   // hidden2out.weight^T [ncols][Do]
-    g.M = (int)N; g.N = ncols; g.K = Do; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dh; g.ldc = ncols;
-    CHK(launch_gemm_b16(g, 1, s));
-  } else {
-  CHK(linear_backward_weight(gy, Do, W.h[Lc - 1].as<float>(), ncols, N, Do, ncols, G.last.dW, G.last.db, acc, e->slabs, e->colp, s));
-  CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * ncols + Do, s));
-  CHK(linear_backward_data(gy, Do, G.last.W, G.last.in, 0, dh, ncols, N, Do, ncols, ACT_NONE, nullptr, 0, no_drop(), s));
-  }
+  CHK(W.dout.ensure((size_t)2 * N * std::max(ncols, inmax) * sizeof(float)));      // first half: gradient w.r.t. the top layer's h
+  OutTop top{W.h[Lc - 1].as<float>(), ncols};
+  if (sru_b16(e, GT_ROLE_G) && (int)W.s_in_b.size() == Lc + 1 && (int)W.ssh.size() == Lc + 1) { top.img = &W.s_in_b[Lc]; top.sh = &W.ssh[Lc]; }
+  CHK(out_layer_backward(e, GT_ROLE_G, gy, G.d.out_dim, N, top, OutGrad{B16Dst(W.dout.as<float>(), ncols), ACT_NONE, no_drop(), false}, nullptr, s));
   const int passes[1] = {0};
   return sru_stack_backward(e, GT_ROLE_G, x, G.d.in_dim, B, T, passes, 1, true, nullptr, s);
 }
@@ -428,39 +396,36 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
                          &e->colp, s));
     }
     if (want_w) {      // (the generator step's pass through a discriminator launches no weight-gradient kernel: train.py:307-308)
-    hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(2 * ncols, 64)), dim3(1024), 0, s, e->s_dbias.as<float>(), (long)2 * ncols, B,
-                       2 * ncols, L.db, acc ? 1 : 0);
-    LAUNCH_CHECK();
-    const float* xin = rdrop ? W.xdrop[l].as<float>() : in;
-    const int ld_xin = rdrop ? L.in : ld_in;
-    if (b16) {
-      // dW = xinT . dUT^T over the frames, d in = dU . W^T
-      B16Img& DU = W.du_b;
-      B16Img& I = W.s_in_b[l];
-      CHK(weight_grad_b16(I.t(), I.ldt, DU.t(), DU.ldt, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs, s));
-    } else {
-    // dW = xin^T dU   (TN: A = xin is m-contiguous over n_in, B = dU)
-    CHK(linear_backward_weight(xin, ld_xin, e->s_du.as<float>(), ncols * L.k, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs,
-                               e->colp, s));
-    }
-    CHK(comm_grads_ready(e, role, L.dW, (long)L.in * ncols * L.k + 2L * ncols, s));
-    if (l > 0 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
+      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(2 * ncols, 64)), dim3(1024), 0, s, e->s_dbias.as<float>(), (long)2 * ncols, B,
+                         2 * ncols, L.db, acc ? 1 : 0);
+      LAUNCH_CHECK();
+      const float* xin = rdrop ? W.xdrop[l].as<float>() : in;
+      const int ld_xin = rdrop ? L.in : ld_in;
+      if (b16) {
+        // dW = xinT . dUT^T over the frames, d in = dU . W^T
+        B16Img& DU = W.du_b;
+        B16Img& I = W.s_in_b[l];
+        CHK(weight_grad_b16(I.t(), I.ldt, DU.t(), DU.ldt, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs, s));
+      } else {
+        // dW = xin^T dU   (TN: A = xin is m-contiguous over n_in, B = dU)
+        CHK(linear_backward_weight(xin, ld_xin, e->s_du.as<float>(), ncols * L.k, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs,
+                                   e->colp, s));
+      }
+      CHK(comm_grads_ready(e, role, L.dW, (long)L.in * ncols * L.k + 2L * ncols, s));
+      if (l > 0 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
     }
     if (l > 0) {
-      if (b16) {
-        GemmB16Args g = b16_args();
-        g.A = W.du_b.r(); g.lda = W.du_b.ld; g.B = W.ssh[l].w.as<__bf16>(); g.ldb = W.ssh[l].ldw;    // W [n_in][ncols*k]: k contiguous
-        g.M = (int)N; g.N = L.in; g.K = ncols * L.k; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dh_other; g.ldc = L.in;
-        g.accumulate = (L.k == 3 && !rdrop) ? 1 : 0;
-        CHK(launch_gemm_b16(g, 1, s));
+      if (b16) {      // W [n_in][ncols*k]: k contiguous
+        CHK(b16_backward_data(W.du_b.r(), W.du_b.ld, N, W.ssh[l].r(), W.ssh[l].ldw, L.in, ncols * L.k, ACT_NONE, nullptr, no_drop(),
+                              B16Dst(dh_other, L.in, L.k == 3 && !rdrop), s));
       } else {
-      // d in = (dU W^T) (.) mask_in + highway term     (NT: B[n = i][k = c] = W[i*ldw + c])
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = e->s_du.as<float>(); g.lda = ncols * L.k; g.B = L.W; g.ldb = ncols * L.k; g.C = dh_other; g.ldc = L.in;
-      g.M = (int)N; g.N = L.in; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
-      g.accumulate = (L.k == 3 && !rdrop) ? 1 : 0;
-      CHK(launch_gemm(GEMM_NT, g, 1, s));
+        // d in = (dU W^T) (.) mask_in + highway term     (NT: B[n = i][k = c] = W[i*ldw + c])
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A = e->s_du.as<float>(); g.lda = ncols * L.k; g.B = L.W; g.ldb = ncols * L.k; g.C = dh_other; g.ldc = L.in;
+        g.M = (int)N; g.N = L.in; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
+        g.accumulate = (L.k == 3 && !rdrop) ? 1 : 0;
+        CHK(launch_gemm(GEMM_NT, g, 1, s));
       }
       std::swap(dh, dh_other);         // (with input dropout: finished by the scan of layer l - 1, SruArgs::up_mul / up_add)
     }
@@ -476,18 +441,15 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
       const int Bf = nseq / npass;
       const long Nf = (long)Bf * T, row0 = N - Nf;
       if (b16) {      // the bf16 product from the dU image's row offset and the row slice of the layer-0 shadow (both 16-byte aligned: pitches % 8 == 0)
-        GemmB16Args g = b16_args();
-        g.A = W.du_b.r() + (size_t)row0 * W.du_b.ld; g.lda = W.du_b.ld;
-        g.B = W.ssh[0].w.as<__bf16>() + (size_t)col0 * W.ssh[0].ldw; g.ldb = W.ssh[0].ldw;
-        g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.epi = B16_BWD_DATA; g.act = ACT_NONE; g.C = dx_adv; g.ldc = Da;
-        CHK(launch_gemm_b16(g, 1, s));
+        CHK(b16_backward_data(W.du_b.r() + (size_t)row0 * W.du_b.ld, W.du_b.ld, Nf, W.ssh[0].r() + (size_t)col0 * W.ssh[0].ldw, W.ssh[0].ldw, Da,
+                              ncols * L.k, ACT_NONE, nullptr, no_drop(), B16Dst(dx_adv, Da), s));
       } else {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = e->s_du.as<float>() + (size_t)row0 * ncols * L.k; g.lda = ncols * L.k;
-      g.B = L.W + (size_t)col0 * ncols * L.k; g.ldb = ncols * L.k; g.C = dx_adv; g.ldc = Da;
-      g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
-      CHK(launch_gemm(GEMM_NT, g, 1, s));
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A = e->s_du.as<float>() + (size_t)row0 * ncols * L.k; g.lda = ncols * L.k;
+        g.B = L.W + (size_t)col0 * ncols * L.k; g.ldb = ncols * L.k; g.C = dx_adv; g.ldc = Da;
+        g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
+        CHK(launch_gemm(GEMM_NT, g, 1, s));
       }
       if (rdrop || L.k == 3) {
         SruDxAdvArgs f;

@@ -201,11 +201,9 @@ static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s
     if (l == n.hidden.size() && !with_last) break;
     const Lin& L = l < n.hidden.size() ? n.hidden[l] : n.last;
     LinShadow& w = sh[l];
-    w.ldw = pad8(L.in); w.ldwt = pad8(L.out);
-    CHK(w.w.ensure((size_t)L.out * w.ldw * 2 + 64));
-    CHK(w.wt.ensure((size_t)L.in * w.ldwt * 2 + 64));
+    CHK(w.ensure(L.out, L.in));
     if (jobs.n == CAST_MAX_JOBS) CHK(flush());
-    CHK(cast_jobs_add(jobs, blocks, L.W, L.in, L.out, L.in, w.w.as<__bf16>(), w.ldw, w.wt.as<__bf16>(), w.ldwt));
+    CHK(cast_jobs_add(jobs, blocks, L.W, L.in, L.out, L.in, w.r(), w.ldw, w.t(), w.ldwt));
   }
   return flush();
 }
@@ -225,12 +223,7 @@ static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_
     const float* inj = nullptr;
     CHK(stage_injected(e, role, (int)l, passes, npass, rows_each, L.out, &inj, s));
     specs[l] = drop_spec(e, role, passes[0], (int)l, inj, L.out, npass == 2 ? rows_each : 0);
-    GemmB16Args g = b16_args();
-    g.A = cur; g.lda = ld; g.B = wsh[l].w.as<__bf16>(); g.ldb = wsh[l].ldw;
-    g.M = (int)rows; g.N = L.out; g.K = L.in; g.bias = L.b; g.epi = B16_FWD; g.act = ACT_LEAKY_DROPOUT; g.drop = specs[l];
-    g.Cb = acts[l].r(); g.ldcb = acts[l].ld;
-    if (want_t) { g.CbT = acts[l].t(); g.ldcbt = (int)acts[l].ldt; }
-    CHK(launch_gemm_b16(g, 1, s));
+    CHK(b16_forward(cur, ld, rows, wsh[l].r(), wsh[l].ldw, L.out, L.in, L.b, ACT_LEAKY_DROPOUT, specs[l], B16Dst(acts[l], want_t), s));
     cur = acts[l].r();
     ld = acts[l].ld;
   }
@@ -257,35 +250,67 @@ static int stack_backward_b16(gt_engine* e, int role, const __bf16* in_t, long l
     if (l > 0) {
       B16Img& nx = e->dz_b[cur ^ 1];
       CHK(nx.ensure(rows, Lr.in, want_w));
-      GemmB16Args g = b16_args();
-      g.A = dz.r(); g.lda = dz.ld; g.B = wsh[l].wt.as<__bf16>(); g.ldb = wsh[l].ldwt;
-      g.M = (int)rows; g.N = Lr.in; g.K = Lr.out; g.epi = B16_BWD_DATA; g.act = ACT_LEAKY_DROPOUT;
-      g.H = acts[l - 1].r(); g.ldh = acts[l - 1].ld; g.drop = specs[l - 1];
-      g.Cb = nx.r(); g.ldcb = nx.ld;
-      if (want_w) { g.CbT = nx.t(); g.ldcbt = (int)nx.ldt; }
-      CHK(launch_gemm_b16(g, 1, s));
+      CHK(b16_backward_data(dz.r(), dz.ld, rows, wsh[l].t(), wsh[l].ldwt, Lr.in, Lr.out, ACT_LEAKY_DROPOUT, &acts[l - 1], specs[l - 1],
+                            B16Dst(nx, want_w), s));
       cur ^= 1;
     } else if (dX) {
-      GemmB16Args g = b16_args();
-      g.A = dz.r() + row0 * dz.ld; g.lda = dz.ld;
-      g.B = wsh[0].wt.as<__bf16>() + (long)col0 * wsh[0].ldwt; g.ldb = wsh[0].ldwt;
-      g.M = (int)nrows; g.N = ncols; g.K = Lr.out; g.epi = B16_BWD_DATA; g.act = ACT_NONE;
-      g.C = dX; g.ldc = lddx;
-      CHK(launch_gemm_b16(g, 1, s));
+      CHK(b16_backward_data(dz.r() + row0 * dz.ld, dz.ld, nrows, wsh[0].t() + (long)col0 * wsh[0].ldwt, wsh[0].ldwt, ncols, Lr.out, ACT_NONE,
+                            nullptr, no_drop(), B16Dst(dX, lddx), s));
     }
   }
   return GT_OK;
 }
-// last_linear of a bf16-storage MLP: out [rows][out_dim] (float32) = act(acts.back() . W_last^T + b), W_last's shadow from refresh_shadows(with_last)
-static int last_forward_b16(gt_engine* e, int role, long rows, float* out, hipStream_t s) {
-  Net& n = e->net[role];
-  B16Img& top = e->ws[role].actb.back();
-  const LinShadow& ws = e->ws[role].wsh[n.hidden.size()];
-  GemmB16Args g = b16_args();
-  g.A = top.r(); g.lda = top.ld; g.B = ws.w.as<__bf16>(); g.ldb = ws.ldw;
-  g.M = (int)rows; g.N = n.last.out; g.K = n.last.in; g.bias = n.last.b; g.epi = B16_FWD;
-  g.act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE; g.C = out; g.ldc = n.d.out_dim;
-  return launch_gemm_b16(g, 1, s);
+
+// ------------------------------------------------------------------------------------------
+// The output layer of every stack (`last`: an MLP's last_linear, a recurrent network's hidden2out), either storage form
+// ------------------------------------------------------------------------------------------
+// out [rows][out_dim] (float32) = act(top . W_last^T + b), act = sigmoid iff last_sigmoid
+int out_layer_forward(gt_engine* e, int role, const OutTop& top, long rows, float* out, hipStream_t s) {
+  const Net& n = e->net[role];
+  const Lin& L = n.last;
+  const int act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE;
+  if (!top.img) return linear_forward(top.x, top.ld, L.W, L.in, L.b, out, n.d.out_dim, rows, L.in, L.out, act, no_drop(), s);
+  B16Img& I = *top.img;
+  if (!top.img_ready) {
+    CHK(I.ensure(rows, L.in, top.want_t));
+    CHK(cast_transpose(top.x, top.ld, rows, L.in, I.r(), I.ld, top.want_t ? I.t() : (__bf16*)nullptr, I.ldt, nullptr, false, &e->colp, s));
+  }
+  return b16_forward(I.r(), I.ld, rows, top.sh->r(), top.sh->ldw, L.out, L.in, L.b, act, no_drop(), B16Dst(out, n.d.out_dim), s);
+}
+// gy [rows][ldgy] = d loss / d (W_last's product): dW = gy^T top, db, then d loss / d top through dst.  bf16 storage: gy goes to the image
+// e->gy_b in both orientations first; the weight gradient reads its and top's transposed twins, backward-data the shadow's wt.
+int out_layer_backward(gt_engine* e, int role, const float* gy, int ldgy, long rows, const OutTop& top, const OutGrad& dst, SlabDefer* defer,
+                       hipStream_t s) {
+  const Net& n = e->net[role];
+  const Lin& L = n.last;
+  const int Do = n.d.out_dim;
+  const bool through_act = dst.act_prev != ACT_NONE;
+  if (top.img) {
+    B16Img& GY = e->gy_b;
+    CHK(GY.ensure(rows, Do, true));
+    CHK(cast_transpose(gy, ldgy, rows, Do, GY.r(), GY.ld, GY.t(), GY.ldt, nullptr, false, &e->colp, s));
+    CHK(weight_grad_b16(GY.t(), GY.ldt, top.img->t(), top.img->ldt, rows, Do, L.in, L.dW, L.db, n.grads_dirty, e->slabs, s, defer));
+    CHK(comm_grads_ready(e, role, L.dW, (long)Do * L.in + Do, s));
+    return b16_backward_data(GY.r(), GY.ld, rows, top.sh->t(), top.sh->ldwt, L.in, Do, dst.act_prev, through_act ? top.img : nullptr, dst.drop,
+                             dst.to, s);
+  }
+  const GemmArgs nn = backward_data_args(gy, ldgy, L.W, L.in, 0, dst.to.C, dst.to.ldc, rows, Do, L.in, dst.act_prev, through_act ? top.x : nullptr,
+                                         through_act ? top.ld : 0, dst.drop);
+  bool rode = false;
+  CHK(linear_backward_weight(gy, ldgy, top.x, top.ld, rows, Do, L.in, L.dW, L.db, n.grads_dirty, e->slabs, e->colp, s, defer,
+                             dst.ride ? &nn : nullptr, &rode));
+  CHK(comm_grads_ready(e, role, L.dW, (long)Do * L.in + Do, s));
+  if (!rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+  return GT_OK;
+}
+// what an MLP stack's pass left for its output layer: the top activation, as float32 rows or (bf16 storage, after refresh_shadows(with_last)) as image
+static OutTop mlp_top(gt_engine* e, int role, bool b16) {
+  const Net& n = e->net[role];
+  NetWs& W = e->ws[role];
+  OutTop top;
+  if (b16) { top.img = &W.actb.back(); top.sh = &W.wsh[n.hidden.size()]; top.img_ready = true; }
+  else { top.x = W.act.back().as<float>(); top.ld = n.hidden.back().out; }
+  return top;
 }
 
 // row pitch of the generator's input / of the conditioning x (gt_set_x_pitch; dense by default)
@@ -333,20 +358,18 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
   } else if (G.d.arch == GT_ARCH_SRU) {
     CHK(sru_forward(e, x, B, T, y_hat, s));
   } else {
-    if (use_b16(e, GT_ROLE_G)) {
+    const bool b16 = use_b16(e, GT_ROLE_G);
+    if (b16) {
       const bool want_t = stash && G.d.grads != nullptr;
       CHK(e->xin_b.ensure(N, G.d.in_dim, want_t));
       CHK(cast_transpose(x, G.d.in_dim, N, G.d.in_dim, e->xin_b.r(), e->xin_b.ld, want_t ? e->xin_b.t() : (__bf16*)nullptr, e->xin_b.ldt,
                                 nullptr, false, &e->colp, s));
       CHK(refresh_shadows(e, GT_ROLE_G, true, s));
       CHK(stack_forward_b16(e, GT_ROLE_G, e->xin_b.r(), e->xin_b.ld, N, pass0, 1, N, specs, want_t, s));
-      CHK(last_forward_b16(e, GT_ROLE_G, N, y_hat, s));
     } else {
       CHK(stack_forward(e, GT_ROLE_G, x, gx_pitch(e), N, pass0, 1, N, specs, s));
-      const Lin& Lh = G.hidden.back();
-      CHK(linear_forward(e->ws[GT_ROLE_G].act.back().as<float>(), Lh.out, G.last.W, G.last.in, G.last.b, y_hat, G.d.out_dim, N, G.last.in,
-                         G.last.out, G.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s));
     }
+    CHK(out_layer_forward(e, GT_ROLE_G, mlp_top(e, GT_ROLE_G, b16), N, y_hat, s));
   }
   if (is_i2o(G.d.arch)) {
     if (!R) return fail(GT_ERR_INVALID, "In2OutHighwayNet needs the MLPG matrix R (models.py:54)");
@@ -1080,37 +1103,20 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     G.grads_dirty = true;
     return GT_OK;
   }
+  // last_linear: dW = gy^T H_top, db ; dZ_top = (gy W_last) (.) f'(H_top), into the buffer the hidden stack's backward starts from
+  const int H = G.d.hidden_dim;
   if (use_b16(e, GT_ROLE_G)) {
-    // dloss/dy_hat -> bf16 image (both orientations); last_linear: dW = gyT . H_topT^T, dZ_top = (gy . W_lastT^T) (.) f'(H_top)
-    const int H = G.d.hidden_dim;
-    CHK(e->gy_b.ensure(N, Do, true));
-    CHK(cast_transpose(gy, ldgy, N, Do, e->gy_b.r(), e->gy_b.ld, e->gy_b.t(), e->gy_b.ldt, nullptr, false, &e->colp, s));
-    B16Img& top = W.actb.back();
-    CHK(weight_grad_b16(e->gy_b.t(), e->gy_b.ldt, top.t(), top.ldt, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty, e->slabs, s, &W.sdefer));
-    CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * G.last.in + Do, s));
-    const LinShadow& ws = W.wsh[G.hidden.size()];
     CHK(e->dz_b[0].ensure(N, H, true));
-    GemmB16Args g = b16_args();
-    g.A = e->gy_b.r(); g.lda = e->gy_b.ld; g.B = ws.wt.as<__bf16>(); g.ldb = ws.ldwt; g.M = (int)N; g.N = H; g.K = Do;
-    g.epi = B16_BWD_DATA; g.act = ACT_LEAKY_DROPOUT; g.H = top.r(); g.ldh = top.ld; g.drop = W.specs.back();
-    g.Cb = e->dz_b[0].r(); g.ldcb = e->dz_b[0].ld; g.CbT = e->dz_b[0].t(); g.ldcbt = (int)e->dz_b[0].ldt;
-    CHK(launch_gemm_b16(g, 1, s));
+    CHK(out_layer_backward(e, GT_ROLE_G, gy, ldgy, N, mlp_top(e, GT_ROLE_G, true), OutGrad{B16Dst(e->dz_b[0], true), ACT_LEAKY_DROPOUT, W.specs.back(), false},
+                           &W.sdefer, s));
     CHK(stack_backward_b16(e, GT_ROLE_G, e->xin_b.t(), e->xin_b.ldt, N, W.specs, 0, true, nullptr, 0, 0, 0, 0, 0, s));
     G.grads_dirty = true;
     return GT_OK;
   }
-  // last_linear: dW = gy^T H_top, db ; dZ_top = (gy W_last) (.) f'(H_top)
-  const Lin& Lt = G.hidden.back();
-  const int H = G.d.hidden_dim;
   CHK(e->dzA.ensure((size_t)2 * N * H * sizeof(float)));
   CHK(e->dzB.ensure((size_t)2 * N * H * sizeof(float)));
-  const GemmArgs nn_last = backward_data_args(gy, ldgy, G.last.W, G.last.in, 0, e->dzA.as<float>(), H, N, Do, H, ACT_LEAKY_DROPOUT,
-                                              W.act.back().as<float>(), H, W.specs.back());
-  bool rode = false;
-  CHK(linear_backward_weight(gy, ldgy, W.act.back().as<float>(), Lt.out, N, Do, G.last.in, G.last.dW, G.last.db, G.grads_dirty,
-                             e->slabs, e->colp, s, &W.sdefer, &nn_last, &rode));
-  CHK(comm_grads_ready(e, GT_ROLE_G, G.last.dW, (long)Do * G.last.in + Do, s));
-  if (!rode) CHK(launch_gemm(GEMM_NN, nn_last, 1, s));
+  CHK(out_layer_backward(e, GT_ROLE_G, gy, ldgy, N, mlp_top(e, GT_ROLE_G, false), OutGrad{B16Dst(e->dzA.as<float>(), H), ACT_LEAKY_DROPOUT, W.specs.back(), true},
+                         &W.sdefer, s));
   // The first layer's weight gradient reads G's input as its n-contiguous frame operand: with a 16-byte pitch it takes the
   // 16-byte loader and the 64 x 64 tiles.  The caller's tensor when it has one, else the discriminator's input image of this step
   // when that holds the very same x (bit-exact copy), else a pitched copy made once per step (shared with the split first layer
@@ -1340,25 +1346,22 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
       p.npass = 1; p.passes[0] = 0; p.B = p.nseq = B; p.T = T; p.img = x; p.ldc = n.d.in_dim;
       CHK(d_pass_forward(e, p, s));
       if (p.kind == D_SRU) tl_gemm_prec = PREC_F32;      // hidden2out stays a float32 product under either bf16 option
-      const float* top = p.top;
-      const int ld = p.ld_top;
-      return linear_forward(top, ld, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in, n.last.out,
-                            n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
+      return out_layer_forward(e, role, OutTop{p.top, p.ld_top}, N, out, s);
     }
     e->g_pass_valid = false;
     return n.d.arch == GT_ARCH_LSTM ? lstm_forward(e, x, B, T, out, s) : sru_forward(e, x, B, T, out, s);
   }
   const int pass0[1] = {0};
   if (role == GT_ROLE_G) e->g_pass_valid = false;
-  if (use_b16(e, role)) {
+  const bool b16 = use_b16(e, role);
+  if (b16) {
     CHK(e->fwd_b.ensure(N, n.d.in_dim, false));
     CHK(cast_transpose(x, n.d.in_dim, N, n.d.in_dim, e->fwd_b.r(), e->fwd_b.ld, (__bf16*)nullptr, 0, nullptr, false, &e->colp, s));
     CHK(refresh_shadows(e, role, true, s));
     CHK(stack_forward_b16(e, role, e->fwd_b.r(), e->fwd_b.ld, N, pass0, 1, N, specs, false, s));
-    return last_forward_b16(e, role, N, out, s);
+  } else {
+    CHK(stack_forward(e, role, x, n.d.in_dim, N, pass0, 1, N, specs, s));      // (plain forward: dense rows)
   }
-  CHK(stack_forward(e, role, x, n.d.in_dim, N, pass0, 1, N, specs, s));      // (plain forward: dense rows)
-  return linear_forward(e->ws[role].act.back().as<float>(), n.hidden.back().out, n.last.W, n.last.in, n.last.b, out, n.d.out_dim, N, n.last.in,
-                        n.last.out, n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE, no_drop(), s);
+  return out_layer_forward(e, role, mlp_top(e, role, b16), N, out, s);
 }
 

@@ -12,9 +12,11 @@
 //   * every reduction is two-stage with a fixed order => run-to-run bit-reproducible.
 //
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
-// of the two product families), eng_step (the G+D step, its ResultsChannel and the MLP stacks), eng_mlpg (band cache, MLPG launches), eng_dstack (fused
-// discriminator stack), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc (data-parallel communicator), eng_ops (stand-alone
-// operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage (GT_KERNEL) so that several units may include them.
+// of the two product families; eng_gemm_b16 also holds the stacks' bf16 vocabulary: LinShadow::ensure / shadow_cast, b16_forward / b16_backward_data),
+// eng_step (the G+D step, its ResultsChannel, the MLP stacks and the output layer of every stack: out_layer_forward / out_layer_backward), eng_mlpg
+// (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
+// (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage
+// (GT_KERNEL) so that several units may include them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -155,7 +157,18 @@ struct B16Img {
   void release() { rm.release(); tr.release(); }
 };
 // bf16 shadows of one nn.Linear weight (out, in): w [out][ldw] feeds the forward product, wt [in][ldwt] backward-data
-struct LinShadow { Scratch w, wt; int ldw = 0, ldwt = 0; void release() { w.release(); wt.release(); } };
+struct LinShadow {
+  Scratch w, wt; int ldw = 0, ldwt = 0;
+  __bf16* r() const { return w.as<__bf16>(); }
+  __bf16* t() const { return wt.as<__bf16>(); }
+  int ensure(int out, int in) {
+    ldw = pad8(in); ldwt = pad8(out);
+    CHK(w.ensure((size_t)out * ldw * 2 + 64));
+    CHK(wt.ensure((size_t)in * ldwt * 2 + 64));
+    return GT_OK;
+  }
+  void release() { w.release(); wt.release(); }
+};
 static inline bool is_i2o(int arch) { return arch == GT_ARCH_IN2OUT || arch == GT_ARCH_IN2OUT_RNN; }
 static inline bool has_lstm_body(int arch) { return arch == GT_ARCH_LSTM || arch == GT_ARCH_IN2OUT_RNN; }
 struct LstmDirP { float *Wih, *Whh, *bih, *bhh, *dWih, *dWhh, *dbih, *dbhh; };
@@ -474,6 +487,21 @@ int cat_cast_transpose(const gt::CatSrc& src, long rows, int cols, __bf16* out, 
 int catdrop_cast_transpose(const gt::CatDropSrc& src, long rows, int cols, __bf16* out, int ldo, __bf16* outT, long ldt, hipStream_t s);
 int weight_grad_b16(const __bf16* dZT, long lddzt, const __bf16* XT, long ldxt, long rows, int out, int in, float* dW, float* db,
                     bool accumulate, Scratch& slabs, hipStream_t s, SlabDefer* defer = nullptr);
+// the float32 matrix W (out, in) into rows [r0, r0 + out) of sh.w and columns [r0, r0 + out) of sh.wt (sh sized by LinShadow::ensure)
+int shadow_cast(LinShadow& sh, const float* W, int r0, int out, int in, hipStream_t s);
+// where a product of the family leaves its result: a float32 matrix (+= when accumulate), or an image, with its transposed twin when asked
+struct B16Dst {
+  float* C = nullptr; int ldc = 0; B16Img* img = nullptr; bool twin = false, accumulate = false;
+  B16Dst(float* C_, int ldc_, bool accumulate_ = false) : C(C_), ldc(ldc_), accumulate(accumulate_) {}
+  B16Dst(B16Img& img_, bool twin_) : img(&img_), twin(twin_) {}
+};
+// The two product shapes of the stacks, one launch each (launch_gemm_b16(g, 1, s)); W [n][ldw]: a shadow's w or wt, from whichever row.
+//   forward:        dst [rows][n] = act(X [rows][k] . W^T + bias), dropout site `drop` under ACT_LEAKY_DROPOUT
+//   backward-data:  dst [rows][n] = (dZ [rows][k] . W^T) (.) f'(H), f' and `drop` of the layer that produced H (act_prev == ACT_NONE: H is null)
+int b16_forward(const __bf16* X, int ldx, long rows, const __bf16* W, int ldw, int n, int k, const float* bias, int act,
+                const gt::DropoutSpec& drop, const B16Dst& dst, hipStream_t s);
+int b16_backward_data(const __bf16* dZ, int lddz, long rows, const __bf16* W, int ldw, int n, int k, int act_prev, const B16Img* H,
+                      const gt::DropoutSpec& drop, const B16Dst& dst, hipStream_t s);
 
 // eng_mlpg.hip: a launch takes the band it goes through, as ensure_band handed it back
 int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBand** out);
@@ -487,6 +515,17 @@ int mlpg_backward(gt_engine* e, const float* gs, int ldgs, const int* scol, cons
 // eng_step.hip
 // ------------------------------------------------------------------------------------------
 int cond_dim(gt_engine* e);
+// The output layer (`last`: last_linear / hidden2out, + sigmoid iff last_sigmoid) of every stack and role, in either storage form.
+// OutTop, the rows it reads.  float32: x / ld.  bf16 storage: img and sh, the shadow of `last`; img_ready: the image is written already (an MLP
+// stack's top activation, a folded SRU scan's output), else the forward casts x / ld into it, with the transposed twin iff want_t.
+struct OutTop { const float* x = nullptr; int ld = 0; B16Img* img = nullptr; const LinShadow* sh = nullptr; bool img_ready = false, want_t = false; };
+// OutGrad, where d loss / d top goes (the buffer the stack below reads) and what it passes on the way.  act_prev = ACT_LEAKY_DROPOUT: times f'(top)
+// at dropout site `drop` (an MLP's top hidden layer); ACT_NONE: as it is (recurrent stacks).  ride: the float32 product is offered to the weight
+// gradient's launch as its rider and launched on its own only when it did not ride.
+struct OutGrad { B16Dst to; int act_prev; gt::DropoutSpec drop; bool ride; };
+int out_layer_forward(gt_engine* e, int role, const OutTop& top, long rows, float* out, hipStream_t s);
+int out_layer_backward(gt_engine* e, int role, const float* gy, int ldgy, long rows, const OutTop& top, const OutGrad& dst, SlabDefer* defer,
+                       hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // eng_comm.hip
