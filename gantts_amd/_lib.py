@@ -188,6 +188,10 @@ class AssembleCase(C.Structure):
                                              "y_static", "mask", "lengths")])
 
 
+class AssembleShard(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("world", C.c_int32), ("B_global", C.c_int32), ("pad_", C.c_int32), ("tv_global", C.c_void_p)]
+
+
 class CorpusStatsCase(C.Structure):
     _fields_ = ([("D", C.c_int32), ("ld", C.c_int32)] + [(n, C.c_int64) for n in ("F", "n_seg", "prior_count")]
                 + [(n, C.c_void_p) for n in ("A", "seg", "prior_mean", "prior_var", "workspace")] + [("workspace_bytes", C.c_int64)]
@@ -264,6 +268,7 @@ SIGNATURES = {
     "gt_op_mlpg_var": (_I, [C.POINTER(MlpgVarCase), _P]),
     "gt_mlpg_var_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_op_assemble_batch": (_I, [C.POINTER(AssembleCase), _P]),
+    "gt_op_assemble_shard": (_I, [C.POINTER(AssembleCase), C.POINTER(AssembleShard), _P]),
     "gt_corpus_stats_workspace_bytes": (_L, [_L, C.c_int32]),
     "gt_op_corpus_stats": (_I, [C.POINTER(CorpusStatsCase), _P]),
     "gt_clear_faults": (_I, [_P, _P]),

@@ -4,7 +4,10 @@
 //   gi (B, T, Dx + nz) on pitch ld_gi   [ scaled x | z ~ U[0,1) | zero pad columns ]
 //   y (B, T, Dy)   y_static (B, T, Ds)   mask (B, T)   lengths (B)
 // from the un-normalised corpus X_all [F][ldX], Y_all [F][ldY] and one row of the epoch table per sequence:
-//   table[slot] = { first frame, length, corpus utterance index }     (int64, slot = first_slot + b)
+//   table[slot] = { first frame, length, corpus utterance index }     (int64, slot = first_slot + b * slot_stride)
+// gt_op_assemble_batch passes slot_stride 1.  gt_op_assemble_shard (one data-parallel rank's share of a batch) passes first_slot + rank
+// and stride world -- local sequence b is sequence rank + world * b of the whole batch, padded to the WHOLE batch's T -- and may ask
+// for tv_global, the valid frames of the whole batch: sum of min(length, T) over its slots, every rank's launch writing the same value.
 //
 // Arithmetic: what numpy does on the host, bit for bit.  The statistics' dtype of a side (SX, SY) is that side's compute dtype (numpy promotes the float32
 // utterance to float64 when the statistics are float64, and np.array(..., dtype=np.float32) rounds ONCE at the end); every operation is
@@ -41,7 +44,10 @@ struct AssembleArgs {
   int ldX, ldY, ld_gi, ld_y, ld_ys;
   int x_kind, y_kind, n_windows;
   uint32_t key0, key1;
-  long F, first_slot;
+  long F, first_slot, slot_stride;         // sequence b is table slot first_slot + b * slot_stride
+  long tv_first;                           // tv_global: the slots [tv_first, tv_first + tv_count) of the WHOLE batch
+  int tv_count;
+  double* tv_global;                       // null: not wanted
   const float *X_all, *Y_all;
   const void *x_a, *x_b, *y_a, *y_b;       // MINMAX: a = scale_, b = min_;  MEANVAR: a = mean, b = std
   const long* table;
@@ -70,6 +76,13 @@ __device__ __forceinline__ ST assemble_scale(float v, int kind, ST a, ST b) {
   if (kind == 1) { const ST m = x * a; return m + b; }
   if (kind == 2) { const ST d = x - a; return d / b; }
   return x;
+}
+
+// Valid frames of one table row in a batch padded to T: a row that does not lie inside the corpus reads nothing (the sequence comes
+// out empty), a length above T is cut.
+__device__ __forceinline__ long assemble_row_length(long start, long len, long F, int T) {
+  if (start < 0 || len < 0 || start > F || len > F - start) len = 0;
+  return len > T ? (long)T : len;
 }
 
 template <typename SX, typename SY, bool DELTA>
@@ -105,6 +118,19 @@ __global__ __launch_bounds__(ASM_WAVES * 64) void assemble_batch_kernel(const As
   __syncthreads();
   float* my_stage = stage + (long)wave * g.ldY;
 
+  // ---- tv_global (a sharded launch): the valid frames of the WHOLE batch, summed by wave 0 of workgroup 0 over the batch's table rows.
+  // An integer sum -- exact, and the same on every rank --, converted once and stored by one lane.
+  if (g.tv_global && blockIdx.x == 0 && wave == 0) {
+    long long sum = 0;
+    for (int i = lane; i < g.tv_count; i += 64) {
+      const long* e = g.table + 3 * (g.tv_first + i);
+      sum += assemble_row_length(e[0], e[1], g.F, g.T);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) *g.tv_global = (double)sum;
+  }
+
   const long n_rows = (long)g.B * g.T;
   const long row0 = ((long)blockIdx.x * ASM_WAVES + wave) * ASM_ROWS_PER_WAVE;
   // per row of this wave (all wave-uniform): does it exist, is it a valid frame, where does it come from
@@ -118,12 +144,9 @@ __global__ __launch_bounds__(ASM_WAVES * 64) void assemble_batch_kernel(const As
     exists[j] = r < n_rows;
     const long b = exists[j] ? r / g.T : 0;
     tt[j] = exists[j] ? (int)(r - b * g.T) : 0;
-    const long* e = g.table + 3 * (g.first_slot + b);
-    long start = e[0], len = e[1];
+    const long* e = g.table + 3 * (g.first_slot + b * g.slot_stride);
+    const long start = e[0], len = assemble_row_length(start, e[1], g.F, g.T);
     utt[j] = (uint32_t)e[2];
-    // a table row that does not lie inside the corpus reads nothing: the sequence comes out empty
-    if (start < 0 || len < 0 || start > g.F || len > g.F - start) len = 0;
-    if (len > g.T) len = g.T;
     ustart[j] = start; ulen[j] = len;
     valid[j] = exists[j] && tt[j] < len;
     src[j] = valid[j] ? start + tt[j] : 0;

@@ -1,4 +1,5 @@
-// libgantts_hip.so -- the data path's stand-alone operators: gt_op_assemble_batch (one training batch out of a device-resident corpus)
+// libgantts_hip.so -- the data path's stand-alone operators: gt_op_assemble_batch (one training batch out of a device-resident corpus),
+// gt_op_assemble_shard (one data-parallel rank's share of it)
 // and gt_op_corpus_stats (the normalisation statistics of one side of that corpus)
 #include "engine_internal.hip.h"
 #include "data_kernels.hip.h"
@@ -22,7 +23,10 @@ static int launch_assemble(const AssembleArgs& a, hipStream_t s) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
+static bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+// Both entry points: sh == null is gt_op_assemble_batch (slot stride 1, no tv_global), otherwise one rank's share of the batch.
+static int assemble(const gt_assemble_case* c, const gt_assemble_shard* sh, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "assemble_batch: null case");
   if (!c->X_all || !c->Y_all || !c->table) return fail(GT_ERR_INVALID, "assemble_batch: null corpus or table");
   if (c->B < 1 || c->T < 1 || c->Dx < 1 || c->Dy < 1 || c->nz < 0 || c->Ds < 0 || c->F < 0)
@@ -31,9 +35,20 @@ extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
   if (c->ldX < c->Dx || c->ldY < c->Dy || c->ldX % 4 || c->ldY % 4 || !aligned16(c->X_all) || !aligned16(c->Y_all))
     return fail(GT_ERR_INVALID, "assemble_batch: the corpus rows must sit on a 16-byte pitch (ldX=%d for %d, ldY=%d for %d columns)", c->ldX,
                 c->Dx, c->ldY, c->Dy);
-  if (c->first_slot < 0 || c->n_slots < 0 || c->first_slot + c->B > c->n_slots)
+  if (sh) {
+    if (sh->world < 1 || sh->rank < 0 || sh->rank >= sh->world)
+      return fail(GT_ERR_INVALID, "assemble_shard: rank %d of a world of %d", sh->rank, sh->world);
+    if (sh->B_global < 1) return fail(GT_ERR_INVALID, "assemble_shard: B_global = %d", sh->B_global);
+    const long share = sh->rank < sh->B_global ? ((long)sh->B_global - sh->rank + sh->world - 1) / sh->world : 0;
+    if (share < 1 || c->B != share)
+      return fail(GT_ERR_INVALID, "assemble_shard: rank %d of %d holds %ld of %d sequences, the case has B = %d", sh->rank, sh->world, share,
+                  sh->B_global, c->B);
+    if (!aligned8(sh->tv_global)) return fail(GT_ERR_INVALID, "assemble_shard: tv_global must be 8-byte aligned");
+  }
+  const long n_seq = sh ? sh->B_global : c->B;      // the slots of the whole batch
+  if (c->first_slot < 0 || c->n_slots < 0 || c->first_slot > c->n_slots - n_seq)      // (n_seq >= 1: no overflow)
     return fail(GT_ERR_INVALID, "assemble_batch: slots [%lld, %lld) of a table of %lld", (long long)c->first_slot,
-                (long long)(c->first_slot + c->B), (long long)c->n_slots);
+                (long long)((unsigned long long)c->first_slot + (unsigned long long)n_seq), (long long)c->n_slots);
   for (int k = 0; k < 2; ++k) {
     const int kind = k ? c->y_kind : c->x_kind;
     if (kind < GT_SCALE_NONE || kind > GT_SCALE_MEANVAR) return fail(GT_ERR_INVALID, "assemble_batch: unknown scaling kind %d", kind);
@@ -60,7 +75,8 @@ extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
   a.ldX = c->ldX; a.ldY = c->ldY; a.ld_gi = c->ld_gi; a.ld_y = c->ld_y; a.ld_ys = c->ld_ys;
   a.x_kind = c->x_kind; a.y_kind = c->y_kind; a.n_windows = delta ? c->n_windows : 0;
   a.key0 = c->key0; a.key1 = c->key1;
-  a.F = c->F; a.first_slot = c->first_slot;
+  a.F = c->F; a.first_slot = c->first_slot + (sh ? sh->rank : 0); a.slot_stride = sh ? sh->world : 1;
+  a.tv_first = c->first_slot; a.tv_count = (int)n_seq; a.tv_global = sh ? sh->tv_global : nullptr;
   a.X_all = c->X_all; a.Y_all = c->Y_all;
   a.x_a = c->x_a; a.x_b = c->x_b; a.y_a = c->y_a; a.y_b = c->y_b;
   a.table = (const long*)c->table;
@@ -81,6 +97,13 @@ extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) {
     case 6: return launch_assemble<double, double, false>(a, s);
     default: return launch_assemble<double, double, true>(a, s);
   }
+}
+
+extern "C" int gt_op_assemble_batch(const gt_assemble_case* c, void* stream) { return assemble(c, nullptr, stream); }
+
+extern "C" int gt_op_assemble_shard(const gt_assemble_case* c, const gt_assemble_shard* s, void* stream) {
+  if (!s) return fail(GT_ERR_INVALID, "assemble_shard: null shard");
+  return assemble(c, s, stream);
 }
 
 extern "C" int64_t gt_corpus_stats_workspace_bytes(int64_t F, int32_t D) {

@@ -266,11 +266,16 @@ def get_tts_data_loaders(X, Y, X_data_min, X_data_max, Y_data_mean, Y_data_std, 
 # ---- device side --------------------------------------------------------------------------------
 class DeviceBatch(object):
     """One length-sorted batch resident on the device (what train_loop consumes per step)."""
-    __slots__ = ("x", "y", "lengths", "cpu_lengths", "max_len", "ready", "generator_input", "y_static", "mask")
+    __slots__ = ("x", "y", "lengths", "cpu_lengths", "max_len", "ready", "generator_input", "y_static", "mask", "tv_global")
 
-    def __init__(self, x, y, lengths, cpu_lengths, ready, generator_input=None, y_static=None, mask=None):
+    def __init__(self, x, y, lengths, cpu_lengths, ready, generator_input=None, y_static=None, mask=None, tv_global=None, max_len=None):
         self.x, self.y, self.lengths, self.cpu_lengths = x, y, lengths, cpu_lengths
-        self.max_len = int(cpu_lengths[0]) if len(cpu_lengths) else 0
+        # max_len: the T the batch is padded to where that is not its own longest sequence -- a data-parallel rank's share of a batch is
+        # padded to the WHOLE batch's longest sequence, which may live on another rank
+        self.max_len = int(max_len) if max_len is not None else (int(cpu_lengths[0]) if len(cpu_lengths) else 0)
+        # tv_global: the valid frames of the WHOLE batch as a 1-element float64 device tensor (a sharded ResidentLoader; the loss
+        # normaliser of the data-parallel step), None where the batch is the whole batch
+        self.tv_global = tv_global
         self.ready = ready
         # what train_loop derives from (x, y, lengths) per batch, when the loader has made it already (ResidentLoader): [x | z] with
         # x its prefix view, get_static_features(y), sequence_mask(lengths).unsqueeze(-1); None: train_loop derives it
@@ -422,6 +427,31 @@ def plan_epoch(offsets, lengths, batches):
             u = idx[k]
             rows.append((int(offsets[u]), int(lengths[u]), u))
     return np.array(rows, dtype=np.int64).reshape(-1, 3), plan
+
+
+def shard_plan(plan, rank, world, short_batch="error"):
+    """One data-parallel rank's share of an epoch planned by ``plan_epoch`` (no device): per batch ``(first_slot, B_global, B_local, T,
+    local lengths)``.  Whole sequences are dealt round-robin -- local sequence b of rank r is sequence r + world * b of the length-sorted
+    batch, so the local lengths are ``lengths[rank::world]`` -- and ``T`` stays the WHOLE batch's longest sequence on every rank.
+
+    A batch with fewer sequences than ranks cannot give every rank one; the last batch of an epoch (the loader's ``drop_last=False``) is
+    the usual case.  ``short_batch="error"`` raises ValueError for it -- at plan time, on every rank alike --, ``short_batch="drop"``
+    leaves it out on every rank."""
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("shard_plan: rank %d of a world of %d" % (rank, world))
+    if short_batch not in ("error", "drop"):
+        raise ValueError("shard_plan: short_batch is \"error\" or \"drop\", not %r" % (short_batch,))
+    out = []
+    for k, (first, B, T, cpu_lengths) in enumerate(plan):
+        if B < world:
+            if short_batch == "error":
+                raise ValueError("shard_plan: batch %d has %d sequences for a world of %d ranks; every rank needs one "
+                                 "(short_batch=\"drop\" leaves such a batch out)" % (k, B, world))
+            continue
+        local = list(cpu_lengths[rank::world])
+        out.append((first, B, len(local), T, local))
+    return out
 
 
 def _stat_vector(v, D, name):
@@ -677,9 +707,18 @@ class ResidentLoader(object):
 
     Noise: Philox4x32-10 keyed by (``hp.generator_noise_seed`` low word, draw counter); the draw counter starts at ``first_draw`` and
     advances once per epoch (per ``__iter__``); the counters are (corpus utterance index, t * ceil(nz / 4) + column group of 4), so a
-    frame's noise depends on its utterance, not on the utterance's place in the batch (data_kernels.hip.h)."""
+    frame's noise depends on its utterance, not on the utterance's place in the batch (data_kernels.hip.h).
 
-    def __init__(self, dataset, batch_size, shuffle, hp, batch_sampler=None, device="cuda", first_draw=0):
+    Data parallelism (``world > 1``): every rank holds the whole corpus and plans the whole epoch; rank ``rank`` assembles sequences
+    ``rank::world`` of each length-sorted batch (``shard_plan``), padded to the WHOLE batch's T, through gt_op_assemble_shard, whose
+    launch also writes the whole batch's valid-frame count (``DeviceBatch.tv_global``, the step's loss normaliser -- no collective for
+    it).  The ranks' rows are the rows of the one-process batch, noise included.  EVERY RANK MUST PLAN THE SAME EPOCH: the loader's own
+    shuffling then draws from a private ``torch.Generator`` seeded with ``hp.shard_sampler_seed`` (default ``hp.generator_noise_seed``),
+    whose state advances from epoch to epoch identically on all ranks; a caller's ``batch_sampler`` must be rank-identical itself.
+    ``last_table_crc`` (zlib.crc32 of the epoch table's bytes) lets a driver enforce it (``parallel.resident_epoch`` does).
+    ``short_batch``: see ``shard_plan``.  With ``world == 1`` nothing changes."""
+
+    def __init__(self, dataset, batch_size, shuffle, hp, batch_sampler=None, device="cuda", first_draw=0, rank=0, world=1, short_batch="error"):
         from torch.utils import data as data_utils
         from .multistream import static_columns
         self.dataset, self.hp, self.device = dataset, hp, device
@@ -689,10 +728,20 @@ class ResidentLoader(object):
                 raise ValueError("ResidentLoader: this corpus was made from raw arrays and has no statistics attached yet; compute them "
                                  "(corpus.minmax / corpus.meanvar) and call corpus.attach_statistics(dataset) first")
             self.dataset = dataset.dataset
+        self.rank, self.world, self.short_batch = int(rank), int(world), short_batch
+        shard_plan([], self.rank, self.world, short_batch)       # the argument checks
+        self.last_table_crc = None
         n = len(self.corpus.lengths)
+        self._short_last = False       # the loader's own last batch is shorter than the world and is dropped
         if batch_sampler is None:
-            sampler = data_utils.RandomSampler(range(n)) if shuffle else data_utils.SequentialSampler(range(n))
+            if shuffle and self.world > 1:
+                g = torch.Generator()
+                g.manual_seed(int(getattr(hp, "shard_sampler_seed", getattr(hp, "generator_noise_seed", 0))))
+                sampler = data_utils.RandomSampler(range(n), generator=g)
+            else:
+                sampler = data_utils.RandomSampler(range(n)) if shuffle else data_utils.SequentialSampler(range(n))
             batch_sampler = data_utils.BatchSampler(sampler, int(batch_size), drop_last=False)
+            self._short_last = short_batch == "drop" and 0 < n % int(batch_size) < self.world
         self.batch_sampler = batch_sampler
         self.nz = int(hp.generator_noise_dim) if getattr(hp, "generator_add_noise", False) else 0
         self.seed = int(getattr(hp, "generator_noise_seed", 0))
@@ -703,11 +752,15 @@ class ResidentLoader(object):
         self._scol = None
 
     def __len__(self):
-        return len(self.batch_sampler)
+        return len(self.batch_sampler) - int(self._short_last)
 
     def plan(self):
-        """The host plan of the next epoch (draws the sampler): see ``plan_epoch``."""
-        return plan_epoch(self.corpus.offsets, self.corpus.lengths, self.batch_sampler)
+        """The host plan of the next epoch (draws the sampler): see ``plan_epoch``.  The WHOLE epoch on every rank (``shard_plan``
+        takes this rank's share of it); sets ``last_table_crc``."""
+        import zlib
+        table, plan = plan_epoch(self.corpus.offsets, self.corpus.lengths, self.batch_sampler)
+        self.last_table_crc = zlib.crc32(table.tobytes())
+        return table, plan
 
     def _case(self, table, n_slots):
         from . import _lib as L
@@ -731,11 +784,14 @@ class ResidentLoader(object):
 
     def begin_epoch(self):
         """Uploads the corpus if it is not resident yet, plans the next epoch on the host and uploads its table: ``(case, plan)`` for
-        ``assemble``.  Advances the draw counter."""
+        ``assemble``.  Advances the draw counter.  With ``world > 1`` the plan is this rank's ``shard_plan``; the table is the whole
+        epoch's on every rank."""
         c = self.corpus.upload(self.device)
         if self._scol is None:
             self._scol = torch.from_numpy(self.scol_host).to(c.device) if len(self.scol_host) else torch.zeros(1, dtype=torch.int32, device=c.device)
         table_host, plan = self.plan()
+        if self.world > 1:
+            plan = shard_plan(plan, self.rank, self.world, self.short_batch)
         if not plan:
             return None, plan
         table = torch.from_numpy(table_host).pin_memory().to(c.device, non_blocking=True)      # the epoch's one upload
@@ -744,9 +800,12 @@ class ResidentLoader(object):
         self.draws += 1
         return case, plan
 
-    def assemble(self, case, first, B, T, out=None):
+    def assemble(self, case, first, B, T, out=None, B_global=None, tv_global=None):
         """One batch of the epoch in one launch on the current stream: ``(gi (B, T, ld_gi), y, y_static, mask (B, T, 1), lengths)``.
-        ``out``: the five buffers to write instead of fresh ones (dense, gi on its pitch ``roundup(Dx + nz, 4)``)."""
+        ``out``: the five buffers to write instead of fresh ones (dense, gi on its pitch ``roundup(Dx + nz, 4)``).
+        With ``world > 1``: ``B`` is this rank's share of the ``B_global`` sequences in the slots from ``first``, ``T`` the whole
+        batch's, the launch is gt_op_assemble_shard and a sixth element follows: ``tv_global``, the 1-element float64 tensor (the given
+        one or a fresh one) that receives the whole batch's valid-frame count."""
         import ctypes as C
         from . import _lib as L
         c = self.corpus
@@ -764,32 +823,57 @@ class ResidentLoader(object):
         case.ld_gi, case.ld_y, case.ld_ys = ld_gi, Dy, Ds
         case.gi, case.y, case.y_static = gi.data_ptr(), y.data_ptr(), ys.data_ptr() if Ds else None
         case.mask, case.lengths = mask.data_ptr(), lengths.data_ptr()
-        L.check(L.lib.gt_op_assemble_batch(C.byref(case), L.current_stream()))
-        return out
+        if self.world == 1:
+            L.check(L.lib.gt_op_assemble_batch(C.byref(case), L.current_stream()))
+            return out
+        if B_global is None:
+            raise ValueError("ResidentLoader.assemble: a sharded loader needs B_global, the sequence count of the whole batch")
+        if tv_global is None:
+            tv_global = torch.empty(1, device=c.device, dtype=torch.float64)
+        if tuple(tv_global.shape) != (1,) or tv_global.dtype != torch.float64 or not tv_global.is_cuda:
+            raise ValueError("ResidentLoader.assemble: tv_global is a 1-element float64 device tensor")
+        shard = L.AssembleShard()
+        shard.rank, shard.world, shard.B_global, shard.tv_global = self.rank, self.world, int(B_global), tv_global.data_ptr()
+        L.check(L.lib.gt_op_assemble_shard(C.byref(case), C.byref(shard), L.current_stream()))
+        return tuple(out) + (tv_global,)
 
     def __iter__(self):
         case, plan = self.begin_epoch()
+        yield from self.batches(case, plan)
+
+    def batches(self, case, plan):
+        """The ``DeviceBatch``es of an epoch begun with ``begin_epoch``."""
         Dx, nz = self.corpus.Dx, self.nz
-        for first, B, T, cpu_lengths in plan:
-            gi, y, ys, mask, lengths = self.assemble(case, first, B, T)
+        for entry in plan:
+            if self.world == 1:
+                first, B, T, cpu_lengths = entry
+                gi, y, ys, mask, lengths = self.assemble(case, first, B, T)
+                tv = None
+            else:
+                first, B_global, B, T, cpu_lengths = entry
+                gi, y, ys, mask, lengths, tv = self.assemble(case, first, B, T, B_global=B_global)
             g = gi if gi.size(-1) == Dx + nz else gi[:, :, :Dx + nz]
-            yield DeviceBatch(gi[:, :, :Dx] if gi.size(-1) != Dx else gi, y, lengths, cpu_lengths, None, generator_input=g, y_static=ys, mask=mask)
+            yield DeviceBatch(gi[:, :, :Dx] if gi.size(-1) != Dx else gi, y, lengths, cpu_lengths, None, generator_input=g, y_static=ys, mask=mask,
+                              tv_global=tv, max_len=T)
 
 
-def _resident_loaders(corpora, datasets, hp):
+def _resident_loaders(corpora, datasets, hp, rank=0, world=1, short_batch="error"):
     loaders = {}
     for ph, shuffle, first_draw in (("train", True, 0), ("test", False, 1 << 31)):      # the draw counters of _loaders
         corpora[ph].attach_statistics(datasets[ph])
-        loaders[ph] = ResidentLoader(corpora[ph], hp.batch_size, shuffle, hp, device=corpora[ph].device, first_draw=first_draw)
+        loaders[ph] = ResidentLoader(corpora[ph], hp.batch_size, shuffle, hp, device=corpora[ph].device, first_draw=first_draw,
+                                     rank=rank, world=world, short_batch=short_batch)
     return loaders
 
 
-def resident_tts_loaders(X, Y, hp, device="cuda"):
+def resident_tts_loaders(X, Y, hp, device="cuda", rank=0, world=1, short_batch="error"):
     """train.py:744-770 on a device-resident corpus, raw arrays in: ``X``, ``Y`` are the reference's ``{"train": ..., "test": ...}`` of
     utterance sequences.  Each phase is uploaded once; the TRAIN statistics -- ``minmax`` of X, ``meanvar`` of Y -- are one device
     pass per side (gt_op_corpus_stats), no host arithmetic on frames; the ordinary ``TTSDataset``s carry them (``loader.dataset``), and
     the uploaded corpora go to the ``ResidentLoader``s as they are.  Returns ``(loaders, stats)``, ``stats`` under the names of the
-    ``.npy`` files the reference saves: X_data_min, X_data_max, Y_data_mean, Y_data_var."""
+    ``.npy`` files the reference saves: X_data_min, X_data_max, Y_data_mean, Y_data_var.  ``rank``, ``world``, ``short_batch``: a
+    data-parallel rank's loaders (``ResidentLoader``); every rank uploads the whole corpus and computes the statistics itself -- the
+    statistics pass is bit-identical from run to run, so the ranks agree without an exchange."""
     corpora = {ph: ResidentCorpus.from_arrays(X[ph], Y[ph], device=device) for ph in ("train", "test")}
     X_data_min, X_data_max = corpora["train"].minmax("x")
     Y_data_mean, Y_data_var = corpora["train"].meanvar("y")
@@ -797,12 +881,13 @@ def resident_tts_loaders(X, Y, hp, device="cuda"):
     datasets = {ph: TTSDataset(MemoryCacheDataset(X[ph], cache_size=hp.cache_size), MemoryCacheDataset(Y[ph], cache_size=hp.cache_size),
                                X_data_min, X_data_max, Y_data_mean, Y_data_std, hp=hp) for ph in corpora}
     stats = dict(X_data_min=X_data_min, X_data_max=X_data_max, Y_data_mean=Y_data_mean, Y_data_var=Y_data_var)
-    return _resident_loaders(corpora, datasets, hp), stats
+    return _resident_loaders(corpora, datasets, hp, rank, world, short_batch), stats
 
 
-def resident_vc_loaders(X, Y, hp, device="cuda"):
+def resident_vc_loaders(X, Y, hp, device="cuda", rank=0, world=1, short_batch="error"):
     """train.py:725-741 on a device-resident corpus: the joint ``meanvar`` over the TRAIN X continued over the TRAIN Y, each cut to the
-    utterance lengths, on the device; ``VCDataset``s carry the result.  Returns ``(loaders, stats)`` with data_mean, data_var."""
+    utterance lengths, on the device; ``VCDataset``s carry the result.  Returns ``(loaders, stats)`` with data_mean, data_var.
+    ``rank``, ``world``, ``short_batch`` as in ``resident_tts_loaders``."""
     corpora = {ph: ResidentCorpus.from_arrays(X[ph], Y[ph], device=device) for ph in ("train", "test")}
     train = corpora["train"]
     data_mean, data_var, last_sample_count = train.meanvar("x", train.lengths, return_last_sample_count=True)
@@ -810,4 +895,4 @@ def resident_vc_loaders(X, Y, hp, device="cuda"):
     data_std = np.sqrt(data_var)
     datasets = {ph: VCDataset(MemoryCacheDataset(X[ph], cache_size=hp.cache_size), MemoryCacheDataset(Y[ph], cache_size=hp.cache_size),
                               data_mean, data_std) for ph in corpora}
-    return _resident_loaders(corpora, datasets, hp), dict(data_mean=data_mean, data_var=data_var)
+    return _resident_loaders(corpora, datasets, hp, rank, world, short_batch), dict(data_mean=data_mean, data_var=data_var)

@@ -109,6 +109,7 @@ class StepEngine(object):
         self._ld_gx = self._ld_cx = 0            # row pitches last announced through gt_set_x_pitch (0 = dense)
         self._pitch_sent = (0, 0)
         self._opt_bf16 = False
+        self._dp_world = 1                       # ranks the minibatch is dealt over (comm_init / set_shard); train.apply_generator reads it
         nW = len(hp.windows)
         ss = [s // nW if d else s for s, d in zip(hp.stream_sizes, hp.has_dynamic_features)]
         self.static_dim = int(sum(ss))
@@ -172,6 +173,7 @@ class StepEngine(object):
 
     def comm_destroy(self):
         check(lib.gt_comm_destroy(self._h))
+        self._dp_world = 1
 
     def comm_ipc_export(self):
         """This rank's interprocess arena for the two-shot all-reduce (``gt_comm_ipc_export``): the handle to ship to every rank."""

@@ -12,6 +12,8 @@ Exchange steps per global step:
   3. G step: same with G's flat gradient (the D->G "leak" gradient stays local: it is a
      per-frame upstream gradient, already normalised by the global Tv).
 Gradients are single flat buffers (<= 19 MB), so each exchange is ONE all-reduce per network.
+A batch that carries ``tv_global`` (a sharded ``data.ResidentLoader``: the launch that assembles this rank's share of the batch
+also writes the whole batch's valid-frame count, the same integer sum on every rank) needs no exchange 1: two collectives per step.
 
 The class only orchestrates; compute goes through a backend object with the split-phase methods
 of ``StepEngine`` (``*_begin`` / ``*_end``), which lets the CPU tests drive it with the oracle.
@@ -75,6 +77,8 @@ class DataParallelStep(object):
         generator scalars as a ``LazyResult`` (no host wait at the end of the step)."""
         be = self.backend
         tv_work = None
+        if tv_global is None and isinstance(batch, dict):
+            tv_global = batch.get("tv_global")       # computed on every rank by the batch's own assembly: no mask.sum(), no all-reduce, no host read
         if tv_global is None:
             if getattr(be, "device_normalizer", False) and be.mask_of(batch).is_cuda:
                 # the global valid-frame count stays on the device: its all-reduce overlaps the generator
@@ -120,6 +124,55 @@ class DataParallelStep(object):
             else:
                 g_res = be.update_generator_end(batch, adv_w, mse_w, mge_w, phase)
         return d_res, g_res
+
+
+def step_batch(device_batch, hp):
+    """The batch ``HipStepBackend`` takes, from a ``data.DeviceBatch`` of a ``ResidentLoader``: ``dict(x=, g_in=, y=, y_static=, mask=,
+    lengths=, R=, tv_global=)``.  ``R`` is the MLPG band for the batch's padded length -- ``max_len``, on a data-parallel rank the
+    WHOLE batch's T --, or None without dynamic features; ``tv_global`` is None on an unsharded batch."""
+    from . import paramgen
+    b = device_batch
+    if b.generator_input is None or b.y_static is None or b.mask is None:
+        raise ValueError("step_batch: a DeviceBatch of a ResidentLoader is needed (generator_input, y_static and mask set)")
+    R = paramgen.unit_variance_mlpg_band(hp.windows, b.max_len) if any(hp.has_dynamic_features) else None
+    return dict(x=b.x, g_in=b.generator_input, y=b.y, y_static=b.y_static, mask=b.mask, lengths=b.cpu_lengths, R=R, tv_global=b.tv_global)
+
+
+def _same_plan_everywhere(crc, all_reduce_max):
+    """True if every rank holds ``crc``: MAX over the ranks of (crc, -crc) is (crc, -crc) only then."""
+    t = torch.tensor([int(crc), -int(crc)], dtype=torch.int64)
+    t = all_reduce_max(t)
+    return int(t[0]) == int(crc) and int(t[1]) == -int(crc)
+
+
+def _all_reduce_max(t, group=None):
+    if dist.get_backend(group) == "nccl":
+        d = t.cuda()
+        dist.all_reduce(d, op=dist.ReduceOp.MAX, group=group)
+        return d.cpu()
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t
+
+
+def resident_epoch(dp, loader, phase="train", all_reduce_max=None, **weights):
+    """One epoch of a sharded ``data.ResidentLoader`` through ``dp.step(..., lazy_g=True)``: the list of the per-batch
+    ``(d_result, g_result)``.  ``weights``: ``adv_w``, ``mse_w``, ``mge_w``, ``update_d``, ``update_g`` of ``DataParallelStep.step``.
+
+    Before the first step, when a process group is initialised, the ranks compare the epoch they planned: (crc, -crc) of the epoch
+    table (``loader.last_table_crc``) all-reduced with MAX comes back unchanged only where every rank holds the same table.  RuntimeError
+    otherwise -- ranks that planned different epochs would train, silently, on overlapping data.  ``all_reduce_max``: the reduction to
+    use instead of ``torch.distributed``'s (a function of one int64 tensor that returns the element-wise maximum over the ranks)."""
+    case, plan = loader.begin_epoch()
+    if all_reduce_max is None and dist.is_initialized():
+        all_reduce_max = lambda t: _all_reduce_max(t, dp.pg)       # noqa: E731
+    if all_reduce_max is not None and not _same_plan_everywhere(loader.last_table_crc, all_reduce_max):
+        raise RuntimeError("resident_epoch: the ranks planned different epochs (this rank's table has crc32 %08x); every rank must draw "
+                           "the same batches -- the loader's own seeded sampler, or a rank-identical batch_sampler" % loader.last_table_crc)
+    hp = loader.hp
+    results = []
+    for batch in loader.batches(case, plan):
+        results.append(dp.step(step_batch(batch, hp), phase=phase, lazy_g=True, **weights))
+    return results
 
 
 class LazyResult(object):

@@ -1026,6 +1026,25 @@ typedef struct gt_assemble_case {
 } gt_assemble_case;
 int gt_op_assemble_batch(const gt_assemble_case* c, void* stream);
 
+/* One data-parallel rank's share of a batch, by the same kernel.  Whole sequences are dealt round-robin: local sequence b of rank r is
+ * sequence r + world * b of the length-sorted batch, table slot first_slot + rank + b * world.  c->B is the LOCAL sequence count,
+ * ceil((B_global - rank) / world) and at least 1; c->T is the T of the WHOLE batch (every rank pads to it: MLPG is built for the padded
+ * length); every output of gt_op_assemble_batch keeps its meaning for the local rows, lengths is the local (B).  The noise of a row is
+ * keyed by its corpus utterance, so the ranks' rows are the rows of the whole batch.
+ *   tv_global   device double, 8-byte aligned, may be null: receives sum of min(length, T) over the B_global slots of the whole
+ *               batch (a slot that does not lie inside [0, F) counts 0) -- the loss normaliser of the data-parallel step
+ *               (gt_set_loss_normalizer_device).  Written by the launch itself (workgroup 0; an int64 sum, one conversion, one store):
+ *               exact, identical on every rank, no atomics, no second launch, no host read.
+ * Everything gt_op_assemble_batch checks is checked the same way (the table must hold the slots [first_slot, first_slot + B_global));
+ * a null shard, world < 1, a rank outside [0, world), B_global < 1, a c->B that is not the rank's share (a share of 0 included) and a
+ * misaligned tv_global return GT_ERR_INVALID before the launch.  rank 0 of world 1 writes what gt_op_assemble_batch writes. */
+typedef struct gt_assemble_shard {
+  int32_t rank, world;
+  int32_t B_global, pad_;
+  double* tv_global;
+} gt_assemble_shard;
+int gt_op_assemble_shard(const gt_assemble_case* c, const gt_assemble_shard* s, void* stream);
+
 /* Normalisation statistics of one side of a device-resident corpus in one pass (gantts_amd/csrc/corpus_stats_kernels.hip.h; gantts_amd/data.py:
  * ResidentCorpus.minmax / .meanvar): what data.minmax and data.meanvar compute on the host (train.py:718-751).  Stateless; every pointer is
  * caller-owned device memory; no synchronisation; two launches on `stream`, no atomics, bit-identical from run to run.

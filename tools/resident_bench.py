@@ -10,8 +10,10 @@
 3. Batches per second on the same corpus through DevicePrefetcher(DataLoader) -- collate_fn and hp.device_collate -- and through
    ResidentLoader: each loader alone (a device synchronise at the end), then each inside train_loop's G+D step (one epoch:
    train phase + a short test phase, host clock around the call, which ends in the epoch's read-back).
+4. --world N [N ...]: one data-parallel rank's launch (gt_op_assemble_shard, rank 0 of a world of N: 32 / N sequences) beside
+   gt_op_assemble_batch on the whole batch, in the same process and in alternating rounds: launch time and the bytes each moves.
 
-    python tools/resident_bench.py [--utterances 1024] [--workers 1] [--no-loaders] [--out FILE]
+    python tools/resident_bench.py [--utterances 1024] [--workers 1] [--world 2 4 8] [--no-loaders] [--out FILE]
 
 Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -91,11 +93,61 @@ def kernel_time(ds, hp, launches, nbuf=8):
         run_kernel(launches, True)
         run_copy(launches, True)
         torch.cuda.synchronize()
-        res = {"kernel_us": ev[0].elapsed_time(ev[1]) * 1e3 / launches, "copy_us": ev[2].elapsed_time(ev[3]) * 1e3 / launches}
+        res.update(kernel_us=ev[0].elapsed_time(ev[1]) * 1e3 / launches, copy_us=ev[2].elapsed_time(ev[3]) * 1e3 / launches)
         res["round_%d" % rep] = [round(res["kernel_us"], 2), round(res["copy_us"], 2)]
     res.update(algorithmic_bytes=nbytes, launches=launches, kernel_TBps=nbytes / res["kernel_us"] * 1e-6,
                copy_TBps=2 * half * 4 / res["copy_us"] * 1e-6)
     res["kernel_over_copy_rate"] = res["kernel_TBps"] / res["copy_TBps"]
+    return res
+
+
+def shard_time(ds, hp, launches, worlds, nbuf=8):
+    """One data-parallel rank's launch (gt_op_assemble_shard: rank 0 of each world in `worlds`, B / world sequences padded to the same
+    T, tv_global written) beside gt_op_assemble_batch on the whole batch: one corpus, one process, alternating rounds as in kernel_time
+    (HIP events around `launches` back-to-back launches behind a busy device; the first round warms up).  A rank's launch at 4 sequences
+    is 128 workgroups on 256 CUs -- latency-bound --, so the figure to read is the launch time; the bytes each moves are reported beside it."""
+    import torch
+    from gantts_amd import data as D
+    corpus = D.ResidentCorpus(ds)
+    row_bytes = (428 + 188) * 4 + (428 + DY + 63 + 1) * 4
+    busy = torch.rand(8192, 8192, device="cuda")
+    runs = {}
+    for w in [1] + list(worlds):
+        loader = D.ResidentLoader(corpus, B, True, hp, rank=0, world=w, short_batch="drop")
+        Ds, b = len(loader.scol_host), B // w
+        bufs = [(torch.empty(b, T, 428, device="cuda"), torch.empty(b, T, DY, device="cuda"), torch.empty(b, T, Ds, device="cuda"),
+                 torch.empty(b, T, 1, device="cuda"), torch.empty(b, device="cuda", dtype=torch.int64)) for _ in range(nbuf)]
+        case, plan = loader.begin_epoch()
+        plan = [p for p in plan if p[1] == B]                      # the full batches: (first, B, T, ..) / (first, B_global, B_local, T, ..)
+        tv = torch.zeros(1, device="cuda", dtype=torch.float64)
+        runs[w] = (loader, case, plan, bufs, tv, [torch.cuda.Event(enable_timing=True) for _ in range(2)])
+
+    def run(w):
+        loader, case, plan, bufs, tv, ev = runs[w]
+        for _ in range(2):
+            torch.mm(busy, busy)
+        ev[0].record()
+        for k in range(launches):
+            p = plan[k % len(plan)]
+            if w == 1:
+                loader.assemble(case, p[0], p[1], p[2], out=bufs[k % nbuf])
+            else:
+                loader.assemble(case, p[0], p[2], p[3], out=bufs[k % nbuf], B_global=p[1], tv_global=tv)
+        ev[1].record()
+
+    res = {"launches": launches, "rounds_us": {}}
+    for rep in range(3):
+        for w in runs:
+            run(w)
+        torch.cuda.synchronize()
+        for w in runs:
+            ev = runs[w][5]
+            res["rounds_us"].setdefault("world_%d" % w, []).append(round(ev[0].elapsed_time(ev[1]) * 1e3 / launches, 2))
+    for w in runs:
+        if w > 1:
+            assert float(runs[w][4]) == float(B * T)               # every utterance of this corpus has T frames
+        res["world_%d" % w] = {"sequences": B // w, "workgroups": (B // w) * T // 16, "algorithmic_bytes": (B // w) * T * row_bytes,
+                               "launch_us": res["rounds_us"]["world_%d" % w][-1]}
     return res
 
 
@@ -195,9 +247,12 @@ def main():
     ap.add_argument("--workers", type=int, default=1, help="DataLoader workers of the host pipeline (hp.num_workers)")
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--stats-passes", type=int, default=20)
+    ap.add_argument("--world", type=int, nargs="+", default=[], help="also time one rank's launch of a world of N (a divisor of 32)")
     ap.add_argument("--no-loaders", action="store_true", help="the kernel and the statistics only (parts 1 and 2)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if any(w < 2 or B % w for w in a.world):
+        raise SystemExit("resident_bench: --world takes divisors of %d above 1" % B)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("resident_bench: needs a GPU (no CPU path)")
@@ -209,6 +264,8 @@ def main():
     res = {"B": B, "T": T, "utterances": a.utterances, "corpus_bytes": a.utterances * T * (428 + 188) * 4, "workers": a.workers}
     ds = D.TTSDataset(X, Y, lo, hi, mean, std, hp=hp)
     res["kernel"] = kernel_time(ds, hp, a.launches)
+    if a.world:
+        res["shard"] = shard_time(ds, hp, a.launches, a.world)
     res["stats"] = stats_time(X, Y, res["kernel"]["copy_TBps"], a.stats_passes)
     n_train = (a.utterances + B - 1) // B
     for tag, flags in () if a.no_loaders else (("host_collate", {}), ("host_device_collate", {"device_collate": True}), ("resident", {"resident_corpus": True})):
