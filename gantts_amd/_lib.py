@@ -51,6 +51,12 @@ COMM_ID_BYTES = 128
 SCALE_NONE, SCALE_MINMAX, SCALE_MEANVAR = 0, 1, 2      # AssembleCase.x_kind / y_kind
 ASSEMBLE_MAX_WINDOWS, ASSEMBLE_MAX_TAPS = 4, 9
 CORPUS_STATS_SLAB, CORPUS_STATS_FANIN = 256, 64        # GT_CORPUS_STATS_SLAB / _FANIN: rows per workgroup, partial chains per column of the merge
+LEDGER_SLOTS = 32                                      # GT_LEDGER_SLOTS: doubles of the epoch ledger's record
+LEDGER_HAS_D, LEDGER_HAS_G, LEDGER_HAS_DIST = 1, 2, 4  # gt_ledger_add / gt_op_epoch_ledger flags
+LEDGER_ACOUSTIC, LEDGER_DURATION, LEDGER_VC = 0, 1, 2  # ... kind
+# slot i of the record holds the running sum named LEDGER_KEYS[i]; the slots behind them are reserved
+LEDGER_KEYS = ("generator", "mse", "mge", "loss_real_d", "loss_fake_d", "loss_adv", "discriminator", "real_correct", "fake_correct",
+               "mcd", "bap_mcd", "f0_rmse", "vuv_err", "dur_rmse", "d_updates", "g_updates")
 
 
 class StreamConfig(C.Structure):
@@ -295,6 +301,13 @@ SIGNATURES = {
     "gt_op_masked_mse": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_F), _P, _P]),
     "gt_compute_distortions": (_I, [_P, _P, _I, _P, _P, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_L), _I, _I,
                                     C.POINTER(DistortionSums), _P]),
+    "gt_ledger_configure": (_I, [_P, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _P, _P, _I, C.c_double]),
+    "gt_ledger_reset": (_I, [_P, _P]),
+    "gt_ledger_add": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
+    "gt_ledger_read": (_I, [_P, C.POINTER(C.c_double), _P]),
+    "gt_ledger_buffers": (_I, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "gt_op_epoch_ledger": (_I, [_P, _P, _P, _I, _I, _I, C.c_double, _P]),
+    "gt_host_wait_count": (_I, [_P, C.POINTER(C.c_longlong)]),
     "gt_op_gather_cols": (_I, [_P, _I, _P, _I, _P, _I, _I, _L, _P]),
     "gt_op_pad_sequences": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _P]),
     "gt_op_mlpg_forward": (_I, [_P, _P, _P, _I, _I, _P, _P]),

@@ -157,6 +157,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   int* ints[] = {e->d_scol, e->d_sstride, e->d_adv_cols, e->d_adv_inv, e->d_scol_i2o, e->d_sstride_i2o};
   for (int* p : ints) if (p) (void)hipFree(p);
   e->results.destroy();
+  e->ledger.release();
   delete e;
 }
 

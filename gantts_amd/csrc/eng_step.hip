@@ -687,6 +687,7 @@ int ResultsChannel::post_deferred(int role, hipStream_t s) {
   return GT_OK;
 }
 int ResultsChannel::wait_early() {
+  ++waits;
   if (ticket_wait) {
     volatile unsigned* t = ticket_host();
     const unsigned want = ticket_wait;

@@ -267,6 +267,7 @@ struct ResultsChannel {
   unsigned ticket_next = 0, ticket_wait = 0; hipEvent_t ev_res = nullptr;      // last number handed out / the one the posted early results carry (0: ev_res is used)
   StepResults* h_def[2] = {nullptr, nullptr}; hipEvent_t ev_def[2] = {nullptr, nullptr}; bool def_pending[2] = {false, false};
   bool begin_done[2] = {false, false};     // per role: gt_update_*_begin has run, _end has not
+  long long waits = 0;                     // gt_host_wait_count: times a call blocked its thread on the device (wait_early, collect, fetch; gt_ledger_read adds its own)
   int create(StepResults* device_results, const bool* poll_option);
   void destroy() {
     if (h_res) (void)hipHostFree(h_res);      if (ev_res) (void)hipEventDestroy(ev_res);
@@ -282,14 +283,34 @@ struct ResultsChannel {
   int post_deferred(int role, hipStream_t s);
   int collect(int role) {                  // ... then in h_def[role]
     if (!def_pending[role]) return fail(GT_ERR_STATE, "no deferred %s result pending", role == GT_ROLE_D ? "discriminator" : "generator");
+    ++waits;
     HIPCHK(hipEventSynchronize(ev_def[role]));
     def_pending[role] = false;
     return GT_OK;
   }
-  int fetch(hipStream_t s) { HIPCHK(hipMemcpyAsync(h_res, d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); return GT_OK; }
+  int fetch(hipStream_t s) { ++waits; HIPCHK(hipMemcpyAsync(h_res, d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); return GT_OK; }
   void abandon() { early_done = false; ticket_wait = 0; }      // a fused call whose _begin failed
   void forget_begin() { begin_done[0] = begin_done[1] = false; }      // an option changed what an open _begin had stashed
   void reset() { forget_begin(); early_done = false; }         // gt_clear_faults
+};
+
+// Epoch ledger (eng_ledger.hip, ledger_kernels.hip.h): train_loop's running sums of a phase in device memory.  `rec` is sized once by
+// gt_ledger_configure and never grows afterwards: [GT_LEDGER_SLOTS doubles: the record | 8 doubles: the last batch's distortion sums |
+// col_stat[Ds], col_role[Ds] | 1024 x DIST_NSUM doubles: partials of the distortion reduction].
+struct EpochLedger {
+  bool configured = false;
+  int kind = 0, Ds = 0, vuv_col = -1, stats_f64 = 0;
+  double logdb_const = 0.0;
+  const void *mean = nullptr, *stdv = nullptr;     // the caller's statistics (device), read by every gt_ledger_add
+  Scratch rec, len;                                // len: the batch's lengths as int32 (grows with B only)
+  size_t off_tab = 0, off_part = 0;
+  double* h_out = nullptr;                         // pinned: gt_ledger_read's copy
+  double* record() const { return rec.as<double>(); }
+  double* dist() const { return rec.as<double>() + GT_LEDGER_SLOTS; }
+  int* col_stat() const { return (int*)((char*)rec.p + off_tab); }
+  int* col_role() const { return col_stat() + Ds; }
+  double* partials() const { return (double*)((char*)rec.p + off_part); }
+  void release() { rec.release(); len.release(); if (h_out) (void)hipHostFree(h_out); h_out = nullptr; configured = false; }
 };
 
 struct gt_engine {
@@ -311,6 +332,7 @@ struct gt_engine {
   Scratch dcat, dzA, dzB, leak, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
   Scratch scal;                            // StepScalars + StepResults
   ResultsChannel results;                  // how the step's scalars reach the host
+  EpochLedger ledger;                      // gt_ledger_*: the loop's running sums, added on the device behind each step
   // per-step state
   int B = 0, T = 0; long N = 0;
   const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;

@@ -532,6 +532,74 @@ class StepEngine(object):
         check(lib.gt_update_generator_result(self._h, C.byref(res)))
         return res.loss_mse, res.loss_mge, res.loss_adv, res.loss_g
 
+    # ---- epoch ledger: train_loop's running sums of a phase, kept on the device (include/gantts_hip.h gt_ledger_*) ----------
+    def ledger_configure(self, kind, roles, stats, vuv_col, stat_mean, stat_std, logdb_const):
+        """Once per layout: ``kind`` L.LEDGER_ACOUSTIC / _DURATION / _VC; ``roles`` / ``stats``: per static column its role and the
+        index of its statistics (``train._acoustic_columns``); ``stat_mean`` / ``stat_std``: 1-D device tensors of one dtype, float32
+        or float64, kept alive here and read by every ``ledger_add``; ``logdb_const``: ``train._LOGDB_CONST`` (the host's value is
+        the one the device multiplies by).  Synchronises; zeroes the record."""
+        Ds = len(roles)
+        if len(stats) != Ds:
+            raise ValueError("roles and stats must have one entry per static column")
+        for t in (stat_mean, stat_std):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError("the ledger's statistics must be contiguous 1-D device tensors")
+        if stat_mean.dtype != stat_std.dtype or stat_mean.dtype not in (torch.float32, torch.float64):
+            raise TypeError("the ledger's statistics must both be float32 or both float64")
+        if stat_mean.numel() != stat_std.numel() or max(stats) >= stat_mean.numel():
+            raise RuntimeError("Y_data_mean / Y_data_std are shorter than the feature layout")
+        check(lib.gt_ledger_configure(self._h, int(kind), Ds, (C.c_int * Ds)(*[int(v) for v in stats]),
+                                      (C.c_int * Ds)(*[int(v) for v in roles]), int(vuv_col), ptr(stat_mean), ptr(stat_std),
+                                      int(stat_mean.dtype == torch.float64), float(logdb_const)))
+        self._keep["ledger"] = (stat_mean, stat_std)
+        self._ledger_Ds = Ds
+
+    def ledger_reset(self):
+        """Zeroes the record in stream order (the start of a phase)."""
+        check(lib.gt_ledger_reset(self._h, L.current_stream()))
+
+    def ledger_add(self, flags, y_static=None, y_hat_static=None, lengths=None):
+        """Adds the step just finalised into the record -- to be called behind ``update_*_end(defer=True)`` on the same stream; it
+        enqueues and never waits.  ``flags``: L.LEDGER_HAS_D | L.LEDGER_HAS_G | L.LEDGER_HAS_DIST; with HAS_DIST the batch's distortion
+        sums are formed first from ``y_static`` / ``y_hat_static`` and ``lengths``, a DEVICE int64 tensor of B entries
+        (``DeviceBatch.lengths``) or None for full-length sequences."""
+        B = T = 0
+        if flags & L.LEDGER_HAS_DIST:
+            if y_static.dim() == 2:
+                y_static, y_hat_static = y_static.unsqueeze(0), y_hat_static.unsqueeze(0)
+            y_static = _check_frames(y_static, "y_static", self._ledger_Ds)
+            y_hat_static = _check_frames(y_hat_static, "y_hat_static", self._ledger_Ds)
+            if y_static.shape != y_hat_static.shape:
+                raise RuntimeError("You probably have specified wrong dimention params.")
+            B, T, _ = y_static.shape
+            if lengths is not None:
+                if not (isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.dtype == torch.int64):
+                    raise TypeError("ledger_add takes the batch's lengths as a device int64 tensor (no host copy on this path)")
+                if lengths.numel() != B:
+                    raise RuntimeError("lengths has %d entries for a batch of %d sequences" % (lengths.numel(), B))
+                lengths = lengths if lengths.is_contiguous() else lengths.contiguous()
+        else:
+            y_static = y_hat_static = lengths = None
+        check(lib.gt_ledger_add(self._h, int(flags), ptr(y_static), ptr(y_hat_static), ptr(lengths), B, T, L.current_stream()))
+
+    def ledger_read(self):
+        """The record as a dict keyed by ``L.LEDGER_KEYS``: one copy and one wait (the end of a phase)."""
+        out = (C.c_double * L.LEDGER_SLOTS)()
+        check(lib.gt_ledger_read(self._h, out, L.current_stream()))
+        return {k: out[i] for i, k in enumerate(L.LEDGER_KEYS)}
+
+    def ledger_buffers(self):
+        """Device addresses ``(record, distortion sums of the last batch)`` (gt_ledger_buffers; introspection)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib.gt_ledger_buffers(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def host_waits(self):
+        """How often a call into this engine has blocked the calling thread on the device so far (gt_host_wait_count)."""
+        n = C.c_longlong()
+        check(lib.gt_host_wait_count(self._h, C.byref(n)))
+        return n.value
+
     def _adv_width(self):
         ss, hd, nW, adv, nmask, _ = self.signature
         static = [s // nW if d else s for s, d in zip(ss, hd)]

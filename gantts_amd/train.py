@@ -203,6 +203,34 @@ def compute_distortions(y_static, y_hat_static, Y_data_mean, Y_data_std, lengths
     assert False
 
 
+def _ledger_configure(eng, Ds, Y_data_mean, Y_data_std):
+    """Sets the engine's epoch ledger up for ``hp.name``: the column roles and statistics ``compute_distortions`` would pass per
+    batch, uploaded once; returns the metric names in the order ``compute_distortions`` returns them."""
+    from . import _lib as L
+    if hp.name == "acoustic":
+        roles, stats, vuv_col, _ = _acoustic_columns()
+        kind, names = L.LEDGER_ACOUSTIC, ("mcd", "bap_mcd", "f0_rmse", "vuv_err")
+    elif hp.name == "duration":
+        roles, stats, vuv_col = [ROLE_MSE] * Ds, list(range(Ds)), -1
+        kind, names = L.LEDGER_DURATION, ("dur_rmse",)
+    elif hp.name == "vc":
+        if Ds != hp.order:
+            raise RuntimeError("vc distortion expects static_dim == hp.order (train.py:423)")
+        roles, stats, vuv_col = [ROLE_MCD] * Ds, list(range(Ds)), -1
+        kind, names = L.LEDGER_VC, ("mcd",)
+    else:
+        assert False
+    if Ds != len(roles):
+        raise RuntimeError("You probably have specified wrong dimention params.")
+    # the dtype rule of _distortion_sums: float64 statistics on either side make both float64
+    f64 = Y_data_mean.dtype == torch.float64 or Y_data_std.dtype == torch.float64
+    dt = torch.float64 if f64 else torch.float32
+    mean = Y_data_mean.detach().to("cuda", dt).contiguous().view(-1)
+    std = Y_data_std.detach().to("cuda", dt).contiguous().view(-1)
+    eng.ledger_configure(kind, roles, stats, vuv_col, mean, std, _LOGDB_CONST)
+    return names
+
+
 def exp_lr_scheduler(optimizer, epoch, nepoch, init_lr=0.0001, lr_decay_epoch=100):
     """lr = init_lr * 0.1 ** (epoch // lr_decay_epoch), written into param_groups (train.py:323-333)."""
     lr = init_lr * (0.1 ** (epoch // lr_decay_epoch))
@@ -251,7 +279,10 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     (train.py:509-513) -- or, with ``hp.mlpg_device_band``, never formed: the band is built on the device from
     ``hp.windows`` -- and the distortion metrics come from one fused reduction.  A ``data.ResidentLoader`` (``hp.resident_corpus``) is
     iterated as it is: its batches are assembled on the device in one launch each and bring the generator input (noise included), the
-    static features and the mask with them."""
+    static features and the mask with them.  With ``hp.device_epoch_ledger`` the loop's running sums are kept on the device (the engine's
+    epoch ledger: one extra launch per batch, one read per phase) and the host does not wait for a step's scalars or a batch's
+    distortion sums; the logged values are the same bits."""
+    from . import _lib as L
     from .data import DevicePrefetcher, ResidentLoader
     from .multistream import get_static_features
     from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
@@ -280,6 +311,10 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     has_dynamic = bool(np.any(hp.has_dynamic_features))
     noise_gen = torch.Generator(device="cuda")
     noise_gen.manual_seed(int(getattr(hp, "generator_noise_seed", 0)))
+    # hp.device_epoch_ledger: the running sums below live in the engine's epoch ledger and are read once per phase; per batch the
+    # host waits for nothing (no step scalars, no distortion sums).  Off: the sums are kept here, three waits per batch.
+    ledger = bool(getattr(hp, "device_epoch_ledger", False))
+    ledger_eng, ledger_open, ledger_metrics = None, False, ()
 
     for global_epoch in range(global_epoch + 1, hp.nepoch + 1):
         if hp.lr_decay_schedule and update_g:
@@ -337,6 +372,32 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
                     # accumulated on the device (float64 count); read once per epoch, no per-batch host synchronisation
                     regard_fake_as_natural = regard_fake_as_natural + ((target > 0.5).float() * mask).sum(dtype=torch.float64)
 
+                if ledger:
+                    # hp.device_epoch_ledger: the split-phase forms of the same two steps with deferred results -- nothing is waited for
+                    # -- and one launch that adds the step's scalars and the batch's distortion metrics into the engine's ledger
+                    eng = _engine_of(y_hat_static, model_g)
+                    if ledger_eng is not eng:
+                        ledger_metrics = _ledger_configure(eng, y_static.size(-1), Y_data_mean, Y_data_std)
+                        ledger_eng, ledger_open = eng, False
+                    if not ledger_open:
+                        eng.ledger_reset()
+                        ledger_open = True
+                    flags = 0
+                    if update_d:
+                        eng.update_discriminator_begin(model_d, optimizer_d, x, y_static, y_hat_static, mask, phase,
+                                                       lengths=cpu_sorted_lengths)
+                        eng.update_discriminator_end(optimizer_d, phase, defer=True)
+                        flags |= L.LEDGER_HAS_D
+                    if update_g:
+                        adv_w = w_d * float(np.clip(E_loss_mge / E_loss_adv, 0, 1e+3))
+                        eng.update_generator_begin(model_g, model_d, optimizer_g, x, y, y_hat, y_static, y_hat_static,
+                                                   adv_w, mask, phase, mse_w, mge_w, lengths=cpu_sorted_lengths)
+                        eng.update_generator_end(optimizer_g, adv_w, mse_w, mge_w, phase, defer=True)
+                        flags |= L.LEDGER_HAS_G | L.LEDGER_HAS_DIST
+                    if flags:
+                        eng.ledger_add(flags, y_static, y_hat_static, sorted_lengths)
+                    continue
+
                 if update_d:
                     loss_d, loss_fake_d, loss_real_d, _real, _fake = update_discriminator(
                         model_d, optimizer_d, x, y_static, y_hat_static, cpu_sorted_lengths, mask, phase)
@@ -358,6 +419,18 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
                     distortions = compute_distortions(y_static, y_hat_static, Y_data_mean, Y_data_std, cpu_sorted_lengths)
                     for k, v in distortions.items():
                         running_metrics[k] = running_metrics.get(k, 0.0) + float(v)
+
+            if ledger and ledger_open:
+                # the one wait of the phase: the sums the loop above would have kept on the host, bit for bit (each addend was formed
+                # and added on the device as here, in batch order); faults of the phase's kernels surface here too
+                led = ledger_eng.ledger_read()
+                ledger_eng.check_faults()
+                ledger_open = False
+                for k in running_loss:
+                    running_loss[k] = led[k]
+                real_correct_count, fake_correct_count = led["real_correct"], led["fake_correct"]
+                if update_g:
+                    running_metrics = {k: led[k] for k in ledger_metrics}
 
             if update_d and update_g and phase == "train":
                 E_loss_mge = (mse_w * running_loss["mse"] + mge_w * running_loss["mge"]) / N

@@ -494,6 +494,51 @@ int gt_compute_distortions(const float* y_static, const float* y_hat_static, int
                            const void* stat_std, int stats_f64, const int32_t* col_stat_host,
                            const int32_t* col_role_host, int vuv_col, const int64_t* lengths_host, int B, int T,
                            gt_distortion_sums* out, void* stream);
+/* ---- epoch ledger: the running sums of the training loop, kept on the device ------------------------------
+ * train_loop (train.py:435-643) adds each step's scalars and each batch's distortion metrics into host sums and uses
+ * none of them before the phase ends.  The ledger is a record of GT_LEDGER_SLOTS doubles in device memory; ONE
+ * single-workgroup launch per batch (epoch_ledger_kernel) adds into it exactly what the loop adds on the host, each
+ * operation in the host's order and rounded alone (no contraction), so a phase's sums have the host sums' bits:
+ *   slots 0..6   generator, mse, mge, loss_real_d, loss_fake_d, loss_adv, discriminator   (float32 results, widened)
+ *   slots 7..8   real_correct, fake_correct
+ *   slots 9..13  mcd, bap_mcd, f0_rmse, vuv_err, dur_rmse     acoustic: mcd += (C * s_mcd) / n, bap_mcd += ((C * s_bap) / n) / 10,
+ *                vuv_err += n_vuv_err / n, f0_rmse += n_voiced > 0 ? sqrt(s_f0 / n_voiced) : NaN (the NaN then stays, as in the
+ *                host sum); duration: dur_rmse += sqrt(s_mse / (n * Ds)); vc: mcd += (C * s_mcd) / n.  C = logdb_const
+ *                (10 / ln 10 * sqrt 2), computed by the HOST and passed as a double.
+ *   slots 14..15 D updates and G updates counted
+ *   slots 16..31 reserved, never written
+ * A batch without valid frames (n == 0) is not defined: train_loop has none.
+ * gt_ledger_configure: once per engine and layout (synchronises; zeroes the record).  The column tables are uploaded here;
+ *   stat_mean / stat_std (device; float, or double when stats_f64) are READ BY EVERY gt_ledger_add and stay the caller's.
+ * gt_ledger_reset: zeroes the record in stream order.
+ * gt_ledger_add: to be enqueued behind the step's gt_update_*_end(out = NULL) calls on the SAME stream (the finalising launches
+ *   leave the step's results in device memory, which this reads).  With GT_LEDGER_HAS_DIST it first forms the batch's seven
+ *   distortion sums -- the kernels and the reduction order of gt_compute_distortions, bit for bit -- from device-resident
+ *   lengths (int64, B entries; NULL: every sequence has T frames); no host table, no copy, no synchronisation.  Never waits.
+ * gt_ledger_read: one copy and one wait.
+ * gt_ledger_buffers: device addresses of the record and of the last batch's seven distortion sums (introspection, tests).
+ * gt_op_epoch_ledger: the same kernel on caller-supplied device values -- results_dev: 12 floats in the order loss_d,
+ *   loss_fake_d, loss_real_d, real_correct, fake_correct, loss_mse, loss_mge, loss_adv, loss_g, gnorm_d, gnorm_g, tv;
+ *   dist_dev: 7 doubles in gt_distortion_sums order (may be NULL without GT_LEDGER_HAS_DIST).
+ * gt_host_wait_count: how often an engine call has blocked the calling thread on the device since creation (the waits for a
+ *   step's scalars -- early, deferred or fetched -- and gt_ledger_read).  A host-side census: no device work. */
+#define GT_LEDGER_SLOTS 32
+#define GT_LEDGER_HAS_D 1
+#define GT_LEDGER_HAS_G 2
+#define GT_LEDGER_HAS_DIST 4
+#define GT_LEDGER_ACOUSTIC 0
+#define GT_LEDGER_DURATION 1
+#define GT_LEDGER_VC 2
+int gt_ledger_configure(gt_engine* e, int kind, int Ds, const int32_t* col_stat_host, const int32_t* col_role_host, int vuv_col,
+                        const void* stat_mean, const void* stat_std, int stats_f64, double logdb_const);
+int gt_ledger_reset(gt_engine* e, void* stream);
+int gt_ledger_add(gt_engine* e, int flags, const float* y_static, const float* y_hat_static, const int64_t* lengths_dev_i64,
+                  int B, int T, void* stream);
+int gt_ledger_read(gt_engine* e, double out[GT_LEDGER_SLOTS], void* stream);
+int gt_ledger_buffers(gt_engine* e, double** ledger_dev, double** dist_dev);
+int gt_op_epoch_ledger(double* ledger_dev, const float* results_dev, const double* dist_dev, int flags, int kind, int Ds,
+                       double logdb_const, void* stream);
+int gt_host_wait_count(gt_engine* e, long long* n);
 /* multi_stream_mlpg(inputs, R, stream_sizes, has_dynamic_features) (gantts/multistream.py:82-123) and its
  * transpose (autograd backward).  Uses the engine's stream config. */
 int gt_op_mlpg_forward(gt_engine* e, const float* y, const float* R, int B, int T, float* y_static, void* stream);

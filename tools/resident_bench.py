@@ -13,7 +13,12 @@
 4. --world N [N ...]: one data-parallel rank's launch (gt_op_assemble_shard, rank 0 of a world of N: 32 / N sequences) beside
    gt_op_assemble_batch on the whole batch, in the same process and in alternating rounds: launch time and the bytes each moves.
 
+5. --ledger: only this part.  train_loop on the resident corpus with hp.device_epoch_ledger off and on, alternating epoch by epoch in
+   one process (one corpus, one pair of networks; the first epoch of each setting warms up), in --processes fresh processes; medians
+   and the spread over all timed epochs.  --layout cfg2 (this tool's corpus) or cfg1 (the VC layout, B = 8, T = 256).
+
     python tools/resident_bench.py [--utterances 1024] [--workers 1] [--world 2 4 8] [--no-loaders] [--out FILE]
+    python tools/resident_bench.py --ledger [--layout cfg1] [--processes 3] [--rounds 5] [--out FILE]
 
 Prints one JSON line (and writes it to --out)."""
 import argparse
@@ -240,8 +245,87 @@ def with_step(loaders, hp):
     return out
 
 
+# ---- 5. --ledger: train_loop on a resident corpus with hp.device_epoch_ledger off and on ------------------------------------------
+CFG1 = dict(B=8, T=256, D=75, order=25,
+            g=dict(in_dim=75, out_dim=75, static_dim=25, num_hidden=3, hidden_dim=512, dropout=0.5),
+            d=dict(in_dim=25, out_dim=1, num_hidden=2, hidden_dim=256, dropout=0.5, last_sigmoid=True))
+
+
+def ledger_leg(layout, utterances, test_utterances, rounds):
+    """One process: epochs of train_loop (train + test phase, host clock around the call, a device synchronise on either side) on ONE
+    resident corpus, ONE pair of networks, the switch alternating off, on, off, on, ...; the first epoch of each setting warms up and
+    is not reported.  layout "cfg2": this tool's corpus and networks; "cfg1": the VC layout (In2OutHighwayNet 75 -> 512 x 3 -> 75,
+    MLP D 25 -> 256 x 2 -> 1, B = 8, T = 256)."""
+    import torch
+    import gantts_amd.train as TR
+    from gantts_amd import data as D
+    from gantts_amd import hparams, models, optim
+    torch.manual_seed(0)
+    if layout == "cfg2":
+        hp = make_hp(1)
+        X, Y, lo, hi, mean, std = make_corpus(utterances)
+        hp.resident_corpus = True
+        loaders = D.get_tts_data_loaders({"train": X, "test": X[:test_utterances]}, {"train": Y, "test": Y[:test_utterances]}, lo, hi, mean, std, hp)
+        mg, md = models.MLP(**G_SPEC).cuda(), models.MLP(**D_SPEC).cuda()
+    else:
+        c = CFG1
+        hp = types.SimpleNamespace(**hparams.vc.values())
+        hp.batch_size, hp.num_workers, hp.nepoch, hp.lr_decay_schedule = c["B"], 1, 1, False
+        hp.stream_sizes, hp.has_dynamic_features, hp.order, hp.adversarial_streams = [c["D"]], [True], c["order"], None
+        hp.generator_add_noise, hp.resident_corpus = False, True
+        rng = np.random.default_rng(0)
+        X = [rng.standard_normal((c["T"], c["D"]), dtype=np.float32) for _ in range(utterances)]
+        Y = [rng.standard_normal((c["T"], c["D"]), dtype=np.float32) for _ in range(utterances)]
+        mean, std = rng.standard_normal(c["D"]) * 0.3, 0.5 + rng.random(c["D"])
+        loaders = D.get_vc_data_loaders({"train": X, "test": X[:test_utterances]}, {"train": Y, "test": Y[:test_utterances]}, mean, std, hp)
+        mg, md = models.In2OutHighwayNet(**c["g"]).cuda(), models.MLP(**c["d"]).cuda()
+    TR.hp = hp
+    og = optim.Adagrad(mg.parameters(), lr=0.01, weight_decay=1e-7)
+    od = optim.Adagrad(md.parameters(), lr=0.01, weight_decay=1e-7)
+    n = len(loaders["train"]) + len(loaders["test"])
+    rates = {"off": [], "on": []}
+    for rep in range(rounds + 1):
+        for tag in ("off", "on"):
+            hp.device_epoch_ledger = tag == "on"
+            TR.global_epoch = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            TR.train_loop((mg, md), (og, od), loaders, w_d=1.0, mse_w=0.0, mge_w=1.0)
+            torch.cuda.synchronize()
+            if rep:
+                rates[tag].append(n / (time.perf_counter() - t0))
+    return {"layout": layout, "batches_per_epoch": n, "B": hp.batch_size, "off_batches_per_s": rates["off"], "on_batches_per_s": rates["on"]}
+
+
+def ledger_processes(a):
+    """--ledger: `--processes` fresh processes in turn, each one ledger_leg(); medians and spread over every timed epoch of every process."""
+    import subprocess
+    runs = []
+    for _ in range(a.processes):
+        cmd = [sys.executable, os.path.abspath(__file__), "--ledger-child", "--layout", a.layout, "--utterances", str(a.utterances),
+               "--test-utterances", str(a.test_utterances), "--rounds", str(a.rounds)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.child_timeout)
+        if p.returncode != 0:      # nothing more is started on the device behind a failed process
+            raise SystemExit("resident_bench: a --ledger process ended with status %d" % p.returncode)
+        runs.append(json.loads(p.stdout.decode().strip().splitlines()[-1]))
+    res = {"layout": a.layout, "processes": a.processes, "rounds": a.rounds, "batches_per_epoch": runs[0]["batches_per_epoch"], "B": runs[0]["B"]}
+    for tag in ("off", "on"):
+        v = sorted(r for run in runs for r in run[tag + "_batches_per_s"])
+        res[tag] = {"median_batches_per_s": float(np.median(v)), "min": v[0], "max": v[-1],
+                    "per_process_median": [float(np.median(run[tag + "_batches_per_s"])) for run in runs]}
+    res["on_over_off"] = res["on"]["median_batches_per_s"] / res["off"]["median_batches_per_s"]
+    res["ms_per_batch_saved"] = 1e3 / res["off"]["median_batches_per_s"] - 1e3 / res["on"]["median_batches_per_s"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ledger", action="store_true", help="only part 5: train_loop with hp.device_epoch_ledger off and on, alternating, in fresh processes")
+    ap.add_argument("--ledger-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--layout", choices=["cfg2", "cfg1"], default="cfg2")
+    ap.add_argument("--processes", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=5, help="timed epochs per setting and process (one more warms up)")
+    ap.add_argument("--child-timeout", type=float, default=300.0)
     ap.add_argument("--utterances", type=int, default=1024, help="utterances of 512 frames (1024: a 1.3 GB corpus)")
     ap.add_argument("--test-utterances", type=int, default=64)
     ap.add_argument("--workers", type=int, default=1, help="DataLoader workers of the host pipeline (hp.num_workers)")
@@ -253,9 +337,20 @@ def main():
     a = ap.parse_args()
     if any(w < 2 or B % w for w in a.world):
         raise SystemExit("resident_bench: --world takes divisors of %d above 1" % B)
+    if a.ledger and not a.ledger_child:      # this process starts the measuring ones and never opens the device itself
+        line = json.dumps({"ledger": ledger_processes(a)})
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("resident_bench: needs a GPU (no CPU path)")
+    if a.ledger_child:
+        print(json.dumps(ledger_leg(a.layout, a.utterances, a.test_utterances, a.rounds)))
+        return
     from gantts_amd import data as D
     hp = make_hp(a.workers)
     X, Y, lo, hi, mean, std = make_corpus(a.utterances)
