@@ -584,9 +584,15 @@ extern "C" int gt_check_faults(gt_engine* e, void* stream) {
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return fault_seen(e);
 }
+// The precision of the float32-storage products (eng_gemm_f32.hip) that network `role` launches: an SRU network in the discriminator slot
+// stays in float32 under either bf16 option (stack and hidden2out; its bf16 route is the bf16-storage family, GT_OPT_SRU_D_BF16); everything
+// else -- MLP, LSTM and In2Out stacks of either role, the In2Out gate, the output layers -- follows GT_OPT_MATMUL_BF16.
+int product_prec(const gt_engine* e, int role) {
+  if (role == GT_ROLE_D && e->net[GT_ROLE_D].d.arch == GT_ARCH_SRU) return PREC_F32;
+  return e->matmul_bf16 ? PREC_BF16 : PREC_F32;
+}
 int check_common(gt_engine* e, int B, int T) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  tl_gemm_prec = e->matmul_bf16 ? PREC_BF16 : PREC_F32;       // every step / forward entry point passes through here
   if (B < 1 || T < 1) return fail(GT_ERR_INVALID, "B and T must be positive");
   if ((long)B * T > 0x3fffffffL) return fail(GT_ERR_INVALID, "B*T too large");
   e->chk_B = B; e->chk_T = T;

@@ -224,53 +224,12 @@ int weight_grad_b16(const __bf16* dZT, long lddzt, const __bf16* XT, long ldxt, 
   nslab = std::min<long>(nslab, std::max<long>(1, rows / 512));
   const int k_chunk = cdiv(cdiv(rows, nslab), B16_BK) * B16_BK;
   nslab = cdiv(rows, k_chunk);
-  const long slab_stride = (long)out * in;
-  const size_t need = (((size_t)nslab * slab_stride + (size_t)nslab * out) * sizeof(float) + 255) & ~(size_t)255;
-  const bool can4 = slab_stride % 4 == 0 && ((uintptr_t)dW) % 16 == 0;
-  float* slab_base = nullptr;
-  if (defer && defer->active && accumulate) { CHK(slab_defer_flush(*defer, s)); defer = nullptr; }
-  if (defer && defer->active && can4) {
-    if (defer->jobs.n == SLAB_MAX_JOBS || defer->used + need > defer->pool.bytes) {
-      CHK(slab_defer_flush(*defer, s));
-      if (need > defer->pool.bytes) CHK(defer->pool.ensure(std::max(need * 4, (size_t)64 << 20)));
-    }
-    slab_base = (float*)((char*)defer->pool.p + defer->used);
-    defer->used += need;
-  } else {
-    defer = nullptr;
-    CHK(slabs.ensure(need));
-    slab_base = slabs.as<float>();
-  }
-  float* bias_slabs = slab_base + (size_t)nslab * slab_stride;
+  SlabSet set;
+  CHK(slab_place(defer, slabs, nslab, out, in, dW, accumulate, s, &set));
   GemmB16Args g = b16_args();
   g.A = dZT; g.lda = (int)lddzt; g.B = XT; g.ldb = (int)ldxt; g.M = out; g.N = in; g.K = (int)rows;
-  g.C = slab_base; g.ldc = in; g.epi = B16_SLAB; g.k_chunk = k_chunk; g.slab_stride = slab_stride;
-  g.rowsum_slab = db ? bias_slabs : nullptr;
+  g.C = set.base; g.ldc = in; g.epi = B16_SLAB; g.k_chunk = k_chunk; g.slab_stride = set.stride;
+  g.rowsum_slab = db ? set.bias : nullptr;
   CHK(launch_gemm_b16(g, nslab, s, huge ? 256 : (big ? 128 : 64)));
-  if (can4) {
-    const int main_blocks = cdiv(slab_stride / 4, 256), bias_blocks = db ? cdiv(out, 256) : 0;
-    if (defer) {
-      SlabJob& J = defer->jobs.j[defer->jobs.n++];
-      J.slabs = slab_base; J.slab_stride = slab_stride; J.n4 = slab_stride / 4; J.out = dW; J.bslabs = bias_slabs; J.bout = db;
-      J.nslab = nslab; J.accumulate = accumulate ? 1 : 0; J.nb = out; J.main_blocks = main_blocks; J.block0 = defer->blocks; J.pad_ = 0;
-      defer->blocks += main_blocks + bias_blocks;
-      return GT_OK;
-    }
-    gemm_path_count(GEMM_PATH_REDUCE4);
-    hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride / 4,
-                       dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
-    LAUNCH_CHECK();
-  } else {
-    gemm_path_count(GEMM_PATH_REDUCE);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride, dW,
-                       accumulate ? 1 : 0);
-    LAUNCH_CHECK();
-    if (db) {
-      gemm_path_count(GEMM_PATH_REDUCE_SMALL);
-      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db, accumulate ? 1 : 0);
-      LAUNCH_CHECK();
-    }
-  }
-  return GT_OK;
+  return slab_combine(set, dW, db, accumulate, s);
 }
-

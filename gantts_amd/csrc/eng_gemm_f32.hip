@@ -4,11 +4,11 @@
 
 using namespace gt;
 // the kernels are instantiated per operand orientation in their own translation units (eng_gemm_f32_{nt,nn,tn,pair}.hip)
-int launch_gemm_nt(const GemmArgs& g, int bm, int bn, hipStream_t s);
-int launch_gemm_nn(const GemmArgs& g, int bm, int bn, hipStream_t s);
-int launch_gemm_tn(const GemmArgs& g, int bm, int bn, int nslab, hipStream_t s);
-int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, hipStream_t s);
-int launch_gemm_tn_pair(const GemmArgs& g1_in, const GemmArgs& g2_in, int nslab1, int nslab2, hipStream_t s, const GemmArgs* rider, bool* rode);
+int launch_gemm_nt(const GemmArgs& g, int bm, int bn, int prec, hipStream_t s);
+int launch_gemm_nn(const GemmArgs& g, int bm, int bn, int prec, hipStream_t s);
+int launch_gemm_tn(const GemmArgs& g, int bm, int bn, int nslab, int prec, hipStream_t s);
+int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, int prec, hipStream_t s);
+int launch_gemm_tn_pair(const GemmArgs& g1_in, const GemmArgs& g2_in, int nslab1, int nslab2, int prec, hipStream_t s, const GemmArgs* rider, bool* rode);
 // ------------------------------------------------------------------------------------------
 // GEMM dispatch
 // ------------------------------------------------------------------------------------------
@@ -23,9 +23,8 @@ int gemm_cu_count() {
   cus[dev] = n;
   return n;
 }
-// products of the GEMM family: f32 MFMA (default) or bf16 MFMA with f32 accumulation (GT_OPT_MATMUL_BF16; set per engine
-// entry point for the launches it issues on this thread)
-thread_local int tl_gemm_prec = PREC_F32;
+// products of the GEMM family: f32 MFMA (PREC_F32) or bf16 MFMA with f32 accumulation on the same float32 storage (PREC_BF16).  Every launch
+// function takes the precision as an argument; the engine's callers get it from product_prec(e, role) (eng_core.hip)
 
 // gt_gemm_path_counts: process-wide, one relaxed increment per launch on the host (no device work, no synchronisation)
 static std::atomic<int64_t> g_gemm_paths[GT_GEMM_PATH_SLOTS];
@@ -61,33 +60,30 @@ bool gemm_wide_store_ok(int kind, const GemmArgs& g) {
 bool gemm_small_tiles_ok() { return gemm_tile_mode() == 0; }   // f32 and bf16 products alike (bf16: cfg2 1.30 -> 1.21 ms, SRU 32.0 -> 28.2 ms)
 
 
-int launch_gemm(int kind, const GemmArgs& g, int nslab, hipStream_t s) {
+// forward and backward-data products (one slab)
+int launch_gemm(int kind, const GemmArgs& g, int prec, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0 || g.K <= 0) return fail(GT_ERR_INVALID, "empty GEMM");
-  const int bn = pick_bn(g.N);
-  const bool vec = gemm_vec_ok(g.A, g.lda, kind != GEMM_TN) && gemm_vec_ok(g.B, g.ldb, kind == GEMM_NT);
-  if (kind != GEMM_TN && vec && g.M > 64 && gemm_small_tiles_ok())
-    return kind == GEMM_NT ? launch_gemm_nt(g, 64, 64, s) : launch_gemm_nn(g, 64, 64, s);
+  if (kind != GEMM_NT && kind != GEMM_NN) return fail(GT_ERR_INVALID, "launch_gemm: forward and backward-data products only");
+  const bool nt = kind == GEMM_NT;
+  const bool vec = gemm_vec_ok(g.A, g.lda, true) && gemm_vec_ok(g.B, g.ldb, nt);
+  if (vec && g.M > 64 && gemm_small_tiles_ok()) return nt ? launch_gemm_nt(g, 64, 64, prec, s) : launch_gemm_nn(g, 64, 64, prec, s);
   // Otherwise tile height by a residency model: 128-row tiles keep 2 workgroups per CU resident (512 at once),
   // 64-row tiles 3-4 (LDS-limited: 768 with 128 columns, 1024 with 64) at ~0.55x the work each.
   // Cost = resident rounds x work per tile; e.g. 384 tiles (187-wide output) or 1024 tiles (2N x 483)
   // finish sooner as 64-row tiles, exactly 512 tiles do not.
-  bool small = false;
-  if (kind != GEMM_TN && g.M > 64) {
+  const int bn = pick_bn(g.N);
+  int bm = 128;
+  if (g.M > 64) {
     const long t128 = (long)cdiv(g.M, 128) * cdiv(g.N, bn), t64 = (long)cdiv(g.M, 64) * cdiv(g.N, bn);
     const double c128 = (double)cdiv(t128, 512), c64 = 0.55 * (double)cdiv(t64, bn == 64 ? 1024 : 768);
-    small = c64 < c128;
+    if (c64 < c128) bm = 64;
   }
-  switch (kind) {
-    case GEMM_NT:
-      if (small) return bn == 64 ? launch_gemm_nt(g, 64, 64, s) : launch_gemm_nt(g, 64, 128, s);
-      return bn == 64 ? launch_gemm_nt(g, 128, 64, s) : launch_gemm_nt(g, 128, 128, s);
-    case GEMM_NN:
-      if (small) return bn == 64 ? launch_gemm_nn(g, 64, 64, s) : launch_gemm_nn(g, 64, 128, s);
-      return bn == 64 ? launch_gemm_nn(g, 128, 64, s) : launch_gemm_nn(g, 128, 128, s);
-    default:
-      if (g.n_tiles_m == 64) return launch_gemm_tn(g, 64, 64, nslab, s);     // linear_backward_weight's choice (tile height in n_tiles_m)
-      return bn == 64 ? launch_gemm_tn(g, 128, 64, nslab, s) : launch_gemm_tn(g, 128, 128, nslab, s);
-  }
+  return nt ? launch_gemm_nt(g, bm, bn, prec, s) : launch_gemm_nn(g, bm, bn, prec, s);
+}
+// weight-gradient slabs: tile_m = 64 -> 64 x 64 tiles (the caller sized its slabs for them), else 128 rows by pick_bn(N) columns
+static int launch_gemm_slabs(const GemmArgs& g, int tile_m, int nslab, int prec, hipStream_t s) {
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0) return fail(GT_ERR_INVALID, "empty GEMM");
+  return tile_m == 64 ? launch_gemm_tn(g, 64, 64, nslab, prec, s) : launch_gemm_tn(g, 128, pick_bn(g.N), nslab, prec, s);
 }
 
 DropoutSpec no_drop() {
@@ -97,29 +93,51 @@ DropoutSpec no_drop() {
   d.scale = 1.f;
   return d;
 }
-
-// Y = act(X W^T + b)
-int linear_forward(const float* X, int ldx, const float* W, int ldw, const float* b, float* Y, int ldy,
-                          long rows, int in, int out, int act, const DropoutSpec& drop, hipStream_t s) {
+// C [M][N] = A [M][K] x B, everything else off (no bias, activation, dropout)
+static GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, long M, int N, int K) {
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = Y; g.ldc = ldy;
-  g.M = (int)rows; g.N = out; g.K = in; g.bias = b; g.act = act; g.drop = drop;
-  return launch_gemm(GEMM_NT, g, 1, s);
+  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K;
+  g.drop = no_drop();
+  return g;
+}
+int plain_product(int kind, const float* A, int lda, const float* B, int ldb, float* C, int ldc, long M, int N, int K, bool accumulate, int prec,
+                  hipStream_t s) {
+  GemmArgs g = gemm_args(A, lda, B, ldb, C, ldc, M, N, K);
+  g.accumulate = accumulate ? 1 : 0;
+  return launch_gemm(kind, g, prec, s);
+}
+
+// Y = act(X W^T + b [+ addm[r mod addm_wrap]])
+int linear_forward(const float* X, int ldx, const float* W, int ldw, const float* b, float* Y, int ldy, long rows, int in, int out, int act,
+                   const DropoutSpec& drop, int prec, hipStream_t s, const float* addm, int ld_addm, long addm_wrap, bool accumulate) {
+  GemmArgs g = gemm_args(X, ldx, W, ldw, Y, ldy, rows, out, in);
+  g.bias = b; g.act = act; g.drop = drop; g.accumulate = accumulate ? 1 : 0;
+  if (addm) { g.addm = addm; g.ld_addm = ld_addm; g.addm_wrap = (int)addm_wrap; }
+  return launch_gemm(GEMM_NT, g, prec, s);
+}
+// Split first layer in ONE launch (GEMM_A_LEAKY_PHILOX_SEG), W [out][ldw] = [conditioning columns cd | adversarial columns in - cd]: every tile
+// multiplies its `wrap` rows of x by W[:, :cd]^T once, then -- per half of the pass (rows = wrap or 2 wrap) -- continues the same
+// accumulators over the adversarial columns and runs that half's epilogue: no buffer for the x product
+int linear_forward_seg(const float* x, int ldx, long wrap, int cd, const float* adv, int ld_adv, long rows, const float* W, int ldw, int in,
+                       const float* b, float* Y, int ldy, int out, int act, const DropoutSpec& drop, int prec, hipStream_t s) {
+  GemmArgs g = gemm_args(x, ldx, W, ldw, Y, ldy, wrap, out, cd);
+  g.bias = b; g.act = act; g.drop = drop;
+  g.A_seg = adv; g.lda_seg = ld_adv; g.B_seg = W + cd; g.K_seg = in - cd;
+  g.dual_rows = rows == 2 * wrap ? (int)wrap : 0;
+  return launch_gemm(GEMM_NT, g, prec, s);
 }
 // dX = (dZ W[:, col0:col0+ncols]) (.) f'(H)
 GemmArgs backward_data_args(const float* dZ, int lddz, const float* W, int ldw, int col0, float* dX, int lddx,
                                    long rows, int out, int ncols, int act_prev, const float* H, int ldh, const DropoutSpec& drop) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = dZ; g.lda = lddz; g.B = W + col0; g.ldb = ldw; g.C = dX; g.ldc = lddx;
-  g.M = (int)rows; g.N = ncols; g.K = out; g.act = act_prev; g.H = H; g.ldh = ldh; g.drop = drop;
+  GemmArgs g = gemm_args(dZ, lddz, W + col0, ldw, dX, lddx, rows, ncols, out);
+  g.act = act_prev; g.H = H; g.ldh = ldh; g.drop = drop;
   return g;
 }
 int linear_backward_data(const float* dZ, int lddz, const float* W, int ldw, int col0, float* dX, int lddx,
                                 long rows, int out, int ncols, int act_prev, const float* H, int ldh,
-                                const DropoutSpec& drop, hipStream_t s) {
-  return launch_gemm(GEMM_NN, backward_data_args(dZ, lddz, W, ldw, col0, dX, lddx, rows, out, ncols, act_prev, H, ldh, drop), 1, s);
+                                const DropoutSpec& drop, int prec, hipStream_t s) {
+  return launch_gemm(GEMM_NN, backward_data_args(dZ, lddz, W, ldw, col0, dX, lddx, rows, out, ncols, act_prev, H, ldh, drop), prec, s);
 }
 // Pair launch (gemm_pair_kernel): the same layer's backward-data product rides in the weight gradient's launch when both
 // run on 64x64 tiles with 16-byte loadable operands.  GT_GEMM_PAIR=0 keeps them apart (measurement switch).
@@ -143,10 +161,61 @@ int slab_defer_flush(SlabDefer& d, hipStream_t s) {
   d.jobs.n = 0; d.blocks = 0; d.used = 0;
   return GT_OK;
 }
+// One weight gradient's partial slabs: [nslab][out * in] of the product with the bias slabs [nslab][out] behind them, in the pool of `defer`
+// (the combine is then recorded) or in the caller's private scratch (the combine runs in place).  Shared by both product families.
+int slab_place(SlabDefer* defer, Scratch& slabs, int nslab, int out, int in, const float* dW, bool accumulate, hipStream_t s, SlabSet* set) {
+  const long stride = (long)out * in;
+  const size_t need = (((size_t)nslab * stride + (size_t)nslab * out) * sizeof(float) + 255) & ~(size_t)255;
+  const bool can4 = stride % 4 == 0 && ((uintptr_t)dW) % 16 == 0;
+  float* base = nullptr;
+  if (defer && defer->active && accumulate) { CHK(slab_defer_flush(*defer, s)); defer = nullptr; }   // never two combines of one dW in a launch
+  if (defer && defer->active && can4) {
+    if (defer->jobs.n == SLAB_MAX_JOBS || defer->used + need > defer->pool.bytes) {
+      CHK(slab_defer_flush(*defer, s));                       // recorded combines first, then (maybe) a larger pool
+      if (need > defer->pool.bytes) CHK(defer->pool.ensure(std::max(need * 4, (size_t)64 << 20)));
+    }
+    base = (float*)((char*)defer->pool.p + defer->used);
+    defer->used += need;
+  } else {
+    defer = nullptr;
+    CHK(slabs.ensure(need));
+    base = slabs.as<float>();
+  }
+  *set = SlabSet{base, base + (size_t)nslab * stride, stride, need, nslab, out, can4, defer};
+  return GT_OK;
+}
+// fixed-order sum of the slabs into dW (and of the bias slabs into db, when given): recorded as a SlabJob, or launched here
+int slab_combine(const SlabSet& t, float* dW, float* db, bool accumulate, hipStream_t s) {
+  const int acc = accumulate ? 1 : 0;
+  if (t.can4) {
+    const int main_blocks = cdiv(t.stride / 4, 256), bias_blocks = db ? cdiv(t.out, 256) : 0;
+    if (SlabDefer* d = t.defer) {
+      SlabJob& J = d->jobs.j[d->jobs.n++];
+      J.slabs = t.base; J.slab_stride = t.stride; J.n4 = t.stride / 4; J.out = dW; J.bslabs = t.bias; J.bout = db;
+      J.nslab = t.nslab; J.accumulate = acc; J.nb = t.out; J.main_blocks = main_blocks; J.block0 = d->blocks; J.pad_ = 0;
+      d->blocks += main_blocks + bias_blocks;
+      return GT_OK;
+    }
+    gemm_path_count(GEMM_PATH_REDUCE4);
+    hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, t.base, t.stride, t.nslab, t.stride / 4, dW, acc,
+                       (const float*)t.bias, t.out, db, main_blocks);
+    LAUNCH_CHECK();
+    return GT_OK;
+  }
+  gemm_path_count(GEMM_PATH_REDUCE);
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(t.stride, 256)), dim3(256), 0, s, t.base, t.stride, t.nslab, t.stride, dW, acc);
+  LAUNCH_CHECK();
+  if (db) {
+    gemm_path_count(GEMM_PATH_REDUCE_SMALL);
+    hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(t.out, 64)), dim3(1024), 0, s, t.bias, (long)t.out, t.nslab, t.out, db, acc);
+    LAUNCH_CHECK();
+  }
+  return GT_OK;
+}
 // `ride_along` (optional): the backward-data product of the same layer; if it can share the weight gradient's launch it
 // does and *rode is set, otherwise the caller launches it itself.
 int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, long rows, int out, int in,
-                                  float* dW, float* db, bool accumulate, Scratch& slabs, Scratch& colp, hipStream_t s,
+                                  float* dW, float* db, bool accumulate, Scratch& slabs, Scratch& colp, int prec, hipStream_t s,
                                   SlabDefer* defer, const GemmArgs* ride_along, bool* rode) {
   if (rode) *rode = false;
   if (dW) {
@@ -162,64 +231,20 @@ int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, l
     if (nslab < 1) nslab = 1;
     int k_chunk = cdiv(cdiv(rows, nslab), GEMM_BK) * GEMM_BK;
     nslab = cdiv(rows, k_chunk);
-    const long slab_stride = (long)out * in;
-    const size_t need = (((size_t)nslab * slab_stride + (size_t)nslab * out) * sizeof(float) + 255) & ~(size_t)255;
-    const bool can4 = slab_stride % 4 == 0 && ((uintptr_t)dW) % 16 == 0;
-    float* slab_base = nullptr;
-    if (defer && defer->active && accumulate) { CHK(slab_defer_flush(*defer, s)); defer = nullptr; }   // never two combines of one dW in a launch
-    if (defer && defer->active && can4) {
-      if (defer->jobs.n == SLAB_MAX_JOBS || defer->used + need > defer->pool.bytes) {
-        CHK(slab_defer_flush(*defer, s));                       // recorded combines first, then (maybe) a larger pool
-        if (need > defer->pool.bytes) CHK(defer->pool.ensure(std::max(need * 4, (size_t)64 << 20)));
-      }
-      slab_base = (float*)((char*)defer->pool.p + defer->used);
-      defer->used += need;
-    } else {
-      defer = nullptr;
-      CHK(slabs.ensure(need));
-      slab_base = slabs.as<float>();
-    }
-    float* bias_slabs = slab_base + (size_t)nslab * slab_stride;
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = dZ; g.lda = lddz; g.B = X; g.ldb = ldx; g.C = slab_base; g.ldc = in;
-    g.M = out; g.N = in; g.K = (int)rows; g.k_chunk = k_chunk; g.slab_stride = slab_stride;
-    g.colsum_slab = db ? bias_slabs : nullptr;
-    g.drop = no_drop();
-    g.n_tiles_m = t64 ? 64 : 128;        // tile height request (launch_gemm_t overwrites the field with the tile count)
+    SlabSet set;
+    CHK(slab_place(defer, slabs, nslab, out, in, dW, accumulate, s, &set));
+    GemmArgs g = gemm_args(dZ, lddz, X, ldx, set.base, in, out, in, (int)rows);
+    g.k_chunk = k_chunk; g.slab_stride = set.stride;
+    g.colsum_slab = db ? set.bias : nullptr;
     if (t64 && ride_along && rode && gemm_pair_ok(*ride_along)) {
-      CHK(launch_gemm_pair(*ride_along, g, nslab, s));
+      CHK(launch_gemm_pair(*ride_along, g, nslab, prec, s));
       *rode = true;
     } else {
-      CHK(launch_gemm(GEMM_TN, g, nslab, s));
+      CHK(launch_gemm_slabs(g, t64 ? 64 : 128, nslab, prec, s));
     }
-    if (can4) {
-      const int main_blocks = cdiv(slab_stride / 4, 256);
-      const int bias_blocks = db ? cdiv(out, 256) : 0;
-      if (defer) {
-        SlabJob& J = defer->jobs.j[defer->jobs.n++];
-        J.slabs = slab_base; J.slab_stride = slab_stride; J.n4 = slab_stride / 4; J.out = dW; J.bslabs = bias_slabs; J.bout = db;
-        J.nslab = nslab; J.accumulate = accumulate ? 1 : 0; J.nb = out; J.main_blocks = main_blocks; J.block0 = defer->blocks; J.pad_ = 0;
-        defer->blocks += main_blocks + bias_blocks;
-        return GT_OK;
-      }
-      gemm_path_count(GEMM_PATH_REDUCE4);
-    hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab,
-                         slab_stride / 4, dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
-      LAUNCH_CHECK();
-    } else {
-      gemm_path_count(GEMM_PATH_REDUCE);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slabs.as<float>(),
-                         slab_stride, nslab, slab_stride, dW, accumulate ? 1 : 0);
-      LAUNCH_CHECK();
-      if (db) {
-        gemm_path_count(GEMM_PATH_REDUCE_SMALL);
-      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db,
-                           accumulate ? 1 : 0);
-        LAUNCH_CHECK();
-      }
-    }
-  } else if (db) {
+    return slab_combine(set, dW, db, accumulate, s);
+  }
+  if (db) {
     const int rows_per_blk = 128;
     const int nblk = cdiv(rows, rows_per_blk);
     CHK(colp.ensure((size_t)nblk * out * sizeof(float)));
@@ -243,10 +268,10 @@ int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, l
 // xp: x with a 16-byte row pitch (n-contiguous operand), adv: [rows][ld_adv] with a 16-byte pitch.
 int linear_backward_weight_split(const float* dZ, int lddz, long rows, long wrap, const float* xp, int ldxp, int cd,
                                  const float* adv, int ld_adv, int Da, int out, float* dW, float* db, bool accumulate,
-                                 Scratch& slabs, hipStream_t s, SlabDefer* defer, const GemmArgs* rider, bool* rode) {
+                                 Scratch& slabs, int prec, hipStream_t s, SlabDefer* defer, const GemmArgs* rider, bool* rode) {
   if (rode) *rode = false;
   if (rows != wrap && rows != 2 * wrap) return fail(GT_ERR_INVALID, "split weight gradient: rows must be one or two halves");
-  if (!gemm_vec_ok(dZ, lddz) || !gemm_vec_ok(xp, ldxp) || !gemm_vec_ok(adv, ld_adv) || tl_gemm_prec != PREC_F32)
+  if (!gemm_vec_ok(dZ, lddz) || !gemm_vec_ok(xp, ldxp) || !gemm_vec_ok(adv, ld_adv) || prec != PREC_F32)
     return fail(GT_ERR_INVALID, "split weight gradient: operands must be 16-byte loadable (float32 products)");
   const int in = cd + Da;
   // Slab count: the adversarial block has cdiv(Da, 64) tile columns against cdiv(cd, 64) of the x block but twice the frames, so
@@ -259,65 +284,21 @@ int linear_backward_weight_split(const float* dZ, int lddz, long rows, long wrap
   const int ns1 = cdiv(wrap, kc1);
   const int kc2 = cdiv(cdiv(rows, ns1), GEMM_BK) * GEMM_BK;
   const int ns2 = cdiv(rows, kc2);                      // <= ns1
-  nslab = ns1;
-  const long slab_stride = (long)out * in;
-  const size_t need = (((size_t)nslab * slab_stride + (size_t)nslab * out) * sizeof(float) + 255) & ~(size_t)255;
-  const bool can4 = slab_stride % 4 == 0 && ((uintptr_t)dW) % 16 == 0;
-  float* slab_base = nullptr;
-  if (defer && defer->active && accumulate) { CHK(slab_defer_flush(*defer, s)); defer = nullptr; }
-  if (defer && defer->active && can4) {
-    if (defer->jobs.n == SLAB_MAX_JOBS || defer->used + need > defer->pool.bytes) {
-      CHK(slab_defer_flush(*defer, s));
-      if (need > defer->pool.bytes) CHK(defer->pool.ensure(std::max(need * 4, (size_t)64 << 20)));
-    }
-    slab_base = (float*)((char*)defer->pool.p + defer->used);
-    defer->used += need;
-  } else {
-    defer = nullptr;
-    CHK(slabs.ensure(need));
-    slab_base = slabs.as<float>();
-  }
-  float* bias_slabs = slab_base + (size_t)nslab * slab_stride;
+  SlabSet set;
+  CHK(slab_place(defer, slabs, ns1, out, in, dW, accumulate, s, &set));
   if (ns2 < ns1)      // (tiny batches) the adversarial block and the bias sums of the trailing slabs are not written by any workgroup
-    HIPCHK(hipMemsetAsync(slab_base, 0, need, s));
-  GemmArgs g1, g2;
-  memset(&g1, 0, sizeof(g1));
-  g1.A = dZ; g1.lda = lddz; g1.A2 = rows == 2 * wrap ? dZ + wrap * (long)lddz : nullptr;
-  g1.B = xp; g1.ldb = ldxp; g1.C = slab_base; g1.ldc = in;
-  g1.M = out; g1.N = cd; g1.K = (int)wrap; g1.k_chunk = kc1; g1.slab_stride = slab_stride; g1.drop = no_drop();
-  g2 = g1;
-  g2.A2 = nullptr; g2.B = adv; g2.ldb = ld_adv; g2.C = slab_base + cd; g2.N = Da; g2.K = (int)rows; g2.k_chunk = kc2;
-  g2.colsum_slab = db ? bias_slabs : nullptr;
+    HIPCHK(hipMemsetAsync(set.base, 0, set.bytes, s));
+  GemmArgs g1 = gemm_args(dZ, lddz, xp, ldxp, set.base, in, out, cd, (int)wrap);
+  g1.A2 = rows == 2 * wrap ? dZ + wrap * (long)lddz : nullptr;
+  g1.k_chunk = kc1; g1.slab_stride = set.stride;
+  GemmArgs g2 = g1;
+  g2.A2 = nullptr; g2.B = adv; g2.ldb = ld_adv; g2.C = set.base + cd; g2.N = Da; g2.K = (int)rows; g2.k_chunk = kc2;
+  g2.colsum_slab = db ? set.bias : nullptr;
   if (g1.A2) {
-    CHK(launch_gemm_tn_pair(g1, g2, ns1, ns2, s, rider, rode));
+    CHK(launch_gemm_tn_pair(g1, g2, ns1, ns2, prec, s, rider, rode));
   } else {             // one half only: two plain weight-gradient launches
-    g1.n_tiles_m = 64; g2.n_tiles_m = 64;
-    CHK(launch_gemm(GEMM_TN, g1, ns1, s));
-    CHK(launch_gemm(GEMM_TN, g2, ns2, s));
+    CHK(launch_gemm_slabs(g1, 64, ns1, prec, s));
+    CHK(launch_gemm_slabs(g2, 64, ns2, prec, s));
   }
-  if (can4) {
-    const int main_blocks = cdiv(slab_stride / 4, 256), bias_blocks = db ? cdiv(out, 256) : 0;
-    if (defer) {
-      SlabJob& J = defer->jobs.j[defer->jobs.n++];
-      J.slabs = slab_base; J.slab_stride = slab_stride; J.n4 = slab_stride / 4; J.out = dW; J.bslabs = bias_slabs; J.bout = db;
-      J.nslab = nslab; J.accumulate = accumulate ? 1 : 0; J.nb = out; J.main_blocks = main_blocks; J.block0 = defer->blocks; J.pad_ = 0;
-      defer->blocks += main_blocks + bias_blocks;
-      return GT_OK;
-    }
-    gemm_path_count(GEMM_PATH_REDUCE4);
-    hipLaunchKernelGGL(slab_reduce4_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, slab_base, slab_stride, nslab,
-                       slab_stride / 4, dW, accumulate ? 1 : 0, (const float*)bias_slabs, out, db, main_blocks);
-    LAUNCH_CHECK();
-  } else {
-    gemm_path_count(GEMM_PATH_REDUCE);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(slab_stride, 256)), dim3(256), 0, s, slab_base, slab_stride, nslab, slab_stride, dW,
-                       accumulate ? 1 : 0);
-    LAUNCH_CHECK();
-    if (db) {
-      gemm_path_count(GEMM_PATH_REDUCE_SMALL);
-      hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(out, 64)), dim3(1024), 0, s, bias_slabs, (long)out, nslab, out, db, accumulate ? 1 : 0);
-      LAUNCH_CHECK();
-    }
-  }
-  return GT_OK;
+  return slab_combine(set, dW, db, accumulate, s);
 }

@@ -1,7 +1,7 @@
 // libgantts_hip.so -- float32 MFMA family, forward products Y = act(X.W^T + b) (GEMM_NT): kernel instantiations
 #include "gemm_f32_launch.hip.h"
 
-int launch_gemm_nt(const GemmArgs& g, int bm, int bn, hipStream_t s) {
-  if (bm == 64) return bn == 64 ? launch_gemm_v<GEMM_NT, 64, 64>(g, 1, s) : launch_gemm_v<GEMM_NT, 64, 128>(g, 1, s);
-  return bn == 64 ? launch_gemm_v<GEMM_NT, 128, 64>(g, 1, s) : launch_gemm_v<GEMM_NT, 128, 128>(g, 1, s);
+int launch_gemm_nt(const GemmArgs& g, int bm, int bn, int prec, hipStream_t s) {
+  if (bm == 64) return bn == 64 ? launch_gemm_v<GEMM_NT, 64, 64>(g, 1, prec, s) : launch_gemm_v<GEMM_NT, 64, 128>(g, 1, prec, s);
+  return bn == 64 ? launch_gemm_v<GEMM_NT, 128, 64>(g, 1, prec, s) : launch_gemm_v<GEMM_NT, 128, 128>(g, 1, prec, s);
 }

@@ -1,14 +1,14 @@
 // libgantts_hip.so -- float32 MFMA family, pair launches (a layer's backward-data product + weight gradient in one launch, gemm_pair_kernel)
 #include "gemm_f32_launch.hip.h"
 
-int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, hipStream_t s) {
+int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, int prec, hipStream_t s) {
   GemmArgs nn = nn_in, tn = tn_in;
   nn.wide_store = gemm_wide_store_ok(GEMM_NN, nn) ? 1 : 0;
   tn.wide_store = 0;
   nn.n_tiles_m = cdiv(nn.M, 64); nn.n_tiles_n = cdiv(nn.N, 64);
   tn.n_tiles_m = cdiv(tn.M, 64); tn.n_tiles_n = cdiv(tn.N, 64);
   const int n1 = nn.n_tiles_m * nn.n_tiles_n, n2 = tn.n_tiles_m * tn.n_tiles_n * nslab;
-  const bool bf16 = tl_gemm_prec == PREC_BF16;
+  const bool bf16 = prec == PREC_BF16;
   const size_t lds = bf16 ? std::max(gemm_lds_bytes<GEMM_NN, 64, 64, PREC_BF16>(), gemm_lds_bytes<GEMM_TN, 64, 64, PREC_BF16>())
                           : std::max(gemm_lds_bytes<GEMM_NN, 64, 64>(), gemm_lds_bytes<GEMM_TN, 64, 64>());
   const int am = bf16 ? GEMM_A_RUNTIME : (nn.act == ACT_NONE ? GEMM_A_NONE : ((nn.act == ACT_LEAKY_DROPOUT && nn.drop.mode == DROP_PHILOX) ? GEMM_A_LEAKY_PHILOX : GEMM_A_RUNTIME));
@@ -38,12 +38,12 @@ int launch_gemm_pair(const GemmArgs& nn_in, const GemmArgs& tn_in, int nslab, hi
 // the two weight-gradient products of a split first layer in one launch (gemm_tn_pair_kernel); float32, 64 x 64 tiles
 // rider (optional): a backward-data product without activation derivative whose B operand takes the 4-byte loader (K-contiguous A, 16-byte
 // loadable): its 64 x 64 tiles are the launch's last workgroups.  *rode tells the caller whether it was taken.
-int launch_gemm_tn_pair(const GemmArgs& g1_in, const GemmArgs& g2_in, int nslab1, int nslab2, hipStream_t s, const GemmArgs* rider, bool* rode) {
+int launch_gemm_tn_pair(const GemmArgs& g1_in, const GemmArgs& g2_in, int nslab1, int nslab2, int prec, hipStream_t s, const GemmArgs* rider, bool* rode) {
   GemmArgs g1 = g1_in, g2 = g2_in, g3;
   memset(&g3, 0, sizeof(g3));
   int n3 = 0;
   if (rode) *rode = false;
-  if (rider && rider->act == ACT_NONE && !rider->accumulate && rider->M > 0 && gemm_vec_ok(rider->A, rider->lda, true) && tl_gemm_prec == PREC_F32 &&
+  if (rider && rider->act == ACT_NONE && !rider->accumulate && rider->M > 0 && gemm_vec_ok(rider->A, rider->lda, true) && prec == PREC_F32 &&
       gemm_small_tiles_ok()) {
     g3 = *rider;
     g3.wide_store = gemm_wide_store_ok(GEMM_NN, g3) ? 1 : 0;

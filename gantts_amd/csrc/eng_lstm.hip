@@ -218,7 +218,7 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
     } else {
       for (int d = 0; d < dirs; ++d)   // Xp[:, d*4H:(d+1)*4H] = X W_ih^T (biases are added in the step kernel)
         CHK(linear_forward(in, ld_in, L.d[d].Wih, L.in, nullptr, W.xproj[l].as<float>() + (size_t)d * 4 * H, dirs * 4 * H, N, L.in,
-                           4 * H, ACT_NONE, no_drop(), s));
+                           4 * H, ACT_NONE, no_drop(), product_prec(e, role), s));
     }
     bool seq = false;
     CHK(lstm_launch_seq(e, G, W, role == GT_ROLE_G && e->matmul_bf16, l, B, T, false, nullptr, s, &seq));
@@ -274,6 +274,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, Lc = G.d.num_hidden;
   const bool acc = G.grads_dirty;
+  const int prec = product_prec(e, role);
   CHK(W.dout.ensure((size_t)2 * N * dirs * H * sizeof(float)));
   CHK(W.hshift.ensure((size_t)N * H * sizeof(float)));
   float* dout = W.dout.as<float>();                          // gradient w.r.t. the current layer's output
@@ -321,7 +322,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
     for (int d = 0; d < dirs && want_w; ++d) {
       const float* dGd = dG + (size_t)d * 4 * H;
       // dW_ih = dG_d^T X, db_ih = colsum(dG_d) (= db_hh)
-      CHK(linear_backward_weight(dGd, dirs * 4 * H, Xl, ldx, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, e->slabs, e->colp, s));
+      CHK(linear_backward_weight(dGd, dirs * 4 * H, Xl, ldx, N, 4 * H, L.in, L.d[d].dWih, L.d[d].dbih, acc, e->slabs, e->colp, prec, s));
       // bias_ih and bias_hh always receive the same gradient: keep them equal by copy
       hipLaunchKernelGGL(slab_reduce_small_kernel, dim3(cdiv(4 * H, 64)), dim3(1024), 0, s, L.d[d].dbih, (long)4 * H, 1, 4 * H,
                          L.d[d].dbhh, 0);
@@ -331,7 +332,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
                          e->d_lengths(), W.hshift.as<float>());
       LAUNCH_CHECK();
       CHK(linear_backward_weight(dGd, dirs * 4 * H, W.hshift.as<float>(), H, N, 4 * H, H, L.d[d].dWhh, nullptr, acc, e->slabs,
-                                 e->colp, s));
+                                 e->colp, prec, s));
     }
     // this layer's parameters (both directions: W_ih, W_hh, b_ih, b_hh each) are one contiguous bucket
     if (want_w) {
@@ -340,13 +341,8 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
     }
     if (l > 0 || dx0) {   // gradient w.r.t. the layer below's output (or the stack's input): sum over directions of dG_d W_ih_d
       float* const dst = l > 0 ? dout_other : dx0;
-      for (int d = 0; d < dirs; ++d) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = dG + (size_t)d * 4 * H; g.lda = dirs * 4 * H; g.B = L.d[d].Wih; g.ldb = L.in; g.C = dst; g.ldc = L.in;
-        g.M = (int)N; g.N = L.in; g.K = 4 * H; g.act = ACT_NONE; g.accumulate = d > 0 ? 1 : 0; g.drop = no_drop();
-        CHK(launch_gemm(GEMM_NN, g, 1, s));
-      }
+      for (int d = 0; d < dirs; ++d)
+        CHK(plain_product(GEMM_NN, dG + (size_t)d * 4 * H, dirs * 4 * H, L.d[d].Wih, L.in, dst, L.in, N, L.in, 4 * H, d > 0, prec, s));
       // through the inter-layer dropout of layer l-1 (same Philox sites as the forward)
       if (dropped_in) CHK(lstm_interlayer_dropout(e, role, l - 1, passes, npass, dout_other, dout_other, N, dirs * H, s));
       if (l > 0) std::swap(dout, dout_other);

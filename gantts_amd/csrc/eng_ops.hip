@@ -119,8 +119,7 @@ extern "C" int gt_op_linear_forward(const float* X, int ldx, const float* W, con
                                     int in_dim, int out_dim, int act, const float* keep_mask, float p, void* stream) {
   if (!X || !W || !Y || rows < 1 || in_dim < 1 || out_dim < 1) return fail(GT_ERR_INVALID, "bad argument");
   if (act < 0 || act > 2) return fail(GT_ERR_INVALID, "unknown activation");
-  tl_gemm_prec = PREC_F32;
-  return linear_forward(X, ldx, W, in_dim, bias, Y, ldy, rows, in_dim, out_dim, act, buffer_spec(keep_mask, p, out_dim), (hipStream_t)stream);
+  return linear_forward(X, ldx, W, in_dim, bias, Y, ldy, rows, in_dim, out_dim, act, buffer_spec(keep_mask, p, out_dim), PREC_F32, (hipStream_t)stream);
 }
 
 extern "C" int gt_op_linear_backward(const float* dY, int lddy, const float* X, int ldx, const float* W, int64_t rows, int in_dim,
@@ -128,17 +127,16 @@ extern "C" int gt_op_linear_backward(const float* dY, int lddy, const float* X, 
                                      const float* keep_mask_prev, float p_prev, float* dW, float* db, void* stream) {
   if (!dY || rows < 1 || in_dim < 1 || out_dim < 1) return fail(GT_ERR_INVALID, "bad argument");
   hipStream_t s = (hipStream_t)stream;
-  tl_gemm_prec = PREC_F32;
   if (dX) {
     if (!W) return fail(GT_ERR_INVALID, "dX requested without W");
     if (act_prev != ACT_NONE && !H_prev) return fail(GT_ERR_INVALID, "activation derivative requested without H_prev");
     CHK(linear_backward_data(dY, lddy, W, in_dim, 0, dX, lddx, rows, out_dim, in_dim, act_prev, H_prev, in_dim,
-                             buffer_spec(keep_mask_prev, p_prev, in_dim), s));
+                             buffer_spec(keep_mask_prev, p_prev, in_dim), PREC_F32, s));
   }
   if (dW || db) {
     if (dW && !X) return fail(GT_ERR_INVALID, "dW requested without X");
     Scratch slabs, colp;
-    int r = linear_backward_weight(dY, lddy, X, ldx, rows, out_dim, in_dim, dW, db, false, slabs, colp, s);
+    int r = linear_backward_weight(dY, lddy, X, ldx, rows, out_dim, in_dim, dW, db, false, slabs, colp, PREC_F32, s);
     hipError_t err = hipStreamSynchronize(s);
     slabs.release(); colp.release();
     if (r) return r;
@@ -224,9 +222,8 @@ static DropoutSpec case_drop_spec(int mode, const float* mask, int ld_mask, floa
 }
 
 // One product of the float32 MFMA family through the engine's own dispatch (linear_forward / launch_gemm / linear_backward_data /
-// linear_backward_weight / linear_backward_weight_split): parity hook of tests/test_gpu_gemm_f32.py.  Forms the engine builds in
-// place (the added-matrix and two-segment forward of the split first layer, eng_step.hip: stack_forward; accumulate) are built
-// here the same way and go to launch_gemm.
+// linear_backward_weight / linear_backward_weight_split): parity hook of tests/test_gpu_gemm_f32.py.  The added-matrix and two-segment
+// forward of the split first layer go through the builders the engine's stack_forward calls (linear_forward, linear_forward_seg).
 extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "null case");
   if (c->route < GT_GEMM_ROUTE_FORWARD || c->route > GT_GEMM_ROUTE_WEIGHT_GRAD_SPLIT) return fail(GT_ERR_INVALID, "unknown route %d", c->route);
@@ -252,57 +249,37 @@ extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
   Scratch slabs, colp;
   SlabDefer sd;
   sd.active = c->defer != 0;
-  tl_gemm_prec = c->prec ? PREC_BF16 : PREC_F32;
+  const int prec = c->prec ? PREC_BF16 : PREC_F32;
   auto body = [&]() -> int {
-    if (route == GT_GEMM_ROUTE_FORWARD) {
-      if (!c->addm && !c->accumulate)
-        return linear_forward(c->x, c->ldx, c->w, c->ldw, c->bias, c->y, c->ldy, c->rows, c->in_dim, c->out_dim, c->act, drop, s);
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = c->x; g.lda = c->ldx; g.B = c->w; g.ldb = c->ldw; g.C = c->y; g.ldc = c->ldy;
-      g.M = c->rows; g.N = c->out_dim; g.K = c->in_dim; g.bias = c->bias; g.act = c->act; g.drop = drop; g.accumulate = c->accumulate ? 1 : 0;
-      if (c->addm) { g.addm = c->addm; g.ld_addm = c->ld_addm; g.addm_wrap = c->wrap; }
-      return launch_gemm(GEMM_NT, g, 1, s);
-    }
-    if (seg) {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = c->x; g.lda = c->ldx; g.B = c->w; g.ldb = c->ldw; g.C = c->y; g.ldc = c->ldy;
-      g.M = c->wrap; g.N = c->out_dim; g.K = c->cd; g.bias = c->bias; g.act = c->act; g.drop = drop;
-      g.A_seg = c->adv; g.lda_seg = c->ld_adv; g.B_seg = c->w + c->cd; g.K_seg = c->in_dim - c->cd;
-      g.dual_rows = c->rows == 2 * c->wrap ? c->wrap : 0;
-      return launch_gemm(GEMM_NT, g, 1, s);
-    }
+    if (route == GT_GEMM_ROUTE_FORWARD)
+      return linear_forward(c->x, c->ldx, c->w, c->ldw, c->bias, c->y, c->ldy, c->rows, c->in_dim, c->out_dim, c->act, drop, prec, s, c->addm,
+                            c->ld_addm, c->wrap, c->accumulate != 0);
+    if (seg)
+      return linear_forward_seg(c->x, c->ldx, c->wrap, c->cd, c->adv, c->ld_adv, c->rows, c->w, c->ldw, c->in_dim, c->bias, c->y, c->ldy, c->out_dim,
+                                c->act, drop, prec, s);
     if (route == GT_GEMM_ROUTE_BACKWARD_DATA) {
-      if (!c->accumulate)
-        return linear_backward_data(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h, c->ldh,
-                                    drop, s);
       GemmArgs g = backward_data_args(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h,
                                       c->ldh, drop);
-      g.accumulate = 1;
-      return launch_gemm(GEMM_NN, g, 1, s);
+      g.accumulate = c->accumulate ? 1 : 0;
+      return launch_gemm(GEMM_NN, g, prec, s);
     }
     bool rode = false;
-    GemmArgs nn;
-    memset(&nn, 0, sizeof(nn));
-    if (route == GT_GEMM_ROUTE_WEIGHT_GRAD) {
-      if (c->rider)
-        nn = backward_data_args(c->dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows, c->out_dim, c->ncols, c->act, c->h, c->ldh, drop);
-      CHK(linear_backward_weight(c->dy, c->ld_dy, c->x, c->ldx, c->rows, c->out_dim, c->in_dim, c->dw, c->db, c->accumulate != 0, slabs, colp, s,
+    const long row0 = split ? c->rows - c->wrap : 0;      // split: the rider reads the last half's rows (the generated rows of the D step)
+    GemmArgs nn{};
+    if (c->rider)
+      nn = backward_data_args(c->dy + row0 * c->ld_dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->rows - row0, c->out_dim, c->ncols, c->act,
+                              c->h, c->ldh, drop);
+    if (!split) {
+      CHK(linear_backward_weight(c->dy, c->ld_dy, c->x, c->ldx, c->rows, c->out_dim, c->in_dim, c->dw, c->db, c->accumulate != 0, slabs, colp, prec, s,
                                  &sd, c->rider ? &nn : nullptr, &rode));
     } else {
-      const long row0 = c->rows - c->wrap;      // the rider reads the last half's rows (the generated rows of the D step)
-      if (c->rider)
-        nn = backward_data_args(c->dy + row0 * c->ld_dy, c->ld_dy, c->w, c->ldw, c->col0, c->dx, c->ld_dx, c->wrap, c->out_dim, c->ncols, c->act,
-                                c->h, c->ldh, drop);
       CHK(linear_backward_weight_split(c->dy, c->ld_dy, c->rows, c->wrap, c->x, c->ldx, c->cd, c->adv, c->ld_adv, c->in_dim - c->cd, c->out_dim,
-                                       c->dw, c->db, c->accumulate != 0, slabs, s, &sd, c->rider ? &nn : nullptr, &rode));
+                                       c->dw, c->db, c->accumulate != 0, slabs, prec, s, &sd, c->rider ? &nn : nullptr, &rode));
     }
-    if (c->rider && !rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+    if (c->rider && !rode) CHK(launch_gemm(GEMM_NN, nn, prec, s));
     return slab_defer_flush(sd, s);
   };
   const int r = body();
-  tl_gemm_prec = PREC_F32;
   const hipError_t err = hipStreamSynchronize(s);
   slabs.release(); colp.release(); sd.pool.release();
   if (r) return r;

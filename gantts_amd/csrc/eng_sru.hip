@@ -166,12 +166,7 @@ bool sru_d_needs_f32_input(const gt_engine* e) {
   const Net& D = e->net[GT_ROLE_D];
   return !sru_b16(e, GT_ROLE_D) || D.sru.empty() || D.sru[0].k == 3;
 }
-// (whatever a discriminator's stack calls through the precision-dispatched float32 helpers stays in the float32 family)
-struct SruPrecScope {
-  int saved;
-  explicit SruPrecScope(int role) : saved(tl_gemm_prec) { if (role != GT_ROLE_G) tl_gemm_prec = PREC_F32; }
-  ~SruPrecScope() { tl_gemm_prec = saved; }
-};
+// (the float32-storage products of a stack run at product_prec(e, role): a discriminator's stay float32 products)
 // ... with the cooperative scans on whole 8-frame blocks and whole workgroups: the scans write the bf16 images of the next product's input
 static bool sru_fold(const gt_engine* e, int role, int nseq, int T) {
   const Net& G = e->net[role];
@@ -186,7 +181,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
                       const float** top, int* ld_top, const CatSrc* cat0, bool want_w) {
   Net& G = e->net[role];
   NetWs& W = e->ws[role];
-  const SruPrecScope prec(role);
+  const int prec = product_prec(e, role);
   const int B = nseq;
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs;
@@ -268,17 +263,9 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
       CHK(W.wt[l].ensure((size_t)ncols * L.k * L.in * sizeof(float)));
       launch_transpose_f32(L.W, L.in, ncols * L.k, ncols * L.k, W.wt[l].as<float>(), L.in, s);
       LAUNCH_CHECK();
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = xin; g.lda = ld_xin; g.B = W.wt[l].as<float>(); g.ldb = L.in; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
-      g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.act = ACT_NONE; g.drop = no_drop();
-      CHK(launch_gemm(GEMM_NT, g, 1, s));
+      CHK(plain_product(GEMM_NT, xin, ld_xin, W.wt[l].as<float>(), L.in, W.u[l].as<float>(), ncols * L.k, N, ncols * L.k, L.in, false, prec, s));
     } else {  // U = xin W   (W is (n_in, ncols*k): n-contiguous rows -> NN orientation)
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = xin; g.lda = ld_xin; g.B = L.W; g.ldb = ncols * L.k; g.C = W.u[l].as<float>(); g.ldc = ncols * L.k;
-      g.M = (int)N; g.N = ncols * L.k; g.K = L.in; g.act = ACT_NONE; g.drop = no_drop();
-      CHK(launch_gemm(GEMM_NN, g, 1, s));
+      CHK(plain_product(GEMM_NN, xin, ld_xin, L.W, ncols * L.k, W.u[l].as<float>(), ncols * L.k, N, ncols * L.k, L.in, false, prec, s));
     }
     SruArgs a = sru_args(e, role, W, l, B, T, in, ld_in);
     img_ready = false;
@@ -341,7 +328,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
   (void)passes;      // (the passes' dropout tables are the forward's stash)
   Net& G = e->net[role];
   NetWs& W = e->ws[role];
-  const SruPrecScope prec(role);
+  const int prec = product_prec(e, role);
   const int B = nseq;
   const long N = (long)B * T;
   const int H = G.d.hidden_dim, dirs = G.d.bidirectional ? 2 : 1, ncols = H * dirs, Lc = G.d.num_hidden;
@@ -409,7 +396,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
       } else {
         // dW = xin^T dU   (TN: A = xin is m-contiguous over n_in, B = dU)
         CHK(linear_backward_weight(xin, ld_xin, e->s_du.as<float>(), ncols * L.k, N, L.in, ncols * L.k, L.dW, nullptr, acc, e->slabs,
-                                   e->colp, s));
+                                   e->colp, prec, s));
       }
       CHK(comm_grads_ready(e, role, L.dW, (long)L.in * ncols * L.k + 2L * ncols, s));
       if (l > 0 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
@@ -420,12 +407,7 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
                               B16Dst(dh_other, L.in, L.k == 3 && !rdrop), s));
       } else {
         // d in = (dU W^T) (.) mask_in + highway term     (NT: B[n = i][k = c] = W[i*ldw + c])
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = e->s_du.as<float>(); g.lda = ncols * L.k; g.B = L.W; g.ldb = ncols * L.k; g.C = dh_other; g.ldc = L.in;
-        g.M = (int)N; g.N = L.in; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
-        g.accumulate = (L.k == 3 && !rdrop) ? 1 : 0;
-        CHK(launch_gemm(GEMM_NT, g, 1, s));
+        CHK(plain_product(GEMM_NT, e->s_du.as<float>(), ncols * L.k, L.W, ncols * L.k, dh_other, L.in, N, L.in, ncols * L.k, L.k == 3 && !rdrop, prec, s));
       }
       std::swap(dh, dh_other);         // (with input dropout: finished by the scan of layer l - 1, SruArgs::up_mul / up_add)
     }
@@ -444,12 +426,8 @@ int sru_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int nse
         CHK(b16_backward_data(W.du_b.r() + (size_t)row0 * W.du_b.ld, W.du_b.ld, Nf, W.ssh[0].r() + (size_t)col0 * W.ssh[0].ldw, W.ssh[0].ldw, Da,
                               ncols * L.k, ACT_NONE, nullptr, no_drop(), B16Dst(dx_adv, Da), s));
       } else {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = e->s_du.as<float>() + (size_t)row0 * ncols * L.k; g.lda = ncols * L.k;
-        g.B = L.W + (size_t)col0 * ncols * L.k; g.ldb = ncols * L.k; g.C = dx_adv; g.ldc = Da;
-        g.M = (int)Nf; g.N = Da; g.K = ncols * L.k; g.act = ACT_NONE; g.drop = no_drop();
-        CHK(launch_gemm(GEMM_NT, g, 1, s));
+        CHK(plain_product(GEMM_NT, e->s_du.as<float>() + (size_t)row0 * ncols * L.k, ncols * L.k, L.W + (size_t)col0 * ncols * L.k, ncols * L.k, dx_adv, Da,
+                          Nf, Da, ncols * L.k, false, prec, s));
       }
       if (rdrop || L.k == 3) {
         SruDxAdvArgs f;

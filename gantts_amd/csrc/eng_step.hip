@@ -68,6 +68,7 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
                          sites and the stash buffers of ALL layers are still set up: the fused stack launch takes over from there) */) {
   Net& n = e->net[role];
   std::vector<Scratch>& acts = e->ws[role].act;
+  const int prec = product_prec(e, role);
   specs.resize(n.hidden.size());
   const float* cur = in;
   int ld = ld_in;
@@ -80,16 +81,10 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
     if ((int)l >= max_layers) continue;
     if (l == 0 && fs && specs[l].mode == DROP_PHILOX && gt_tuning().split_fused && gemm_vec_ok(fs->x, fs->ldx, true) &&
         gemm_vec_ok(L.W, L.in, true) && gemm_vec_ok(fs->adv, fs->ld_adv, true) && fs->wrap > 64 && gemm_small_tiles_ok() &&
-        tl_gemm_prec == PREC_F32 && (rows == fs->wrap || rows == 2 * fs->wrap)) {
-      // ONE launch (GEMM_A_LEAKY_PHILOX_SEG): every tile multiplies its rows of x by W[:, :cd]^T once, then -- per half of the
-      // pass -- continues the same accumulators over the adversarial columns and runs that half's epilogue: no P buffer
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = fs->x; g.lda = fs->ldx; g.B = L.W; g.ldb = L.in; g.C = acts[l].as<float>(); g.ldc = L.out;
-      g.M = (int)fs->wrap; g.N = L.out; g.K = fs->cd; g.bias = L.b; g.act = ACT_LEAKY_DROPOUT; g.drop = specs[l];
-      g.A_seg = fs->adv; g.lda_seg = fs->ld_adv; g.B_seg = L.W + fs->cd; g.K_seg = L.in - fs->cd;
-      g.dual_rows = rows == 2 * fs->wrap ? (int)fs->wrap : 0;
-      CHK(launch_gemm(GEMM_NT, g, 1, s));
+        prec == PREC_F32 && (rows == fs->wrap || rows == 2 * fs->wrap)) {
+      // ONE launch (linear_forward_seg): no P buffer
+      CHK(linear_forward_seg(fs->x, fs->ldx, fs->wrap, fs->cd, fs->adv, fs->ld_adv, rows, L.W, L.in, L.in, L.b, acts[l].as<float>(), L.out, L.out,
+                             ACT_LEAKY_DROPOUT, specs[l], prec, s));
       cur = acts[l].as<float>();
       ld = L.out;
       continue;
@@ -97,20 +92,16 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
     if (l == 0 && fs) {
       const int Da = L.in - fs->cd;
       CHK(e->d_pre.ensure((size_t)fs->wrap * L.out * sizeof(float)));
-      CHK(linear_forward(fs->x, fs->ldx, L.W, L.in, L.b, e->d_pre.as<float>(), L.out, fs->wrap, fs->cd, L.out, ACT_NONE, no_drop(), s));
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = fs->adv; g.lda = fs->ld_adv; g.B = L.W + fs->cd; g.ldb = L.in; g.C = acts[l].as<float>(); g.ldc = L.out;
-      g.M = (int)rows; g.N = L.out; g.K = Da; g.act = ACT_LEAKY_DROPOUT; g.drop = specs[l];
-      g.addm = e->d_pre.as<float>(); g.ld_addm = L.out; g.addm_wrap = (int)fs->wrap;
-      CHK(launch_gemm(GEMM_NT, g, 1, s));
+      CHK(linear_forward(fs->x, fs->ldx, L.W, L.in, L.b, e->d_pre.as<float>(), L.out, fs->wrap, fs->cd, L.out, ACT_NONE, no_drop(), prec, s));
+      CHK(linear_forward(fs->adv, fs->ld_adv, L.W + fs->cd, L.in, nullptr, acts[l].as<float>(), L.out, rows, Da, L.out, ACT_LEAKY_DROPOUT, specs[l],
+                         prec, s, e->d_pre.as<float>(), L.out, fs->wrap));
       cur = acts[l].as<float>();
       ld = L.out;
       continue;
     }
     const float* W = L.W;
     int ldw = L.in;
-    if (l == 0 && (L.in & 3) && gemm_vec_ok(cur, ld) && !gemm_vec_ok(L.W, L.in, true) && tl_gemm_prec == PREC_F32) {
+    if (l == 0 && (L.in & 3) && gemm_vec_ok(cur, ld) && !gemm_vec_ok(L.W, L.in, true) && prec == PREC_F32) {
       // The input image takes 16-byte loads (the discriminator's [x | adv] image, pitch 484) but the weight rows (483
       // floats) do not: multiply by a copy of W with its row pitch rounded up to 4 floats, re-made from the caller's
       // parameter buffer before every pass (it may have been stepped, loaded or broadcast since).
@@ -120,7 +111,7 @@ static int stack_forward(gt_engine* e, int role, const float* in, int ld_in, lon
       LAUNCH_CHECK();
       W = e->ws[role].w0pad.as<float>();
     }
-    CHK(linear_forward(cur, ld, W, ldw, L.b, acts[l].as<float>(), L.out, rows, L.in, L.out, ACT_LEAKY_DROPOUT, specs[l], s));
+    CHK(linear_forward(cur, ld, W, ldw, L.b, acts[l].as<float>(), L.out, rows, L.in, L.out, ACT_LEAKY_DROPOUT, specs[l], prec, s));
     cur = acts[l].as<float>();
     ld = L.out;
   }
@@ -139,7 +130,7 @@ static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, lo
                           float* dX, int lddx, int col0, int ncols, long row0, long nrows, hipStream_t s, const FirstSplit* fs = nullptr) {
   Net& n = e->net[role];
   std::vector<Scratch>& acts = e->ws[role].act;
-  const int L = (int)n.hidden.size();
+  const int L = (int)n.hidden.size(), prec = product_prec(e, role);
   // per-layer launches: each layer's weight gradient right behind the product that made its dZ (still warm in L2 / MALL)
   for (int l = L - 1; l >= 0; --l) {
     const Lin& Lr = n.hidden[l];
@@ -154,10 +145,10 @@ static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, lo
       GemmArgs leak;
       if (dX) leak = backward_data_args(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0, no_drop());
       CHK(linear_backward_weight_split(cur, Lr.out, rows, fs->wrap, fs->xp, fs->ldxp, fs->cd, fs->adv, fs->ld_adv, Lr.in - fs->cd, Lr.out,
-                                       Lr.dW, Lr.db, n.grads_dirty, e->slabs, s, &e->ws[role].sdefer, dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
+                                       Lr.dW, Lr.db, n.grads_dirty, e->slabs, prec, s, &e->ws[role].sdefer, dX && gt_tuning().leak_rider ? &leak : nullptr, &rode));
       CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
     } else if (want_w) {
-      CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, s, &e->ws[role].sdefer,
+      CHK(linear_backward_weight(cur, Lr.out, Xin, ldx, rows, Lr.out, Lr.in, Lr.dW, Lr.db, n.grads_dirty, e->slabs, e->colp, prec, s, &e->ws[role].sdefer,
                                  l > 0 ? &nn : nullptr, &rode));
       CHK(comm_grads_ready(e, role, Lr.dW, (long)Lr.out * Lr.in + Lr.out, s));
       // generator: all layers above the first leave as one message under the first layer's backward; the discriminator's
@@ -165,11 +156,11 @@ static int stack_backward(gt_engine* e, int role, const float* in, int ld_in, lo
       if (l == 1 && (role == GT_ROLE_G || !e->opt_comm_d_one_msg)) CHK(comm_flush(e, role, s));
     }
     if (l > 0) {
-      if (!rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+      if (!rode) CHK(launch_gemm(GEMM_NN, nn, prec, s));
       std::swap(cur, other);
     } else if (dX && !rode) {
       CHK(linear_backward_data(cur + row0 * Lr.out, Lr.out, Lr.W, Lr.in, col0, dX, lddx, nrows, Lr.out, ncols, ACT_NONE, nullptr, 0,
-                               no_drop(), s));
+                               no_drop(), prec, s));
     }
   }
   return GT_OK;
@@ -269,7 +260,7 @@ int out_layer_forward(gt_engine* e, int role, const OutTop& top, long rows, floa
   const Net& n = e->net[role];
   const Lin& L = n.last;
   const int act = n.d.last_sigmoid ? ACT_SIGMOID : ACT_NONE;
-  if (!top.img) return linear_forward(top.x, top.ld, L.W, L.in, L.b, out, n.d.out_dim, rows, L.in, L.out, act, no_drop(), s);
+  if (!top.img) return linear_forward(top.x, top.ld, L.W, L.in, L.b, out, n.d.out_dim, rows, L.in, L.out, act, no_drop(), product_prec(e, role), s);
   B16Img& I = *top.img;
   if (!top.img_ready) {
     CHK(I.ensure(rows, L.in, top.want_t));
@@ -296,11 +287,12 @@ int out_layer_backward(gt_engine* e, int role, const float* gy, int ldgy, long r
   }
   const GemmArgs nn = backward_data_args(gy, ldgy, L.W, L.in, 0, dst.to.C, dst.to.ldc, rows, Do, L.in, dst.act_prev, through_act ? top.x : nullptr,
                                          through_act ? top.ld : 0, dst.drop);
+  const int prec = product_prec(e, role);
   bool rode = false;
-  CHK(linear_backward_weight(gy, ldgy, top.x, top.ld, rows, Do, L.in, L.dW, L.db, n.grads_dirty, e->slabs, e->colp, s, defer,
+  CHK(linear_backward_weight(gy, ldgy, top.x, top.ld, rows, Do, L.in, L.dW, L.db, n.grads_dirty, e->slabs, e->colp, prec, s, defer,
                              dst.ride ? &nn : nullptr, &rode));
   CHK(comm_grads_ready(e, role, L.dW, (long)Do * L.in + Do, s));
-  if (!rode) CHK(launch_gemm(GEMM_NN, nn, 1, s));
+  if (!rode) CHK(launch_gemm(GEMM_NN, nn, prec, s));
   return GT_OK;
 }
 // what an MLP stack's pass left for its output layer: the top activation, as float32 rows or (bf16 storage, after refresh_shadows(with_last)) as image
@@ -380,7 +372,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     CHK(e->tx.ensure((size_t)N * sd * sizeof(float)));
     CHK(e->gx.ensure((size_t)N * sd * sizeof(float)));
     // T(x) = sigmoid(T x_static), x_static = x[:, :, :static_dim]   (models.py:57-60)
-    CHK(linear_forward(x, G.d.in_dim, G.gate.W, sd, G.gate.b, e->tx.as<float>(), sd, N, sd, sd, ACT_SIGMOID, no_drop(), s));
+    CHK(linear_forward(x, G.d.in_dim, G.gate.W, sd, G.gate.b, e->tx.as<float>(), sd, N, sd, sd, ACT_SIGMOID, no_drop(), product_prec(e, GT_ROLE_G), s));
     CHK(mlpg_forward(e, gsrc, G.d.out_dim, e->d_scol_i2o, e->d_sstride_i2o, sd, e->gx.as<float>(), sd, B, T, *band, s));
     launch_highway_forward(x, G.d.in_dim, e->tx.as<float>(), sd, e->gx.as<float>(), sd, y_hat_static, sd, N, sd, s);
     LAUNCH_CHECK();
@@ -547,7 +539,7 @@ static int head_sums(gt_engine* e, int nblk, int K, bool dw, HeadSums* o) {
 static bool d_fused_ok(gt_engine* e, long rows) {
   Net& D = e->net[GT_ROLE_D];
   if (e->opt_fused_dstack < 2 && dstack_panels(rows) < gemm_cu_count()) return false;
-  if (!e->opt_fused_dstack || D.d.arch != GT_ARCH_MLP || tl_gemm_prec != PREC_F32 || !dstack_hidden_ok(D.d.hidden_dim)) return false;
+  if (!e->opt_fused_dstack || D.d.arch != GT_ARCH_MLP || product_prec(e, GT_ROLE_D) != PREC_F32 || !dstack_hidden_ok(D.d.hidden_dim)) return false;
   if (D.hidden.empty() || (int)D.hidden.size() > DS_MAXL || D.last.out != 1 || e->Da < 1 || e->Da > 64) return false;
   for (size_t l = 0; l < D.hidden.size(); ++l)
     if (D.hidden[l].out != D.d.hidden_dim || (l > 0 && D.hidden[l].in != D.d.hidden_dim)) return false;
@@ -725,7 +717,7 @@ int ResultsChannel::post_early(hipStream_t s, unsigned ticket) {
 // ------------------------------------------------------------------------------------------
 // the split first layer (FirstSplit) applies to the conditioned float32 MLP discriminator
 static bool d_split_ok(gt_engine* e, const float* x) {
-  return e->opt_split_first && tl_gemm_prec == PREC_F32 && e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0 &&
+  return e->opt_split_first && product_prec(e, GT_ROLE_D) == PREC_F32 && e->cfg.discriminator_linguistic_condition && x && cond_dim(e) > 0 &&
          e->Da > 0 && gemm_small_tiles_ok() && (e->net[GT_ROLE_D].d.hidden_dim & 3) == 0;     // (dZ as a 16-byte loadable operand)
 }
 // A recurrent discriminator (LSTMRNN / SRURNN in the discriminator slot, train.py:773-774) runs the natural and the generated sequences of
@@ -1083,7 +1075,8 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     CHK(e->dtz.ensure((size_t)N * sd * sizeof(float)));
     launch_highway_backward(gs, sd, e->tx.as<float>(), sd, e->gx.as<float>(), sd, e->dgx.as<float>(), sd, e->dtz.as<float>(), sd, N, sd, s);
     LAUNCH_CHECK();
-    CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, s, &W.sdefer));
+    CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, product_prec(e, GT_ROLE_G), s,
+                               &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.gate.dW, (long)sd * sd + sd, s));
     CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o, e->d_sstride_i2o, sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->g_band, s));
   } else if (e->g_band) {
@@ -1124,7 +1117,7 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   // of D when it conditions on the same tensor).
   const float* xin = x;
   int ldxin = gx_pitch(e);
-  if (!gemm_vec_ok(x, ldxin) && tl_gemm_prec == PREC_F32) {
+  if (!gemm_vec_ok(x, ldxin) && product_prec(e, GT_ROLE_G) == PREC_F32) {
     if (e->img_cat.valid && e->img_cat.x == x && e->cfg.discriminator_linguistic_condition && cond_dim(e) == G.d.in_dim && e->dcat.p) {
       ldxin = (d_in_dim(e) + 3) & ~3;
       xin = e->dcat.as<float>() + N * ldxin;      // the generated half: the one that is valid whenever img_cat is
@@ -1297,7 +1290,6 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
   Net& G = e->net[GT_ROLE_G];
   if (!G.bound || !G.d.grads || !e->g_pass_valid) return fail(GT_ERR_STATE, "no generator pass to back-propagate");
   hipStream_t s = (hipStream_t)stream;
-  tl_gemm_prec = e->matmul_bf16 ? PREC_BF16 : PREC_F32;      // this entry point launches GEMMs without check_common
   CHK(fault_seen(e));
   e->ws[GT_ROLE_G].sdefer.reset(false);      // combines run in place here
   const long N = e->N;
@@ -1346,7 +1338,6 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
       p.kind = n.d.arch == GT_ARCH_SRU ? D_SRU : D_LSTM;
       p.npass = 1; p.passes[0] = 0; p.B = p.nseq = B; p.T = T; p.img = x; p.ldc = n.d.in_dim;
       CHK(d_pass_forward(e, p, s));
-      if (p.kind == D_SRU) tl_gemm_prec = PREC_F32;      // hidden2out stays a float32 product under either bf16 option
       return out_layer_forward(e, role, OutTop{p.top, p.ld_top}, N, out, s);
     }
     e->g_pass_valid = false;

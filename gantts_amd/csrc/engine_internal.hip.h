@@ -435,10 +435,11 @@ gt::DropoutSpec philox_site_spec(gt_engine* e, int role, int pass, int layer, ui
 gt::DropoutSpec drop_spec(gt_engine* e, int role, int pass, int layer, const float* stacked_mask, int ld, long half_rows = 0);
 
 // ------------------------------------------------------------------------------------------
-// eng_gemm_f32.hip -- products of the float32 family (PREC_F32) or bf16 products on float32 storage (PREC_BF16), chosen per
-// engine entry point for the launches it issues on this thread
+// eng_gemm_f32.hip -- products of the float32 family (PREC_F32) or bf16 products on float32 storage (PREC_BF16): `prec`, an argument of
+// every launch function.  product_prec (eng_core.hip) is the policy: PREC_F32 for an SRU network in the discriminator slot (its stack and
+// hidden2out stay float32 products under either bf16 option), else PREC_BF16 iff GT_OPT_MATMUL_BF16.
 // ------------------------------------------------------------------------------------------
-extern thread_local int tl_gemm_prec;
+int product_prec(const gt_engine* e, int role);
 // gt_gemm_path_counts: launches of the family by kernel, counted on the host where they are issued (slot encoding in gantts_hip.h)
 enum { GEMM_PATH_PAIR = 576, GEMM_PATH_TN_PAIR = 580, GEMM_PATH_REDUCE4 = 582, GEMM_PATH_REDUCE = 583, GEMM_PATH_REDUCE_SMALL = 584,
        GEMM_PATH_COLSUM_PARTIAL = 585, GEMM_PATH_COLSUM_FINALIZE = 586, GEMM_PATH_REDUCE_MULTI = 587 };
@@ -470,21 +471,38 @@ int launch_head_finalize(const gt::HeadCall& c, const gt::HeadSums& o, int nblk,
 int launch_d_head(const gt::HeadArgs& a, hipStream_t s);
 int launch_dstack_pass(const gt::DStackCall& k, hipStream_t s);
 gt::DropoutSpec no_drop();
-int launch_gemm(int kind, const gt::GemmArgs& g, int nslab, hipStream_t s);
-int linear_forward(const float* X, int ldx, const float* W, int ldw, const float* b, float* Y, int ldy,
-                   long rows, int in, int out, int act, const gt::DropoutSpec& drop, hipStream_t s);
+int launch_gemm(int kind, const gt::GemmArgs& g, int prec, hipStream_t s);      // GEMM_NT / GEMM_NN, tiles chosen from the shape
+// C [M][N] (+)= A [M][K] . B^T (GEMM_NT: B [N][K]) or A . B (GEMM_NN: B [K][N]): no bias, activation or dropout
+int plain_product(int kind, const float* A, int lda, const float* B, int ldb, float* C, int ldc, long M, int N, int K, bool accumulate, int prec,
+                  hipStream_t s);
+// Y (+)= act(X W^T + b [+ addm[r mod addm_wrap]]): addm, the split first layer's added matrix (forward of [x | adv] as two products)
+int linear_forward(const float* X, int ldx, const float* W, int ldw, const float* b, float* Y, int ldy, long rows, int in, int out, int act,
+                   const gt::DropoutSpec& drop, int prec, hipStream_t s, const float* addm = nullptr, int ld_addm = 0, long addm_wrap = 0,
+                   bool accumulate = false);
+int linear_forward_seg(const float* x, int ldx, long wrap, int cd, const float* adv, int ld_adv, long rows, const float* W, int ldw, int in,
+                       const float* b, float* Y, int ldy, int out, int act, const gt::DropoutSpec& drop, int prec, hipStream_t s);
 gt::GemmArgs backward_data_args(const float* dZ, int lddz, const float* W, int ldw, int col0, float* dX, int lddx,
                                 long rows, int out, int ncols, int act_prev, const float* H, int ldh, const gt::DropoutSpec& drop);
 int linear_backward_data(const float* dZ, int lddz, const float* W, int ldw, int col0, float* dX, int lddx,
-                         long rows, int out, int ncols, int act_prev, const float* H, int ldh, const gt::DropoutSpec& drop, hipStream_t s);
+                         long rows, int out, int ncols, int act_prev, const float* H, int ldh, const gt::DropoutSpec& drop, int prec, hipStream_t s);
+// the weight-gradient slab protocol of both product families: slab_place decides where the partial slabs of one dW go (the pool of an
+// active `defer`, flushed first when it is full or dW accumulates; else `slabs`), slab_combine records or launches their fixed-order sum
+struct SlabSet {
+  float* base; float* bias;      // [nslab][stride] product slabs, [nslab][out] bias slabs behind them
+  long stride; size_t bytes;     // out * in; bytes of both slab sets
+  int nslab, out;
+  bool can4;                     // 16-byte combine (a recorded SlabJob or slab_reduce4_kernel)
+  SlabDefer* defer;              // where the combine is recorded, or null: launched by slab_combine
+};
 int slab_defer_flush(SlabDefer& d, hipStream_t s);
+int slab_place(SlabDefer* defer, Scratch& slabs, int nslab, int out, int in, const float* dW, bool accumulate, hipStream_t s, SlabSet* set);
+int slab_combine(const SlabSet& set, float* dW, float* db, bool accumulate, hipStream_t s);
 int linear_backward_weight(const float* dZ, int lddz, const float* X, int ldx, long rows, int out, int in,
-                           float* dW, float* db, bool accumulate, Scratch& slabs, Scratch& colp, hipStream_t s,
+                           float* dW, float* db, bool accumulate, Scratch& slabs, Scratch& colp, int prec, hipStream_t s,
                            SlabDefer* defer = nullptr, const gt::GemmArgs* ride_along = nullptr, bool* rode = nullptr);
-
 int linear_backward_weight_split(const float* dZ, int lddz, long rows, long wrap, const float* xp, int ldxp, int cd,
                                  const float* adv, int ld_adv, int Da, int out, float* dW, float* db, bool accumulate,
-                                 Scratch& slabs, hipStream_t s, SlabDefer* defer, const GemmArgs* rider = nullptr, bool* rode = nullptr);
+                                 Scratch& slabs, int prec, hipStream_t s, SlabDefer* defer, const GemmArgs* rider = nullptr, bool* rode = nullptr);
 
 // ------------------------------------------------------------------------------------------
 // eng_gemm_b16.hip

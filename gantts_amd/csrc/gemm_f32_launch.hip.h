@@ -66,12 +66,12 @@ static int launch_gemm_t(const GemmArgs& g, int nslab, hipStream_t s) {
   return launch_gemm_impl<KIND, BM, BN, VA, VB, PREC, GEMM_A_RUNTIME>(g, nslab, s);
 }
 template <int KIND, int BM, int BN>
-static int launch_gemm_v(const GemmArgs& g_in, int nslab, hipStream_t s) {
+static int launch_gemm_v(const GemmArgs& g_in, int nslab, int prec, hipStream_t s) {
   GemmArgs g = g_in;
   g.wide_store = gemm_wide_store_ok(KIND, g) ? 1 : 0;
   const bool va = gemm_vec_ok(g.A, g.lda, KIND != GEMM_TN);
   const bool vb = gemm_vec_ok(g.B, g.ldb, KIND == GEMM_NT);
-  if (tl_gemm_prec == PREC_BF16) {
+  if (prec == PREC_BF16) {
     if (va && vb) return launch_gemm_t<KIND, BM, BN, true, true, PREC_BF16>(g, nslab, s);
     if (va) return launch_gemm_t<KIND, BM, BN, true, false, PREC_BF16>(g, nslab, s);
     if (vb) return launch_gemm_t<KIND, BM, BN, false, true, PREC_BF16>(g, nslab, s);

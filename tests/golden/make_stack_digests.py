@@ -1,7 +1,9 @@
 """Digests of two G + D steps and one plain forward per role through every stack (MLP, LSTM, SRU) in both storage forms, case by case:
 what tests/test_gpu_stack_digests.py demands bit for bit.
 
-    python tests/golden/make_stack_digests.py [out.json]        (needs the GPU; default: stack_step_digests.json beside this file)
+    python tests/golden/make_stack_digests.py [out.json [case ...]]      (needs the GPU; default: stack_step_digests.json beside this file)
+
+Without case names every case is recorded; with names only those are, into the entries out.json already holds (the others stay as they are).
 
 Every case runs hip_runner.run_hip_case's loop (apply_generator -> update_discriminator -> update_generator, `steps` = 2: the second
 step goes through re-made shadows, accumulated-gradient flags and warm optimizer state) from seeded state and records the SHA-256 of
@@ -15,7 +17,9 @@ The loop is run_hip_case's with one difference: a discriminator's injected masks
 (an SRURNN discriminator has more sites per pass than cases.hidden_sites counts), as tests/test_gpu_sru_d_bf16.py does.
 
 The recorded file is the behaviour of the commit named in it -- the one before the output layer and the bf16 product helpers became one
-function each; it is re-recorded only by a change that means to change a bit or a launch of the step."""
+function each; it is re-recorded only by a change that means to change a bit or a launch of the step.  A case added later carries its own
+"recorded_on" (CASE_RECORDED_ON): the three precision routes of the float32 family were recorded on the commit before its product precision
+became an argument."""
 import copy
 import ctypes
 import hashlib
@@ -29,6 +33,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 DEFAULT_OUT = os.path.join(HERE, "stack_step_digests.json")
 RECORDED_ON = "f6c54f8"
+CASE_RECORDED_ON = {"mlp_mixed_bf16": "3a0194b", "lstm_d_p16": "3a0194b", "chain_d_fused_f32": "3a0194b"}      # cases added after RECORDED_ON
 BF16, D16 = {"matmul_bf16": 1}, {"sru_d_bf16": 1}
 STEPS = 2
 COUNTERS = ("gemm", "gemm_b16", "sru", "head", "lstm")
@@ -64,12 +69,18 @@ def case_table():
         "sru_pair_f32": (PAIR, {}),                                # SRU G and SRU D, H = 64, T = 16: the folded scans write the output layer's images
         "sru_pair_d16": (PAIR, D16),
         "sru_pair_both": (PAIR, dict(BF16, **D16)),
+        # the float32 family's precision routes: G on float32 storage with bf16 products (12 is no multiple of 8; pair launches) beside D on
+        # bf16 storage; both recurrent stacks (12, 20) on float32 storage at bf16 precision; the conditioned split first layer, its weight
+        # gradient with the rider and the fused stack
+        "mlp_mixed_bf16": (_with_hidden(K["acoustic_mlp_dropout"], 12), BF16),
+        "lstm_d_p16": (O["acoustic_lstm_d_dropout"], BF16),
+        "chain_d_fused_f32": (K["acoustic_chain_d"], {"fused_dstack": 2}),
     }
 
 
 CASES = ("mlp_f32", "mlp_bf16", "mlp_sigmoid_f32", "mlp_sigmoid_bf16", "duration_bf16", "lstm_f32", "lstm_bf16", "lstm_sigmoid_bf16",
          "lstm_d_f32", "i2o_rnn_f32", "i2o_rnn_bf16", "sru_f32", "sru_k3_f32", "sru_bf16_nofold", "sru_pair_f32", "sru_pair_d16",
-         "sru_pair_both")
+         "sru_pair_both", "mlp_mixed_bf16", "lstm_d_p16", "chain_d_fused_f32")
 
 
 def _read_counts(eng, reset):
@@ -164,6 +175,8 @@ def run_case(name):
         rec[part] = h.hexdigest()
     rec["all"] = whole.hexdigest()
     rec["counts"] = {k: {str(i): int(v) for i, v in enumerate(counts[k]) if v} for k in COUNTERS}
+    if name in CASE_RECORDED_ON:
+        rec["recorded_on"] = CASE_RECORDED_ON[name]
     return rec
 
 
@@ -173,10 +186,15 @@ def check_family(name, rec):
     b16 ={int(k): v for k, v in rec["counts"]["gemm_b16"].items()}
     sru = {int(k): v for k, v in rec["counts"]["sru"].items()}
     products = sum(v for k, v in b16.items() if k < 60)      # (slots below the cast kernels': b16_path_slot)
-    if name.endswith("_f32"):
+    if name.endswith("_f32") or name == "lstm_d_p16":
         assert not b16, "%s: launches of the bf16 family %s" % (name, b16)
     else:
         assert products > 0, "%s: no bf16 product launch" % name
+    if name in ("lstm_d_p16", "mlp_mixed_bf16"):      # bf16 products on float32 storage: gemm_path_slot's precision bit, the bf16 pair launch
+        p16 = [k for k in map(int, rec["counts"]["gemm"]) if (k < 576 and (k // 6) % 2) or k == 579]
+        assert p16, "%s: no float32-family launch at bf16 precision %s" % (name, rec["counts"]["gemm"])
+    if name == "chain_d_fused_f32":      # split weight gradient with its rider (GEMM_PATH_TN_PAIR + 1), fused stack (HEAD_PATH_DSTACK128 / 256)
+        assert ("580" in rec["counts"]["gemm"] or "581" in rec["counts"]["gemm"]) and ("11" in rec["counts"]["head"] or "12" in rec["counts"]["head"]), rec["counts"]
     if name in ("sru_pair_d16", "sru_pair_both"):
         # folded: every scan with a product behind it writes that product's images itself -- each generator layer (the top one writes the
         # output layer's, so no cast of its input is launched), each discriminator layer but the top one (the head reads float32)
@@ -190,17 +208,21 @@ def main(argv):
     for p in (ROOT, os.path.join(ROOT, "tests"), HERE):
         if p not in sys.path:
             sys.path.insert(0, p)
+    out = argv[1] if len(argv) > 1 else DEFAULT_OUT
+    names = argv[2:] or CASES
     record = {"recorded_on": RECORDED_ON, "steps": STEPS, "cases": {}}
-    for name in CASES:
+    if argv[2:]:
+        with open(out) as f:
+            record = json.load(f)
+    for name in names:
         record["cases"][name] = run_case(name)
         print("%-18s %s" % (name, json.dumps(record["cases"][name]["counts"], sort_keys=True)), flush=True)
-    for name in CASES:
+    for name in names:
         check_family(name, record["cases"][name])
-    out = argv[1] if len(argv) > 1 else DEFAULT_OUT
     with open(out, "w") as f:
         json.dump(record, f, indent=1, sort_keys=True)
         f.write("\n")
-    print("wrote %s: %d cases" % (out, len(CASES)))
+    print("wrote %s: %d cases recorded, %d held" % (out, len(names), len(record["cases"])))
 
 
 if __name__ == "__main__":
