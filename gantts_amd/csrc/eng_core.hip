@@ -329,6 +329,8 @@ extern "C" int gt_set_seed(gt_engine* e, uint64_t seed) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   e->seed = seed;
   e->step_counter = 0;
+  // the step count is part of the per-step copies' key and has just gone back: none of them is this step's any more
+  e->dx_pitched.forget(); e->gx_pitched.forget(); e->cx_dense.forget();
   return GT_OK;
 }
 extern "C" int gt_set_dropout_mask(gt_engine* e, int role, int pass, int layer, const float* mask) {

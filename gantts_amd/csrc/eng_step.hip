@@ -43,7 +43,9 @@ struct FirstSplit {
 };
 // M's copy of p [rows][cols] (row pitch ld) with row pitch ldo, dense or with a 16-byte pitch: made unless M holds it already, i.e. once per step.
 // (the key: source pointer, pitch, columns, rows, step -- ADVICE r5: the pointer and the step alone served a too small copy to a caller that
-//  changed B*T between two update_* calls of one step.  The CONTENTS of p are not part of it: a tensor refilled in place within a step is not seen.)
+//  changed B*T between two update_* calls of one step.  The CONTENTS of p are not part of it: a tensor refilled in place within a step is not seen.
+//  A copy never outlives its batch: gt_apply_generator and gt_set_seed forget all three -- the step count goes back under gt_set_seed, and the next
+//  batch from a staging buffer refilled in place then had the key of the one before.)
 static int step_copy(gt_engine* e, StepCopy& M, const float* p, int ld, int cols, long rows, int ldo, bool dense, const float** out, hipStream_t s) {
   if (!M.holds(p, ld, cols, rows, e->step_counter)) {
     CHK(M.buf.ensure((size_t)rows * ldo * sizeof(float)));
@@ -406,7 +408,10 @@ extern "C" int gt_apply_generator(gt_engine* e, const float* x, const float* R, 
   e->step_counter++;
   e->B = B; e->T = T; e->N = (long)B * T;
   e->g_pass_valid = false;
-  invalidate_d_images(e); e->cx_dense.forget();
+  invalidate_d_images(e);
+  // no StepCopy outlives a batch: the step count alone does not tell two batches apart (gt_set_seed restarts it, and a staging buffer
+  // refilled in place has the same pointer, pitch and shape).  Both update calls of a batch come behind this one: they still share a copy.
+  e->dx_pitched.forget(); e->gx_pitched.forget(); e->cx_dense.forget();
   e->tv.forget(); e->tv_inflight = false;             // a new batch: the mask contents may have changed
   CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->ws[GT_ROLE_G].specs));
   e->last_x = e->gx_dense_on ? e->gx_dense.as<float>() : x;      // (what the backward pass reads: the dense copy when one was made)

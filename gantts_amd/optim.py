@@ -194,6 +194,12 @@ class _FlatOptimizer(object):
                     raise ValueError("per-parameter %s differ; not a checkpoint of this optimizer" % " / ".join(self.SCALAR_KEYS))
                 self._scalars = (list(scalars.pop()) + [0.0])[:2]
             self._live0 = len(keys) > 0
+        else:
+            # torch replaces the state by the loaded one: an optimizer that has stepped goes back to "no state yet" -- step 0, and
+            # buffers that _ensure_state() makes anew at the next bind, as after construction
+            self._state = [None, None, None]
+            self._step = 0
+            self._scalars = self._initial_scalars()
         self._step0 = self._step
         self._version += 1
 

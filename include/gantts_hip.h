@@ -201,6 +201,9 @@ int gt_get_optimizer_step(gt_engine* e, int role, int64_t* step);
 /* The host scalar state of the bound optimizer after the updates taken so far (what optimizer.state_dict() holds beside
  * "step"): NADAM out[0] = mu_product; ASGD out[0] = eta, out[1] = mu; 0 for every other kind. */
 int gt_get_optimizer_scalars(gt_engine* e, int role, double out[2]);
+/* The seed of the Philox dropout streams.  RESTARTS THE STEP COUNT (the streams are keyed by seed, step count and site: the step
+ * behind gt_set_seed is step 1 again) and forgets the engine-made per-step copies of x, whose key holds the step count.  From here
+ * on the engine computes what a new engine with this seed computes, bit for bit. */
 int gt_set_seed(gt_engine* e, uint64_t seed);
 /* Parity hook: use the caller's 0/1 float mask ((rows, hidden) contiguous, device) instead of the
  * Philox stream for dropout site `layer` of forward pass `pass` of `role`; NULL restores Philox.
@@ -348,7 +351,12 @@ int gt_set_tuning(const char* name, int value);
  * 16-byte aligned tensor lets every product read the caller's rows with 16-byte loads -- a batch pipeline that stages batches
  * anyway (gantts_amd.data.DevicePrefetcher(pitch_x=True)) provides it for free; with dense 425-wide rows the engine makes the
  * 16-byte-pitch copy its weight-gradient products need itself, once per step.  Supported where it pays: float32 MLP generators
- * and the conditioned float32 discriminator; other paths reject a non-dense pitch. */
+ * and the conditioned float32 discriminator; other paths reject a non-dense pitch.
+ * The engine-made copies are remembered by (pointer, pitch, columns, rows, step count), not by contents, and last one batch:
+ * gt_apply_generator and gt_set_seed forget them, so a staging buffer refilled in place between steps is read anew.  The single
+ * exception to "a step's result depends on the values of its inputs, not on what the engine did before"  is an x
+ * refilled in place BETWEEN THE TWO UPDATE CALLS OF ONE STEP (behind one gt_apply_generator): the second call may read the copy
+ * the first one made. */
 int gt_set_x_pitch(gt_engine* e, int ld_generator_input, int ld_condition);
 /* The persistent recurrence kernels bound every inter-workgroup wait by a wall-clock timeout and raise a device fault
  * word instead of hanging.  The step functions report a fault they have seen (GT_ERR_HIP) at their next entry;

@@ -1,0 +1,139 @@
+"""CPU: the comparator, the shape table and the tables' own shape of tests/engine_history.py (the GPU side: tests/test_gpu_engine_history.py)."""
+import numpy as np
+import pytest
+
+import engine_history as H
+
+
+# ---------------------------------------------------------------------------------------------
+# the comparator
+# ---------------------------------------------------------------------------------------------
+def test_comparator_passes_equal_finite_arrays():
+    a = np.linspace(-3, 3, 24, dtype=np.float32).reshape(2, 3, 4)
+    assert H.difference("a", a, a.copy()) is None
+    assert H.differences({"a": a, "n": np.array([3, 4], dtype=np.int64)}, {"a": a.copy(), "n": np.array([3, 4], dtype=np.int64)}) == []
+
+
+def test_comparator_reports_one_ulp():
+    a = np.linspace(0.5, 3, 24, dtype=np.float32).reshape(4, 6)
+    for toward in (np.float32(np.inf), np.float32(-np.inf)):
+        b = a.copy()
+        b[2, 5] = np.nextafter(b[2, 5], toward)
+        assert np.allclose(a, b, rtol=2e-7, atol=0)        # (what a tolerance would let through)
+        d = H.difference("a", a, b)
+        assert d is not None and "1 of 24" in d and "(2, 5)" in d, d
+
+
+def test_comparator_reports_the_sign_of_zero():
+    a, b = np.zeros(5, dtype=np.float32), np.zeros(5, dtype=np.float32)
+    b[3] = -0.0
+    assert np.array_equal(a, b)
+    d = H.difference("z", a, b)
+    assert d is not None and "(3,)" in d, d
+    assert H.difference("z", b, a) is not None
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+def test_comparator_rejects_non_finite_on_either_side(bad):
+    a = np.ones(6, dtype=np.float32)
+    b = a.copy()
+    b[1] = bad
+    assert "twin" in H.difference("v", a, b)
+    assert "worn" in H.difference("v", b, a)
+    assert "non-finite" in H.difference("v", b, b.copy())       # the same NaN bits on both sides are still refused
+    assert "non-finite" in H.difference("s", np.float32(bad), np.float32(bad))
+
+
+def test_comparator_takes_zero_dimensional_records():
+    """an optimizer's "step" entry is a 0-dim tensor"""
+    assert H.difference("s", np.array(3.0, dtype=np.float32), np.array(3.0, dtype=np.float32)) is None
+    d = H.difference("s", np.array(3.0, dtype=np.float32), np.array(2.0, dtype=np.float32))
+    assert d is not None and "1 of 1" in d, d
+
+
+def test_comparator_reports_shape_dtype_and_missing_records():
+    a = np.ones((2, 3), dtype=np.float32)
+    assert H.difference("a", a, a.reshape(3, 2)) is not None
+    assert H.difference("a", a, a.astype(np.float64)) is not None
+    assert len(H.differences({"a": a}, {"b": a})) == 2
+    assert H.difference("n", np.array([1, 2]), np.array([1, 3])) is not None
+
+
+# ---------------------------------------------------------------------------------------------
+# the shape table: what each shape is claimed to wear
+# ---------------------------------------------------------------------------------------------
+def test_shape_table_properties():
+    p, big, wide = H.shape_facts("probe"), H.shape_facts("BIG"), H.shape_facts("WIDE")
+    assert (p["B"], p["T"]) == (3, 19) and p["N"] == 57 and p["n_mod16"] == 9 and p["pad8_n"] == 64
+    assert p["panels"] == 2 and p["last_panel_rows"] == 25
+    assert big["N"] == 280 and big["n_mod16"] == 8 and big["panels"] == 9 and big["last_panel_rows"] == 24
+    assert big["pad8_t"] != p["pad8_t"]
+    assert wide["batch_tiles32"] == 2 and wide["B"] % 32 == 1 and wide["len_ring_grows"] and not p["len_ring_grows"] and not big["len_ring_grows"]
+    assert H.SHAPES["TINY_A"] == (1, 2) and H.SHAPES["TINY_B"] == (2, 1)
+
+
+def test_every_padding_boundary_of_a_wear_shape_differs_from_the_probes():
+    p = H.shape_facts("probe")
+    for name in ("BIG", "WIDE", "TINY_A", "TINY_B"):
+        f = H.shape_facts(name)
+        for key in ("N", "n_mod16", "pad8_n", "panels", "last_panel_rows", "B", "T"):
+            assert f[key] != p[key], (name, key, f[key])
+    assert H.shape_facts("BIG")["N"] > p["N"] > H.shape_facts("TINY_A")["N"]       # shrink shrinks, grow grows
+    assert H.shape_facts("WIDE")["N"] > p["N"]
+    assert len(set(H.ABANDONED_T)) == 5 and H.FORWARD_SHAPE not in H.SHAPES.values()
+
+
+# ---------------------------------------------------------------------------------------------
+# the tables' own shape
+# ---------------------------------------------------------------------------------------------
+EXPECTED_BACKENDS = ["mlp_philox", "mlp_cond_split", "mlp_cond_cat", "mlp_cond_fused", "mlp_bf16", "mlp_adam_noR", "lstm_g", "lstm_steps",
+                     "lstm_bf16", "lstm_d", "gru_g", "sru_g", "sru_bf16", "sru_d", "sru_d_bf16", "in2out", "in2out_rnn"]
+
+
+def test_every_backend_names_an_existing_case():
+    assert sorted(H.BACKENDS) == sorted(EXPECTED_BACKENDS)
+    for name, b in H.BACKENDS.items():
+        case = H.backend_case(name)
+        assert case["update_d"] and case["update_g"] and case["adv_w"] > 0, name
+        for opt, v in b["options"].items():
+            assert v in H.OPTION_VALUES[opt], (name, opt, v)
+    assert H.backend_case("mlp_adam_noR")["windows"] == 1 and H.backend_case("mlp_adam_noR")["opt_g"][0] == "Adam"
+    assert H.backend_case("mlp_cond_split")["din"] % 4 != 0        # dense rows of x are not 16-byte pitched: the per-step copies are made
+    for name in ("mlp_philox", "mlp_cond_split", "mlp_cond_cat", "mlp_cond_fused", "sru_g"):
+        assert H.backend_case(name)["dropout_on"], name              # Philox on, nothing injected
+
+
+def test_every_option_flip_names_an_option_with_two_values():
+    from gantts_amd.engine import StepEngine
+    import inspect
+    known = inspect.getsource(StepEngine.set_option)
+    for name, b in H.BACKENDS.items():
+        opt, home, away = b["flip"]
+        assert '"%s"' % opt in known, (name, opt)
+        assert home != away and home in H.OPTION_VALUES[opt] and away in H.OPTION_VALUES[opt], (name, b["flip"])
+        assert b["options"].get(opt, home) == home, (name, "the flip's home value is the one the backend runs with")
+        if b["options"]:
+            assert opt in b["options"], (name, "a backend with an option of its own flips that one")
+
+
+def test_every_pair_of_the_tables_is_present_once():
+    assert len(H.PAIRS) == len(set(H.PAIRS)) == 17 * 7 + 3 * 5
+    assert set(h for _, h in H.PAIRS) == set(H.HISTORIES) == set(H.HISTORIES_ALL) | set(H.HISTORIES_FEW)
+    for b in H.BACKENDS:
+        assert [h for bb, h in H.PAIRS if bb == b][:7] == list(H.HISTORIES_ALL)
+    assert set(b for b, h in H.PAIRS if h in H.HISTORIES_FEW) == set(H.BACKENDS_FEW)
+    probe = H.SHAPES["probe"]
+    for name, (shapes, wear) in H.HISTORIES.items():
+        assert probe in shapes and callable(wear), name
+    for b in H.BACKENDS_FEW:        # other_d: another kind, the same in_dim
+        assert H.OTHER_D[H.backend_case(b)["d"]["kind"]]["kind"] != H.backend_case(b)["d"]["kind"]
+
+
+def test_batches_are_cached_per_shape_and_poison_covers_the_valid_frames():
+    a, b = H.shape_batch("mlp_cond_split", "BIG", 1), H.shape_batch("mlp_cond_split", "BIG", 1)
+    assert a is b and not a["x"].flags.writeable
+    p = H.shape_batch("mlp_cond_split", "BIG", 1, poison=True)
+    valid = np.arange(p["T"])[None, :] < p["lengths"][:, None]
+    assert np.isnan(p["x"][valid]).all() and np.isnan(p["y"][valid]).all()
+    assert np.isfinite(p["x"][~valid]).all() and (~valid).any() and int(p["lengths"].max()) == p["T"]
+    assert not np.array_equal(H.shape_batch("mlp_cond_split", "probe", 1)["x"], H.shape_batch("mlp_cond_split", "probe", 2)["x"])

@@ -76,6 +76,26 @@ def test_state_dict_round_trip_with_torch(name, tname, kw, keys):
         o.step()
 
 
+@pytest.mark.parametrize("name,tname,kw,keys", [c for c in CASES if c[3]], ids=[i for i, c in zip(IDS, CASES) if c[3]])
+def test_loading_a_checkpoint_without_state_empties_a_populated_optimizer(name, tname, kw, keys):
+    """torch's load_state_dict REPLACES the state: a checkpoint written before the first step, loaded into an optimizer that has stepped
+    (resume into live objects), leaves no state and step 0 -- not the old moments under the old step count."""
+    from gantts_amd import optim
+    m = _mlp()
+    empty = getattr(optim, name)(m.parameters(), **kw).state_dict()
+    assert empty["state"] == {}
+    _, t = _torch_after_one_step(tname, kw)
+    o = getattr(optim, name)(m.parameters())
+    o.load_state_dict(t.state_dict())
+    assert o.state_dict()["state"] != {} and o._version > 0
+    version = o._version
+    o.load_state_dict(empty)
+    assert o.state_dict()["state"] == {} and o._step == 0 and o._step0 == 0 and not o._live()
+    assert all(s is None for s in o._state) and o._version > version        # buffers are made anew (zeros) at the next bind, engines re-bind
+    t.load_state_dict(empty)
+    assert t.state_dict()["state"] == {}                                     # (torch does the same)
+
+
 @pytest.mark.parametrize("name", ["SGD", "RMSprop", "Adadelta", "AdamW", "Adamax", "Adam", "Adagrad"])
 def test_constructor_defaults_match_torch(name):
     from gantts_amd import optim
