@@ -1024,8 +1024,18 @@ static __global__ void dropout_apply_kernel(const float* __restrict__ in, float*
 enum DistRole { DIST_MCD = 0, DIST_BAP = 1, DIST_LF0 = 2, DIST_VUV = 3, DIST_MSE = 4 };
 constexpr int DIST_NSUM = 7;   // s_mcd, s_bap, s_f0, n_voiced, n_vuv_err, s_mse, n_frames
 
-__device__ __forceinline__ float inv_scale_rn(float x, float s, float m) { return __fadd_rn(__fmul_rn(x, s), m); }
-__device__ __forceinline__ double inv_scale_rn(double x, double s, double m) { return __dadd_rn(__dmul_rn(x, s), m); }
+// The HIP headers define __fmul_rn / __fadd_rn (and the double forms) as a plain `*` and `+`, which hipcc's default -ffp-contract=fast
+// fuses into one fma after inlining: the two roundings are pinned with the pragma instead (tests/test_gpu_distortion_sums.py: threshold*).
+__device__ __forceinline__ float inv_scale_rn(float x, float s, float m) {
+#pragma clang fp contract(off)
+  const float p = x * s;
+  return p + m;
+}
+__device__ __forceinline__ double inv_scale_rn(double x, double s, double m) {
+#pragma clang fp contract(off)
+  const double p = x * s;
+  return p + m;
+}
 __device__ __forceinline__ float dist_exp(float v) { return expf(v); }
 __device__ __forceinline__ double dist_exp(double v) { return exp(v); }
 
