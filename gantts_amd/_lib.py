@@ -23,6 +23,11 @@ OPT_COMM_D_ONE_MSG, OPT_COMM_EARLY_G, OPT_COMM_FORCE = 10, 11, 13      # (7, 8, 
 OPT_LAUNCH_RIDERS, OPT_COMM_CLOSE_INLINE, OPT_POLL_RESULTS = 14, 15, 16
 OPT_COMM_TV_IN_SUMS, OPT_COMM_IPC, OPT_FUSED_DSTACK = 17, 18, 19
 OPT_SRU_D_BF16 = 20
+OPT_GAN_OBJECTIVE = 21
+# GT_OPT_GAN_OBJECTIVE ids by hp.gan_objective name, and the "correct" threshold of D(x) under each (sigmoid output: 0.5; ls scores z
+# against the labels 0 / 1: 0.5; hinge and wgan: the sign of z)
+GAN_OBJECTIVES = {"bce": 0, "ls": 1, "hinge": 2, "wgan": 3}
+GAN_OBJECTIVE_THRESHOLD = {"bce": 0.5, "ls": 0.5, "hinge": 0.0, "wgan": 0.0}
 IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts
@@ -142,7 +147,7 @@ class DropSite(C.Structure):
 
 class DHeadCase(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("mode", "K", "ldh", "h_ld", "has_act", "want_grad", "want_w", "defer_scalars", "accumulate", "unit_tv",
-                                          "has_tv", "lddh", "lddhb", "pad_")]
+                                          "has_tv", "lddh", "lddhb", "objective")]
                 + [("eps", C.c_float), ("tv", C.c_float)]
                 + [(n, C.c_int64) for n in ("rows", "n_real", "n_mask", "lddhbt")]
                 + [("drop", DropSite)]
@@ -152,7 +157,7 @@ class DHeadCase(C.Structure):
 
 class DStackCase(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("mode", "L", "hidden_dim", "want_grad", "accumulate", "unit_tv", "has_tv", "ldw0", "col0", "Da",
-                                          "ld_gadv", "pad_")]
+                                          "ld_gadv", "objective")]
                 + [("eps", C.c_float), ("tv", C.c_float)]
                 + [(n, C.c_int64) for n in ("rows", "n_real", "n_mask")]
                 + [("drop", DropSite * 4), ("H0", C.c_void_p), ("W", C.c_void_p * 4), ("b", C.c_void_p * 4)]
@@ -251,6 +256,7 @@ SIGNATURES = {
     "gt_set_loss_normalizer": (_I, [_P, _F]),
     "gt_set_loss_normalizer_device": (_I, [_P, _P]),
     "gt_set_option": (_I, [_P, _I, _I]),
+    "gt_set_weight_clip": (_I, [_P, _I, _F]),
     "gt_set_x_pitch": (_I, [_P, _I, _I]),
     "gt_set_tuning": (_I, [C.c_char_p, _I]),
     "gt_check_faults": (_I, [_P, _P]),

@@ -86,7 +86,8 @@ __device__ __forceinline__ float dstack_fprime(uint32_t code, float scale) {    
   return code == 0u ? 0.f : (code == 1u ? 0.01f * scale : scale);
 }
 
-template <int HD>
+// OBJ: the adversarial objective of the head (gan_objective.hip.h); 0 is the reference's sigmoid + log loss.
+template <int HD, int OBJ = 0>
 __global__ __launch_bounds__(DS_THREADS, 2) void dstack_kernel(const DStackArgs a) {
   static_assert(HD == 128 || HD == 256, "hidden widths the fused discriminator stack is instantiated for");
   constexpr int NT = HD / 128;                 // 32-column MFMA tiles per wave
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(DS_THREADS, 2) void dstack_kernel(const DStackArgs 
     }
   }
 
-  // ---- head: z = <h, w> + b, D = sigmoid(z), BCE terms, seed dz per row ------------------------------------------------------------
+  // ---- head: z = <h, w> + b, then the objective's D, loss terms and seed dz per row (gan_objective.hip.h; id 0: D = sigmoid(z), BCE) ----
   // The row's dot product is summed exactly as d_head_kernel sums it (lane <-> units lane + 64 j as an fmaf chain, then the xor
   // butterfly over the wave): the two paths then differ by the activations' rounding only.  Wave w takes rows 8 w .. 8 w + 7; lane i
   // of the wave does row 8 w + i's scalar work (all eight exp / log sequences run side by side).
@@ -352,25 +353,16 @@ __global__ __launch_bounds__(DS_THREADS, 2) void dstack_kernel(const DStackArgs 
       const int m = wave * 8 + lane, row = r0 + m;
       const bool valid = row < a.rows;
       const float z = zrow;
-      const float D = 1.f / (1.f + expf(-z));
       const float mk = head_mask;
       const bool is_real = g_mode || row < a.n_real;
+      const GanRow g = gan_objective_row<OBJ>(z, mk, is_real, g_mode, a.eps, inv_tv, valid && want_grad);
       double s_real = 0, s_fake = 0, n_rok = 0, n_fok = 0;
-      float dD;
-      if (is_real) {
-        s_real = (double)(logf(D + a.eps) * mk);
-        if (!g_mode) n_rok = (D > 0.5f ? 1.0 : 0.0) * (double)mk;
-        dD = -mk * inv_tv / (D + a.eps);
-      } else {
-        const float om = (1.f - D) + a.eps;
-        s_fake = (double)(logf(om) * mk);
-        n_fok = (D < 0.5f ? 1.0 : 0.0) * (double)mk;
-        dD = mk * inv_tv / om;
-      }
-      const float dz = (valid && want_grad) ? dD * ((1.f - D) * D) : 0.f;
+      if (is_real) { s_real = (double)g.addend; n_rok = g.n_real_ok; }
+      else { s_fake = (double)g.addend; n_fok = g.n_fake_ok; }
+      const float dz = g.dz;
       if (!valid) { s_real = 0; s_fake = 0; n_rok = 0; n_fok = 0; }
       seeds[m] = dz;
-      if (a.Dout && valid) a.Dout[row] = D;
+      if (a.Dout && valid) a.Dout[row] = g.D;
       red[0 * 32 + m] = s_real; red[1 * 32 + m] = s_fake; red[2 * 32 + m] = n_rok; red[3 * 32 + m] = n_fok; red[4 * 32 + m] = (double)dz;
     }
   }

@@ -187,6 +187,27 @@ static long expected_params(const gt_model_desc& d) {
   return n;
 }
 
+// GT_OPT_GAN_OBJECTIVE against a discriminator's output layer: the sigmoid belongs to objective 0 alone (ls, hinge and wgan score z itself)
+static int gan_objective_fits(int objective, bool last_sigmoid) {
+  if (objective == 0 && !last_sigmoid)
+    return fail(GT_ERR_INVALID, "discriminator must be MLP, LSTMRNN or SRURNN with out_dim=1, last_sigmoid=True (hparams.py:56-64,230-239; train.py:773-774)");
+  if (objective != 0 && last_sigmoid)
+    return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE %d (1 ls, 2 hinge, 3 wgan) scores the output layer's pre-activation: the discriminator must have last_sigmoid=False",
+                objective);
+  return GT_OK;
+}
+int check_gan_objective(const gt_engine* e) {
+  const Net& D = e->net[GT_ROLE_D];
+  return D.bound ? gan_objective_fits(e->gan_objective, D.d.last_sigmoid != 0) : GT_OK;
+}
+extern "C" int gt_set_weight_clip(gt_engine* e, int role, float c) {
+  if (!e) return fail(GT_ERR_INVALID, "null engine");
+  if (role != GT_ROLE_D) return fail(GT_ERR_INVALID, "gt_set_weight_clip: role %d -- weight clipping is the discriminator's (role 1) alone", role);
+  if (!(c >= 0.f) || !(c <= 3.402823466e+38f)) return fail(GT_ERR_INVALID, "gt_set_weight_clip: c = %g -- 0 (off) or a positive finite bound", (double)c);
+  e->weight_clip[role] = c;
+  return GT_OK;
+}
+
 extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) {
   if (!e || !desc || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
   if (desc->arch < GT_ARCH_MLP || desc->arch > GT_ARCH_IN2OUT_RNN)
@@ -197,8 +218,10 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   if (desc->n_params != expected_params(*desc))
     return fail(GT_ERR_INVALID, "n_params %ld does not match the architecture (%ld)", (long)desc->n_params, expected_params(*desc));
   if (desc->arch == GT_ARCH_LSTM && desc->hidden_dim < 1) return fail(GT_ERR_INVALID, "hidden_dim must be positive");
-  if (role == GT_ROLE_D && ((desc->arch != GT_ARCH_MLP && desc->arch != GT_ARCH_LSTM && desc->arch != GT_ARCH_SRU) || desc->out_dim != 1 || !desc->last_sigmoid))
+  if (role == GT_ROLE_D && ((desc->arch != GT_ARCH_MLP && desc->arch != GT_ARCH_LSTM && desc->arch != GT_ARCH_SRU) || desc->out_dim != 1 ||
+                            (e->gan_objective == 0 && !desc->last_sigmoid)))
     return fail(GT_ERR_INVALID, "discriminator must be MLP, LSTMRNN or SRURNN with out_dim=1, last_sigmoid=True (hparams.py:56-64,230-239; train.py:773-774)");
+  if (role == GT_ROLE_D) CHK(gan_objective_fits(e->gan_objective, desc->last_sigmoid != 0));
   if (role == GT_ROLE_D && (desc->arch == GT_ARCH_LSTM || desc->arch == GT_ARCH_SRU) && desc->hidden_dim * (desc->bidirectional ? 2 : 1) > 1024)
     return fail(GT_ERR_INVALID, "recurrent discriminator: hidden_dim x directions > 1024 is not supported by the fused head kernel");
   Net& n = e->net[role];
@@ -372,6 +395,13 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
       if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak_pending = false; e->results.forget_begin(); }
       e->sru_d_bf16 = value != 0;
+      return GT_OK;
+    case GT_OPT_GAN_OBJECTIVE:
+      if (value < 0 || value >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE takes 0 (bce), 1 (ls), 2 (hinge) or 3 (wgan), not %d", value);
+      if (e->net[GT_ROLE_D].bound) CHK(gan_objective_fits(value, e->net[GT_ROLE_D].d.last_sigmoid != 0));
+      // (a discriminator pass begun under one objective is not finished, and its kept gradient not used, under another)
+      if (e->gan_objective != value) { e->leak_pending = false; e->results.forget_begin(); }
+      e->gan_objective = value;
       return GT_OK;
   }
   return fail(GT_ERR_INVALID, "unknown option %d", option);

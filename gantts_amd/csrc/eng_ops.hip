@@ -607,6 +607,7 @@ extern "C" int gt_op_d_head(const gt_d_head_case* c, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "null case");
   if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
     return fail(GT_ERR_INVALID, "head hook: %s", why);
+  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "head hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan)", c->objective);
   if (c->K < 1 || c->K > 1024) return fail(GT_ERR_INVALID, "head hook: K = %d (1 .. 1024)", c->K);
   if (!c->H || !c->w || !c->bias) return fail(GT_ERR_INVALID, "head hook: needs H, w and bias");
   const bool img = c->h_ld > 0;
@@ -634,7 +635,7 @@ extern "C" int gt_op_d_head(const gt_d_head_case* c, void* stream) {
     memset(&h, 0, sizeof(h));
     h.c.mode = c->mode; h.c.rows = (long)c->rows; h.c.n_real = (long)c->n_real; h.c.mask = c->mask; h.c.n_mask = (long)c->n_mask; h.c.eps = c->eps;
     h.c.want_grad = c->want_grad != 0; h.c.want_w = c->want_w != 0; h.c.defer_scalars = c->defer_scalars ? &deferred : nullptr;
-    h.c.tv_dev = c->tv_dev; h.c.unit_tv = c->unit_tv != 0;
+    h.c.tv_dev = c->tv_dev; h.c.unit_tv = c->unit_tv != 0; h.c.objective = c->objective;
     h.o = t.o;
     h.H = c->H; h.K = c->K; h.ldh = c->ldh; h.h_ld = c->h_ld; h.has_act = c->has_act != 0; h.spec = tail_site_spec(c->drop);
     h.w = c->w; h.bias = c->bias; h.Dout = c->Dout; h.dH = c->dH; h.lddh = c->lddh;
@@ -648,6 +649,7 @@ extern "C" int gt_op_dstack(const gt_dstack_case* c, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "null case");
   if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
     return fail(GT_ERR_INVALID, "fused stack hook: %s", why);
+  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "fused stack hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan)", c->objective);
   if (c->L < 1 || c->L > DS_MAXL) return fail(GT_ERR_INVALID, "fused stack hook: L = %d (1 .. %d)", c->L, DS_MAXL);
   if (!dstack_hidden_ok(c->hidden_dim)) return fail(GT_ERR_INVALID, "fused stack hook: hidden_dim 128 or 256");
   const int H = c->hidden_dim;
@@ -676,7 +678,7 @@ extern "C" int gt_op_dstack(const gt_dstack_case* c, void* stream) {
     DStackCall k;
     memset(&k, 0, sizeof(k));
     k.c.mode = c->mode; k.c.rows = (long)c->rows; k.c.n_real = (long)c->n_real; k.c.mask = c->mask; k.c.n_mask = (long)c->n_mask; k.c.eps = c->eps;
-    k.c.want_grad = grad; k.c.want_w = grad && !g_mode; k.c.tv_dev = c->tv_dev; k.c.unit_tv = c->unit_tv != 0;
+    k.c.want_grad = grad; k.c.want_w = grad && !g_mode; k.c.tv_dev = c->tv_dev; k.c.unit_tv = c->unit_tv != 0; k.c.objective = c->objective;
     k.o = t.o; k.hidden_dim = H;
     DStackArgs& a = k.a;
     a.L = c->L; a.H0 = c->H0;
@@ -1130,10 +1132,11 @@ static OptimSpec optim_spec(const gt_optim_desc_ex& od, long step, bool buf_live
 
 int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
                       const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
-                      unsigned int* skipped_host, const float* gscale, hipStream_t s) {
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip) {
   const dim3 grid((unsigned)std::min<long>(1024, cdiv(n, RED_THREADS))), block(RED_THREADS);
   unsigned step_flags = 0u;
-  const OptimSpec o = optim_spec(od, step, buf_live, cache, &step_flags);
+  OptimSpec o = optim_spec(od, step, buf_live, cache, &step_flags);
+  o.wclip = weight_clip;      // gt_set_weight_clip: the updated parameters are clamped to [-c, c] in the same launch (0: stored as computed)
   const OptimVariant* v = optim_variant(od.kind, optim_flags(od, step_flags));
   if (!v) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
   hipLaunchKernelGGL(v->kernel, grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, n_partial, norm2_out, o,

@@ -1,6 +1,7 @@
 // libgantts_hip.so -- the G+D step: MLP stacks, apply_generator / update_discriminator / update_generator (reference train.py:245-355), plain forward
 #include "engine_internal.hip.h"
 #include "d_tail_args.hip.h"
+#include "d_tail_launch.hip.h"
 #include <atomic>
 
 using namespace gt;
@@ -489,35 +490,16 @@ int launch_dstack_pass(const DStackCall& k, hipStream_t s) {
   a.sc = k.o.sc; a.want_grad = c.want_grad ? 1 : 0; a.hp = k.o.hp;
   a.dw_partial = (d_step && c.want_grad) ? k.o.dw_partial : (float*)nullptr;
   if (!d_step && c.want_grad && !a.gadv) return fail(GT_ERR_INVALID, "fused discriminator stack: no gradient buffer");
-  CHK(launch_dstack(a, H, s));
+  CHK(launch_dstack(a, H, s, c.objective));
   return launch_head_finalize(c, k.o, nblk, H, s);
 }
 
-template <int KP, typename TH, bool IMG, bool VEC = false>
-static void head_launch(const HeadArgs& a, int nblk, hipStream_t s) {
-  const HeadCall& c = a.c;
-  hipLaunchKernelGGL((d_head_kernel<KP, TH, IMG, VEC>), dim3(nblk), dim3(256), (size_t)4 * a.K * sizeof(float), s, (const TH*)a.H, IMG ? a.h_ld : a.ldh, a.K,
-                     a.w, a.bias, c.mask, (int)c.n_mask, (int)c.n_real, (int)c.rows, c.mode, c.eps, a.Dout, a.dH, a.lddh,
-                     c.want_grad ? 1 : 0, a.spec, a.has_act ? 1 : 0, a.o.sc, a.o.hp, a.o.dw_partial,
-                     IMG ? a.dHb : (__bf16*)nullptr, IMG ? a.lddhb : 0, IMG ? a.dHbT : (__bf16*)nullptr, IMG ? a.lddhbt : 0L, c.tv_dev, c.unit_tv ? 1 : 0);
-  constexpr int kp = KP == 2 ? 0 : KP == 4 ? 1 : KP == 8 ? 2 : 3;
-  head_path_count(IMG ? HEAD_PATH_IMG + kp : VEC ? HEAD_PATH_VEC + kp - 1 : HEAD_PATH_F32 + kp);
-}
-template <int KP>
-static void head_launch_k(const HeadArgs& a, int nblk, hipStream_t s) {
-  if (a.h_ld > 0) head_launch<KP, __bf16, true>(a, nblk, s);
-  else if (KP % 4 == 0 && gt_tuning().head_vec) head_launch<(KP % 4 == 0 ? KP : 4), float, false, true>(a, nblk, s);
-  else head_launch<KP, float, false>(a, nblk, s);
-}
+// (the launch templates of the head pass: d_tail_launch.hip.h; objective 0 is instantiated here, 1 .. 3 in eng_gan_objective.hip)
 int launch_d_head(const HeadArgs& a, hipStream_t s) {
   const int nblk = d_head_blocks(a.c.rows);
   if (nblk > a.o.hp_cap || (long)nblk * a.K > a.o.dw_cap) return fail(GT_ERR_INVALID, "discriminator head: partial buffers too small for %d workgroups", nblk);
-  if (a.K <= 128) head_launch_k<2>(a, nblk, s);
-  else if (a.K <= 256) head_launch_k<4>(a, nblk, s);
-  else if (a.K <= 512) head_launch_k<8>(a, nblk, s);
-  else if (a.K <= 1024) head_launch_k<16>(a, nblk, s);
-  else return fail(GT_ERR_INVALID, "discriminator hidden_dim > 1024 is not supported by the fused head kernel");
-  LAUNCH_CHECK();
+  if (a.c.objective == GAN_OBJ_BCE) CHK(head_launch_by_k<GAN_OBJ_BCE>(a, nblk, s));
+  else CHK(launch_d_head_objective(a, nblk, s));
   return launch_head_finalize(a.c, a.o, nblk, a.K, s);
 }
 
@@ -660,7 +642,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   }
   n.step += 1;
   CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
-                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s));
+                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s, e->weight_clip[role]));
   n.buf_live = true;
   return GT_OK;
 }
@@ -858,11 +840,13 @@ static int d_pass_forward(gt_engine* e, DPass& p, hipStream_t s) {
 
 // the head on what the stack left, seeding the backward pass where that backend's stack backward reads it (c.want_grad).
 // dst: where the fused launch of the adversarial term writes the generated rows' adversarial-column gradient (it IS that pass's backward).
-static int d_pass_head(gt_engine* e, DPass& p, const HeadCall& c, float* dst, hipStream_t s) {
+static int d_pass_head(gt_engine* e, DPass& p, const HeadCall& c_in, float* dst, hipStream_t s) {
   const int H = p.H;
   NetWs& W = e->ws[GT_ROLE_D];
   CHK(e->dzA.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
   CHK(e->dzB.ensure((size_t)2 * p.N * std::max(H, 1) * sizeof(float)));
+  HeadCall c = c_in;
+  c.objective = e->gan_objective;      // the one place a pass learns the engine's objective: every discriminator kind reaches its head from here
   if (p.fused) return run_dstack(e, c, p.npass == 1 ? dst : nullptr, s);
   HeadAct a;
   memset(&a, 0, sizeof(a));
@@ -921,6 +905,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   Net& D = e->net[GT_ROLE_D];
   if (!D.bound) return fail(GT_ERR_STATE, "discriminator not bound");
   if (!y_static || !y_hat_static || !mask) return fail(GT_ERR_INVALID, "null tensor");
+  CHK(check_gan_objective(e));
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
   const bool tr = train != 0;
@@ -1164,6 +1149,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   Net& D = e->net[GT_ROLE_D];
   if (!G.bound) return fail(GT_ERR_STATE, "generator not bound");
   if (!y || !y_hat || !y_static || !y_hat_static || !mask) return fail(GT_ERR_INVALID, "null tensor");
+  if (adv_w > 0.f) CHK(check_gan_objective(e));
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
   const bool tr = train != 0;

@@ -410,6 +410,8 @@ struct gt_engine {
   int len_cap = 0, len_slot = -1;
   int* d_lengths() { return len_slot < 0 ? nullptr : len_dev[len_slot].as<int>(); }
   bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);      // GT_OPT_SRU_D_BF16: an SRU discriminator's products through the bf16-storage family
+  int gan_objective = 0;                           // GT_OPT_GAN_OBJECTIVE: the head's adversarial objective (gan_objective.hip.h), 0 = the reference's sigmoid + log loss
+  float weight_clip[2] = {0.f, 0.f};               // gt_set_weight_clip (role D only): every optimizer step clamps the updated parameters to [-c, c]; 0 = off
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
@@ -428,7 +430,10 @@ int optim_check_desc(const gt_optim_desc_ex* od);
 void optim_desc_copy(const gt_optim_desc_ex* in, gt_optim_desc_ex* out);      // head only for the first family's kinds
 int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
                       const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
-                      unsigned int* skipped_host, const float* gscale, hipStream_t s);
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip = 0.f);
+// GT_OPT_GAN_OBJECTIVE against the bound discriminator's last_sigmoid (true under objective 0, false under 1 .. 3): checked at whichever of
+// gt_bind_model / gt_set_option comes second and at the entry of every step that runs the discriminator, before any launch
+int check_gan_objective(const gt_engine* e);
 // NAdam's mu_product / ASGD's eta and mu after `t` updates (t >= od.step); `cache` may be null
 void optim_host_scalars(const gt_optim_desc_ex& od, long t, OptimScalarCache* cache, double out[2]);
 gt::DropoutSpec philox_site_spec(gt_engine* e, int role, int pass, int layer, uint64_t step, float p, long half_rows = 0);
@@ -458,7 +463,9 @@ bool gemm_small_tiles_ok();
 namespace gt { struct DStackArgs; }
 bool dstack_hidden_ok(int hidden_dim);
 int dstack_panels(long rows);
-int launch_dstack(const gt::DStackArgs& a, int hidden_dim, hipStream_t s);
+int launch_dstack(const gt::DStackArgs& a, int hidden_dim, hipStream_t s, int objective = 0);
+// eng_gan_objective.hip: the instantiations of both tail kernels for the objectives 1 .. 3 (gan_objective.hip.h), in a unit of their own
+int launch_dstack_objective(const gt::DStackArgs& a, int hidden_dim, int objective, hipStream_t s);
 // gt_head_path_counts: launches of the discriminator's tail by kernel, counted on the host where they are issued (slot layout in
 // gantts_hip.h).  launch_d_head / launch_dstack_pass / launch_head_finalize (eng_step.hip, d_tail_args.hip.h): the one launch site of each
 // kernel, shared by the engine's run_head / run_dstack and the parity hooks (eng_ops.hip).
@@ -469,6 +476,7 @@ void head_path_count(int slot);
 namespace gt { struct HeadCall; struct HeadSums; struct HeadArgs; struct DStackCall; }
 int launch_head_finalize(const gt::HeadCall& c, const gt::HeadSums& o, int nblk, int K, hipStream_t s);
 int launch_d_head(const gt::HeadArgs& a, hipStream_t s);
+int launch_d_head_objective(const gt::HeadArgs& a, int nblk, hipStream_t s);      // (eng_gan_objective.hip) the head pass alone, objectives 1 .. 3
 int launch_dstack_pass(const gt::DStackCall& k, hipStream_t s);
 gt::DropoutSpec no_drop();
 int launch_gemm(int kind, const gt::GemmArgs& g, int prec, hipStream_t s);      // GEMM_NT / GEMM_NN, tiles chosen from the shape

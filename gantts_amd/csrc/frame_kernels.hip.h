@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gemm_f32.hip.h"
+#include "gan_objective.hip.h"
 
 namespace gt {
 
@@ -368,7 +369,8 @@ static __global__ __launch_bounds__(RED_THREADS) void g_losses_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// Discriminator head: last_linear (out_dim 1) + sigmoid + BCE terms + backward seed, fused.
+// Discriminator head: last_linear (out_dim 1) + the adversarial objective (gan_objective.hip.h; below: id 0, sigmoid + BCE terms)
+// + backward seed, fused.
 // rows [0, n_real) are "natural" frames, rows [n_real, n_rows) are generated frames
 // (reference train.py:261-271 for the D step; :307-308 for the adversarial term of the G step
 //  where every row is a generated frame scored against the "natural" label).
@@ -390,7 +392,8 @@ struct HeadPartials {   // one per workgroup; summed in fixed order afterwards
 // VEC (float32 storage, KP % 4 == 0): lane <-> FOUR consecutive hidden units (k = 4 lane + j, + 256 per further group of four): the
 // row and the seed gradient move as 16-byte accesses instead of four 4-byte ones per lane.  Philox bits are keyed by the unit's index,
 // not by the lane that holds it: same masks.
-template <int KP, typename TH = float, bool B16OUT = false, bool VEC = false>
+// OBJ: the adversarial objective (gan_objective.hip.h); 0 is the reference's sigmoid + log loss.
+template <int KP, typename TH = float, bool B16OUT = false, bool VEC = false, int OBJ = 0>
 __global__ __launch_bounds__(256) void d_head_kernel(
     const TH* __restrict__ H, int ldh, int K, const float* __restrict__ w, const float* __restrict__ bias,
     const float* __restrict__ mask, int n_mask, int n_real, int n_rows, int mode, float eps,
@@ -474,24 +477,16 @@ __global__ __launch_bounds__(256) void d_head_kernel(
 #pragma unroll
       for (int j = 0; j < KP; ++j) part = fmaf(hrow[ri][j], wreg[j], part);
       const float z = wave_sum(part) + b0;
-      const float D = 1.f / (1.f + expf(-z));
       const float m = mask[r % n_mask];
       const bool is_real = (mode == HEAD_G_ADV) || (r < n_real);
-      float dD;
-      if (is_real) {
-        const float l = logf(D + eps) * m;
-        if (lane == 0) s_real += (double)l;
-        if (lane == 0 && mode == HEAD_D_STEP) n_rok += (D > 0.5f ? 1.0 : 0.0) * (double)m;
-        dD = -m * inv_tv / (D + eps);
-      } else {
-        const float om = (1.f - D) + eps;
-        const float l = logf(om) * m;
-        if (lane == 0) { s_fake += (double)l; n_fok += (D < 0.5f ? 1.0 : 0.0) * (double)m; }
-        dD = m * inv_tv / om;
+      const GanRow row = gan_objective_row<OBJ>(z, m, is_real, mode == HEAD_G_ADV, eps, inv_tv, want_grad != 0);
+      if (lane == 0) {
+        if (is_real) { s_real += (double)row.addend; n_rok += row.n_real_ok; }
+        else { s_fake += (double)row.addend; n_fok += row.n_fake_ok; }
       }
-      if (lane == 0 && Dout) Dout[r] = D;
+      if (lane == 0 && Dout) Dout[r] = row.D;
       if (want_grad) {
-        const float dz = dD * ((1.f - D) * D);
+        const float dz = row.dz;
         if (lane == 0) dbs += (double)dz;
         float vals[KP];
 #pragma unroll

@@ -47,6 +47,7 @@ struct OptimSpec {
   float lr_decay;      // OPTI_ORIGINAL Adagrad
   float beta1, beta2;  // OPTI_ORIGINAL Adam
   long step;           // OPTI_ORIGINAL: 1-based step count of THIS update
+  float wclip;         // gt_set_weight_clip: > 0 clamps every updated parameter to [-wclip, wclip] behind the rule (param.clamp_ after optimizer.step()); 0: off
 };
 // which of the three state streams a (kind, flags) pair reads and writes
 template <int KIND, unsigned F> struct OptimStreams {
@@ -180,6 +181,38 @@ __device__ __forceinline__ void optim_update(float& p, float& g, float& s0, floa
   }
 }
 
+// the elements of one thread: clip coefficient and step scalars are known.  CLIP: each updated parameter is clamped to [-wclip, wclip]
+// behind the rule and before the store -- two comparisons, so that a NaN parameter stays a NaN, as Tensor.clamp_ leaves it.
+template <int KIND, unsigned F, bool CLIP>
+__device__ __forceinline__ void optim_step_elements(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
+                                                    float* __restrict__ s2, long n, float coef, const OptimSpec& o) {
+  typedef OptimStreams<KIND, F> S;
+  // four grid strides per trip: the loads of four elements are in flight together (a thread of the cfg2 generator's launch walks 3-4)
+  const long gstride = (long)gridDim.x * blockDim.x;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < n; i += 4 * gstride) {      // (the last trip is predicated: no one-element tail)
+    float pv[4], gv[4], av[4], bv[4], cv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long k = i + u * gstride;
+      const bool ok = k < n;
+      pv[u] = ok ? p[k] : 0.f; gv[u] = ok ? g[k] : 0.f;
+      av[u] = (S::s0 && ok) ? s0[k] : 0.f; bv[u] = (S::s1 && ok) ? s1[k] : 0.f; cv[u] = (S::s2 && ok) ? s2[k] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long k = i + u * gstride;
+      if (k >= n) continue;
+      optim_update<KIND, F>(pv[u], gv[u], av[u], bv[u], cv[u], coef, o);
+      if (CLIP) pv[u] = pv[u] < -o.wclip ? -o.wclip : pv[u] > o.wclip ? o.wclip : pv[u];
+      p[k] = pv[u]; g[k] = gv[u];
+      if (S::s0) s0[k] = av[u];
+      if (S::s1) s1[k] = bv[u];
+      if (S::s2) s2[k] = cv[u];
+    }
+  }
+}
+
 template <int KIND, unsigned F>
 static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
     float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1, float* __restrict__ s2, long n,
@@ -187,7 +220,6 @@ static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
     const unsigned int* __restrict__ fault_dev, unsigned int* fault_host /* pinned, or null */,
     unsigned int* skipped_host /* pinned, or null */,
     const float* __restrict__ gscale /* or null: the gradient in g is that of a loss still to be multiplied by *gscale (1 / Tv) */) {
-  typedef OptimStreams<KIND, F> S;
   __shared__ float coef_sh;
   __shared__ double shn[16];
   // A persistent launch of this step that gave up raised the device fault word: its gradients are garbage.  Mirror the
@@ -226,29 +258,10 @@ static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
   __syncthreads();
   const float coef = coef_sh;
   if constexpr ((F & OPTI_ORIGINAL) != 0) optim_original_scalars<KIND>(o);
-  // four grid strides per trip: the loads of four elements are in flight together (a thread of the cfg2 generator's launch walks 3-4)
-  const long gstride = (long)gridDim.x * blockDim.x;
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i < n; i += 4 * gstride) {      // (the last trip is predicated: no one-element tail)
-    float pv[4], gv[4], av[4], bv[4], cv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long k = i + u * gstride;
-      const bool ok = k < n;
-      pv[u] = ok ? p[k] : 0.f; gv[u] = ok ? g[k] : 0.f;
-      av[u] = (S::s0 && ok) ? s0[k] : 0.f; bv[u] = (S::s1 && ok) ? s1[k] : 0.f; cv[u] = (S::s2 && ok) ? s2[k] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long k = i + u * gstride;
-      if (k >= n) continue;
-      optim_update<KIND, F>(pv[u], gv[u], av[u], bv[u], cv[u], coef, o);
-      p[k] = pv[u]; g[k] = gv[u];
-      if (S::s0) s0[k] = av[u];
-      if (S::s1) s1[k] = bv[u];
-      if (S::s2) s2[k] = cv[u];
-    }
-  }
+  // weight clipping (gt_set_weight_clip): ONE uniform test of a spec field per thread, not a row of the (kind, flags) table and not a
+  // test per element.  With the field 0 the elements go through the loop that was always here, compiled from the same statements.
+  if (o.wclip > 0.f) optim_step_elements<KIND, F, true>(p, g, s0, s1, s2, n, coef, o);
+  else optim_step_elements<KIND, F, false>(p, g, s0, s1, s2, n, coef, o);
 }
 
 }  // namespace gt

@@ -37,12 +37,23 @@ def stream_config_from_hp(hp):
     return cfg
 
 
+def gan_objective_of(hp):
+    """``hp.gan_objective`` (opt-in, read with getattr: "bce" -- the reference's sigmoid + log loss, the default --, "ls", "hinge" or
+    "wgan"), checked against the names the engine knows."""
+    name = getattr(hp, "gan_objective", "bce")
+    if name not in L.GAN_OBJECTIVES:
+        raise ValueError("hp.gan_objective = %r: one of %s" % (name, ", ".join(sorted(L.GAN_OBJECTIVES))))
+    return name
+
+
 def _hp_signature(hp):
     adv = getattr(hp, "adversarial_streams", None)
+    # (the adversarial objective and the weight clip are set once per engine: two settings never share one)
     return (tuple(hp.stream_sizes), tuple(bool(b) for b in hp.has_dynamic_features), len(hp.windows),
             None if adv is None else tuple(bool(a) for a in adv),
             int(getattr(hp, "mask_nth_mgc_for_adv_loss", 0)),
-            bool(getattr(hp, "discriminator_linguistic_condition", False)))
+            bool(getattr(hp, "discriminator_linguistic_condition", False)),
+            gan_objective_of(hp), float(getattr(hp, "discriminator_weight_clip", 0.0)))
 
 
 def _same_storage(t, c, name):
@@ -116,6 +127,13 @@ class StepEngine(object):
         self.num_windows = nW
         self._windows_sent = None                # window signature registered through gt_set_mlpg_windows
         self._hp_windows = list(hp.windows)      # what mlpg_var registers when it is given none
+        # hp.gan_objective / hp.discriminator_weight_clip: opt-in switches beyond the reference, sent before any network is bound
+        self.gan_objective = gan_objective_of(hp)
+        if self.gan_objective != "bce":
+            self.set_option("gan_objective", L.GAN_OBJECTIVES[self.gan_objective])
+        clip = float(getattr(hp, "discriminator_weight_clip", 0.0))
+        if clip != 0.0:
+            self.set_weight_clip(L.ROLE_D, clip)
 
     @classmethod
     def for_forward_only(cls, model):
@@ -274,7 +292,10 @@ class StepEngine(object):
         with float32 accumulation (an SRURNN discriminator keeps float32 under it);
         ``"sru_d_bf16"`` (0 / 1, default 0 or ``GT_SRU_D_BF16``; independent of ``"matmul_bf16"``) runs the products of an SRURNN in
         the discriminator slot on bf16 images with float32 accumulation -- ``hidden_dim % 8 == 0`` is needed, any other width
-        silently keeps the float32 path."""
+        silently keeps the float32 path.
+        ``"gan_objective"`` (0 bce, 1 ls, 2 hinge, 3 wgan -- ``_lib.GAN_OBJECTIVES``; default 0, or ``hp.gan_objective`` at creation)
+        selects the adversarial objective of both update steps: same launches, other losses.  The bound discriminator must have
+        ``last_sigmoid=True`` under 0 and ``last_sigmoid=False`` under 1 .. 3."""
         opts = {"lstm_persistent": L.OPT_LSTM_PERSISTENT,
                 "lstm_fwd_units": L.OPT_LSTM_FWD_UNITS, "lstm_xcd_local": L.OPT_LSTM_XCD_LOCAL,
                 "matmul_bf16": L.OPT_MATMUL_BF16, "split_first_layer": L.OPT_SPLIT_FIRST_LAYER,
@@ -282,12 +303,19 @@ class StepEngine(object):
                 "comm_force": L.OPT_COMM_FORCE, "launch_riders": L.OPT_LAUNCH_RIDERS,
                 "comm_close_inline": L.OPT_COMM_CLOSE_INLINE, "poll_results": L.OPT_POLL_RESULTS,
                 "comm_tv_in_sums": L.OPT_COMM_TV_IN_SUMS, "comm_ipc": L.OPT_COMM_IPC, "fused_dstack": L.OPT_FUSED_DSTACK,
-                "sru_d_bf16": L.OPT_SRU_D_BF16}
+                "sru_d_bf16": L.OPT_SRU_D_BF16, "gan_objective": L.OPT_GAN_OBJECTIVE}
         if name not in opts:
             raise ValueError("unknown engine option %r" % (name,))
         check(lib.gt_set_option(self._h, opts[name], int(value)))
         if name == "matmul_bf16":
             self._opt_bf16 = bool(value)
+        if name == "gan_objective":
+            self.gan_objective = [k for k, v in L.GAN_OBJECTIVES.items() if v == int(value)][0]
+
+    def set_weight_clip(self, role, c):
+        """Every later optimizer step of ``role`` (the discriminator's alone) clamps each updated parameter to ``[-c, c]`` inside the
+        fused clip + update launch -- ``p.data.clamp_(-c, c)`` after ``optimizer_d.step()``, the WGAN weight clipping.  ``c = 0``: off."""
+        check(lib.gt_set_weight_clip(self._h, int(role), float(c)))
 
     def set_loss_normalizer(self, tv):
         """``tv``: python number, or a 1-element CUDA float64 tensor (kept alive here; read in stream order --
@@ -601,7 +629,7 @@ class StepEngine(object):
         return n.value
 
     def _adv_width(self):
-        ss, hd, nW, adv, nmask, _ = self.signature
+        ss, hd, nW, adv, nmask = self.signature[:5]
         static = [s // nW if d else s for s, d in zip(ss, hd)]
         if adv is None:
             return sum(static)

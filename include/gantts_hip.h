@@ -338,7 +338,25 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  * hidden_dim % 8 == 0, the generator's rule: any other width silently keeps the float32 path.  LSTMRNN discriminators are not
  * affected.  Results differ from the float32 path at the 1e-2 relative level (tests/test_gpu_sru_d_bf16.py). */
 #define GT_OPT_SRU_D_BF16 20
+/* GT_OPT_GAN_OBJECTIVE (default 0; beyond the reference): the adversarial objective of both update steps.  With z the discriminator's
+ * output pre-activation of a frame, m its mask value and Tv the valid-frame count:
+ *   0 bce    D = sigmoid(z)  real -log(D + eps)   generated, D step -log(1 - D + eps)   generated, G step -log(D + eps)   threshold 0.5
+ *   1 ls     D = z           real 0.5 (z - 1)^2   generated, D step 0.5 z^2             generated, G step 0.5 (z - 1)^2   threshold 0.5
+ *   2 hinge  D = z           real max(0, 1 - z)   generated, D step max(0, 1 + z)       generated, G step -z              threshold 0
+ *   3 wgan   D = z           real -z              generated, D step z                   generated, G step -z              threshold 0
+ * The results keep their meaning: loss_real_d / loss_fake_d / loss_adv = sum(phi m) / Tv of the column, real_correct_count =
+ * sum([D > threshold] m), fake_correct_count = sum([D < threshold] m).  Same launches as objective 0 (the objective is a template
+ * parameter of the two head kernels); `eps` is read by objective 0 alone.  The bound discriminator must have last_sigmoid = 1 under
+ * objective 0 and last_sigmoid = 0 under 1 .. 3: checked at whichever of gt_bind_model and this option comes second, and at the entry of
+ * every step that runs the discriminator, before any launch.  Any other value returns GT_ERR_INVALID.  A change drops pending
+ * split-phase results and the kept dloss_d / dy_hat_static.  hinge and wgan losses can be <= 0. */
+#define GT_OPT_GAN_OBJECTIVE 21
 int gt_set_option(gt_engine* e, int option, int value);
+/* Weight clipping (WGAN): every later optimizer step of `role` clamps each updated parameter to [-c, c] inside the fused clip + update
+ * launch, behind the update rule (what `for p in D.parameters(): p.data.clamp_(-c, c)` does after optimizer_d.step()); a NaN parameter
+ * stays a NaN.  c = 0 switches it off (the default: the stored values are the rule's own); c must be finite and >= 0, and role
+ * GT_ROLE_D -- anything else returns GT_ERR_INVALID.  Independent of GT_OPT_GAN_OBJECTIVE. */
+int gt_set_weight_clip(gt_engine* e, int role, float c);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,
  * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_coop (its former name sru_lw, 0 / 1 / 2, is still accepted: 2 = 1), head_vec, lstm_bt; the environment variables GT_<NAME>
@@ -793,6 +811,8 @@ int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ldy, int B, i
  *   7..10    d_head_kernel<KP, bf16, B16OUT>, the image form:  7 + log2(KP) - 1, KP = 2, 4, 8, 16
  *   11, 12   dstack_kernel<128>, dstack_kernel<256>
  *   13, 14   d_head_finalize_kernel with 64 / with 16 columns per workgroup (the latter with the extra scalar workgroup)
+ * A launch is counted in the slot of its FORM whatever its adversarial objective (GT_OPT_GAN_OBJECTIVE): the objective is a further
+ * template parameter of d_head_kernel and dstack_kernel and changes neither the dispatch nor the number of launches.
  * Copies the GT_HEAD_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
 #define GT_HEAD_PATH_SLOTS 15
 int gt_head_path_counts(int64_t* counts, int reset);
@@ -826,12 +846,14 @@ typedef struct gt_drop_site {
  *            weight gradients are wanted.
  *   scalars  host, 8 doubles or null, filled after the stream is synchronised: s_real, s_fake, n_real_ok, n_fake_ok, s_adv, tv, inv_tv
  *            as the scratch scalars hold them (what no launch wrote stays NaN), and the number of partials (workgroups of the pass).
+ *   objective  GT_OPT_GAN_OBJECTIVE id (0 .. 3): Dout, the sums and the seed gradient are that objective's; same kernel form, same slot of
+ *            gt_head_path_counts
  * The partial buffers are scratch of the call, filled with NaN first.  A malformed case returns GT_ERR_INVALID before any launch. */
 typedef struct gt_d_head_case {
   int32_t mode, K, ldh, h_ld;
   int32_t has_act, want_grad, want_w, defer_scalars;
   int32_t accumulate, unit_tv, has_tv, lddh;
-  int32_t lddhb, pad_;
+  int32_t lddhb, objective;    /* GT_OPT_GAN_OBJECTIVE id of the pass, 0 .. 3 (formerly padding: a zero-initialised case is objective 0) */
   float eps, tv;
   int64_t rows, n_real, n_mask, lddhbt;
   gt_drop_site drop;
@@ -861,7 +883,7 @@ int gt_op_d_head(const gt_d_head_case* c, void* stream);
 typedef struct gt_dstack_case {
   int32_t mode, L, hidden_dim, want_grad;
   int32_t accumulate, unit_tv, has_tv, ldw0;
-  int32_t col0, Da, ld_gadv, pad_;
+  int32_t col0, Da, ld_gadv, objective;      /* as in gt_d_head_case */
   float eps, tv;
   int64_t rows, n_real, n_mask;
   gt_drop_site drop[4];
