@@ -35,6 +35,7 @@ GEMM_PATH_SLOTS = 588                                                   # gt_gem
 GEMM_B16_PATH_SLOTS = 66                                                # gt_gemm_b16_path_counts
 SRU_PATH_SLOTS = 13                                                     # gt_sru_path_counts
 HEAD_PATH_SLOTS = 15                                                    # gt_head_path_counts
+SN_MAX_LAYERS, SN_PATH_SLOTS = 17, 5                                    # GT_SN_MAX_LAYERS; gt_sn_path_counts: W^T u, W v, normalise + W_eff, G (.) W_eff partials, element pass
 (FRAME_MASK_SUM, FRAME_MASK_TOTAL, FRAME_SQERR, FRAME_G_LOSSES, FRAME_STATIC_GRAD, FRAME_FINALIZE_G, FRAME_FINALIZE_G_RIDER, FRAME_FINALIZE_D,
  FRAME_SCALE_INV_TV, FRAME_HIGHWAY_FWD, FRAME_HIGHWAY_BWD, FRAME_SIGMOID_GRAD, FRAME_DROPOUT_APPLY, FRAME_BUILD_ADV, FRAME_BUILD_CAT2, FRAME_REPITCH,
  FRAME_DENSE_COPY, FRAME_PAD_ROWS, FRAME_TRANSPOSE) = range(19)         # FrameCase.op
@@ -209,6 +210,13 @@ class CorpusStatsCase(C.Structure):
                 + [(n, C.c_void_p) for n in ("out_min", "out_max", "out_count", "out_mean", "out_m2")])
 
 
+class SnCase(C.Structure):
+    _fields_ = ([("n_layers", C.c_int32), ("iterate", C.c_int32), ("n_flat", C.c_int64), ("norm_cap", C.c_int64),
+                 ("w_off", C.c_int64 * SN_MAX_LAYERS), ("out", C.c_int32 * SN_MAX_LAYERS), ("in_", C.c_int32 * SN_MAX_LAYERS)]
+                + [(n, C.c_void_p) for n in ("W", "u", "v", "weff", "sigma", "G", "s", "norm_partials")]
+                + [("n_norm_partials", C.POINTER(C.c_int32))])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -257,6 +265,10 @@ SIGNATURES = {
     "gt_set_loss_normalizer_device": (_I, [_P, _P]),
     "gt_set_option": (_I, [_P, _I, _I]),
     "gt_set_weight_clip": (_I, [_P, _I, _F]),
+    "gt_set_spectral_norm": (_I, [_P, _I, _P, _P, _L, _L]),
+    "gt_op_spectral_norm": (_I, [C.POINTER(SnCase), _P]),
+    "gt_op_sn_project": (_I, [C.POINTER(SnCase), _P]),
+    "gt_sn_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_set_x_pitch": (_I, [_P, _I, _I]),
     "gt_set_tuning": (_I, [C.c_char_p, _I]),
     "gt_check_faults": (_I, [_P, _P]),

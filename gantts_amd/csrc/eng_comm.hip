@@ -86,6 +86,7 @@ extern "C" int gt_comm_destroy(gt_engine* e) {
 }
 extern "C" int gt_comm_init(gt_engine* e, int rank, int world, const void* id) {
   if (!e || !id || world < 1 || rank < 0 || rank >= world) return fail(GT_ERR_INVALID, "bad argument");
+  if (e->sn.on) return fail(GT_ERR_INVALID, "gt_comm_init: spectral normalisation (gt_set_spectral_norm) is on; a communicating engine is not supported with it yet");
   RcclApi* api = rccl_api();
   if (!api) return fail(GT_ERR_HIP, "RCCL (librccl.so) could not be loaded");
   CHK(gt_comm_destroy(e));
@@ -111,6 +112,7 @@ extern "C" int gt_comm_init(gt_engine* e, int rank, int world, const void* id) {
 // dropout streams globally, so that every rank draws its own rows of the ONE mask a single process would draw.
 extern "C" int gt_set_shard(gt_engine* e, int rank, int world) {
   if (!e || world < 1 || rank < 0 || rank >= world) return fail(GT_ERR_INVALID, "bad argument");
+  if (e->sn.on && world > 1) return fail(GT_ERR_INVALID, "gt_set_shard: spectral normalisation (gt_set_spectral_norm) is on; a sharded engine is not supported with it yet");
   if (e->comm && (e->comm->rank != rank || e->comm->world != world))
     return fail(GT_ERR_STATE, "gt_set_shard(%d, %d) contradicts the attached communicator (%d, %d)", rank, world, e->comm->rank, e->comm->world);
   e->dp_rank = rank; e->dp_world = world;

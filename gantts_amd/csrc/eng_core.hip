@@ -158,6 +158,8 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   for (int* p : ints) if (p) (void)hipFree(p);
   e->results.destroy();
   e->ledger.release();
+  if (e->sn.plan) sn_plan_free(e->sn.plan);
+  e->sn.weff.release(); e->sn.ws.release();
   delete e;
 }
 
@@ -286,6 +288,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   n.bound = true;
   n.grads_dirty = false;
   W.act.resize(desc->num_hidden);
+  if (role == GT_ROLE_D) CHK(sn_rebind(e));      // gt_set_spectral_norm is on: Lin::W into W_eff again, the registered u and v against the new network
   if (role == GT_ROLE_G && is_i2o(desc->arch)) {
     // single dynamic stream of width out_dim (models.py:66,115)
     const int sd = desc->out_dim / e->cfg.num_windows;

@@ -1184,3 +1184,45 @@ extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, flo
   }
   return GT_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// spectral normalisation (eng_spectral_norm.hip): the hooks build the job table the engine builds at a bind and call its launch functions
+// ------------------------------------------------------------------------------------------
+static int sn_case_plan(const gt_sn_case* c, SnPlan** plan, SnBufs* b) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (c->n_layers < 1 || c->n_layers > GT_SN_MAX_LAYERS) return fail(GT_ERR_INVALID, "spectral norm: n_layers %d (1 .. %d)", c->n_layers, GT_SN_MAX_LAYERS);
+  if (c->n_flat < 1 || !c->u || !c->v || !c->weff || !c->sigma) return fail(GT_ERR_INVALID, "spectral norm: null buffer or empty flat buffer");
+  SnLayerDesc layers[GT_SN_MAX_LAYERS];
+  for (int q = 0; q < c->n_layers; ++q) { layers[q].w_off = (long)c->w_off[q]; layers[q].out = c->out[q]; layers[q].in = c->in[q]; }
+  CHK(sn_plan_build(layers, c->n_layers, (long)c->n_flat, plan));
+  static thread_local Scratch tls_ws;     // the double sums between the launches (grow-only)
+  const int r = tls_ws.ensure(sn_plan_bytes(*plan));
+  if (r != GT_OK) { sn_plan_free(*plan); return r; }
+  *b = sn_plan_bufs(*plan, tls_ws.p);
+  b->sigma = c->sigma;
+  return GT_OK;
+}
+extern "C" int gt_op_spectral_norm(const gt_sn_case* c, void* stream) {
+  SnPlan* plan = nullptr;
+  SnBufs b;
+  CHK(sn_case_plan(c, &plan, &b));
+  int r = c->W ? GT_OK : fail(GT_ERR_INVALID, "spectral norm: W is null");
+  if (r == GT_OK) r = launch_sn_prepare(plan, c->W, c->u, c->v, c->weff, b, c->iterate != 0, (hipStream_t)stream);
+  sn_plan_free(plan);
+  return r;
+}
+extern "C" int gt_op_sn_project(const gt_sn_case* c, void* stream) {
+  SnPlan* plan = nullptr;
+  SnBufs b;
+  CHK(sn_case_plan(c, &plan, &b));
+  int r = GT_OK;
+  if (!c->G || !c->s || !c->norm_partials || !c->n_norm_partials) r = fail(GT_ERR_INVALID, "spectral norm projection: null buffer");
+  else if (c->norm_cap < sn_plan_partials(plan)) r = fail(GT_ERR_INVALID, "spectral norm projection: %d squared-norm partials, room for %ld", sn_plan_partials(plan), (long)c->norm_cap);
+  if (r == GT_OK) {
+    b.s = c->s;
+    *c->n_norm_partials = sn_plan_partials(plan);
+    r = launch_sn_project(plan, c->G, c->weff, c->u, c->v, b, c->norm_partials, (hipStream_t)stream);
+  }
+  sn_plan_free(plan);
+  return r;
+}

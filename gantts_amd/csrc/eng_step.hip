@@ -593,8 +593,14 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   const float* gscale = (role == GT_ROLE_D && e->d_unnorm) ? &e->sc()->inv_tv : (const float*)nullptr;
   if (role == GT_ROLE_D) e->d_unnorm = false;
   SlabDefer& sd = e->ws[role].sdefer;
-  int n_partial = 0;      // squared-norm partials in `part`: none until one of the two routes below has launched them
-  if (sd.active && sd.jobs.n > 0) {
+  int n_partial = 0;      // squared-norm partials in `part`: none until one of the routes below has launched them
+  if (role == GT_ROLE_D && e->sn.on) {
+    // gt_set_spectral_norm: the flat gradient holds d loss / d W_eff.  Combines first, then the projection onto the caller's W, whose element
+    // pass leaves the squared-norm partials of the whole projected gradient: clip-norm and the update see d loss / d W
+    CHK(slab_defer_flush(sd, s));
+    sd.active = false;
+    CHK(sn_project_grads(e, part, &n_partial, s));
+  } else if (sd.active && sd.jobs.n > 0) {
     // The fused step recorded this network's weight-gradient combines.  They write disjoint ranges of the flat gradient; whatever
     // they do not cover (the discriminator's last layer, written by the head's reduction) still counts for the norm and is
     // stepped: `rest`.  Combines + squared norm in ONE launch (slab_reduce_norm_kernel), then clip + step.
@@ -816,6 +822,7 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
 
 // the stack forward; a recurrent stack leaves its output in p.top / p.ld_top (= p.H)
 static int d_pass_forward(gt_engine* e, DPass& p, hipStream_t s) {
+  CHK(sn_prepare_pass(e, s));      // gt_set_spectral_norm: W_eff of this pass, ahead of every reader of Lin::W (refresh_shadows and w0pad included)
   switch (p.kind) {
     case D_SRU:        // (sequence lengths ignored as in the reference)
       CHK(sru_stack_forward(e, GT_ROLE_D, p.img, p.ldc, p.nseq, p.T, p.passes, p.npass, s, &p.top, &p.ld_top, p.sru_d16 ? &p.cat0 : nullptr, p.want_w));
@@ -917,6 +924,8 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   CHK(d_pass_plan(e, x, y_static, y_hat_static, e->Ds, 2, B, T, tr, &p));
   if (comm_on(e) && tr && D.grads_dirty)
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_d.zero_grad() must precede update_discriminator (the gradient buckets are summed over the ranks in place)");
+  if (e->sn.on && tr && D.grads_dirty)
+    return fail(GT_ERR_STATE, "spectral norm: optimizer_d.zero_grad() must precede update_discriminator (the last step's gradient was projected in place)");
   e->ws[GT_ROLE_D].sdefer.reset(rc.early && tr && D.has_opt);
   // data parallel: the global count travels under the D forward pass.  With the split first layer its local term is summed by a
   // rider of the gather launch (tv_ride_dp), else by a launch of its own right here.
@@ -1337,6 +1346,7 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
   const int pass0[1] = {0};
   if (role == GT_ROLE_G) e->g_pass_valid = false;
   const bool b16 = use_b16(e, role);
+  if (role == GT_ROLE_D) CHK(sn_prepare_pass(e, s));
   if (b16) {
     CHK(e->fwd_b.ensure(N, n.d.in_dim, false));
     CHK(cast_transpose(x, n.d.in_dim, N, n.d.in_dim, e->fwd_b.r(), e->fwd_b.ld, (__bf16*)nullptr, 0, nullptr, false, &e->colp, s));

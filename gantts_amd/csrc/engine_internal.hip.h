@@ -14,7 +14,7 @@
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
 // of the two product families; eng_gemm_b16 also holds the stacks' bf16 vocabulary: LinShadow::ensure / shadow_cast, b16_forward / b16_backward_data),
 // eng_step (the G+D step, its ResultsChannel, the MLP stacks and the output layer of every stack: out_layer_forward / out_layer_backward), eng_mlpg
-// (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
+// (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_spectral_norm (spectral normalisation of the MLP discriminator), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
 // (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage
 // (GT_KERNEL) so that several units may include them.
 #pragma once
@@ -313,6 +313,20 @@ struct EpochLedger {
   void release() { rec.release(); len.release(); if (h_out) (void)hipHostFree(h_out); h_out = nullptr; configured = false; }
 };
 
+// Spectral normalisation of the MLP discriminator (eng_spectral_norm.hip, spectral_norm_kernels.hip.h).  SnPlan: the job table of a
+// network (one job per nn.Linear weight), its launch grids and the ranges no job covers, built once per bind.  SnBufs: the double sums
+// between the launches, sized by sn_plan_bytes.  SnState: the engine's -- u, v are the caller's (like optimizer state), W_eff the engine's.
+struct SnLayerDesc { long w_off; int out, in; };
+struct SnPlan;
+struct SnBufs { double *t, *r, *sp, *s; float* sigma; };
+struct SnState {
+  bool on = false;
+  float *u = nullptr, *v = nullptr;                // caller-owned, sum(out) and sum(in) floats
+  SnPlan* plan = nullptr;
+  Scratch weff, ws;                                // W / sigma in the flat buffer's layout (biases unused); SnBufs
+  SnBufs bufs = {nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
 struct gt_engine {
   gt_stream_config cfg;
   Net net[2];
@@ -412,6 +426,7 @@ struct gt_engine {
   bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);      // GT_OPT_SRU_D_BF16: an SRU discriminator's products through the bf16-storage family
   int gan_objective = 0;                           // GT_OPT_GAN_OBJECTIVE: the head's adversarial objective (gan_objective.hip.h), 0 = the reference's sigmoid + log loss
   float weight_clip[2] = {0.f, 0.f};               // gt_set_weight_clip (role D only): every optimizer step clamps the updated parameters to [-c, c]; 0 = off
+  SnState sn;                                      // gt_set_spectral_norm (role D, MLP only): Lin::W of the discriminator then points into sn.weff
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
@@ -574,6 +589,27 @@ struct OutGrad { B16Dst to; int act_prev; gt::DropoutSpec drop; bool ride; };
 int out_layer_forward(gt_engine* e, int role, const OutTop& top, long rows, float* out, hipStream_t s);
 int out_layer_backward(gt_engine* e, int role, const float* gy, int ldgy, long rows, const OutTop& top, const OutGrad& dst, SlabDefer* defer,
                        hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// eng_spectral_norm.hip -- the launch functions below are the one launch site of each kernel, shared by the step and the hooks
+// gt_op_spectral_norm / gt_op_sn_project (eng_ops.hip); gt_sn_path_counts counts them on the host (slot layout in gantts_hip.h)
+// ------------------------------------------------------------------------------------------
+int sn_plan_build(const SnLayerDesc* layers, int n, long n_flat, SnPlan** out);      // checks the table: dims in [1, 512], ranges ascending inside [0, n_flat)
+void sn_plan_free(SnPlan* p);
+long sn_plan_sum_out(const SnPlan* p);
+long sn_plan_sum_in(const SnPlan* p);
+int sn_plan_partials(const SnPlan* p);                   // squared-norm partials launch_sn_project writes
+size_t sn_plan_bytes(const SnPlan* p);                   // of the SnBufs
+SnBufs sn_plan_bufs(const SnPlan* p, void* ws);
+// W_eff (and sigma) from W; iterate: one power iteration, u and v advanced (3 launches); else the eval form from the stored u, v (2 launches)
+int launch_sn_prepare(const SnPlan* p, const float* W, float* u, float* v, float* weff, const SnBufs& b, bool iterate, hipStream_t s);
+// G (d loss / d W_eff, the flat gradient) -> d loss / d W in place (2 launches); norm_part: sn_plan_partials() squared-norm partials of all of G
+int launch_sn_project(const SnPlan* p, float* G, const float* weff, const float* u, const float* v, const SnBufs& b, double* norm_part, hipStream_t s);
+// the engine's: (re)points the discriminator's Lin::W, prepares W_eff at the head of a pass, projects in front of the optimizer step
+void sn_point_weights(gt_engine* e);
+int sn_rebind(gt_engine* e);                              // gt_bind_model(role D) with the feature on: the new network against the registered buffers
+int sn_prepare_pass(gt_engine* e, hipStream_t s);         // no-op when the feature is off
+int sn_project_grads(gt_engine* e, double* norm_part, int* n_partial, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------
 // eng_comm.hip

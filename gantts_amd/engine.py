@@ -53,7 +53,8 @@ def _hp_signature(hp):
             None if adv is None else tuple(bool(a) for a in adv),
             int(getattr(hp, "mask_nth_mgc_for_adv_loss", 0)),
             bool(getattr(hp, "discriminator_linguistic_condition", False)),
-            gan_objective_of(hp), float(getattr(hp, "discriminator_weight_clip", 0.0)))
+            gan_objective_of(hp), float(getattr(hp, "discriminator_weight_clip", 0.0)),
+            bool(getattr(hp, "discriminator_spectral_norm", False)))
 
 
 def _same_storage(t, c, name):
@@ -104,6 +105,7 @@ class _SingleStreamHP(object):
         self.adversarial_streams = None
         self.mask_nth_mgc_for_adv_loss = 0
         self.discriminator_linguistic_condition = False
+        self.discriminator_spectral_norm = False
 
 
 class StepEngine(object):
@@ -134,12 +136,21 @@ class StepEngine(object):
         clip = float(getattr(hp, "discriminator_weight_clip", 0.0))
         if clip != 0.0:
             self.set_weight_clip(L.ROLE_D, clip)
+        # hp.discriminator_spectral_norm: the discriminator bound to this engine is an ``MLP(..., spectral_norm=True)`` (checked at the bind)
+        self.spectral_norm = bool(getattr(hp, "discriminator_spectral_norm", False))
+        self._sn_on = False                      # gt_set_spectral_norm holds buffers right now
 
     @classmethod
     def for_forward_only(cls, model):
         if model.include_parameter_generation():
             return cls(_SingleStreamHP(model.out_dim, model.out_dim // model.static_dim, True))
-        return cls(_SingleStreamHP(model.out_dim))
+        hp = _SingleStreamHP(model.out_dim)
+        if getattr(model, "spectral_norm", False):
+            # a spectrally normalised discriminator's plain forward runs in the discriminator slot (role D owns the normalisation); the
+            # objective only has to fit last_sigmoid for the bind, a forward pass never reads it
+            hp.discriminator_spectral_norm = True
+            hp.gan_objective = "bce" if model.last_sigmoid else "ls"
+        return cls(hp)
 
     # ---- binding --------------------------------------------------------------------------
     def bind_model(self, role, model, with_grads=True):
@@ -147,8 +158,18 @@ class StepEngine(object):
         if ref is not None and ref() is model and ver == model._version and (wg or not with_grads):
             check(lib.gt_set_training(self._h, role, int(model.training)))
             return
+        sn = bool(getattr(model, "spectral_norm", False))
+        if role == L.ROLE_G and sn:
+            raise ValueError("spectral_norm=True is the discriminator's: a spectrally normalised network cannot be bound as the generator")
+        if role == L.ROLE_D and sn != self.spectral_norm:
+            raise ValueError("hp.discriminator_spectral_norm is %s but the discriminator was built with spectral_norm=%s: set both"
+                             % (self.spectral_norm, sn))
+        if role == L.ROLE_D and self._sn_on and (ref is None or ref() is not model):
+            self.set_spectral_norm(L.ROLE_D, None, None)      # another network: checked against ITS buffers below, not against the old ones
         desc = model._desc(with_grads)
         check(lib.gt_bind_model(self._h, role, C.byref(desc)))
+        if role == L.ROLE_D and sn:
+            self.set_spectral_norm(L.ROLE_D, model.sn_u, model.sn_v)
         for (pass_idx, layer), m in model._masks.items():
             check(lib.gt_set_dropout_mask(self._h, role, pass_idx, layer, ptr(m)))
         check(lib.gt_set_training(self._h, role, int(model.training)))
@@ -316,6 +337,30 @@ class StepEngine(object):
         """Every later optimizer step of ``role`` (the discriminator's alone) clamps each updated parameter to ``[-c, c]`` inside the
         fused clip + update launch -- ``p.data.clamp_(-c, c)`` after ``optimizer_d.step()``, the WGAN weight clipping.  ``c = 0``: off."""
         check(lib.gt_set_weight_clip(self._h, int(role), float(c)))
+
+    def set_spectral_norm(self, role, u, v):
+        """Spectral normalisation of the bound MLP discriminator (gt_set_spectral_norm): ``u`` (sum of out) and ``v`` (sum of in) are the
+        model's ``sn_u`` / ``sn_v`` buffers, float32 on the device, advanced in place by every discriminator pass in training mode and
+        kept alive here.  ``None, None`` switches it off.  Called by ``bind_model`` for an ``MLP(..., spectral_norm=True)``."""
+        if u is None or v is None:
+            check(lib.gt_set_spectral_norm(self._h, int(role), None, None, 0, 0))
+            self._keep.pop("sn", None)
+            self._sn_on = False
+            return
+        for t, name in ((u, "sn_u"), (v, "sn_v")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous 1-D float32 device tensor" % name)
+        check(lib.gt_set_spectral_norm(self._h, int(role), ptr(u), ptr(v), u.numel(), v.numel()))
+        self._keep["sn"] = (u, v)
+        self._sn_on = True
+
+    @staticmethod
+    def sn_path_counts(reset=False):
+        """Launches of the spectral-normalisation kernels so far (gt_sn_path_counts; process-wide): [W^T u, W v, normalise + W_eff,
+        partial sums of G (.) W_eff, element pass]."""
+        out = (C.c_int64 * L.SN_PATH_SLOTS)()
+        check(lib.gt_sn_path_counts(out, 1 if reset else 0))
+        return list(out)
 
     def set_loss_normalizer(self, tv):
         """``tv``: python number, or a 1-element CUDA float64 tensor (kept alive here; read in stream order --
@@ -645,7 +690,8 @@ class StepEngine(object):
         x = _check_frames(x, "x", model.in_dim)
         B, T, _ = x.shape
         model._check_masks(B, T)
-        self.bind_model(L.ROLE_G, model, with_grads=False)
+        role = L.ROLE_D if getattr(model, "spectral_norm", False) else L.ROLE_G      # (role D owns the normalisation: the eval form unless model.training)
+        self.bind_model(role, model, with_grads=False)
         if getattr(model, "needs_lengths", False):
             self.set_lengths(lengths, B, T)
         out = torch.empty(B, T, model.out_dim, device=x.device, dtype=torch.float32)
@@ -657,7 +703,7 @@ class StepEngine(object):
             out2 = torch.empty(B, T, model.static_dim, device=x.device, dtype=torch.float32)
         else:
             Rp = None if R is None or isinstance(R, MLPGBand) else ptr(R)      # ignored by the library
-        check(lib.gt_model_forward(self._h, L.ROLE_G, ptr(x), Rp, B, T, ptr(out), ptr(out2), L.current_stream()))
+        check(lib.gt_model_forward(self._h, role, ptr(x), Rp, B, T, ptr(out), ptr(out2), L.current_stream()))
         if out2 is not None:
             return out, out2
         return out.squeeze(0) if squeeze else out

@@ -135,6 +135,9 @@ class _FlatNetwork(AbstractModel, nn.Module):
         self._flat = fn(self._flat)
         if self._flat.dtype != torch.float32:
             raise TypeError("gantts_amd networks are float32 only")
+        for name, buf in self._buffers.items():      # (sn_u / sn_v of a spectrally normalised MLP; engines re-bind through _version)
+            if buf is not None:
+                self._buffers[name] = fn(buf)
         if self._flat_grad is not None:
             self._flat_grad = fn(self._flat_grad)
         self._repoint()
@@ -202,14 +205,30 @@ class MLP(_FlatNetwork):
     ARCH = L.ARCH_MLP
 
     def __init__(self, in_dim=118, out_dim=1, num_hidden=2, hidden_dim=256,
-                 dropout=0.5, last_sigmoid=True, bidirectional=None):
+                 dropout=0.5, last_sigmoid=True, bidirectional=None, spectral_norm=False):
         super(MLP, self).__init__()
+        self.spectral_norm = bool(spectral_norm)
+        if self.spectral_norm and out_dim != 1:
+            raise ValueError("spectral_norm=True is the discriminator's (out_dim = 1), not out_dim = %d" % out_dim)
         self.in_dim, self.out_dim, self.num_hidden, self.hidden_dim = in_dim, out_dim, num_hidden, hidden_dim
         self.dropout_p, self.last_sigmoid = dropout, last_sigmoid
         ins = [in_dim] + [hidden_dim] * (num_hidden - 1)
         self.layers = nn.ModuleList([_LinearParams(hidden_dim, i) for i in ins])
         self.last_linear = _LinearParams(out_dim, hidden_dim)
         self._finish_init()
+        if self.spectral_norm:
+            # torch.nn.utils.spectral_norm's weight_u / weight_v of every nn.Linear, initialised as it does (normalize(randn), eps 1e-12), the
+            # layers' slices one after the other in state_dict order.  Registered only when the feature is on: only then do checkpoints carry them
+            holders = self._holders()
+            self.register_buffer("sn_u", torch.cat([nn.functional.normalize(torch.randn(h.out_features), dim=0, eps=1e-12) for h in holders]))
+            self.register_buffer("sn_v", torch.cat([nn.functional.normalize(torch.randn(h.in_features), dim=0, eps=1e-12) for h in holders]))
+
+    def state_dict(self, *args, **kwargs):
+        """The parameters first, in the order the optimizer indexes them (what every consumer of the key list relies on); sn_u / sn_v behind."""
+        sd = super(MLP, self).state_dict(*args, **kwargs)
+        for k in [k for k in sd if k.endswith("sn_u") or k.endswith("sn_v")]:
+            sd.move_to_end(k)
+        return sd
 
     def forward(self, x, lengths=None):
         return self._own_engine().model_forward(self, x)

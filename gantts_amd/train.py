@@ -287,7 +287,11 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     beyond the reference, read with getattr; the discriminator then has ``last_sigmoid=False`` and the spoofing rate compares against the
     objective's threshold.  The curriculum formula stays as written: under "hinge" / "wgan" ``E_adv`` can be <= 0, and the clip then
     yields 0 (a negative ratio) or 1e3 (a tiny positive one) -- ``adv_w`` is 0 or ``1e3 * w_d`` for that epoch; an ``E_adv`` of exactly
-    0 raises ZeroDivisionError as it would in the reference."""
+    0 raises ZeroDivisionError as it would in the reference.
+
+    ``hp.discriminator_spectral_norm`` (off by default, read with getattr) goes with a discriminator built as ``MLP(..., spectral_norm=True)``:
+    the engine then normalises every weight of the discriminator by its spectral norm, one power iteration per discriminator pass in the
+    train phase, none in the test phase or for ``reference_discriminator`` (both in eval mode); this loop is unchanged."""
     from . import _lib as L
     from .engine import gan_objective_of
     from .data import DevicePrefetcher, ResidentLoader

@@ -357,6 +357,23 @@ int gt_set_option(gt_engine* e, int option, int value);
  * stays a NaN.  c = 0 switches it off (the default: the stored values are the rule's own); c must be finite and >= 0, and role
  * GT_ROLE_D -- anything else returns GT_ERR_INVALID.  Independent of GT_OPT_GAN_OBJECTIVE. */
 int gt_set_weight_clip(gt_engine* e, int role, float c);
+/* Spectral normalisation of the MLP discriminator (SN-GAN; beyond the reference; torch.nn.utils.spectral_norm with n_power_iterations = 1
+ * on every nn.Linear weight, biases untouched).  u [n_u] and v [n_v] are caller-owned float32 device buffers, like optimizer state:
+ * per layer in state_dict order a unit vector of `out` entries in u and one of `in` entries in v (torch's weight_u / weight_v), so
+ * n_u = sum(out) and n_v = sum(in) of the bound discriminator -- checked.  u = v = NULL switches the feature off (the default).
+ * With W (out, in) a layer's weight and eps = 1e-12, every discriminator pass in training mode (gt_set_training) runs ONE power iteration
+ *   v' = W^T u / max(|W^T u|, eps);  r = W v';  u' = r / max(|r|, eps);  sigma = u'^T r;  u <- u', v <- v'
+ * and multiplies by W_eff = W / sigma everywhere; in eval mode nothing is iterated or stored and sigma = u^T W v.  A pass is: the D step
+ * (ONE pass over the natural and the generated rows, where the reference calls D twice: one iteration, not torch's two), the generator
+ * step's adversarial pass, gt_model_forward(role D).  The D step's optimizer sees the gradient w.r.t. W,
+ *   (G - (sum G (.) W_eff) u' v'^T) / sigma,   G = d loss / d W_eff,
+ * (u', v' constants, as in torch) for clip-norm and update; the optimizer updates the caller's W and gt_set_weight_clip keeps clamping it.
+ * An all-zero W gives sigma = 0 and NaN weights, as in torch.  At most 3 launches per pass and 2 per D step are added; with the feature
+ * off nothing changes.  optimizer_d.zero_grad() must precede every update_discriminator(phase = "train") (GT_ERR_STATE otherwise: a
+ * projected gradient is not accumulated into).  GT_ERR_INVALID: role G; an LSTMRNN or SRURNN discriminator; out or in of a layer above
+ * 512; lengths that do not fit; a sharded or communicating engine (gt_set_shard with world > 1, gt_comm_init -- which in turn refuse an
+ * engine with the feature on).  The discriminator must be bound first; binding another one keeps the feature on if the lengths still fit. */
+int gt_set_spectral_norm(gt_engine* e, int role, float* u, float* v, int64_t n_u, int64_t n_v);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,
  * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_coop (its former name sru_lw, 0 / 1 / 2, is still accepted: 2 = 1), head_vec, lstm_bt; the environment variables GT_<NAME>
@@ -816,6 +833,41 @@ int gt_op_sru_input_dropout(const float* x, int ldx, float* y, int ldy, int B, i
  * Copies the GT_HEAD_PATH_SLOTS counts to `counts` (may be null); reset != 0 then zeroes them. */
 #define GT_HEAD_PATH_SLOTS 15
 int gt_head_path_counts(int64_t* counts, int reset);
+
+/* Parity hooks of the spectral normalisation (gt_set_spectral_norm), through the launch functions the step calls.  The job table: n_layers
+ * weights inside a flat float32 buffer of n_flat elements, layer q = (w_off[q], out[q], in[q]) in ascending, non-overlapping order; its
+ * u slice starts at sum(out[0 .. q)), its v slice at sum(in[0 .. q)).  Whatever lies between the weights (biases) is never read by
+ * gt_op_spectral_norm and only squared by gt_op_sn_project.  All pointers are device memory; no synchronisation.
+ * Arithmetic: products of two float32 values in double (exact), two-stage double sums in an order fixed by the table, no atomics
+ * (bit-identical from run to run); u', v', sigma rounded to float32 once; W / sigma the correctly rounded float32 quotient.
+ *   gt_op_spectral_norm   iterate != 0: one power iteration, u and v advanced in place (3 launches); iterate == 0: the eval form, u and v
+ *                         only read (2 launches).  Writes sigma [n_layers] and the weight ranges of weff [n_flat] (nothing else of it).
+ *   gt_op_sn_project      G [n_flat] (d loss / d W_eff in the weight ranges) -> d loss / d W in place, element (i, j) of a layer as
+ *                         ((G - (float(s) * u_i) * v_j) / sigma) in float32 without contraction, s = sum G (.) weff of the layer in double
+ *                         -> s [n_layers].  norm_partials [norm_cap]: *n_norm_partials doubles whose sum is the squared norm of ALL of G
+ *                         afterwards, biases included (what the fused clip + update launch takes).  2 launches.
+ * gt_sn_path_counts: launches by kernel, process-wide, counted on the host: 0 W^T u, 1 W v, 2 normalise + W_eff, 3 partial sums of
+ * G (.) W_eff, 4 the element pass. */
+#define GT_SN_MAX_LAYERS 17
+#define GT_SN_PATH_SLOTS 5
+typedef struct gt_sn_case {
+  int32_t n_layers, iterate;
+  int64_t n_flat, norm_cap;
+  int64_t w_off[GT_SN_MAX_LAYERS];
+  int32_t out[GT_SN_MAX_LAYERS], in[GT_SN_MAX_LAYERS];
+  const float* W;              /* gt_op_spectral_norm: the flat buffer */
+  float* u;
+  float* v;
+  float* weff;
+  float* sigma;                /* [n_layers]: written by gt_op_spectral_norm, read by gt_op_sn_project */
+  float* G;                    /* gt_op_sn_project */
+  double* s;
+  double* norm_partials;
+  int32_t* n_norm_partials;    /* host */
+} gt_sn_case;
+int gt_op_spectral_norm(const gt_sn_case* c, void* stream);
+int gt_op_sn_project(const gt_sn_case* c, void* stream);
+int gt_sn_path_counts(int64_t* counts, int reset);
 
 /* One dropout site of the tail hooks: mode 0 none, 1 the Philox keep bits of (key0, key1) at drop probability p, 2 the 0 / 1 float
  * `mask` [rows][ld_mask] (p still gives the scale 1 / (1 - p)).  dp_*: the data-parallel row-group map of the Philox counter
