@@ -36,6 +36,8 @@ GEMM_B16_PATH_SLOTS = 66                                                # gt_gem
 SRU_PATH_SLOTS = 13                                                     # gt_sru_path_counts
 HEAD_PATH_SLOTS = 15                                                    # gt_head_path_counts
 SN_MAX_LAYERS, SN_PATH_SLOTS = 17, 5                                    # GT_SN_MAX_LAYERS; gt_sn_path_counts: W^T u, W v, normalise + W_eff, G (.) W_eff partials, element pass
+GP_MAX_LAYERS, GP_PATH_SLOTS = 16, 8                                    # GT_GP_MAX_LAYERS; gt_gp_path_counts: gp_interp, gp_slope, gp_row, gp_finalize, gp_add_cols launches, then backward-data, forward, weight-gradient calls
+GRAD_PENALTIES = {None: 0, "r1": 1, "wgan-gp": 2}                       # gt_set_grad_penalty kinds by hp.discriminator_grad_penalty name
 (FRAME_MASK_SUM, FRAME_MASK_TOTAL, FRAME_SQERR, FRAME_G_LOSSES, FRAME_STATIC_GRAD, FRAME_FINALIZE_G, FRAME_FINALIZE_G_RIDER, FRAME_FINALIZE_D,
  FRAME_SCALE_INV_TV, FRAME_HIGHWAY_FWD, FRAME_HIGHWAY_BWD, FRAME_SIGMOID_GRAD, FRAME_DROPOUT_APPLY, FRAME_BUILD_ADV, FRAME_BUILD_CAT2, FRAME_REPITCH,
  FRAME_DENSE_COPY, FRAME_PAD_ROWS, FRAME_TRANSPOSE) = range(19)         # FrameCase.op
@@ -217,6 +219,12 @@ class SnCase(C.Structure):
                 + [("n_norm_partials", C.POINTER(C.c_int32))])
 
 
+class GpCase(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "L", "H", "cd", "Da", "ld_g")] + [("rows", C.c_int64), ("weight", C.c_float), ("inv_tv", C.c_float)]
+                + [(n, C.c_void_p * GP_MAX_LAYERS) for n in ("W", "dW", "Hact", "a", "c")] + [("drop", DropSite * GP_MAX_LAYERS)]
+                + [(n, C.c_void_p) for n in ("w_last", "dw_last", "mask", "g", "g_copy", "phi", "nrm", "sums", "rec")])
+
+
 class CastJob(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("in_", "out", "outT")] + [("rows", C.c_int64), ("ldt", C.c_int64)]
                 + [(n, C.c_int32) for n in ("ldi", "cols", "ldo", "pad_")])
@@ -269,6 +277,12 @@ SIGNATURES = {
     "gt_op_spectral_norm": (_I, [C.POINTER(SnCase), _P]),
     "gt_op_sn_project": (_I, [C.POINTER(SnCase), _P]),
     "gt_sn_path_counts": (_I, [C.POINTER(_L), _I]),
+    "gt_set_grad_penalty": (_I, [_P, _I, _I, _F]),
+    "gt_set_gp_epsilon": (_I, [_P, _P]),
+    "gt_grad_penalty_result": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_L), _I]),
+    "gt_grad_penalty_peek": (_I, [_P, _P, _P, _P]),
+    "gt_op_grad_penalty": (_I, [C.POINTER(GpCase), _P]),
+    "gt_gp_path_counts": (_I, [C.POINTER(_L), _I]),
     "gt_set_x_pitch": (_I, [_P, _I, _I]),
     "gt_set_tuning": (_I, [C.c_char_p, _I]),
     "gt_check_faults": (_I, [_P, _P]),

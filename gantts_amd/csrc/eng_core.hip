@@ -160,6 +160,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   e->ledger.release();
   if (e->sn.plan) sn_plan_free(e->sn.plan);
   e->sn.weff.release(); e->sn.ws.release();
+  e->gp.release();
   delete e;
 }
 
@@ -360,7 +361,7 @@ extern "C" int gt_set_seed(gt_engine* e, uint64_t seed) {
   return GT_OK;
 }
 extern "C" int gt_set_dropout_mask(gt_engine* e, int role, int pass, int layer, const float* mask) {
-  if (!e || role < 0 || role > 1 || pass < 0 || pass > 2 || layer < 0 || layer > 15) return fail(GT_ERR_INVALID, "bad argument");
+  if (!e || role < 0 || role > 1 || pass < 0 || pass > (role == GT_ROLE_D ? 3 : 2) || layer < 0 || layer > 15) return fail(GT_ERR_INVALID, "bad argument");
   e->net[role].inj[pass][layer] = mask;
   return GT_OK;
 }
@@ -541,6 +542,8 @@ DropoutSpec philox_site_spec(gt_engine* e, int role, int pass, int layer, uint64
   }
   d.key0 = (uint32_t)(e->seed ^ (site * 0x9E3779B97F4A7C15ULL)) ^ (rk * 0x85EBCA6Bu);
   d.key1 = (uint32_t)((e->seed >> 32) ^ (site >> 7) ^ 0xA5A5A5A5u) + (uint32_t)site + rk * 0xC2B2AE35u;
+  // pass 3 (the discriminator's forward over the WGAN-GP interpolates): its site number runs into the next step's, so it gets a salt of its own
+  if (pass == 3) { d.key0 ^= 0x3C6EF372u; d.key1 += 0x510E527Fu; }
   return d;
 }
 
@@ -562,7 +565,7 @@ DropoutSpec drop_spec(gt_engine* e, int role, int pass, int layer, const float* 
 // that starts `steps_ahead` apply_generator calls from now (1 = the next one), for a (rows, cols) activation.
 extern "C" int gt_op_philox_mask(gt_engine* e, int role, int pass, int layer, int64_t steps_ahead, float p, int64_t rows, int cols,
                                  float* mask, void* stream) {
-  if (!e || !mask || role < 0 || role > 1 || pass < 0 || pass > 2 || layer < 0 || layer > 15 || rows < 1 || cols < 1 ||
+  if (!e || !mask || role < 0 || role > 1 || pass < 0 || pass > (role == GT_ROLE_D ? 3 : 2) || layer < 0 || layer > 15 || rows < 1 || cols < 1 ||
       steps_ahead < 0 || !(p > 0.f && p < 1.f) || rows > 0x7fffffffL)
     return fail(GT_ERR_INVALID, "bad argument");
   // (data parallel: the row-group map of the last entry point's (B, T); a 2*B*T-row request is the D step's two-half pass)

@@ -1226,3 +1226,34 @@ extern "C" int gt_op_sn_project(const gt_sn_case* c, void* stream) {
   sn_plan_free(plan);
   return r;
 }
+
+// ------------------------------------------------------------------------------------------
+// gradient penalties (eng_grad_penalty.hip): the hook fills the block the step fills from the engine and calls the same launch function
+// ------------------------------------------------------------------------------------------
+extern "C" int gt_op_grad_penalty(const gt_gp_case* c, void* stream) {
+  if (!c) return fail(GT_ERR_INVALID, "null case");
+  if (c->L < 1 || c->L > GT_GP_MAX_LAYERS || c->H < 1 || c->cd < 0 || c->Da < 1 || c->rows < 1 || c->ld_g < c->Da || (c->kind != GP_R1 && c->kind != GP_WGAN))
+    return fail(GT_ERR_INVALID, "gradient penalty: malformed case (L %d, H %d, cd %d, Da %d, rows %ld, ld_g %d, kind %d)", c->L, c->H, c->cd, c->Da,
+                (long)c->rows, c->ld_g, c->kind);
+  if (!c->w_last || !c->dw_last || !c->mask || !c->g || !c->sums) return fail(GT_ERR_INVALID, "gradient penalty: null buffer");
+  GpCall k;
+  memset(&k, 0, sizeof(k));
+  k.L = c->L; k.cd = c->cd; k.Da = c->Da; k.kind = c->kind; k.prec = PREC_F32; k.weight = c->weight; k.rows = (long)c->rows;
+  for (int l = 0; l < c->L; ++l) {
+    const char* why = nullptr;
+    if (!c->W[l] || !c->dW[l] || !c->Hact[l] || !c->a[l] || !c->c[l]) return fail(GT_ERR_INVALID, "gradient penalty: null buffer of layer %d", l);
+    if (!tail_site_ok(c->drop[l], c->H, (long)c->rows, false, &why)) return fail(GT_ERR_INVALID, "gradient penalty: layer %d: %s", l, why);
+    GpLayer& q = k.l[l];
+    q.W = c->W[l]; q.dW = c->dW[l]; q.in = l == 0 ? c->cd + c->Da : c->H; q.out = c->H;
+    q.H = c->Hact[l]; q.spec = tail_site_spec(c->drop[l]); q.a = c->a[l]; q.c = c->c[l];
+  }
+  static thread_local Scratch tls_part, tls_dw0, tls_slabs, tls_colp;      // scratch of the call (grow-only)
+  const int nblk = gp_row_blocks((long)c->rows);
+  CHK(tls_part.ensure((size_t)2 * nblk * sizeof(double)));
+  CHK(tls_dw0.ensure((size_t)c->H * c->Da * sizeof(float)));
+  k.w_last = c->w_last; k.dw_last = c->dw_last; k.g = c->g; k.ld_g = c->ld_g; k.g_copy = c->g_copy;
+  k.mask = c->mask; k.inv_tv = c->inv_tv; k.phi = c->phi; k.nrm = c->nrm;
+  k.part = tls_part.as<double>(); k.part_cap = 2L * nblk; k.sums = c->sums; k.rec = c->rec;
+  k.dw0s = tls_dw0.as<float>(); k.slabs = &tls_slabs; k.colp = &tls_colp;
+  return launch_grad_penalty(k, (hipStream_t)stream);
+}

@@ -551,6 +551,7 @@ static int run_dstack(gt_engine* e, const HeadCall& c, float* gadv, hipStream_t 
   if (d_step) {
     for (int l = 1; l + 1 < L; ++l) a.Hout[l] = W.act[l].as<float>();      // (the top layer's activation only feeds the head, which is fused: no stash)
     a.dZtop = e->dzA.as<float>();
+    if (e->gp.kind == GP_R1 && c.want_grad && L > 1) a.Hout[L - 1] = W.act[L - 1].as<float>();      // R1 recovers the top layer's slopes from it (d_pass_penalty)
   } else {
     a.W0 = D.hidden[0].W; a.ldw0 = D.hidden[0].in; a.col0 = cond_dim(e); a.Da = e->Da; a.gadv = gadv; a.ld_gadv = e->Da;
   }
@@ -903,6 +904,57 @@ static int d_pass_backward(gt_engine* e, DPass& p, float* dst, hipStream_t s) {
   return GT_OK;
 }
 
+// gt_set_grad_penalty: the second-order pass behind the D step's backward pass (eng_grad_penalty.hip), its weight gradients added to what
+// that pass left.  R1 penalises the natural rows, whose activations and dropout sites (pass 0) the forward pass stored; WGAN-GP runs one
+// more forward (dropout pass 3, per-layer launches) over x_hat = eps real + (1 - eps) fake, written over the natural half of the pass's
+// input image.  Scratch: the generated rows' half of every stored activation (a_l), dzA / dzB (c_l, alternating) -- all dead by now.
+static int d_pass_penalty(gt_engine* e, DPass& p, const float* mask, hipStream_t s) {
+  GpState& G = e->gp;
+  if (G.kind == GP_OFF) return GT_OK;
+  Net& D = e->net[GT_ROLE_D];
+  NetWs& W = e->ws[GT_ROLE_D];
+  const long N = p.N;
+  const int L = (int)D.hidden.size(), H = D.d.hidden_dim, cd = cond_dim(e), Da = e->Da, ld_g = (Da + 3) & ~3;
+  if (p.kind != D_MLP_F32 || L < 1 || Da < 1) return fail(GT_ERR_INVALID, "gradient penalty: float32 MLP discriminator only");
+  CHK(slab_defer_flush(W.sdefer, s));      // the backward pass's recorded combines land before anything is added to their results
+  G.stream = s;
+  if (G.kind == GP_WGAN) {
+    float* img = p.split ? e->adv2.as<float>() : e->dcat.as<float>();
+    const int ldo = p.split ? p.fs.ld_adv : p.ldc, col0 = p.split ? 0 : cd;
+    uint32_t k0, k1;
+    gp_eps_keys(e, &k0, &k1);
+    CHK(G.eps.ensure((size_t)N * sizeof(float)));
+    CHK(launch_gp_interp(p.real, p.fake, p.ldf, e->d_adv_cols, Da, G.eps_inj, k0, k1, img, ldo, col0, N, G.eps.as<float>(), s));
+    G.img = img; G.img_ld = ldo; G.img_col0 = col0; G.img_rows = N;
+    const int pass3[1] = {3};
+    CHK(stack_forward(e, GT_ROLE_D, p.img, p.ldc, N, pass3, 1, N, W.specs, s, p.split ? &p.fs : nullptr));
+  }
+  CHK(G.g.ensure((size_t)N * ld_g * sizeof(float)));
+  CHK(G.dw0.ensure((size_t)H * Da * sizeof(float)));
+  const int nblk = gp_row_blocks(N);
+  CHK(G.part.ensure((size_t)2 * nblk * sizeof(double)));
+  GpCall c;
+  memset(&c, 0, sizeof(c));
+  c.L = L; c.cd = cd; c.Da = Da; c.kind = G.kind; c.prec = product_prec(e, GT_ROLE_D); c.weight = G.weight; c.rows = N;
+  for (int l = 0; l < L; ++l) {
+    const Lin& Lr = D.hidden[l];
+    if (Lr.out != H) return fail(GT_ERR_INVALID, "gradient penalty: hidden layers of one width only");
+    GpLayer& q = c.l[l];
+    q.W = Lr.W; q.dW = Lr.dW; q.in = Lr.in; q.out = Lr.out;
+    q.H = W.act[l].as<float>(); q.spec = W.specs[l];
+    q.a = W.act[l].as<float>() + N * (long)Lr.out;
+    q.c = (l & 1) ? e->dzB.as<float>() : e->dzA.as<float>();
+  }
+  c.w_last = D.last.W; c.dw_last = D.last.dW;
+  c.g = G.g.as<float>(); c.ld_g = ld_g;
+  c.mask = mask; c.inv_tv_dev = &e->sc()->inv_tv;
+  c.part = G.part.as<double>(); c.part_cap = (long)(G.part.bytes / sizeof(double));
+  c.rec = G.rec.as<double>();
+  c.dw0s = G.dw0.as<float>();
+  c.slabs = &e->slabs; c.colp = &e->colp;
+  return launch_grad_penalty(c, s);
+}
+
 // ------------------------------------------------------------------------------------------
 // update_discriminator
 // ------------------------------------------------------------------------------------------
@@ -913,6 +965,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   if (!D.bound) return fail(GT_ERR_STATE, "discriminator not bound");
   if (!y_static || !y_hat_static || !mask) return fail(GT_ERR_INVALID, "null tensor");
   CHK(check_gan_objective(e));
+  CHK(gp_refusals(e));
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
   const bool tr = train != 0;
@@ -972,6 +1025,7 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
     float* leak = nullptr;
     if (want_leak) { CHK(e->leak.ensure((size_t)N * e->Da * sizeof(float))); leak = e->leak.as<float>(); }
     CHK(d_pass_backward(e, p, leak, s));
+    CHK(d_pass_penalty(e, p, mask, s));      // gt_set_grad_penalty: added before anything closes the step's gradients (sdefer, clip-norm)
     D.grads_dirty = true;
     if (want_leak) { e->leak_pending = true; e->leak_unnorm = unnorm; }
   }

@@ -14,7 +14,7 @@
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
 // of the two product families; eng_gemm_b16 also holds the stacks' bf16 vocabulary: LinShadow::ensure / shadow_cast, b16_forward / b16_backward_data),
 // eng_step (the G+D step, its ResultsChannel, the MLP stacks and the output layer of every stack: out_layer_forward / out_layer_backward), eng_mlpg
-// (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_spectral_norm (spectral normalisation of the MLP discriminator), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
+// (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_spectral_norm (spectral normalisation of the MLP discriminator), eng_grad_penalty (its R1 / WGAN-GP gradient penalties), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
 // (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage
 // (GT_KERNEL) so that several units may include them.
 #pragma once
@@ -193,8 +193,8 @@ struct Net {
   long bound_step = 0;            // `step` at the bind
   bool buf_live = false;          // SGD: momentum_buffer holds a value (GT_OPTF_BUFFER_LIVE at the bind, or an update since)
   OptimScalarCache hs_cache;      // reset by every bind
-  // injected dropout masks [pass][layer]
-  const float* inj[3][16];
+  // injected dropout masks [pass][layer] (pass 3: the discriminator's forward over the WGAN-GP interpolates)
+  const float* inj[4][16];
   Net() { memset(inj, 0, sizeof(inj)); }
 };
 
@@ -327,6 +327,36 @@ struct SnState {
   SnBufs bufs = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
+// Gradient penalties of the MLP discriminator (eng_grad_penalty.hip, grad_penalty_kernels.hip.h).  GpCall: one second-order pass over plain
+// buffers, what the step (d_pass_penalty) and the hook gt_op_grad_penalty hand to launch_grad_penalty.  GpState: the engine's switch, its
+// scratch and the running record {sum P, sum mean-norm, steps} in device memory.
+namespace gt { enum GpKind { GP_OFF = 0, GP_R1 = 1, GP_WGAN = 2 }; }
+struct GpLayer {
+  const float* W; float* dW; int in, out;          // dense (out, in) weight and its gradient (layer 0: in = cd + Da)
+  const float* H; gt::DropoutSpec spec;            // the stored activation [rows][out] and its dropout site
+  float* a; float* c;                              // [rows][out]: gradient chain and tangent chain (c may alias another layer's c two layers away)
+};
+struct GpCall {
+  int L, cd, Da, kind, prec; float weight; long rows;
+  GpLayer l[16];
+  const float* w_last; float* dw_last;             // the head's weight [H] and its gradient
+  float* g; int ld_g; float* g_copy;               // [rows][ld_g]: g, then r in its place; g_copy (may be null) keeps g
+  const float* mask; const float* inv_tv_dev; float inv_tv;
+  float* phi; float* nrm;                          // per-row values [rows], may be null
+  double* part; long part_cap;                     // [2][workgroups of gp_row]
+  double* sums; double* rec;                       // this call's two sums; the running record (either may be null)
+  float* dw0s;                                     // dense [out_0][Da]: a_0^T r before it is added into dW_0[:, cd:]
+  Scratch* slabs; Scratch* colp;
+};
+struct GpState {
+  int kind = 0; float weight = 0.f;                // gt_set_grad_penalty: 0 off, 1 r1, 2 wgan-gp
+  const float* eps_inj = nullptr;                  // gt_set_gp_epsilon: [N] or null (Philox)
+  Scratch g, dw0, part, rec, eps;
+  hipStream_t stream = nullptr;                    // of the last penalised step (gt_grad_penalty_result synchronises it)
+  const float* img = nullptr; int img_ld = 0, img_col0 = 0; long img_rows = 0;      // where the last step's x_hat image lies (gt_grad_penalty_peek)
+  void release() { g.release(); dw0.release(); part.release(); rec.release(); eps.release(); }
+};
+
 struct gt_engine {
   gt_stream_config cfg;
   Net net[2];
@@ -427,6 +457,7 @@ struct gt_engine {
   int gan_objective = 0;                           // GT_OPT_GAN_OBJECTIVE: the head's adversarial objective (gan_objective.hip.h), 0 = the reference's sigmoid + log loss
   float weight_clip[2] = {0.f, 0.f};               // gt_set_weight_clip (role D only): every optimizer step clamps the updated parameters to [-c, c]; 0 = off
   SnState sn;                                      // gt_set_spectral_norm (role D, MLP only): Lin::W of the discriminator then points into sn.weff
+  GpState gp;                                      // gt_set_grad_penalty (role D, MLP only): one more stage of the D step (d_pass_penalty)
   std::vector<int> h_lengths;
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
@@ -610,6 +641,17 @@ void sn_point_weights(gt_engine* e);
 int sn_rebind(gt_engine* e);                              // gt_bind_model(role D) with the feature on: the new network against the registered buffers
 int sn_prepare_pass(gt_engine* e, hipStream_t s);         // no-op when the feature is off
 int sn_project_grads(gt_engine* e, double* norm_part, int* n_partial, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------
+// eng_grad_penalty.hip -- launch_grad_penalty / launch_gp_interp are the one launch site of each kernel, shared by the step and the hook
+// gt_op_grad_penalty (eng_ops.hip); gt_gp_path_counts counts them on the host (slot layout in gantts_hip.h)
+// ------------------------------------------------------------------------------------------
+int gp_row_blocks(long rows);                             // workgroups of gp_row: GpCall::part holds two doubles for each
+void gp_eps_keys(const gt_engine* e, uint32_t* key0, uint32_t* key1);      // Philox keys of the current step's eps draws
+int launch_gp_interp(const float* real, const float* fake, int ldf, const int* idx, int na, const float* eps_in, uint32_t key0, uint32_t key1,
+                     float* out, int ldo, int col0, long rows, float* eps_out, hipStream_t s);
+int launch_grad_penalty(const GpCall& c, hipStream_t s);
+int gp_refusals(const gt_engine* e);                      // no-op when the feature is off
 
 // ------------------------------------------------------------------------------------------
 // eng_comm.hip

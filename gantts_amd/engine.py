@@ -46,6 +46,15 @@ def gan_objective_of(hp):
     return name
 
 
+def grad_penalty_of(hp):
+    """``(hp.discriminator_grad_penalty, hp.discriminator_grad_penalty_weight)`` (opt-in, read with getattr: None -- the default --,
+    "r1" or "wgan-gp"; weight 10.0), checked against the names the engine knows."""
+    kind = getattr(hp, "discriminator_grad_penalty", None)
+    if kind not in L.GRAD_PENALTIES:
+        raise ValueError("hp.discriminator_grad_penalty = %r: None, \"r1\" or \"wgan-gp\"" % (kind,))
+    return kind, float(getattr(hp, "discriminator_grad_penalty_weight", 10.0))
+
+
 def _hp_signature(hp):
     adv = getattr(hp, "adversarial_streams", None)
     # (the adversarial objective and the weight clip are set once per engine: two settings never share one)
@@ -54,7 +63,7 @@ def _hp_signature(hp):
             int(getattr(hp, "mask_nth_mgc_for_adv_loss", 0)),
             bool(getattr(hp, "discriminator_linguistic_condition", False)),
             gan_objective_of(hp), float(getattr(hp, "discriminator_weight_clip", 0.0)),
-            bool(getattr(hp, "discriminator_spectral_norm", False)))
+            bool(getattr(hp, "discriminator_spectral_norm", False)), grad_penalty_of(hp) if grad_penalty_of(hp)[0] else None)
 
 
 def _same_storage(t, c, name):
@@ -139,6 +148,11 @@ class StepEngine(object):
         # hp.discriminator_spectral_norm: the discriminator bound to this engine is an ``MLP(..., spectral_norm=True)`` (checked at the bind)
         self.spectral_norm = bool(getattr(hp, "discriminator_spectral_norm", False))
         self._sn_on = False                      # gt_set_spectral_norm holds buffers right now
+        # hp.discriminator_grad_penalty / _weight: R1 or WGAN-GP on the MLP discriminator, sent before any network is bound
+        self.grad_penalty = None
+        kind, weight = grad_penalty_of(hp)
+        if kind is not None:
+            self.set_grad_penalty(kind, weight)
 
     @classmethod
     def for_forward_only(cls, model):
@@ -353,6 +367,51 @@ class StepEngine(object):
         check(lib.gt_set_spectral_norm(self._h, int(role), ptr(u), ptr(v), u.numel(), v.numel()))
         self._keep["sn"] = (u, v)
         self._sn_on = True
+
+    def set_grad_penalty(self, kind, weight=10.0):
+        """Gradient penalty of the MLP discriminator (gt_set_grad_penalty): ``None`` (off), ``"r1"`` (on the natural rows of the D step) or
+        ``"wgan-gp"`` (on per-frame interpolates of natural and generated rows).  Every later ``update_discriminator(phase="train")`` adds
+        the penalty's weight gradients ahead of clip-norm and the update; ``loss_d`` stays the adversarial loss (``grad_penalty_result``
+        reads the penalty).  Refused by the engine: recurrent discriminators, bf16 products, data parallel, spectral norm, a negative
+        or non-finite weight."""
+        if kind not in L.GRAD_PENALTIES:
+            raise ValueError("grad penalty %r: None, \"r1\" or \"wgan-gp\"" % (kind,))
+        check(lib.gt_set_grad_penalty(self._h, L.ROLE_D, L.GRAD_PENALTIES[kind], float(weight)))
+        self.grad_penalty = kind
+
+    def set_gp_epsilon(self, eps):
+        """Parity hook (gt_set_gp_epsilon): the WGAN-GP interpolation weights, one per frame (``B * T`` float32 on the device, kept alive
+        here), instead of the engine's Philox draws; ``None`` restores them."""
+        if eps is None:
+            check(lib.gt_set_gp_epsilon(self._h, None))
+            self._keep.pop("gp_eps", None)
+            return
+        if not (isinstance(eps, torch.Tensor) and eps.is_cuda and eps.dtype == torch.float32 and eps.is_contiguous()):
+            raise ValueError("eps must be a contiguous float32 device tensor")
+        check(lib.gt_set_gp_epsilon(self._h, ptr(eps)))
+        self._keep["gp_eps"] = eps
+
+    def grad_penalty_result(self, reset=True):
+        """``{"grad_penalty", "grad_norm_at_penalty", "steps"}``: the means of the penalty and of the masked mean gradient norm over the
+        penalised D steps since the last reset (zeros when there were none).  Waits for the step stream: once per phase, not per batch."""
+        p, n, k = C.c_double(), C.c_double(), C.c_int64()
+        check(lib.gt_grad_penalty_result(self._h, C.byref(p), C.byref(n), C.byref(k), 1 if reset else 0))
+        return {"grad_penalty": p.value, "grad_norm_at_penalty": n.value, "steps": int(k.value)}
+
+    def grad_penalty_peek(self, rows, cols):
+        """Parity hook (gt_grad_penalty_peek): the last wgan-gp step's ``eps`` (rows) and ``x_hat`` image (rows, cols)."""
+        eps = torch.empty(rows, device="cuda", dtype=torch.float32)
+        xh = torch.empty(rows, cols, device="cuda", dtype=torch.float32)
+        check(lib.gt_grad_penalty_peek(self._h, ptr(eps), ptr(xh), L.current_stream()))
+        return eps, xh
+
+    @staticmethod
+    def gp_path_counts(reset=False):
+        """Launches of the gradient-penalty stage so far (gt_gp_path_counts; process-wide): [gp_interp, gp_slope, gp_row, gp_finalize,
+        gp_add_cols, backward-data calls, forward calls, weight-gradient calls]."""
+        out = (C.c_int64 * L.GP_PATH_SLOTS)()
+        check(lib.gt_gp_path_counts(out, 1 if reset else 0))
+        return list(out)
 
     @staticmethod
     def sn_path_counts(reset=False):

@@ -291,9 +291,14 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
 
     ``hp.discriminator_spectral_norm`` (off by default, read with getattr) goes with a discriminator built as ``MLP(..., spectral_norm=True)``:
     the engine then normalises every weight of the discriminator by its spectral norm, one power iteration per discriminator pass in the
-    train phase, none in the test phase or for ``reference_discriminator`` (both in eval mode); this loop is unchanged."""
+    train phase, none in the test phase or for ``reference_discriminator`` (both in eval mode); this loop is unchanged.
+
+    ``hp.discriminator_grad_penalty`` (None, "r1" or "wgan-gp"; ``hp.discriminator_grad_penalty_weight``, default 10) adds a gradient
+    penalty to every D step of the train phase inside the engine.  The losses logged here do not contain it; its mean and the mean
+    gradient norm it was taken at are read once at the end of the train phase (never per batch, with or without
+    ``hp.device_epoch_ledger``) and logged as ``grad_penalty`` and ``grad_norm_at_penalty``."""
     from . import _lib as L
-    from .engine import gan_objective_of
+    from .engine import gan_objective_of, grad_penalty_of
     from .data import DevicePrefetcher, ResidentLoader
     from .multistream import get_static_features
     from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
@@ -327,6 +332,7 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     ledger = bool(getattr(hp, "device_epoch_ledger", False))
     spoof_threshold = L.GAN_OBJECTIVE_THRESHOLD[gan_objective_of(hp)]
     ledger_eng, ledger_open, ledger_metrics = None, False, ()
+    grad_penalty = grad_penalty_of(hp)[0]
 
     for global_epoch in range(global_epoch + 1, hp.nepoch + 1):
         if hp.lr_decay_schedule and update_g:
@@ -444,6 +450,11 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
                 real_correct_count, fake_correct_count = led["real_correct"], led["fake_correct"]
                 if update_g:
                     running_metrics = {k: led[k] for k in ledger_metrics}
+
+            if grad_penalty is not None and update_d and phase == "train" and N > 0:
+                gp = _engine_of(y_hat_static, model_g).grad_penalty_result(reset=True)
+                log_value("grad_penalty", gp["grad_penalty"], global_epoch)
+                log_value("grad_norm_at_penalty", gp["grad_norm_at_penalty"], global_epoch)
 
             if update_d and update_g and phase == "train":
                 E_loss_mge = (mse_w * running_loss["mse"] + mge_w * running_loss["mge"]) / N

@@ -208,7 +208,8 @@ int gt_set_seed(gt_engine* e, uint64_t seed);
 /* Parity hook: use the caller's 0/1 float mask ((rows, hidden) contiguous, device) instead of the
  * Philox stream for dropout site `layer` of forward pass `pass` of `role`; NULL restores Philox.
  * passes: G: 0 = apply_generator.  D: 0 = real rows of the D step, 1 = generated rows of the
- * D step, 2 = generated rows of the G step (the order nn.Dropout is consumed in train.py:261-307).
+ * D step, 2 = generated rows of the G step (the order nn.Dropout is consumed in train.py:261-307), 3 = the WGAN-GP
+ * interpolates of the D step (gt_set_grad_penalty; role D only).
  * SRURNN (models.py:152-154: rnn_dropout / dropout of the SRU cell are VARIATIONAL masks, one per sequence and shared
  * over time): `layer` = 2*l selects the input mask of SRU layer l, shape (B, n_in_l); 2*l + 1 its output mask, (B, H*dirs); an
  * SRURNN in the discriminator slot takes them per pass like every discriminator. */
@@ -374,6 +375,25 @@ int gt_set_weight_clip(gt_engine* e, int role, float c);
  * 512; lengths that do not fit; a sharded or communicating engine (gt_set_shard with world > 1, gt_comm_init -- which in turn refuse an
  * engine with the feature on).  The discriminator must be bound first; binding another one keeps the feature on if the lengths still fit. */
 int gt_set_spectral_norm(gt_engine* e, int role, float* u, float* v, int64_t n_u, int64_t n_v);
+/* Gradient penalties of the MLP discriminator (beyond the reference): kind 0 off (the default), 1 R1 (Mescheder et al. 2018) on the natural
+ * rows of the D step, 2 WGAN-GP (Gulrajani et al. 2017) on x_hat = eps real + (1 - eps) fake with eps ~ U[0, 1) per frame.  The penalty is
+ * taken on the output layer's pre-activation z under every objective, w.r.t. the Da adversarial columns only (the conditioning x is data).
+ * Per frame, with g = dz / d adv, n = sqrt(sum g^2 + 1e-12), T the step's valid-frame count:
+ *   r1: phi = (weight / 2) sum g^2;   wgan-gp: phi = weight (n - 1)^2;   P = sum mask phi / T
+ * Every gt_update_discriminator(train) then adds dP / dW to the discriminator's weight gradients behind its backward pass and ahead of
+ * clip-norm and the update, so gt_d_result.grad_norm sees the sum; loss_d stays the adversarial loss alone.  Biases, the conditioning
+ * columns of the first layer and the generator (the kept dloss_d / dy_hat_static included) get exactly nothing: LeakyReLU and dropout are
+ * piecewise linear.  WGAN-GP runs one more forward pass, dropout pass 3 of gt_set_dropout_mask; eps is one Philox4x32-10 draw per frame
+ * keyed by the seed and the step, or the caller's (gt_set_gp_epsilon: [B T] device floats, NULL restores Philox).  With kind 0 nothing
+ * changes, bit for bit.  GT_ERR_INVALID, at the switch or at the next D step before any launch: role G; an LSTMRNN or SRURNN
+ * discriminator; GT_OPT_MATMUL_BF16; a sharded or communicating engine; spectral normalisation on; weight < 0 or not finite; unknown kind.
+ * gt_grad_penalty_result synchronises the stream of the last penalised step and reads the running device record: the means of P and of
+ * sum mask n / T over the D steps since the last reset (0 when there were none), their number, and zeroes the record when reset != 0.
+ * gt_grad_penalty_peek (parity): the last wgan-gp step's eps [B T] and x_hat [B T][Da] into the caller's device buffers (either may be null). */
+int gt_set_grad_penalty(gt_engine* e, int role, int kind, float weight);
+int gt_set_gp_epsilon(gt_engine* e, const float* eps);
+int gt_grad_penalty_result(gt_engine* e, double* penalty_mean, double* grad_norm_mean, int64_t* steps, int reset);
+int gt_grad_penalty_peek(gt_engine* e, float* eps, float* x_hat, void* stream);
 /* Process-wide dispatch knobs of the kernels (tile shapes, pair launches, loader variants ...: measurement switches of the tools/
  * harnesses and A/B runs; none selects different arithmetic).  Names: gemm_pair, pair_order, gemm_tiles_big, gemm_unaligned, tn_wgs, tn_split_wgs, split_fused,
  * b16_tiles, b16_wg_tile, b16_dma, mlpg_fpl, mlpg_tt, sru_coop (its former name sru_lw, 0 / 1 / 2, is still accepted: 2 = 1), head_vec, lstm_bt; the environment variables GT_<NAME>
@@ -883,6 +903,44 @@ typedef struct gt_drop_site {
   int32_t ld_mask, pad_;
   const float* mask;
 } gt_drop_site;
+
+/* Parity hook of the gradient penalties (gt_set_grad_penalty): the four parts of the second-order pass through the launch functions the
+ * step calls, over `rows` rows of an MLP with L hidden layers of width H whose first layer reads [cd conditioning | Da adversarial]
+ * columns.  All pointers but the case itself are device memory; no synchronisation.
+ *   reads    W[l] dense (H, in_l) with in_0 = cd + Da and in_l = H above; w_last [H]; Hact[l] [rows][H], the stored activations, and drop[l],
+ *            the dropout site each was stored under; mask [rows]; inv_tv = 1 / T
+ *   writes   a[l], c[l] [rows][H] (the gradient and tangent chains); g_copy [rows][ld_g] (may be null): g; g [rows][ld_g]: r (pad columns
+ *            [Da, ld_g) zero); phi, nrm [rows]: per-row phi and n; sums [2] doubles: sum mask phi, sum mask n (before the 1 / T);
+ *            rec [3] doubles or null: {sum P, sum mean-norm, steps} += {sums[0] / T, sums[1] / T, 1}
+ *   adds     dW[0][:, cd : cd + Da] += a_0^T r;  dW[l] += a_l^T c_{l-1};  dw_last [H] += column sums of c_{L-1}.  Nothing else of a gradient
+ *            buffer is written: no bias gradient, no dW[0][:, :cd].
+ * gt_gp_path_counts: process-wide, counted on the host: 0 gp_interp, 1 gp_slope, 2 gp_row, 3 gp_finalize, 4 gp_add_cols (launches); 5
+ * backward-data, 6 forward, 7 weight-gradient calls of the product family (their launches are in gt_gemm_path_counts).  A pass over L
+ * layers issues L + 1 slope, 1 row, 1 finalize, 1 add_cols launches and L backward-data, L forward, L + 1 weight-gradient calls. */
+#define GT_GP_MAX_LAYERS 16
+#define GT_GP_PATH_SLOTS 8
+typedef struct gt_gp_case {
+  int32_t kind, L, H, cd, Da, ld_g;      /* kind: 1 r1, 2 wgan-gp */
+  int64_t rows;
+  float weight, inv_tv;
+  const float* W[GT_GP_MAX_LAYERS];
+  float* dW[GT_GP_MAX_LAYERS];
+  const float* Hact[GT_GP_MAX_LAYERS];
+  float* a[GT_GP_MAX_LAYERS];
+  float* c[GT_GP_MAX_LAYERS];
+  gt_drop_site drop[GT_GP_MAX_LAYERS];
+  const float* w_last;
+  float* dw_last;
+  const float* mask;
+  float* g;
+  float* g_copy;
+  float* phi;
+  float* nrm;
+  double* sums;
+  double* rec;
+} gt_gp_case;
+int gt_op_grad_penalty(const gt_gp_case* c, void* stream);
+int gt_gp_path_counts(int64_t* counts, int reset);
 
 /* Parity hook of the discriminator's per-layer head: ONE head pass plus its finalising launch through the launch function the engine
  * uses (launch_d_head), so the kernel form follows from K (KP), h_ld (> 0: the bf16 image form) and the tuning knob head_vec exactly as
