@@ -104,7 +104,7 @@ extern "C" int gt_comm_init(gt_engine* e, int rank, int world, const void* id) {
   const unsigned evf = hipEventDisableTiming | (env_flag("GT_COMM_EVENT_DEVICE_SCOPE", true) ? hipEventReleaseToDevice : 0u);
   for (auto& ev : c->ev) HIPCHK(hipEventCreateWithFlags(&ev, evf));
   HIPCHK(hipEventCreateWithFlags(&c->ev_done, evf));
-  CHK(e->comm_tv.ensure(64));
+  CHK(e->norm.attach());
   return GT_OK;
 }
 // The engine's shard of the minibatch without a communicator (hosts that all-reduce themselves between the split-phase
@@ -278,48 +278,32 @@ int comm_finish_step(gt_engine* e, int role, bool grads, double* sums, int n_sum
 int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float adv_w, float mse_w, float mge_w, hipStream_t compute) {
   GtComm* c = e->comm;
   CHK(comm_allreduce_after(e, sums, (size_t)n_sums, GT_NCCL_DOUBLE, compute));
-  if (role == GT_ROLE_D) launch_finalize_d(e->sc(), e->results.target(), 1, e->d_unnorm ? 1 : 0, c->stream);
+  if (role == GT_ROLE_D) launch_finalize_d(e->sc(), e->results.target(), 1, e->norm.d_unnormalised() ? 1 : 0, c->stream);
   else launch_finalize_g(e->sc(), e->results.target(), adv_w, mse_w, mge_w, e->g_has_adv ? 1 : 0, 1, nullptr, 0, nullptr, 0, c->stream);
   LAUNCH_CHECK();
   return e->results.post_early(c->stream);
 }
 
-// tv = sum(mask) (or the data-parallel override) -> device scalars; once per (step, mask).  With a communicator the
-// count is the GLOBAL one: losses are normalised by the valid frames of the whole minibatch (train.py:258, seqloss.py:43).
-// Two halves so that the all-reduce of the count runs under the forward pass that precedes its first use:
-// ensure_tv_begin where the mask is first seen, ensure_tv right before the first kernel that reads the normaliser.
-int ensure_tv_begin(gt_engine* e, const float* mask, long N, hipStream_t s) {
-  if (e->tv.known(mask, N, e->tv_override)) return GT_OK;
-  if (comm_on(e) && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight) {
-    launch_mask_total(mask, N, e->comm_tv.as<double>(), s);
-    LAUNCH_CHECK();
-    CHK(comm_allreduce_after(e, e->comm_tv.p, 1, GT_NCCL_DOUBLE, s));
-    e->tv_inflight = true;
-  }
-  return GT_OK;
-}
-// riders (eng_step.hip): the local count was written to comm_tv by a rider of another launch / is consumed by the head directly
-int comm_tv_sent(gt_engine* e, hipStream_t s) {
-  CHK(comm_allreduce_after(e, e->comm_tv.p, 1, GT_NCCL_DOUBLE, s));
-  e->tv_inflight = true;
-  return GT_OK;
-}
-int comm_tv_join(gt_engine* e, hipStream_t s) {
-  CHK(comm_join(e, s));
-  e->tv_inflight = false;
-  return GT_OK;
-}
-int ensure_tv(gt_engine* e, const float* mask, long N, hipStream_t s) {
-  if (e->tv.known(mask, N, e->tv_override)) return GT_OK;
-  const double* tv_dev = e->tv_dev;
-  if (comm_on(e) && !tv_dev && !(e->tv_override > 0.f)) {
-    CHK(ensure_tv_begin(e, mask, N, s));
-    CHK(comm_tv_join(e, s));
-    tv_dev = e->comm_tv.as<double>();
-  }
-  launch_mask_sum(mask, N, e->tv_override, tv_dev, e->sc(), s);
+// LossNormaliser (engine_internal.hip.h): the launches and collectives behind its events.  start and join are two halves so that the
+// all-reduce of the count runs under the forward pass that precedes its first use (TvPlan, eng_step.hip); ensure() is both at once.
+int LossNormaliser::start(gt_engine* e, const float* m, long N, hipStream_t s) {
+  launch_mask_total(m, N, reduced(), s);
   LAUNCH_CHECK();
-  e->tv.note(mask, N, e->tv_override);
+  return send(e, s);
+}
+int LossNormaliser::send(gt_engine* e, hipStream_t s) { return comm_allreduce_after(e, total.p, 1, GT_NCCL_DOUBLE, s); }
+int LossNormaliser::join(gt_engine* e, hipStream_t s) { return comm_join(e, s); }
+int LossNormaliser::file(gt_engine* e, const float* m, long N, const double* from, hipStream_t s) {
+  launch_mask_sum(m, N, ovr, from, e->sc(), s);
+  LAUNCH_CHECK();
+  note(m, N);
   return GT_OK;
+}
+int LossNormaliser::ensure(gt_engine* e, const float* m, long N, hipStream_t s) {
+  if (known(m, N)) return GT_OK;
+  if (!comm_on(e) || given()) return file(e, m, N, dev, s);
+  CHK(start(e, m, N, s));
+  CHK(join(e, s));
+  return file(e, m, N, reduced(), s);
 }
 

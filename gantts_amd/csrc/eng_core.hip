@@ -148,9 +148,9 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
     if (e->len_host[i]) (void)hipHostFree(e->len_host[i]);
     if (e->len_ev[i]) (void)hipEventDestroy(e->len_ev[i]);
   }
-  Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->leak, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
+  Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
                     &e->cx_dense.buf, &e->dx_pitched.buf, &e->gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
-                    &e->mlpg.fac, &e->mlpg.wide, &e->comm_tv, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2, &e->mlpg_var_ws};
+                    &e->mlpg.fac, &e->mlpg.wide, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2, &e->mlpg_var_ws};
   for (auto* s : all) s->release();
   e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
   e->mlpg.clear();
@@ -161,6 +161,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
   if (e->sn.plan) sn_plan_free(e->sn.plan);
   e->sn.weff.release(); e->sn.ws.release();
   e->gp.release();
+  e->norm.release(); e->leak.release();
   delete e;
 }
 
@@ -390,21 +391,21 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       // instead of back-propagating through buffers the forward never filled
       if (e->matmul_bf16 != (value != 0)) {
         invalidate_d_images(e);
-        e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget(); e->results.forget_begin();
+        e->g_pass_valid = false; e->leak.drop(); e->cx_dense.forget(); e->results.forget_begin();
       }
       e->matmul_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_SRU_D_BF16:
       if (value != 0 && value != 1) return fail(GT_ERR_INVALID, "GT_OPT_SRU_D_BF16 takes 0 or 1, not %d", value);
       // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
-      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak_pending = false; e->results.forget_begin(); }
+      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak.drop(); e->results.forget_begin(); }
       e->sru_d_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_GAN_OBJECTIVE:
       if (value < 0 || value >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE takes 0 (bce), 1 (ls), 2 (hinge) or 3 (wgan), not %d", value);
       if (e->net[GT_ROLE_D].bound) CHK(gan_objective_fits(value, e->net[GT_ROLE_D].d.last_sigmoid != 0));
       // (a discriminator pass begun under one objective is not finished, and its kept gradient not used, under another)
-      if (e->gan_objective != value) { e->leak_pending = false; e->results.forget_begin(); }
+      if (e->gan_objective != value) { e->leak.drop(); e->results.forget_begin(); }
       e->gan_objective = value;
       return GT_OK;
   }
@@ -449,14 +450,12 @@ extern "C" int gt_set_x_pitch(gt_engine* e, int ld_generator_input, int ld_condi
 }
 extern "C" int gt_set_loss_normalizer(gt_engine* e, float tv) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  e->tv_override = tv;
-  e->tv_dev = nullptr;
+  e->norm.set_override(tv);
   return GT_OK;
 }
 extern "C" int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_dev) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  e->tv_dev = tv_dev;
-  e->tv.forget(); e->tv_inflight = false;          // re-read on the next step function
+  e->norm.set_total_dev(tv_dev);
   return GT_OK;
 }
 extern "C" int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, void* stream) {
@@ -495,8 +494,8 @@ extern "C" int gt_zero_grad(gt_engine* e, int role) {
   if (!e || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
   e->net[role].grads_dirty = false;   // lazily: the next backward overwrites
   e->ws[role].sdefer.reset(false);      // nothing recorded survives a zero_grad
-  e->tv.forget(); e->tv_inflight = false;
-  if (role == GT_ROLE_G) { e->leak_pending = false; e->leak_unnorm = false; }
+  e->norm.forget();
+  if (role == GT_ROLE_G) e->leak.drop();
   return GT_OK;
 }
 extern "C" int gt_scalar_buffer(gt_engine* e, double** dev_ptr, int* n) {
@@ -607,7 +606,7 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   }
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   invalidate_d_images(e);
-  e->g_pass_valid = false; e->leak_pending = false; e->cx_dense.forget(); e->results.reset();
+  e->g_pass_valid = false; e->leak.drop(); e->cx_dense.forget(); e->results.reset();
   return GT_OK;
 }
 extern "C" int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset) {

@@ -94,7 +94,7 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
 }
 // the stashed generator pass would transpose through a band that is about to be freed: it can no longer be back-propagated
 static void drop_pass_of(gt_engine* e, const MlpgBand* b) {
-  if (e->g_band == b) { e->g_band = nullptr; e->g_pass_valid = false; e->leak_pending = false; }
+  if (e->g_band == b) { e->g_band = nullptr; e->g_pass_valid = false; e->leak.drop(); }
 }
 extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
@@ -349,10 +349,10 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
   if (!bwd) {
     r = mlpg_forward(e, c->y, c->ldy, scol, sstride, Ds, c->ys, c->ldys, c->B, c->T, *band, s);
   } else {
-    if (mse) {      // sum(mask) and its reciprocal, as ensure_tv puts them there; the step's memo of it no longer holds
+    if (mse) {      // sum(mask) and its reciprocal, as LossNormaliser::file puts them there, behind the step's memo of them
       launch_mask_sum(c->mask, (long)c->B * c->T, -1.f, nullptr, e->sc(), s);
       LAUNCH_CHECK();
-      e->tv.forget();
+      e->norm.overwritten();
     }
     r = mlpg_backward(e, c->gs, c->ldgs, scol, sstride, Ds, c->gy, c->ldgy, c->B, c->T, mse ? c->mse_w : 0.f, mse ? c->yhat : nullptr,
                       mse ? c->ytgt : nullptr, mse ? c->ldt : 0, mse ? c->mask : nullptr, *band, s);

@@ -413,7 +413,7 @@ extern "C" int gt_apply_generator(gt_engine* e, const float* x, const float* R, 
   // no StepCopy outlives a batch: the step count alone does not tell two batches apart (gt_set_seed restarts it, and a staging buffer
   // refilled in place has the same pointer, pitch and shape).  Both update calls of a batch come behind this one: they still share a copy.
   e->dx_pitched.forget(); e->gx_pitched.forget(); e->cx_dense.forget();
-  e->tv.forget(); e->tv_inflight = false;             // a new batch: the mask contents may have changed
+  e->norm.forget();             // a new batch: the mask contents may have changed
   CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->ws[GT_ROLE_G].specs));
   e->last_x = e->gx_dense_on ? e->gx_dense.as<float>() : x;      // (what the backward pass reads: the dense copy when one was made)
   e->last_yhat = y_hat; e->last_yhs = y_hat_static;
@@ -591,8 +591,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   double* part = e->partial.as<double>() + 2048;
   unsigned int* skipped = e->h_fault_dev ? e->h_fault_dev + 1 + role : (unsigned int*)nullptr;
   // the discriminator's gradient of a GT_OPT_COMM_TV_IN_SUMS step is that of the unnormalised loss: x 1 / Tv in the update kernel
-  const float* gscale = (role == GT_ROLE_D && e->d_unnorm) ? &e->sc()->inv_tv : (const float*)nullptr;
-  if (role == GT_ROLE_D) e->d_unnorm = false;
+  const float* gscale = role == GT_ROLE_D ? e->norm.take_d_scale(e->sc()) : (const float*)nullptr;
   SlabDefer& sd = e->ws[role].sdefer;
   int n_partial = 0;      // squared-norm partials in `part`: none until one of the routes below has launched them
   if (role == GT_ROLE_D && e->sn.on) {
@@ -760,17 +759,68 @@ static int d_pass_plan(gt_engine* e, const float* x, const float* real, const fl
   return GT_OK;
 }
 
-// The valid-frame count as an extra workgroup of the adversarial-column gather (D step, split first layer): decided by the caller.
-struct AdvRiders {
-  const float* mask;
-  bool tv_ride;                // fused single-GPU call: the count is not known yet
-  bool tv_ride_dp;             // data parallel: the local term of the global count, all-reduced right behind the launch
-  bool unnorm;                 // GT_OPT_COMM_TV_IN_SUMS: the local count leaves with the loss sums
+// How Tv = sum(mask) and 1 / Tv reach the discriminator step's head and its gradient consumers: decided once, at the top of
+// gt_update_discriminator_begin, from what LossNormaliser knows.  F: a fused call with GT_OPT_LAUNCH_RIDERS; S: GT_OPT_COMM_TV_IN_SUMS in a
+// step that trains through a bound optimizer (`steps`).
+//   the scalars hold it | communicator | the caller's | F   | S   | route     | the (local) sum                                   | the head's normaliser
+//   yes                 |              |              |     |     | KNOWN     | --                                                | the scalars
+//   no                  | no           |              | no  |     | LOCAL     | mask_sum launch in front of the head              | the scalars
+//   no                  | no           |              | yes |     | LOCAL     | split: rider (*), else as the row above           | the scalars
+//   no                  | yes          | yes          |     |     | LOCAL     | mask_sum launch in front of the head              | the scalars
+//   no                  | yes          | no           | no  |     | ALLREDUCE | mask_total launch in front of the input           | riders on: the message; else the scalars (mask_sum launch)
+//   no                  | yes          | no           | yes | no  | ALLREDUCE | split: rider, else mask_total launch              | the message
+//   no                  | yes          | no           | yes | yes | IN_SUMS   | split: rider, else mask_total launch; into tv_sum | none: unit seeds, 1 / Tv where the gradient is consumed
+// rider: one extra workgroup of the adversarial-column gather (split first layer), `ride`.  (*) takes the override, not a device total.
+// ALLREDUCE: the message is sent by before_input or rode and joined by before_head -- in flight only between the two, inside this one call.
+// The generator step takes none of these routes: one LossNormaliser::ensure.
+struct TvPlan {
+  enum Route { KNOWN, LOCAL, ALLREDUCE, IN_SUMS } route;
+  bool ride, head_reads;      // head_reads (ALLREDUCE): the head takes the count where the collective left it and files it in the scalars
+  const float* mask; long N;
+  TvPlan(gt_engine* e, const DPass& p, const float* mask_, bool steps) : mask(mask_), N(p.N) {
+    const bool comm = comm_on(e), fused = e->results.early && e->opt_launch_riders;
+    route = e->norm.known(mask, N) ? KNOWN : !comm || e->norm.given() ? LOCAL : fused && e->opt_comm_tv_in_sums && steps ? IN_SUMS : ALLREDUCE;
+    ride = p.split && (route == IN_SUMS || (route == ALLREDUCE && fused) || (route == LOCAL && fused && !comm));
+    head_reads = e->opt_launch_riders;
+  }
+  int before_input(gt_engine* e, hipStream_t s) const {      // the local sum as a launch of its own, where a message or the loss sums carry it
+    if (ride || route == KNOWN || route == LOCAL) return GT_OK;
+    if (route == ALLREDUCE) return e->norm.start(e, mask, N, s);      // (the all-reduce then runs under the forward pass)
+    launch_mask_total(mask, N, &e->sc()->tv_sum, s);
+    LAUNCH_CHECK();
+    return GT_OK;
+  }
+  void ride_on(gt_engine* e, BuildAdvArgs& ba) const {      // ... or as a rider of the gather launch
+    ba.tv_mask = ride ? mask : (const float*)nullptr; ba.tv_n = N; ba.tv_override = e->norm.override(); ba.sc = e->sc();
+    ba.tv_total = !ride || route == LOCAL ? (double*)nullptr : route == IN_SUMS ? &e->sc()->tv_sum : e->norm.reduced();
+  }
+  int rode(gt_engine* e, hipStream_t s) const {
+    if (ride && route == LOCAL) e->norm.note(mask, N);
+    return ride && route == ALLREDUCE ? e->norm.send(e, s) : GT_OK;      // on the communicator's stream, joined in front of the head
+  }
+  int before_head(gt_engine* e, HeadCall& hc, hipStream_t s) const {
+    LossNormaliser& n = e->norm;
+    hc.unit_tv = route == IN_SUMS;
+    switch (route) {
+      case KNOWN: return GT_OK;
+      case LOCAL: return n.ensure(e, mask, N, s);      // (a no-op behind the rider)
+      case ALLREDUCE:
+        CHK(n.join(e, s));
+        if (!head_reads) return n.file(e, mask, N, n.reduced(), s);
+        hc.tv_dev = n.reduced();      // no conversion launch between the join and the head
+        break;
+      case IN_SUMS: break;      // the normaliser arrives with the sums (finalize_d_kernel on the communicator's stream files it); valid from the join on
+    }
+    n.note(mask, N);
+    return GT_OK;
+  }
+  // what the early results' collective carries: the four loss / count sums, with the count in front of them under IN_SUMS
+  double* early_sums(StepScalars* sc) const { return route == IN_SUMS ? &sc->tv_sum : &sc->s_real; }      int n_early_sums() const { return route == IN_SUMS ? 5 : 4; }
 };
 // What the backend reads: the float32 [x | adv] image, its bf16 image (transposed twin too when want_w), the adversarial columns alone
 // (split), or nothing (an SRU-bf16 discriminator that does not read float32 rows).  The D step writes both halves; the adversarial term
 // writes the generated half (rows N .. 2N of the same buffers) unless the D step of the same batch left it there.
-static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t s) {
+static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's, else null */, hipStream_t s) {
   const long N = p.N;
   const bool both = p.npass == 2;
   const long row0 = both ? 0 : N;
@@ -792,16 +842,13 @@ static int d_pass_input(gt_engine* e, DPass& p, const AdvRiders& r, hipStream_t 
     CHK(e->adv2.ensure((size_t)2 * N * ld * sizeof(float)));
     float* dst = e->adv2.as<float>() + row0 * ld;
     if (both || !e->img_adv2.holds(nullptr, p.fake)) {
-      const bool any_ride = r.tv_ride || r.tv_ride_dp || r.unnorm;
       BuildAdvArgs ba;
       memset(&ba, 0, sizeof(ba));
       ba.fa = p.cat0.fa; ba.fb = p.cat0.fb; ba.ldf = p.ldf; ba.idx = e->d_adv_cols; ba.na = e->Da; ba.out = dst; ba.ldo = ld; ba.split = N; ba.rows = p.rows;
-      ba.tv_mask = any_ride ? r.mask : (const float*)nullptr; ba.tv_n = N; ba.tv_override = e->tv_override; ba.sc = e->sc();
-      ba.tv_total = r.unnorm ? &e->sc()->tv_sum : r.tv_ride_dp ? e->comm_tv.as<double>() : (double*)nullptr;
+      if (tv) tv->ride_on(e, ba);
       launch_build_adv(ba, s);
       LAUNCH_CHECK();
-      if (r.tv_ride) e->tv.note(r.mask, N, e->tv_override);
-      if (r.tv_ride_dp) CHK(comm_tv_sent(e, s));          // all-reduce of the count on the communicator's stream, joined in front of the head
+      if (tv) CHK(tv->rode(e, s));
       e->img_adv2.built(nullptr, p.fake);
     }
     p.fs.adv = dst;
@@ -947,7 +994,7 @@ static int d_pass_penalty(gt_engine* e, DPass& p, const float* mask, hipStream_t
   }
   c.w_last = D.last.W; c.dw_last = D.last.dW;
   c.g = G.g.as<float>(); c.ld_g = ld_g;
-  c.mask = mask; c.inv_tv_dev = &e->sc()->inv_tv;
+  c.mask = mask; c.inv_tv_dev = LossNormaliser::inv_tv(e->sc());
   c.part = G.part.as<double>(); c.part_cap = (long)(G.part.bytes / sizeof(double));
   c.rec = G.rec.as<double>();
   c.dw0s = G.dw0.as<float>();
@@ -958,6 +1005,18 @@ static int d_pass_penalty(gt_engine* e, DPass& p, const float* mask, hipStream_t
 // ------------------------------------------------------------------------------------------
 // update_discriminator
 // ------------------------------------------------------------------------------------------
+// keep dloss_d/dy_hat_static only when y_hat_static is the tensor apply_generator produced (the autograd graph in the reference,
+// train.py:265) and a generator with grads exists
+int KeptLeak::claim(gt_engine* e, const float* y_hat_static, long N, float** out) {
+  const Net& G = e->net[GT_ROLE_G];
+  *out = nullptr;
+  if (!(G.bound && G.d.grads && e->g_pass_valid && y_hat_static == e->last_yhs && e->N == N)) return GT_OK;
+  if (pending) return fail(GT_ERR_STATE, "update_discriminator called twice without optimizer_g.zero_grad() (train.py:538)");
+  CHK(buf.ensure((size_t)N * e->Da * sizeof(float)));
+  *out = buf.as<float>();
+  return GT_OK;
+}
+
 extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const float* y_static, const float* y_hat_static,
                                              const float* mask, int B, int T, int train, float eps, void* stream) {
   CHK(check_common(e, B, T));
@@ -980,54 +1039,29 @@ extern "C" int gt_update_discriminator_begin(gt_engine* e, const float* x, const
   if (e->sn.on && tr && D.grads_dirty)
     return fail(GT_ERR_STATE, "spectral norm: optimizer_d.zero_grad() must precede update_discriminator (the last step's gradient was projected in place)");
   e->ws[GT_ROLE_D].sdefer.reset(rc.early && tr && D.has_opt);
-  // data parallel: the global count travels under the D forward pass.  With the split first layer its local term is summed by a
-  // rider of the gather launch (tv_ride_dp), else by a launch of its own right here.
-  const bool tv_known = e->tv.known(mask, N, e->tv_override);
-  const bool dp_count = comm_early && e->opt_launch_riders && !tv_known && !e->tv_dev && !(e->tv_override > 0.f) && !e->tv_inflight;
-  // GT_OPT_COMM_TV_IN_SUMS: no collective for the count at all -- it leaves with the loss sums (engine_internal.hip.h)
-  const bool unnorm = dp_count && e->opt_comm_tv_in_sums && tr && D.has_opt && D.d.grads;
-  e->d_unnorm = unnorm;
-  const AdvRiders ride = {mask, /* tv_ride */ plain_early && e->opt_launch_riders && !tv_known, /* tv_ride_dp */ dp_count && !unnorm && p.split, unnorm};
-  if (!ride.tv_ride_dp && !unnorm) CHK(ensure_tv_begin(e, mask, N, s));
-  if (unnorm && !p.split) {
-    launch_mask_total(mask, N, &e->sc()->tv_sum, s);
-    LAUNCH_CHECK();
-  }
-  CHK(d_pass_input(e, p, ride, s));
+  const TvPlan tv(e, p, mask, tr && D.has_opt && D.d.grads);
+  e->norm.d_step_begins(tv.route == TvPlan::IN_SUMS);
+  CHK(tv.before_input(e, s));
+  CHK(d_pass_input(e, p, &tv, s));
   CHK(d_pass_forward(e, p, s));
   if (tr && !D.d.grads) return fail(GT_ERR_STATE, "phase == \"train\" but the discriminator was bound without grads");
   HeadCall hc;
   memset(&hc, 0, sizeof(hc));
   hc.mode = HEAD_D_STEP; hc.rows = p.rows; hc.n_real = N; hc.mask = mask; hc.n_mask = N; hc.eps = eps; hc.want_grad = tr; hc.want_w = tr;
   if (plain_early) { hc.early_res = rc.target(); hc.ticket = rc.take_ticket(); }
-  hc.unit_tv = unnorm;
-  if (unnorm) {      // the normaliser arrives with the sums (finalize_d_kernel on the communicator's stream files it); valid from the join on
-    e->tv.note(mask, N, e->tv_override);
-  } else if (comm_on(e) && e->opt_launch_riders && e->tv_inflight && !tv_known) {
-    // data parallel + riders: the head reads the all-reduced count where the collective left it (and files it in the step's scalars):
-    // no conversion launch between the join and the head
-    CHK(comm_tv_join(e, s));
-    hc.tv_dev = e->comm_tv.as<double>();
-    e->tv.note(mask, N, e->tv_override);
-  } else CHK(ensure_tv(e, mask, N, s));
+  CHK(tv.before_head(e, hc, s));
   CHK(d_pass_head(e, p, hc, nullptr, s));
   rc.clear_early();
   if (plain_early) CHK(rc.post_early(s, hc.ticket));
-  if (comm_early) CHK(comm_early_results(e, GT_ROLE_D, unnorm ? &e->sc()->tv_sum : &e->sc()->s_real, unnorm ? 5 : 4, 0.f, 0.f, 0.f, s));
+  if (comm_early) CHK(comm_early_results(e, GT_ROLE_D, tv.early_sums(e->sc()), tv.n_early_sums(), 0.f, 0.f, 0.f, s));
   if (tr) {
     CHK(comm_grads_ready(e, GT_ROLE_D, D.last.dW, (long)D.last.in * D.last.out + D.last.out, s));
-    // keep dloss_d/dy_hat_static only when y_hat_static is the tensor apply_generator produced
-    // (the autograd graph in the reference, train.py:265) and a generator with grads exists
-    Net& G = e->net[GT_ROLE_G];
-    const bool want_leak = G.bound && G.d.grads && e->g_pass_valid && y_hat_static == e->last_yhs && e->N == N;
-    if (want_leak && e->leak_pending)
-      return fail(GT_ERR_STATE, "update_discriminator called twice without optimizer_g.zero_grad() (train.py:538)");
-    float* leak = nullptr;
-    if (want_leak) { CHK(e->leak.ensure((size_t)N * e->Da * sizeof(float))); leak = e->leak.as<float>(); }
+    float* leak;
+    CHK(e->leak.claim(e, y_hat_static, N, &leak));
     CHK(d_pass_backward(e, p, leak, s));
     CHK(d_pass_penalty(e, p, mask, s));      // gt_set_grad_penalty: added before anything closes the step's gradients (sdefer, clip-norm)
     D.grads_dirty = true;
-    if (want_leak) { e->leak_pending = true; e->leak_unnorm = unnorm; }
+    if (leak) e->leak.kept(tv.route == TvPlan::IN_SUMS);
   }
   // data parallel: the rest of D's gradient + the four loss / count sums, then the step stream waits for the communicator
   CHK(comm_finish_step(e, GT_ROLE_D, tr, &e->sc()->s_real, comm_early ? 0 : 4, s));
@@ -1081,7 +1115,7 @@ extern "C" int gt_update_discriminator(gt_engine* e, const float* x, const float
   e->results.early = true;
   int r = gt_update_discriminator_begin(e, x, y_static, y_hat_static, mask, B, T, train, eps, stream);
   e->results.early = false;
-  if (r != GT_OK) { e->results.abandon(); e->d_unnorm = false; return r; }
+  if (r != GT_OK) { e->results.abandon(); e->norm.d_step_begins(false); return r; }
   return gt_update_discriminator_end(e, train, out, stream);
 }
 
@@ -1185,7 +1219,8 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   return GT_OK;
 }
 
-// Which launches of the generator step carry which sums, and how its scalars are reported.  With X = mse_in_backward:
+// Which launches of the generator step carry which sums, and how its scalars are reported (the discriminator side: DPass, and TvPlan for the
+// loss normaliser).  With X = mse_in_backward:
 //   call                               | sums                                                        | report
 //   split-phase, or X                  | own launches (with X the MSE sum comes from the backward)   | at _end
 //   fused, single GPU, riders off      | folded                                                      | early, this stream
@@ -1227,7 +1262,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     return fail(GT_ERR_STATE, "data-parallel step: optimizer_g.zero_grad() must precede update_generator");
   ResultsChannel& rc = e->results;
   e->ws[GT_ROLE_G].sdefer.reset(rc.early && tr && G.has_opt);
-  CHK(ensure_tv(e, mask, N, s));
+  CHK(e->norm.ensure(e, mask, N, s));
   const GPlan plan(e, tr, mse_w);
   const bool riders = plan.sums == GPlan::SUMS_RIDERS;
   CHK(e->partial.ensure(4096 * sizeof(double)));
@@ -1251,9 +1286,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     if (!D.bound) return fail(GT_ERR_STATE, "adv_w > 0 but no discriminator bound");
     DPass p;
     CHK(d_pass_plan(e, x, nullptr, y_hat_static, Ds, 1, B, T, false, &p));
-    AdvRiders none;
-    memset(&none, 0, sizeof(none));
-    CHK(d_pass_input(e, p, none, s));      // the generated half: kept from the D step of the same batch, or built here
+    CHK(d_pass_input(e, p, nullptr, s));      // the generated half: kept from the D step of the same batch, or built here
     CHK(d_pass_forward(e, p, s));
     if (tr) { CHK(e->gadv.ensure((size_t)N * e->Da * sizeof(float))); gadv = e->gadv.as<float>(); }
     HeadCall hc;
@@ -1268,7 +1301,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   int mge_blocks = frame_red_blocks(N * Ds);
   float* gs = nullptr;
   if (tr) { CHK(e->gs.ensure((size_t)N * Ds * sizeof(float))); gs = e->gs.as<float>(); }
-  const float* leak = (tr && e->leak_pending) ? e->leak.as<float>() : nullptr;
+  const float* leak = tr ? e->leak.get() : nullptr;
   GFinalize fin;
   memset(&fin, 0, sizeof(fin));
   const bool reports = riders && plan.report == GPlan::REPORT_EARLY;      // the rider writes results and ticket; else it only files the sums
@@ -1284,7 +1317,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     memset(&q, 0, sizeof(q));
     q.yhs = y_hat_static; q.ld1 = Ds; q.ys = y_static; q.ld2 = Ds; q.mask = mask; q.rows = N; q.Ds = Ds; q.mge_w = mge_w;
     q.adv_inv = e->d_adv_inv; q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
-    q.partial = riders ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak_unnorm ? 1 : 0;
+    q.partial = riders ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak.unnormalised() ? 1 : 0;
     mge_blocks = launch_static_grad(q, s);
   } else      // phase != "train": no gradient to assemble, the finalisation alone
     launch_finalize_g_rider(fin, s);
@@ -1304,7 +1337,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   if (comm_early) CHK(comm_early_results(e, GT_ROLE_G, &e->sc()->s_adv, 3, adv_w, mse_w, mge_w, s));
   if (tr) {
     CHK(generator_backward(e, e->last_x, y, y_hat, mask, mse_w, s));  // G's own input (cat(x, z), train.py:542)
-    e->leak_pending = false; e->leak_unnorm = false;
+    e->leak.drop();
   }
   CHK(comm_finish_step(e, GT_ROLE_G, tr, &e->sc()->s_adv, comm_early ? 0 : 3, s));
   rc.begin_done[GT_ROLE_G] = true;
@@ -1350,17 +1383,17 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   CHK(e->gs.ensure((size_t)N * Ds * sizeof(float)));
   HIPCHK(hipMemsetAsync(e->gs.p, 0, (size_t)N * Ds * sizeof(float), s));
-  if (e->leak_pending) {
+  if (const float* leak = e->leak.get()) {
     // scatter leak[:, j] -> gs[:, adv_cols[j]]  (gather with swapped roles: one column at a time is fine here)
     std::vector<int>& cols = e->h_adv_cols;
     for (int j = 0; j < e->Da; ++j) {
-      launch_copy_cols(e->leak.as<float>(), e->Da, j, e->gs.as<float>(), Ds, cols[j], N, 1, s);
+      launch_copy_cols(leak, e->Da, j, e->gs.as<float>(), Ds, cols[j], N, 1, s);
     }
-    if (e->leak_unnorm) launch_scale_by_inv_tv(e->gs.as<float>(), N * Ds, e->sc(), s);
+    if (e->leak.unnormalised()) launch_scale_by_inv_tv(e->gs.as<float>(), N * Ds, e->sc(), s);
     LAUNCH_CHECK();
   }
   CHK(generator_backward(e, e->last_x, e->last_yhat, e->last_yhat, (const float*)nullptr, 0.f, s));
-  e->leak_pending = false; e->leak_unnorm = false;
+  e->leak.drop();
   HIPCHK(hipStreamSynchronize(s));
   return GT_OK;
 }

@@ -13,7 +13,7 @@
 //
 // Translation units: eng_core (life cycle, binding, options, dropout sites, faults), eng_gemm_f32 / eng_gemm_b16 (dispatch
 // of the two product families; eng_gemm_b16 also holds the stacks' bf16 vocabulary: LinShadow::ensure / shadow_cast, b16_forward / b16_backward_data),
-// eng_step (the G+D step, its ResultsChannel, the MLP stacks and the output layer of every stack: out_layer_forward / out_layer_backward), eng_mlpg
+// eng_step (the G+D step, its ResultsChannel, its plans GPlan / TvPlan -- the latter: how LossNormaliser's count reaches the D head --, the MLP stacks and the output layer of every stack: out_layer_forward / out_layer_backward), eng_mlpg
 // (band cache, MLPG launches), eng_dstack (fused discriminator stack), eng_spectral_norm (spectral normalisation of the MLP discriminator), eng_grad_penalty (its R1 / WGAN-GP gradient penalties), eng_lstm / eng_sru (recurrent stacks of either role), eng_comm / eng_ipc
 // (data-parallel communicator), eng_ops (stand-alone operators).  Kernels live in the *.hip.h headers; the non-template ones have internal linkage
 // (GT_KERNEL) so that several units may include them.
@@ -357,13 +357,65 @@ struct GpState {
   void release() { g.release(); dw0.release(); part.release(); rec.release(); eps.release(); }
 };
 
+// The loss normaliser Tv = sum(mask) (or what the caller gave instead) and 1 / Tv in the step's scalars: the one owner of everything the host
+// knows about them, one method per event.  Which launches put them there in a discriminator step is TvPlan's (eng_step.hip); every other
+// reader calls ensure().  With a communicator the count is the GLOBAL one: losses are normalised by the valid frames of the whole minibatch
+// (train.py:258, seqloss.py:43); start / send hand the local term to the communicator's stream, join makes the step stream wait for it.
+// No "all-reduce in flight" flag is kept: a call that sends also joins before it returns (ensure; TvPlan's ALLREDUCE route), so the flag was
+// false between calls unless one failed midway -- and then the resets on a new batch / zero_grad made the next call count afresh, as every call
+// does now.  The un-joined message of such a failed call stays ordered on the communicator's stream in front of the next one.
+struct LossNormaliser {
+  float override() const { return ovr; }                      // gt_set_loss_normalizer: > 0 wins over the mask's sum
+  const double* total_dev() const { return dev; }             // gt_set_loss_normalizer_device: the caller's global count, read in stream order
+  bool given() const { return dev || ovr > 0.f; }             // the caller's: no collective of the engine's own
+  double* reduced() const { return total.as<double>(); }      // the all-reduced count (local term before send, global after join)
+  bool known(const float* m, long N) const { return mask == m && n == N && memo_ovr == ovr; }      // the scalars hold the normaliser of this mask already
+  void note(const float* m, long N) { mask = m; n = N; memo_ovr = ovr; }
+  // forget: a new batch (gt_apply_generator), gt_zero_grad, another device total -- the mask's contents may have changed.  overwritten: the MLPG
+  // hook's masked-MSE gradient put another mask's normaliser into the scalars (with no in-flight flag, all there is to clear is the memo).
+  void forget() { mask = nullptr; }      void overwritten() { forget(); }
+  void set_override(float tv) { ovr = tv; dev = nullptr; }      // (the memo is keyed on the override: nothing to forget)
+  void set_total_dev(const double* p) { dev = p; forget(); }    // re-read on the next step function
+  int attach() { return total.ensure(64); }      void release() { total.release(); }      // gt_comm_init, gt_engine_destroy
+  int start(gt_engine* e, const float* m, long N, hipStream_t s);      // the local count by a launch of its own, then send
+  int send(gt_engine* e, hipStream_t s);                               // all-reduce of reduced() on the communicator's stream, behind what `s` holds
+  int join(gt_engine* e, hipStream_t s);
+  int file(gt_engine* e, const float* m, long N, const double* from, hipStream_t s);      // override / *from / sum(mask) -> the scalars, by a launch; noted
+  int ensure(gt_engine* e, const float* m, long N, hipStream_t s);     // once per (step, mask): no-op when known
+  // GT_OPT_COMM_TV_IN_SUMS: D's gradient of the running step is that of the UNNORMALISED loss.  Set by every D step's _begin, read by the early
+  // finalisation, taken (and cleared) by the optimizer step as the update kernel's gradient scale.
+  void d_step_begins(bool unnormalised) { d_unnorm = unnormalised; }
+  bool d_unnormalised() const { return d_unnorm; }
+  const float* take_d_scale(StepScalars* sc) { const bool u = d_unnorm; d_unnorm = false; return u ? &sc->inv_tv : (const float*)nullptr; }
+  static const float* inv_tv(StepScalars* sc) { return &sc->inv_tv; }      // 1 / Tv on the device, for launches that read it there
+ private:
+  float ovr = -1.f; const double* dev = nullptr;
+  const float* mask = nullptr; long n = 0; float memo_ovr = 0.f;      // the memo: of which mask, over how many frames, under which override
+  Scratch total; bool d_unnorm = false;                                // total: device double, the communicator's message
+};
+
+// dloss_d/dy_hat_static of the D step, kept for the generator step's gradient assembly (the reference's un-detached "leak", train.py:265,274).
+// unnorm: it is that of the unnormalised loss (GT_OPT_COMM_TV_IN_SUMS): x 1 / Tv where it is consumed.
+struct KeptLeak {
+  // D step: *out = where the backward pass leaves it, or null when this step keeps none (eng_step.hip); refuses a second one before zero_grad
+  int claim(gt_engine* e, const float* y_hat_static, long N, float** out);
+  void kept(bool unnormalised) { pending = true; unnorm = unnormalised; }
+  const float* get() const { return pending ? buf.as<float>() : (const float*)nullptr; }      // null: none pending
+  bool unnormalised() const { return pending && unnorm; }
+  // gt_zero_grad(G); consumed by the G step / gt_flush_generator_grads; no longer the gradient of what the next G step runs (storage form,
+  // objective, spectral norm, a recycled band, gt_clear_faults)
+  void drop() { pending = unnorm = false; }      void release() { buf.release(); }
+ private:
+  Scratch buf; bool pending = false, unnorm = false;
+};
+
 struct gt_engine {
   gt_stream_config cfg;
   Net net[2];
   uint64_t seed = 0x5DEECE66DULL;
   uint64_t step_counter = 0;
-  float tv_override = -1.f;
-  const double* tv_dev = nullptr;   // device-resident global normaliser (data parallel: no host round trip)
+  LossNormaliser norm;
+  KeptLeak leak;
   // derived stream maps (device)
   int Dout_cfg = 0, Ds = 0, Da = 0;
   std::vector<int> h_scol, h_sstride, h_adv_cols, h_adv_inv;
@@ -373,14 +425,14 @@ struct gt_engine {
   MlpgCache mlpg;
   Scratch mlpg_var_ws;                     // variance-weighted MLPG: refusal flag, lengths, then L and z of one group of sequences (float64)
   NetWs ws[2];                             // workspace: per role, then (below) what one call uses and both roles share
-  Scratch dcat, dzA, dzB, leak, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
+  Scratch dcat, dzA, dzB, gadv, gs, gy, slabs, colp, partial, headp, headw, dmask, tx, gx, dgx, dtz, dout;
   Scratch scal;                            // StepScalars + StepResults
   ResultsChannel results;                  // how the step's scalars reach the host
   EpochLedger ledger;                      // gt_ledger_*: the loop's running sums, added on the device behind each step
   // per-step state
   int B = 0, T = 0; long N = 0;
   const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;
-  bool g_pass_valid = false, leak_pending = false;
+  bool g_pass_valid = false;
   const MlpgBand* g_band = nullptr;        // the band the stashed generator pass went through (null: R is None); the cache never recycles it while g_pass_valid
   // "the generated half of this image of D's input is built", and from which x / y_hat_static: the generator step's adversarial term
   // reuses what the D step of the same batch left behind.  One record per image kind; all dropped by invalidate_d_images().
@@ -391,11 +443,6 @@ struct gt_engine {
   };
   DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
   bool g_has_adv = false;
-  struct TvMemo {      // sum(mask) is already on the device for this step: of which mask, over how many frames, under which override
-    const float* mask = nullptr; long n = 0; float ovr = 0.f;
-    bool known(const float* m, long N, float o) const { return mask == m && n == N && ovr == o; }
-    void note(const float* m, long N, float o) { mask = m; n = N; ovr = o; }      void forget() { mask = nullptr; }
-  } tv;
   Scratch i2o_gout, d_dx0;                         // In2OutRNNHighwayNet: hidden2out output G(x); a recurrent DISCRIMINATOR (train.py:773-774 allows any model class): gradient w.r.t. its [x | adv] input
   Scratch l_state, l_xch, s_du, s_dx, s_dbias;     // recurrent layer in hand (either role): LSTM per-step kernels' state, persistent kernels' exchange granules; SRU backward temporaries
   struct GtComm* comm = nullptr;                   // gt_comm_init: RCCL communicator + comm stream (data parallel)
@@ -406,8 +453,6 @@ struct gt_engine {
   int chk_B = 0, chk_T = 0;                        // (B, T) of the entry point that is running (check_common)
   std::vector<std::pair<long, long>> comm_done[2]; // per role: gradient ranges (offset, count) already handed to RCCL this step
   std::vector<std::pair<long, long>> comm_pending[2];   // final on the step stream, not handed over yet (merged into few messages)
-  Scratch comm_tv;                                 // device double: global valid-frame count
-  bool tv_inflight = false;                        // its all-reduce has been issued for the current mask
   // GT_OPT_MATMUL_BF16 on MLP stacks: bf16 images (both orientations) of everything that only feeds products
   B16Img xin_b, dcat_b, gy_b, dz_b[2], fwd_b;      // G's input, D's [x | adv] image (2N rows), dloss/dy_hat, dZ ping-pong, gt_model_forward's input
   Scratch d_pre;                                   // split first layer of the conditioned D: P = x . W[:, :cd]^T + b  (eng_step.hip: FirstSplit)
@@ -425,9 +470,9 @@ struct gt_engine {
   // GT_OPT_COMM_TV_IN_SUMS: the data-parallel D step does not all-reduce the valid-frame count ahead of the head; the head seeds the
   // backward pass of the UNNORMALISED loss, the local count leaves with the four loss / count sums (one message instead of two), and
   // 1 / Tv is applied where the gradient is consumed: by the optimizer kernel (which writes the normalised, clipped gradient back) and
-  // by the generator step's gradient assembly for the kept dloss_d/dy_hat_static.  d_unnorm / leak_unnorm: in that state right now.
+  // by the generator step's gradient assembly for the kept dloss_d/dy_hat_static.  In that state right now: LossNormaliser::d_unnormalised,
+  // KeptLeak::unnormalised.
   bool opt_comm_tv_in_sums = env_flag("GT_COMM_TV_IN_SUMS", true);
-  bool d_unnorm = false, leak_unnorm = false;
   bool opt_poll_results = env_flag("GT_POLL_RESULTS", true);      // GT_OPT_POLL_RESULTS (ResultsChannel::take_ticket): round 4: no gain (1.380 / 1.384 vs 1.381 / 1.375 ms); round 5, the step 60 us shorter: 1.3125 / 1.312 vs
                                                                   // 1.319 / 1.315 / 1.3175 / 1.3206 ms, b = 4 0.400 vs 0.406 -- the two 5.8 us holes behind the finalising launches now show
   bool opt_launch_riders = env_flag("GT_LAUNCH_RIDERS", true);     // GT_OPT_LAUNCH_RIDERS: small reductions as extra workgroups of neighbouring launches
@@ -672,16 +717,13 @@ struct GtComm {
 bool comm_on(const gt_engine* e);
 int comm_grads_ready(gt_engine* e, int role, const float* lo, long count, hipStream_t compute);
 int comm_flush(gt_engine* e, int role, hipStream_t compute, bool closing = false);
-int comm_tv_sent(gt_engine* e, hipStream_t s);
 // eng_ipc.hip
 void ipc_destroy(gt_engine* e);
 bool ipc_usable(const gt_engine* e, size_t bytes);
 int ipc_allreduce(gt_engine* e, void* buf, size_t count, bool dtype_double, hipStream_t s);
-int comm_tv_join(gt_engine* e, hipStream_t s);
 int comm_finish_step(gt_engine* e, int role, bool grads, double* sums, int n_sums, hipStream_t compute);
 int comm_early_results(gt_engine* e, int role, double* sums, int n_sums, float adv_w, float mse_w, float mge_w, hipStream_t compute);
-int ensure_tv_begin(gt_engine* e, const float* mask, long N, hipStream_t s);
-int ensure_tv(gt_engine* e, const float* mask, long N, hipStream_t s);
+// (LossNormaliser::start / send / join / file / ensure are defined there too, next to the collectives they use)
 // (the data-parallel schedule switches are per-engine state: gt_engine::opt_comm_*)
 
 // ------------------------------------------------------------------------------------------

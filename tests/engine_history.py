@@ -51,7 +51,7 @@ def _case_tables():
 
 
 OPTION_VALUES = {"split_first_layer": (0, 1), "fused_dstack": (0, 1, 2), "matmul_bf16": (0, 1), "lstm_persistent": (0, 1), "sru_d_bf16": (0, 1),
-                 "launch_riders": (0, 1)}
+                 "launch_riders": (0, 1), "comm_tv_in_sums": (0, 1)}
 _RIDERS = ("launch_riders", 1, 0)
 BACKENDS = {
     "mlp_philox": dict(case=("CASES", "acoustic_mlp_dropout"), options={}, flip=_RIDERS),
@@ -77,13 +77,25 @@ HISTORIES_FEW = ("phase_and_roles", "abandoned_passes", "other_d", "shard_and_no
 BACKENDS_FEW = ("mlp_cond_split", "lstm_d", "sru_g")
 # every (backend, history) pair applies: no NaN poison had to become +-3e38, no pair is left out
 PAIRS = [(b, h) for b in BACKENDS for h in HISTORIES_ALL] + [(b, h) for b in BACKENDS_FEW for h in HISTORIES_FEW]
+# Communicating engines: Session.__init__ attaches a one-rank communicator (comm: True), so every step takes the data-parallel routes of the
+# valid-frame count -- with the loss sums (comm_tv_in_sums, the default; the flip's other value all-reduces it ahead of the head), its local
+# term a rider of the adversarial-column gather (split first layer) or a launch of its own (no split).  A table and a pair list of their own:
+# the full cross product stays what it is.
+COMM_BACKENDS = {
+    "comm_cond_split": dict(case=("CASES", "acoustic_chain_d"), options={}, flip=("comm_tv_in_sums", 1, 0), comm=True),
+    # (this case's discriminator is conditioned too and would split by default: the option is what makes the count a launch of its own)
+    "comm_philox": dict(case=("CASES", "acoustic_mlp_dropout"), options={"split_first_layer": 0}, flip=("comm_tv_in_sums", 1, 0), comm=True),
+}
+HISTORIES_COMM = ("same_shape_refill", "shrink", "poison_train_restore", "option_flip", "split_phase")
+COMM_PAIRS = [(b, h) for b in COMM_BACKENDS for h in HISTORIES_COMM]
+ALL_BACKENDS = dict(BACKENDS, **COMM_BACKENDS)
 # the second discriminator of `other_d`: another kind and width, the same in_dim
 OTHER_D = {"MLP": dict(kind="LSTMRNN", out_dim=1, num_hidden=1, hidden_dim=20, bidirectional=True, dropout=0.0, last_sigmoid=True),
            "LSTMRNN": dict(kind="MLP", out_dim=1, num_hidden=2, hidden_dim=24, dropout=0.0, last_sigmoid=True)}
 
 
 def backend_case(backend):
-    table, name = BACKENDS[backend]["case"]
+    table, name = ALL_BACKENDS[backend]["case"]
     return _case_tables()[table][name]
 
 
@@ -134,7 +146,7 @@ _BATCHES = {}
 
 def make_batch(backend, B, T, seed, poison=False):
     """dict(B, T, x, y, lengths) of cases.make_batch for the backend's case at (B, T); poison: x and y are NaN at every valid frame."""
-    key = (BACKENDS[backend]["case"], B, T, seed, poison)
+    key = (ALL_BACKENDS[backend]["case"], B, T, seed, poison)
     if key not in _BATCHES:
         x, y, lengths = C.make_batch(dict(backend_case(backend), B=B, T=T), seed=seed)
         if poison:
@@ -199,9 +211,12 @@ class Session(object):
             self.restore(snapshot)
         self.train_mode()
         self.engine = engine_for(self.hp, self.mg)
-        self.options = dict(BACKENDS[backend]["options"], **(options or {}))
+        self.options = dict(ALL_BACKENDS[backend]["options"], **(options or {}))
         for k, v in self.options.items():
             self.engine.set_option(k, v)
+        if ALL_BACKENDS[backend].get("comm"):      # as hip_runner.run_hip_case(comm_world_1=True); one rank's collectives are issued, not skipped
+            self.engine.set_option("comm_force", 1)
+            self.engine.comm_init(0, 1, self.engine.comm_unique_id())
         self._keep = []
         if policy == "inplace":
             n, b = max(B * T for B, T in shapes), max(B for B, _ in shapes)
@@ -393,7 +408,7 @@ def _h_poison_train_restore(s):
 
 
 def _h_option_flip(s):
-    name, home, away = BACKENDS[s.backend]["flip"]
+    name, home, away = ALL_BACKENDS[s.backend]["flip"]
     s.set_option(name, away)
     s.step(shape_batch(s.backend, "BIG", 5701), "train")
     s.set_option(name, home)

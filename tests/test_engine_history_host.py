@@ -129,6 +129,20 @@ def test_every_pair_of_the_tables_is_present_once():
         assert H.OTHER_D[H.backend_case(b)["d"]["kind"]]["kind"] != H.backend_case(b)["d"]["kind"]
 
 
+def test_the_communicating_backends_have_a_table_and_a_pair_list_of_their_own():
+    assert sorted(H.COMM_BACKENDS) == ["comm_cond_split", "comm_philox"] and not set(H.COMM_BACKENDS) & set(H.BACKENDS)
+    assert H.COMM_BACKENDS["comm_cond_split"]["case"] == H.BACKENDS["mlp_cond_split"]["case"]       # split first layer: the count rides the gather
+    assert H.COMM_BACKENDS["comm_philox"]["case"] == H.BACKENDS["mlp_philox"]["case"]               # split switched off: a launch of its own
+    assert H.backend_case("comm_cond_split")["cond"] and not H.COMM_BACKENDS["comm_cond_split"]["options"]
+    assert H.backend_case("comm_philox")["cond"] and H.COMM_BACKENDS["comm_philox"]["options"] == {"split_first_layer": 0}
+    for name, b in H.COMM_BACKENDS.items():
+        assert b["comm"] and b["flip"] == ("comm_tv_in_sums", 1, 0), name
+        assert all(v in H.OPTION_VALUES["comm_tv_in_sums"] for v in b["flip"][1:])
+    assert H.HISTORIES_COMM == ("same_shape_refill", "shrink", "poison_train_restore", "option_flip", "split_phase")
+    assert len(H.COMM_PAIRS) == len(set(H.COMM_PAIRS)) == 10 and not set(H.COMM_PAIRS) & set(H.PAIRS)
+    assert set(h for _, h in H.COMM_PAIRS) <= set(H.HISTORIES) and not any(b.get("comm") for b in H.BACKENDS.values())
+
+
 def test_batches_are_cached_per_shape_and_poison_covers_the_valid_frames():
     a, b = H.shape_batch("mlp_cond_split", "BIG", 1), H.shape_batch("mlp_cond_split", "BIG", 1)
     assert a is b and not a["x"].flags.writeable

@@ -3,10 +3,11 @@ comparator; DESIGN.md "Engine state across steps" the contract).
 
 Every other GPU test runs on an engine created for its case.  A training run keeps one engine for hours: batches of many (B, T) from
 staging buffers refilled in place, train and eval phases, re-seeds, re-binds.  What decides correctness there is the engine's host-side
-state -- pointer-keyed memos (StepCopy, DImage, TvMemo, the MLPG band cache), per-step flags, the lengths ring, grow-only workspaces whose
+state -- pointer-keyed memos (StepCopy, DImage, LossNormaliser's, the MLPG band cache), per-step flags, the lengths ring, grow-only workspaces whose
 pads and tails keep another batch's data.  One test per (backend, history): the worn session runs the history, then both it and its twin
 (new objects and a new engine, loaded from the worn session's snapshot, exact-size new buffers) run the probe -- set_seed, two train steps
-and one eval-phase step at (3, 19) -- and everything the probe returns or leaves behind must be the same bits and finite.
+and one eval-phase step at (3, 19) -- and everything the probe returns or leaves behind must be the same bits and finite.  The
+COMM_PAIRS run the same on engines that carry a one-rank communicator: the forgetting rules of the data-parallel valid-frame count.
 
 On the commit before this module 13 pairs failed: same_shape_refill on the seven backends that make a 16-byte-pitch copy of a dense x
 (gt_set_seed restarts the step count while the per-step copies of x stayed keyed on it), poison_train_restore on the six Adam backends
@@ -19,7 +20,7 @@ import engine_history as H
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("backend,history", H.PAIRS, ids=["%s-%s" % p for p in H.PAIRS])
+@pytest.mark.parametrize("backend,history", H.PAIRS + H.COMM_PAIRS, ids=["%s-%s" % p for p in H.PAIRS + H.COMM_PAIRS])
 def test_used_engine_equals_fresh_engine(backend, history):
     worn, twin = H.run_pair(backend, history)
     assert len(worn) > 20 and any(k.startswith("step2.") for k in worn) and "philox_d" in worn

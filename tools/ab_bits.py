@@ -2,7 +2,8 @@
     python tools/ab_bits.py dump out.npz [case] [key=value ...]   # with GT_HIP_LIB selecting the build
     python tools/ab_bits.py cmp a.npz b.npz
 `case` is a name from cases.CASES or cases.ORACLE_ONLY_CASES (default acoustic_mlp); every key=value is an engine option handed to
-run_hip_case(engine_options=...), e.g. fused_dstack=2 split_first_layer=0.  One dump per process."""
+run_hip_case(engine_options=...), e.g. fused_dstack=2 split_first_layer=0; comm=1 is no engine option: it attaches a one-rank communicator
+(run_hip_case(comm_world_1=True)) and switches its collectives on.  One dump per process."""
 import os
 import sys
 
@@ -19,7 +20,10 @@ if sys.argv[1] == "dump":
     name = rest.pop(0) if rest and "=" not in rest[0] else "acoustic_mlp"
     case = C.CASES[name] if name in C.CASES else C.ORACLE_ONLY_CASES[name]
     options = {k: int(v) for k, v in (kv.split("=", 1) for kv in rest)}
-    got = run_hip_case(case, engine_options=options or None)
+    comm = bool(options.pop("comm", 0))
+    if comm:      # a one-rank communicator whose collectives are issued: the data-parallel schedule
+        options.setdefault("comm_force", 1)
+    got = run_hip_case(case, engine_options=options or None, comm_world_1=comm)
     np.savez(sys.argv[2], **{k: np.asarray(v) for k, v in got.items()})
 else:
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])
