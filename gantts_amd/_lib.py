@@ -273,6 +273,10 @@ SIGNATURES = {
     "gt_set_loss_normalizer_device": (_I, [_P, _P]),
     "gt_set_option": (_I, [_P, _I, _I]),
     "gt_set_weight_clip": (_I, [_P, _I, _F]),
+    "gt_set_param_ema": (_I, [_P, _I, _P, _L, C.c_double]),
+    "gt_set_param_ema_count": (_I, [_P, _I, _L]),
+    "gt_get_param_ema_count": (_I, [_P, _I, C.POINTER(_L)]),
+    "gt_op_optim_step_ema": (_I, [C.POINTER(OptimDescEx), _P, _P, _L, _P, C.POINTER(_F), _P, _L, C.c_double, _P]),
     "gt_set_spectral_norm": (_I, [_P, _I, _P, _P, _L, _L]),
     "gt_op_spectral_norm": (_I, [C.POINTER(SnCase), _P]),
     "gt_op_sn_project": (_I, [C.POINTER(SnCase), _P]),

@@ -55,6 +55,7 @@ extern "C" int gt_profile_read(double* out_ms, double* out_flops, int64_t* out_c
     if (r.kind == 5) v = 8;                                   // pair launch
     else if (r.kind == 6) v = 12;                             // weight-gradient pair of a split first layer
     else if (r.kind == 7) v = 14;                             // fused discriminator stack (dstack_f32.hip.h)
+    else if (r.kind == 8) v = 15;                             // fused clip + update launch (launch_optim_step)
     else if (r.kind == GEMM_NT && r.am == GEMM_A_NONE) v = 6;
     else if (r.kind == GEMM_NT && r.am == GEMM_A_LEAKY_PHILOX) v = 7;
     else if (r.kind == GEMM_NT && r.am == GEMM_A_LEAKY_PHILOX_ADDM) v = 9;
@@ -209,6 +210,43 @@ extern "C" int gt_set_weight_clip(gt_engine* e, int role, float c) {
   if (role != GT_ROLE_D) return fail(GT_ERR_INVALID, "gt_set_weight_clip: role %d -- weight clipping is the discriminator's (role 1) alone", role);
   if (!(c >= 0.f) || !(c <= 3.402823466e+38f)) return fail(GT_ERR_INVALID, "gt_set_weight_clip: c = %g -- 0 (off) or a positive finite bound", (double)c);
   e->weight_clip[role] = c;
+  return GT_OK;
+}
+// gt_set_param_ema against the bound generator: at the call when a generator is bound, and at the entry of every training generator step,
+// before any launch (a generator bound later, or another one)
+int check_param_ema(const gt_engine* e) {
+  const Net& G = e->net[GT_ROLE_G];
+  if (e->ema.buf && G.bound && e->ema.n != (long)G.d.n_params)
+    return fail(GT_ERR_INVALID, "gt_set_param_ema: n = %ld -- the bound generator has %ld parameters", e->ema.n, (long)G.d.n_params);
+  return GT_OK;
+}
+extern "C" int gt_set_param_ema(gt_engine* e, int role, float* ema, int64_t n, double decay) {
+  if (!e) return fail(GT_ERR_INVALID, "null engine");
+  if (role != GT_ROLE_G) return fail(GT_ERR_INVALID, "gt_set_param_ema: role %d -- the weight average is the generator's (role 0) alone", role);
+  if (!ema) {
+    if (!(decay == 0.0)) return fail(GT_ERR_INVALID, "gt_set_param_ema: ema is null (off) but decay = %g -- pass 0 with it, or a buffer", decay);
+    e->ema = gt_engine::ParamEma();
+    return GT_OK;
+  }
+  CHK(param_ema_check_decay("gt_set_param_ema", decay));
+  if (n < 1) return fail(GT_ERR_INVALID, "gt_set_param_ema: n = %lld -- the generator's parameter count", (long long)n);
+  const gt_engine::ParamEma was = e->ema;
+  e->ema.buf = ema; e->ema.n = (long)n; e->ema.decay = decay;      // (the count stays: a moved buffer is the same average)
+  const int r = check_param_ema(e);
+  if (r != GT_OK) e->ema = was;
+  return r;
+}
+extern "C" int gt_set_param_ema_count(gt_engine* e, int role, int64_t n_averaged) {
+  if (!e) return fail(GT_ERR_INVALID, "null engine");
+  if (role != GT_ROLE_G) return fail(GT_ERR_INVALID, "gt_set_param_ema_count: role %d -- the weight average is the generator's (role 0) alone", role);
+  if (n_averaged < 0) return fail(GT_ERR_INVALID, "gt_set_param_ema_count: n_averaged = %lld -- the updates already averaged, >= 0", (long long)n_averaged);
+  e->ema.count = (long)n_averaged;
+  return GT_OK;
+}
+extern "C" int gt_get_param_ema_count(gt_engine* e, int role, int64_t* n_averaged) {
+  if (!e || !n_averaged) return fail(GT_ERR_INVALID, "bad argument");
+  if (role != GT_ROLE_G) return fail(GT_ERR_INVALID, "gt_get_param_ema_count: role %d -- the weight average is the generator's (role 0) alone", role);
+  *n_averaged = e->ema.count;
   return GT_OK;
 }
 
@@ -604,6 +642,8 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
     // every update since the bind was skipped: SGD's momentum_buffer is as live as the bind said, not more
     if (e->h_fault[2 + r] && n.step <= n.bound_step) n.buf_live = (n.od.flags & GT_OPTF_BUFFER_LIVE) != 0;
   }
+  // the skipped generator updates left the weight average untouched as well (they returned before any element)
+  if (e->ema.buf) e->ema.count = std::max(0L, e->ema.count - (long)e->h_fault[2 + GT_ROLE_G]);
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
   invalidate_d_images(e);
   e->g_pass_valid = false; e->leak.drop(); e->cx_dense.forget(); e->results.reset();

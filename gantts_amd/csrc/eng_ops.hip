@@ -976,9 +976,11 @@ static int optim_check_tail(const gt_optim_desc_ex* od) {
 // reads and writes.
 typedef void (*OptimKernel)(float*, float*, float*, float*, float*, long, const double*, int, double*, OptimSpec, const unsigned int*,
                             unsigned int*, unsigned int*, const float*);
-struct OptimVariant { int kind; unsigned flags; bool s0, s1, s2; OptimKernel kernel; };
+// kernel_ema: the same pair with the weight-average rider (gt_set_param_ema) compiled in -- a second column, not a second set of rows
+struct OptimVariant { int kind; unsigned flags; bool s0, s1, s2; OptimKernel kernel, kernel_ema; };
 #define OPTIM_ROW(KIND, F) \
-  {KIND, (F), OptimStreams<KIND, (F)>::s0, OptimStreams<KIND, (F)>::s1, OptimStreams<KIND, (F)>::s2, optim_step_kernel<KIND, (F)>}
+  {KIND, (F), OptimStreams<KIND, (F)>::s0, OptimStreams<KIND, (F)>::s1, OptimStreams<KIND, (F)>::s2, optim_step_kernel<KIND, (F)>, \
+   optim_step_kernel<KIND, (F), true>}
 static const OptimVariant OPTIM_VARIANTS[] = {
   OPTIM_ROW(OPTK_ADAGRAD, OPTI_ORIGINAL),
   OPTIM_ROW(OPTK_ADAM, OPTI_ORIGINAL), OPTIM_ROW(OPTK_ADAM, OPTI_AMSGRAD),
@@ -1132,16 +1134,28 @@ static OptimSpec optim_spec(const gt_optim_desc_ex& od, long step, bool buf_live
 
 int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
                       const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
-                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip) {
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip, float* ema, float ema_w,
+                      bool ema_first) {
   const dim3 grid((unsigned)std::min<long>(1024, cdiv(n, RED_THREADS))), block(RED_THREADS);
   unsigned step_flags = 0u;
   OptimSpec o = optim_spec(od, step, buf_live, cache, &step_flags);
   o.wclip = weight_clip;      // gt_set_weight_clip: the updated parameters are clamped to [-c, c] in the same launch (0: stored as computed)
+  o.ema = ema; o.ema_w = ema_w; o.ema_first = ema_first ? 1 : 0;      // gt_set_param_ema: the average of the stored parameters, same launch (null: none)
   const OptimVariant* v = optim_variant(od.kind, optim_flags(od, step_flags));
   if (!v) return fail(GT_ERR_INVALID, "unknown optimizer kind %d", od.kind);
-  hipLaunchKernelGGL(v->kernel, grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, n_partial, norm2_out, o,
+  // gt_profile_enable(2 + 8): this launch between two events (slot 15).  Only when selected by its kind, never under "every product launch"
+  GemmProfiler::Rec rec;
+  const bool prof = g_prof.on && g_prof.only_kind == 8;
+  if (prof) {
+    rec.kind = 8; rec.bn = 0; rec.am = -1; rec.flops = 0.0;
+    rec.bytes = (double)n * (16.0 + 8.0 * ((v->s0 ? 1 : 0) + (v->s1 ? 1 : 0) + (v->s2 ? 1 : 0)) + (ema ? 8.0 : 0.0));
+    rec.e0 = g_prof.get(); rec.e1 = g_prof.get();
+    HIPCHK(hipEventRecord(rec.e0, s));
+  }
+  hipLaunchKernelGGL(ema ? v->kernel_ema : v->kernel, grid, block, 0, s, params, grads, od.state0, od.state1, od.state2, n, part, n_partial, norm2_out, o,
                      fault_dev, fault_host, skipped_host, gscale);
   LAUNCH_CHECK();
+  if (prof) { HIPCHK(hipEventRecord(rec.e1, s)); g_prof.recs.push_back(rec); }
   return GT_OK;
 }
 
@@ -1158,8 +1172,14 @@ extern "C" int gt_op_optim_scalars(const gt_optim_desc_ex* desc, int64_t t, doub
   return GT_OK;
 }
 
-extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
-                                float* grad_norm_out, void* stream) {
+// gt_set_param_ema / gt_op_optim_step_ema: the decay is a number in [0, 1] (written so that a NaN fails)
+int param_ema_check_decay(const char* who, double decay) {
+  if (!(decay >= 0.0 && decay <= 1.0)) return fail(GT_ERR_INVALID, "%s: decay = %g -- a number in [0, 1]", who, decay);
+  return GT_OK;
+}
+
+static int op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale, float* grad_norm_out,
+                         float* ema, bool ema_first, double decay, void* stream) {
   if (!desc || !params || !grads || n < 1) return fail(GT_ERR_INVALID, "bad argument");
   CHK(optim_check_desc(desc));
   hipStream_t s = (hipStream_t)stream;
@@ -1175,7 +1195,7 @@ extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, flo
   LAUNCH_CHECK();
   CHK(launch_optim_step(od, (long)desc->step + 1, (desc->flags & GT_OPTF_BUFFER_LIVE) != 0, (OptimScalarCache*)nullptr, params, grads, (long)n, part, nblk,
                         grad_norm_out ? part + 512 : (double*)nullptr, (const unsigned int*)nullptr, (unsigned int*)nullptr,
-                        (unsigned int*)nullptr, gscale, s));
+                        (unsigned int*)nullptr, gscale, s, 0.f, ema, param_ema_weight(decay), ema_first));
   if (grad_norm_out) {
     double norm2 = 0.0;
     HIPCHK(hipMemcpyAsync(&norm2, part + 512, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1183,6 +1203,17 @@ extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, flo
     *grad_norm_out = (float)sqrt(norm2);
   }
   return GT_OK;
+}
+extern "C" int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
+                                float* grad_norm_out, void* stream) {
+  return op_optim_step(desc, params, grads, n, gscale, grad_norm_out, (float*)nullptr, false, 0.0, stream);
+}
+extern "C" int gt_op_optim_step_ema(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
+                                    float* grad_norm_out, float* ema, int64_t n_averaged, double decay, void* stream) {
+  if (!ema) return fail(GT_ERR_INVALID, "gt_op_optim_step_ema: ema is null");
+  if (n_averaged < 0) return fail(GT_ERR_INVALID, "gt_op_optim_step_ema: n_averaged = %lld -- the updates already averaged, >= 0", (long long)n_averaged);
+  CHK(param_ema_check_decay("gt_op_optim_step_ema", decay));
+  return op_optim_step(desc, params, grads, n, gscale, grad_norm_out, ema, n_averaged == 0, decay, stream);
 }
 
 // ------------------------------------------------------------------------------------------

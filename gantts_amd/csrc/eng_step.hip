@@ -647,8 +647,12 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
     LAUNCH_CHECK();
   }
   n.step += 1;
+  // gt_set_param_ema: the generator's weight average rides this launch; its first applied update copies, every later one is a lerp
+  float* ema = role == GT_ROLE_G ? e->ema.buf : (float*)nullptr;
   CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
-                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s, e->weight_clip[role]));
+                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s, e->weight_clip[role], ema,
+                        param_ema_weight(e->ema.decay), e->ema.count == 0));
+  if (ema) e->ema.count += 1;
   n.buf_live = true;
   return GT_OK;
 }
@@ -1248,6 +1252,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   if (!G.bound) return fail(GT_ERR_STATE, "generator not bound");
   if (!y || !y_hat || !y_static || !y_hat_static || !mask) return fail(GT_ERR_INVALID, "null tensor");
   if (adv_w > 0.f) CHK(check_gan_objective(e));
+  if (train) CHK(check_param_ema(e));
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
   const bool tr = train != 0;

@@ -501,6 +501,9 @@ struct gt_engine {
   bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);      // GT_OPT_SRU_D_BF16: an SRU discriminator's products through the bf16-storage family
   int gan_objective = 0;                           // GT_OPT_GAN_OBJECTIVE: the head's adversarial objective (gan_objective.hip.h), 0 = the reference's sigmoid + log loss
   float weight_clip[2] = {0.f, 0.f};               // gt_set_weight_clip (role D only): every optimizer step clamps the updated parameters to [-c, c]; 0 = off
+  // gt_set_param_ema (role G only): the caller's running average of the generator's parameters, its length, the decay, and the updates
+  // applied to it (torch's n_averaged: counted where Net::step is, skipped steps taken back out by gt_clear_faults); buf null = off
+  struct ParamEma { float* buf = nullptr; long n = 0; double decay = 0.0; long count = 0; } ema;
   SnState sn;                                      // gt_set_spectral_norm (role D, MLP only): Lin::W of the discriminator then points into sn.weff
   GpState gp;                                      // gt_set_grad_penalty (role D, MLP only): one more stage of the D step (d_pass_penalty)
   std::vector<int> h_lengths;
@@ -521,7 +524,13 @@ int optim_check_desc(const gt_optim_desc_ex* od);
 void optim_desc_copy(const gt_optim_desc_ex* in, gt_optim_desc_ex* out);      // head only for the first family's kinds
 int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, OptimScalarCache* cache, float* params, float* grads, long n,
                       const double* part, int n_partial, double* norm2_out, const unsigned int* fault_dev, unsigned int* fault_host,
-                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip = 0.f);
+                      unsigned int* skipped_host, const float* gscale, hipStream_t s, float weight_clip = 0.f, float* ema = nullptr,
+                      float ema_w = 0.f, bool ema_first = false);
+// the weight average of gt_set_param_ema: its decay's check (`who` names the entry point in the message), the lerp weight float32(1.0 - decay)
+// -- the subtraction in double, rounded once, as python forms it for Tensor.lerp_ --, and the setting against the bound generator
+int param_ema_check_decay(const char* who, double decay);
+static inline float param_ema_weight(double decay) { return (float)(1.0 - decay); }
+int check_param_ema(const gt_engine* e);
 // GT_OPT_GAN_OBJECTIVE against the bound discriminator's last_sigmoid (true under objective 0, false under 1 .. 3): checked at whichever of
 // gt_bind_model / gt_set_option comes second and at the entry of every step that runs the discriminator, before any launch
 int check_gan_objective(const gt_engine* e);

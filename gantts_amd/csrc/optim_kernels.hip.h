@@ -5,7 +5,8 @@
 // slab_reduce_norm_kernel (frame_kernels.hip.h).
 // One instantiation per (kind, flags): nothing is decided per element.  Each rule restates torch's single-tensor code path
 // (torch/optim/<name>.py, _single_tensor_<name>, foreach=False), operation by operation in float32.
-// HBM traffic: 16 B per parameter (p and g, read and written) + 8 B per live state buffer, up to three of them (40 B).
+// HBM traffic: 16 B per parameter (p and g, read and written) + 8 B per live state buffer, up to three of them (40 B); + 8 B with the
+// weight-average rider (gt_set_param_ema: the average read and written).
 #pragma once
 #include "frame_kernels.hip.h"
 
@@ -48,6 +49,9 @@ struct OptimSpec {
   float beta1, beta2;  // OPTI_ORIGINAL Adam
   long step;           // OPTI_ORIGINAL: 1-based step count of THIS update
   float wclip;         // gt_set_weight_clip: > 0 clamps every updated parameter to [-wclip, wclip] behind the rule (param.clamp_ after optimizer.step()); 0: off
+  float* ema;          // gt_set_param_ema: the running average of the parameters, updated from every STORED parameter (behind rule and clamp); null: off
+  float ema_w;         // its lerp weight, float32(1.0 - decay)
+  int ema_first;       // the first applied update: the average becomes a copy of the stored parameters (AveragedModel, n_averaged == 0)
 };
 // which of the three state streams a (kind, flags) pair reads and writes
 template <int KIND, unsigned F> struct OptimStreams {
@@ -181,23 +185,34 @@ __device__ __forceinline__ void optim_update(float& p, float& g, float& s0, floa
   }
 }
 
+// AveragedModel.update_parameters with get_ema_multi_avg_fn(decay): ema.lerp_(p, w) as this torch build's CPU path evaluates it, ONE fused
+// multiply-add per element in the form that is exact at the nearer end.  Spelled out, not left to contraction (torch_lerp above, with its two
+// roundings where the compiler does not contract, stays what the rules were pinned with).
+__device__ __forceinline__ float ema_lerp(float ema, float p, float w) {
+  const float d = p - ema;
+  return w < 0.5f ? fmaf(w, d, ema) : fmaf(-(1.f - w), d, p);
+}
+
 // the elements of one thread: clip coefficient and step scalars are known.  CLIP: each updated parameter is clamped to [-wclip, wclip]
 // behind the rule and before the store -- two comparisons, so that a NaN parameter stays a NaN, as Tensor.clamp_ leaves it.
-template <int KIND, unsigned F, bool CLIP>
+// EMA: the average's four loads join the group of p / g / s0..s2; its update reads the value that is stored, behind rule and clamp.
+template <int KIND, unsigned F, bool CLIP, bool EMA>
 __device__ __forceinline__ void optim_step_elements(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1,
                                                     float* __restrict__ s2, long n, float coef, const OptimSpec& o) {
   typedef OptimStreams<KIND, F> S;
+  float* __restrict__ const ema = EMA ? o.ema : (float*)nullptr;      // (no other stream of this launch: gt_set_param_ema's buffer is the caller's own)
   // four grid strides per trip: the loads of four elements are in flight together (a thread of the cfg2 generator's launch walks 3-4)
   const long gstride = (long)gridDim.x * blockDim.x;
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += 4 * gstride) {      // (the last trip is predicated: no one-element tail)
-    float pv[4], gv[4], av[4], bv[4], cv[4];
+    float pv[4], gv[4], av[4], bv[4], cv[4], ev[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long k = i + u * gstride;
       const bool ok = k < n;
       pv[u] = ok ? p[k] : 0.f; gv[u] = ok ? g[k] : 0.f;
       av[u] = (S::s0 && ok) ? s0[k] : 0.f; bv[u] = (S::s1 && ok) ? s1[k] : 0.f; cv[u] = (S::s2 && ok) ? s2[k] : 0.f;
+      ev[u] = (EMA && ok) ? ema[k] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -209,11 +224,16 @@ __device__ __forceinline__ void optim_step_elements(float* __restrict__ p, float
       if (S::s0) s0[k] = av[u];
       if (S::s1) s1[k] = bv[u];
       if (S::s2) s2[k] = cv[u];
+      if (EMA) ema[k] = o.ema_first ? pv[u] : ema_lerp(ev[u], pv[u], o.ema_w);
     }
   }
 }
 
-template <int KIND, unsigned F>
+// EMA: the weight-average rider (gt_set_param_ema; o.ema is then not null).  A template parameter of the KERNEL, chosen by the launch, and not
+// a third uniform test beside wclip's: as a test it cost every instantiation some 20 VGPRs -- a kernel is allocated for its widest path -- and
+// 16 of the 23 an occupancy step with the average off (Adagrad 6 -> 4 waves per SIMD, the amsgrad rows 4 -> 3: fewer than the 1024 workgroups
+// of a large launch resident at once).  With EMA = false this is the kernel that was always here.
+template <int KIND, unsigned F, bool EMA = false>
 static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
     float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0, float* __restrict__ s1, float* __restrict__ s2, long n,
     const double* __restrict__ norm_partial, int n_partial, double* __restrict__ norm2_out, OptimSpec o,
@@ -260,8 +280,8 @@ static __global__ __launch_bounds__(RED_THREADS) void optim_step_kernel(
   if constexpr ((F & OPTI_ORIGINAL) != 0) optim_original_scalars<KIND>(o);
   // weight clipping (gt_set_weight_clip): ONE uniform test of a spec field per thread, not a row of the (kind, flags) table and not a
   // test per element.  With the field 0 the elements go through the loop that was always here, compiled from the same statements.
-  if (o.wclip > 0.f) optim_step_elements<KIND, F, true>(p, g, s0, s1, s2, n, coef, o);
-  else optim_step_elements<KIND, F, false>(p, g, s0, s1, s2, n, coef, o);
+  if (o.wclip > 0.f) optim_step_elements<KIND, F, true, EMA>(p, g, s0, s1, s2, n, coef, o);
+  else optim_step_elements<KIND, F, false, EMA>(p, g, s0, s1, s2, n, coef, o);
 }
 
 }  // namespace gt

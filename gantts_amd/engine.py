@@ -148,6 +148,7 @@ class StepEngine(object):
         # hp.discriminator_spectral_norm: the discriminator bound to this engine is an ``MLP(..., spectral_norm=True)`` (checked at the bind)
         self.spectral_norm = bool(getattr(hp, "discriminator_spectral_norm", False))
         self._sn_on = False                      # gt_set_spectral_norm holds buffers right now
+        self._ema_on = False                     # gt_set_param_ema holds a buffer right now
         # hp.discriminator_grad_penalty / _weight: R1 or WGAN-GP on the MLP discriminator, sent before any network is bound
         self.grad_penalty = None
         kind, weight = grad_penalty_of(hp)
@@ -184,6 +185,12 @@ class StepEngine(object):
         check(lib.gt_bind_model(self._h, role, C.byref(desc)))
         if role == L.ROLE_D and sn:
             self.set_spectral_norm(L.ROLE_D, model.sn_u, model.sn_v)
+        if role == L.ROLE_G:
+            # model.enable_weight_average(): the generator's average rides its optimizer launch; the model owns buffer and count
+            if getattr(model, "_ema", None) is not None:
+                self.set_param_ema(L.ROLE_G, model._ema, model._ema_decay, model._n_averaged)
+            elif self._ema_on:
+                self.set_param_ema(L.ROLE_G, None)
         for (pass_idx, layer), m in model._masks.items():
             check(lib.gt_set_dropout_mask(self._h, role, pass_idx, layer, ptr(m)))
         check(lib.gt_set_training(self._h, role, int(model.training)))
@@ -351,6 +358,42 @@ class StepEngine(object):
         """Every later optimizer step of ``role`` (the discriminator's alone) clamps each updated parameter to ``[-c, c]`` inside the
         fused clip + update launch -- ``p.data.clamp_(-c, c)`` after ``optimizer_d.step()``, the WGAN weight clipping.  ``c = 0``: off."""
         check(lib.gt_set_weight_clip(self._h, int(role), float(c)))
+
+    def set_param_ema(self, role, ema, decay=0.0, n_averaged=None):
+        """Weight averaging of the bound generator (gt_set_param_ema): ``ema`` is the model's average buffer (``num_flat_params()`` float32
+        on the device, kept alive here), updated inside every later generator optimizer launch -- a copy of the updated parameters while
+        the count is 0, ``ema.lerp_(p, float32(1 - decay))`` afterwards.  ``n_averaged`` (if given) sets the count.  ``None`` switches
+        it off.  Called by ``bind_model`` for a generator with ``enable_weight_average``."""
+        if ema is None:
+            check(lib.gt_set_param_ema(self._h, int(role), None, 0, 0.0))
+            self._keep.pop("ema", None)
+            self._ema_on = False
+            return
+        if not (isinstance(ema, torch.Tensor) and ema.is_cuda and ema.dtype == torch.float32 and ema.dim() == 1 and ema.is_contiguous()):
+            raise ValueError("ema must be a contiguous 1-D float32 device tensor")
+        check(lib.gt_set_param_ema(self._h, int(role), ptr(ema), ema.numel(), float(decay)))
+        self._keep["ema"] = ema
+        self._ema_on = True
+        if n_averaged is not None:
+            check(lib.gt_set_param_ema_count(self._h, int(role), int(n_averaged)))
+
+    def param_ema_count(self, role=L.ROLE_G):
+        """Updates applied to the weight average so far (gt_get_param_ema_count): ``AveragedModel.n_averaged``."""
+        n = C.c_int64()
+        check(lib.gt_get_param_ema_count(self._h, int(role), C.byref(n)))
+        return n.value
+
+    def _note_ema(self):
+        """Behind a training generator step, where the optimizer's step count is read back: the bound generator's ``n_averaged``."""
+        if self._ema_on:
+            ref = self._bound[L.ROLE_G][0]
+            model = ref() if ref is not None else None
+            if model is not None and getattr(model, "_ema", None) is not None:
+                model._n_averaged = self.param_ema_count(L.ROLE_G)
+
+    def _no_step_on_average(self, model_g, train):
+        if train and getattr(model_g, "_ema_swapped", False):
+            raise RuntimeError("update_generator(phase=\"train\") inside averaged_weights(): the parameters are the average there")
 
     def set_spectral_norm(self, role, u, v):
         """Spectral normalisation of the bound MLP discriminator (gt_set_spectral_norm): ``u`` (sum of out) and ``v`` (sum of in) are the
@@ -563,6 +606,7 @@ class StepEngine(object):
         B, T, _ = y.shape
         mask = self._mask2d(mask, B, T)
         train = phase == "train"
+        self._no_step_on_average(model_g, train)
         self.bind_model(L.ROLE_G, model_g, with_grads=True)
         if train:
             self.bind_optimizer(L.ROLE_G, optimizer_g)
@@ -579,6 +623,7 @@ class StepEngine(object):
                                       float(eps), C.byref(res), L.current_stream()))
         if train:
             optimizer_g._note_step(self, L.ROLE_G)
+            self._note_ema()
         return res.loss_mse, res.loss_mge, res.loss_adv, res.loss_g
 
     # ---- split-phase forms (data parallelism, gantts_amd/parallel.py) ------------------------
@@ -634,6 +679,7 @@ class StepEngine(object):
         B, T, _ = y.shape
         mask = self._mask2d(mask, B, T)
         train = phase == "train"
+        self._no_step_on_average(model_g, train)
         self.bind_model(L.ROLE_G, model_g, with_grads=True)
         if train:
             self.bind_optimizer(L.ROLE_G, optimizer_g)
@@ -655,6 +701,7 @@ class StepEngine(object):
                                           None if defer else C.byref(res), L.current_stream()))
         if train:
             optimizer_g._note_step(self, L.ROLE_G)
+            self._note_ema()
         if defer:
             return None
         return res.loss_mse, res.loss_mge, res.loss_adv, res.loss_g

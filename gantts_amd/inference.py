@@ -16,6 +16,10 @@ of these calls:
 ``hp_acoustic`` / ``hp_duration`` / ``hp_vc`` are module globals like in the reference scripts.
 Checkpoints written by the reference load unchanged (``gantts_amd.train.load_checkpoint``): the
 model classes keep torch's state_dict keys.
+
+A generator trained with a weight average (``hp.generator_ema_decay`` / ``model.enable_weight_average``) synthesises from the averaged
+weights inside ``with model.averaged_weights():`` (``model.eval()`` first) -- every call above made there runs on them --, or from a
+plain model that loaded the checkpoint's ``"ema_state_dict"`` with ``load_state_dict``.
 """
 import numpy as np
 import torch

@@ -10,8 +10,10 @@ ONE flat float32 device buffer per network (state_dict order), so that
     (fused clip-norm + optimizer kernel, one all-reduce bucket per network).
 No torch op touches the numbers: forward/backward/step run in libgantts_hip.so.
 """
+import contextlib
 import math
 import weakref
+from collections import OrderedDict
 
 import torch
 from torch import nn
@@ -111,6 +113,10 @@ class _FlatNetwork(AbstractModel, nn.Module):
         self._masks = {}             # (pass, layer) -> injected dropout mask tensor (tests)
         self._bound_engines = {}     # id(engine) -> (weakref(engine), role): who must hear zero_grad()
         self._version = 0            # bumped whenever buffers are re-homed (engines re-bind)
+        self._ema = None             # enable_weight_average: a second flat buffer, the running average of _flat (engines send it at the bind)
+        self._ema_decay = None
+        self._n_averaged = 0         # generator updates applied to the average (AveragedModel.n_averaged), read back from the engine
+        self._ema_swapped = False    # inside averaged_weights(): the two buffers' contents are exchanged
 
     def _holders(self):
         return [m for m in self.modules() if isinstance(m, (_LinearParams, _LSTMParams, _SRUCellParams))]
@@ -140,8 +146,126 @@ class _FlatNetwork(AbstractModel, nn.Module):
                 self._buffers[name] = fn(buf)
         if self._flat_grad is not None:
             self._flat_grad = fn(self._flat_grad)
+        if self._ema is not None:
+            self._ema = fn(self._ema)
         self._repoint()
         return self
+
+    # -- weight averaging (EMA of the parameters, kept by the engine inside the generator's fused clip + update launch) ----------------
+    def enable_weight_average(self, decay):
+        """Keeps an exponential moving average of the parameters, defined as ``torch.optim.swa_utils.AveragedModel(self,
+        multi_avg_fn=get_ema_multi_avg_fn(decay))`` with ``update_parameters`` called after every applied generator update: the first
+        update copies the parameters, every later one is ``ema.lerp_(p, float32(1 - decay))``.  The average is a second flat float32
+        buffer, a copy of the parameters until the first update; it follows ``.cuda()`` / ``.to()``.  Only a network in the generator
+        slot is averaged.  Calling it again restarts the average."""
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:      # (a NaN fails it)
+            raise ValueError("weight average: decay = %r -- a number in [0, 1]" % (decay,))
+        if self._ema_swapped:
+            raise RuntimeError("enable_weight_average inside averaged_weights()")
+        self._ema = self._flat.detach().clone()
+        self._ema_decay = decay
+        self._n_averaged = 0
+        self._version += 1
+
+    def disable_weight_average(self):
+        if self._ema_swapped:
+            raise RuntimeError("disable_weight_average inside averaged_weights()")
+        self._ema, self._ema_decay, self._n_averaged = None, None, 0
+        self._version += 1
+
+    @property
+    def ema_decay(self):
+        """The decay of the weight average, or None while it is off."""
+        return self._ema_decay
+
+    @property
+    def n_averaged(self):
+        """Generator updates applied to the weight average so far (``AveragedModel.n_averaged``)."""
+        return self._n_averaged
+
+    def _need_average(self):
+        if self._ema is None:
+            raise RuntimeError("the weight average is off: call enable_weight_average(decay) first")
+
+    def _flat_slices(self):
+        """(key, offset, shape) of every parameter inside the flat buffer, in state_dict order."""
+        base = self._flat.data_ptr()
+        psd = super(_FlatNetwork, self).state_dict()
+        out = []
+        for k, v in psd.items():
+            off = (v.data_ptr() - base) // 4
+            if v.dtype == torch.float32 and 0 <= off and off + v.numel() <= self._flat.numel() and v.device == self._flat.device:
+                out.append((k, off, v.shape))
+        return out
+
+    def ema_state_dict(self):
+        """``state_dict()`` with the averaged values: same keys, shapes and order (buffers that are no parameters are copied as they
+        are), so that a plain model -- or the reference's -- loads it with ``load_state_dict``."""
+        self._need_average()
+        src = self._flat if self._ema_swapped else self._ema
+        slices = dict((k, (off, shape)) for k, off, shape in self._flat_slices())
+        sd = OrderedDict()
+        for k, v in self.state_dict().items():
+            if k in slices:
+                off, shape = slices[k]
+                sd[k] = src[off:off + v.numel()].detach().clone().view(shape)
+            else:
+                sd[k] = v.detach().clone()
+        return sd
+
+    def load_ema_state_dict(self, state_dict, n_averaged):
+        """The inverse of ``ema_state_dict()``: the average becomes ``state_dict``'s values, its count ``n_averaged``."""
+        self._need_average()
+        if self._ema_swapped:
+            raise RuntimeError("load_ema_state_dict inside averaged_weights()")
+        n_averaged = int(n_averaged)
+        if n_averaged < 0:
+            raise ValueError("n_averaged = %d: the updates already averaged, >= 0" % n_averaged)
+        slices = self._flat_slices()
+        missing = [k for k, _, _ in slices if k not in state_dict]
+        if missing:
+            raise KeyError("load_ema_state_dict: missing %s" % ", ".join(missing))
+        with torch.no_grad():
+            for k, off, shape in slices:
+                v = state_dict[k]
+                if tuple(v.shape) != tuple(shape):
+                    raise RuntimeError("load_ema_state_dict: %s has shape %s, the parameter %s" % (k, tuple(v.shape), tuple(shape)))
+                self._ema[off:off + v.numel()].view(shape).copy_(v)
+        self._n_averaged = n_averaged
+        self._version += 1      # engines send the count with the buffer at their next bind
+
+    def _reset_weight_average(self):
+        """The average restarts from the parameters as they are (a checkpoint without an average was loaded)."""
+        with torch.no_grad():
+            self._ema.copy_(self._flat)
+        self._n_averaged = 0
+        self._version += 1
+
+    def _swap_average(self):
+        with torch.no_grad():
+            tmp = self._flat.detach().clone()
+            self._flat.copy_(self._ema)
+            self._ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """``with model.averaged_weights():`` exchanges the contents of the parameter buffer and of the average on entry and again on exit:
+        every forward inside it -- the engine's, ``model(x)``, ``inference.*`` -- runs on the averaged weights (no pointer moves, nothing
+        is re-bound; the engine re-makes its bf16 weight shadows from the parameters before every pass).  Evaluation only: entering
+        while ``model.training`` is true raises, and so does a train-phase step inside it."""
+        self._need_average()
+        if self.training:
+            raise RuntimeError("averaged_weights() is for evaluation: call model.eval() first (a training step would update the average as if it were the parameters)")
+        if self._ema_swapped:
+            raise RuntimeError("averaged_weights() is already entered")
+        self._swap_average()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_average()
+            self._ema_swapped = False
 
     def flat_params(self):
         return self._flat

@@ -242,19 +242,31 @@ def exp_lr_scheduler(optimizer, epoch, nepoch, init_lr=0.0001, lr_decay_epoch=10
 
 
 def save_checkpoint(model, optimizer, epoch, checkpoint_dir, name):
-    """{"state_dict", "optimizer", "global_epoch"} -> checkpoint_epoch{N}_{name}.pth (train.py:162-171)."""
+    """{"state_dict", "optimizer", "global_epoch"} -> checkpoint_epoch{N}_{name}.pth (train.py:162-171).  A model that keeps a weight
+    average (``enable_weight_average``) adds "ema_state_dict" and "ema_n_averaged"; without one the file has exactly the three keys."""
     path = join(checkpoint_dir, "checkpoint_epoch{}_{}.pth".format(epoch, name))
-    torch.save({"state_dict": model.state_dict(), "optimizer": optimizer.state_dict(), "global_epoch": epoch}, path)
+    ckpt = {"state_dict": model.state_dict(), "optimizer": optimizer.state_dict(), "global_epoch": epoch}
+    if getattr(model, "ema_decay", None) is not None:
+        ckpt["ema_state_dict"] = model.ema_state_dict()
+        ckpt["ema_n_averaged"] = int(model.n_averaged)
+    torch.save(ckpt, path)
     print("Saved checkpoint:", path)
     return path
 
 
 def load_checkpoint(model, optimizer, checkpoint_path):
-    """Restores model, optionally optimizer, and global_epoch (train.py:651-658)."""
+    """Restores model, optionally optimizer, and global_epoch (train.py:651-658).  The weight average: restored when both the checkpoint
+    and the model have one; a checkpoint without one resets an averaging model's average to the loaded parameters (count 0); a plain model
+    ignores a checkpoint's average."""
     global global_epoch
     print("Load checkpoint from: {}".format(checkpoint_path))
     ckpt = torch.load(checkpoint_path, map_location="cpu")
     model.load_state_dict(ckpt["state_dict"])
+    if getattr(model, "ema_decay", None) is not None:
+        if "ema_state_dict" in ckpt and "ema_n_averaged" in ckpt:
+            model.load_ema_state_dict(ckpt["ema_state_dict"], ckpt["ema_n_averaged"])
+        else:
+            model._reset_weight_average()
     if optimizer is not None:
         optimizer.load_state_dict(ckpt["optimizer"])
     global_epoch = ckpt["global_epoch"]
@@ -296,7 +308,14 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     ``hp.discriminator_grad_penalty`` (None, "r1" or "wgan-gp"; ``hp.discriminator_grad_penalty_weight``, default 10) adds a gradient
     penalty to every D step of the train phase inside the engine.  The losses logged here do not contain it; its mean and the mean
     gradient norm it was taken at are read once at the end of the train phase (never per batch, with or without
-    ``hp.device_epoch_ledger``) and logged as ``grad_penalty`` and ``grad_norm_at_penalty``."""
+    ``hp.device_epoch_ledger``) and logged as ``grad_penalty`` and ``grad_norm_at_penalty``.
+
+    ``hp.generator_ema_decay`` (default 0 = off; a value in (0, 1), read with getattr) keeps an exponential moving average of the
+    generator's weights inside its update launch (``model_g.enable_weight_average(decay)``, unless the model has enabled one itself); it
+    moves with every applied generator update, so not under ``update_g=False``.  ``hp.generator_ema_eval`` (default False): the test
+    phase runs inside ``model_g.averaged_weights()``, i.e. on the averaged generator.  The generator's checkpoints carry the average
+    either way (``save_checkpoint``)."""
+    import contextlib
     from . import _lib as L
     from .engine import gan_objective_of, grad_penalty_of
     from .data import DevicePrefetcher, ResidentLoader
@@ -333,6 +352,13 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     spoof_threshold = L.GAN_OBJECTIVE_THRESHOLD[gan_objective_of(hp)]
     ledger_eng, ledger_open, ledger_metrics = None, False, ()
     grad_penalty = grad_penalty_of(hp)[0]
+    ema_decay = float(getattr(hp, "generator_ema_decay", 0.0))
+    if ema_decay != 0.0:
+        if not 0.0 < ema_decay < 1.0:
+            raise ValueError("hp.generator_ema_decay = %r: 0 (off) or a value in (0, 1)" % (ema_decay,))
+        if model_g.ema_decay is None:
+            model_g.enable_weight_average(ema_decay)
+    ema_eval = bool(getattr(hp, "generator_ema_eval", False)) and model_g.ema_decay is not None
 
     for global_epoch in range(global_epoch + 1, hp.nepoch + 1):
         if hp.lr_decay_schedule and update_g:
@@ -360,84 +386,86 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
             # (noise included), the static features and the mask with it; nothing is staged, drawn, concatenated or gathered here
             loader = dataset_loaders[phase]
             batches = loader if isinstance(loader, ResidentLoader) else DevicePrefetcher(loader, pitch_x=bool(getattr(hp, "pitch_x", True)))
-            for batch in batches:
-                x, y, sorted_lengths, cpu_sorted_lengths = batch.x, batch.y, batch.lengths, batch.cpu_lengths
-                max_len = batch.max_len
-                assembled = batch.generator_input is not None
-                # generator noise z ~ U[0,1) (train.py:504-506), drawn on the device
-                z = torch.rand(x.size(0), max_len, hp.generator_noise_dim, device=x.device, generator=noise_gen) \
-                    if hp.generator_add_noise and not assembled else None
-                R = mlpg_matrix(hp.windows, max_len) if has_dynamic else None
-                y_static = batch.y_static if batch.y_static is not None else \
-                    get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
-                total_num_frames += float(sum(cpu_sorted_lengths))
-                mask = batch.mask if batch.mask is not None else sequence_mask(sorted_lengths).unsqueeze(-1)
-                optimizer_g.zero_grad()
-                optimizer_d.zero_grad()
+            # hp.generator_ema_eval: the test phase runs on the averaged generator (the buffers' contents are exchanged, and back behind the phase)
+            with (model_g.averaged_weights() if ema_eval and phase == "test" else contextlib.nullcontext()):
+                for batch in batches:
+                    x, y, sorted_lengths, cpu_sorted_lengths = batch.x, batch.y, batch.lengths, batch.cpu_lengths
+                    max_len = batch.max_len
+                    assembled = batch.generator_input is not None
+                    # generator noise z ~ U[0,1) (train.py:504-506), drawn on the device
+                    z = torch.rand(x.size(0), max_len, hp.generator_noise_dim, device=x.device, generator=noise_gen) \
+                        if hp.generator_add_noise and not assembled else None
+                    R = mlpg_matrix(hp.windows, max_len) if has_dynamic else None
+                    y_static = batch.y_static if batch.y_static is not None else \
+                        get_static_features(y, len(hp.windows), hp.stream_sizes, hp.has_dynamic_features)
+                    total_num_frames += float(sum(cpu_sorted_lengths))
+                    mask = batch.mask if batch.mask is not None else sequence_mask(sorted_lengths).unsqueeze(-1)
+                    optimizer_g.zero_grad()
+                    optimizer_d.zero_grad()
 
-                if assembled:
-                    generator_input = batch.generator_input
-                else:
-                    generator_input = torch.cat((x, z), -1) if z is not None else x
-                y_hat, y_hat_static = apply_generator(model_g, generator_input, R, cpu_sorted_lengths)
-                assert x.size(1) == y_hat.size(1)
+                    if assembled:
+                        generator_input = batch.generator_input
+                    else:
+                        generator_input = torch.cat((x, z), -1) if z is not None else x
+                    y_hat, y_hat_static = apply_generator(model_g, generator_input, R, cpu_sorted_lengths)
+                    assert x.size(1) == y_hat.size(1)
 
-                # spoofing rate against a frozen reference discriminator (train.py:549-558)
-                if reference_discriminator is not None:
-                    y_hat_static_ref = get_selected_static_stream(y_hat_static) \
-                        if hp.adversarial_streams is not None else y_hat_static
-                    target = reference_discriminator(y_hat_static_ref, lengths=cpu_sorted_lengths)
-                    # accumulated on the device (float64 count); read once per epoch, no per-batch host synchronisation
-                    # (the objective's own "natural" threshold: 0.5 for "bce" and "ls", 0 for "hinge" and "wgan", whose D returns z)
-                    regard_fake_as_natural = regard_fake_as_natural + ((target > spoof_threshold).float() * mask).sum(dtype=torch.float64)
+                    # spoofing rate against a frozen reference discriminator (train.py:549-558)
+                    if reference_discriminator is not None:
+                        y_hat_static_ref = get_selected_static_stream(y_hat_static) \
+                            if hp.adversarial_streams is not None else y_hat_static
+                        target = reference_discriminator(y_hat_static_ref, lengths=cpu_sorted_lengths)
+                        # accumulated on the device (float64 count); read once per epoch, no per-batch host synchronisation
+                        # (the objective's own "natural" threshold: 0.5 for "bce" and "ls", 0 for "hinge" and "wgan", whose D returns z)
+                        regard_fake_as_natural = regard_fake_as_natural + ((target > spoof_threshold).float() * mask).sum(dtype=torch.float64)
 
-                if ledger:
-                    # hp.device_epoch_ledger: the split-phase forms of the same two steps with deferred results -- nothing is waited for
-                    # -- and one launch that adds the step's scalars and the batch's distortion metrics into the engine's ledger
-                    eng = _engine_of(y_hat_static, model_g)
-                    if ledger_eng is not eng:
-                        ledger_metrics = _ledger_configure(eng, y_static.size(-1), Y_data_mean, Y_data_std)
-                        ledger_eng, ledger_open = eng, False
-                    if not ledger_open:
-                        eng.ledger_reset()
-                        ledger_open = True
-                    flags = 0
+                    if ledger:
+                        # hp.device_epoch_ledger: the split-phase forms of the same two steps with deferred results -- nothing is waited for
+                        # -- and one launch that adds the step's scalars and the batch's distortion metrics into the engine's ledger
+                        eng = _engine_of(y_hat_static, model_g)
+                        if ledger_eng is not eng:
+                            ledger_metrics = _ledger_configure(eng, y_static.size(-1), Y_data_mean, Y_data_std)
+                            ledger_eng, ledger_open = eng, False
+                        if not ledger_open:
+                            eng.ledger_reset()
+                            ledger_open = True
+                        flags = 0
+                        if update_d:
+                            eng.update_discriminator_begin(model_d, optimizer_d, x, y_static, y_hat_static, mask, phase,
+                                                           lengths=cpu_sorted_lengths)
+                            eng.update_discriminator_end(optimizer_d, phase, defer=True)
+                            flags |= L.LEDGER_HAS_D
+                        if update_g:
+                            adv_w = w_d * float(np.clip(E_loss_mge / E_loss_adv, 0, 1e+3))
+                            eng.update_generator_begin(model_g, model_d, optimizer_g, x, y, y_hat, y_static, y_hat_static,
+                                                       adv_w, mask, phase, mse_w, mge_w, lengths=cpu_sorted_lengths)
+                            eng.update_generator_end(optimizer_g, adv_w, mse_w, mge_w, phase, defer=True)
+                            flags |= L.LEDGER_HAS_G | L.LEDGER_HAS_DIST
+                        if flags:
+                            eng.ledger_add(flags, y_static, y_hat_static, sorted_lengths)
+                        continue
+
                     if update_d:
-                        eng.update_discriminator_begin(model_d, optimizer_d, x, y_static, y_hat_static, mask, phase,
-                                                       lengths=cpu_sorted_lengths)
-                        eng.update_discriminator_end(optimizer_d, phase, defer=True)
-                        flags |= L.LEDGER_HAS_D
+                        loss_d, loss_fake_d, loss_real_d, _real, _fake = update_discriminator(
+                            model_d, optimizer_d, x, y_static, y_hat_static, cpu_sorted_lengths, mask, phase)
+                        running_loss["discriminator"] += loss_d
+                        running_loss["loss_fake_d"] += loss_fake_d
+                        running_loss["loss_real_d"] += loss_real_d
+                        real_correct_count += _real
+                        fake_correct_count += _fake
+
                     if update_g:
                         adv_w = w_d * float(np.clip(E_loss_mge / E_loss_adv, 0, 1e+3))
-                        eng.update_generator_begin(model_g, model_d, optimizer_g, x, y, y_hat, y_static, y_hat_static,
-                                                   adv_w, mask, phase, mse_w, mge_w, lengths=cpu_sorted_lengths)
-                        eng.update_generator_end(optimizer_g, adv_w, mse_w, mge_w, phase, defer=True)
-                        flags |= L.LEDGER_HAS_G | L.LEDGER_HAS_DIST
-                    if flags:
-                        eng.ledger_add(flags, y_static, y_hat_static, sorted_lengths)
-                    continue
-
-                if update_d:
-                    loss_d, loss_fake_d, loss_real_d, _real, _fake = update_discriminator(
-                        model_d, optimizer_d, x, y_static, y_hat_static, cpu_sorted_lengths, mask, phase)
-                    running_loss["discriminator"] += loss_d
-                    running_loss["loss_fake_d"] += loss_fake_d
-                    running_loss["loss_real_d"] += loss_real_d
-                    real_correct_count += _real
-                    fake_correct_count += _fake
-
-                if update_g:
-                    adv_w = w_d * float(np.clip(E_loss_mge / E_loss_adv, 0, 1e+3))
-                    loss_mse, loss_mge, loss_adv, loss_g = update_generator(
-                        model_g, model_d, optimizer_g, x, y, y_hat, y_static, y_hat_static,
-                        adv_w, cpu_sorted_lengths, mask, phase, mse_w=mse_w, mge_w=mge_w)
-                    running_loss["mse"] += loss_mse
-                    running_loss["mge"] += loss_mge
-                    running_loss["loss_adv"] += loss_adv
-                    running_loss["generator"] += loss_g
-                    distortions = compute_distortions(y_static, y_hat_static, Y_data_mean, Y_data_std, cpu_sorted_lengths)
-                    for k, v in distortions.items():
-                        running_metrics[k] = running_metrics.get(k, 0.0) + float(v)
+                        loss_mse, loss_mge, loss_adv, loss_g = update_generator(
+                            model_g, model_d, optimizer_g, x, y, y_hat, y_static, y_hat_static,
+                            adv_w, cpu_sorted_lengths, mask, phase, mse_w=mse_w, mge_w=mge_w)
+                        running_loss["mse"] += loss_mse
+                        running_loss["mge"] += loss_mge
+                        running_loss["loss_adv"] += loss_adv
+                        running_loss["generator"] += loss_g
+                        distortions = compute_distortions(y_static, y_hat_static, Y_data_mean, Y_data_std, cpu_sorted_lengths)
+                        for k, v in distortions.items():
+                            running_metrics[k] = running_metrics.get(k, 0.0) + float(v)
 
             if ledger and ledger_open:
                 # the one wait of the phase: the sums the loop above would have kept on the host, bit for bit (each addend was formed

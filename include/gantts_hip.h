@@ -358,6 +358,26 @@ int gt_set_option(gt_engine* e, int option, int value);
  * stays a NaN.  c = 0 switches it off (the default: the stored values are the rule's own); c must be finite and >= 0, and role
  * GT_ROLE_D -- anything else returns GT_ERR_INVALID.  Independent of GT_OPT_GAN_OBJECTIVE. */
 int gt_set_weight_clip(gt_engine* e, int role, float c);
+/* Weight averaging of the generator (beyond the reference): an exponential moving average of its parameters, kept inside the fused clip +
+ * update launch.  The definition is torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay)) with
+ * update_parameters() called once after every applied generator update, bit for bit: the first applied update makes the average a copy of
+ * the updated parameters; every later one is ema.lerp_(p, w), w = float32(1.0 - decay) (the subtraction in double, rounded once), ONE fused
+ * multiply-add per element -- fmaf(w, p - ema, ema) for w < 0.5, fmaf(-(1 - w), p - ema, p) otherwise.  p is the value the launch stores,
+ * behind the update rule and behind gt_set_weight_clip's clamp.  `ema`: a caller-owned float32 device buffer of n floats, like optimizer
+ * state, n the bound generator's parameter count; it costs 8 B of memory traffic per parameter and no launch.  ema = NULL (with decay 0)
+ * switches the average off (the default): nothing is read or written, and the launch computes what it always did, bit for bit.  The setting
+ * and the count survive gt_bind_optimizer* and gt_set_lr; giving another buffer keeps the count (the same average, moved).
+ * gt_get_param_ema_count: the updates applied to the average so far -- torch's n_averaged --, counted where the optimizer's step count is
+ * counted; an update skipped on the device fault word leaves the average untouched and is taken back out by gt_clear_faults.  The host
+ * picks "copy" or the lerp weight from this count at every launch.  gt_set_param_ema_count sets it (a restored checkpoint's n_averaged; 0
+ * makes the next applied update a copy again).
+ * GT_ERR_INVALID: role D; a decay outside [0, 1] or NaN; n < 1; a NULL buffer with a decay; an n that is not the bound generator's parameter
+ * count -- checked at the call when a generator is bound, and at the entry of every training generator step before any launch.
+ * DATA PARALLEL: nothing to do and nothing refused -- every rank applies the same all-reduced update to the same parameters, so the ranks'
+ * averages are identical without a collective. */
+int gt_set_param_ema(gt_engine* e, int role, float* ema, int64_t n, double decay);
+int gt_set_param_ema_count(gt_engine* e, int role, int64_t n_averaged);
+int gt_get_param_ema_count(gt_engine* e, int role, int64_t* n_averaged);
 /* Spectral normalisation of the MLP discriminator (SN-GAN; beyond the reference; torch.nn.utils.spectral_norm with n_power_iterations = 1
  * on every nn.Linear weight, biases untouched).  u [n_u] and v [n_v] are caller-owned float32 device buffers, like optimizer state:
  * per layer in state_dict order a unit vector of `out` entries in u and one of `in` entries in v (torch's weight_u / weight_v), so
@@ -523,6 +543,11 @@ int gt_op_masked_mse(const float* input, const float* target, const float* mask,
  * *gscale.  grads receives the clipped gradient.  grad_norm_out (host, may be NULL): the pre-clip norm; synchronises if given. */
 int gt_op_optim_step(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
                      float* grad_norm_out, void* stream);
+/* The same two launches with the weight-average rider of gt_set_param_ema: `ema` (device, n floats, not NULL) holds the average after
+ * n_averaged >= 0 applied updates and receives the next one -- a copy of the updated parameters when n_averaged == 0, the lerp with
+ * float32(1.0 - decay) otherwise.  The caller counts. */
+int gt_op_optim_step_ema(const gt_optim_desc_ex* desc, float* params, float* grads, int64_t n, const float* gscale,
+                         float* grad_norm_out, float* ema, int64_t n_averaged, double decay, void* stream);
 /* Host only, no device: the host scalar state of desc's kind after `t` >= desc->step updates, from desc's hyper-parameters, step and
  * host_state* (the routine behind gt_get_optimizer_scalars and the update's own scalars; the descriptor is checked as by gt_bind_optimizer_ex, its state buffers aside, which are not looked at).  A caller
  * that steps through gt_op_optim_step passes out[] back in as host_state* of the next step's descriptor. */
@@ -1274,7 +1299,9 @@ int gt_op_corpus_stats(const gt_corpus_stats_case* c, void* stream);
  *   10,11 = 64x64 backward-data kernels with a compiled-in epilogue: none / LeakyReLU + Philox;
  *   12    = the two weight-gradient products of a split first layer in one launch;
  *   13    = the split first layer's forward in one launch (two K segments, two result halves);
- *   14    = the fused discriminator stack (GT_OPT_FUSED_DSTACK: layers 1..L-1 + head [+ backward-data chain] of one pass);  15 unused.
+ *   14    = the fused discriminator stack (GT_OPT_FUSED_DSTACK: layers 1..L-1 + head [+ backward-data chain] of one pass);
+ *   15    = the fused clip + update launch of either network (kind 8; no flops, bytes = 16 + 8 per live state buffer + 8 with the weight
+ *           average, per parameter).  Instrumented ONLY when selected by its kind, gt_profile_enable(2 + 8): (1) leaves it alone.
  * flops are algorithmic 2*M*N*K of the unpadded problems.  The three arrays hold GT_PROFILE_SLOTS entries.
  * gt_profile_enable(0) off, (1) every product launch, (2 + k) only launches of kind k (5 = the pair launches: what bench.py samples
  * inside its timed region -- two events per launch are not free). */
