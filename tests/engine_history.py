@@ -6,7 +6,11 @@ history (`inplace`: every batch starts at the same device address and is filled 
 new set of objects loaded from the worn session's snapshot -- engine_for keys engines on the generator object, so it has a new engine --
 that stages into exact-size new allocations (`fresh`) and runs the probe alone.  DESIGN.md ("Engine state across steps"): a step's result
 depends on the parameters, the optimizer state, the seed, the step count and the inputs' values, not on what the engine did before -- so
-everything the probe returns and leaves behind is compared on its bits, with no tolerance anywhere in this module."""
+everything the probe returns and leaves behind is compared on its bits, with no tolerance anywhere in this module.
+
+FEATURE_BACKENDS / FEATURE_PAIRS / FEATURE_HISTORIES / feature_probe: the same for the opt-in GAN features (objectives, weight clip, spectral
+normalisation, gradient penalties, the generator's weight average), whose state the old probe does not record; a table, a pair list and a probe
+of their own, PAIRS and COMM_PAIRS stay what they are."""
 import contextlib
 
 import numpy as np
@@ -46,8 +50,9 @@ def shape_facts(name):
 # flip: (option, value the backend runs with, its other value) of the option_flip history -- the backend's own option, else launch_riders
 # ---------------------------------------------------------------------------------------------
 def _case_tables():
+    from gan_objective_ref import STEP_CASES
     from test_gpu_sru_discriminator import SRUD_CASES
-    return {"CASES": C.CASES, "ORACLE_ONLY_CASES": C.ORACLE_ONLY_CASES, "SRUD_CASES": SRUD_CASES}
+    return {"CASES": C.CASES, "ORACLE_ONLY_CASES": C.ORACLE_ONLY_CASES, "SRUD_CASES": SRUD_CASES, "STEP_CASES": STEP_CASES}
 
 
 OPTION_VALUES = {"split_first_layer": (0, 1), "fused_dstack": (0, 1, 2), "matmul_bf16": (0, 1), "lstm_persistent": (0, 1), "sru_d_bf16": (0, 1),
@@ -88,7 +93,49 @@ COMM_BACKENDS = {
 }
 HISTORIES_COMM = ("same_shape_refill", "shrink", "poison_train_restore", "option_flip", "split_phase")
 COMM_PAIRS = [(b, h) for b in COMM_BACKENDS for h in HISTORIES_COMM]
+# The opt-in GAN features, which keep state of their own between steps.  A row carries, beside case / options / flip, any of
+# objective (hp.gan_objective), weight_clip (hp.discriminator_weight_clip), spectral_norm (hp.discriminator_spectral_norm and
+# MLP(spectral_norm=True)), grad_penalty=(kind, weight) (hp.discriminator_grad_penalty[_weight]) and ema_decay (mg.enable_weight_average).
+# Cases of gan_objective_ref.STEP_CASES have last_sigmoid=False; a row without an objective ("bce") runs their bce_twin (backend_case).
+# Dropout is Philox as everywhere in this module.  One row per path: the per-layer head, the fused stack, a recurrent D; the bf16 shadows
+# cast from W_eff; R1 per layer and fused; x_hat written into adv2 (split first layer) and into dcat (no split); the average riding Adagrad
+# and Adam; and everything that may be on together in one engine.
+FEATURE_BACKENDS = {
+    "wgan_clip": dict(case=("STEP_CASES", "mlp32"), options={}, flip=_RIDERS, objective="wgan", weight_clip=0.01),
+    "hinge_fused": dict(case=("STEP_CASES", "mlp128_fused"), options={"fused_dstack": 2}, flip=("fused_dstack", 2, 0), objective="hinge"),
+    "ls_lstm_d": dict(case=("STEP_CASES", "lstm"), options={}, flip=_RIDERS, objective="ls"),
+    "sn_hinge": dict(case=("STEP_CASES", "mlp32_cond"), options={}, flip=_RIDERS, objective="hinge", spectral_norm=True),
+    "sn_bce_bf16": dict(case=("STEP_CASES", "mlp32"), options={"matmul_bf16": 1}, flip=("matmul_bf16", 1, 0), spectral_norm=True),
+    "gp_r1": dict(case=("STEP_CASES", "mlp32_cond"), options={}, flip=_RIDERS, grad_penalty=("r1", 10.0)),
+    "gp_r1_fused": dict(case=("STEP_CASES", "mlp128_fused"), options={"fused_dstack": 2}, flip=("fused_dstack", 2, 0), grad_penalty=("r1", 10.0)),
+    "gp_wgan_split": dict(case=("STEP_CASES", "mlp32_cond"), options={}, flip=_RIDERS, objective="wgan", grad_penalty=("wgan-gp", 10.0)),
+    "gp_wgan_cat": dict(case=("STEP_CASES", "mlp32_cond"), options={"split_first_layer": 0}, flip=("split_first_layer", 0, 1), objective="wgan",
+                        grad_penalty=("wgan-gp", 10.0)),
+    "ema_adagrad": dict(case=("CASES", "acoustic_mlp_dropout"), options={}, flip=_RIDERS, ema_decay=0.9),
+    "ema_adam": dict(case=("CASES", "duration_mlp"), options={}, flip=_RIDERS, ema_decay=0.999),
+    "all_wgan": dict(case=("STEP_CASES", "mlp32_cond"), options={}, flip=_RIDERS, objective="wgan", weight_clip=0.01, grad_penalty=("wgan-gp", 10.0),
+                     ema_decay=0.9),
+}
+FEATURE_KEYS = ("objective", "weight_clip", "spectral_norm", "grad_penalty", "ema_decay")
+LAST_SIGMOID = {"bce": True, "ls": False, "hinge": False, "wgan": False}       # what the bound discriminator must have under the objective
+AWAY_OBJECTIVE = {"ls": "hinge", "hinge": "ls", "wgan": "ls"}                    # feature_off_and_on: another objective with the same last_sigmoid
+HISTORIES_FEATURE_FEW = ("phase_and_roles", "abandoned_passes", "split_phase")
+FEATURE_BACKENDS_FEW = ("sn_hinge", "gp_wgan_split", "ema_adam")
+
+
+def _rows_with(*keys):
+    return [b for b, row in FEATURE_BACKENDS.items() if any(row.get(k) and row.get(k) != "bce" for k in keys)]
+
+
+FEATURE_PAIRS = ([(b, h) for b in FEATURE_BACKENDS for h in HISTORIES_ALL]
+                 + [(b, "feature_off_and_on") for b in _rows_with("grad_penalty", "weight_clip", "objective")]
+                 + [(b, "gp_hooks") for b in _rows_with("grad_penalty")]
+                 + [(b, "sn_other_d") for b in _rows_with("spectral_norm")]
+                 + [(b, "ema_swap_and_roles") for b in _rows_with("ema_decay")]
+                 + [(b, h) for b in FEATURE_BACKENDS_FEW for h in HISTORIES_FEATURE_FEW]
+                 + [("gp_wgan_split", "normaliser"), ("sn_hinge", "shard_and_normaliser"), ("ema_adam", "shard_and_normaliser")])
 ALL_BACKENDS = dict(BACKENDS, **COMM_BACKENDS)
+ALL_BACKENDS.update(FEATURE_BACKENDS)
 # the second discriminator of `other_d`: another kind and width, the same in_dim
 OTHER_D = {"MLP": dict(kind="LSTMRNN", out_dim=1, num_hidden=1, hidden_dim=20, bidirectional=True, dropout=0.0, last_sigmoid=True),
            "LSTMRNN": dict(kind="MLP", out_dim=1, num_hidden=2, hidden_dim=24, dropout=0.0, last_sigmoid=True)}
@@ -96,7 +143,16 @@ OTHER_D = {"MLP": dict(kind="LSTMRNN", out_dim=1, num_hidden=1, hidden_dim=20, b
 
 def backend_case(backend):
     table, name = ALL_BACKENDS[backend]["case"]
-    return _case_tables()[table][name]
+    case = _case_tables()[table][name]
+    if table == "STEP_CASES" and ALL_BACKENDS[backend].get("objective", "bce") == "bce":
+        from gan_objective_ref import bce_twin
+        case = bce_twin(case)
+    return case
+
+
+def backend_features(backend, override=None):
+    row = ALL_BACKENDS[backend]
+    return dict({k: row[k] for k in FEATURE_KEYS if k in row}, **(override or {}))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -192,10 +248,26 @@ def _struct_array(s):
     return np.array([getattr(s, n) for n, _ in s._fields_], dtype=np.float32)
 
 
+def build_sn_mlp(spec, seed):
+    """The case's MLP discriminator as MLP(spectral_norm=True): the weights build_model gives it, sn_u / sn_v the deterministic unit vectors
+    of spectral_norm_ref.initial_uv (the constructor's are drawn from torch's global generator)."""
+    import torch
+    import spectral_norm_ref as S
+    from gantts_amd import models
+    assert spec["kind"] == "MLP"
+    m = models.MLP(spectral_norm=True, **{k: v for k, v in spec.items() if k != "kind"})
+    sd = {k: torch.from_numpy(v) for k, v in C.make_weights(spec, seed).items()}
+    u0, v0 = S.initial_uv(spec)
+    sd["sn_u"], sd["sn_v"] = torch.from_numpy(np.concatenate(u0)), torch.from_numpy(np.concatenate(v0))
+    m.load_state_dict(sd)
+    return m.cuda()
+
+
 class Session(object):
-    def __init__(self, backend, policy, shapes=(), options=None, snapshot=None):
+    def __init__(self, backend, policy, shapes=(), options=None, snapshot=None, features=None):
         """policy "inplace": x, y, y_static, mask and the lengths tensor are views of the first elements of buffers sized for the largest of
-        `shapes` ((B, T) pairs); "fresh": exact-size new allocations, all kept alive so that no address comes back."""
+        `shapes` ((B, T) pairs); "fresh": exact-size new allocations, all kept alive so that no address comes back.  features: values that
+        replace the row's own (FEATURE_KEYS), for the negative controls."""
         import torch
         from gantts_amd import optim
         from gantts_amd.engine import engine_for
@@ -203,8 +275,21 @@ class Session(object):
         assert policy in ("inplace", "fresh")
         self.backend, self.policy = backend, policy
         self.case = case = backend_case(backend)
+        self.features = ft = backend_features(backend, features)
+        # the opt-in features as a train_loop user switches them on: on the hp before engine_for, MLP(spectral_norm=True), enable_weight_average
         self.hp = make_hp(case)
-        self.mg, self.md = build_model(case["g"], 11, case.get("saturate_gates", False)), build_model(case["d"], 22)
+        if "objective" in ft:
+            self.hp.gan_objective = ft["objective"]
+        if ft.get("weight_clip"):
+            self.hp.discriminator_weight_clip = ft["weight_clip"]
+        if ft.get("spectral_norm"):
+            self.hp.discriminator_spectral_norm = True
+        if ft.get("grad_penalty"):
+            self.hp.discriminator_grad_penalty, self.hp.discriminator_grad_penalty_weight = ft["grad_penalty"]
+        self.mg = build_model(case["g"], 11, case.get("saturate_gates", False))
+        self.md = build_sn_mlp(case["d"], 22) if ft.get("spectral_norm") else build_model(case["d"], 22)
+        if ft.get("ema_decay") is not None:
+            self.mg.enable_weight_average(ft["ema_decay"])
         self.og = getattr(optim, case["opt_g"][0])(self.mg.parameters(), **case["opt_g"][1])
         self.od = getattr(optim, case["opt_d"][0])(self.md.parameters(), **case["opt_d"][1])
         if snapshot is not None:
@@ -235,15 +320,20 @@ class Session(object):
 
     def snapshot(self):
         import copy
-        return dict(g={k: v.detach().clone() for k, v in self.mg.state_dict().items()},
-                    d={k: v.detach().clone() for k, v in self.md.state_dict().items()},
+        snap = dict(g={k: v.detach().clone() for k, v in self.mg.state_dict().items()},
+                    d={k: v.detach().clone() for k, v in self.md.state_dict().items()},      # (sn_u / sn_v of a spectrally normalised D are in here)
                     og=copy.deepcopy(self.og.state_dict()), od=copy.deepcopy(self.od.state_dict()))
+        if self.mg.ema_decay is not None:      # what a generator checkpoint carries beside the parameters (train.save_checkpoint)
+            snap["ema"], snap["n_averaged"] = self.mg.ema_state_dict(), self.mg.n_averaged
+        return snap
 
     def restore(self, snap):
         self.mg.load_state_dict(snap["g"])
         self.md.load_state_dict(snap["d"])
         self.og.load_state_dict(snap["og"])
         self.od.load_state_dict(snap["od"])
+        if "ema" in snap:
+            self.mg.load_ema_state_dict(snap["ema"], snap["n_averaged"])
 
     def set_option(self, name, value):
         self.options[name] = value
@@ -274,10 +364,10 @@ class Session(object):
         return x, y, ys, mask, R, [int(v) for v in batch["lengths"]]
 
     # ---- steps ------------------------------------------------------------------------------
-    def step(self, batch, phase, update_d=True, update_g=True, split_phase=False, model_d=None, optimizer_d=None):
+    def step(self, batch, phase, update_d=True, update_g=True, split_phase=False, model_d=None, optimizer_d=None, after_d=None):
         """One batch through zero_grad twice, T.apply_generator, T.update_discriminator, T.update_generator (split_phase: the engine's
         update_*_begin / _end(defer=True) / _result instead of the two fused calls).  Returns dict(y_hat, y_hat_static, d_scalars (six),
-        g_scalars (five)) as numpy; a skipped update leaves its scalars out."""
+        g_scalars (five)) as numpy; a skipped update leaves its scalars out.  after_d(out): called between the two updates."""
         import torch
         import gantts_amd.train as T
         case, eng = self.case, self.engine
@@ -303,6 +393,8 @@ class Session(object):
                 else:
                     T.update_discriminator(md, od, x, ys, yhs, lengths, mask, phase)
                 out["d_scalars"] = _struct_array(seen["d"])
+                if after_d is not None:
+                    after_d(out)
             if update_g:
                 if split_phase:
                     eng.update_generator_begin(self.mg, md, self.og, x, y, y_hat, ys, yhs, case["adv_w"], mask, phase, case["mse_w"],
@@ -366,6 +458,61 @@ def probe(session, seed=PROBE_SEED):
     return rec
 
 
+def gp_record(engine, reset):
+    """gt_grad_penalty_result as two records: the two means (float64) and the count of penalised steps"""
+    r = engine.grad_penalty_result(reset=reset)
+    return np.array([r["grad_penalty"], r["grad_norm_at_penalty"]], dtype=np.float64), np.array([r["steps"]], dtype=np.int64)
+
+
+def feature_probe(session, seed=PROBE_SEED):
+    """The probe of the FEATURE_PAIRS: the same three steps, and beside what `probe` records what the features leave behind --
+    gradient penalty: the running record, read and reset before the first step as train_loop does once per phase (what a history left in it
+      is discarded) and read again behind the third; wgan-gp: eps and the x_hat image of the last train step, peeked between its two updates;
+    weight average: its bits, both counts (the model's and the engine's), y_hat of one eval-mode forward inside averaged_weights() and the
+      parameters behind it (the swap gives them back);
+    spectral norm: sn_u / sn_v are part of D's state_dict, so of state();
+    gp_paths / sn_paths: the launches of either feature's kernels over the probe (process-wide counters, read before and after)."""
+    import torch
+    eng, ft = session.engine, session.features
+    gp_kind = ft["grad_penalty"][0] if ft.get("grad_penalty") else None
+    eng.set_seed(seed)
+    before = (eng.gp_path_counts(), eng.sn_path_counts())
+    if gp_kind:
+        gp_record(eng, reset=True)
+    b = probe_batches(session.backend)
+    B, Tn = SHAPES["probe"]
+    rec = {}
+
+    def peek(out):
+        e_, xh = eng.grad_penalty_peek(B * Tn, eng._adv_width())
+        torch.cuda.synchronize()
+        rec["gp_peek.eps"], rec["gp_peek.x_hat"] = e_.cpu().numpy(), xh.cpu().numpy()
+
+    for i, (batch, phase) in enumerate(zip(b, ("train", "train", "test"))):
+        for k, v in session.step(batch, phase, after_d=peek if (gp_kind == "wgan-gp" and i == 1) else None).items():
+            rec["step%d.%s" % (i, k)] = v
+    if gp_kind:
+        rec["gp_record"], rec["gp_steps"] = gp_record(eng, reset=True)
+    if ft.get("ema_decay") is not None:
+        mg = session.mg
+        for k, v in mg.ema_state_dict().items():
+            rec["ema.%s" % k] = v.cpu().numpy()
+        rec["ema_counts"] = np.array([mg.n_averaged, eng.param_ema_count()], dtype=np.int64)
+        mg.eval()
+        with mg.averaged_weights():
+            rec["ema_forward.y_hat"] = eng.model_forward(mg, torch.tensor(b[2]["x"], device="cuda"),
+                                                         lengths=[int(v) for v in b[2]["lengths"]]).cpu().numpy()
+        session.train_mode()
+        rec["ema_after_swap.params"] = mg.flat_params().detach().cpu().numpy()
+    rec.update(session.state())
+    rec.update(session.next_masks(B * Tn))
+    after = (eng.gp_path_counts(), eng.sn_path_counts())
+    rec["gp_paths"] = np.array(after[0], dtype=np.int64) - np.array(before[0], dtype=np.int64)
+    rec["sn_paths"] = np.array(after[1], dtype=np.int64) - np.array(before[1], dtype=np.int64)
+    eng.check_faults()
+    return rec
+
+
 # ---------------------------------------------------------------------------------------------
 # histories: name -> (the shapes its inplace buffers must hold, what the worn session does before the probe).
 # A history returns the snapshot the twin is loaded from when that is not the state at its end.
@@ -403,6 +550,17 @@ def _h_poison_train_restore(s):
     # the premise: parameters and optimizer state of both networks are poisoned, so the restore below has something to undo
     for model, opt in ((s.mg, s.og), (s.md, s.od)):
         assert torch.isnan(model.flat_params()).any() and any(torch.isnan(st).any() for st in opt._state if st is not None), s.backend
+    # ... and so is what the features keep: the average and sn_u / sn_v (undone through the snapshot).  The penalty's record has taken the step
+    # (cleared by the probe's opening reset) but is NOT NaN: the penalty sees D's input only through the signs of the activations -- a NaN
+    # activation takes the leaky slope, in the kernels (leaky_drop_grad) as in torch's leaky_relu_backward -- and the weights are still finite
+    # when it is formed, so |grad_x D| and the penalty are finite numbers in the double-backward reference too.
+    if s.features.get("ema_decay") is not None:
+        assert torch.isnan(s.mg._ema).any() and s.mg.n_averaged == 1, s.backend
+    if s.features.get("spectral_norm"):
+        assert torch.isnan(s.md.sn_u).any() and torch.isnan(s.md.sn_v).any(), s.backend
+    if s.features.get("grad_penalty"):
+        means, steps = gp_record(s.engine, reset=False)
+        assert steps[0] == 1 and np.isfinite(means).all() and means.all(), (s.backend, means, steps)
     s.restore(snap)
     return snap
 
@@ -479,3 +637,152 @@ def run_pair(backend, history):
     snap = wear(worn) or worn.snapshot()
     twin = Session(backend, "fresh", options=worn.options, snapshot=snap)
     return probe(worn), probe(twin)
+
+
+# ---------------------------------------------------------------------------------------------
+# the features' own histories (FEATURE_PAIRS).  Each asserts its premise: that it wore the state it names.
+# ---------------------------------------------------------------------------------------------
+def _gp_steps(s):
+    return int(gp_record(s.engine, reset=False)[1][0])
+
+
+def _h_feature_off_and_on(s):
+    """Every switch of the row goes off (the penalty, the clip, the objective to another one that fits the same discriminator) for one
+    train step at BIG and comes back; a penalised row then takes one step under the other kind and another weight."""
+    import torch
+    from gantts_amd import _lib as L
+    eng, ft = s.engine, s.features
+    gp, clip, obj = ft.get("grad_penalty"), ft.get("weight_clip"), ft.get("objective", "bce")
+    assert gp or clip or obj != "bce", s.backend
+    steps0 = _gp_steps(s) if gp else 0
+    if gp:
+        eng.set_grad_penalty(None)
+    if clip:
+        eng.set_weight_clip(L.ROLE_D, 0.0)
+    if obj != "bce":
+        assert LAST_SIGMOID[AWAY_OBJECTIVE[obj]] == LAST_SIGMOID[obj]
+        eng.set_option("gan_objective", L.GAN_OBJECTIVES[AWAY_OBJECTIVE[obj]])
+    s.step(shape_batch(s.backend, "BIG", 6301), "train")
+    # the premises: no penalty was recorded; no parameter was clamped (the unclipped network has weights beyond the bound)
+    if gp:
+        assert eng.grad_penalty is None and _gp_steps(s) == steps0, (s.backend, steps0, _gp_steps(s))
+    if clip:
+        assert float(s.md.flat_params().abs().max()) > clip, s.backend
+    if obj != "bce":
+        assert eng.gan_objective == AWAY_OBJECTIVE[obj]
+        eng.set_option("gan_objective", L.GAN_OBJECTIVES[obj])
+    if clip:
+        eng.set_weight_clip(L.ROLE_D, clip)
+    if gp:
+        other = "wgan-gp" if gp[0] == "r1" else "r1"      # (either kind is allowed under every objective)
+        eng.set_grad_penalty(other, 0.5 * gp[1] + 1.0)
+        s.step(shape_batch(s.backend, "BIG", 6302), "train")
+        assert _gp_steps(s) == steps0 + 1, (s.backend, _gp_steps(s))
+        eng.set_grad_penalty(*gp)
+    torch.cuda.synchronize()
+
+
+def _h_gp_hooks(s):
+    """The parity hooks around a step at BIG: injected interpolation weights, and the two readers in between.  Reading changes nothing."""
+    import torch
+    eng, (kind, _) = s.engine, s.features["grad_penalty"]
+    B, Tn = SHAPES["BIG"]
+    eps = torch.from_numpy(np.random.RandomState(6401).rand(B * Tn).astype(np.float32)).cuda()
+    steps0 = _gp_steps(s)
+    eng.set_gp_epsilon(eps)
+    seen = {}
+
+    def between(out):
+        seen["record"] = gp_record(eng, reset=False)
+        if kind == "wgan-gp":
+            e_, xh = eng.grad_penalty_peek(B * Tn, eng._adv_width())
+            seen["eps"], seen["x_hat"] = e_.cpu().numpy(), xh.cpu().numpy()
+
+    s.step(shape_batch(s.backend, "BIG", 6402), "train", after_d=between)
+    eng.set_gp_epsilon(None)
+    assert seen["record"][1][0] == steps0 + 1 and np.isfinite(seen["record"][0]).all(), (s.backend, seen["record"])
+    if kind == "wgan-gp":      # the premise: the step interpolated with the injected weights
+        assert np.array_equal(seen["eps"].view(np.uint32), eps.cpu().numpy().view(np.uint32)) and np.isfinite(seen["x_hat"]).all(), s.backend
+    assert _gp_steps(s) == steps0 + 1
+
+
+def _h_sn_other_d(s):
+    """other_d with a second spectrally normalised MLP of other widths (a new job table, W_eff of another size, its own sn_u / sn_v), one
+    D-only train step; then an eval-phase step at BIG with the first discriminator, which must leave its sn_u / sn_v alone."""
+    import torch
+    from gantts_amd import optim
+    spec = dict(s.case["d"], num_hidden=2, hidden_dim=24, dropout=0.0, in_dim=s.md.in_dim)
+    assert (spec["num_hidden"], spec["hidden_dim"]) != (s.case["d"]["num_hidden"], s.case["d"]["hidden_dim"])
+    md2 = build_sn_mlp(spec, 33)
+    od2 = optim.Adagrad(md2.parameters(), lr=0.01)
+    u2 = md2.sn_u.clone()
+    s.step(shape_batch(s.backend, "probe", 6501), "train", update_g=False, model_d=md2, optimizer_d=od2)
+    assert not torch.equal(md2.sn_u, u2), "the second discriminator's pass did not iterate"
+    u, v = s.md.sn_u.clone(), s.md.sn_v.clone()
+    s.step(shape_batch(s.backend, "BIG", 6502), "test")
+    torch.cuda.synchronize()
+    assert torch.equal(s.md.sn_u.view(torch.int32), u.view(torch.int32)) and torch.equal(s.md.sn_v.view(torch.int32), v.view(torch.int32)), \
+        "%s: an eval-phase step advanced sn_u / sn_v" % s.backend
+
+
+def _h_ema_swap_and_roles(s):
+    """An eval-phase step at BIG on the averaged weights, a discriminator-only train step (the average stays), a generator-only one (it moves)."""
+    import torch
+    mg, eng = s.mg, s.engine
+    params, count = mg.flat_params().detach().clone(), mg.n_averaged
+    mg.eval()
+    with mg.averaged_weights():
+        s.step(shape_batch(s.backend, "BIG", 6601), "test")
+    s.train_mode()
+    assert torch.equal(mg.flat_params().view(torch.int32), params.view(torch.int32)) and mg.n_averaged == count == eng.param_ema_count()
+    s.step(shape_batch(s.backend, "probe", 6602), "train", update_g=False)
+    assert mg.n_averaged == count == eng.param_ema_count(), (s.backend, mg.n_averaged, eng.param_ema_count())
+    s.step(shape_batch(s.backend, "probe", 6603), "train", update_d=False)
+    assert mg.n_averaged == count + 1 == eng.param_ema_count(), (s.backend, mg.n_averaged, eng.param_ema_count())
+
+
+def _h_normaliser(s):
+    """The penalty reads 1 / Tv where the head does (LossNormaliser::inv_tv); sharding is refused under a penalty, so the override alone."""
+    s.engine.set_loss_normalizer(123.0)
+    s.step(shape_batch(s.backend, "BIG", 6701), "train")
+    s.engine.set_loss_normalizer(-1.0)
+
+
+def _h_feature_shard_and_normaliser(s):
+    """shard_and_normaliser; where the engine refuses the shard (spectral norm), the refusal by its message, then the override alone on
+    the engine that refused."""
+    if not s.features.get("spectral_norm"):
+        return _h_shard_and_normaliser(s)
+    s.step(shape_batch(s.backend, "probe", 6801), "train")      # (binds the discriminator: the normalisation is the bound network's)
+    try:
+        s.engine.set_shard(1, 2)
+    except ValueError as e:
+        assert "gt_set_shard: spectral normalisation" in str(e), str(e)
+    else:
+        raise AssertionError("%s: set_shard(1, 2) was not refused" % s.backend)
+    s.engine.set_shard(0, 1)
+    return _h_normaliser(s)
+
+
+_BIG2 = (_P, SHAPES["BIG"])
+FEATURE_HISTORIES = {
+    "feature_off_and_on": (_BIG2, _h_feature_off_and_on),
+    "gp_hooks": (_BIG2, _h_gp_hooks),
+    "sn_other_d": (_BIG2, _h_sn_other_d),
+    "ema_swap_and_roles": (_BIG2, _h_ema_swap_and_roles),
+    "normaliser": (_BIG2, _h_normaliser),
+    "shard_and_normaliser": (_BIG2, _h_feature_shard_and_normaliser),
+}
+
+
+def feature_history(name):
+    return FEATURE_HISTORIES[name] if name in FEATURE_HISTORIES else HISTORIES[name]
+
+
+def run_feature_pair(backend, history):
+    """run_pair for the FEATURE_PAIRS: the features' histories first, feature_probe on both sides"""
+    shapes, wear = feature_history(history)
+    worn = Session(backend, "inplace", shapes=shapes)
+    snap = wear(worn) or worn.snapshot()
+    twin = Session(backend, "fresh", options=worn.options, snapshot=snap)
+    return feature_probe(worn), feature_probe(twin)

@@ -143,6 +143,87 @@ def test_the_communicating_backends_have_a_table_and_a_pair_list_of_their_own():
     assert set(h for _, h in H.COMM_PAIRS) <= set(H.HISTORIES) and not any(b.get("comm") for b in H.BACKENDS.values())
 
 
+EXPECTED_FEATURE_BACKENDS = ["wgan_clip", "hinge_fused", "ls_lstm_d", "sn_hinge", "sn_bce_bf16", "gp_r1", "gp_r1_fused", "gp_wgan_split", "gp_wgan_cat",
+                             "ema_adagrad", "ema_adam", "all_wgan"]
+
+
+def test_every_feature_backend_names_an_existing_case_that_fits_its_settings():
+    from gantts_amd.engine import StepEngine
+    import inspect
+    known = inspect.getsource(StepEngine.set_option)
+    assert list(H.FEATURE_BACKENDS) == EXPECTED_FEATURE_BACKENDS and not set(H.FEATURE_BACKENDS) & (set(H.BACKENDS) | set(H.COMM_BACKENDS))
+    for name, b in H.FEATURE_BACKENDS.items():
+        case, ft = H.backend_case(name), H.backend_features(name)
+        assert case["update_d"] and case["update_g"] and case["adv_w"] > 0 and not b.get("comm"), name
+        assert ft and set(b) <= {"case", "options", "flip"} | set(H.FEATURE_KEYS), name
+        # the discriminator's last_sigmoid fits the objective (check_gan_objective refuses the bind otherwise)
+        obj = ft.get("objective", "bce")
+        assert obj in H.LAST_SIGMOID and bool(case["d"]["last_sigmoid"]) == H.LAST_SIGMOID[obj], (name, obj)
+        if obj != "bce":
+            assert H.LAST_SIGMOID[H.AWAY_OBJECTIVE[obj]] == H.LAST_SIGMOID[obj] and H.AWAY_OBJECTIVE[obj] != obj
+        # the engine refuses penalty and spectral norm together, either of them on a recurrent discriminator, a penalty under bf16 products
+        assert not (ft.get("grad_penalty") and ft.get("spectral_norm")), name
+        if ft.get("grad_penalty") or ft.get("spectral_norm"):
+            assert case["d"]["kind"] == "MLP", name
+        if ft.get("grad_penalty"):
+            assert ft["grad_penalty"][0] in ("r1", "wgan-gp") and ft["grad_penalty"][1] > 0 and not b["options"].get("matmul_bf16"), name
+        if ft.get("ema_decay") is not None:
+            assert 0.0 < ft["ema_decay"] < 1.0 and case["g"]["kind"] == "MLP", name
+        # options and the flip, as for the old rows
+        for opt, v in b["options"].items():
+            assert v in H.OPTION_VALUES[opt], (name, opt, v)
+        opt, home, away = b["flip"]
+        assert '"%s"' % opt in known and home != away and home in H.OPTION_VALUES[opt] and away in H.OPTION_VALUES[opt], (name, b["flip"])
+        assert b["options"].get(opt, home) == home and (opt in b["options"] if b["options"] else b["flip"] == ("launch_riders", 1, 0)), name
+        assert case["dropout_on"] or name == "ema_adam", name          # Philox on, nothing injected
+        assert case["din"] % 4 != 0 or name.startswith("ema_"), name    # dense rows of x are not 16-byte pitched: the per-step copies are made
+    # the paths the rows were picked for
+    fb, case_of = H.FEATURE_BACKENDS, H.backend_case
+    assert case_of("hinge_fused")["d"]["hidden_dim"] == 128 == case_of("gp_r1_fused")["d"]["hidden_dim"]
+    assert fb["hinge_fused"]["options"] == fb["gp_r1_fused"]["options"] == {"fused_dstack": 2}
+    assert case_of("ls_lstm_d")["d"]["kind"] == "LSTMRNN"
+    assert fb["sn_bce_bf16"]["options"] == {"matmul_bf16": 1} and "objective" not in fb["sn_bce_bf16"]
+    assert case_of("gp_wgan_split")["cond"] and not fb["gp_wgan_split"]["options"] and fb["gp_wgan_cat"]["options"] == {"split_first_layer": 0}
+    assert case_of("gp_wgan_cat") == case_of("gp_wgan_split") and case_of("gp_r1")["cond"] and case_of("sn_hinge")["cond"]
+    assert case_of("ema_adagrad")["opt_g"][0] == "Adagrad" and case_of("ema_adam")["opt_g"][0] == "Adam"
+    assert set(H.backend_features("all_wgan")) == {"objective", "weight_clip", "grad_penalty", "ema_decay"}
+    # a bce row runs the reference's discriminator, every other one the case as it is
+    import gan_objective_ref as G
+    assert case_of("gp_r1") == G.bce_twin(G.STEP_CASES["mlp32_cond"]) and case_of("sn_hinge") == G.STEP_CASES["mlp32_cond"]
+
+
+def test_the_feature_pairs_have_a_pair_list_of_their_own():
+    FB = H.FEATURE_BACKENDS
+    assert len(H.FEATURE_PAIRS) == len(set(H.FEATURE_PAIRS)) and not set(H.FEATURE_PAIRS) & (set(H.PAIRS) | set(H.COMM_PAIRS))
+    assert set(b for b, _ in H.FEATURE_PAIRS) == set(FB)
+    for b in FB:          # every row runs the seven histories of the old rows
+        assert [h for bb, h in H.FEATURE_PAIRS if bb == b][:7] == list(H.HISTORIES_ALL)
+
+    def rows_of(history):
+        return sorted(b for b, h in H.FEATURE_PAIRS if h == history)
+    gp = sorted(b for b in FB if FB[b].get("grad_penalty"))
+    assert gp == sorted(["gp_r1", "gp_r1_fused", "gp_wgan_split", "gp_wgan_cat", "all_wgan"]) == rows_of("gp_hooks")
+    assert rows_of("feature_off_and_on") == sorted(set(gp) | {"wgan_clip", "hinge_fused", "ls_lstm_d", "sn_hinge"})
+    assert rows_of("sn_other_d") == ["sn_bce_bf16", "sn_hinge"] == sorted(b for b in FB if FB[b].get("spectral_norm"))
+    assert rows_of("ema_swap_and_roles") == ["all_wgan", "ema_adagrad", "ema_adam"] == sorted(b for b in FB if "ema_decay" in FB[b])
+    for h in ("phase_and_roles", "abandoned_passes", "split_phase"):
+        assert rows_of(h) == ["ema_adam", "gp_wgan_split", "sn_hinge"], h
+    assert rows_of("normaliser") == ["gp_wgan_split"] and rows_of("shard_and_normaliser") == ["ema_adam", "sn_hinge"]
+    assert len(H.FEATURE_PAIRS) == 12 * 7 + 9 + 5 + 2 + 3 + 3 * 3 + 3
+    # every history of a feature pair exists, lists the probe shape and, where it steps at BIG, that one too
+    probe = H.SHAPES["probe"]
+    assert not set(H.FEATURE_HISTORIES) & (set(H.HISTORIES) - {"shard_and_normaliser"})
+    for name in set(h for _, h in H.FEATURE_PAIRS):
+        shapes, wear = H.feature_history(name)
+        assert probe in shapes and callable(wear), name
+    for name, (shapes, wear) in H.FEATURE_HISTORIES.items():
+        assert probe in shapes and H.SHAPES["BIG"] in shapes and callable(wear), name
+    assert H.feature_history("shard_and_normaliser")[1] is not H.HISTORIES["shard_and_normaliser"][1]      # (it asserts the refusal under spectral norm)
+    # the old tables are what they were
+    assert len(H.PAIRS) == 17 * 7 + 3 * 5 and len(H.COMM_PAIRS) == 10
+    assert set(H.ALL_BACKENDS) == set(H.BACKENDS) | set(H.COMM_BACKENDS) | set(FB)
+
+
 def test_batches_are_cached_per_shape_and_poison_covers_the_valid_frames():
     a, b = H.shape_batch("mlp_cond_split", "BIG", 1), H.shape_batch("mlp_cond_split", "BIG", 1)
     assert a is b and not a["x"].flags.writeable
