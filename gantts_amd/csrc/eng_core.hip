@@ -150,7 +150,7 @@ extern "C" void gt_engine_destroy(gt_engine* e) {
     if (e->len_ev[i]) (void)hipEventDestroy(e->len_ev[i]);
   }
   Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
-                    &e->cx_dense.buf, &e->dx_pitched.buf, &e->gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
+                    &e->din.cx_dense.buf, &e->din.dx_pitched.buf, &e->din.gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
                     &e->mlpg.fac, &e->mlpg.wide, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2, &e->mlpg_var_ws};
   for (auto* s : all) s->release();
   e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
@@ -339,7 +339,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
     CHK(upload_ints(ss, &e->d_sstride_i2o));
     if (sd != desc->static_dim) return fail(GT_ERR_DIM, "In2OutHighwayNet: out_dim/num_windows (%d) != static_dim (%d)", sd, desc->static_dim);
   }
-  if (role == GT_ROLE_G) e->g_pass_valid = false;
+  if (role == GT_ROLE_G) on_generator_rebound(e);
   return GT_OK;
 }
 
@@ -395,8 +395,7 @@ extern "C" int gt_set_seed(gt_engine* e, uint64_t seed) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   e->seed = seed;
   e->step_counter = 0;
-  // the step count is part of the per-step copies' key and has just gone back: none of them is this step's any more
-  e->dx_pitched.forget(); e->gx_pitched.forget(); e->cx_dense.forget();
+  on_reseed(e);
   return GT_OK;
 }
 extern "C" int gt_set_dropout_mask(gt_engine* e, int role, int pass, int layer, const float* mask) {
@@ -411,7 +410,7 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
     case GT_OPT_LSTM_FWD_UNITS: e->lstm_fwd_upc = value; return GT_OK;
     case GT_OPT_LSTM_XCD_LOCAL: e->lstm_xcd_local = value != 0; return GT_OK;
     case GT_OPT_SPLIT_FIRST_LAYER:
-      if (e->opt_split_first != (value != 0)) invalidate_d_images(e);
+      if (e->opt_split_first != (value != 0)) on_first_layer_route_changed(e);
       e->opt_split_first = value != 0;
       return GT_OK;
     case GT_OPT_COMM_D_ONE_MSG: e->opt_comm_d_one_msg = value != 0; return GT_OK;
@@ -424,26 +423,18 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
     case GT_OPT_POLL_RESULTS: e->opt_poll_results = value != 0; return GT_OK;
     case GT_OPT_LAUNCH_RIDERS: e->opt_launch_riders = value != 0; return GT_OK;
     case GT_OPT_MATMUL_BF16:
-      // the storage precision belongs to a PASS: buffers of a stashed forward pass (bf16 images vs float32 stashes) are not
-      // interchangeable, so a change drops whatever is stashed -- the next update_* then asks for a fresh apply_generator
-      // instead of back-propagating through buffers the forward never filled
-      if (e->matmul_bf16 != (value != 0)) {
-        invalidate_d_images(e);
-        e->g_pass_valid = false; e->leak.drop(); e->cx_dense.forget(); e->results.forget_begin();
-      }
+      if (e->matmul_bf16 != (value != 0)) on_storage_form_changed(e);
       e->matmul_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_SRU_D_BF16:
       if (value != 0 && value != 1) return fail(GT_ERR_INVALID, "GT_OPT_SRU_D_BF16 takes 0 or 1, not %d", value);
-      // (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
-      if (e->sru_d_bf16 != (value != 0)) { invalidate_d_images(e); e->leak.drop(); e->results.forget_begin(); }
+      if (e->sru_d_bf16 != (value != 0)) on_sru_d_storage_form_changed(e);
       e->sru_d_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_GAN_OBJECTIVE:
       if (value < 0 || value >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE takes 0 (bce), 1 (ls), 2 (hinge) or 3 (wgan), not %d", value);
       if (e->net[GT_ROLE_D].bound) CHK(gan_objective_fits(value, e->net[GT_ROLE_D].d.last_sigmoid != 0));
-      // (a discriminator pass begun under one objective is not finished, and its kept gradient not used, under another)
-      if (e->gan_objective != value) { e->leak.drop(); e->results.forget_begin(); }
+      if (e->gan_objective != value) on_objective_changed(e);
       e->gan_objective = value;
       return GT_OK;
   }
@@ -532,8 +523,7 @@ extern "C" int gt_zero_grad(gt_engine* e, int role) {
   if (!e || role < 0 || role > 1) return fail(GT_ERR_INVALID, "bad argument");
   e->net[role].grads_dirty = false;   // lazily: the next backward overwrites
   e->ws[role].sdefer.reset(false);      // nothing recorded survives a zero_grad
-  e->norm.forget();
-  if (role == GT_ROLE_G) e->leak.drop();
+  on_zero_grad(e, role);
   return GT_OK;
 }
 extern "C" int gt_scalar_buffer(gt_engine* e, double** dev_ptr, int* n) {
@@ -645,8 +635,7 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   // the skipped generator updates left the weight average untouched as well (they returned before any element)
   if (e->ema.buf) e->ema.count = std::max(0L, e->ema.count - (long)e->h_fault[2 + GT_ROLE_G]);
   for (int i = 0; i < 4; ++i) e->h_fault[i] = 0;
-  invalidate_d_images(e);
-  e->g_pass_valid = false; e->leak.drop(); e->cx_dense.forget(); e->results.reset();
+  on_faults_cleared(e);
   return GT_OK;
 }
 extern "C" int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset) {

@@ -136,7 +136,7 @@ extern "C" int gt_set_grad_penalty(gt_engine* e, int role, int kind, float weigh
     CHK(G.rec.ensure(3 * sizeof(double)));
     HIPCHK(hipMemset(G.rec.p, 0, 3 * sizeof(double)));
   }
-  if (was != kind) e->results.forget_begin();      // (a D step begun under one setting is not finished under another)
+  if (was != kind) on_penalty_kind_changed(e);
   return GT_OK;
 }
 extern "C" int gt_set_gp_epsilon(gt_engine* e, const float* eps) {

@@ -75,7 +75,7 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
                 "R = (W^T W)^-1 W^T decays (hparams.py:22-26) are supported", kb, T);
   MlpgBand* b = nullptr;
   if (m.entries.size() >= MlpgCache::MAX_ENTRIES) {      // recycle the least recently used entry, the stashed generator pass's band apart
-    const MlpgBand* held = e->g_pass_valid ? e->g_band : nullptr;
+    const MlpgBand* held = e->pass.live() ? e->pass.band() : nullptr;
     for (auto* c : m.entries) if (c != held && (!b || c->last_use < b->last_use)) b = c;
     HIPCHK(hipStreamSynchronize(s));                      // its band may still be read by queued kernels
   } else {
@@ -92,14 +92,10 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
   *out = b;
   return GT_OK;
 }
-// the stashed generator pass would transpose through a band that is about to be freed: it can no longer be back-propagated
-static void drop_pass_of(gt_engine* e, const MlpgBand* b) {
-  if (e->g_band == b) { e->g_band = nullptr; e->g_pass_valid = false; e->leak.drop(); }
-}
 extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   HIPCHK(hipDeviceSynchronize());
-  for (auto* b : e->mlpg.entries) drop_pass_of(e, b);
+  for (auto* b : e->mlpg.entries) on_band_freed(e, b);
   e->mlpg.clear();
   return GT_OK;
 }
@@ -127,7 +123,7 @@ extern "C" int gt_set_mlpg_windows(gt_engine* e, int n, const int32_t* l, const 
   for (size_t i = 0; i < m.entries.size();) {
     MlpgBand* b = m.entries[i];
     if (b->R != GT_MLPG_R_FROM_WINDOWS) { ++i; continue; }
-    drop_pass_of(e, b);
+    on_band_freed(e, b);
     b->band.release();
     delete b;
     m.entries.erase(m.entries.begin() + i);

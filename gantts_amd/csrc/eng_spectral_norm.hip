@@ -158,13 +158,13 @@ extern "C" int gt_set_spectral_norm(gt_engine* e, int role, float* u, float* v, 
     const bool was = S.on;
     S.on = false; S.u = S.v = nullptr;
     if (S.plan) { sn_plan_free(S.plan); S.plan = nullptr; }
-    if (was) { sn_point_weights(e); invalidate_d_images(e); e->leak.drop(); e->results.forget_begin(); }
+    if (was) { sn_point_weights(e); on_spectral_norm_off(e); }
     return GT_OK;
   }
   if (!e->net[GT_ROLE_D].bound) return fail(GT_ERR_STATE, "gt_set_spectral_norm: bind the discriminator first (the lengths are checked against it)");
   const bool was = S.on;
   CHK(sn_install(e, u, v, (long)n_u, (long)n_v));
-  if (!was) { e->leak.drop(); e->results.forget_begin(); }      // (a pass begun without the feature is not finished with it)
+  if (!was) on_spectral_norm_on(e);
   return GT_OK;
 }
 // gt_bind_model(role D) while the feature is on: the registered buffers must fit the new network too

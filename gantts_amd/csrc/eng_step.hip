@@ -309,13 +309,13 @@ static OutTop mlp_top(gt_engine* e, int role, bool b16) {
 }
 
 // row pitch of the generator's input / of the conditioning x (gt_set_x_pitch; dense by default)
-static int gx_pitch(const gt_engine* e) { return (e->ld_gx > 0 && !e->gx_dense_on) ? e->ld_gx : e->net[GT_ROLE_G].d.in_dim; }
+static int gx_pitch(const gt_engine* e) { return (e->ld_gx > 0 && !e->pass.input_dense()) ? e->ld_gx : e->net[GT_ROLE_G].d.in_dim; }
 static int cx_pitch(gt_engine* e) { return e->ld_cx > 0 ? e->ld_cx : cond_dim(e); }
 // the generator input as the network can read it: pitched rows (gt_set_x_pitch) stay where they are for the float32 MLP generator;
-// every other generator reads a dense copy made here (the copy is also what its backward pass reads: e->last_x)
+// every other generator reads a dense copy made here (the copy is also what its backward pass reads: GenPass::input)
 static int dense_gx(gt_engine* e, const float** x, long N, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
-  e->gx_dense_on = false;
+  e->pass.input_dense(false);
   if (e->ld_gx <= 0 || e->ld_gx == G.d.in_dim) return GT_OK;
   if (e->ld_gx < G.d.in_dim) return fail(GT_ERR_INVALID, "gt_set_x_pitch: pitch %d for %d generator input columns", e->ld_gx, G.d.in_dim);
   if (G.d.arch == GT_ARCH_MLP && !use_b16(e, GT_ROLE_G)) return GT_OK;
@@ -323,7 +323,7 @@ static int dense_gx(gt_engine* e, const float** x, long N, hipStream_t s) {
   launch_copy_cols(*x, e->ld_gx, 0, e->gx_dense.as<float>(), G.d.in_dim, 0, N, G.d.in_dim, s);
   LAUNCH_CHECK();
   *x = e->gx_dense.as<float>();
-  e->gx_dense_on = true;
+  e->pass.input_dense(true);
   return GT_OK;
 }
 // the conditioning x of the discriminator passes that cannot read pitched rows (no split first layer): a dense copy, once per step
@@ -331,7 +331,7 @@ static int dense_cx(gt_engine* e, const float** x, long N, hipStream_t s) {
   if (!*x || !e->cfg.discriminator_linguistic_condition || e->ld_cx <= 0 || e->ld_cx == cond_dim(e)) return GT_OK;
   const int cd = cond_dim(e);
   if (e->ld_cx < cd) return fail(GT_ERR_INVALID, "gt_set_x_pitch: pitch %d for %d conditioning columns", e->ld_cx, cd);
-  return step_copy(e, e->cx_dense, *x, e->ld_cx, cd, N, cd, true, x, s);
+  return step_copy(e, e->din.cx_dense, *x, e->ld_cx, cd, N, cd, true, x, s);
 }
 
 static int generator_forward(gt_engine* e, const float* x, const float* R, int B, int T, float* y_hat, float* y_hat_static,
@@ -371,7 +371,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     const int sd = G.d.static_dim;
     const MlpgBand* band;
     CHK(ensure_band(e, R, T, s, &band));
-    if (stash) e->g_band = band;
+    if (stash) e->pass.went_through(band);
     CHK(e->tx.ensure((size_t)N * sd * sizeof(float)));
     CHK(e->gx.ensure((size_t)N * sd * sizeof(float)));
     // T(x) = sigmoid(T x_static), x_static = x[:, :, :static_dim]   (models.py:57-60)
@@ -385,11 +385,11 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     if (R) {
       const MlpgBand* band;
       CHK(ensure_band(e, R, T, s, &band));
-      if (stash) e->g_band = band;
+      if (stash) e->pass.went_through(band);
       CHK(mlpg_forward(e, y_hat, G.d.out_dim, e->d_scol, e->d_sstride, e->Ds, y_hat_static, e->Ds, B, T, *band, s));
     } else {
       if (e->Ds != G.d.out_dim) return fail(GT_ERR_INVALID, "R is None but the stream config has dynamic features");
-      if (stash) e->g_band = nullptr;
+      if (stash) e->pass.went_through(nullptr);
       // R is None: num_windows = 1, every stream passes through (multistream.py:88-89,119-120)
       launch_copy_cols(y_hat, G.d.out_dim, 0, y_hat_static, G.d.out_dim, 0, N, G.d.out_dim, s);
       LAUNCH_CHECK();
@@ -407,17 +407,9 @@ extern "C" int gt_apply_generator(gt_engine* e, const float* x, const float* R, 
   hipStream_t s = (hipStream_t)stream;
   CHK(fault_seen(e));
   e->step_counter++;
-  e->B = B; e->T = T; e->N = (long)B * T;
-  e->g_pass_valid = false;
-  invalidate_d_images(e);
-  // no StepCopy outlives a batch: the step count alone does not tell two batches apart (gt_set_seed restarts it, and a staging buffer
-  // refilled in place has the same pointer, pitch and shape).  Both update calls of a batch come behind this one: they still share a copy.
-  e->dx_pitched.forget(); e->gx_pitched.forget(); e->cx_dense.forget();
-  e->norm.forget();             // a new batch: the mask contents may have changed
+  on_new_batch(e);
   CHK(generator_forward(e, x, R, B, T, y_hat, y_hat_static, true, s, e->ws[GT_ROLE_G].specs));
-  e->last_x = e->gx_dense_on ? e->gx_dense.as<float>() : x;      // (what the backward pass reads: the dense copy when one was made)
-  e->last_yhat = y_hat; e->last_yhs = y_hat_static;
-  e->g_pass_valid = true;
+  e->pass.stash(B, T, e->pass.input_dense() ? e->gx_dense.as<float>() : x, y_hat, y_hat_static);
   return GT_OK;
 }
 
@@ -832,20 +824,20 @@ static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's
     CHK(dense_cx(e, &p.x, N, s));
     p.cat0.x = p.x;
   }
-  if (both) invalidate_d_images(e);
+  if (both) e->din.invalidate_d_images();
   if (p.kind == D_MLP_B16) {
     CHK(e->dcat_b.ensure(2 * N, p.K0, p.want_w));
-    if (both || !e->img_cat_b.holds(p.x, p.fake)) {
+    if (both || !e->din.img_cat_b.holds(p.x, p.fake)) {
       CHK(cat_cast_transpose(p.cat0, p.rows, p.K0, e->dcat_b.r() + row0 * e->dcat_b.ld, e->dcat_b.ld, p.want_w ? e->dcat_b.t() : (__bf16*)nullptr,
                              p.want_w ? e->dcat_b.ldt : 0L, s));
-      e->img_cat_b.built(p.x, p.fake);
+      e->din.img_cat_b.built(p.x, p.fake);
     }
   } else if (p.split) {
     // only the adversarial columns are gathered (58 of 483 columns at cfg2)
     const int ld = e->ld_adv2 = p.fs.ld_adv;
     CHK(e->adv2.ensure((size_t)2 * N * ld * sizeof(float)));
     float* dst = e->adv2.as<float>() + row0 * ld;
-    if (both || !e->img_adv2.holds(nullptr, p.fake)) {
+    if (both || !e->din.img_adv2.holds(nullptr, p.fake)) {
       BuildAdvArgs ba;
       memset(&ba, 0, sizeof(ba));
       ba.fa = p.cat0.fa; ba.fb = p.cat0.fb; ba.ldf = p.ldf; ba.idx = e->d_adv_cols; ba.na = e->Da; ba.out = dst; ba.ldo = ld; ba.split = N; ba.rows = p.rows;
@@ -853,10 +845,10 @@ static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's
       launch_build_adv(ba, s);
       LAUNCH_CHECK();
       if (tv) CHK(tv->rode(e, s));
-      e->img_adv2.built(nullptr, p.fake);
+      e->din.img_adv2.built(nullptr, p.fake);
     }
     p.fs.adv = dst;
-    if (p.want_w) CHK(pitched_rows(e, e->dx_pitched, p.x, p.fs.ldx, p.fs.cd, N, &p.fs.xp, &p.fs.ldxp, s));
+    if (p.want_w) CHK(pitched_rows(e, e->din.dx_pitched, p.x, p.fs.ldx, p.fs.cd, N, &p.fs.xp, &p.fs.ldxp, s));
   } else if (p.needs_f32_image) {
     CHK(e->dcat.ensure((size_t)2 * N * p.ldc * sizeof(float)));
     if (both && p.cat0.cd > 0) {
@@ -864,9 +856,9 @@ static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's
       LAUNCH_CHECK();
     } else {
       if (both) CHK(build_cat(e, p.x, p.real, p.ldf, 0, N, p.ldc, s));
-      if (both || !e->img_cat.holds(p.x, p.fake)) CHK(build_cat(e, p.x, p.fake, p.ldf, N, N, p.ldc, s));
+      if (both || !e->din.img_cat.holds(p.x, p.fake)) CHK(build_cat(e, p.x, p.fake, p.ldf, N, N, p.ldc, s));
     }
-    e->img_cat.built(p.x, p.fake);
+    e->din.img_cat.built(p.x, p.fake);
     p.img = e->dcat.as<float>() + row0 * p.ldc;
   }
   return GT_OK;
@@ -1014,7 +1006,7 @@ static int d_pass_penalty(gt_engine* e, DPass& p, const float* mask, hipStream_t
 int KeptLeak::claim(gt_engine* e, const float* y_hat_static, long N, float** out) {
   const Net& G = e->net[GT_ROLE_G];
   *out = nullptr;
-  if (!(G.bound && G.d.grads && e->g_pass_valid && y_hat_static == e->last_yhs && e->N == N)) return GT_OK;
+  if (!(G.bound && G.d.grads && e->pass.made(y_hat_static, N))) return GT_OK;
   if (pending) return fail(GT_ERR_STATE, "update_discriminator called twice without optimizer_g.zero_grad() (train.py:538)");
   CHK(buf.ensure((size_t)N * e->Da * sizeof(float)));
   *out = buf.as<float>();
@@ -1149,13 +1141,13 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
                               float mse_w, hipStream_t s) {
   Net& G = e->net[GT_ROLE_G];
   NetWs& W = e->ws[GT_ROLE_G];
-  const long N = e->N;
-  const int B = e->B, T = e->T, Do = G.d.out_dim;
+  const long N = e->pass.N();
+  const int B = e->pass.B(), T = e->pass.T(), Do = G.d.out_dim;
   // dloss/dy_hat is an engine buffer: for the MLP stacks its row pitch is rounded up to 4 floats, so that the last layer's
   // two backward products (K = out_dim = 187 for the acoustic model) take the 16-byte loader and the 64x64 tiles; the
   // pad column is never read as data (K tail / row clamp of the GEMM loader)
   const bool mlp_body = !(has_lstm_body(G.d.arch) || G.d.arch == GT_ARCH_SRU);
-  const int ldgy = mlp_body && e->g_band ? (Do + 3) & ~3 : Do;      // (In2Out always has one)
+  const int ldgy = mlp_body && e->pass.band() ? (Do + 3) & ~3 : Do;      // (In2Out always has one)
   CHK(e->gy.ensure((size_t)N * ldgy * sizeof(float)));
   float* gy = e->gy.as<float>();
   const float* gs = e->gs.as<float>();
@@ -1169,9 +1161,9 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, product_prec(e, GT_ROLE_G), s,
                                &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.gate.dW, (long)sd * sd + sd, s));
-    CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o, e->d_sstride_i2o, sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->g_band, s));
-  } else if (e->g_band) {
-    CHK(mlpg_backward(e, gs, e->Ds, e->d_scol, e->d_sstride, e->Ds, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->g_band, s));
+    CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o, e->d_sstride_i2o, sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
+  } else if (e->pass.band()) {
+    CHK(mlpg_backward(e, gs, e->Ds, e->d_scol, e->d_sstride, e->Ds, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
   } else {
     // no parameter generation: y_hat_static == y_hat, the gradient passes straight through,
     // plus the masked-MSE gradient (which also yields loss_mse's sum)
@@ -1209,11 +1201,11 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
   const float* xin = x;
   int ldxin = gx_pitch(e);
   if (!gemm_vec_ok(x, ldxin) && product_prec(e, GT_ROLE_G) == PREC_F32) {
-    if (e->img_cat.valid && e->img_cat.x == x && e->cfg.discriminator_linguistic_condition && cond_dim(e) == G.d.in_dim && e->dcat.p) {
+    if (e->din.img_cat.valid && e->din.img_cat.x == x && e->cfg.discriminator_linguistic_condition && cond_dim(e) == G.d.in_dim && e->dcat.p) {
       ldxin = (d_in_dim(e) + 3) & ~3;
       xin = e->dcat.as<float>() + N * ldxin;      // the generated half: the one that is valid whenever img_cat is
     } else {
-      StepCopy& M = e->dx_pitched.holds(x, gx_pitch(e), G.d.in_dim, N, e->step_counter) ? e->dx_pitched : e->gx_pitched;
+      StepCopy& M = e->din.dx_pitched.holds(x, gx_pitch(e), G.d.in_dim, N, e->step_counter) ? e->din.dx_pitched : e->din.gx_pitched;
       CHK(pitched_rows(e, M, x, gx_pitch(e), G.d.in_dim, N, &xin, &ldxin, s));
     }
   }
@@ -1236,7 +1228,7 @@ struct GPlan {
   // where the reported sums of squares and the head's partials are reduced: launches of their own; the finalisation launch; riders -- both sums of squares in ONE launch,
   enum { SUMS_OWN, SUMS_FOLDED, SUMS_RIDERS } sums;      // the head's scalars and the finalisation as one extra workgroup of the gradient assembly: four launches become two
   enum { REPORT_AT_END, REPORT_EARLY, REPORT_EARLY_COMM } report;      // by _end; early from this stream; early from the communicator's stream
-  GPlan(gt_engine* e, bool train, float mse_w) : mse_in_backward(train && !e->g_band && mse_w != 0.f) {
+  GPlan(gt_engine* e, bool train, float mse_w) : mse_in_backward(train && !e->pass.band() && mse_w != 0.f) {
     const bool fused = e->results.early && !mse_in_backward, comm = comm_on(e);
     sums = !fused ? SUMS_OWN : e->opt_launch_riders ? SUMS_RIDERS : comm ? SUMS_OWN : SUMS_FOLDED;
     report = !fused ? REPORT_AT_END : !comm ? REPORT_EARLY : e->opt_comm_early_g ? REPORT_EARLY_COMM : REPORT_AT_END;
@@ -1257,7 +1249,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   const long N = (long)B * T;
   const bool tr = train != 0;
   if (tr) {
-    if (!e->g_pass_valid || y_hat != e->last_yhat || y_hat_static != e->last_yhs || N != e->N)
+    if (!e->pass.is(y_hat, y_hat_static, N))
       return fail(GT_ERR_STATE, "update_generator(phase=\"train\") needs the y_hat / y_hat_static returned by the last apply_generator");
     if (!G.d.grads) return fail(GT_ERR_STATE, "phase == \"train\" but the generator was bound without grads");
   }
@@ -1341,7 +1333,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
   const bool comm_early = plan.report == GPlan::REPORT_EARLY_COMM;
   if (comm_early) CHK(comm_early_results(e, GT_ROLE_G, &e->sc()->s_adv, 3, adv_w, mse_w, mge_w, s));
   if (tr) {
-    CHK(generator_backward(e, e->last_x, y, y_hat, mask, mse_w, s));  // G's own input (cat(x, z), train.py:542)
+    CHK(generator_backward(e, e->pass.input(), y, y_hat, mask, mse_w, s));  // G's own input (cat(x, z), train.py:542)
     e->leak.drop();
   }
   CHK(comm_finish_step(e, GT_ROLE_G, tr, &e->sc()->s_adv, comm_early ? 0 : 3, s));
@@ -1380,11 +1372,11 @@ extern "C" int gt_update_generator(gt_engine* e, const float* x, const float* y,
 extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   Net& G = e->net[GT_ROLE_G];
-  if (!G.bound || !G.d.grads || !e->g_pass_valid) return fail(GT_ERR_STATE, "no generator pass to back-propagate");
+  if (!G.bound || !G.d.grads || !e->pass.live()) return fail(GT_ERR_STATE, "no generator pass to back-propagate");
   hipStream_t s = (hipStream_t)stream;
   CHK(fault_seen(e));
   e->ws[GT_ROLE_G].sdefer.reset(false);      // combines run in place here
-  const long N = e->N;
+  const long N = e->pass.N();
   const int Ds = is_i2o(G.d.arch) ? G.d.static_dim : e->Ds;
   CHK(e->gs.ensure((size_t)N * Ds * sizeof(float)));
   HIPCHK(hipMemsetAsync(e->gs.p, 0, (size_t)N * Ds * sizeof(float), s));
@@ -1397,7 +1389,7 @@ extern "C" int gt_flush_generator_grads(gt_engine* e, void* stream) {
     if (e->leak.unnormalised()) launch_scale_by_inv_tv(e->gs.as<float>(), N * Ds, e->sc(), s);
     LAUNCH_CHECK();
   }
-  CHK(generator_backward(e, e->last_x, e->last_yhat, e->last_yhat, (const float*)nullptr, 0.f, s));
+  CHK(generator_backward(e, e->pass.input(), e->pass.y_hat(), e->pass.y_hat(), (const float*)nullptr, 0.f, s));
   e->leak.drop();
   HIPCHK(hipStreamSynchronize(s));
   return GT_OK;
@@ -1418,7 +1410,7 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
   std::vector<DropoutSpec> specs;
   if (role == GT_ROLE_G && is_i2o(n.d.arch)) {
     if (!out2) return fail(GT_ERR_INVALID, "In2OutHighwayNet forward returns two tensors");
-    e->g_pass_valid = false;
+    on_generator_plain_forward(e);
     return generator_forward(e, x, R, B, T, out, out2, false, s, specs);
   }
   if (n.d.arch == GT_ARCH_LSTM || n.d.arch == GT_ARCH_SRU) {
@@ -1432,11 +1424,11 @@ extern "C" int gt_model_forward(gt_engine* e, int role, const float* x, const fl
       CHK(d_pass_forward(e, p, s));
       return out_layer_forward(e, role, OutTop{p.top, p.ld_top}, N, out, s);
     }
-    e->g_pass_valid = false;
+    on_generator_plain_forward(e);
     return n.d.arch == GT_ARCH_LSTM ? lstm_forward(e, x, B, T, out, s) : sru_forward(e, x, B, T, out, s);
   }
   const int pass0[1] = {0};
-  if (role == GT_ROLE_G) e->g_pass_valid = false;
+  if (role == GT_ROLE_G) on_generator_plain_forward(e);
   const bool b16 = use_b16(e, role);
   if (role == GT_ROLE_D) CHK(sn_prepare_pass(e, s));
   if (b16) {

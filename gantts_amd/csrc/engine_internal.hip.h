@@ -409,6 +409,47 @@ struct KeptLeak {
   Scratch buf; bool pending = false, unnorm = false;
 };
 
+// The stashed generator pass: what gt_apply_generator's forward left behind for the step's one backward pass (the training G step, or
+// gt_flush_generator_grads).  The activations themselves are ws[GT_ROLE_G]'s; this is which pass they are of, and whether they still are.
+struct GenPass {
+  // gt_apply_generator, after its forward has succeeded (dropped before it); x: what the backward pass reads, the dense copy when one was made
+  void stash(int B_, int T_, const float* x_, const float* y_hat, const float* y_hat_static) {
+    b = B_; t = T_; n = (long)B_ * T_; x = x_; yhat = y_hat; yhs = y_hat_static; valid = true;
+  }
+  void drop() { valid = false; }
+  bool live() const { return valid; }
+  bool is(const float* y_hat, const float* y_hat_static, long N_) const { return valid && yhat == y_hat && yhs == y_hat_static && n == N_; }      // the training G step's
+  bool made(const float* y_hat_static, long N_) const { return valid && yhs == y_hat_static && n == N_; }      // KeptLeak::claim's
+  // the band the pass went through (null: R is None), set by generator_forward under `stash` alone; the cache never recycles it while live().
+  // band_freed: the cache frees b; true when it was this pass's, which can then no longer be back-propagated
+  const MlpgBand* band() const { return bnd; }      void went_through(const MlpgBand* band_) { bnd = band_; }
+  bool band_freed(const MlpgBand* band_) { if (bnd != band_) return false;      bnd = nullptr; valid = false; return true; }
+  // the generator forward in hand reads the dense copy of its input (dense_gx, every generator forward): gx_pitch() == in_dim
+  bool input_dense() const { return dense; }      void input_dense(bool on) { dense = on; }
+  int B() const { return b; }      int T() const { return t; }      long N() const { return n; }
+  const float* input() const { return x; }      const float* y_hat() const { return yhat; }
+ private:
+  int b = 0, t = 0; long n = 0;
+  const float *x = nullptr, *yhat = nullptr, *yhs = nullptr;
+  const MlpgBand* bnd = nullptr;
+  bool dense = false, valid = false;
+};
+
+// The memos of D's input.  DImage: "the generated half of this image of D's input is built", and from which x / y_hat_static: the generator
+// step's adversarial term reuses what the D step of the same batch left behind.  One record per image kind, one StepCopy per engine-made copy
+// of x; the buffers they describe (dcat, dcat_b, adv2) stay the engine's.
+struct DImage {
+  bool valid = false; const float* x = nullptr; const float* yhs = nullptr;
+  bool holds(const float* x_, const float* yhs_) const { return valid && x == x_ && yhs == yhs_; }
+  void built(const float* x_, const float* yhs_) { valid = true; x = x_; yhs = yhs_; }
+};
+struct DInputMemos {
+  DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
+  StepCopy dx_pitched, gx_pitched, cx_dense;       // 16-byte-pitch copies of D's conditioning x / G's input (pitched_rows), the dense conditioning x (dense_cx)
+  void invalidate_d_images() { img_cat.valid = img_cat_b.valid = img_adv2.valid = false; }      // whatever image of D's input is kept gets rebuilt
+  void forget_copies() { dx_pitched.forget(); gx_pitched.forget(); cx_dense.forget(); }
+};
+
 struct gt_engine {
   gt_stream_config cfg;
   Net net[2];
@@ -429,19 +470,9 @@ struct gt_engine {
   Scratch scal;                            // StepScalars + StepResults
   ResultsChannel results;                  // how the step's scalars reach the host
   EpochLedger ledger;                      // gt_ledger_*: the loop's running sums, added on the device behind each step
-  // per-step state
-  int B = 0, T = 0; long N = 0;
-  const float* last_x = nullptr; const float* last_yhat = nullptr; const float* last_yhs = nullptr;
-  bool g_pass_valid = false;
-  const MlpgBand* g_band = nullptr;        // the band the stashed generator pass went through (null: R is None); the cache never recycles it while g_pass_valid
-  // "the generated half of this image of D's input is built", and from which x / y_hat_static: the generator step's adversarial term
-  // reuses what the D step of the same batch left behind.  One record per image kind; all dropped by invalidate_d_images().
-  struct DImage {
-    bool valid = false; const float* x = nullptr; const float* yhs = nullptr;
-    bool holds(const float* x_, const float* yhs_) const { return valid && x == x_ && yhs == yhs_; }
-    void built(const float* x_, const float* yhs_) { valid = true; x = x_; yhs = yhs_; }
-  };
-  DImage img_cat, img_cat_b, img_adv2;             // of dcat (float32 [x | adv]), dcat_b (its bf16 image), adv2 (adversarial columns only: x is ignored, kept null)
+  // per-step state: what outlives a call is forgotten by the events below the struct
+  GenPass pass;
+  DInputMemos din;
   bool g_has_adv = false;
   Scratch i2o_gout, d_dx0;                         // In2OutRNNHighwayNet: hidden2out output G(x); a recurrent DISCRIMINATOR (train.py:773-774 allows any model class): gradient w.r.t. its [x | adv] input
   Scratch l_state, l_xch, s_du, s_dx, s_dbias;     // recurrent layer in hand (either role): LSTM per-step kernels' state, persistent kernels' exchange granules; SRU backward temporaries
@@ -480,8 +511,7 @@ struct gt_engine {
   // gt_set_x_pitch: pitched rows are read in place by the float32 MLP generator and by the split first layer of the conditioned float32 MLP
   // discriminator.  Every other network gets a DENSE copy made by the engine, once per step (dense_gx / dense_cx in eng_step.hip):
   // gt_set_x_pitch never makes a step fail (DevicePrefetcher(pitch_x=True) with a recurrent discriminator did).
-  StepCopy dx_pitched, gx_pitched, cx_dense;       // 16-byte-pitch copies of D's conditioning x / G's input (pitched_rows), the dense conditioning x (dense_cx)
-  Scratch gx_dense; bool gx_dense_on = false;      // gx_dense_on: this step's generator input is the dense copy, gx_pitch() == in_dim
+  Scratch gx_dense;                                // dense_gx's copy (GenPass::input_dense)
   unsigned int* h_fault_dev = nullptr;             // device view of h_fault[1]: the optimizer kernel mirrors a raised fault word
   unsigned int* d_fault = nullptr;                 // device fault word of the persistent kernels (0 = ok)
   unsigned int* h_fault = nullptr;                 // pinned mirror, refreshed behind every persistent launch
@@ -510,8 +540,36 @@ struct gt_engine {
   StepScalars* sc() { return scal.as<StepScalars>(); }
   StepResults* res() { return (StepResults*)((char*)scal.p + 256); }
 };
-// a new batch, another storage form or first-layer route, a cleared fault: whatever image of D's input is kept gets rebuilt
-static inline void invalidate_d_images(gt_engine* e) { e->img_cat.valid = e->img_cat_b.valid = e->img_adv2.valid = false; }
+// What each event forgets of the state the engine keeps between calls: one function per event, each entry point calls its
+// own and writes none of this itself.  Assignments only -- several are on the step path.  (A D step rebuilding both halves of its input
+// calls DInputMemos::invalidate_d_images itself: that is use, not an event; KeptLeak::drop where the gradient is consumed likewise.)
+// gt_apply_generator.  No StepCopy outlives a batch: the step count alone does not tell two batches apart (gt_set_seed restarts it, and a staging
+// buffer refilled in place has the same pointer, pitch and shape).  Both update calls of a batch come behind this one: they still share a copy.
+// The mask's contents may have changed as well.
+static inline void on_new_batch(gt_engine* e) { e->pass.drop(); e->din.invalidate_d_images(); e->din.forget_copies(); e->norm.forget(); }
+static inline void on_reseed(gt_engine* e) { e->din.forget_copies(); }      // gt_set_seed: the step count, part of the copies' key, has just gone back
+static inline void on_first_layer_route_changed(gt_engine* e) { e->din.invalidate_d_images(); }      // GT_OPT_SPLIT_FIRST_LAYER
+// GT_OPT_MATMUL_BF16: the storage precision belongs to a PASS -- buffers of a stashed forward pass (bf16 images vs float32 stashes) are not
+// interchangeable, so the next update_* asks for a fresh apply_generator instead of back-propagating through buffers the forward never filled
+static inline void on_storage_form_changed(gt_engine* e) {
+  e->din.invalidate_d_images(); e->pass.drop(); e->leak.drop(); e->din.cx_dense.forget(); e->results.forget_begin();
+}
+// GT_OPT_SRU_D_BF16 (as above: a discriminator pass stashed in one storage form is not back-propagated in the other)
+static inline void on_sru_d_storage_form_changed(gt_engine* e) { e->din.invalidate_d_images(); e->leak.drop(); e->results.forget_begin(); }
+// GT_OPT_GAN_OBJECTIVE: a discriminator pass begun under one objective is not finished, and its kept gradient not used, under another
+static inline void on_objective_changed(gt_engine* e) { e->leak.drop(); e->results.forget_begin(); }
+// gt_set_spectral_norm, off / on: a pass begun with the feature is not finished without it, nor the other way round
+static inline void on_spectral_norm_off(gt_engine* e) { e->din.invalidate_d_images(); e->leak.drop(); e->results.forget_begin(); }
+static inline void on_spectral_norm_on(gt_engine* e) { e->leak.drop(); e->results.forget_begin(); }
+static inline void on_penalty_kind_changed(gt_engine* e) { e->results.forget_begin(); }      // gt_set_grad_penalty: a D step begun under one setting is not finished under another
+// the MLPG cache frees b: the stashed pass would transpose through it
+static inline void on_band_freed(gt_engine* e, const MlpgBand* b) { if (e->pass.band_freed(b)) e->leak.drop(); }
+static inline void on_generator_rebound(gt_engine* e) { e->pass.drop(); }      // gt_bind_model(role G)
+static inline void on_generator_plain_forward(gt_engine* e) { e->pass.drop(); }      // gt_model_forward(role G): it ran over the stashed pass's activations
+static inline void on_zero_grad(gt_engine* e, int role) { e->norm.forget();      if (role == GT_ROLE_G) e->leak.drop(); }
+static inline void on_faults_cleared(gt_engine* e) {      // gt_clear_faults
+  e->din.invalidate_d_images(); e->pass.drop(); e->leak.drop(); e->din.cx_dense.forget(); e->results.reset();
+}
 
 // ------------------------------------------------------------------------------------------
 // eng_core.hip
