@@ -250,6 +250,7 @@ SIGNATURES = {
     "gt_version": (C.c_char_p, []),
     "gt_engine_create": (_I, [C.POINTER(StreamConfig), C.POINTER(_P)]),
     "gt_engine_destroy": (None, [_P]),
+    "gt_live_resources": (_I, [C.POINTER(_L)]),
     "gt_bind_model": (_I, [_P, _I, C.POINTER(ModelDesc)]),
     "gt_bind_optimizer": (_I, [_P, _I, C.POINTER(OptimDesc)]),
     "gt_bind_optimizer_ex": (_I, [_P, _I, C.POINTER(OptimDescEx)]),

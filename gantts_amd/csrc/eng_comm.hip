@@ -60,7 +60,6 @@ enum { GT_NCCL_SUM = 0, GT_NCCL_FLOAT = 7, GT_NCCL_DOUBLE = 8 };
 // stream).  GT_COMM_FORCE_COLLECTIVES=1 issues every call anyway -- the launch / cross-stream cost of the schedule can
 // then be measured on one GPU (bench.py --force-dp).
 
-static void trace_clear(GtComm* c);
 extern "C" int gt_comm_unique_id(void* id_out) {
   if (!id_out) return fail(GT_ERR_INVALID, "null argument");
   RcclApi* api = rccl_api();
@@ -75,11 +74,8 @@ extern "C" int gt_comm_destroy(gt_engine* e) {
   (void)hipDeviceSynchronize();
   GtComm* c = e->comm;
   if (c->comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
-  for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-  if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-  trace_clear(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;      // its events
   e->comm = nullptr;
   e->dp_rank = 0; e->dp_world = 1;
   return GT_OK;
@@ -102,8 +98,8 @@ extern "C" int gt_comm_init(gt_engine* e, int rank, int world, const void* id) {
   // stream-to-stream hand-offs on ONE device: a device-scope release is enough (the collective's own kernels fence what leaves the
   // device), and a record then does not flush to system scope in the middle of the step
   const unsigned evf = hipEventDisableTiming | (env_flag("GT_COMM_EVENT_DEVICE_SCOPE", true) ? hipEventReleaseToDevice : 0u);
-  for (auto& ev : c->ev) HIPCHK(hipEventCreateWithFlags(&ev, evf));
-  HIPCHK(hipEventCreateWithFlags(&c->ev_done, evf));
+  for (auto& ev : c->ev) CHK(ev.ensure(evf));
+  CHK(c->ev_done.ensure(evf));
   CHK(e->norm.attach());
   return GT_OK;
 }
@@ -129,7 +125,6 @@ extern "C" int gt_comm_info(gt_engine* e, int* rank, int* world) {
 // (the first one behind the hand-off wait: the message may start there) and comm_join brackets the step stream's wait, so a run tells
 // how many messages a step sends, how long each one holds the communicator's stream and how long the step stream stands still for them.
 static void trace_clear(GtComm* c) {
-  for (auto& r : c->trec) { if (r.e0) (void)hipEventDestroy(r.e0); if (r.e1) (void)hipEventDestroy(r.e1); }
   c->trec.clear();
   c->trace_dropped = 0;
 }
@@ -137,13 +132,9 @@ static GtComm::TraceRec* trace_open(GtComm* c, int kind, bool inl, double bytes,
   if (!c->trace) return nullptr;
   if (c->trec.size() >= 65536) { ++c->trace_dropped; return nullptr; }      // (reported by gt_comm_trace_read)
   GtComm::TraceRec r;
-  r.kind = kind; r.inl = inl ? 1 : 0; r.bytes = bytes; r.e0 = r.e1 = nullptr; r.closed = false;
-  if (hipEventCreate(&r.e0) != hipSuccess || hipEventCreate(&r.e1) != hipSuccess || hipEventRecord(r.e0, on) != hipSuccess) {
-    if (r.e0) (void)hipEventDestroy(r.e0);
-    if (r.e1) (void)hipEventDestroy(r.e1);
-    return nullptr;
-  }
-  c->trec.push_back(r);
+  r.kind = kind; r.inl = inl ? 1 : 0; r.bytes = bytes; r.closed = false;
+  if (r.e0.ensure(hipEventDefault) != GT_OK || r.e1.ensure(hipEventDefault) != GT_OK || hipEventRecord(r.e0, on) != hipSuccess) return nullptr;
+  c->trec.push_back(std::move(r));
   return &c->trec.back();
 }
 extern "C" int gt_comm_trace(gt_engine* e, int enable) {

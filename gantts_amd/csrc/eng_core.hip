@@ -75,11 +75,19 @@ extern "C" int gt_profile_bytes(double* out_bytes) {
   return GT_OK;
 }
 
-static int upload_ints(const std::vector<int>& v, int** dptr) {
-  if (*dptr) { (void)hipFree(*dptr); *dptr = nullptr; }
+// gt_live_resources: what the owning types (engine_internal.hip.h) hold right now
+static std::atomic<int64_t> g_live[4];
+void live_count(int slot, int64_t delta) { g_live[slot].fetch_add(delta, std::memory_order_relaxed); }
+extern "C" int gt_live_resources(int64_t out[4]) {
+  if (!out) return fail(GT_ERR_INVALID, "null argument");
+  for (int i = 0; i < 4; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
+  return GT_OK;
+}
+
+static int upload_ints(const std::vector<int>& v, Scratch& d) {
   if (v.empty()) return GT_OK;
-  HIPCHK(hipMalloc((void**)dptr, v.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+  CHK(d.ensure(v.size() * sizeof(int)));
+  HIPCHK(hipMemcpy(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
   return GT_OK;
 }
 
@@ -87,7 +95,7 @@ extern "C" int gt_engine_create(const gt_stream_config* cfg, gt_engine** out) {
   if (!cfg || !out) return fail(GT_ERR_INVALID, "null argument");
   if (cfg->n_streams < 1 || cfg->n_streams > GT_MAX_STREAMS) return fail(GT_ERR_INVALID, "n_streams out of range");
   if (cfg->num_windows < 1 || cfg->num_windows > MLPG_MAXW) return fail(GT_ERR_INVALID, "num_windows must be in [1,%d]", MLPG_MAXW);
-  gt_engine* e = new gt_engine();
+  std::unique_ptr<gt_engine> e(new gt_engine());      // an error below frees whatever was allocated so far
   e->cfg = *cfg;
   // static layout: get_static_stream_sizes (multistream.py:46-53) + per-column source map
   int col = 0, scol_out = 0;
@@ -115,54 +123,33 @@ extern "C" int gt_engine_create(const gt_stream_config* cfg, gt_engine** out) {
       if (cfg->adversarial_streams[s])
         for (int c = 0; c < static_size[s]; ++c) e->h_adv_cols.push_back(static_start[s] + c);
     if (cfg->mask_nth_mgc_for_adv_loss > 0) {
-      if ((size_t)cfg->mask_nth_mgc_for_adv_loss >= e->h_adv_cols.size()) { delete e; return fail(GT_ERR_INVALID, "mask_nth_mgc_for_adv_loss too large"); }
+      if ((size_t)cfg->mask_nth_mgc_for_adv_loss >= e->h_adv_cols.size()) return fail(GT_ERR_INVALID, "mask_nth_mgc_for_adv_loss too large");
       e->h_adv_cols.erase(e->h_adv_cols.begin(), e->h_adv_cols.begin() + cfg->mask_nth_mgc_for_adv_loss);
     }
   }
   e->Da = (int)e->h_adv_cols.size();
   e->h_adv_inv.assign(e->Ds, -1);
   for (int j = 0; j < e->Da; ++j) e->h_adv_inv[e->h_adv_cols[j]] = j;
-  int r;
-  if ((r = upload_ints(e->h_scol, &e->d_scol)) || (r = upload_ints(e->h_sstride, &e->d_sstride)) ||
-      (r = upload_ints(e->h_adv_cols, &e->d_adv_cols)) || (r = upload_ints(e->h_adv_inv, &e->d_adv_inv))) { delete e; return r; }
-  if ((r = e->scal.ensure(1024))) { delete e; return r; }
-  if (hipMemset(e->scal.p, 0, 1024) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipMemset failed"); }
-  if ((r = e->results.create(e->res(), &e->opt_poll_results))) { delete e; return r; }
-  if (hipMalloc((void**)&e->d_fault, 64) != hipSuccess || hipMemset(e->d_fault, 0, 64) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipMalloc failed"); }
-  if (hipHostMalloc((void**)&e->h_fault, 64) != hipSuccess) { delete e; return fail(GT_ERR_HIP, "hipHostMalloc failed"); }
+  CHK(upload_ints(e->h_scol, e->d_scol)); CHK(upload_ints(e->h_sstride, e->d_sstride));
+  CHK(upload_ints(e->h_adv_cols, e->d_adv_cols)); CHK(upload_ints(e->h_adv_inv, e->d_adv_inv));
+  CHK(e->scal.ensure(1024));
+  HIPCHK(hipMemset(e->scal.p, 0, 1024));
+  CHK(e->results.create(e->res(), &e->opt_poll_results));
+  CHK(e->d_fault.ensure(64));
+  HIPCHK(hipMemset(e->d_fault.p, 0, 64));
+  CHK(e->h_fault.alloc(64));
   for (int i = 0; i < 16; ++i) e->h_fault[i] = 0;   // [0] copy of the device word, [1] its mirror by the optimizer kernel, [2 + role] skipped steps
   if (hipHostGetDevicePointer((void**)&e->h_fault_dev, e->h_fault, 0) != hipSuccess) { (void)hipGetLastError(); e->h_fault_dev = nullptr; }
   else e->h_fault_dev += 1;
-  *out = e;
+  *out = e.release();
   return GT_OK;
 }
 
+// The communicator goes first: its stream may still name LossNormaliser's message buffer.  Everything else is the members' own.
 extern "C" void gt_engine_destroy(gt_engine* e) {
   if (!e) return;
   (void)hipDeviceSynchronize();
-  e->ws[GT_ROLE_G].release(); e->ws[GT_ROLE_D].release();
   (void)gt_comm_destroy(e);
-  if (e->d_fault) (void)hipFree(e->d_fault);
-  if (e->h_fault) (void)hipHostFree(e->h_fault);
-  for (int i = 0; i < gt_engine::LEN_RING; ++i) {
-    e->len_dev[i].release();
-    if (e->len_host[i]) (void)hipHostFree(e->len_host[i]);
-    if (e->len_ev[i]) (void)hipEventDestroy(e->len_ev[i]);
-  }
-  Scratch* all[] = {&e->dcat, &e->dzA, &e->dzB, &e->gadv, &e->gs, &e->gy, &e->slabs, &e->colp, &e->partial, &e->headp, &e->headw, &e->gx_dense,
-                    &e->din.cx_dense.buf, &e->din.dx_pitched.buf, &e->din.gx_pitched.buf, &e->dmask, &e->tx, &e->gx, &e->dgx, &e->dtz, &e->dout, &e->scal, &e->mlpg.tmp,
-                    &e->mlpg.fac, &e->mlpg.wide, &e->i2o_gout, &e->d_dx0, &e->l_state, &e->l_xch, &e->s_du, &e->s_dx, &e->s_dbias, &e->d_pre, &e->adv2, &e->mlpg_var_ws};
-  for (auto* s : all) s->release();
-  e->xin_b.release(); e->dcat_b.release(); e->gy_b.release(); e->dz_b[0].release(); e->dz_b[1].release(); e->fwd_b.release();
-  e->mlpg.clear();
-  int* ints[] = {e->d_scol, e->d_sstride, e->d_adv_cols, e->d_adv_inv, e->d_scol_i2o, e->d_sstride_i2o};
-  for (int* p : ints) if (p) (void)hipFree(p);
-  e->results.destroy();
-  e->ledger.release();
-  if (e->sn.plan) sn_plan_free(e->sn.plan);
-  e->sn.weff.release(); e->sn.ws.release();
-  e->gp.release();
-  e->norm.release(); e->leak.release();
   delete e;
 }
 
@@ -302,7 +289,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
       n.lstm.push_back(L);
     }
     n.last = take(desc->out_dim, H * dirs);
-    for (auto* v : {&W.xproj, &W.gates, &W.cst, &W.out, &W.outd}) v->resize(desc->num_hidden);
+    for (auto* v : {&W.xproj, &W.gates, &W.cst, &W.out, &W.outd}) CHK(resize_owned(*v, desc->num_hidden));
   } else if (desc->arch == GT_ARCH_SRU) {
     if (desc->rnn_dropout < 0.f || desc->rnn_dropout >= 1.f) return fail(GT_ERR_INVALID, "rnn_dropout must be in [0,1)");
     if (desc->num_hidden > 8) return fail(GT_ERR_INVALID, "SRURNN: at most 8 layers (two dropout sites per layer)");
@@ -318,7 +305,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
       n.sru.push_back(L);
     }
     n.last = take(desc->out_dim, ncols);
-    for (auto* v : {&W.u, &W.h, &W.c, &W.xdrop, &W.xmask, &W.wt, &W.omask}) v->resize(desc->num_hidden);      // (the generator's omask entries stay empty)
+    for (auto* v : {&W.u, &W.h, &W.c, &W.xdrop, &W.xmask, &W.wt, &W.omask}) CHK(resize_owned(*v, desc->num_hidden));      // (the generator's omask entries stay empty)
   } else {
     if (desc->arch == GT_ARCH_IN2OUT) n.gate = take(desc->static_dim, desc->static_dim);
     int in = desc->in_dim;
@@ -327,7 +314,7 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
   }
   n.bound = true;
   n.grads_dirty = false;
-  W.act.resize(desc->num_hidden);
+  CHK(resize_owned(W.act, desc->num_hidden));
   if (role == GT_ROLE_D) CHK(sn_rebind(e));      // gt_set_spectral_norm is on: Lin::W into W_eff again, the registered u and v against the new network
   if (role == GT_ROLE_G && is_i2o(desc->arch)) {
     // single dynamic stream of width out_dim (models.py:66,115)
@@ -335,8 +322,8 @@ extern "C" int gt_bind_model(gt_engine* e, int role, const gt_model_desc* desc) 
     std::vector<int> sc(sd), ss(sd, sd);
     for (int c = 0; c < sd; ++c) sc[c] = c;
     e->i2o_ds = sd;
-    CHK(upload_ints(sc, &e->d_scol_i2o));
-    CHK(upload_ints(ss, &e->d_sstride_i2o));
+    CHK(upload_ints(sc, e->d_scol_i2o));
+    CHK(upload_ints(ss, e->d_sstride_i2o));
     if (sd != desc->static_dim) return fail(GT_ERR_DIM, "In2OutHighwayNet: out_dim/num_windows (%d) != static_dim (%d)", sd, desc->static_dim);
   }
   if (role == GT_ROLE_G) on_generator_rebound(e);
@@ -502,9 +489,8 @@ extern "C" int gt_set_lengths(gt_engine* e, const int64_t* lengths_host, int B, 
     const int cap = std::max(64, 2 * B + B);
     for (int i = 0; i < gt_engine::LEN_RING; ++i) {
       if (e->len_ev[i]) HIPCHK(hipEventSynchronize(e->len_ev[i]));
-      if (e->len_host[i]) { HIPCHK(hipHostFree(e->len_host[i])); e->len_host[i] = nullptr; }
-      HIPCHK(hipHostMalloc((void**)&e->len_host[i], (size_t)cap * sizeof(int)));
-      if (!e->len_ev[i]) HIPCHK(hipEventCreateWithFlags(&e->len_ev[i], hipEventDisableTiming));
+      CHK(e->len_host[i].alloc((size_t)cap * sizeof(int)));
+      CHK(e->len_ev[i].ensure(hipEventDisableTiming));
     }
     e->len_cap = cap;
   }
@@ -624,7 +610,7 @@ extern "C" int gt_clear_faults(gt_engine* e, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemset(e->d_fault, 0, 64));
+  HIPCHK(hipMemset(e->d_fault.p, 0, 64));
   for (int r = 0; r < 2; ++r) {
     Net& n = e->net[r];
     n.step -= (long)e->h_fault[2 + r];
@@ -646,7 +632,7 @@ extern "C" int gt_lstm_path_counts(gt_engine* e, int64_t* counts, int reset) {
 }
 extern "C" int gt_check_faults(gt_engine* e, void* stream) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
-  HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault, sizeof(unsigned int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault.p, sizeof(unsigned int), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return fault_seen(e);
 }

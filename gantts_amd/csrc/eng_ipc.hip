@@ -106,7 +106,7 @@ void ipc_destroy(gt_engine* e) {
   (void)hipDeviceSynchronize();
   for (int p = 0; p < GT_IPC_MAX_WORLD; ++p)
     if (c->peer[p] && c->peer[p] != c->arena) (void)hipIpcCloseMemHandle(c->peer[p]);
-  if (c->arena) (void)hipFree(c->arena);
+  if (c->arena) { (void)hipFree(c->arena); live_count(LIVE_DEV_BLOCKS, -1); live_count(LIVE_DEV_BYTES, -(int64_t)IPC_ARENA_BYTES); }
   delete c;
   e->ipc = nullptr;
 }
@@ -125,8 +125,8 @@ static int ipc_allreduce_t(gt_engine* e, T* buf, long n, hipStream_t s) {
   const long chunk = (n + c->world - 1) / c->world;
   const int grid_c = (int)std::max<long>(1, std::min<long>(256, cdiv(chunk, 256 * 2)));
   hipLaunchKernelGGL(ipc_publish_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)buf, c->arena, n);
-  hipLaunchKernelGGL(ipc_reduce_kernel<T>, dim3(grid_c), dim3(256), 0, s, P, c->rank, c->world, n, c->seq, e->d_fault);
-  hipLaunchKernelGGL(ipc_collect_kernel<T>, dim3(grid), dim3(256), 0, s, P, c->rank, c->world, buf, n, c->seq, e->d_fault);
+  hipLaunchKernelGGL(ipc_reduce_kernel<T>, dim3(grid_c), dim3(256), 0, s, P, c->rank, c->world, n, c->seq, e->fault_dev());
+  hipLaunchKernelGGL(ipc_collect_kernel<T>, dim3(grid), dim3(256), 0, s, P, c->rank, c->world, buf, n, c->seq, e->fault_dev());
   LAUNCH_CHECK();
   c->messages += 1;
   return GT_OK;
@@ -164,6 +164,7 @@ extern "C" int gt_comm_ipc_export(gt_engine* e, void* handle_out) {
     if (hipMalloc(&p, IPC_ARENA_BYTES) != hipSuccess) { ipc_destroy(e); return fail(GT_ERR_HIP, "the interprocess arena could not be allocated"); }
   }
   c->arena = (char*)p;
+  live_count(LIVE_DEV_BLOCKS, 1); live_count(LIVE_DEV_BYTES, (int64_t)IPC_ARENA_BYTES);
   if (hipMemset(c->arena, 0, IPC_FLAGS_BYTES) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { ipc_destroy(e); return fail(GT_ERR_HIP, "hipMemset failed"); }
   hipIpcMemHandle_t h;
   hipError_t r = hipIpcGetMemHandle(&h, c->arena);

@@ -43,7 +43,7 @@ extern "C" int gt_ledger_configure(gt_engine* e, int kind, int Ds, const int32_t
   L.off_part = ((L.off_tab + host.size() * sizeof(int) + 255) / 256) * 256;
   CHK(L.rec.ensure(L.off_part + (size_t)LEDGER_MAX_PARTIALS * DIST_NSUM * sizeof(double)));
   CHK(L.len.ensure(1024 * sizeof(int)));
-  if (!L.h_out) HIPCHK(hipHostMalloc((void**)&L.h_out, GT_LEDGER_SLOTS * sizeof(double)));
+  if (!L.h_out) CHK(L.h_out.alloc(GT_LEDGER_SLOTS * sizeof(double)));
   L.kind = kind; L.Ds = Ds; L.vuv_col = vuv_col; L.stats_f64 = stats_f64 ? 1 : 0; L.logdb_const = logdb_const;
   L.mean = stat_mean; L.stdv = stat_std;
   HIPCHK(hipMemset(L.rec.p, 0, L.off_tab));

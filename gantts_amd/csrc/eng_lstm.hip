@@ -131,7 +131,7 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, NetWs& W, bool bf16, int 
   a.cst = W.cst[layer].as<float>();
   a.out = W.out[layer].as<float>();
   a.dout = dout;
-  a.fault = e->d_fault;
+  a.fault = e->fault_dev();
   a.timeout_ticks = 200000000ULL;          // 2 s at 100 MHz: far beyond any real wait, far below the watchdog
   const int ngroups = dirs * a.nbt;
   const size_t xch_n = (size_t)ngroups * (backward ? lstm_bwd_xch_u64(HP) : lstm_fwd_xch_u64(HP)), chk_n = (size_t)ngroups * 256;
@@ -144,7 +144,7 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, NetWs& W, bool bf16, int 
     a.ncu = cdiv(H, 16);
     CHK(HP == 256 ? launch_bwd_seq<256>(a, bt, bf16, s, launched) : launch_bwd_seq<512>(a, bt, bf16, s, launched));
     e->lstm_paths[*launched ? slot : GT_LSTM_PATH_DECLINED]++;
-    if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault.p, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
     return GT_OK;
   }
   // forward: 8 hidden units per workgroup (32 workgroups per group at H = 256: one XCD's worth), else 16
@@ -157,7 +157,7 @@ static int lstm_launch_seq(gt_engine* e, const Net& G, NetWs& W, bool bf16, int 
     if (*launched) e->lstm_paths[slot + (upc == 16 ? 4 : 0)]++;
   }
   if (!*launched) e->lstm_paths[GT_LSTM_PATH_DECLINED]++;
-  if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  if (*launched) HIPCHK(hipMemcpyAsync(e->h_fault, e->d_fault.p, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   return GT_OK;
 }
 
@@ -194,7 +194,7 @@ int lstm_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nse
   const bool want_t = G.d.grads != nullptr;
   const int Lc_ = G.d.num_hidden;
   if (b16) {
-    W.l_in_b.resize(Lc_ + 1); W.lsh.resize(Lc_ + 1);
+    CHK(resize_owned(W.l_in_b, Lc_ + 1)); CHK(resize_owned(W.lsh, Lc_ + 1));
     for (int l = 0; l < Lc_; ++l) {
       const LstmLayerP& L = G.lstm[l];
       CHK(W.lsh[l].ensure(dirs * 4 * H, L.in));
@@ -280,7 +280,7 @@ int lstm_stack_backward(gt_engine* e, int role, const float* x, int ld_x, int ns
   float* dout = W.dout.as<float>();                          // gradient w.r.t. the current layer's output
   float* dout_other = dout + (size_t)N * dirs * H;
   const bool b16 = role == GT_ROLE_G && lstm_b16(e) && (int)W.l_in_b.size() == Lc + 1 && (int)W.lsh.size() == Lc + 1;
-  if (b16) W.l_dg_b.resize(Lc);
+  if (b16) CHK(resize_owned(W.l_dg_b, Lc));
   for (int l = Lc - 1; l >= 0; --l) {
     const LstmLayerP& L = G.lstm[l];
     bool seq = false;

@@ -39,8 +39,8 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
   MlpgCache& m = e->mlpg;
   *out = nullptr;
   ++m.tick;
-  for (auto* b : m.entries)
-    if (b->R == R && b->T == T) { b->last_use = m.tick; *out = b; return GT_OK; }
+  for (auto& b : m.entries)
+    if (b->R == R && b->T == T) { b->last_use = m.tick; *out = b.get(); return GT_OK; }
   const int nW = e->cfg.num_windows;
   const bool built = R == GT_MLPG_R_FROM_WINDOWS;      // never dereferenced
   if (built && !m.has_win) return fail(GT_ERR_INVALID, "GT_MLPG_R_FROM_WINDOWS without a window set: call gt_set_mlpg_windows first");
@@ -76,11 +76,11 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
   MlpgBand* b = nullptr;
   if (m.entries.size() >= MlpgCache::MAX_ENTRIES) {      // recycle the least recently used entry, the stashed generator pass's band apart
     const MlpgBand* held = e->pass.live() ? e->pass.band() : nullptr;
-    for (auto* c : m.entries) if (c != held && (!b || c->last_use < b->last_use)) b = c;
+    for (auto& c : m.entries) if (c.get() != held && (!b || c->last_use < b->last_use)) b = c.get();
     HIPCHK(hipStreamSynchronize(s));                      // its band may still be read by queued kernels
   } else {
-    b = new MlpgBand();
-    m.entries.push_back(b);
+    m.entries.emplace_back(new MlpgBand());
+    b = m.entries.back().get();
   }
   const int nb = 2 * kb + 1;
   b->R = nullptr;
@@ -95,7 +95,7 @@ int ensure_band(gt_engine* e, const float* R, int T, hipStream_t s, const MlpgBa
 extern "C" int gt_invalidate_mlpg_cache(gt_engine* e) {
   if (!e) return fail(GT_ERR_INVALID, "null engine");
   HIPCHK(hipDeviceSynchronize());
-  for (auto* b : e->mlpg.entries) on_band_freed(e, b);
+  for (auto& b : e->mlpg.entries) on_band_freed(e, b.get());
   e->mlpg.clear();
   return GT_OK;
 }
@@ -121,11 +121,8 @@ extern "C" int gt_set_mlpg_windows(gt_engine* e, int n, const int32_t* l, const 
   // another set: the built entries go (a dense R's stay), with gt_invalidate_mlpg_cache's synchronisation -- queued kernels may read them
   HIPCHK(hipDeviceSynchronize());
   for (size_t i = 0; i < m.entries.size();) {
-    MlpgBand* b = m.entries[i];
-    if (b->R != GT_MLPG_R_FROM_WINDOWS) { ++i; continue; }
-    on_band_freed(e, b);
-    b->band.release();
-    delete b;
+    if (m.entries[i]->R != GT_MLPG_R_FROM_WINDOWS) { ++i; continue; }
+    on_band_freed(e, m.entries[i].get());
     m.entries.erase(m.entries.begin() + i);
   }
   memcpy(&m.win, &win, sizeof(win));      // padding included: the comparison above is a memcmp
@@ -277,7 +274,7 @@ extern "C" int gt_op_mlpg_forward(gt_engine* e, const float* y, const float* R, 
   hipStream_t s = (hipStream_t)stream;
   const MlpgBand* band;
   CHK(ensure_band(e, R, T, s, &band));
-  return mlpg_forward(e, y, e->Dout_cfg, e->d_scol, e->d_sstride, e->Ds, y_static, e->Ds, B, T, *band, s);
+  return mlpg_forward(e, y, e->Dout_cfg, e->d_scol.as<int>(), e->d_sstride.as<int>(), e->Ds, y_static, e->Ds, B, T, *band, s);
 }
 extern "C" int gt_op_mlpg_backward(gt_engine* e, const float* g_static, const float* R, int B, int T, float* g_y, void* stream) {
   CHK(check_common(e, B, T));
@@ -285,7 +282,7 @@ extern "C" int gt_op_mlpg_backward(gt_engine* e, const float* g_static, const fl
   hipStream_t s = (hipStream_t)stream;
   const MlpgBand* band;
   CHK(ensure_band(e, R, T, s, &band));
-  return mlpg_backward(e, g_static, e->Ds, e->d_scol, e->d_sstride, e->Ds, g_y, e->Dout_cfg, B, T, 0.f, nullptr, nullptr, 0, nullptr, *band, s);
+  return mlpg_backward(e, g_static, e->Ds, e->d_scol.as<int>(), e->d_sstride.as<int>(), e->Ds, g_y, e->Dout_cfg, B, T, 0.f, nullptr, nullptr, 0, nullptr, *band, s);
 }
 
 // The column maps a hook's launch indexes with -- the engine's own, or the case's, read back from the device -- hold no negative entry, and
@@ -339,8 +336,8 @@ extern "C" int gt_op_mlpg(const gt_mlpg_case* c, void* stream) {
   const MlpgBand* band;
   CHK(ensure_band(e, c->R, c->T, s, &band));
   if (c->kb) *c->kb = band->kb;
-  const int* scol = own ? e->d_scol : (const int*)c->scol;
-  const int* sstride = own ? e->d_sstride : (const int*)c->sstride;
+  const int* scol = own ? e->d_scol.as<int>() : (const int*)c->scol;
+  const int* sstride = own ? e->d_sstride.as<int>() : (const int*)c->sstride;
   int r;
   if (!bwd) {
     r = mlpg_forward(e, c->y, c->ldy, scol, sstride, Ds, c->ys, c->ldys, c->B, c->T, *band, s);
@@ -399,6 +396,6 @@ extern "C" int gt_op_mlpg_var(const gt_mlpg_var_case* c, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const MlpgPitch pitch[2] = {{"ldy", c->ldy, false}, {"ldv", c->ldv, true}};
   CHK(check_column_maps(e, "variance-weighted MLPG", c->scol, c->sstride, Ds, pitch, c->ldv ? 2 : 1, s));
-  return launch_mlpg_var(e, c->y, c->ldy, c->var, c->ldv, own ? e->d_scol : (const int*)c->scol, own ? e->d_sstride : (const int*)c->sstride, Ds,
+  return launch_mlpg_var(e, c->y, c->ldy, c->var, c->ldv, own ? e->d_scol.as<int>() : (const int*)c->scol, own ? e->d_sstride.as<int>() : (const int*)c->sstride, Ds,
                          c->ys, c->ldys, c->lengths, c->B, c->T, c->max_ws_bytes, s);
 }

@@ -21,7 +21,7 @@ extern "C" int gt_op_masked_mse(const float* input, const float* target, const f
   if (!mask) return fail(GT_ERR_INVALID, "Should provide either lengths or mask");  // seqloss.py:33-34
   hipStream_t s = (hipStream_t)stream;
   const long N = (long)B * T;
-  static thread_local Scratch tls_ws;     // grow-only, no per-call hipMalloc/hipFree (both synchronise the device)
+  static thread_local HookScratch tls_ws;     // grow-only, no per-call hipMalloc/hipFree (both synchronise the device)
   CHK(tls_ws.ensure(1024 + 1024 * sizeof(double)));
   void* ws = tls_ws.p;
   StepScalars* sc = (StepScalars*)ws;
@@ -63,7 +63,7 @@ extern "C" int gt_compute_distortions(const float* y_static, const float* y_hat_
   }
   // grow-only workspace shared by all calls of this thread: the function runs once per training step
   // (train.py:588-595) -- a hipMalloc/hipFree pair per call would synchronise the device every step
-  static thread_local Scratch tls_ws;
+  static thread_local HookScratch tls_ws;
   const size_t off_part = ((host.size() * sizeof(int) + 255) / 256) * 256;
   const size_t off_out = off_part + (size_t)nblk * DIST_NSUM * sizeof(double);
   CHK(tls_ws.ensure(off_out + DIST_NSUM * sizeof(double)));
@@ -137,8 +137,7 @@ extern "C" int gt_op_linear_backward(const float* dY, int lddy, const float* X, 
     if (dW && !X) return fail(GT_ERR_INVALID, "dW requested without X");
     Scratch slabs, colp;
     int r = linear_backward_weight(dY, lddy, X, ldx, rows, out_dim, in_dim, dW, db, false, slabs, colp, PREC_F32, s);
-    hipError_t err = hipStreamSynchronize(s);
-    slabs.release(); colp.release();
+    hipError_t err = hipStreamSynchronize(s);      // on every path: slabs and colp are freed behind it
     if (r) return r;
     if (err != hipSuccess) return fail(GT_ERR_HIP, "linear_backward: %s", hipGetErrorString(err));
   }
@@ -200,8 +199,7 @@ extern "C" int gt_op_linear_bf16(const float* X, const float* W, const float* bi
     return GT_OK;
   };
   r = body();
-  const hipError_t err = hipStreamSynchronize(s);
-  for (Scratch* q : {&xb, &xbt, &wb, &wbt, &yb, &ybt, &dyb, &dybt, &hb, &slabs, &colp}) q->release();
+  const hipError_t err = hipStreamSynchronize(s);      // on every path: the buffers are freed behind it
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "linear_bf16: %s", hipGetErrorString(err));
   return GT_OK;
@@ -280,8 +278,7 @@ extern "C" int gt_op_gemm_f32(const gt_gemm_case* c, void* stream) {
     return slab_defer_flush(sd, s);
   };
   const int r = body();
-  const hipError_t err = hipStreamSynchronize(s);
-  slabs.release(); colp.release(); sd.pool.release();
+  const hipError_t err = hipStreamSynchronize(s);      // on every path: the buffers are freed behind it
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_f32: %s", hipGetErrorString(err));
   return GT_OK;
@@ -362,8 +359,7 @@ extern "C" int gt_op_gemm_b16(const gt_gemm_b16_case* c, void* stream) {
     return launch_gemm_b16(g, 1, s);
   };
   const int r = body();
-  const hipError_t err = hipStreamSynchronize(s);
-  for (Scratch* q : {&ab, &bb, &hb, &slabs, &colp}) q->release();
+  const hipError_t err = hipStreamSynchronize(s);      // on every path: the buffers are freed behind it
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "gemm_b16: %s", hipGetErrorString(err));
   return GT_OK;
@@ -425,7 +421,6 @@ extern "C" int gt_op_cast_image(const gt_cast_case* c, void* stream) {
     }
   }
   const hipError_t err = hipStreamSynchronize(s);
-  colp.release();
   if (r) return r;
   if (err != hipSuccess) return fail(GT_ERR_HIP, "cast_image: %s", hipGetErrorString(err));
   return GT_OK;
@@ -570,7 +565,7 @@ struct TailScratch {
     o.dW = dW; o.db = db; o.accumulate = accumulate;
     return GT_OK;
   }
-  // synchronises, reports the scalars, releases; r: the launch function's status
+  // synchronises and reports the scalars (the memory goes with the object, behind that); r: the launch function's status
   int finish(int r, int nblk, double* scalars, const char* what, hipStream_t s) {
     hipError_t err = hipStreamSynchronize(s);
     StepScalars h;
@@ -581,7 +576,6 @@ struct TailScratch {
         scalars[5] = (double)h.tv; scalars[6] = (double)h.inv_tv; scalars[7] = (double)nblk;
       }
     }
-    mem.release();
     if (r) return r;
     if (err != hipSuccess) return fail(GT_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
     return GT_OK;
@@ -813,7 +807,7 @@ extern "C" int gt_op_frame(const gt_frame_case* c, void* stream) {
   if (c->partials && c->partials_cap < n_part) return fail(GT_ERR_INVALID, "frame hook: %d partials for a buffer of %lld", n_part, (long long)c->partials_cap);
   // ---- scratch: the step's scalars, its results, the two partial regions of the engine -- all NaN (0xFF bytes) until something writes them ----
   const size_t off_res = 256, off_part = 512, total = off_part + 2 * FRAME_RED_MAX_BLOCKS * sizeof(double);
-  static thread_local Scratch mem;     // grow-only, no per-call hipMalloc / hipFree (both synchronise the device)
+  static thread_local HookScratch mem;     // grow-only, no per-call hipMalloc / hipFree (both synchronise the device)
   CHK(mem.ensure(total));
   StepScalars* sc = (StepScalars*)mem.p;
   StepResults* res = (StepResults*)((char*)mem.p + off_res);
@@ -1183,7 +1177,7 @@ static int op_optim_step(const gt_optim_desc_ex* desc, float* params, float* gra
   if (!desc || !params || !grads || n < 1) return fail(GT_ERR_INVALID, "bad argument");
   CHK(optim_check_desc(desc));
   hipStream_t s = (hipStream_t)stream;
-  static thread_local Scratch tls_ws;     // [0, 512) squared-norm partials, [512] the squared norm
+  static thread_local HookScratch tls_ws;     // [0, 512) squared-norm partials, [512] the squared norm
   CHK(tls_ws.ensure(513 * sizeof(double)));
   double* part = (double*)tls_ws.p;
   gt_optim_desc_ex od;
@@ -1226,7 +1220,7 @@ static int sn_case_plan(const gt_sn_case* c, SnPlan** plan, SnBufs* b) {
   SnLayerDesc layers[GT_SN_MAX_LAYERS];
   for (int q = 0; q < c->n_layers; ++q) { layers[q].w_off = (long)c->w_off[q]; layers[q].out = c->out[q]; layers[q].in = c->in[q]; }
   CHK(sn_plan_build(layers, c->n_layers, (long)c->n_flat, plan));
-  static thread_local Scratch tls_ws;     // the double sums between the launches (grow-only)
+  static thread_local HookScratch tls_ws;     // the double sums between the launches (grow-only)
   const int r = tls_ws.ensure(sn_plan_bytes(*plan));
   if (r != GT_OK) { sn_plan_free(*plan); return r; }
   *b = sn_plan_bufs(*plan, tls_ws.p);
@@ -1278,7 +1272,7 @@ extern "C" int gt_op_grad_penalty(const gt_gp_case* c, void* stream) {
     q.W = c->W[l]; q.dW = c->dW[l]; q.in = l == 0 ? c->cd + c->Da : c->H; q.out = c->H;
     q.H = c->Hact[l]; q.spec = tail_site_spec(c->drop[l]); q.a = c->a[l]; q.c = c->c[l];
   }
-  static thread_local Scratch tls_part, tls_dw0, tls_slabs, tls_colp;      // scratch of the call (grow-only)
+  static thread_local HookScratch tls_part, tls_dw0, tls_slabs, tls_colp;      // scratch of the call (grow-only)
   const int nblk = gp_row_blocks((long)c->rows);
   CHK(tls_part.ensure((size_t)2 * nblk * sizeof(double)));
   CHK(tls_dw0.ensure((size_t)c->H * c->Da * sizeof(float)));

@@ -131,20 +131,17 @@ static int sn_refusals(const gt_engine* e, const Net& D) {
 static int sn_install(gt_engine* e, float* u, float* v, long n_u, long n_v) {
   Net& D = e->net[GT_ROLE_D];
   CHK(sn_refusals(e, D));
-  SnPlan* plan = nullptr;
-  CHK(sn_plan_of(D, &plan));
-  if (n_u != sn_plan_sum_out(plan) || n_v != sn_plan_sum_in(plan)) {
-    const long wu = sn_plan_sum_out(plan), wv = sn_plan_sum_in(plan);
-    sn_plan_free(plan);
-    return fail(GT_ERR_INVALID, "gt_set_spectral_norm: u has %ld and v %ld entries, the bound discriminator needs %ld (sum of out) and %ld (sum of in)", n_u, n_v, wu, wv);
-  }
+  SnPlan* raw = nullptr;
+  CHK(sn_plan_of(D, &raw));
+  SnPlanPtr plan(raw);
+  if (n_u != sn_plan_sum_out(raw) || n_v != sn_plan_sum_in(raw))
+    return fail(GT_ERR_INVALID, "gt_set_spectral_norm: u has %ld and v %ld entries, the bound discriminator needs %ld (sum of out) and %ld (sum of in)", n_u, n_v,
+                sn_plan_sum_out(raw), sn_plan_sum_in(raw));
   SnState& S = e->sn;
-  int r = S.weff.ensure((size_t)D.d.n_params * sizeof(float));
-  if (r == GT_OK) r = S.ws.ensure(sn_plan_bytes(plan));
-  if (r == GT_OK && hipMemset(S.weff.p, 0, (size_t)D.d.n_params * sizeof(float)) != hipSuccess) r = fail(GT_ERR_HIP, "hipMemset failed");
-  if (r != GT_OK) { sn_plan_free(plan); return r; }
-  if (S.plan) sn_plan_free(S.plan);
-  S.plan = plan; S.bufs = sn_plan_bufs(plan, S.ws.p);
+  CHK(S.weff.ensure((size_t)D.d.n_params * sizeof(float)));
+  CHK(S.ws.ensure(sn_plan_bytes(raw)));
+  HIPCHK(hipMemset(S.weff.p, 0, (size_t)D.d.n_params * sizeof(float)));
+  S.plan = std::move(plan); S.bufs = sn_plan_bufs(raw, S.ws.p);
   S.u = u; S.v = v; S.on = true;
   sn_point_weights(e);
   return GT_OK;
@@ -157,7 +154,7 @@ extern "C" int gt_set_spectral_norm(gt_engine* e, int role, float* u, float* v, 
     if (u || v) return fail(GT_ERR_INVALID, "gt_set_spectral_norm: u and v are both given or both null");
     const bool was = S.on;
     S.on = false; S.u = S.v = nullptr;
-    if (S.plan) { sn_plan_free(S.plan); S.plan = nullptr; }
+    S.plan.reset();
     if (was) { sn_point_weights(e); on_spectral_norm_off(e); }
     return GT_OK;
   }
@@ -170,7 +167,7 @@ extern "C" int gt_set_spectral_norm(gt_engine* e, int role, float* u, float* v, 
 // gt_bind_model(role D) while the feature is on: the registered buffers must fit the new network too
 int sn_rebind(gt_engine* e) {
   if (!e->sn.on) return GT_OK;
-  const long n_u = sn_plan_sum_out(e->sn.plan), n_v = sn_plan_sum_in(e->sn.plan);
+  const long n_u = sn_plan_sum_out(e->sn.plan.get()), n_v = sn_plan_sum_in(e->sn.plan.get());
   return sn_install(e, e->sn.u, e->sn.v, n_u, n_v);
 }
 
@@ -179,13 +176,13 @@ int sn_prepare_pass(gt_engine* e, hipStream_t s) {
   SnState& S = e->sn;
   if (!S.on) return GT_OK;
   Net& D = e->net[GT_ROLE_D];
-  return launch_sn_prepare(S.plan, D.d.params, S.u, S.v, S.weff.as<float>(), S.bufs, D.training, s);
+  return launch_sn_prepare(S.plan.get(), D.d.params, S.u, S.v, S.weff.as<float>(), S.bufs, D.training, s);
 }
 int sn_project_grads(gt_engine* e, double* norm_part, int* n_partial, hipStream_t s) {
   SnState& S = e->sn;
   Net& D = e->net[GT_ROLE_D];
-  *n_partial = sn_plan_partials(S.plan);
+  *n_partial = sn_plan_partials(S.plan.get());
   if (*n_partial > 2048) return fail(GT_ERR_INVALID, "spectral norm: %d squared-norm partials (at most 2048)", *n_partial);
-  CHK(launch_sn_project(S.plan, D.d.grads, S.weff.as<float>(), S.u, S.v, S.bufs, norm_part, s));
+  CHK(launch_sn_project(S.plan.get(), D.d.grads, S.weff.as<float>(), S.u, S.v, S.bufs, norm_part, s));
   return GT_OK;
 }

@@ -195,7 +195,7 @@ int sru_stack_forward(gt_engine* e, int role, const float* x, int ld_x, int nseq
   const int Lc_ = G.d.num_hidden, nent = sru_b16_entries(e, role);
   if (!(b16 && cat0) && !x) return fail(GT_ERR_INVALID, "SRU stack: null input");
   if (b16) {      // the shadows are re-made at every call: a discriminator's weights change between the two passes of one step
-    W.s_in_b.resize(nent); W.ssh.resize(nent);
+    CHK(resize_owned(W.s_in_b, nent)); CHK(resize_owned(W.ssh, nent));
     for (int l = 0; l < nent; ++l) {
       const float* Wl = l < Lc_ ? G.sru[l].W : G.last.W;
       const int rows = l < Lc_ ? G.sru[l].in : G.last.out, cols = l < Lc_ ? ncols * G.sru[l].k : G.last.in;

@@ -182,7 +182,7 @@ static bool use_b16(const gt_engine* e, int role) {
 static int refresh_shadows(gt_engine* e, int role, bool with_last, hipStream_t s) {
   Net& n = e->net[role];
   auto& sh = e->ws[role].wsh;
-  sh.resize(n.hidden.size() + 1);
+  CHK(resize_owned(sh, n.hidden.size() + 1));
   CastJobs jobs;
   jobs.n = 0; jobs.pad_ = 0;
   int blocks = 0;
@@ -208,7 +208,7 @@ static int stack_forward_b16(gt_engine* e, int role, const __bf16* in_b, int ld_
   std::vector<B16Img>& acts = e->ws[role].actb;
   const std::vector<LinShadow>& wsh = e->ws[role].wsh;
   specs.resize(n.hidden.size());
-  acts.resize(n.hidden.size());
+  CHK(resize_owned(acts, n.hidden.size()));
   const __bf16* cur = in_b;
   int ld = ld_in;
   for (size_t l = 0; l < n.hidden.size(); ++l) {
@@ -376,7 +376,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
     CHK(e->gx.ensure((size_t)N * sd * sizeof(float)));
     // T(x) = sigmoid(T x_static), x_static = x[:, :, :static_dim]   (models.py:57-60)
     CHK(linear_forward(x, G.d.in_dim, G.gate.W, sd, G.gate.b, e->tx.as<float>(), sd, N, sd, sd, ACT_SIGMOID, no_drop(), product_prec(e, GT_ROLE_G), s));
-    CHK(mlpg_forward(e, gsrc, G.d.out_dim, e->d_scol_i2o, e->d_sstride_i2o, sd, e->gx.as<float>(), sd, B, T, *band, s));
+    CHK(mlpg_forward(e, gsrc, G.d.out_dim, e->d_scol_i2o.as<int>(), e->d_sstride_i2o.as<int>(), sd, e->gx.as<float>(), sd, B, T, *band, s));
     launch_highway_forward(x, G.d.in_dim, e->tx.as<float>(), sd, e->gx.as<float>(), sd, y_hat_static, sd, N, sd, s);
     LAUNCH_CHECK();
   } else {
@@ -386,7 +386,7 @@ static int generator_forward(gt_engine* e, const float* x, const float* R, int B
       const MlpgBand* band;
       CHK(ensure_band(e, R, T, s, &band));
       if (stash) e->pass.went_through(band);
-      CHK(mlpg_forward(e, y_hat, G.d.out_dim, e->d_scol, e->d_sstride, e->Ds, y_hat_static, e->Ds, B, T, *band, s));
+      CHK(mlpg_forward(e, y_hat, G.d.out_dim, e->d_scol.as<int>(), e->d_sstride.as<int>(), e->Ds, y_hat_static, e->Ds, B, T, *band, s));
     } else {
       if (e->Ds != G.d.out_dim) return fail(GT_ERR_INVALID, "R is None but the stream config has dynamic features");
       if (stash) e->pass.went_through(nullptr);
@@ -429,7 +429,7 @@ static int build_cat(gt_engine* e, const float* x, const float* feats, int ld_fe
     launch_copy_cols(x, cd, 0, dst, ldc, 0, N, cd, s);
     LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, feats, ld_feats, 0, e->d_adv_cols, dst, ldc,
+  hipLaunchKernelGGL(gather_cols_kernel, dim3(cdiv(N * e->Da, 256)), dim3(256), 0, s, feats, ld_feats, 0, e->d_adv_cols.as<int>(), dst, ldc,
                      cd, (int)N, e->Da);
   LAUNCH_CHECK();
   return GT_OK;
@@ -642,7 +642,7 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
   // gt_set_param_ema: the generator's weight average rides this launch; its first applied update copies, every later one is a lerp
   float* ema = role == GT_ROLE_G ? e->ema.buf : (float*)nullptr;
   CHK(launch_optim_step(n.od, n.step, n.buf_live, &n.hs_cache, n.d.params, n.d.grads, np, part, n_partial, norm2_out,
-                        (const unsigned int*)e->d_fault, e->h_fault_dev, skipped, gscale, s, e->weight_clip[role], ema,
+                        e->fault_dev(), e->h_fault_dev, skipped, gscale, s, e->weight_clip[role], ema,
                         param_ema_weight(e->ema.decay), e->ema.count == 0));
   if (ema) e->ema.count += 1;
   n.buf_live = true;
@@ -653,15 +653,15 @@ static int optimizer_step(gt_engine* e, int role, double* norm2_out, hipStream_t
 int ResultsChannel::create(StepResults* device_results, const bool* poll_option) {
   static_assert(sizeof(StepResults) <= 64, "the result ticket sits 64 bytes behind the results");
   d_res = device_results; poll = poll_option;
-  if (hipHostMalloc((void**)&h_res, 128) != hipSuccess) return fail(GT_ERR_HIP, "hipHostMalloc failed");
+  CHK(h_res.alloc(128));
   memset(h_res, 0, 128);
   if (hipHostGetDevicePointer((void**)&h_res_dev, h_res, 0) != hipSuccess) { (void)hipGetLastError(); h_res_dev = nullptr; }
   if (!env_flag("GT_RES_HOSTMAP", true)) h_res_dev = nullptr;      // (measurement: results through a device -> host copy instead)
   return GT_OK;
 }
 int ResultsChannel::post_deferred(int role, hipStream_t s) {
-  if (!h_def[role]) HIPCHK(hipHostMalloc((void**)&h_def[role], sizeof(StepResults)));
-  if (!ev_def[role]) HIPCHK(hipEventCreateWithFlags(&ev_def[role], hipEventDisableTiming));
+  if (!h_def[role]) CHK(h_def[role].alloc(sizeof(StepResults)));
+  CHK(ev_def[role].ensure(hipEventDisableTiming));
   HIPCHK(hipMemcpyAsync(h_def[role], d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s));
   HIPCHK(hipEventRecord(ev_def[role], s));
   def_pending[role] = true;
@@ -692,7 +692,7 @@ int ResultsChannel::wait_early() {
 int ResultsChannel::post_early(hipStream_t s, unsigned ticket) {
   ticket_wait = ticket;
   if (!ticket) {
-    if (!ev_res) HIPCHK(hipEventCreateWithFlags(&ev_res, hipEventDisableTiming));
+    CHK(ev_res.ensure(hipEventDisableTiming));
     if (!h_res_dev) HIPCHK(hipMemcpyAsync(h_res, d_res, sizeof(StepResults), hipMemcpyDeviceToHost, s));
     HIPCHK(hipEventRecord(ev_res, s));
   }
@@ -751,7 +751,7 @@ static int d_pass_plan(gt_engine* e, const float* x, const float* real, const fl
   p.needs_f32_image = p.kind == D_LSTM || (p.kind == D_SRU && sru_d_needs_f32_input(e)) || (p.kind == D_MLP_F32 && !p.split);
   if (p.split) { p.fs.x = x; p.fs.ldx = cx_pitch(e); p.fs.cd = cd; p.fs.ld_adv = (e->Da + 3) & ~3; p.fs.wrap = p.N; }
   CatSrc& c = p.cat0;
-  c.x = x; c.cd = cd; c.fa = npass == 2 ? real : fake; c.fb = fake; c.ldf = ldf; c.idx = e->d_adv_cols; c.N = p.N; c.row_off = npass == 2 ? 0 : p.N;
+  c.x = x; c.cd = cd; c.fa = npass == 2 ? real : fake; c.fb = fake; c.ldf = ldf; c.idx = e->d_adv_cols.as<int>(); c.N = p.N; c.row_off = npass == 2 ? 0 : p.N;
   return GT_OK;
 }
 
@@ -840,7 +840,7 @@ static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's
     if (both || !e->din.img_adv2.holds(nullptr, p.fake)) {
       BuildAdvArgs ba;
       memset(&ba, 0, sizeof(ba));
-      ba.fa = p.cat0.fa; ba.fb = p.cat0.fb; ba.ldf = p.ldf; ba.idx = e->d_adv_cols; ba.na = e->Da; ba.out = dst; ba.ldo = ld; ba.split = N; ba.rows = p.rows;
+      ba.fa = p.cat0.fa; ba.fb = p.cat0.fb; ba.ldf = p.ldf; ba.idx = e->d_adv_cols.as<int>(); ba.na = e->Da; ba.out = dst; ba.ldo = ld; ba.split = N; ba.rows = p.rows;
       if (tv) tv->ride_on(e, ba);
       launch_build_adv(ba, s);
       LAUNCH_CHECK();
@@ -852,7 +852,7 @@ static int d_pass_input(gt_engine* e, DPass& p, const TvPlan* tv /* the D step's
   } else if (p.needs_f32_image) {
     CHK(e->dcat.ensure((size_t)2 * N * p.ldc * sizeof(float)));
     if (both && p.cat0.cd > 0) {
-      launch_build_cat2(p.x, p.cat0.cd, p.real, p.fake, p.ldf, e->d_adv_cols, e->Da, e->dcat.as<float>(), p.ldc, N, s);
+      launch_build_cat2(p.x, p.cat0.cd, p.real, p.fake, p.ldf, e->d_adv_cols.as<int>(), e->Da, e->dcat.as<float>(), p.ldc, N, s);
       LAUNCH_CHECK();
     } else {
       if (both) CHK(build_cat(e, p.x, p.real, p.ldf, 0, N, p.ldc, s));
@@ -967,7 +967,7 @@ static int d_pass_penalty(gt_engine* e, DPass& p, const float* mask, hipStream_t
     uint32_t k0, k1;
     gp_eps_keys(e, &k0, &k1);
     CHK(G.eps.ensure((size_t)N * sizeof(float)));
-    CHK(launch_gp_interp(p.real, p.fake, p.ldf, e->d_adv_cols, Da, G.eps_inj, k0, k1, img, ldo, col0, N, G.eps.as<float>(), s));
+    CHK(launch_gp_interp(p.real, p.fake, p.ldf, e->d_adv_cols.as<int>(), Da, G.eps_inj, k0, k1, img, ldo, col0, N, G.eps.as<float>(), s));
     G.img = img; G.img_ld = ldo; G.img_col0 = col0; G.img_rows = N;
     const int pass3[1] = {3};
     CHK(stack_forward(e, GT_ROLE_D, p.img, p.ldc, N, pass3, 1, N, W.specs, s, p.split ? &p.fs : nullptr));
@@ -1161,9 +1161,9 @@ static int generator_backward(gt_engine* e, const float* x, const float* y, cons
     CHK(linear_backward_weight(e->dtz.as<float>(), sd, x, G.d.in_dim, N, sd, sd, G.gate.dW, G.gate.db, G.grads_dirty, e->slabs, e->colp, product_prec(e, GT_ROLE_G), s,
                                &W.sdefer));
     CHK(comm_grads_ready(e, GT_ROLE_G, G.gate.dW, (long)sd * sd + sd, s));
-    CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o, e->d_sstride_i2o, sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
+    CHK(mlpg_backward(e, e->dgx.as<float>(), sd, e->d_scol_i2o.as<int>(), e->d_sstride_i2o.as<int>(), sd, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
   } else if (e->pass.band()) {
-    CHK(mlpg_backward(e, gs, e->Ds, e->d_scol, e->d_sstride, e->Ds, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
+    CHK(mlpg_backward(e, gs, e->Ds, e->d_scol.as<int>(), e->d_sstride.as<int>(), e->Ds, gy, ldgy, B, T, mse_w, y_hat, y, Do, mask, *e->pass.band(), s));
   } else {
     // no parameter generation: y_hat_static == y_hat, the gradient passes straight through,
     // plus the masked-MSE gradient (which also yields loss_mse's sum)
@@ -1313,7 +1313,7 @@ extern "C" int gt_update_generator_begin(gt_engine* e, const float* x, const flo
     StaticGradArgs q;
     memset(&q, 0, sizeof(q));
     q.yhs = y_hat_static; q.ld1 = Ds; q.ys = y_static; q.ld2 = Ds; q.mask = mask; q.rows = N; q.Ds = Ds; q.mge_w = mge_w;
-    q.adv_inv = e->d_adv_inv; q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
+    q.adv_inv = e->d_adv_inv.as<int>(); q.leak = leak; q.ldl = e->Da; q.gadv = gadv; q.lda = e->Da; q.adv_w = adv_w; q.gs = gs; q.ldg = Ds;
     q.partial = riders ? (double*)nullptr : e->partial.as<double>(); q.sc = e->sc(); q.fin = fin; q.leak_unnorm = leak && e->leak.unnormalised() ? 1 : 0;
     mge_blocks = launch_static_grad(q, s);
   } else      // phase != "train": no gradient to assemble, the finalisation alone

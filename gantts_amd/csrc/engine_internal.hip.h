@@ -25,7 +25,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -111,20 +113,58 @@ struct GemmProfiler {
 };
 extern GemmProfiler g_prof;
 
+// Owning types: every device block, pinned host block and event of the engine belongs to one of these and goes back in its destructor.
+// They alone call hipFree / hipHostMalloc / hipHostFree / hipEventCreate* / hipEventDestroy (besides the interprocess arena of eng_ipc.hip
+// and g_prof's pool above) and they keep gt_live_resources' counters.  A destructor does not synchronise: whoever drops one of them
+// under work that may still be queued synchronises first (gt_engine_destroy, resize_owned, the MLPG cache).  All are move-only or fixed.
+enum { LIVE_DEV_BLOCKS = 0, LIVE_DEV_BYTES = 1, LIVE_PINNED = 2, LIVE_EVENTS = 3 };
+void live_count(int slot, int64_t delta);      // eng_core.hip: relaxed, process-wide
+
 struct Scratch {  // growable device buffer
   void* p = nullptr;
   size_t bytes = 0;
+  Scratch() = default;      Scratch(Scratch&& o) noexcept : p(o.p), bytes(o.bytes), counted(o.counted) { o.p = nullptr; o.bytes = 0; }
+  Scratch(const Scratch&) = delete;      Scratch& operator=(const Scratch&) = delete;      // a copy would be freed twice
+  ~Scratch() { release(); }
   int ensure(size_t need) {
     if (need <= bytes) return GT_OK;
-    if (p) { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipFree(p)); p = nullptr; bytes = 0; }
+    if (p) { HIPCHK(hipDeviceSynchronize()); release(); }
     const size_t cap = need + need / 8;
     HIPCHK(hipMalloc(&p, cap));
     bytes = cap;
+    if (counted) { live_count(LIVE_DEV_BLOCKS, 1); live_count(LIVE_DEV_BYTES, (int64_t)cap); }
     return GT_OK;
   }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } }
+  void release() {      // the block goes now (the caller has synchronised); today only ensure() and the destructor call it
+    if (p) { (void)hipFree(p); if (counted) { live_count(LIVE_DEV_BLOCKS, -1); live_count(LIVE_DEV_BYTES, -(int64_t)bytes); } }
+    p = nullptr; bytes = 0;
+  }
   template <typename T> T* as() const { return (T*)p; }
+ protected:
+  bool counted = true;
 };
+// A hook's `static thread_local` buffer: its destructor frees NOTHING, because it runs at thread or process teardown, where a hipFree
+// may come after the HIP runtime has gone.  How: the derived destructor runs first and empties the object, so ~Scratch finds no block.
+// Not counted by gt_live_resources (`counted` is cleared before the first ensure()).
+struct HookScratch : Scratch { HookScratch() { counted = false; }      ~HookScratch() { p = nullptr; bytes = 0; } };
+template <typename T> struct Pinned {  // pinned host block
+  T* p = nullptr;
+  Pinned() = default;      Pinned(const Pinned&) = delete;      Pinned& operator=(const Pinned&) = delete;
+  ~Pinned() { release(); }
+  int alloc(size_t n_bytes) { release(); HIPCHK(hipHostMalloc((void**)&p, n_bytes)); live_count(LIVE_PINNED, 1); return GT_OK; }      // in place of what it held
+  void release() { if (p) { (void)hipHostFree(p); live_count(LIVE_PINNED, -1); p = nullptr; } }
+  operator T*() const { return p; }
+};
+struct Event {  // HIP event, created by the first ensure() with the flags given there
+  hipEvent_t ev = nullptr;
+  Event() = default;      Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+  Event(const Event&) = delete;      Event& operator=(const Event&) = delete;
+  ~Event() { if (ev) { (void)hipEventDestroy(ev); live_count(LIVE_EVENTS, -1); } }
+  int ensure(unsigned flags) { if (!ev) { HIPCHK(hipEventCreateWithFlags(&ev, flags)); live_count(LIVE_EVENTS, 1); } return GT_OK; }
+  operator hipEvent_t() const { return ev; }
+};
+// a per-layer vector of owning buffers takes another length: dropping elements frees their blocks, so the device is idle first
+template <typename V> static inline int resize_owned(V& v, size_t n) { if (n < v.size()) HIPCHK(hipDeviceSynchronize());      v.resize(n); return GT_OK; }
 
 // Deferred weight-gradient combines (eng_gemm_f32.hip: linear_backward_weight): the partial slabs of every layer go to their
 // own piece of a pool and the combine is only RECORDED; slab_defer_flush() runs all recorded combines in one launch.
@@ -154,7 +194,6 @@ struct B16Img {
     if (want_t) CHK(tr.ensure((size_t)cols * ldt * 2 + 64));
     return GT_OK;
   }
-  void release() { rm.release(); tr.release(); }
 };
 // bf16 shadows of one nn.Linear weight (out, in): w [out][ldw] feeds the forward product, wt [in][ldwt] backward-data
 struct LinShadow {
@@ -167,7 +206,6 @@ struct LinShadow {
     CHK(wt.ensure((size_t)in * ldwt * 2 + 64));
     return GT_OK;
   }
-  void release() { w.release(); wt.release(); }
 };
 static inline bool is_i2o(int arch) { return arch == GT_ARCH_IN2OUT || arch == GT_ARCH_IN2OUT_RNN; }
 static inline bool has_lstm_body(int arch) { return arch == GT_ARCH_LSTM || arch == GT_ARCH_IN2OUT_RNN; }
@@ -217,11 +255,6 @@ struct NetWs {
   std::vector<Scratch> u, h, c, xdrop, xmask, wt, omask;
   std::vector<B16Img> s_in_b; B16Img du_b;         // image of every layer's (dropped) input (+ the top output); dU of the current layer, both orientations
   std::vector<LinShadow> ssh;                      // per layer W (n_in, ncols*k) as w [n_in][..] and wt [ncols*k][n_in]; last entry: hidden2out
-  template <typename... V> static void release_all(V&... v) { auto rel = [](auto& m) { for (auto& x : m) x.release(); }; (rel(v), ...); }
-  void release() {      // every member
-    release_all(act, actb, wsh, xproj, gates, cst, out, outd, l_in_b, l_dg_b, lsh, u, h, c, xdrop, xmask, wt, omask, s_in_b, ssh);
-    w0pad.release(); sdefer.pool.release(); hshift.release(); dout.release(); l_hs_b.release(); du_b.release();
-  }
 };
 struct StepCopy {      // a copy of a caller tensor made once per step (with a 16-byte pitch, or dense), keyed by what it was made from
   Scratch buf; const float* src = nullptr; int ld = 0, cols = 0; long rows = 0; uint64_t step = ~0ULL;
@@ -248,34 +281,30 @@ struct MlpgWindows {
 };
 struct MlpgCache {
   static constexpr size_t MAX_ENTRIES = 256;
-  std::vector<MlpgBand*> entries;
+  std::vector<std::unique_ptr<MlpgBand>> entries;
   uint64_t tick = 0;
   Scratch tmp;                      // per-offset maxima of a new R (persistent: no hipFree on the step path)
   bool has_win = false;
   MlpgWindows win;                  // zero-filled beyond the registered windows and coefficients: compared with memcmp
   Scratch fac, wide;                // device build: Cholesky factor and selected inverse (float64), the taps at the candidate width
-  void clear() { for (auto* b : entries) { b->band.release(); delete b; } entries.clear(); }
+  void clear() { entries.clear(); }      // (the caller has synchronised and told on_band_freed)
 };
 
 // How a step's scalars reach the host, three routes and the one owner of their state.  early: the finalising launch of a fused call writes them into
 // the pinned page and the call returns once they have landed -- seen by polling a ticket behind them (GT_OPT_POLL_RESULTS) or, ticket 0, by an event -- with the rest
 // of the step still queued; deferred (split-phase, out == NULL): own pinned copy + event per role, collected by gt_update_*_result; blocking: copy + synchronise.
 struct ResultsChannel {
-  StepResults *h_res = nullptr, *h_res_dev = nullptr;      // pinned page: the results, the ticket 64 bytes behind them; the same page as the kernels see it (null: GT_RES_HOSTMAP=0, or no device view)
+  Pinned<StepResults> h_res; StepResults* h_res_dev = nullptr;      // pinned page: the results, the ticket 64 bytes behind them; the same page as the kernels see it (null: GT_RES_HOSTMAP=0, or no device view)
   StepResults* d_res = nullptr; const bool* poll = nullptr;      // of the engine: res(), where the finalising launches of the other routes leave the results; opt_poll_results
   bool early = false, early_done = false;  // a fused call is running; its early results are posted and not waited for yet
-  unsigned ticket_next = 0, ticket_wait = 0; hipEvent_t ev_res = nullptr;      // last number handed out / the one the posted early results carry (0: ev_res is used)
-  StepResults* h_def[2] = {nullptr, nullptr}; hipEvent_t ev_def[2] = {nullptr, nullptr}; bool def_pending[2] = {false, false};
+  unsigned ticket_next = 0, ticket_wait = 0; Event ev_res;      // last number handed out / the one the posted early results carry (0: ev_res is used)
+  Pinned<StepResults> h_def[2]; Event ev_def[2]; bool def_pending[2] = {false, false};
   bool begin_done[2] = {false, false};     // per role: gt_update_*_begin has run, _end has not
   long long waits = 0;                     // gt_host_wait_count: times a call blocked its thread on the device (wait_early, collect, fetch; gt_ledger_read adds its own)
   int create(StepResults* device_results, const bool* poll_option);
-  void destroy() {
-    if (h_res) (void)hipHostFree(h_res);      if (ev_res) (void)hipEventDestroy(ev_res);
-    for (int r = 0; r < 2; ++r) { if (h_def[r]) (void)hipHostFree(h_def[r]); if (ev_def[r]) (void)hipEventDestroy(ev_def[r]); }
-  }
   StepResults* target() const { return h_res_dev ? h_res_dev : d_res; }      // where a launch that reports early writes the results
   unsigned* ticket_dev() const { return h_res_dev ? (unsigned*)((char*)h_res_dev + 64) : nullptr; }
-  volatile unsigned* ticket_host() const { return (volatile unsigned*)((char*)h_res + 64); }
+  volatile unsigned* ticket_host() const { return (volatile unsigned*)((char*)h_res.p + 64); }
   unsigned take_ticket() { if (!*poll || !h_res_dev) return 0;      if (++ticket_next == 0) ++ticket_next;      return ticket_next; }      // for results that the NEXT finalising launch writes into the host page (0: not available)
   int post_early(hipStream_t s, unsigned ticket = 0);
   int wait_early();                        // only the scalars; backward + step stay queued
@@ -304,13 +333,12 @@ struct EpochLedger {
   const void *mean = nullptr, *stdv = nullptr;     // the caller's statistics (device), read by every gt_ledger_add
   Scratch rec, len;                                // len: the batch's lengths as int32 (grows with B only)
   size_t off_tab = 0, off_part = 0;
-  double* h_out = nullptr;                         // pinned: gt_ledger_read's copy
+  Pinned<double> h_out;                            // gt_ledger_read's copy
   double* record() const { return rec.as<double>(); }
   double* dist() const { return rec.as<double>() + GT_LEDGER_SLOTS; }
   int* col_stat() const { return (int*)((char*)rec.p + off_tab); }
   int* col_role() const { return col_stat() + Ds; }
   double* partials() const { return (double*)((char*)rec.p + off_part); }
-  void release() { rec.release(); len.release(); if (h_out) (void)hipHostFree(h_out); h_out = nullptr; configured = false; }
 };
 
 // Spectral normalisation of the MLP discriminator (eng_spectral_norm.hip, spectral_norm_kernels.hip.h).  SnPlan: the job table of a
@@ -318,11 +346,14 @@ struct EpochLedger {
 // between the launches, sized by sn_plan_bytes.  SnState: the engine's -- u, v are the caller's (like optimizer state), W_eff the engine's.
 struct SnLayerDesc { long w_off; int out, in; };
 struct SnPlan;
+void sn_plan_free(SnPlan* p);
+struct SnPlanFree { void operator()(SnPlan* p) const { sn_plan_free(p); } };
+using SnPlanPtr = std::unique_ptr<SnPlan, SnPlanFree>;
 struct SnBufs { double *t, *r, *sp, *s; float* sigma; };
 struct SnState {
   bool on = false;
   float *u = nullptr, *v = nullptr;                // caller-owned, sum(out) and sum(in) floats
-  SnPlan* plan = nullptr;
+  SnPlanPtr plan;
   Scratch weff, ws;                                // W / sigma in the flat buffer's layout (biases unused); SnBufs
   SnBufs bufs = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
@@ -354,7 +385,6 @@ struct GpState {
   Scratch g, dw0, part, rec, eps;
   hipStream_t stream = nullptr;                    // of the last penalised step (gt_grad_penalty_result synchronises it)
   const float* img = nullptr; int img_ld = 0, img_col0 = 0; long img_rows = 0;      // where the last step's x_hat image lies (gt_grad_penalty_peek)
-  void release() { g.release(); dw0.release(); part.release(); rec.release(); eps.release(); }
 };
 
 // The loss normaliser Tv = sum(mask) (or what the caller gave instead) and 1 / Tv in the step's scalars: the one owner of everything the host
@@ -376,7 +406,7 @@ struct LossNormaliser {
   void forget() { mask = nullptr; }      void overwritten() { forget(); }
   void set_override(float tv) { ovr = tv; dev = nullptr; }      // (the memo is keyed on the override: nothing to forget)
   void set_total_dev(const double* p) { dev = p; forget(); }    // re-read on the next step function
-  int attach() { return total.ensure(64); }      void release() { total.release(); }      // gt_comm_init, gt_engine_destroy
+  int attach() { return total.ensure(64); }      // gt_comm_init
   int start(gt_engine* e, const float* m, long N, hipStream_t s);      // the local count by a launch of its own, then send
   int send(gt_engine* e, hipStream_t s);                               // all-reduce of reduced() on the communicator's stream, behind what `s` holds
   int join(gt_engine* e, hipStream_t s);
@@ -404,7 +434,7 @@ struct KeptLeak {
   bool unnormalised() const { return pending && unnorm; }
   // gt_zero_grad(G); consumed by the G step / gt_flush_generator_grads; no longer the gradient of what the next G step runs (storage form,
   // objective, spectral norm, a recycled band, gt_clear_faults)
-  void drop() { pending = unnorm = false; }      void release() { buf.release(); }
+  void drop() { pending = unnorm = false; }
  private:
   Scratch buf; bool pending = false, unnorm = false;
 };
@@ -460,9 +490,9 @@ struct gt_engine {
   // derived stream maps (device)
   int Dout_cfg = 0, Ds = 0, Da = 0;
   std::vector<int> h_scol, h_sstride, h_adv_cols, h_adv_inv;
-  int *d_scol = nullptr, *d_sstride = nullptr, *d_adv_cols = nullptr, *d_adv_inv = nullptr;
+  Scratch d_scol, d_sstride, d_adv_cols, d_adv_inv;      // int [Ds] / [Da] / [Ds]
   // In2Out uses a single dynamic stream of width out_dim
-  int *d_scol_i2o = nullptr, *d_sstride_i2o = nullptr; int i2o_ds = 0;
+  Scratch d_scol_i2o, d_sstride_i2o; int i2o_ds = 0;
   MlpgCache mlpg;
   Scratch mlpg_var_ws;                     // variance-weighted MLPG: refusal flag, lengths, then L and z of one group of sequences (float64)
   NetWs ws[2];                             // workspace: per role, then (below) what one call uses and both roles share
@@ -513,8 +543,8 @@ struct gt_engine {
   // gt_set_x_pitch never makes a step fail (DevicePrefetcher(pitch_x=True) with a recurrent discriminator did).
   Scratch gx_dense;                                // dense_gx's copy (GenPass::input_dense)
   unsigned int* h_fault_dev = nullptr;             // device view of h_fault[1]: the optimizer kernel mirrors a raised fault word
-  unsigned int* d_fault = nullptr;                 // device fault word of the persistent kernels (0 = ok)
-  unsigned int* h_fault = nullptr;                 // pinned mirror, refreshed behind every persistent launch
+  Scratch d_fault;                                 // device fault word of the persistent kernels (0 = ok)
+  Pinned<unsigned int> h_fault;                    // pinned mirror, refreshed behind every persistent launch
   bool lstm_persistent = getenv("GT_LSTM_STEPS") == nullptr;   // GT_OPT_LSTM_PERSISTENT (the environment only provides the default at creation)
   int lstm_fwd_upc = 0;                            // 0 = automatic
   bool lstm_xcd_local = getenv("GT_LSTM_NO_XCD_LOCAL") == nullptr;   // GT_OPT_LSTM_XCD_LOCAL
@@ -523,10 +553,11 @@ struct gt_engine {
   // sequence lengths travel on the step stream through a small ring (pinned host slot -> device slot): the kernels of
   // the previous step, still queued when the next batch's lengths arrive, keep reading THEIR slot
   static constexpr int LEN_RING = 4;
-  int* len_host[LEN_RING] = {nullptr, nullptr, nullptr, nullptr};
+  Pinned<int> len_host[LEN_RING];
   Scratch len_dev[LEN_RING];
-  hipEvent_t len_ev[LEN_RING] = {nullptr, nullptr, nullptr, nullptr};
+  Event len_ev[LEN_RING];
   int len_cap = 0, len_slot = -1;
+  unsigned int* fault_dev() const { return d_fault.as<unsigned int>(); }
   int* d_lengths() { return len_slot < 0 ? nullptr : len_dev[len_slot].as<int>(); }
   bool sru_d_bf16 = env_flag("GT_SRU_D_BF16", false);      // GT_OPT_SRU_D_BF16: an SRU discriminator's products through the bf16-storage family
   int gan_objective = 0;                           // GT_OPT_GAN_OBJECTIVE: the head's adversarial objective (gan_objective.hip.h), 0 = the reference's sigmoid + log loss
@@ -738,7 +769,6 @@ int out_layer_backward(gt_engine* e, int role, const float* gy, int ldgy, long r
 // gt_op_spectral_norm / gt_op_sn_project (eng_ops.hip); gt_sn_path_counts counts them on the host (slot layout in gantts_hip.h)
 // ------------------------------------------------------------------------------------------
 int sn_plan_build(const SnLayerDesc* layers, int n, long n_flat, SnPlan** out);      // checks the table: dims in [1, 512], ranges ascending inside [0, n_flat)
-void sn_plan_free(SnPlan* p);
 long sn_plan_sum_out(const SnPlan* p);
 long sn_plan_sum_in(const SnPlan* p);
 int sn_plan_partials(const SnPlan* p);                   // squared-norm partials launch_sn_project writes
@@ -772,11 +802,11 @@ struct GtComm {
   void* comm = nullptr;
   int rank = 0, world = 1;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event ev[8];
   int next_ev = 0;
-  hipEvent_t ev_done = nullptr;
+  Event ev_done;
   // schedule trace (gt_comm_trace, a measurement): every message and every join of the step stream bracketed by timed events
-  struct TraceRec { int kind, inl; double bytes; hipEvent_t e0, e1; bool closed; };     // kind 0 message, 1 join; closed: e1 was recorded
+  struct TraceRec { int kind, inl; double bytes; Event e0, e1; bool closed; };     // kind 0 message, 1 join; closed: e1 was recorded
   bool trace = false;
   long trace_dropped = 0;                          // messages / joins that found the trace full
   std::vector<TraceRec> trec;

@@ -178,6 +178,10 @@ const char* gt_last_error(void);
 const char* gt_version(void);
 int gt_engine_create(const gt_stream_config* cfg, gt_engine** out);
 void gt_engine_destroy(gt_engine* e);
+/* What the engines of this process own right now (introspection, tests): out[0] live device blocks, out[1] their bytes, out[2] live
+ * pinned host blocks, out[3] live events -- all of engine lifetime, process-wide relaxed counters kept on the host by the types that own
+ * them.  The grow-only scratch of the stand-alone gt_op_* hooks lives as long as its thread and is not counted. */
+int gt_live_resources(int64_t out[4]);
 
 /* getattr(gantts.models, name)(**params) + .cuda()            (train.py:773-793).  GT_ROLE_G: every architecture; GT_ROLE_D: GT_ARCH_MLP,
  * GT_ARCH_LSTM (an LSTMRNN scoring frames) or GT_ARCH_SRU (an SRURNN scoring frames: sequence lengths ignored as in the reference, at
