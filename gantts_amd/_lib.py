@@ -28,6 +28,10 @@ OPT_GAN_OBJECTIVE = 21
 # against the labels 0 / 1: 0.5; hinge and wgan: the sign of z)
 GAN_OBJECTIVES = {"bce": 0, "ls": 1, "hinge": 2, "wgan": 3}
 GAN_OBJECTIVE_THRESHOLD = {"bce": 0.5, "ls": 0.5, "hinge": 0.0, "wgan": 0.0}
+# the f-GAN divergences (Nowozin et al. 2016) of the same option, in tables of their own: ids and the "correct" threshold on z,
+# g_f(z) > f'(1) (kl: z > 1; reverse kl and Jensen-Shannon: z > 0)
+GAN_F_DIVERGENCES = {"kl": 4, "rkl": 5, "js": 6}
+GAN_F_DIVERGENCE_THRESHOLD = {"kl": 1.0, "rkl": 0.0, "js": 0.0}
 IPC_HANDLE_BYTES, IPC_MAX_WORLD = 64, 8
 PROFILE_SLOTS = 16
 LSTM_PATH_SLOTS, LSTM_PATH_STEPS, LSTM_PATH_DECLINED = 34, 32, 33      # gt_lstm_path_counts

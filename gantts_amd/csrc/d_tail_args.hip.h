@@ -20,7 +20,7 @@ struct HeadCall {
   const double* tv_dev;        // the valid-frame count when it is not in the step's scalars yet
   unsigned ticket;             // early_res in host memory: the ticket that announces it
   bool unit_tv;                // seed the backward pass of the UNNORMALISED loss (GT_OPT_COMM_TV_IN_SUMS)
-  int objective;               // GanObjective (gan_objective.hip.h): 0 the reference's sigmoid + log loss, 1 ls, 2 hinge, 3 wgan
+  int objective;               // GanObjective (gan_objective.hip.h): 0 the reference's sigmoid + log loss, 1 ls, 2 hinge, 3 wgan, 4 kl, 5 rkl, 6 js
 };
 
 // Where a pass leaves its per-workgroup partials and where the finalising launch puts their sums.

@@ -1,5 +1,5 @@
 // The launches of d_head_kernel and dstack_kernel, templated on the adversarial objective (gan_objective.hip.h): included by eng_step.hip
-// and eng_dstack.hip for objective 0 and by eng_gan_objective.hip for the objectives 1 .. 3, so that the two groups of instantiations
+// and eng_dstack.hip for objective 0 and by eng_gan_objective.hip for the objectives 1 .. 3 and eng_gan_fdiv.hip for 4 .. 6, so that the groups of instantiations
 // build in parallel and share one dispatch.  gt_head_path_counts counts a launch in the slot of its FORM, whatever its objective.
 #pragma once
 #include "engine_internal.hip.h"

@@ -179,12 +179,12 @@ static long expected_params(const gt_model_desc& d) {
   return n;
 }
 
-// GT_OPT_GAN_OBJECTIVE against a discriminator's output layer: the sigmoid belongs to objective 0 alone (ls, hinge and wgan score z itself)
+// GT_OPT_GAN_OBJECTIVE against a discriminator's output layer: the sigmoid belongs to objective 0 alone (ls, hinge, wgan and the f-GAN divergences score z itself)
 static int gan_objective_fits(int objective, bool last_sigmoid) {
   if (objective == 0 && !last_sigmoid)
     return fail(GT_ERR_INVALID, "discriminator must be MLP, LSTMRNN or SRURNN with out_dim=1, last_sigmoid=True (hparams.py:56-64,230-239; train.py:773-774)");
   if (objective != 0 && last_sigmoid)
-    return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE %d (1 ls, 2 hinge, 3 wgan) scores the output layer's pre-activation: the discriminator must have last_sigmoid=False",
+    return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE %d (1 ls, 2 hinge, 3 wgan, 4 kl, 5 rkl, 6 js) scores the output layer's pre-activation: the discriminator must have last_sigmoid=False",
                 objective);
   return GT_OK;
 }
@@ -419,7 +419,7 @@ extern "C" int gt_set_option(gt_engine* e, int option, int value) {
       e->sru_d_bf16 = value != 0;
       return GT_OK;
     case GT_OPT_GAN_OBJECTIVE:
-      if (value < 0 || value >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE takes 0 (bce), 1 (ls), 2 (hinge) or 3 (wgan), not %d", value);
+      if (value < 0 || value >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "GT_OPT_GAN_OBJECTIVE takes 0 (bce), 1 (ls), 2 (hinge), 3 (wgan), 4 (kl), 5 (rkl) or 6 (js), not %d", value);
       if (e->net[GT_ROLE_D].bound) CHK(gan_objective_fits(value, e->net[GT_ROLE_D].d.last_sigmoid != 0));
       if (e->gan_objective != value) on_objective_changed(e);
       e->gan_objective = value;

@@ -601,7 +601,7 @@ extern "C" int gt_op_d_head(const gt_d_head_case* c, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "null case");
   if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
     return fail(GT_ERR_INVALID, "head hook: %s", why);
-  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "head hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan)", c->objective);
+  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "head hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan, 4 kl, 5 rkl, 6 js)", c->objective);
   if (c->K < 1 || c->K > 1024) return fail(GT_ERR_INVALID, "head hook: K = %d (1 .. 1024)", c->K);
   if (!c->H || !c->w || !c->bias) return fail(GT_ERR_INVALID, "head hook: needs H, w and bias");
   const bool img = c->h_ld > 0;
@@ -643,7 +643,7 @@ extern "C" int gt_op_dstack(const gt_dstack_case* c, void* stream) {
   if (!c) return fail(GT_ERR_INVALID, "null case");
   if (const char* why = tail_common_bad(c->mode, c->rows, c->n_real, c->n_mask, c->mask, c->has_tv, c->tv, c->tv_dev, c->unit_tv))
     return fail(GT_ERR_INVALID, "fused stack hook: %s", why);
-  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "fused stack hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan)", c->objective);
+  if (c->objective < 0 || c->objective >= GAN_OBJ_COUNT) return fail(GT_ERR_INVALID, "fused stack hook: objective = %d (0 bce, 1 ls, 2 hinge, 3 wgan, 4 kl, 5 rkl, 6 js)", c->objective);
   if (c->L < 1 || c->L > DS_MAXL) return fail(GT_ERR_INVALID, "fused stack hook: L = %d (1 .. %d)", c->L, DS_MAXL);
   if (!dstack_hidden_ok(c->hidden_dim)) return fail(GT_ERR_INVALID, "fused stack hook: hidden_dim 128 or 256");
   const int H = c->hidden_dim;

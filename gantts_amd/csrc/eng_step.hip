@@ -486,7 +486,7 @@ int launch_dstack_pass(const DStackCall& k, hipStream_t s) {
   return launch_head_finalize(c, k.o, nblk, H, s);
 }
 
-// (the launch templates of the head pass: d_tail_launch.hip.h; objective 0 is instantiated here, 1 .. 3 in eng_gan_objective.hip)
+// (the launch templates of the head pass: d_tail_launch.hip.h; objective 0 is instantiated here, 1 .. 3 in eng_gan_objective.hip, 4 .. 6 in eng_gan_fdiv.hip)
 int launch_d_head(const HeadArgs& a, hipStream_t s) {
   const int nblk = d_head_blocks(a.c.rows);
   if (nblk > a.o.hp_cap || (long)nblk * a.K > a.o.dw_cap) return fail(GT_ERR_INVALID, "discriminator head: partial buffers too small for %d workgroups", nblk);

@@ -620,7 +620,7 @@ int launch_optim_step(const gt_optim_desc_ex& od, long step, bool buf_live, Opti
 int param_ema_check_decay(const char* who, double decay);
 static inline float param_ema_weight(double decay) { return (float)(1.0 - decay); }
 int check_param_ema(const gt_engine* e);
-// GT_OPT_GAN_OBJECTIVE against the bound discriminator's last_sigmoid (true under objective 0, false under 1 .. 3): checked at whichever of
+// GT_OPT_GAN_OBJECTIVE against the bound discriminator's last_sigmoid (true under objective 0, false under 1 .. 6): checked at whichever of
 // gt_bind_model / gt_set_option comes second and at the entry of every step that runs the discriminator, before any launch
 int check_gan_objective(const gt_engine* e);
 // NAdam's mu_product / ASGD's eta and mu after `t` updates (t >= od.step); `cache` may be null
@@ -655,6 +655,8 @@ int dstack_panels(long rows);
 int launch_dstack(const gt::DStackArgs& a, int hidden_dim, hipStream_t s, int objective = 0);
 // eng_gan_objective.hip: the instantiations of both tail kernels for the objectives 1 .. 3 (gan_objective.hip.h), in a unit of their own
 int launch_dstack_objective(const gt::DStackArgs& a, int hidden_dim, int objective, hipStream_t s);
+// eng_gan_fdiv.hip: the same for the f-GAN divergences 4 .. 6, reached through launch_dstack_objective
+int launch_dstack_fdiv(const gt::DStackArgs& a, int hidden_dim, int objective, hipStream_t s);
 // gt_head_path_counts: launches of the discriminator's tail by kernel, counted on the host where they are issued (slot layout in
 // gantts_hip.h).  launch_d_head / launch_dstack_pass / launch_head_finalize (eng_step.hip, d_tail_args.hip.h): the one launch site of each
 // kernel, shared by the engine's run_head / run_dstack and the parity hooks (eng_ops.hip).
@@ -665,7 +667,8 @@ void head_path_count(int slot);
 namespace gt { struct HeadCall; struct HeadSums; struct HeadArgs; struct DStackCall; }
 int launch_head_finalize(const gt::HeadCall& c, const gt::HeadSums& o, int nblk, int K, hipStream_t s);
 int launch_d_head(const gt::HeadArgs& a, hipStream_t s);
-int launch_d_head_objective(const gt::HeadArgs& a, int nblk, hipStream_t s);      // (eng_gan_objective.hip) the head pass alone, objectives 1 .. 3
+int launch_d_head_objective(const gt::HeadArgs& a, int nblk, hipStream_t s);      // (eng_gan_objective.hip) the head pass alone, objectives 1 .. 6
+int launch_d_head_fdiv(const gt::HeadArgs& a, int nblk, hipStream_t s);           // (eng_gan_fdiv.hip) objectives 4 .. 6, reached through launch_d_head_objective
 int launch_dstack_pass(const gt::DStackCall& k, hipStream_t s);
 gt::DropoutSpec no_drop();
 int launch_gemm(int kind, const gt::GemmArgs& g, int prec, hipStream_t s);      // GEMM_NT / GEMM_NN, tiles chosen from the shape

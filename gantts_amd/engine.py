@@ -38,12 +38,22 @@ def stream_config_from_hp(hp):
 
 
 def gan_objective_of(hp):
-    """``hp.gan_objective`` (opt-in, read with getattr: "bce" -- the reference's sigmoid + log loss, the default --, "ls", "hinge" or
-    "wgan"), checked against the names the engine knows."""
+    """``hp.gan_objective`` (opt-in, read with getattr: "bce" -- the reference's sigmoid + log loss, the default --, "ls", "hinge",
+    "wgan", or an f-GAN divergence: "kl", "rkl", "js"), checked against the names the engine knows."""
     name = getattr(hp, "gan_objective", "bce")
-    if name not in L.GAN_OBJECTIVES:
-        raise ValueError("hp.gan_objective = %r: one of %s" % (name, ", ".join(sorted(L.GAN_OBJECTIVES))))
+    if name not in L.GAN_OBJECTIVES and name not in L.GAN_F_DIVERGENCES:
+        raise ValueError("hp.gan_objective = %r: one of %s" % (name, ", ".join(sorted(L.GAN_OBJECTIVES) + sorted(L.GAN_F_DIVERGENCES))))
     return name
+
+
+def gan_objective_id(name):
+    """The GT_OPT_GAN_OBJECTIVE id of an objective's name (``_lib.GAN_OBJECTIVES`` and ``_lib.GAN_F_DIVERGENCES`` are one id space)."""
+    return L.GAN_OBJECTIVES[name] if name in L.GAN_OBJECTIVES else L.GAN_F_DIVERGENCES[name]
+
+
+def gan_objective_threshold(name):
+    """What D(x) is compared with to call a frame "natural" under the objective (``train_loop``'s spoofing rate)."""
+    return L.GAN_OBJECTIVE_THRESHOLD[name] if name in L.GAN_OBJECTIVE_THRESHOLD else L.GAN_F_DIVERGENCE_THRESHOLD[name]
 
 
 def grad_penalty_of(hp):
@@ -141,7 +151,7 @@ class StepEngine(object):
         # hp.gan_objective / hp.discriminator_weight_clip: opt-in switches beyond the reference, sent before any network is bound
         self.gan_objective = gan_objective_of(hp)
         if self.gan_objective != "bce":
-            self.set_option("gan_objective", L.GAN_OBJECTIVES[self.gan_objective])
+            self.set_option("gan_objective", gan_objective_id(self.gan_objective))
         clip = float(getattr(hp, "discriminator_weight_clip", 0.0))
         if clip != 0.0:
             self.set_weight_clip(L.ROLE_D, clip)
@@ -335,9 +345,9 @@ class StepEngine(object):
         ``"sru_d_bf16"`` (0 / 1, default 0 or ``GT_SRU_D_BF16``; independent of ``"matmul_bf16"``) runs the products of an SRURNN in
         the discriminator slot on bf16 images with float32 accumulation -- ``hidden_dim % 8 == 0`` is needed, any other width
         silently keeps the float32 path.
-        ``"gan_objective"`` (0 bce, 1 ls, 2 hinge, 3 wgan -- ``_lib.GAN_OBJECTIVES``; default 0, or ``hp.gan_objective`` at creation)
-        selects the adversarial objective of both update steps: same launches, other losses.  The bound discriminator must have
-        ``last_sigmoid=True`` under 0 and ``last_sigmoid=False`` under 1 .. 3."""
+        ``"gan_objective"`` (0 bce, 1 ls, 2 hinge, 3 wgan -- ``_lib.GAN_OBJECTIVES``; 4 kl, 5 rkl, 6 js -- ``_lib.GAN_F_DIVERGENCES``;
+        default 0, or ``hp.gan_objective`` at creation) selects the adversarial objective of both update steps: same launches, other
+        losses.  The bound discriminator must have ``last_sigmoid=True`` under 0 and ``last_sigmoid=False`` under 1 .. 6."""
         opts = {"lstm_persistent": L.OPT_LSTM_PERSISTENT,
                 "lstm_fwd_units": L.OPT_LSTM_FWD_UNITS, "lstm_xcd_local": L.OPT_LSTM_XCD_LOCAL,
                 "matmul_bf16": L.OPT_MATMUL_BF16, "split_first_layer": L.OPT_SPLIT_FIRST_LAYER,
@@ -352,7 +362,7 @@ class StepEngine(object):
         if name == "matmul_bf16":
             self._opt_bf16 = bool(value)
         if name == "gan_objective":
-            self.gan_objective = [k for k, v in L.GAN_OBJECTIVES.items() if v == int(value)][0]
+            self.gan_objective = [k for k, v in list(L.GAN_OBJECTIVES.items()) + list(L.GAN_F_DIVERGENCES.items()) if v == int(value)][0]
 
     def set_weight_clip(self, role, c):
         """Every later optimizer step of ``role`` (the discriminator's alone) clamps each updated parameter to ``[-c, c]`` inside the

@@ -295,9 +295,9 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     epoch ledger: one extra launch per batch, one read per phase) and the host does not wait for a step's scalars or a batch's
     distortion sums; the logged values are the same bits.
 
-    ``hp.gan_objective`` ("bce", the default; "ls", "hinge", "wgan") and ``hp.discriminator_weight_clip`` (0: off) are opt-in switches
+    ``hp.gan_objective`` ("bce", the default; "ls", "hinge", "wgan"; the f-GAN divergences "kl", "rkl", "js") and ``hp.discriminator_weight_clip`` (0: off) are opt-in switches
     beyond the reference, read with getattr; the discriminator then has ``last_sigmoid=False`` and the spoofing rate compares against the
-    objective's threshold.  The curriculum formula stays as written: under "hinge" / "wgan" ``E_adv`` can be <= 0, and the clip then
+    objective's threshold.  The curriculum formula stays as written: under "hinge" / "wgan" / "kl" / "js" ``E_adv`` can be <= 0, and the clip then
     yields 0 (a negative ratio) or 1e3 (a tiny positive one) -- ``adv_w`` is 0 or ``1e3 * w_d`` for that epoch; an ``E_adv`` of exactly
     0 raises ZeroDivisionError as it would in the reference.
 
@@ -317,7 +317,7 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     either way (``save_checkpoint``)."""
     import contextlib
     from . import _lib as L
-    from .engine import gan_objective_of, grad_penalty_of
+    from .engine import gan_objective_of, gan_objective_threshold, grad_penalty_of
     from .data import DevicePrefetcher, ResidentLoader
     from .multistream import get_static_features
     from .paramgen import unit_variance_mlpg_band, unit_variance_mlpg_matrix_cuda
@@ -349,7 +349,7 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
     # hp.device_epoch_ledger: the running sums below live in the engine's epoch ledger and are read once per phase; per batch the
     # host waits for nothing (no step scalars, no distortion sums).  Off: the sums are kept here, three waits per batch.
     ledger = bool(getattr(hp, "device_epoch_ledger", False))
-    spoof_threshold = L.GAN_OBJECTIVE_THRESHOLD[gan_objective_of(hp)]
+    spoof_threshold = gan_objective_threshold(gan_objective_of(hp))
     ledger_eng, ledger_open, ledger_metrics = None, False, ()
     grad_penalty = grad_penalty_of(hp)[0]
     ema_decay = float(getattr(hp, "generator_ema_decay", 0.0))
@@ -416,7 +416,7 @@ def train_loop(models, optimizers, dataset_loaders, w_d=0.0, mse_w=0.0, mge_w=1.
                             if hp.adversarial_streams is not None else y_hat_static
                         target = reference_discriminator(y_hat_static_ref, lengths=cpu_sorted_lengths)
                         # accumulated on the device (float64 count); read once per epoch, no per-batch host synchronisation
-                        # (the objective's own "natural" threshold: 0.5 for "bce" and "ls", 0 for "hinge" and "wgan", whose D returns z)
+                        # (the objective's own "natural" threshold: 0.5 for "bce" and "ls", 0 for "hinge", "wgan", "rkl" and "js", 1 for "kl", whose D returns z)
                         regard_fake_as_natural = regard_fake_as_natural + ((target > spoof_threshold).float() * mask).sum(dtype=torch.float64)
 
                     if ledger:

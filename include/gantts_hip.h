@@ -349,12 +349,21 @@ int gt_set_loss_normalizer_device(gt_engine* e, const double* tv_global_dev);
  *   1 ls     D = z           real 0.5 (z - 1)^2   generated, D step 0.5 z^2             generated, G step 0.5 (z - 1)^2   threshold 0.5
  *   2 hinge  D = z           real max(0, 1 - z)   generated, D step max(0, 1 + z)       generated, G step -z              threshold 0
  *   3 wgan   D = z           real -z              generated, D step z                   generated, G step -z              threshold 0
+ *   4 kl     D = z           real -z              generated, D step exp(z - 1)          generated, G step -z              threshold 1
+ *   5 rkl    D = z           real exp(-z)         generated, D step z - 1               generated, G step exp(-z)         threshold 0
+ *   6 js     D = z           real sp(-z) - ln 2   generated, D step sp(z) - ln 2        generated, G step sp(-z) - ln 2   threshold 0
+ * 4 .. 6 are the f-GAN divergences (Nowozin et al. 2016: KL, reverse KL, Jensen-Shannon): the D loss is the negative of the variational
+ * bound E_real g_f(z) - E_fake f*(g_f(z)) with the paper's output activations g_f and conjugates f*, the G step its non-saturating form
+ * (generated rows scored as real ones), the threshold g_f(z) > f'(1); sp(x) = max(x, 0) + log(1 + exp(-|x|)).  js is the logistic loss
+ * minus 2 ln 2, without eps.  exp(z - 1) and exp(-z) are NOT clamped (a clamp would change the divergence): a frame whose exponent
+ * overflows float32 (z - 1 > 88.7 under kl, z < -88.7 under rkl) gives an infinite loss term and seed gradient, which behaves like any other
+ * non-finite gradient: grad_norm is not finite and the clipped update stores NaN, as torch would (the fault word is for device time-outs).
  * The results keep their meaning: loss_real_d / loss_fake_d / loss_adv = sum(phi m) / Tv of the column, real_correct_count =
  * sum([D > threshold] m), fake_correct_count = sum([D < threshold] m).  Same launches as objective 0 (the objective is a template
  * parameter of the two head kernels); `eps` is read by objective 0 alone.  The bound discriminator must have last_sigmoid = 1 under
- * objective 0 and last_sigmoid = 0 under 1 .. 3: checked at whichever of gt_bind_model and this option comes second, and at the entry of
+ * objective 0 and last_sigmoid = 0 under 1 .. 6: checked at whichever of gt_bind_model and this option comes second, and at the entry of
  * every step that runs the discriminator, before any launch.  Any other value returns GT_ERR_INVALID.  A change drops pending
- * split-phase results and the kept dloss_d / dy_hat_static.  hinge and wgan losses can be <= 0. */
+ * split-phase results and the kept dloss_d / dy_hat_static.  hinge, wgan, kl, rkl (its generated column) and js losses can be <= 0. */
 #define GT_OPT_GAN_OBJECTIVE 21
 int gt_set_option(gt_engine* e, int option, int value);
 /* Weight clipping (WGAN): every later optimizer step of `role` clamps each updated parameter to [-c, c] inside the fused clip + update
@@ -985,14 +994,14 @@ int gt_gp_path_counts(int64_t* counts, int reset);
  *            weight gradients are wanted.
  *   scalars  host, 8 doubles or null, filled after the stream is synchronised: s_real, s_fake, n_real_ok, n_fake_ok, s_adv, tv, inv_tv
  *            as the scratch scalars hold them (what no launch wrote stays NaN), and the number of partials (workgroups of the pass).
- *   objective  GT_OPT_GAN_OBJECTIVE id (0 .. 3): Dout, the sums and the seed gradient are that objective's; same kernel form, same slot of
+ *   objective  GT_OPT_GAN_OBJECTIVE id (0 .. 6): Dout, the sums and the seed gradient are that objective's; same kernel form, same slot of
  *            gt_head_path_counts
  * The partial buffers are scratch of the call, filled with NaN first.  A malformed case returns GT_ERR_INVALID before any launch. */
 typedef struct gt_d_head_case {
   int32_t mode, K, ldh, h_ld;
   int32_t has_act, want_grad, want_w, defer_scalars;
   int32_t accumulate, unit_tv, has_tv, lddh;
-  int32_t lddhb, objective;    /* GT_OPT_GAN_OBJECTIVE id of the pass, 0 .. 3 (formerly padding: a zero-initialised case is objective 0) */
+  int32_t lddhb, objective;    /* GT_OPT_GAN_OBJECTIVE id of the pass, 0 .. 6 (formerly padding: a zero-initialised case is objective 0) */
   float eps, tv;
   int64_t rows, n_real, n_mask, lddhbt;
   gt_drop_site drop;
